@@ -9,13 +9,21 @@ A step = one pass of the hot path over one synthetic batch resident in HBM: forw
 fused AdamW update, bf16 storage / fp32 accumulation (configs[1] of BASELINE.json).  Per-GPU batch is fixed as N
 grows (weak scaling, as DDP shards a global batch).  Rank 0 prints ONE JSON line.
 
-Extra legs after the timed region (rank 0):
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs DIR also writes what the last timed
+step computed (the forward's output dict, the loss, seeded samples of the updated parameters and of the step's gradients)
+as DIR/<name>.npy, float32, at most 64 MB in all: with the same arguments two builds can be compared output for output.
+
+--full adds the extra legs after the timed region (rank 0; each can still be switched off by its --no-* option):
   roofline     -- every GEMM / attention launch of two further steps is bracketed by HIP events on its launch
                   stream; `roofline` reports the dominant kernel (the bf16 MFMA "NT" GEMM): algorithmic FLOPs of
                   its launches / their summed durations vs the 2.5 PFLOP/s dense bf16 peak, plus the fused
                   cross-attention forward (north_star's kernel) at the batch it ran.
+  parity       -- the bf16 path against the full-size reference fixture (configs[1], B = 2).
   cpu_baseline -- the oracle (CPU restatement of the reference path, fp32) timed on this node's host cores on a
                   bounded sample (B = 2, fwd + bwd), N = 1 only.  A reported baseline, not the target.
+  secondary    -- configs[2] recipe and per-GPU batch 32 lines, child processes (N = 1 default run only).
+  distributed  -- (N > 1 or --rehearse-ddp) an all-reduce probe before the timed region and the exposed communication
+                  time of every timed step.
 """
 import argparse
 import json
@@ -98,6 +106,27 @@ def to_dev(batch, dev):
     return out
 
 
+DUMP_BYTES = 60 * 2 ** 20   # --dump-outputs: data of all arrays together (the limit is 64 MB, .npy headers included)
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each tensor as out_dir/<name>.npy in float32.  Every array gets an equal share of the budget; a larger tensor is
+    replaced by a fixed sample of its flattened elements (sorted indices drawn from a generator seeded by the name), so
+    that two runs with the same arguments write the same elements."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BYTES // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(t.numel(), (cap,), generator=g).unique()   # sorted
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+    log(f"wrote {len(arrays)} outputs of the last timed step to {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -110,6 +139,12 @@ def main():
     ap.add_argument("--t5", default="t5-small", help="t5-small (reference-faithful) | t5-base (BASELINE configs[2])")
     ap.add_argument("--arch", choices=["base", "large"], default="base",
                     help="large: configs[4] towers (ViT-L/16 + RoBERTa-large, 512x512; fusion stays 768 / 6 layers)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the extra legs (roofline, cross-attention forward, parity, cpu_baseline, "
+                         "secondary lines; the all-reduce probe under a process group): off by default, a plain run times the "
+                         "steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary line (configs[2]: frozen M3AE + t5-base head at per-GPU batch 64, run as a child "
@@ -130,6 +165,10 @@ def main():
                     help="single GPU only: run the N > 1 code path (one-rank RCCL group, bucketed async all-reduces from the "
                          "backward hooks, one-tile-per-workgroup NT launches) -- a rehearsal of the scaling run, not a metric")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_roofline = args.no_parity = args.no_cpu_baseline = args.no_secondary = True
 
     # stdout carries exactly ONE line, the JSON record: everything else this process (or a library in it: RCCL prints a version
     # banner to stdout when its first communicator is created) writes to fd 1 goes to stderr instead
@@ -222,6 +261,17 @@ def main():
             store.adamw_step(max_steps=max_steps, grad_scale=gs)
         return loss
 
+    # --dump-outputs: the forward's output dict of every step is kept until the next one (a captured graph replays into the
+    # dict its capture filled)
+    fwd_out, hook = {}, None
+
+    def keep_output(mod, inp, out):   # returns None: a forward hook that returns a value replaces the module's output
+        fwd_out.clear()
+        fwd_out.update(out)
+
+    if args.dump_outputs and rank == 0:
+        hook = model.register_forward_hook(keep_output)
+
     graphed, graph_note = None, "eager launches"
     want_graph = args.graph == "on"   # "auto" = off: measured on ROCm 7.2 a replay of the ~1000-node two-branch graph costs the
     # host 35 ms and serialises the two streams (44 ms/step against 34.6 eager at per-GPU batch 32, profiles/r04_hipgraph_replay_B32_measured.log)
@@ -252,7 +302,7 @@ def main():
     # data-parallel runs: what RCCL sees and what the links deliver, recorded BEFORE the timed region so that the scaling curve can
     # be read against it (DESIGN.md 7's prediction): a 20-iteration all-reduce of 64 MiB fp32 (one gradient bucket)
     dist_info = None
-    if world > 1 or args.rehearse_ddp:
+    if args.full and (world > 1 or args.rehearse_ddp):
         probe = torch.ones(16 * 2 ** 20, dtype=torch.float32, device=dev)
         for _ in range(3):
             dist.all_reduce(probe)
@@ -305,10 +355,18 @@ def main():
     value = B * world * args.steps / dt
     final_loss = loss.item()
     log(f"timed region: {ms_per_step:.2f} ms/step, {value:.1f} pairs/s")
+    if hook is not None:
+        hook.remove()
+        arrays = {f"forward.{k}": v for k, v in fwd_out.items() if isinstance(v, torch.Tensor) and v.is_floating_point()}
+        arrays.update({"step_loss": loss.detach(), "params_after_step": store.flat, "grads_of_step": store.grad})
+        dump_outputs(args.dump_outputs, arrays)
+        fwd_out.clear()
+        del arrays
 
     roofline, xattn, kern_table = None, None, None
     if dist_info is None:
-        dist_info = {"world_size_seen_by_rccl": 1, "note": "single process, no process group"}
+        dist_info = ({"world_size_seen_by_rccl": dist.get_world_size(), "note": "all-reduce probe and exposed communication: --full"}
+                     if dist.is_initialized() else {"world_size_seen_by_rccl": 1, "note": "single process, no process group"})
     if rank == 0 and not args.no_roofline:
         log("roofline leg")
         reducer.detach()

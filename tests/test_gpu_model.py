@@ -1275,15 +1275,15 @@ def test_configure_optimizers_returns_a_torch_optimizer_and_scheduler():
 
 
 def test_bench_line_contract():
-    """bench.py as the driver runs it (a child process, defaults except a smaller batch and fewer steps): exactly one JSON
+    """bench.py --full as the driver runs it (a child process, defaults except a smaller batch and fewer steps): exactly one JSON
     line with the contract's keys, the roofline object of the dominant kernel measured live, finite positive numbers."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--batch", "64", "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, timeout=600,
-                       cwd=root)
+                        "--batch", "64", "--full", "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True,
+                       timeout=600, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -1307,6 +1307,43 @@ def test_bench_line_contract():
     assert x["path"].startswith("m3ae_xattn_fwd") and x["tflop"] == round(17.922 * 64 / 1e3, 3)
     x = d["cross_attention_fwd"]
     assert x["batch"] == 64 and 0 < x["frac"] < 1
+
+
+def test_bench_plain_run_and_output_dump(tmp_path):
+    """A plain bench.py run (no --full) times the steps and nothing else: the headline keys, --steps timed steps, no extra leg.
+    --dump-outputs writes the last timed step's outputs (float32, at most 64 MB), and a second run with the same arguments
+    writes the same arrays up to the order of the fp32 atomics."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--batch", "32", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "pairs/s" and d["dtype"] == "bf16"
+        assert d["higher_is_better"] is True and d["value"] > 0 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 32 / (d["ms_per_step"] * 1e-3)) <= 1e-2 * d["value"]
+        for k in ("roofline", "cross_attention_fwd", "kernels", "cpu_baseline", "parity", "secondary"):
+            assert d[k] is None, k
+        files = sorted(os.listdir(out))
+        assert {"step_loss.npy", "params_after_step.npy", "grads_of_step.npy", "forward.vqa_logits.npy"} <= set(files), files
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 * 10 ** 6
+        arrs = {f: np.load(out / f, allow_pickle=False) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        assert arrs["forward.vqa_logits.npy"].shape == (32, 498)
+        assert abs(float(arrs["step_loss.npy"]) - d["final_loss"]) <= 1e-3 * abs(d["final_loss"]) + 1e-4
+        runs.append(arrs)
+    assert runs[0].keys() == runs[1].keys()
+    for f, a in runs[0].items():
+        b = runs[1][f]
+        assert a.shape == b.shape, f
+        assert np.linalg.norm((a - b).astype(np.float64)) <= 1e-2 * np.linalg.norm(a.astype(np.float64)) + 1e-6, f
 
 
 def test_graphed_step_equals_eager_and_draws_fresh_dropout_masks_per_replay():

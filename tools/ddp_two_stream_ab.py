@@ -51,5 +51,5 @@ elif variant == "hooks_only":     # reducer hooks and bucket bookkeeping, no pro
     R.__init__ = init
 import bench  # noqa: E402
 
-sys.argv = ["bench.py", "--no-secondary", "--no-cpu-baseline", "--no-roofline"] + ([] if variant in ("no_hooks", "pg_only", "hooks_only") else ["--rehearse-ddp"])
+sys.argv = ["bench.py", "--full", "--no-secondary", "--no-cpu-baseline", "--no-roofline"] + ([] if variant in ("no_hooks", "pg_only", "hooks_only") else ["--rehearse-ddp"])
 bench.main()

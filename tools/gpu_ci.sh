@@ -22,7 +22,7 @@ for st in "$@"; do
     ops)      run ops 900 python -m pytest tests/test_gpu_ops.py -m gpu -q ;;
     model)    run model 900 python -m pytest tests/test_gpu_model.py -m gpu -q ;;
     smoke)    run smoke 600 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)    run bench 900 python bench.py ;;
+    bench)    run bench 900 python bench.py --full ;;
     all)      run all 1100 python -m pytest tests -m gpu -q -x ;;
     *) echo "unknown stage $st" ;;
   esac

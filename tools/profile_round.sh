@@ -15,7 +15,7 @@ step() {  # name timeout cmd...
   if [ $rc -eq 124 ] || [ $rc -eq 137 ] || [ $rc -eq 134 ] || [ $rc -eq 139 ]; then exit $rc; fi
 }
 : > $out/steps.log
-step bench 600 python bench.py
+step bench 600 python bench.py --full
 grep '^{' $out/bench.log | tail -1 > $out/bench_line.json
 step stats 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o run -- python bench.py --no-cpu-baseline --no-roofline --no-secondary --no-parity --steps 5 --warmup 3
 step fetch 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/pmc -o fetch -- python bench.py --no-cpu-baseline --no-roofline --no-secondary --no-parity --steps 2 --warmup 1
