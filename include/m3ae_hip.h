@@ -30,7 +30,10 @@ extern "C" {
  *    m3ae_dropout take it as an argument: an optional DEVICE pointer to a 32-bit value the kernels fold into the mask key, so a
  *    step captured in a hipGraph (kernel arguments frozen, seeds included) draws new masks at every replay once the caller bumps
  *    that value; m3ae_adamw takes `hyper_dev` (device {lr, step size} of the step) for the same reason. */
-#define M3AE_ABI_VERSION 3
+/* 4: attention maps.  m3ae_attn_probs (the probabilities of an m3ae_attn_fwd call, recomputed from its log-sum-exp table) and
+ *    m3ae_xattn_probs_export (the probabilities a fused cross-attention call left in `probs` / `probs_drop`), both as fp32
+ *    [B][H][Lq][Lk]; no descriptor changed. */
+#define M3AE_ABI_VERSION 4
 
 enum { M3AE_F32 = 0, M3AE_BF16 = 1 };
 enum { M3AE_ACT_NONE = 0, M3AE_ACT_GELU = 1, M3AE_ACT_QUICKGELU = 2, M3AE_ACT_TANH = 3, M3AE_ACT_RELU = 4,
@@ -143,6 +146,17 @@ enum { M3AE_ATTN_LEGACY_KERNELS = 1 };
 int64_t m3ae_attn_workspace_bytes(const m3ae_attn_desc* d, int backward);
 int m3ae_attn_fwd(const m3ae_attn_desc* d, void* stream);
 int m3ae_attn_bwd(const m3ae_attn_desc* d, void* stream);
+/* The attention probabilities of the m3ae_attn_fwd call made with the same descriptor (the visualisation maps of
+ * bert_model.py:346): probs[b * p_sb + h * p_sh + q * p_sq + k] (fp32, strides in elements, p_sq >= Lk) for q < Lq, k < Lk,
+ *   = softmax_k(q.k / sqrt(dh) + key_mask[b][k])                    with dropout_p == 0,
+ *   = the same times the forward's keep mask / (1 - dropout_p)      with dropout_p > 0 (the drop(P) that multiplied V: the
+ *     same seed, salt and mask index ((b*H + h)*Lq + q) * ld(Lk) + k).
+ * Padding keys (additive -10000 mask) come out as 0 (exp underflow); padding query rows are computed like any other.
+ * bf16: read q, k, key_mask and the `lse` table the forward wrote (v, o, workspace unused), Dh = 64.  fp32: the forward's
+ * scores GEMM, row softmax and dropout run again with `probs` as their buffer, which must then be dense (p_sq = Lk,
+ * p_sh = Lq*Lk, p_sb = H*Lq*Lk).
+ * No pos_bias, no causal mask (M3AE_ERR_UNSUPPORTED).  ABI 4. */
+int m3ae_attn_probs(const m3ae_attn_desc* d, float* probs, int64_t p_sb, int64_t p_sh, int64_t p_sq, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Fused cross-attention sub-block of BertCrossLayer (north_star's kernel), bf16: BertAttention as `crossattention`
@@ -218,6 +232,12 @@ int m3ae_xattn_fwd(const m3ae_xattn_desc* d, void* stream);
  * and the per-head weight gradients as split-K fp32 atomics.  d(b_k) is exactly zero (b_k drops out of the softmax) and is
  * not touched.  Dropout masks are regenerated from the forward's seeds. */
 int m3ae_xattn_bwd(const m3ae_xattn_desc* d, void* stream);
+/* The attention probabilities a m3ae_xattn_fwd call wrote (dir 0 always; dir 1 when `probs` was passed), as fp32
+ * out[b * o_sb + h * o_sh + q * o_sq + k] for q < Lq, k < Lk: `probs` (dropped == 0) or `probs_drop` (dropped != 0, the dropped
+ * and rescaled P of a call with dropout_p > 0), with dir 0's key padding (640 columns) sliced off.  Reads d->dir, B, Lq, Lk, H and
+ * the chosen buffer only.  ABI 4. */
+int m3ae_xattn_probs_export(const m3ae_xattn_desc* d, int dropped, float* out, int64_t o_sb, int64_t o_sh, int64_t o_sq,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * LayerNorm (biased variance, eps inside the sqrt, fp32 statistics), optional fused activation on the output.

@@ -381,6 +381,77 @@ __global__ __launch_bounds__(256, (NQ == 1 && !MASK && !BIAS && !CAUSAL && !DROP
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// probabilities (m3ae_attn_probs): P[b][h][q][k] = exp2(c S + mask log2 e - lse), recomputed from the forward's log-sum-exp
+// table like the backward tiles do, times the forward's keep mask / (1 - p) under dropout: the drop(P) that multiplied V.
+// The kernel is bound by the fp32 write (577 x 577 x 4 B per (b, h)), not by the 64-deep products, so the score tile is taken
+// UNswapped, S[q][key] = Q . K^T: one accumulator register then holds keys key0 .. key0 + 31 of two query rows, and one
+// dword store per register writes two 128-B row segments -- the full-rate store shape, no shuffle.  K tiles are staged through
+// LDS as in attn_fwd_coop_kernel (4 waves x 32 query rows of one (b, head) per workgroup, images double-buffered).
+template <bool MASK, bool DROP>
+__global__ __launch_bounds__(256, 2) void attn_probs_kernel(AttnArgs a, float* __restrict__ P, int64_t p_sb, int64_t p_sh,
+                                                             int64_t p_sq) {
+    if (DROP) drop_resolve(a.drop);
+    __shared__ __attribute__((aligned(16))) char lds[2 * RIMG];
+    const int t = threadIdx.x;
+    const int lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const AttnBlock blk = attn_block();
+    const int head = blk.head;
+    const int64_t b = blk.b;
+    const int64_t q0 = ((int64_t)blk.bx * 4 + wave) * 32;
+    const bool active = q0 < a.Lq;  // wave-uniform; inactive waves still help with the cooperative loads
+
+    const int64_t qa = q0 + r < a.Lq ? q0 + r : a.Lq - 1;   // A operand row (clamped: its results are never stored)
+    const bf16_t* qp = a.q + b * a.q_sb + qa * a.q_sl + head * 64;
+    s16x8 qf[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = row_frag(qp, ks, h);
+    // accumulator register reg holds query row q0 + crow(reg, h): its -lse, and its row of P and of the dropout index space
+    const float* lrow = a.lse + (b * a.H + head) * a.lse_stride;
+    float nl[16];
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const int64_t q = q0 + crow(reg, h);
+        nl[reg] = -lrow[q < a.Lq ? q : a.Lq - 1];
+    }
+    float* prow = P + b * p_sb + head * p_sh;
+    const uint64_t drow0 = (uint64_t)((b * a.H + head) * a.Lq) * drop_ldk(a.Lk);
+    const bf16_t* kbase = a.k + b * a.k_sb + head * 64;
+    const float* mrow = MASK ? a.key_mask + b * a.Lk : nullptr;
+    const int nkt = (int)((a.Lk + 31) / 32);
+
+    s16x8 kreg = coop_load(kbase, a.k_sl, 0, a.Lk, t);
+    put_row_img(lds, kreg, t);
+    if (nkt > 1) kreg = coop_load(kbase, a.k_sl, 32, a.Lk, t);
+    coop_barrier();
+    for (int kt = 0; kt < nkt; ++kt) {
+        const bool last = kt + 1 == nkt;
+        s16x8 kreg2 = kreg;
+        if (kt + 2 < nkt) kreg2 = coop_load(kbase, a.k_sl, (int64_t)(kt + 2) * 32, a.Lk, t);
+        const char* kimg = lds + (kt & 1) * RIMG;
+        if (active) {
+            f32x16 s = zero16();
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) s = mfma32(qf[ks], get_row_frag(kimg, r, ks, h), s);  // S[q][key] = Q . K^T
+            const int64_t key = (int64_t)kt * 32 + r;
+            const bool kin = key < a.Lk;
+            const float madd = MASK ? mrow[kin ? key : a.Lk - 1] * LOG2E : 0.f;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int64_t q = q0 + crow(reg, h);
+                float p = fast_exp2(fmaf(s[reg], a.scale_log2, madd) + nl[reg]);
+                if (DROP) p = drop_keep(a.drop, drow0 + (uint64_t)q * drop_ldk(a.Lk) + (uint64_t)key) ? p * a.drop.inv_keep : 0.f;
+                if (kin && q < a.Lq) prow[q * p_sq + key] = p;
+            }
+        }
+        if (!last) put_row_img(lds + ((kt + 1) & 1) * RIMG, kreg, t);
+        kreg = kreg2;
+        coop_barrier();
+    }
+}
+
 template <bool MASK, bool BIAS, bool CAUSAL, bool DROP>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_coop_kernel(AttnArgs a) {
     if (DROP) drop_resolve(a.drop);
@@ -1173,6 +1244,41 @@ extern "C" int m3ae_attn_fwd(const m3ae_attn_desc* dp, void* stream) {
     g.B = d.v; g.b_sk = d.v_sl; g.b_sn = 1; g.b_sb1 = d.v_sb; g.b_sb2 = d.Dh;
     g.C = d.o; g.c_sm = d.o_sl; g.c_sn = 1; g.c_sb1 = d.o_sb; g.c_sb2 = d.Dh;
     return m3ae_gemm_generic(g, s);
+}
+
+extern "C" int m3ae_attn_probs(const m3ae_attn_desc* dp, float* probs, int64_t p_sb, int64_t p_sh, int64_t p_sq, void* stream) {
+    if (!dp || !dp->q || !dp->k || !probs) return M3AE_ERR_ARG;
+    const m3ae_attn_desc& d = *dp;
+    if (d.B <= 0 || d.H <= 0 || d.Lq <= 0 || d.Lk <= 0 || d.Dh <= 0) return M3AE_ERR_ARG;
+    if (p_sq < d.Lk || p_sh <= 0 || p_sb <= 0) return M3AE_ERR_ARG;
+    if (d.pos_bias || d.causal) return M3AE_ERR_UNSUPPORTED;   // BERT layers only (no T5 relative-position bias, no causal mask)
+    hipStream_t s = (hipStream_t)stream;
+    if (d.dtype == M3AE_BF16) {
+        auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
+        auto st = [](int64_t x) { return x % 8 == 0; };
+        if (d.Dh != 64 || !al(d.q) || !al(d.k) || !st(d.q_sl) || !st(d.k_sl) || !st(d.q_sb) || !st(d.k_sb) || !d.lse ||
+            d.lse_stride < d.Lq || d.lse_stride % 32 != 0)
+            return M3AE_ERR_UNSUPPORTED;
+        if (d.H > 65535 || d.B > 65535) return M3AE_ERR_UNSUPPORTED;
+        AttnArgs a = to_args(d);
+        dim3 grid((unsigned)cdiv(d.Lq, 128), (unsigned)d.H, (unsigned)d.B);
+        if (a.key_mask) {
+            if (a.has_drop) hipLaunchKernelGGL((attn_probs_kernel<true, true>), grid, dim3(256), 0, s, a, probs, p_sb, p_sh, p_sq);
+            else hipLaunchKernelGGL((attn_probs_kernel<true, false>), grid, dim3(256), 0, s, a, probs, p_sb, p_sh, p_sq);
+        } else {
+            if (a.has_drop) hipLaunchKernelGGL((attn_probs_kernel<false, true>), grid, dim3(256), 0, s, a, probs, p_sb, p_sh, p_sq);
+            else hipLaunchKernelGGL((attn_probs_kernel<false, false>), grid, dim3(256), 0, s, a, probs, p_sb, p_sh, p_sq);
+        }
+        return hip_launch_status();
+    }
+    if (d.dtype != M3AE_F32) return M3AE_ERR_UNSUPPORTED;
+    // parity mode: the forward's scores GEMM, row softmax and dropout run once more, straight into a dense [B][H][Lq][Lk] output
+    if (p_sq != d.Lk || p_sh != d.Lq * d.Lk || p_sb != d.H * d.Lq * d.Lk) return M3AE_ERR_UNSUPPORTED;
+    int rc = attn_f32_scores(d, probs, s);
+    if (rc) return rc;
+    if (d.dropout_p > 0.f)
+        return m3ae_dropout(probs, probs, nullptr, d.B * d.H * d.Lq, d.Lk, d.dropout_p, d.dropout_seed, d.dropout_salt, M3AE_F32, stream);
+    return 0;
 }
 
 extern "C" int m3ae_attn_bwd(const m3ae_attn_desc* dp, void* stream) {

@@ -1462,3 +1462,42 @@ extern "C" int m3ae_xattn_bwd(const m3ae_xattn_desc* dp, void* stream) {
     }
     return 0;
 }
+
+namespace {
+// out[b][h][q][k] = P[b*s_b + h*s_h + q*s_q + k] in fp32: one wave per output row (b, h, q), its lanes along the row; the row's
+// indices are decomposed once per wave, in scalar registers
+__global__ __launch_bounds__(256) void xattn_probs_export_kernel(const bf16_t* __restrict__ src, int64_t s_b, int64_t s_h,
+                                                                  int64_t s_q, float* __restrict__ out, int64_t o_sb, int64_t o_sh,
+                                                                  int64_t o_sq, int64_t H, int64_t Lq, int64_t Lk, int64_t rows) {
+    const int lane = threadIdx.x & 63;
+    const int64_t row = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (row >= rows) return;
+    const int64_t q = row % Lq, bh = row / Lq;
+    const int64_t h = bh % H, b = bh / H;
+    const bf16_t* sp = src + b * s_b + h * s_h + q * s_q;
+    float* op = out + b * o_sb + h * o_sh + q * o_sq;
+    for (int64_t k = lane; k < Lk; k += 64) op[k] = bf2f(sp[k]);
+}
+}  // namespace
+
+extern "C" int m3ae_xattn_probs_export(const m3ae_xattn_desc* d, int dropped, float* out, int64_t o_sb, int64_t o_sh, int64_t o_sq,
+                                       void* stream) {
+    if (!d || !out) return M3AE_ERR_ARG;
+    const void* src = dropped ? d->probs_drop : d->probs;
+    if (!src || d->B <= 0 || d->H <= 0 || d->Lq <= 0 || d->Lk <= 0) return M3AE_ERR_ARG;
+    if (o_sq < d->Lk || o_sh <= 0 || o_sb <= 0) return M3AE_ERR_ARG;
+    const int64_t H = d->H, Lq = d->Lq, Lk = d->Lk;
+    int64_t s_b, s_h, s_q;
+    if (d->dir == 0) {            // [B][Lq*H rows r = q*H + h][640 key columns, zero padding beyond Lk]
+        if (Lk > 640) return M3AE_ERR_UNSUPPORTED;
+        s_h = 640; s_q = H * 640; s_b = Lq * H * 640;
+    } else if (d->dir == 1) {     // [B][Lq][H*Lk columns n = h*Lk + j]
+        s_h = Lk; s_q = H * Lk; s_b = Lq * H * Lk;
+    } else {
+        return M3AE_ERR_ARG;
+    }
+    const int64_t rows = d->B * H * Lq;
+    hipLaunchKernelGGL(xattn_probs_export_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)src, s_b, s_h, s_q, out, o_sb, o_sh, o_sq, H, Lq, Lk, rows);
+    return hip_launch_status();
+}

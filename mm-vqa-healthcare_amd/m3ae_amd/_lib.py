@@ -59,7 +59,7 @@ class XattnDesc(C.Structure):
 GEMM_NO_PERSISTENT = 1                            # m3ae_gemm_desc.launch_flags
 ATTN_LEGACY_KERNELS = 1                           # m3ae_attn_desc.launch_flags
 XATTN_NO_PERSISTENT, XATTN_LEGACY_CHAIN = 1, 2    # m3ae_xattn_desc.launch_flags
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 
 _SIGS = {
@@ -70,11 +70,13 @@ _SIGS = {
     "m3ae_attn_workspace_bytes": (i64, [C.POINTER(AttnDesc), C.c_int]),
     "m3ae_attn_fwd": (C.c_int, [C.POINTER(AttnDesc), vp]),
     "m3ae_attn_bwd": (C.c_int, [C.POINTER(AttnDesc), vp]),
+    "m3ae_attn_probs": (C.c_int, [C.POINTER(AttnDesc), vp, i64, i64, i64, vp]),
     "m3ae_xattn_supported": (C.c_int, [C.POINTER(XattnDesc)]),
     "m3ae_xattn_bwd_supported": (C.c_int, [C.POINTER(XattnDesc)]),
     "m3ae_xattn_probs_ld": (i64, [C.POINTER(XattnDesc)]),
     "m3ae_xattn_fwd": (C.c_int, [C.POINTER(XattnDesc), vp]),
     "m3ae_xattn_bwd": (C.c_int, [C.POINTER(XattnDesc), vp]),
+    "m3ae_xattn_probs_export": (C.c_int, [C.POINTER(XattnDesc), C.c_int, vp, i64, i64, i64, vp]),
     "m3ae_layernorm_fwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, f32, C.c_int, C.c_int, C.c_int, vp]),
     "m3ae_layernorm_bwd_blocks": (i64, [i64]),
     "m3ae_layernorm_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, C.c_int, C.c_int, C.c_int, vp]),

@@ -4,8 +4,10 @@ m3ae/modules/language_encoders/bert_model.py:211-546 (and HF RobertaLayer, whose
 Each block is three fused pieces instead of the reference's ~20 ATen calls:
   packed Q|K|V (or Q and K|V) projection GEMM -> flash attention -> output GEMM with the residual add in its
   epilogue -> LayerNorm;   FFN = GEMM(+bias+erf-GELU, pre-activation kept) -> GEMM(+bias+residual) -> LayerNorm.
-Attention probabilities are never materialised (the reference hard-wires output_attentions=True,
-m3ae_module.py:276-277).  Dropout: see DESIGN.md (parity runs are eval-mode).
+Attention probabilities are not materialised on the default path (the reference hard-wires output_attentions=True,
+m3ae_module.py:276-277, and drops them unless infer was asked for them).  BertCrossLayer(output_attentions=True)
+recomputes them afterwards in their own kernels (ops.attn_probs / ops.xattn_probs).  Dropout: see DESIGN.md (parity runs are
+eval-mode).
 """
 from types import SimpleNamespace as NS
 
@@ -147,11 +149,16 @@ class BertCrossLayer(nn.Module):
         self.output = BertOutput(hidden, inter, eps)
         self._bp = None
 
-    def forward(self, hidden_states, encoder_hidden_states, attention_mask=None, encoder_attention_mask=None):
+    def forward(self, hidden_states, encoder_hidden_states, attention_mask=None, encoder_attention_mask=None,
+                output_attentions=False):
+        """Returns the layer output; with output_attentions the reference's tuple (output, self-attention probabilities
+        [B, H, L, L], cross-attention probabilities [B, H, L, Lo]) (bert_model.py:457-498): fp32, contiguous, detached (the
+        reference's gradient hook on them is disabled, :328); in training mode the dropped P the layer used (:334)."""
         if self._bp is None:
             self._bp = NS(attn=self.attention.block_params(), cross=self.crossattention.block_params(),
                           ffn=_ffn_params(self))
             self._anchors = tuple(self.parameters())
+        self._bp.want_probs = self._bp.cross.want_probs = bool(output_attentions)
         self._bp.pdrop = self.drop_rate if self.training else 0.0
         # forward-only calls always take the fused cross-attention sub-block; training takes it with its fused backward
         self._bp.fused_cross = (not torch.is_grad_enabled()) or (ops.XATTN_TRAIN != "off" and

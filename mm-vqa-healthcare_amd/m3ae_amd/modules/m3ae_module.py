@@ -8,7 +8,8 @@ runs in hand-written gfx950 kernels (libm3ae_hip.so) -- there is no PyTorch-op f
 
 Differences that are deliberate (DESIGN.md): weights are never downloaded (architecture comes from the config);
 `finalize(device)` moves the parameters into the flat MI355X layout (ParamStore) and must be called before the
-first forward; attention probabilities are not materialised (`output_attentions` is rejected); dropout
+first forward; attention probabilities are not materialised unless `infer(..., output_attentions=True)` asks for the
+fusion layers' maps (fp32 [B, H, Lq, Lk], detached: the reference's gradient hook on them is disabled); dropout
 (`module.training`, RoBERTa p = 0.1, fusion layers p = `drop_rate`) uses the library's counter-hash masks fused into
 the kernels (seeded by `ops.set_dropout_seed`), not torch's Philox stream.
 """
@@ -178,7 +179,7 @@ class M3AETransformerSS(_Base):
                 warn_off(False)
         return self._side_stream
 
-    def _fusion_two_streams(self, text_tower, v, mt, mv, mask_image, ret, main, side, ev_inputs):
+    def _fusion_two_streams(self, text_tower, v, mt, mv, mask_image, ret, main, side, ev_inputs, attns=None):
         """The text tower and the text half of every fusion layer on a second HIP stream.  The towers are independent until the
         fusion layers and a fusion layer's two halves read only the PREVIOUS layer's outputs, so the short text-side kernels
         (B*32 rows: half-empty grids) fill the tail rounds of the image-side launches instead of running alone.  Events order
@@ -204,15 +205,23 @@ class M3AETransformerSS(_Base):
             side.wait_event(ev_y)
             y.record_stream(side)
             with torch.cuda.stream(side):
-                x1 = text_layer(xa, yb, mt, mv)
+                x1 = text_layer(xa, yb, mt, mv, output_attentions=attns is not None)
                 ev_x1 = side.record_event()
             main.wait_event(ev_x)
             x.record_stream(main)
-            y1 = image_layer(ya, xb, mv, mt)
+            y1 = image_layer(ya, xb, mv, mt, output_attentions=attns is not None)
+            if attns is not None:   # (the layers' reference-shaped tuples: output, self-attention map, cross-attention map)
+                (x1, *tmaps), (y1, *imaps) = x1, y1
+                attns["text2image_attns"].append(tuple(tmaps))
+                attns["image2text_attns"].append(tuple(imaps))
             ev_y = main.record_event()
             x, y, ev_x = x1, y1, ev_x1
         main.wait_event(ev_x)
         x.record_stream(main)
+        if attns is not None:   # the text maps were written on the side stream: ordered before ev_x, handed to the caller's stream
+            for p in attns["text2image_attns"]:
+                for t in p:
+                    t.record_stream(main)
         if torch.is_grad_enabled():
             # whichever of the two runs in backward queues the end-of-backward join: when loss.backward() returns, the caller's
             # stream has waited for the side stream (the weight gradients land in the flat buffer as side effects of the nodes,
@@ -243,8 +252,6 @@ class M3AETransformerSS(_Base):
         """m3ae_module.py:203-312."""
         if self.store is None:
             raise RuntimeError("call finalize(device) before the first forward")
-        if output_attentions:
-            raise NotImplementedError("attention probabilities are never materialised on this path")
         ret = dict()
         if img is None:
             img_key = f"image_{image_token_type_idx - 1}" if f"image_{image_token_type_idx - 1}" in batch else "image"
@@ -291,6 +298,8 @@ class M3AETransformerSS(_Base):
             return ops.linear(t, self.multi_modal_language_proj.weight, self.multi_modal_language_proj.bias,
                               extra_bias=type_emb[0])
 
+        # m3ae_module.py:266,280-283: per fusion layer the (self, cross) attention maps of each direction
+        attns = {"text2image_attns": [], "image2text_attns": []} if output_attentions else None
         if side is None:
             t = text_tower()
             # == Multi-Modal Fusion (m3ae_module.py:266-285): both streams read the PRE-update x, y ==
@@ -300,11 +309,15 @@ class M3AETransformerSS(_Base):
                 if mask_image and self.hparams.config["mim_layer"] == layer_idx:
                     ret[f"multi_modal_text_feats_{layer_idx}"], ret[f"multi_modal_image_feats_{layer_idx}"] = x, y
                 (xa, xb), (ya, yb) = ops.fork2(x), ops.fork2(y)
-                x1 = text_layer(xa, yb, mt, mv)
-                y1 = image_layer(ya, xb, mv, mt)
+                x1 = text_layer(xa, yb, mt, mv, output_attentions=output_attentions)
+                y1 = image_layer(ya, xb, mv, mt, output_attentions=output_attentions)
+                if output_attentions:
+                    (x1, *tmaps), (y1, *imaps) = x1, y1
+                    attns["text2image_attns"].append(tuple(tmaps))
+                    attns["image2text_attns"].append(tuple(imaps))
                 x, y = x1, y1
         else:
-            x, y = self._fusion_two_streams(text_tower, v, mt, mv, mask_image, ret, main, side, ev_inputs)
+            x, y = self._fusion_two_streams(text_tower, v, mt, mv, mask_image, ret, main, side, ev_inputs, attns)
         # == Output (m3ae_module.py:287-297) ==
         cls_t = self.multi_modal_language_pooler(x)
         cls_v = self.multi_modal_vision_pooler(y)
@@ -322,7 +335,7 @@ class M3AETransformerSS(_Base):
         })
         if mask_image:  # only MIM needs it (the reference recomputes it on every call, m3ae_module.py:301)
             ret["patched_images"] = self.patchify(img)
-        ret["attentions"] = None
+        ret["attentions"] = attns
         return ret
 
     def vqa_head_forward(self, cls):

@@ -612,6 +612,30 @@ def attn_backward(q, k, v, o, lse, do, dq, dk, dv, heads, key_mask=None, pos_bia
     del ws, delta
 
 
+def attn_probs(q, k, lse, heads, key_mask=None, scale=None, dropout=None):
+    """The attention probabilities of the attn_forward call that returned `lse` for these q / k (same heads, mask, scale and
+    dropout = (p, seed)): fp32 [B, H, Lq, Lk], contiguous (m3ae_attn_probs).  Under dropout: the dropped and rescaled P that
+    multiplied V (bert_model.py:334).  A fresh tensor outside autograd (the reference's hook on the maps is disabled, :328)."""
+    _need_cuda(q)
+    B, Lq, D = q.shape
+    Lk = k.shape[1]
+    Dh = D // heads
+    if q.dtype == torch.bfloat16 and Dh != 64:   # attn_forward's fp32 detour: its softmax is recomputed in fp32
+        return attn_probs(q.float(), k.float(), None, heads, key_mask, scale, dropout)
+    scale = (1.0 / math.sqrt(Dh)) if scale is None else scale
+    out = torch.empty((B, heads, Lq, Lk), dtype=torch.float32, device=q.device)
+    lse_stride = lse.shape[-1] if lse is not None else 0
+    d = _attn_desc(B, heads, Lq, Lk, Dh, q, k, k, q, key_mask, None, scale, False, lse, lse_stride, _dt(q))
+    if dropout is not None and dropout[0] > 0:
+        d.dropout_p, d.dropout_seed = dropout
+        d.dropout_salt = _salt()
+    e0 = _prof_begin()
+    check(_lib.lib().m3ae_attn_probs(C.byref(d), C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1), out.stride(2),
+                                     _stream()), "m3ae_attn_probs")
+    _prof_end(e0, "attn_probs", (B, heads, Lq, Lk, Dh))
+    return out
+
+
 class SelfAttnFn(torch.autograd.Function):
     """softmax(QK^T / sqrt(dh) + mask) V on a packed [B, L, 3D] projection (rows Q | K | V)."""
 
@@ -732,9 +756,10 @@ def xattn_supported(h2, L, other2, Lo, mask, P, backward=False):
     return bool(_lib.lib().m3ae_xattn_bwd_supported(C.byref(d)))
 
 
-def xattn_fwd(h2, B, L, other2, Lo, mask, P, pdrop=0.0, need_bwd=True):
+def xattn_fwd(h2, B, L, other2, Lo, mask, P, pdrop=0.0, need_bwd=True, want_probs=False):
     """BertAttention as crossattention (bert_model.py:480-488) through the fused kernels.  Returns (out, saved).
-    need_bwd=False (forward-only call): the image-query direction keeps scores and probabilities on chip."""
+    need_bwd=False (forward-only call): the image-query direction keeps scores and probabilities on chip, unless want_probs
+    (attention maps asked for: the same launch copies them out of LDS, xattn_probs reads them)."""
     _need_cuda(h2)
     dev, D, H = h2.device, h2.shape[1], P.heads
     seeds = (next_dropout_seed(), next_dropout_seed()) if pdrop > 0 else None
@@ -756,7 +781,7 @@ def xattn_fwd(h2, B, L, other2, Lo, mask, P, pdrop=0.0, need_bwd=True):
         t["proj"] = e(B * Lo, 2 * D)
         t["prime"] = e(2, B, R, D)
         t["colbias"] = e(B, R, dt=torch.float32)
-        if need_bwd or XATTN_LEGACY_CHAIN:
+        if need_bwd or XATTN_LEGACY_CHAIN or want_probs:
             t["probs"] = e(B, L, R)
             if pdrop > 0:
                 t["probs_drop"] = e(B, L, R)
@@ -770,6 +795,30 @@ def xattn_fwd(h2, B, L, other2, Lo, mask, P, pdrop=0.0, need_bwd=True):
     check(_lib.lib().m3ae_xattn_fwd(C.byref(d), _stream()), "m3ae_xattn_fwd")
     _prof_end(e0, "xattn_fwd", (B, H, L, Lo, D // H))
     return t["out"], ("xattn", h2, other2, mask, t, seeds, pdrop)
+
+
+def xattn_probs(saved):
+    """The attention probabilities of an xattn_fwd call from its saved buffers: fp32 [B, H, Lq, Lk], contiguous
+    (m3ae_xattn_probs_export: padding keys sliced off; under dropout the dropped and rescaled P the call used)."""
+    _, h2, other2, mask, t, seeds, pdrop = saved
+    if "probs" not in t:
+        raise _lib.M3AEHipError("this fused cross-attention call kept its probabilities on chip (xattn_fwd(want_probs=True))")
+    d = XattnDesc()
+    prime = t["prime"]
+    dir1 = prime.dim() == 4                  # dir 1 keeps K' and V' ([2, B, R, D]), dir 0 Q' ([B, R, D])
+    B = prime.shape[1] if dir1 else prime.shape[0]
+    L, Lo = h2.shape[0] // B, other2.shape[0] // B
+    d.dir = 1 if dir1 else 0
+    d.B, d.Lq, d.Lk, d.D = B, L, Lo, h2.shape[1]
+    d.H = prime.shape[-2] // min(L, Lo)
+    d.probs = t["probs"].data_ptr()
+    dropped = pdrop > 0
+    if dropped:
+        d.probs_drop = t["probs_drop"].data_ptr()
+    out = torch.empty((B, d.H, L, Lo), dtype=torch.float32, device=h2.device)
+    check(_lib.lib().m3ae_xattn_probs_export(C.byref(d), int(dropped), C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1),
+                                             out.stride(2), _stream()), "m3ae_xattn_probs_export")
+    return out
 
 
 def xattn_bwd(dy, saved, B, L, Lo, P, need_dother=True):
@@ -815,13 +864,14 @@ def xattn_bwd(dy, saved, B, L, Lo, P, need_dother=True):
 
 def _attn_sub_fwd(h2, B, L, other2, Lo, mask, P, pdrop=0.0, fused_cross=False):
     """BertAttention (bert_model.py:367-413) on 2-D token-major activations. Returns (y, saved).
-    pdrop > 0 (training): attention-probability dropout (:334) and hidden dropout on the output dense (:362)."""
+    pdrop > 0 (training): attention-probability dropout (:334) and hidden dropout on the output dense (:362).
+    P.want_probs: the attention map will be asked of `saved` (_attn_sub_probs): a forward-only fused call copies it out."""
     heads = P.heads
     D = h2.shape[1]
     if other2 is not None and fused_cross:
         need_bwd = getattr(P, "need_bwd", True)
         if xattn_supported(h2, L, other2, Lo, mask, P, backward=need_bwd):
-            return xattn_fwd(h2, B, L, other2, Lo, mask, P, pdrop, need_bwd=need_bwd)
+            return xattn_fwd(h2, B, L, other2, Lo, mask, P, pdrop, need_bwd=need_bwd, want_probs=getattr(P, "want_probs", False))
     da = (pdrop, next_dropout_seed()) if pdrop > 0 else None
     dh = (pdrop, next_dropout_seed()) if pdrop > 0 else None
     if other2 is None:
@@ -839,6 +889,20 @@ def _attn_sub_fwd(h2, B, L, other2, Lo, mask, P, pdrop=0.0, fused_cross=False):
     s, _ = mm_nt(o2, D, B * L, compute_weight(P.w_o), bias=_bdata(P.b_o), residual=h2, dropout=dh)
     y, mean, rstd = ln_fwd_raw(s, P.ln)
     return y, (h2, other2, proj, o, lse, s, mean, rstd, mask, da, dh)
+
+
+def _attn_sub_probs(saved, B, L, Lo, P):
+    """The attention map of an _attn_sub_fwd call (fp32 [B, H, L, Lo]) from what it saved: the fused cross-attention's buffers,
+    or the composition's projections and log-sum-exp table."""
+    if isinstance(saved[0], str):
+        return xattn_probs(saved)
+    h2, other2, proj, o, lse, s, mean, rstd, mask, da, dh = saved
+    D = h2.shape[1]
+    if other2 is None:
+        v3 = proj[0].view(B, L, 3 * D)
+        return attn_probs(v3[..., :D], v3[..., D:2 * D], lse, P.heads, mask, dropout=da)
+    q, kv = proj
+    return attn_probs(q.view(B, L, D), kv.view(B, Lo, 2 * D)[..., :D], lse, P.heads, mask, dropout=da)
 
 
 def _attn_sub_bwd(dy, saved, B, L, Lo, P, need_dother=True):
@@ -917,10 +981,15 @@ class BertCrossLayerFn(torch.autograd.Function):
         ctx.saved = (s1, s2, s3)
         ctx.P, ctx.dims, ctx.n_anchor = P, (B, L, Lo, D), len(anchors)
         ctx.need_other = other.requires_grad
+        if getattr(P, "want_probs", False):
+            # the two attention maps (bert_model.py:346 of the self- and the cross-attention), read-only outputs
+            maps = (_attn_sub_probs(s1, B, L, L, P.attn), _attn_sub_probs(s2, B, L, Lo, P.cross))
+            ctx.mark_non_differentiable(*maps)
+            return (y.view(B, L, D),) + maps
         return y.view(B, L, D)
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, *_maps):   # (the maps, when returned, carry no gradient)
         B, L, Lo, D = ctx.dims
         s1, s2, s3 = ctx.saved
         ctx.saved = None

@@ -1,0 +1,82 @@
+"""Host side (no GPU) of the fusion-layer attention maps: the two ABI-4 entry points are declared, bound and documented, infer
+accepts output_attentions, and the reference fixture holds what the GPU tests read."""
+import inspect
+import os
+import re
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (os.path.join(ROOT, "mm-vqa-healthcare_amd"), ROOT, os.path.join(ROOT, "tools")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+from m3ae_amd import _lib  # noqa: E402
+from m3ae_amd.modules import M3AETransformerSS  # noqa: E402
+from m3ae_amd.modules.bert_model import BertCrossLayer  # noqa: E402
+
+ENTRIES = ("m3ae_attn_probs", "m3ae_xattn_probs_export")
+
+
+def test_attention_map_entry_points_are_declared_bound_and_in_the_stub():
+    import gen_integration_stub as gen
+    hdr = open(os.path.join(ROOT, "include", "m3ae_hip.h")).read()
+    assert int(re.search(r"#define M3AE_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 4
+    stub = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    for name in ENTRIES:
+        assert re.search(r"\bint " + name + r"\(", hdr), name
+        assert name in _lib.EXPORTS
+        assert f"lib.{name}.restype" in gen.block() and f"lib.{name}.restype" in stub
+    res, args = _lib._SIGS["m3ae_attn_probs"]
+    assert args[0]._type_ is _lib.AttnDesc and len(args) == 6
+    res, args = _lib._SIGS["m3ae_xattn_probs_export"]
+    assert args[0]._type_ is _lib.XattnDesc and len(args) == 7
+
+
+def test_infer_accepts_output_attentions():
+    src = inspect.getsource(M3AETransformerSS.infer)
+    assert "NotImplementedError" not in src
+    assert "output_attentions" in inspect.signature(M3AETransformerSS.infer).parameters
+    assert inspect.signature(BertCrossLayer.forward).parameters["output_attentions"].default is False
+
+
+def test_attention_map_fixture_layout():
+    g = np.load(os.path.join(ROOT, "tests", "golden", "attn_maps.npz"), allow_pickle=False)
+    B, H, T, I = 2, 2, 32, 17
+    shapes = {"t2i": ((T, T), (T, I)), "i2t": ((I, I), (I, T))}
+    for tag in ("t2i", "i2t"):
+        for l in range(2):
+            for kind, (lq, lk) in zip(("self", "cross"), shapes[tag]):
+                p = g[f"tiny_{tag}_{l}_{kind}"]
+                assert p.shape == (B, H, lq, lk) and p.dtype == np.float32
+                np.testing.assert_allclose(p.sum(-1), 1.0, rtol=0, atol=1e-5)
+        I = 577
+        for l in range(6):
+            for kind, (lq, lk) in zip(("self", "cross"), {"t2i": ((T, T), (T, I)), "i2t": ((I, I), (I, T))}[tag]):
+                assert g[f"full_{tag}_{l}_{kind}_cls"].shape == (2, 12, lk)
+                assert g[f"full_{tag}_{l}_{kind}_fro"].shape == (2, 12)
+        I = 17
+
+
+def test_bf16_map_bound_rejects_uniform_and_key_reversed_maps():
+    """The perf-mode check of tests/test_gpu_attn_maps.py (tests/attn_map_checks.py) must be able to fail.  It rejects a uniform
+    map and a key-reversed map in place of every full-size image-key map (the question-over-image and image-over-image maps, CLS
+    rows), and in place of every map whose reference lies farther than the bound from them; the parity-mode check (rtol 1e-4,
+    atol 1e-6) rejects both in place of every tiny map, the near-uniform layer-0 ones included."""
+    from attn_map_checks import LOG_BOUND, keys_reversed, map_errors, uniform_like, within_bf16_bound
+    g = np.load(os.path.join(ROOT, "tests", "golden", "attn_maps.npz"), allow_pickle=False)
+    for name in g.files:
+        if name.endswith("_fro"):
+            continue
+        ref = g[name]
+        assert within_bf16_bound(ref, ref)
+        for fake in (uniform_like(ref), keys_reversed(ref)):
+            far = map_errors(fake, ref)[0] > LOG_BOUND
+            image_keys = name.startswith("full_") and ("_t2i_" in name and "_cross" in name or "_i2t_" in name and "_self" in name)
+            if image_keys:
+                assert far, name
+            if far:
+                assert not within_bf16_bound(fake, ref), name
+            if name.startswith("tiny_"):
+                assert not np.allclose(fake, ref, rtol=1e-4, atol=1e-6), name

@@ -27,11 +27,27 @@ def struct_stub(cls, c_name):
            f"    _fields_ = [\n{body}]\n"
 
 
+MAP_ENTRIES = ("m3ae_attn_probs", "m3ae_xattn_probs_export")
+
+
+def _ctype_name(t):
+    if t in _NAMES:
+        return _NAMES[t]
+    if t is C.c_int:
+        return "C.c_int"
+    return f"C.POINTER({t._type_.__name__})"
+
+
 def block():
     from m3ae_amd import _lib
     out = ["```python", "import ctypes as C", f"ABI_VERSION = {_lib.ABI_VERSION}        # == lib.m3ae_abi_version()", ""]
     out.append(struct_stub(_lib.GemmDesc, "m3ae_gemm_desc"))
     out.append(struct_stub(_lib.XattnDesc, "m3ae_xattn_desc"))
+    out.append(struct_stub(_lib.AttnDesc, "m3ae_attn_desc"))
+    out.append("# attention maps (ABI 4): fp32 [B, H, Lq, Lk] out of an m3ae_attn_fwd / m3ae_xattn_fwd call")
+    for name in MAP_ENTRIES:
+        res, args = _lib._SIGS[name]
+        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
     out.append("```")
     return "\n".join(out)
 
