@@ -44,7 +44,7 @@ int m3ae_abi_version(void);
 /* sizeof(m3ae_gemm_desc), sizeof(m3ae_attn_desc), sizeof(m3ae_xattn_desc) as this library was compiled: a binding compares
  * them with its own struct definitions before the first call (a descriptor that is too short is read past its end). */
 void m3ae_desc_sizes(int64_t out3[3]);
-/* name of the kernel family the last m3ae_gemm call on this thread dispatched to ("mfma_nt", "mfma_tn", "generic") */
+/* name of the kernel family the last m3ae_gemm call on this thread dispatched to ("mfma_nt", "mfma_tn", "generic", "f32x3") */
 const char* m3ae_last_gemm_path(void);
 
 /* ------------------------------------------------------------------------------------------------------------
@@ -64,7 +64,8 @@ const char* m3ae_last_gemm_path(void);
  * (A = dY^T) that is the bias gradient, so no separate column-sum pass over dY is needed.
  * Dispatch: bf16 A,B with K-contiguous operands (a_sk == b_sk == 1) -> MFMA "NT" kernel;
  *           bf16 A,B with reduction-strided operands (a_sm == b_sn == 1), fp32 C, accumulate -> MFMA "TN" (wgrad)
- *           kernel with split-K fp32 atomics; anything else (fp32 operands, odd shapes, batched) -> generic kernel.
+ *           kernel with split-K fp32 atomics; anything else (fp32 operands, odd shapes, batched) -> generic kernel;
+ *           fp32 A, B, C with launch_flags & M3AE_GEMM_F32_X3 (and not force_generic) -> fp32x3 kernel, any layout.
  */
 typedef struct {
     int64_t M, N, K;
@@ -93,7 +94,13 @@ typedef struct {
                             * hold CUs; a persistent workgroup that finds none starts after another has walked its list) */
     const void* dropout_salt; /* NULL, or device uint32: folded into the dropout mask key at kernel entry (ABI 3, above) */
 } m3ae_gemm_desc;
-enum { M3AE_GEMM_NO_PERSISTENT = 1 };
+enum { M3AE_GEMM_NO_PERSISTENT = 1,
+       M3AE_GEMM_F32_X3 = 2   /* fp32x3 mode (ABI 4, additive): fp32 A, B and C run csrc/gemm_f32x3.hip, which splits every operand
+                               * element into bf16 hi + lo and forms a_hi b_hi + a_hi b_lo + a_lo b_hi on the bf16 MFMA with fp32
+                               * accumulation: |C - C_exact| <= 3 (2^-16 + K 2^-23) (|A||B|)_mn before the epilogue, which is
+                               * gemm_generic's.  The whole descriptor contract holds (strides, batches, every epilogue, dropout
+                               * masks, a_rowsum over the fp32 A values); m3ae_last_gemm_path() = "f32x3".  force_generic wins;
+                               * with bf16 operands or output the call returns M3AE_ERR_UNSUPPORTED. */ };
 /* Diagnostic selectors in launch_flags (0 in the product path = kernel chosen by shape): tests pin the kernel variants
  * per call to compare them bit for bit, tools time them against each other.  The library keeps no tuning state.
  *   NT variant v: 0 = 128x128 tile, 4 = 256x256 2-stage, 7 = 256x256 ping-pong, 8 = its persistent form;
@@ -142,7 +149,11 @@ typedef struct {
     const void* dropout_salt; /* as m3ae_gemm_desc.dropout_salt */
     int32_t launch_flags;     /* M3AE_ATTN_LEGACY_KERNELS: the round-3 bf16 kernels (tests compare the two generations); ABI 3 */
 } m3ae_attn_desc;
-enum { M3AE_ATTN_LEGACY_KERNELS = 1 };
+enum { M3AE_ATTN_LEGACY_KERNELS = 1,
+       M3AE_ATTN_F32_X3 = 2   /* fp32 path: every product inside m3ae_attn_fwd (scores, P V), m3ae_attn_bwd (dP, dV, dQ, dK) and
+                               * m3ae_attn_probs (the scores recompute) takes the fp32x3 GEMM (M3AE_GEMM_F32_X3); the softmax,
+                               * softmax backward, dropout and pos-bias gradient kernels are unchanged.  Ignored by the bf16
+                               * kernels.  ABI 4, additive. */ };
 int64_t m3ae_attn_workspace_bytes(const m3ae_attn_desc* d, int backward);
 int m3ae_attn_fwd(const m3ae_attn_desc* d, void* stream);
 int m3ae_attn_bwd(const m3ae_attn_desc* d, void* stream);

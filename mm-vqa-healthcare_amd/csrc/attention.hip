@@ -19,6 +19,7 @@
 #include <type_traits>
 
 int m3ae_gemm_generic(const m3ae_gemm_desc& d, hipStream_t s);
+int m3ae_gemm_f32x3(const m3ae_gemm_desc& d, hipStream_t s);
 
 namespace {
 
@@ -1160,6 +1161,11 @@ m3ae_gemm_desc bgemm(const m3ae_attn_desc& d) {
     return g;
 }
 
+// every product of the fp32 path: the generic fp32 FMA kernel, or under M3AE_ATTN_F32_X3 the split-bf16 MFMA kernel
+int attn_gemm(const m3ae_attn_desc& d, const m3ae_gemm_desc& g, hipStream_t s) {
+    return (d.launch_flags & M3AE_ATTN_F32_X3) ? m3ae_gemm_f32x3(g, s) : m3ae_gemm_generic(g, s);
+}
+
 int attn_f32_scores(const m3ae_attn_desc& d, float* S, hipStream_t s) {
     const int64_t QK = d.Lq * d.Lk;
     m3ae_gemm_desc g = bgemm(d);
@@ -1167,7 +1173,7 @@ int attn_f32_scores(const m3ae_attn_desc& d, float* S, hipStream_t s) {
     g.A = d.q; g.a_sm = d.q_sl; g.a_sk = 1; g.a_sb1 = d.q_sb; g.a_sb2 = d.Dh;
     g.B = d.k; g.b_sk = 1; g.b_sn = d.k_sl; g.b_sb1 = d.k_sb; g.b_sb2 = d.Dh;
     g.C = S; g.c_sm = d.Lk; g.c_sn = 1; g.c_sb1 = d.H * QK; g.c_sb2 = QK;
-    int rc = m3ae_gemm_generic(g, s);
+    int rc = attn_gemm(d, g, s);
     if (rc) return rc;
     const int64_t rows = d.B * d.H * d.Lq;
     hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, s, S, d.key_mask, d.pos_bias,
@@ -1243,7 +1249,7 @@ extern "C" int m3ae_attn_fwd(const m3ae_attn_desc* dp, void* stream) {
     g.A = S; g.a_sm = d.Lk; g.a_sk = 1; g.a_sb1 = d.H * QK; g.a_sb2 = QK;
     g.B = d.v; g.b_sk = d.v_sl; g.b_sn = 1; g.b_sb1 = d.v_sb; g.b_sb2 = d.Dh;
     g.C = d.o; g.c_sm = d.o_sl; g.c_sn = 1; g.c_sb1 = d.o_sb; g.c_sb2 = d.Dh;
-    return m3ae_gemm_generic(g, s);
+    return attn_gemm(d, g, s);
 }
 
 extern "C" int m3ae_attn_probs(const m3ae_attn_desc* dp, float* probs, int64_t p_sb, int64_t p_sh, int64_t p_sq, void* stream) {
@@ -1328,14 +1334,14 @@ extern "C" int m3ae_attn_bwd(const m3ae_attn_desc* dp, void* stream) {
     g.A = d.d_o; g.a_sm = d.o_sl; g.a_sk = 1; g.a_sb1 = d.o_sb; g.a_sb2 = d.Dh;
     g.B = d.v; g.b_sk = 1; g.b_sn = d.v_sl; g.b_sb1 = d.v_sb; g.b_sb2 = d.Dh;
     g.C = dS; g.c_sm = d.Lk; g.c_sn = 1; g.c_sb1 = d.H * QK; g.c_sb2 = QK;
-    if ((rc = m3ae_gemm_generic(g, s))) return rc;
+    if ((rc = attn_gemm(d, g, s))) return rc;
     // dV = P^T . dO   (before dS overwrites nothing of P)
     g = bgemm(d);
     g.M = d.Lk; g.N = d.Dh; g.K = d.Lq;
     g.A = P; g.a_sm = 1; g.a_sk = d.Lk; g.a_sb1 = d.H * QK; g.a_sb2 = QK;
     g.B = d.d_o; g.b_sk = d.o_sl; g.b_sn = 1; g.b_sb1 = d.o_sb; g.b_sb2 = d.Dh;
     g.C = d.dv; g.c_sm = d.v_sl; g.c_sn = 1; g.c_sb1 = d.v_sb; g.c_sb2 = d.Dh;
-    if ((rc = m3ae_gemm_generic(g, s))) return rc;
+    if ((rc = attn_gemm(d, g, s))) return rc;
     const int64_t rows = d.B * d.H * d.Lq;
     if (drop) {  // the softmax backward needs the un-dropped P and dP wrt it
         if ((rc = attn_f32_scores(d, P, s))) return rc;
@@ -1354,13 +1360,13 @@ extern "C" int m3ae_attn_bwd(const m3ae_attn_desc* dp, void* stream) {
     g.A = dS; g.a_sm = d.Lk; g.a_sk = 1; g.a_sb1 = d.H * QK; g.a_sb2 = QK;
     g.B = d.k; g.b_sk = d.k_sl; g.b_sn = 1; g.b_sb1 = d.k_sb; g.b_sb2 = d.Dh;
     g.C = d.dq; g.c_sm = d.q_sl; g.c_sn = 1; g.c_sb1 = d.q_sb; g.c_sb2 = d.Dh;
-    if ((rc = m3ae_gemm_generic(g, s))) return rc;
+    if ((rc = attn_gemm(d, g, s))) return rc;
     // dK = scale * dS^T . Q
     g = bgemm(d);
     g.M = d.Lk; g.N = d.Dh; g.K = d.Lq; g.alpha = d.scale;
     g.A = dS; g.a_sm = 1; g.a_sk = d.Lk; g.a_sb1 = d.H * QK; g.a_sb2 = QK;
     g.B = d.q; g.b_sk = d.q_sl; g.b_sn = 1; g.b_sb1 = d.q_sb; g.b_sb2 = d.Dh;
     g.C = d.dk; g.c_sm = d.k_sl; g.c_sn = 1; g.c_sb1 = d.k_sb; g.c_sb2 = d.Dh;
-    if ((rc = m3ae_gemm_generic(g, s))) return rc;
+    if ((rc = attn_gemm(d, g, s))) return rc;
     return hip_launch_status();
 }

@@ -239,6 +239,7 @@ static thread_local const char* g_last_path = "none";
 const char* m3ae_last_gemm_path(void) { return g_last_path; }
 
 int m3ae_gemm_generic(const m3ae_gemm_desc& d, hipStream_t s);
+int m3ae_gemm_f32x3(const m3ae_gemm_desc& d, hipStream_t s);
 
 static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
@@ -1024,6 +1025,11 @@ extern "C" int m3ae_gemm(const m3ae_gemm_desc* dp, void* stream) {
     const m3ae_gemm_desc& d = *dp;
     if (d.M <= 0 || d.N <= 0 || d.K <= 0 || d.batch1 <= 0 || d.batch2 <= 0) return M3AE_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
+    if ((d.launch_flags & M3AE_GEMM_F32_X3) && !d.force_generic) {   // fp32x3 mode (csrc/gemm_f32x3.hip): fp32 operands only
+        if (d.dtype_a != M3AE_F32 || d.dtype_b != M3AE_F32 || d.dtype_c != M3AE_F32) return M3AE_ERR_UNSUPPORTED;
+        g_last_path = "f32x3";
+        return m3ae_gemm_f32x3(d, s);
+    }
     const bool bf = d.dtype_a == M3AE_BF16 && d.dtype_b == M3AE_BF16;
     const bool single = d.batch1 == 1 && d.batch2 == 1;
     if (bf && single && !d.force_generic && d.c_sn == 1) {

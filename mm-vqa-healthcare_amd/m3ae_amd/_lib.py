@@ -56,8 +56,8 @@ class XattnDesc(C.Structure):
     ]
 
 
-GEMM_NO_PERSISTENT = 1                            # m3ae_gemm_desc.launch_flags
-ATTN_LEGACY_KERNELS = 1                           # m3ae_attn_desc.launch_flags
+GEMM_NO_PERSISTENT, GEMM_F32_X3 = 1, 2           # m3ae_gemm_desc.launch_flags
+ATTN_LEGACY_KERNELS, ATTN_F32_X3 = 1, 2           # m3ae_attn_desc.launch_flags
 XATTN_NO_PERSISTENT, XATTN_LEGACY_CHAIN = 1, 2    # m3ae_xattn_desc.launch_flags
 ABI_VERSION = 4
 

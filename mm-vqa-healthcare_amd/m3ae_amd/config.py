@@ -40,7 +40,7 @@ DEFAULTS = dict(
     num_gpus=1, num_nodes=1, load_path="", decoder_load_path="", load_path_t5="", num_workers=8, precision=32,
     gpu_device_number=0, label_column_name="",
     # build extensions (not in the reference): compute mode of the HIP path
-    compute_dtype="bf16",  # "bf16" (perf mode) | "fp32" (parity mode)
+    compute_dtype="bf16",  # "bf16" (perf mode) | "fp32" (parity mode) | "fp32x3" (parity mode's storage, GEMMs on the split-bf16 MFMA)
 )
 
 NAMED = {

@@ -137,7 +137,7 @@ class PositionalEncoding(nn.Module):
         self.register_buffer("pe", pe.unsqueeze(0))
 
 
-class _DecoderEmbedFn(torch.autograd.Function):
+class _DecoderEmbedFn(ops.Function):
     """2 * embedding[ids] + pe (m3ae_decoder.py:125-127), gradient 2 * d_out scatter-added into the table."""
 
     @staticmethod
@@ -180,6 +180,7 @@ class Decoder(nn.Module):
         self.final_linear = nn.Linear(d_model, target_vocab_size)
         self.p_drop = dropout   # nn.Dropout on the (doubled) embedding (:128)
         self.head_dtype = torch.float32   # DecoderModel.finalize: the configured compute dtype
+        self.f32x3 = False                # DecoderModel.finalize: fp32x3 mode (ops.model_mode of the entry points below)
 
     def weight_units(self):
         """GEMM weights that need a transposed bf16 copy for dgrad (perf mode): the live layer's and the vocabulary
@@ -190,6 +191,7 @@ class Decoder(nn.Module):
         return [l.mha1.in_proj_weight, l.mha1.out_proj.weight, l.mha2.in_proj_weight, l.mha2.out_proj.weight,
                 l.ffn[0].weight, l.ffn[2].weight, self.final_linear.weight]
 
+    @ops.model_mode
     def forward(self, padded_targets, padding_mask, cross_attn_feats):
         """padded_targets int64 [B, T]; padding_mask bool [B, T] (True = token) or None; features [B, Le, D]."""
         B, T = padded_targets.shape
@@ -206,6 +208,7 @@ class Decoder(nn.Module):
         return ops.vocab_linear(x, self.final_linear.weight, self.final_linear.bias)
 
     @torch.no_grad()
+    @ops.model_mode
     def step_logits(self, last_ids, pos, enc_kv, cache):
         """Logits of the next token from the NEW token alone (last_ids [B, 1] at position `pos`): the prefix's keys / values
         come from `cache`, the encoder side from `enc_kv`; equal to forward(prefix)[:, -1] (eval mode)."""
@@ -217,6 +220,7 @@ class Decoder(nn.Module):
         return ops.vocab_linear(x, self.final_linear.weight, self.final_linear.bias)[:, -1]
 
     @torch.no_grad()
+    @ops.model_mode
     def search_path(self, cross_attn_feats, cls_id=101, sep_id=102, eos_id=None, pad_id=0, use_cache=True):
         """m3ae_decoder.py:141-182: greedy decoding.  The reference re-runs the whole prefix every step; here a step is one
         decoder row: the prefix's self-attention keys / values are cached, the encoder-side keys / values are projected
@@ -281,7 +285,8 @@ class DecoderModel(_Base):
     def finalize(self, device="cuda", compute_dtype=None):
         cfg = self.m3ae.hparams.config
         if compute_dtype is not None:
-            self.m3ae._dtype = compute_dtype
+            self.m3ae.set_compute_dtype(compute_dtype)
+        self.decoder.f32x3 = self.m3ae.f32x3
         for _, b in list(self.named_buffers()):
             b.data = b.data.to(device)
         # layers 0 .. n-2 never receive a gradient in the reference (torch's AdamW skips them: no update, no weight
@@ -293,6 +298,11 @@ class DecoderModel(_Base):
         self.m3ae.store = self.store
         return self
 
+    @property
+    def f32x3(self):
+        return self.m3ae.f32x3
+
+    @ops.model_mode
     def features(self, batch):
         """m3ae_decoder.py:296-314: the encoder-side sequence the decoder cross-attends to."""
         cfg = self.m3ae.hparams.config
@@ -314,6 +324,7 @@ class DecoderModel(_Base):
         return self.tokenizer(flat, padding=True, truncation=True, return_tensors="pt",
                               max_length=self.max_answer_length).input_ids.to(batch["text_ids"].device)
 
+    @ops.model_mode
     def forward(self, batch, test=False):
         if self.store is None:
             raise RuntimeError("call finalize(device) before the first forward")

@@ -25,7 +25,7 @@ from . import objectives, prediction_heads
 from .bert_model import BertCrossLayer, RobertaModel
 from .clip_model import adapt_position_encoding, build_model
 
-class _JoinAtEndFn(torch.autograd.Function):
+class _JoinAtEndFn(ops.Function):
     """Identity.  Its backward (among the first nodes of a backward pass) queues `main.wait_stream(side)` to run when the pass ends."""
 
     @staticmethod
@@ -130,6 +130,20 @@ class M3AETransformerSS(_Base):
             self._load(cfg["load_path"])
         self.store = None
         self._dtype = torch.bfloat16 if cfg.get("compute_dtype", "bf16") == "bf16" else torch.float32
+        self._x3 = cfg.get("compute_dtype") == "fp32x3"   # fp32x3 mode: fp32 storage, fp32 GEMMs on the split-bf16 MFMA kernel
+
+    @property
+    def f32x3(self):
+        """True in fp32x3 mode (compute_dtype="fp32x3"): parity mode's storage, every GEMM and attention product on the
+        fp32-accurate MFMA kernel (ops.f32x3_mode)."""
+        return self._x3 and self._dtype == torch.float32
+
+    def set_compute_dtype(self, compute_dtype):
+        """"bf16" | "fp32" | "fp32x3", or a torch dtype (which keeps the configured fp32x3 choice for float32)."""
+        if isinstance(compute_dtype, str):
+            self._x3 = compute_dtype == "fp32x3"
+            compute_dtype = torch.bfloat16 if compute_dtype == "bf16" else torch.float32
+        self._dtype = compute_dtype
 
     # ------------------------------------------------------------------------------------------------------
     def _load(self, path):
@@ -158,7 +172,7 @@ class M3AETransformerSS(_Base):
     def finalize(self, device="cuda", compute_dtype=None, frozen=()):
         """Move parameters into the flat MI355X layout (ParamStore).  Call once, after loading weights."""
         if compute_dtype is not None:
-            self._dtype = compute_dtype
+            self.set_compute_dtype(compute_dtype)
         for b_name, b in list(self.named_buffers()):
             b.data = b.data.to(device)
         self.store = ParamStore(self, self.hparams.config, device, self._dtype, self.weight_units, frozen=frozen)
@@ -247,6 +261,7 @@ class M3AETransformerSS(_Base):
         """m3ae_module.py:185-192 (`m3ae_mim_targets` without the standardisation)."""
         return ops.mim_targets(imgs, self.hparams.config["patch_size"], False)
 
+    @ops.model_mode
     def infer(self, batch, mask_text=False, mask_image=False, image_token_type_idx=1, img=None,
               output_attentions=False, unimodal=False):
         """m3ae_module.py:203-312."""
@@ -347,6 +362,7 @@ class M3AETransformerSS(_Base):
         # (6 launches per step at 3 TFLOP/s); the zero-padded operand copies of ops.vocab_linear keep them on the MFMA kernels
         return ops.vocab_linear(h, self.vqa_head[3].weight, self.vqa_head[3].bias)
 
+    @ops.model_mode
     def forward(self, batch, test=False):
         """m3ae_module.py:314-345."""
         ret = dict()

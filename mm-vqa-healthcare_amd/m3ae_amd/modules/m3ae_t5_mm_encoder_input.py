@@ -75,12 +75,17 @@ class T5VQA_MMEncoderInput(_Base):
     def finalize(self, device="cuda", compute_dtype=None):
         cfg = self.m3ae.hparams.config
         if compute_dtype is not None:
-            self.m3ae._dtype = compute_dtype
+            self.m3ae.set_compute_dtype(compute_dtype)
         self.store = ParamStore(self, cfg, device, self.m3ae._dtype, self.weight_units,
                                 group_fn=param_group_of_decoder, hparams_fn=group_hparams_decoder)
         self.m3ae.store = self.store
         return self
 
+    @property
+    def f32x3(self):
+        return self.m3ae.f32x3
+
+    @ops.model_mode
     def prepare_inputs(self, batch):
         """m3ae_t5_mm_encoder_input.py:100-190 with include_cls_feats=True, include_imagetext_feats=False (the
         run_scripts/finetune_m3ae.sh setting), batched."""
@@ -107,6 +112,7 @@ class T5VQA_MMEncoderInput(_Base):
         return self.tokenizer(flat, padding=True, truncation=True, return_tensors="pt").input_ids.to(
             batch["text_ids"].device)
 
+    @ops.model_mode
     def forward(self, batch, test=False):
         """Training branch of m3ae_t5_mm_encoder_input.py:193-295."""
         if self.store is None:

@@ -6,9 +6,12 @@ gradient buffer) by the wgrad / reduction kernels themselves, and the Functions 
 accumulation kernels, and the data-parallel reducer (m3ae_amd/ddp.py) is told the moment a gradient is complete
 through `grad_ready_hook`.
 """
+import contextlib
 import ctypes as C
+import functools
 import math
 import os
+import threading
 
 import torch
 
@@ -36,6 +39,65 @@ def _gemm_flags():
     return ((1 if NT_NO_PERSISTENT else 0) | (((GEMM_NT_VARIANT + 1) & 0xF) << 8) | (((GEMM_TN_VARIANT + 1) & 0xF) << 12)
             | ((GEMM_COL_GROUP & 0xF) << 16) | ((GEMM_ST_POLICY & 0x3) << 20))
 PROFILE = None  # when a list: every GEMM / attention launch is bracketed by HIP events on the launch stream
+
+
+# fp32x3 mode (compute_dtype="fp32x3"): parity mode's fp32 storage and kernels, with every fp32 GEMM -- the attention products
+# included -- on the split-bf16 MFMA kernel (M3AE_GEMM_F32_X3 / M3AE_ATTN_F32_X3, csrc/gemm_f32x3.hip).  The mode is per thread:
+# a model's entry points run inside `f32x3_mode(model.f32x3)` (`model_mode`), and every autograd node (`Function`) records the
+# mode of its forward and restores it around its backward, which autograd runs on a thread of its own.  A parity-mode model in
+# the same process never sees the bits.
+class _Mode(threading.local):
+    x3 = False
+
+
+_MODE = _Mode()
+
+
+@contextlib.contextmanager
+def f32x3_mode(on):
+    prev, _MODE.x3 = _MODE.x3, bool(on)
+    try:
+        yield
+    finally:
+        _MODE.x3 = prev
+
+
+def f32x3_active():
+    return _MODE.x3
+
+
+def model_mode(fn):
+    """Decorator of a model method: run it in the model's GEMM mode (`self.f32x3`)."""
+    @functools.wraps(fn)
+    def run(self, *args, **kwargs):
+        with f32x3_mode(getattr(self, "f32x3", False)):
+            return fn(self, *args, **kwargs)
+    return run
+
+
+class Function(torch.autograd.Function):
+    """torch.autograd.Function whose backward runs in the fp32x3 mode its forward ran in (saved on ctx)."""
+
+    def __init_subclass__(cls, **kwargs):
+        super().__init_subclass__(**kwargs)
+        fwd, bwd = cls.__dict__.get("forward"), cls.__dict__.get("backward")
+        if fwd is not None:
+            f = fwd.__func__ if isinstance(fwd, staticmethod) else fwd
+
+            def forward(ctx, *args):
+                ctx.m3ae_x3 = _MODE.x3
+                return f(ctx, *args)
+            cls.forward = staticmethod(functools.wraps(f)(forward))
+        if bwd is not None:
+            b = bwd.__func__ if isinstance(bwd, staticmethod) else bwd
+
+            def backward(ctx, *grads):
+                prev, _MODE.x3 = _MODE.x3, getattr(ctx, "m3ae_x3", False)
+                try:
+                    return b(ctx, *grads)
+                finally:
+                    _MODE.x3 = prev
+            cls.backward = staticmethod(functools.wraps(b)(backward))
 
 
 def _prof_begin():
@@ -149,6 +211,8 @@ def gemm(a, a_sm, a_sk, b, b_sk, b_sn, c, c_sm, M, N, K, *, alpha=1.0, accumulat
     d.dact = dact
     d.preact_grad = int(preact_grad)
     d.launch_flags = _gemm_flags()
+    if _MODE.x3 and d.dtype_a == F32 and d.dtype_b == F32 and d.dtype_c == F32:
+        d.launch_flags |= _lib.GEMM_F32_X3
     d.force_generic = int(force_generic)
     if a_rowsum is not None:
         assert a_rowsum.dtype == torch.float32 and a_rowsum.numel() >= M and batch == (1, 1)
@@ -300,7 +364,7 @@ def add(a, b, out=None):
     return out
 
 
-class Fork2Fn(torch.autograd.Function):
+class Fork2Fn(Function):
     """Identity with two outputs for a tensor that feeds two consumers (a fusion layer's x / y feed the text layer AND the image
     layer of the pair, m3ae_module.py:269-278): the two gradients meet here and are summed by the library's add instead of by
     autograd's accumulation (12 ATen adds per step in round 3).  Runs on the stream of its forward, i.e. the producer's."""
@@ -322,7 +386,7 @@ def fork2(x):
     return Fork2Fn.apply(x) if (x.requires_grad and torch.is_grad_enabled()) else (x, x)
 
 
-class LinearFn(torch.autograd.Function):
+class LinearFn(Function):
     """y = act(x W^T + b + extra_bias) (+ residual).  nn.Linear sites of clip_model.py / bert_model.py /
     m3ae_module.py.  `weight` / `bias` are Parameters or PackedParams; `anchors` are the underlying Parameters of a
     PackedParam (graph recording only)."""
@@ -370,7 +434,7 @@ class LinearFn(torch.autograd.Function):
         return (dx, dres, dextra, None, None, None, None) + (None,) * ctx.n_anchor
 
 
-class GatherLinearFn(torch.autograd.Function):
+class GatherLinearFn(Function):
     """y = act(x[:, 0] W^T + b): Pooler (prediction_heads.py:15-18).  The token-0 rows are addressed in place
     through the GEMM's row stride; the backward scatters into a zeroed [B, L, D] gradient."""
 
@@ -402,7 +466,7 @@ class GatherLinearFn(torch.autograd.Function):
         return dx, None, None, None
 
 
-class MLPFn(torch.autograd.Function):
+class MLPFn(Function):
     """y = act(x W1^T + b1) W2^T + b2 (+ residual).  BertIntermediate + BertOutput.dense (bert_model.py:416-440)
     and the CLIP mlp (clip_model.py:46-50).  The activation derivative is fused into the dgrad GEMM's epilogue."""
 
@@ -444,7 +508,7 @@ def mlp(x, w1, b1, w2, b2, act, residual=None):
 # ----------------------------------------------------------------------------------------------------------
 # LayerNorm
 # ----------------------------------------------------------------------------------------------------------
-class LayerNormFn(torch.autograd.Function):
+class LayerNormFn(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, act, rms):
         xc = x.contiguous()
@@ -542,6 +606,8 @@ def _attn_desc(B, H, Lq, Lk, Dh, q, k, v, o, key_mask, pos_bias, scale, causal, 
     d.lse_stride = lse_stride
     d.dtype = dtype
     d.launch_flags = _lib.ATTN_LEGACY_KERNELS if ATTN_LEGACY else 0
+    if _MODE.x3 and dtype == F32:
+        d.launch_flags |= _lib.ATTN_F32_X3
     return d
 
 
@@ -636,7 +702,7 @@ def attn_probs(q, k, lse, heads, key_mask=None, scale=None, dropout=None):
     return out
 
 
-class SelfAttnFn(torch.autograd.Function):
+class SelfAttnFn(Function):
     """softmax(QK^T / sqrt(dh) + mask) V on a packed [B, L, 3D] projection (rows Q | K | V)."""
 
     @staticmethod
@@ -658,7 +724,7 @@ class SelfAttnFn(torch.autograd.Function):
         return dqkv, None, None, None, None
 
 
-class CrossAttnFn(torch.autograd.Function):
+class CrossAttnFn(Function):
     """Q from this stream [B, Lq, D]; packed K | V [B, Lk, 2D] from the other stream (bert_model.py:275-278)."""
 
     @staticmethod
@@ -963,7 +1029,7 @@ def _ffn_sub_bwd(dy, saved, P):
     return mm_dgrad(du, P.w1, residual=ds)
 
 
-class BertCrossLayerFn(torch.autograd.Function):
+class BertCrossLayerFn(Function):
     """BertCrossLayer.forward (bert_model.py:457-498): self-attn -> cross-attn -> FFN as one node."""
 
     @staticmethod
@@ -1001,7 +1067,7 @@ class BertCrossLayerFn(torch.autograd.Function):
                (None,) * ctx.n_anchor
 
 
-class BertSelfLayerFn(torch.autograd.Function):
+class BertSelfLayerFn(Function):
     """BertSelfLayer == HF RobertaLayer (bert_model.py:506-546; m3ae_module.py:233-234)."""
 
     @staticmethod
@@ -1025,7 +1091,7 @@ class BertSelfLayerFn(torch.autograd.Function):
         return (dh.view(B, L, D), None, None) + (None,) * ctx.n_anchor
 
 
-class ClipBlockFn(torch.autograd.Function):
+class ClipBlockFn(Function):
     """ResidualAttentionBlock.forward (clip_model.py:60-63), pre-LN: x += MHA(LN1(x)); x += MLP(LN2(x))."""
 
     @staticmethod
@@ -1188,7 +1254,7 @@ def _t5_ff_bwd(dy, saved, P):
     return ln_bwd_raw(dn, h2, P.ln, None, rstd, dx_add=dy, rms=True)
 
 
-class T5EncBlockFn(torch.autograd.Function):
+class T5EncBlockFn(Function):
     @staticmethod
     def forward(ctx, h, pos_bias, P, *anchors):
         B, L, D = h.shape
@@ -1214,7 +1280,7 @@ class T5EncBlockFn(torch.autograd.Function):
         return (None if dh is None else dh.view(B, L, D), dbias, None) + (None,) * ctx.n_anchor
 
 
-class T5DecBlockFn(torch.autograd.Function):
+class T5DecBlockFn(Function):
     @staticmethod
     def forward(ctx, h, enc, pos_bias, P, *anchors):
         B, T, D = h.shape
@@ -1246,7 +1312,7 @@ class T5DecBlockFn(torch.autograd.Function):
                 None) + (None,) * ctx.n_anchor
 
 
-class EmbedRowsFn(torch.autograd.Function):
+class EmbedRowsFn(Function):
     """rows = table[ids] (T5 `shared` lookup for the teacher-forced decoder input).  `table` is the compute-dtype
     view of `weight`; the gradient (only when the embedding is trainable) is scatter-added into weight.grad."""
 
@@ -1272,7 +1338,7 @@ class EmbedRowsFn(torch.autograd.Function):
 # ----------------------------------------------------------------------------------------------------------
 # embeddings / tokens
 # ----------------------------------------------------------------------------------------------------------
-class RobertaEmbedFn(torch.autograd.Function):
+class RobertaEmbedFn(Function):
     @staticmethod
     def forward(ctx, ids, word, pos, typ, pad_id, dtype):
         _need_cuda(ids)
@@ -1304,7 +1370,7 @@ def roberta_embed(ids, word, pos, typ, pad_id, dtype):
     return RobertaEmbedFn.apply(ids, word, pos, typ, pad_id, dtype)
 
 
-class VitTokensFn(torch.autograd.Function):
+class VitTokensFn(Function):
     """conv1 (k = s = patch, no bias) as im2col + GEMM, prepend class_embedding, optional + positional_embedding
     (clip_model.py:94-99 / :110-116)."""
 
@@ -1357,7 +1423,7 @@ def vit_tokens(img, conv_w, cls, pos, dtype, add_pos=True):
 # ----------------------------------------------------------------------------------------------------------
 # losses
 # ----------------------------------------------------------------------------------------------------------
-class BCELossFn(torch.autograd.Function):
+class BCELossFn(Function):
     """F.binary_cross_entropy_with_logits(x, z) * z.shape[1]  (objectives.py:201)."""
 
     @staticmethod
@@ -1381,7 +1447,7 @@ def bce_with_logits_loss(logits, targets):
     return BCELossFn.apply(logits, targets)
 
 
-class XentFn(torch.autograd.Function):
+class XentFn(Function):
     """F.cross_entropy(logits, labels, ignore_index=-100) (objectives.py:19-23, :101)."""
 
     @staticmethod
@@ -1416,7 +1482,7 @@ def cross_entropy(logits, labels):
     return XentFn.apply(logits, labels)
 
 
-class VocabProjFn(torch.autograd.Function):
+class VocabProjFn(Function):
     """logits = x . W^T + b for a vocabulary that is not a multiple of 128 (RoBERTa: 50265), perf mode.  The MFMA
     kernels need N % 4 == 0 (forward), K % 64 == 0 (dgrad) and N1 % 128 == 0 (wgrad); the odd size would send all three
     to the generic kernel (14 % of a pre-training step).  Zero-padded bf16 operand copies [Vp, K] / [K, Vp] (Vp = V rounded
@@ -1475,7 +1541,7 @@ def vocab_linear(x, weight, bias):
 # ----------------------------------------------------------------------------------------------------------
 # row gather (MIM masking) -- differentiable in the source
 # ----------------------------------------------------------------------------------------------------------
-class GatherRowsFn(torch.autograd.Function):
+class GatherRowsFn(Function):
     @staticmethod
     def forward(ctx, src, idx):
         idx = idx.contiguous()
@@ -1501,7 +1567,7 @@ def gather_rows(src, flat_idx):
     return GatherRowsFn.apply(src, flat_idx)
 
 
-class DropoutFn(torch.autograd.Function):
+class DropoutFn(Function):
     """nn.Dropout as a standalone op (RoBERTa embeddings, HF RobertaEmbeddings.dropout; m3ae_module.py:230)."""
 
     @staticmethod
@@ -1571,7 +1637,7 @@ def mim_targets(img, patch, norm_pix):
     return out
 
 
-class MimLossFn(torch.autograd.Function):
+class MimLossFn(Function):
     """objectives.py:58-62 on the decoder output WITH its class row (x [B, L + 1, D]): masked per-patch MSE."""
 
     @staticmethod

@@ -309,8 +309,8 @@ def build_model(cfg, head, device):
     else:
         # no checkpoint on disk (offline box): deterministic random init of the named architecture
         synth.fill_deterministic(model)
-    dt = torch.bfloat16 if cfg.get("compute_dtype", "bf16") == "bf16" else torch.float32
-    model.finalize(device, dt)
+    mode = cfg.get("compute_dtype", "bf16")
+    model.finalize(device, mode if mode in ("bf16", "fp32", "fp32x3") else torch.float32)
     return model
 
 

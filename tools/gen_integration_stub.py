@@ -44,6 +44,10 @@ def block():
     out.append(struct_stub(_lib.GemmDesc, "m3ae_gemm_desc"))
     out.append(struct_stub(_lib.XattnDesc, "m3ae_xattn_desc"))
     out.append(struct_stub(_lib.AttnDesc, "m3ae_attn_desc"))
+    out.append("# launch_flags bits (fp32x3 mode, ABI 4: additive)")
+    out.append(f"GEMM_NO_PERSISTENT, GEMM_F32_X3 = {_lib.GEMM_NO_PERSISTENT}, {_lib.GEMM_F32_X3}     # m3ae_gemm_desc.launch_flags")
+    out.append(f"ATTN_LEGACY_KERNELS, ATTN_F32_X3 = {_lib.ATTN_LEGACY_KERNELS}, {_lib.ATTN_F32_X3}    # m3ae_attn_desc.launch_flags")
+    out.append("")
     out.append("# attention maps (ABI 4): fp32 [B, H, Lq, Lk] out of an m3ae_attn_fwd / m3ae_xattn_fwd call")
     for name in MAP_ENTRIES:
         res, args = _lib._SIGS[name]
