@@ -72,8 +72,7 @@ class BertAttention(nn.Module):
             h2, o2 = h.contiguous().view(B * L, D), other.contiguous().view(B * Lo, other.shape[2])
             if ops.xattn_supported(h2, L, o2, Lo, other_mask, P):
                 return ops.xattn_fwd(h2, B, L, o2, Lo, other_mask, P, pdrop, need_bwd=False)[0].view(B, L, D)
-        da = (pdrop, ops.next_dropout_seed()) if pdrop > 0 else None
-        dh = (pdrop, ops.next_dropout_seed()) if pdrop > 0 else None
+        da, dh = ops.dropout_pair(pdrop), ops.dropout_pair(pdrop)
         if other is None:
             w, b = self.self.pack("qkv")
             qkv = ops.linear(h, w, b)
@@ -125,11 +124,11 @@ class BertOutput(nn.Module):
 
 def _ffn(layer, h, pdrop=0.0):
     """feed_forward_chunk (bert_model.py:500-503)."""
-    if pdrop > 0:
-        seed = ops.next_dropout_seed()
+    dh = ops.dropout_pair(pdrop)
+    if dh is not None:
         s = ops.mlp(h, layer.intermediate.dense.weight, layer.intermediate.dense.bias, layer.output.dense.weight,
                     layer.output.dense.bias, ops.ACT_GELU)
-        s = ops.DropoutFn.apply(s, pdrop, seed) + h
+        s = ops.DropoutFn.apply(s, *dh) + h
     else:
         s = ops.mlp(h, layer.intermediate.dense.weight, layer.intermediate.dense.bias, layer.output.dense.weight,
                     layer.output.dense.bias, ops.ACT_GELU, residual=h)

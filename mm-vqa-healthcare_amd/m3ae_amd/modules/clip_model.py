@@ -53,9 +53,9 @@ class ResidualAttentionBlock(nn.Module):
     def forward(self, x):
         if self._bp is None:
             a, m = self.attn, self.mlp
-            self._bp = NS(heads=a.num_heads, ln1=self.ln_1, ln2=self.ln_2, w_in=a.in_proj_weight, b_in=a.in_proj_bias,
-                          w_out=a.out_proj.weight, b_out=a.out_proj.bias, w_fc=m.c_fc.weight, b_fc=m.c_fc.bias,
-                          w_proj=m.c_proj.weight, b_proj=m.c_proj.bias)
+            self._bp = NS(heads=a.num_heads, ln1=self.ln_1, ln2=self.ln_2, w_qkv=a.in_proj_weight, b_qkv=a.in_proj_bias,
+                          w_o=a.out_proj.weight, b_o=a.out_proj.bias, w1=m.c_fc.weight, b1=m.c_fc.bias,
+                          w2=m.c_proj.weight, b2=m.c_proj.bias)
             self._anchors = tuple(self.parameters())
         return ops.ClipBlockFn.apply(x, self._bp, *self._anchors)
 

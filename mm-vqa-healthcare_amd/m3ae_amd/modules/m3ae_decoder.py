@@ -70,11 +70,10 @@ class DecoderLayer(nn.Module):
     def forward(self, t, enc, key_mask):
         D, H = self.mha1.embed_dim, self.mha1.num_heads
         p = self.p_drop if self.training else 0.0   # MultiheadAttention(dropout=p) on the weights + dropout1..3 (:43-53)
-        att = (lambda: (p, ops.next_dropout_seed())) if p > 0 else (lambda: None)
         # masked (causal + key padding) self-attention on the pre-normed input; residual = the un-normed input
         xn = self._ln(self.pre_norm, t)
         qkv = ops.linear(xn, self.mha1.in_proj_weight, self.mha1.in_proj_bias)
-        ctx = ops.self_attention(qkv, key_mask, H, dropout=att(), causal=True)
+        ctx = ops.self_attention(qkv, key_mask, H, dropout=ops.dropout_pair(p), causal=True)
         if p > 0:
             x = ops.dropout(ops.linear(ctx, self.mha1.out_proj.weight, self.mha1.out_proj.bias), p) + t
         else:
@@ -83,7 +82,7 @@ class DecoderLayer(nn.Module):
         xn = self._ln(self.layernorm1, x)
         q = ops.linear(xn, self.mha2.in_proj_weight, self.mha2.in_proj_bias)[..., :D]
         kv = ops.linear(enc, self.mha2.in_proj_weight, self.mha2.in_proj_bias)[..., D:]
-        ctx = ops.cross_attention(q, kv, None, H, att())
+        ctx = ops.cross_attention(q, kv, None, H, ops.dropout_pair(p))
         if p > 0:
             x = ops.dropout(ops.linear(ctx, self.mha2.out_proj.weight, self.mha2.out_proj.bias), p) + x
         else:

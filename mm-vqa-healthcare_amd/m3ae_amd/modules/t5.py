@@ -107,9 +107,10 @@ class _FFLayer(nn.Module):
 
 
 def _attn_params(att, ln, cross):
+    # the names ops' attention core reads; T5 has no linear biases
     if cross:
-        return NS(heads=att.heads, w_q=att.q.weight, w_kv=att.pack("kv"), w_o=att.o.weight, ln=ln)
-    return NS(heads=att.heads, w_qkv=att.pack("qkv"), w_o=att.o.weight, ln=ln)
+        return NS(heads=att.heads, w_q=att.q.weight, b_q=None, w_kv=att.pack("kv"), b_kv=None, w_o=att.o.weight, ln=ln)
+    return NS(heads=att.heads, w_qkv=att.pack("qkv"), b_qkv=None, w_o=att.o.weight, ln=ln)
 
 
 class T5Block(nn.Module):
@@ -129,7 +130,8 @@ class T5Block(nn.Module):
             sa = self.layer[0]
             ff = self.layer[-1]
             self._bp = NS(attn=_attn_params(sa.SelfAttention, sa.layer_norm, False),
-                          ffn=NS(w1=ff.DenseReluDense.wi.weight, w2=ff.DenseReluDense.wo.weight, ln=ff.layer_norm))
+                          ffn=NS(w1=ff.DenseReluDense.wi.weight, b1=None, w2=ff.DenseReluDense.wo.weight, b2=None,
+                                 ln=ff.layer_norm))
             if self.is_decoder:
                 ca = self.layer[1]
                 self._bp.cross = _attn_params(ca.EncDecAttention, ca.layer_norm, True)
@@ -193,9 +195,9 @@ class T5Stack(nn.Module):
         h2 = h.contiguous().view(B * T, D)
         for blk, kv in zip(self.block, cross_kv):
             P = blk.params()
-            a, _ = ops._t5_attn_fwd(h2, B, T, None, T, P.attn, bias, True, pd)
-            c, _ = ops._t5_attn_fwd(a, B, T, None, Ls, P.cross, None, False, pd, kv=kv)
-            h2, _ = ops._t5_ff_fwd(c, P.ffn, pd)
+            a, _ = ops.t5_attn_fwd(h2, B, P.attn, bias, True, pd)
+            c, _ = ops.t5_attn_fwd(a, B, P.cross, None, False, pd, kv=kv)
+            h2, _ = ops.t5_ff_fwd(c, P.ffn, pd)
         ln = self.final_layer_norm
         return ops.dropout(ops.layer_norm(h2.view(B, T, D), ln.weight, None, ln.eps, rms=True), self.dropout_rate, self.training)
 
@@ -220,8 +222,8 @@ class T5Stack(nn.Module):
         for blk, kv, cache in zip(self.block, cross_kv, self_cache):
             P = blk.params()
             a = ops.t5_self_attn_step(h2, B, P.attn, bias, cache, t, pd)
-            c, _ = ops._t5_attn_fwd(a, B, 1, None, Ls, P.cross, None, False, pd, kv=kv)
-            h2, _ = ops._t5_ff_fwd(c, P.ffn, pd)
+            c, _ = ops.t5_attn_fwd(a, B, P.cross, None, False, pd, kv=kv)
+            h2, _ = ops.t5_ff_fwd(c, P.ffn, pd)
         ln = self.final_layer_norm
         return ops.dropout(ops.layer_norm(h2.view(B, 1, D), ln.weight, None, ln.eps, rms=True), self.dropout_rate, self.training)
 

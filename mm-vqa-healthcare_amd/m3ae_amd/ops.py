@@ -142,6 +142,18 @@ def next_dropout_seed():
     return ((_drop_base << 32) | (_drop_ctr & 0xFFFFFFFF)) & 0xFFFFFFFFFFFFFFFF
 
 
+def dropout_pair(p):
+    """(p, fresh seed) of one dropout site; None when the site is inactive (p <= 0)."""
+    return (p, next_dropout_seed()) if p > 0 else None
+
+
+def _set_dropout(d, dropout):
+    """dropout = (p, seed) or None into a GEMM / attention descriptor, with the salt of the moment."""
+    if dropout is not None and dropout[0] > 0:
+        d.dropout_p, d.dropout_seed = dropout
+        d.dropout_salt = _salt()
+
+
 def _dt(t):
     if t.dtype == torch.float32:
         return F32
@@ -217,9 +229,7 @@ def gemm(a, a_sm, a_sk, b, b_sk, b_sn, c, c_sm, M, N, K, *, alpha=1.0, accumulat
     if a_rowsum is not None:
         assert a_rowsum.dtype == torch.float32 and a_rowsum.numel() >= M and batch == (1, 1)
         d.a_rowsum = a_rowsum.data_ptr()
-    if dropout is not None and dropout[0] > 0:
-        d.dropout_p, d.dropout_seed = dropout
-        d.dropout_salt = _salt()
+    _set_dropout(d, dropout)
     e0 = _prof_begin()
     check(_lib.lib().m3ae_gemm(C.byref(d), _stream()), "m3ae_gemm")
     if e0 is not None:
@@ -280,22 +290,21 @@ def mm_nt(x2, ldx, M, w, bias=None, act=ACT_NONE, residual=None, want_preact=Fal
     return y, pre
 
 
-def mm_dgrad(dy, w_param, dact_aux=None, dact=ACT_NONE, residual=None, alpha=1.0, dropout=None):
-    """dx[M,K] = dy[M,N] . W[N,K]  (bf16: NT against the transposed shadow; fp32: strided generic)."""
+def mm_dgrad(dy, w_param, dact_aux=None, dact=ACT_NONE, residual=None, alpha=1.0, dropout=None, out=None, ld_out=None):
+    """dx[M,K] = dy[M,N] . W[N,K]  (bf16: NT against the transposed shadow; fp32: strided generic).  out / ld_out: write
+    the rows into this preallocated tensor at this row stride instead of a fresh [M, K]."""
     M, N = dy.shape
     wt = getattr(w_param, "m3ae_t", None)
     if wt is not None:
-        K = wt.shape[0]
-        dx = torch.empty((M, K), dtype=dy.dtype, device=dy.device)
-        gemm(dy, dy.stride(0), 1, wt, 1, wt.stride(0), dx, K, M, K, N, dact_aux=dact_aux, dact=dact, residual=residual,
-             alpha=alpha, dropout=dropout)
+        b, b_sk, b_sn, K = wt, 1, wt.stride(0), wt.shape[0]
     else:
-        w = compute_weight(w_param)
-        K = w.shape[1]
-        dx = torch.empty((M, K), dtype=dy.dtype, device=dy.device)
-        gemm(dy, dy.stride(0), 1, w, w.stride(0), 1, dx, K, M, K, N, dact_aux=dact_aux, dact=dact, residual=residual,
-             alpha=alpha, dropout=dropout)
-    return dx
+        b = compute_weight(w_param)
+        b_sk, b_sn, K = b.stride(0), 1, b.shape[1]
+    if out is None:
+        out, ld_out = torch.empty((M, K), dtype=dy.dtype, device=dy.device), K
+    gemm(dy, dy.stride(0), 1, b, b_sk, b_sn, out, ld_out, M, K, N, dact_aux=dact_aux, dact=dact, residual=residual,
+         alpha=alpha, dropout=dropout)
+    return out
 
 
 def mm_wgrad(dy, x2, ldx, w_param, b_param=None, alpha=1.0):
@@ -455,14 +464,7 @@ class GatherLinearFn(Function):
         dy2 = dy.contiguous()
         dz = act_bwd(dy2, pre, ctx.act) if ctx.act != ACT_NONE else dy2
         mm_wgrad(dz, xc, L * D, ctx.weight, ctx.bias)
-        dx = torch.zeros_like(xc)
-        wt = getattr(ctx.weight, "m3ae_t", None)
-        N = dz.shape[1]
-        if wt is not None:
-            gemm(dz, N, 1, wt, 1, wt.stride(0), dx, L * D, B, D, N)
-        else:
-            w = compute_weight(ctx.weight)
-            gemm(dz, N, 1, w, w.stride(0), 1, dx, L * D, B, D, N)
+        dx = mm_dgrad(dz, ctx.weight, out=torch.zeros_like(xc), ld_out=L * D)
         return dx, None, None, None
 
 
@@ -637,9 +639,7 @@ def attn_forward(q, k, v, heads, key_mask=None, pos_bias=None, scale=None, causa
     # bf16 kernels write every row of the table, padding rows (>= Lq) included; the fp32 path leaves it untouched
     lse = (torch.empty if q.dtype == torch.bfloat16 else torch.zeros)((B, heads, lse_stride), dtype=torch.float32, device=q.device)
     d = _attn_desc(B, heads, Lq, Lk, Dh, q, k, v, o, key_mask, pos_bias, scale, causal, lse, lse_stride, _dt(q))
-    if dropout is not None and dropout[0] > 0:
-        d.dropout_p, d.dropout_seed = dropout
-        d.dropout_salt = _salt()
+    _set_dropout(d, dropout)
     ws = _attn_ws(d, False, q.device)
     e0 = _prof_begin()
     check(_lib.lib().m3ae_attn_fwd(C.byref(d), _stream()), "m3ae_attn_fwd")
@@ -668,9 +668,7 @@ def attn_backward(q, k, v, o, lse, do, dq, dk, dv, heads, key_mask=None, pos_bia
     delta = torch.empty_like(lse) if q.dtype == torch.bfloat16 else torch.zeros_like(lse)
     d.d_o, d.dq, d.dk, d.dv, d.delta = do.data_ptr(), dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), delta.data_ptr()
     d.d_pos_bias = d_pos_bias.data_ptr() if d_pos_bias is not None else None
-    if dropout is not None and dropout[0] > 0:
-        d.dropout_p, d.dropout_seed = dropout
-        d.dropout_salt = _salt()
+    _set_dropout(d, dropout)
     ws = _attn_ws(d, True, q.device)
     e0 = _prof_begin()
     check(_lib.lib().m3ae_attn_bwd(C.byref(d), _stream()), "m3ae_attn_bwd")
@@ -692,9 +690,7 @@ def attn_probs(q, k, lse, heads, key_mask=None, scale=None, dropout=None):
     out = torch.empty((B, heads, Lq, Lk), dtype=torch.float32, device=q.device)
     lse_stride = lse.shape[-1] if lse is not None else 0
     d = _attn_desc(B, heads, Lq, Lk, Dh, q, k, k, q, key_mask, None, scale, False, lse, lse_stride, _dt(q))
-    if dropout is not None and dropout[0] > 0:
-        d.dropout_p, d.dropout_seed = dropout
-        d.dropout_salt = _salt()
+    _set_dropout(d, dropout)
     e0 = _prof_begin()
     check(_lib.lib().m3ae_attn_probs(C.byref(d), C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1), out.stride(2),
                                      _stream()), "m3ae_attn_probs")
@@ -928,31 +924,86 @@ def xattn_bwd(dy, saved, B, L, Lo, P, need_dother=True):
     return dx, dother
 
 
+def _qkv_views(bufs, B):
+    """(q, k, v) as [B, L, inner] views of packed projection buffers -- (qkv [B L, 3 inner],) or (q [B L, inner], kv [B Ls,
+    2 inner]) -- and, with the same call, of their gradient buffers."""
+    if len(bufs) == 1:
+        p3 = bufs[0].view(B, -1, bufs[0].shape[1])
+        n = p3.shape[2] // 3
+        return p3[..., :n], p3[..., n:2 * n], p3[..., 2 * n:]
+    q, kv = bufs
+    n = q.shape[1]
+    kv3 = kv.view(B, -1, 2 * n)
+    return q.view(B, -1, n), kv3[..., :n], kv3[..., n:]
+
+
+def _attn_core_fwd(x2, B, P, src2=None, kv=None, mask=None, pos_bias=None, scale=None, causal=False, dropout=None):
+    """Projections + attention product of every block family.  x2 [B L, D]: the rows the queries come from; keys / values from
+    x2 too (packed P.w_qkv), or from the other stream's rows src2 [B Ls, Ds] (P.w_q, P.w_kv), or ready-made in kv [B Ls,
+    2 inner].  dropout = (p, seed) of the attention probabilities.  Returns (o [B, L, inner], lse, proj), proj = (qkv,) or (q, kv)."""
+    M, D = x2.shape
+    if src2 is None and kv is None:
+        proj = (mm_nt(x2, D, M, compute_weight(P.w_qkv), bias=_bdata(P.b_qkv))[0],)
+    else:
+        q, _ = mm_nt(x2, D, M, compute_weight(P.w_q), bias=_bdata(P.b_q))
+        if kv is None:
+            kv, _ = mm_nt(src2, src2.shape[1], src2.shape[0], compute_weight(P.w_kv), bias=_bdata(P.b_kv))
+        proj = (q, kv)
+    q3, k3, v3 = _qkv_views(proj, B)
+    o, lse = attn_forward(q3, k3, v3, P.heads, mask, pos_bias, scale, causal, dropout)
+    return o, lse, proj
+
+
+def _attn_core_bwd(dctx, x2, src2, proj, o, lse, B, P, mask=None, pos_bias=None, scale=None, causal=False, dropout=None,
+                   d_pos_bias=None, residual=None, need_dx=True, need_dsrc=True):
+    """Backward of _attn_core_fwd from dctx = d(o) [B L, inner]: attention backward into a packed gradient buffer, the weight
+    gradients, then the input gradients.  Returns (dx, dsrc); `residual` is added to dx in the dgrad epilogue.  Self or cross is
+    read off `proj`, i.e. off what the forward did."""
+    dproj = tuple(torch.empty_like(t) for t in proj)
+    attn_backward(*_qkv_views(proj, B), o, lse, dctx.view(o.shape), *_qkv_views(dproj, B), P.heads, mask, pos_bias, scale,
+                  causal, d_pos_bias, dropout)
+    D = x2.shape[1]
+    if len(proj) == 1:
+        mm_wgrad(dproj[0], x2, D, P.w_qkv, P.b_qkv)
+        return (mm_dgrad(dproj[0], P.w_qkv, residual=residual) if need_dx else None), None
+    assert src2 is not None, "the forward was given ready-made kv (inference only): there is no source to differentiate"
+    dq, dkv = dproj
+    mm_wgrad(dq, x2, D, P.w_q, P.b_q)
+    mm_wgrad(dkv, src2, src2.shape[1], P.w_kv, P.b_kv)
+    dx = mm_dgrad(dq, P.w_q, residual=residual) if need_dx else None
+    return dx, (mm_dgrad(dkv, P.w_kv) if need_dsrc else None)
+
+
+def _ffn_core_fwd(x2, P, act, residual, mid_drop=None, out_drop=None):
+    """y = dropout_out(dropout_mid(act(x2 W1^T + b1)) W2^T + b2) + residual.  Returns (y, u, g): g the (dropped) activation,
+    u what the backward GEMM needs of the pre-activation (its act' when SAVE_DACT, else itself)."""
+    M, D = x2.shape
+    g, u = mm_nt(x2, D, M, compute_weight(P.w1), bias=_bdata(P.b1), act=act, want_preact=True, preact_grad=SAVE_DACT,
+                 dropout=mid_drop)
+    y, _ = mm_nt(g, g.shape[1], M, compute_weight(P.w2), bias=_bdata(P.b2), residual=residual, dropout=out_drop)
+    return y, u, g
+
+
+def _ffn_core_bwd(dy, x2, u, g, P, act, mid_drop=None, residual=None):
+    """Backward of _ffn_core_fwd from dy = d(W2 output, before the residual join): returns dx (+ residual, in the epilogue)."""
+    mm_wgrad(dy, g, g.shape[1], P.w2, P.b2)
+    du = mm_dgrad(dy, P.w2, dact_aux=u, dact=ACT_MULAUX if SAVE_DACT else act, dropout=mid_drop)   # dU = (dY W2) * act'(U)
+    mm_wgrad(du, x2, x2.shape[1], P.w1, P.b1)
+    return mm_dgrad(du, P.w1, residual=residual)
+
+
 def _attn_sub_fwd(h2, B, L, other2, Lo, mask, P, pdrop=0.0, fused_cross=False):
     """BertAttention (bert_model.py:367-413) on 2-D token-major activations. Returns (y, saved).
     pdrop > 0 (training): attention-probability dropout (:334) and hidden dropout on the output dense (:362).
     P.want_probs: the attention map will be asked of `saved` (_attn_sub_probs): a forward-only fused call copies it out."""
-    heads = P.heads
-    D = h2.shape[1]
     if other2 is not None and fused_cross:
         need_bwd = getattr(P, "need_bwd", True)
         if xattn_supported(h2, L, other2, Lo, mask, P, backward=need_bwd):
             return xattn_fwd(h2, B, L, other2, Lo, mask, P, pdrop, need_bwd=need_bwd, want_probs=getattr(P, "want_probs", False))
-    da = (pdrop, next_dropout_seed()) if pdrop > 0 else None
-    dh = (pdrop, next_dropout_seed()) if pdrop > 0 else None
-    if other2 is None:
-        qkv, _ = mm_nt(h2, D, B * L, compute_weight(P.w_qkv), bias=_bdata(P.b_qkv))
-        v3 = qkv.view(B, L, 3 * D)
-        o, lse = attn_forward(v3[..., :D], v3[..., D:2 * D], v3[..., 2 * D:], heads, mask, dropout=da)
-        proj = (qkv,)
-    else:
-        q, _ = mm_nt(h2, D, B * L, compute_weight(P.w_q), bias=_bdata(P.b_q))
-        kv, _ = mm_nt(other2, other2.shape[1], B * Lo, compute_weight(P.w_kv), bias=_bdata(P.b_kv))
-        kv3 = kv.view(B, Lo, 2 * D)
-        o, lse = attn_forward(q.view(B, L, D), kv3[..., :D], kv3[..., D:], heads, mask, dropout=da)
-        proj = (q, kv)
-    o2 = o.view(B * L, D)
-    s, _ = mm_nt(o2, D, B * L, compute_weight(P.w_o), bias=_bdata(P.b_o), residual=h2, dropout=dh)
+    da, dh = dropout_pair(pdrop), dropout_pair(pdrop)
+    o, lse, proj = _attn_core_fwd(h2, B, P, src2=other2, mask=mask, dropout=da)
+    D = h2.shape[1]
+    s, _ = mm_nt(o.view(B * L, D), D, B * L, compute_weight(P.w_o), bias=_bdata(P.b_o), residual=h2, dropout=dh)
     y, mean, rstd = ln_fwd_raw(s, P.ln)
     return y, (h2, other2, proj, o, lse, s, mean, rstd, mask, da, dh)
 
@@ -963,12 +1014,17 @@ def _attn_sub_probs(saved, B, L, Lo, P):
     if isinstance(saved[0], str):
         return xattn_probs(saved)
     h2, other2, proj, o, lse, s, mean, rstd, mask, da, dh = saved
-    D = h2.shape[1]
-    if other2 is None:
-        v3 = proj[0].view(B, L, 3 * D)
-        return attn_probs(v3[..., :D], v3[..., D:2 * D], lse, P.heads, mask, dropout=da)
-    q, kv = proj
-    return attn_probs(q.view(B, L, D), kv.view(B, Lo, 2 * D)[..., :D], lse, P.heads, mask, dropout=da)
+    q3, k3, _ = _qkv_views(proj, B)
+    return attn_probs(q3, k3, lse, P.heads, mask, dropout=da)
+
+
+def _post_ln_bwd(dy, s, ln, mean, rstd, dh):
+    """Backward of the post-LayerNorm of a BERT sub-block whose dense output was dropped with dh = (p, seed) or None:
+    (ds, dsd) = the gradient of the LayerNorm input (residual branch) and of the dense output before its dropout."""
+    if dh is not None:
+        return ln_bwd_raw(dy, s, ln, mean, rstd, drop=dh)
+    ds = ln_bwd_raw(dy, s, ln, mean, rstd)
+    return ds, ds
 
 
 def _attn_sub_bwd(dy, saved, B, L, Lo, P, need_dother=True):
@@ -976,57 +1032,25 @@ def _attn_sub_bwd(dy, saved, B, L, Lo, P, need_dother=True):
         return xattn_bwd(dy, saved, B, L, Lo, P, need_dother)
     h2, other2, proj, o, lse, s, mean, rstd, mask, da, dh = saved
     D = h2.shape[1]
-    if dh is not None:
-        ds, dsd = ln_bwd_raw(dy, s, P.ln, mean, rstd, drop=dh)  # dsd: gradient of the (dropped) dense output
-    else:
-        ds = dsd = ln_bwd_raw(dy, s, P.ln, mean, rstd)
-    o2 = o.view(B * L, D)
-    mm_wgrad(dsd, o2, D, P.w_o, P.b_o)
+    ds, dsd = _post_ln_bwd(dy, s, P.ln, mean, rstd, dh)
+    mm_wgrad(dsd, o.view(B * L, D), D, P.w_o, P.b_o)
     dctx = mm_dgrad(dsd, P.w_o)
-    if other2 is None:
-        (qkv,) = proj
-        v3 = qkv.view(B, L, 3 * D)
-        dqkv = torch.empty_like(qkv)
-        d3 = dqkv.view(B, L, 3 * D)
-        attn_backward(v3[..., :D], v3[..., D:2 * D], v3[..., 2 * D:], o, lse, dctx.view(B, L, D), d3[..., :D],
-                      d3[..., D:2 * D], d3[..., 2 * D:], P.heads, mask, dropout=da)
-        mm_wgrad(dqkv, h2, D, P.w_qkv, P.b_qkv)
-        dhid = mm_dgrad(dqkv, P.w_qkv, residual=ds)  # + residual-branch gradient, fused
-        return dhid, None
-    q, kv = proj
-    kv3 = kv.view(B, Lo, 2 * D)
-    dq = torch.empty_like(q)
-    dkv = torch.empty_like(kv)
-    dkv3 = dkv.view(B, Lo, 2 * D)
-    attn_backward(q.view(B, L, D), kv3[..., :D], kv3[..., D:], o, lse, dctx.view(B, L, D), dq.view(B, L, D),
-                  dkv3[..., :D], dkv3[..., D:], P.heads, mask, dropout=da)
-    mm_wgrad(dq, h2, D, P.w_q, P.b_q)
-    mm_wgrad(dkv, other2, other2.shape[1], P.w_kv, P.b_kv)
-    dhid = mm_dgrad(dq, P.w_q, residual=ds)
-    dother = mm_dgrad(dkv, P.w_kv) if need_dother else None
-    return dhid, dother
+    # ds: the residual-branch gradient, joined in the last dgrad's epilogue
+    return _attn_core_bwd(dctx, h2, other2, proj, o, lse, B, P, mask=mask, dropout=da, residual=ds, need_dsrc=need_dother)
 
 
 def _ffn_sub_fwd(h2, P, pdrop=0.0):
     """BertIntermediate + BertOutput (bert_model.py:416-442, 500-503); pdrop: hidden dropout on the output dense (:440)."""
-    M, D = h2.shape
-    dh = (pdrop, next_dropout_seed()) if pdrop > 0 else None
-    g, u = mm_nt(h2, D, M, compute_weight(P.w1), bias=_bdata(P.b1), act=ACT_GELU, want_preact=True, preact_grad=SAVE_DACT)
-    s, _ = mm_nt(g, g.shape[1], M, compute_weight(P.w2), bias=_bdata(P.b2), residual=h2, dropout=dh)
+    dh = dropout_pair(pdrop)
+    s, u, g = _ffn_core_fwd(h2, P, ACT_GELU, h2, out_drop=dh)
     y, mean, rstd = ln_fwd_raw(s, P.ln)
     return y, (h2, u, g, s, mean, rstd, dh)
 
 
 def _ffn_sub_bwd(dy, saved, P):
     h2, u, g, s, mean, rstd, dh = saved
-    if dh is not None:
-        ds, dsd = ln_bwd_raw(dy, s, P.ln, mean, rstd, drop=dh)
-    else:
-        ds = dsd = ln_bwd_raw(dy, s, P.ln, mean, rstd)
-    mm_wgrad(dsd, g, g.shape[1], P.w2, P.b2)
-    du = mm_dgrad(dsd, P.w2, dact_aux=u, dact=ACT_MULAUX if SAVE_DACT else ACT_GELU)  # u holds gelu'(pre-activation)
-    mm_wgrad(du, h2, h2.shape[1], P.w1, P.b1)
-    return mm_dgrad(du, P.w1, residual=ds)
+    ds, dsd = _post_ln_bwd(dy, s, P.ln, mean, rstd, dh)
+    return _ffn_core_bwd(dsd, h2, u, g, P, ACT_GELU, residual=ds)
 
 
 class BertCrossLayerFn(Function):
@@ -1100,15 +1124,11 @@ class ClipBlockFn(Function):
         M = B * L
         x2 = x.contiguous().view(M, D)
         h1, m1, r1 = ln_fwd_raw(x2, P.ln1)
-        qkv, _ = mm_nt(h1, D, M, compute_weight(P.w_in), bias=_bdata(P.b_in))
-        v3 = qkv.view(B, L, 3 * D)
-        o, lse = attn_forward(v3[..., :D], v3[..., D:2 * D], v3[..., 2 * D:], P.heads, None)
-        xa, _ = mm_nt(o.view(M, D), D, M, compute_weight(P.w_out), bias=_bdata(P.b_out), residual=x2)
+        o, lse, proj = _attn_core_fwd(h1, B, P)
+        xa, _ = mm_nt(o.view(M, D), D, M, compute_weight(P.w_o), bias=_bdata(P.b_o), residual=x2)
         h2, m2, r2 = ln_fwd_raw(xa, P.ln2)
-        g, u = mm_nt(h2, D, M, compute_weight(P.w_fc), bias=_bdata(P.b_fc), act=ACT_QUICKGELU, want_preact=True,
-                     preact_grad=SAVE_DACT)
-        y, _ = mm_nt(g, g.shape[1], M, compute_weight(P.w_proj), bias=_bdata(P.b_proj), residual=xa)
-        ctx.saved = (x2, m1, r1, h1, qkv, o, lse, xa, m2, r2, h2, u, g)
+        y, u, g = _ffn_core_fwd(h2, P, ACT_QUICKGELU, xa)
+        ctx.saved = (x2, m1, r1, h1, proj, o, lse, xa, m2, r2, h2, u, g)
         ctx.P, ctx.dims, ctx.n_anchor = P, (B, L, D), len(anchors)
         return y.view(B, L, D)
 
@@ -1116,24 +1136,15 @@ class ClipBlockFn(Function):
     def backward(ctx, dy):
         B, L, D = ctx.dims
         M = B * L
-        x2, m1, r1, h1, qkv, o, lse, xa, m2, r2, h2, u, g = ctx.saved
+        x2, m1, r1, h1, proj, o, lse, xa, m2, r2, h2, u, g = ctx.saved
         ctx.saved = None
         P = ctx.P
         dy2 = dy.contiguous().view(M, D)
-        mm_wgrad(dy2, g, g.shape[1], P.w_proj, P.b_proj)
-        du = mm_dgrad(dy2, P.w_proj, dact_aux=u, dact=ACT_MULAUX if SAVE_DACT else ACT_QUICKGELU)
-        mm_wgrad(du, h2, D, P.w_fc, P.b_fc)
-        dh2 = mm_dgrad(du, P.w_fc)
+        dh2 = _ffn_core_bwd(dy2, h2, u, g, P, ACT_QUICKGELU)
         dxa = ln_bwd_raw(dh2, xa, P.ln2, m2, r2, dx_add=dy2)  # + residual branch, fused into LN backward
-        mm_wgrad(dxa, o.view(M, D), D, P.w_out, P.b_out)
-        dctx = mm_dgrad(dxa, P.w_out)
-        v3 = qkv.view(B, L, 3 * D)
-        dqkv = torch.empty_like(qkv)
-        d3 = dqkv.view(B, L, 3 * D)
-        attn_backward(v3[..., :D], v3[..., D:2 * D], v3[..., 2 * D:], o, lse, dctx.view(B, L, D), d3[..., :D],
-                      d3[..., D:2 * D], d3[..., 2 * D:], P.heads, None)
-        mm_wgrad(dqkv, h1, D, P.w_in, P.b_in)
-        dh1 = mm_dgrad(dqkv, P.w_in)
+        mm_wgrad(dxa, o.view(M, D), D, P.w_o, P.b_o)
+        dctx = mm_dgrad(dxa, P.w_o)
+        dh1, _ = _attn_core_bwd(dctx, h1, None, proj, o, lse, B, P)
         dx = ln_bwd_raw(dh1, x2, P.ln1, m1, r1, dx_add=dxa)
         return (dx.view(B, L, D), None) + (None,) * ctx.n_anchor
 
@@ -1153,38 +1164,23 @@ def _drop_raw(x2, drop):
     return out
 
 
-def _t5_attn_fwd(h2, B, L, src2, Ls, P, bias, causal, pdrop=0.0, kv=None):
-    # kv: the projected keys / values of `src2` computed earlier ([B * Ls, 2 inner]; generation re-uses them every step)
-    # HF T5 (third party, transformers 4.6.0): attention-weight dropout inside T5Attention and `hidden + dropout(attn)`
-    da = (pdrop, next_dropout_seed()) if pdrop > 0 else None
-    dh = (pdrop, next_dropout_seed()) if pdrop > 0 else None
+def t5_attn_fwd(h2, B, P, bias, causal, pdrop=0.0, src2=None, kv=None):
+    """HF T5LayerSelfAttention / T5LayerCrossAttention (third party, transformers 4.6.0) on rows h2 [B L, D]: attention-weight
+    dropout inside T5Attention and `hidden + dropout(attn)`.  src2 [B Ls, D]: the rows the cross-attention reads; kv: their
+    projected keys / values computed earlier ([B Ls, 2 inner]; generation re-uses them every step).  Returns (y, saved)."""
+    da, dh = dropout_pair(pdrop), dropout_pair(pdrop)
     n, _, rstd = ln_fwd_raw(h2, P.ln, rms=True)
-    D = n.shape[1]
-    inner = P.w_o.shape[1]
-    if src2 is None and kv is None:
-        qkv, _ = mm_nt(n, D, B * L, compute_weight(P.w_qkv))
-        v3 = qkv.view(B, L, 3 * inner)
-        o, lse = attn_forward(v3[..., :inner], v3[..., inner:2 * inner], v3[..., 2 * inner:], P.heads, None, bias,
-                              scale=1.0, causal=causal, dropout=da)
-        proj = (qkv,)
-    else:
-        q, _ = mm_nt(n, D, B * L, compute_weight(P.w_q))
-        if kv is None:
-            kv, _ = mm_nt(src2, src2.shape[1], B * Ls, compute_weight(P.w_kv))
-        kv3 = kv.view(B, Ls, 2 * inner)
-        o, lse = attn_forward(q.view(B, L, inner), kv3[..., :inner], kv3[..., inner:], P.heads, None, bias, scale=1.0,
-                              causal=causal, dropout=da)
-        proj = (q, kv)
-    y, _ = mm_nt(o.view(B * L, inner), inner, B * L, compute_weight(P.w_o), residual=h2, dropout=dh)
+    o, lse, proj = _attn_core_fwd(n, B, P, src2=src2, kv=kv, pos_bias=bias, scale=1.0, causal=causal, dropout=da)
+    M, inner = h2.shape[0], o.shape[2]
+    y, _ = mm_nt(o.view(M, inner), inner, M, compute_weight(P.w_o), residual=h2, dropout=dh)
     return y, (h2, rstd, n, proj, o, lse, src2, da, dh)
 
 
 def t5_self_attn_step(h2, B, P, bias_row, cache, t, pdrop=0.0):
     """Generation: the T5 self-attention sub-layer for ONE new position t of every sequence.  h2 [B, D]; `cache` [B, Tmax,
     2 inner] holds the keys | values of positions < t and receives row t; bias_row [H, 1, t + 1] is the relative-position
-    bias of the new query.  Same kernels, same order as _t5_attn_fwd on the whole prefix (whose last row this equals)."""
-    da = (pdrop, next_dropout_seed()) if pdrop > 0 else None
-    dh = (pdrop, next_dropout_seed()) if pdrop > 0 else None
+    bias of the new query.  Same kernels, same order as t5_attn_fwd on the whole prefix (whose last row this equals)."""
+    da, dh = dropout_pair(pdrop), dropout_pair(pdrop)
     n, _, _ = ln_fwd_raw(h2, P.ln, rms=True)
     D = n.shape[1]
     inner = P.w_o.shape[1]
@@ -1197,60 +1193,30 @@ def t5_self_attn_step(h2, B, P, bias_row, cache, t, pdrop=0.0):
     return y
 
 
-def _t5_attn_bwd(dy, saved, B, L, Ls, P, bias, causal, dbias, need_dh=True, need_dsrc=True):
+def _t5_attn_bwd(dy, saved, B, P, bias, causal, dbias, need_dh=True, need_dsrc=True):
     h2, rstd, n, proj, o, lse, src2, da, dh_drop = saved
     need_dh = need_dh or P.ln.weight.requires_grad  # the RMSNorm scale gradient comes out of the same kernel
-    D = n.shape[1]
-    inner = P.w_o.shape[1]
+    M, inner = h2.shape[0], o.shape[2]
     dyd = _drop_raw(dy, dh_drop)  # gradient of the (dropped) sub-layer output; the residual branch keeps dy itself
-    mm_wgrad(dyd, o.view(B * L, inner), inner, P.w_o)
-    dctx = mm_dgrad(dyd, P.w_o).view(B, L, inner)
-    dsrc = None
-    if src2 is None:
-        (qkv,) = proj
-        v3 = qkv.view(B, L, 3 * inner)
-        dqkv = torch.empty_like(qkv)
-        d3 = dqkv.view(B, L, 3 * inner)
-        attn_backward(v3[..., :inner], v3[..., inner:2 * inner], v3[..., 2 * inner:], o, lse, dctx, d3[..., :inner],
-                      d3[..., inner:2 * inner], d3[..., 2 * inner:], P.heads, None, bias, scale=1.0, causal=causal,
-                      d_pos_bias=dbias, dropout=da)
-        mm_wgrad(dqkv, n, D, P.w_qkv)
-        dn = mm_dgrad(dqkv, P.w_qkv) if need_dh else None
-    else:
-        q, kv = proj
-        kv3 = kv.view(B, Ls, 2 * inner)
-        dq = torch.empty_like(q)
-        dkv = torch.empty_like(kv)
-        dkv3 = dkv.view(B, Ls, 2 * inner)
-        attn_backward(q.view(B, L, inner), kv3[..., :inner], kv3[..., inner:], o, lse, dctx, dq.view(B, L, inner),
-                      dkv3[..., :inner], dkv3[..., inner:], P.heads, None, bias, scale=1.0, causal=causal,
-                      d_pos_bias=dbias, dropout=da)
-        mm_wgrad(dq, n, D, P.w_q)
-        mm_wgrad(dkv, src2, src2.shape[1], P.w_kv)
-        dn = mm_dgrad(dq, P.w_q) if need_dh else None
-        dsrc = mm_dgrad(dkv, P.w_kv) if need_dsrc else None
+    mm_wgrad(dyd, o.view(M, inner), inner, P.w_o)
+    dctx = mm_dgrad(dyd, P.w_o)
+    dn, dsrc = _attn_core_bwd(dctx, n, src2, proj, o, lse, B, P, pos_bias=bias, scale=1.0, causal=causal, dropout=da,
+                              d_pos_bias=dbias, need_dx=need_dh, need_dsrc=need_dsrc)
     dh = ln_bwd_raw(dn, h2, P.ln, None, rstd, dx_add=dy, rms=True) if need_dh else None
     return dh, dsrc
 
 
-def _t5_ff_fwd(h2, P, pdrop=0.0):
+def t5_ff_fwd(h2, P, pdrop=0.0):
     # HF T5DenseReluDense: wo(dropout(relu(wi(x)))); T5LayerFF: hidden + dropout(ff)
-    d1 = (pdrop, next_dropout_seed()) if pdrop > 0 else None
-    d2 = (pdrop, next_dropout_seed()) if pdrop > 0 else None
+    d1, d2 = dropout_pair(pdrop), dropout_pair(pdrop)
     n, _, rstd = ln_fwd_raw(h2, P.ln, rms=True)
-    M, D = n.shape
-    g, u = mm_nt(n, D, M, compute_weight(P.w1), act=ACT_RELU, want_preact=True, preact_grad=SAVE_DACT, dropout=d1)
-    y, _ = mm_nt(g, g.shape[1], M, compute_weight(P.w2), residual=h2, dropout=d2)
+    y, u, g = _ffn_core_fwd(n, P, ACT_RELU, h2, mid_drop=d1, out_drop=d2)
     return y, (h2, rstd, n, u, g, d1, d2)
 
 
 def _t5_ff_bwd(dy, saved, P):
     h2, rstd, n, u, g, d1, d2 = saved
-    dyd = _drop_raw(dy, d2)
-    mm_wgrad(dyd, g, g.shape[1], P.w2)                     # g is the dropped activation the forward multiplied by W2
-    du = mm_dgrad(dyd, P.w2, dact_aux=u, dact=ACT_MULAUX if SAVE_DACT else ACT_RELU, dropout=d1)
-    mm_wgrad(du, n, n.shape[1], P.w1)
-    dn = mm_dgrad(du, P.w1)
+    dn = _ffn_core_bwd(_drop_raw(dy, d2), n, u, g, P, ACT_RELU, mid_drop=d1)   # g: the dropped activation W2 multiplied
     return ln_bwd_raw(dn, h2, P.ln, None, rstd, dx_add=dy, rms=True)
 
 
@@ -1261,8 +1227,8 @@ class T5EncBlockFn(Function):
         h2 = h.contiguous().view(B * L, D)
         bias = pos_bias.detach() if pos_bias is not None else None
         pd = getattr(P, "pdrop", 0.0)
-        a, s1 = _t5_attn_fwd(h2, B, L, None, L, P.attn, bias, False, pd)
-        y, s2 = _t5_ff_fwd(a, P.ffn, pd)
+        a, s1 = t5_attn_fwd(h2, B, P.attn, bias, False, pd)
+        y, s2 = t5_ff_fwd(a, P.ffn, pd)
         ctx.saved = (s1, s2, bias)
         ctx.P, ctx.dims, ctx.n_anchor = P, (B, L, D), len(anchors)
         ctx.need_h = h.requires_grad
@@ -1276,7 +1242,7 @@ class T5EncBlockFn(Function):
         ctx.saved = None
         dbias = torch.zeros_like(bias) if ctx.need_bias else None
         da = _t5_ff_bwd(dy.contiguous().view(B * L, D), s2, ctx.P.ffn)
-        dh, _ = _t5_attn_bwd(da, s1, B, L, L, ctx.P.attn, bias, False, dbias, need_dh=ctx.need_h)
+        dh, _ = _t5_attn_bwd(da, s1, B, ctx.P.attn, bias, False, dbias, need_dh=ctx.need_h)
         return (None if dh is None else dh.view(B, L, D), dbias, None) + (None,) * ctx.n_anchor
 
 
@@ -1289,9 +1255,9 @@ class T5DecBlockFn(Function):
         enc2 = enc.contiguous().view(B * Ls, enc.shape[2])
         bias = pos_bias.detach() if pos_bias is not None else None
         pd = getattr(P, "pdrop", 0.0)
-        a, s1 = _t5_attn_fwd(h2, B, T, None, T, P.attn, bias, True, pd)
-        c, s2 = _t5_attn_fwd(a, B, T, enc2, Ls, P.cross, None, False, pd)
-        y, s3 = _t5_ff_fwd(c, P.ffn, pd)
+        a, s1 = t5_attn_fwd(h2, B, P.attn, bias, True, pd)
+        c, s2 = t5_attn_fwd(a, B, P.cross, None, False, pd, src2=enc2)
+        y, s3 = t5_ff_fwd(c, P.ffn, pd)
         ctx.saved = (s1, s2, s3, bias)
         ctx.P, ctx.dims, ctx.n_anchor = P, (B, T, Ls, D), len(anchors)
         ctx.need_h, ctx.need_enc = h.requires_grad, enc.requires_grad
@@ -1306,8 +1272,8 @@ class T5DecBlockFn(Function):
         P = ctx.P
         dbias = torch.zeros_like(bias) if ctx.need_bias else None
         dc = _t5_ff_bwd(dy.contiguous().view(B * T, D), s3, P.ffn)
-        da, denc = _t5_attn_bwd(dc, s2, B, T, Ls, P.cross, None, False, None, need_dsrc=ctx.need_enc)
-        dh, _ = _t5_attn_bwd(da, s1, B, T, T, P.attn, bias, True, dbias, need_dh=ctx.need_h)
+        da, denc = _t5_attn_bwd(dc, s2, B, P.cross, None, False, None, need_dsrc=ctx.need_enc)
+        dh, _ = _t5_attn_bwd(da, s1, B, P.attn, bias, True, dbias, need_dh=ctx.need_h)
         return (None if dh is None else dh.view(B, T, D), None if denc is None else denc.view(B, Ls, -1), dbias,
                 None) + (None,) * ctx.n_anchor
 

@@ -1,0 +1,195 @@
+"""The sequence of C-ABI calls a set of small workloads makes, as one SHA-256 per workload: two copies of the Python package
+that print the same digests drive the library identically (same entry points, same order, same shapes, strides, flags, seeds).
+   python tools/abi_trace.py [--pkg DIR] [--out FILE] [--only SUBSTR]
+Recorded per call: the entry point, every integer / float argument, null or set for every pointer, and for a descriptor passed
+by reference each of its fields the same way.  Addresses are never recorded.  --pkg DIR: import m3ae_amd from DIR (the
+`mm-vqa-healthcare_amd` directory of another checkout); --out FILE: the full trace, for `diff`."""
+import argparse
+import ctypes as C
+import hashlib
+import os
+import sys
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--pkg", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mm-vqa-healthcare_amd"))
+ap.add_argument("--out")
+ap.add_argument("--only", default="")
+args = ap.parse_args()
+sys.path.insert(0, os.path.abspath(args.pkg))
+import torch  # noqa: E402
+from m3ae_amd import _lib, ops, synth  # noqa: E402
+from m3ae_amd.config import tiny_config  # noqa: E402
+from m3ae_amd.modules import DecoderModel, M3AETransformerSS, T5VQA_MMEncoderInput  # noqa: E402
+
+TRACE = []
+
+
+def _ptr(v):
+    return "set" if getattr(v, "value", v) else "null"
+
+
+def _describe(name, argtypes, call_args):
+    parts = [name]
+    for t, a in zip(argtypes, call_args):
+        if issubclass(t, C._Pointer) and issubclass(t._type_, C.Structure):
+            d = a._obj   # byref(desc)
+            for f, ft in d._fields_:
+                assert ft is C.c_void_p or issubclass(ft, C._SimpleCData), f"{name}: field {f} is neither a pointer nor a scalar"
+                parts.append(f"{f}={_ptr(getattr(d, f)) if ft in (C.c_void_p, C.c_char_p) else getattr(d, f)}")
+        elif t is C.c_void_p or issubclass(t, C._Pointer):
+            parts.append(_ptr(a))
+        else:
+            parts.append(repr(a))
+    return " ".join(parts)
+
+
+class Recorder:
+    """Stands in for the loaded library: every entry point appends its call to TRACE, then runs."""
+
+    def __init__(self, real):
+        self._real = real
+
+    def __getattr__(self, name):
+        fn, argtypes = getattr(self._real, name), _lib._SIGS[name][1]
+
+        def call(*a):
+            TRACE.append(_describe(name, argtypes, a))
+            return fn(*a)
+        setattr(self, name, call)
+        return call
+
+
+def to_dev(batch):
+    return {k: v.cuda() if isinstance(v, torch.Tensor) else [t.cuda() for t in v] if isinstance(v, list) and isinstance(v[0], torch.Tensor)
+            else v for k, v in batch.items()}
+
+
+# the shapes of the GPU tests: two samples, 32 text tokens, 64 x 64 images; 768 wide fusion layers so that the fused
+# cross-attention sub-block covers them
+WIDE = dict(image_size=64, hidden_size=768, num_heads=12, input_image_embed_size=128, input_text_embed_size=128, vocab_size=1000,
+            vit_width=128, vit_layers=2, text_hidden=128, text_layers=1, text_heads=2, text_inter=512)
+PRETRAIN = dict(loss_names={"mlm": 1, "mim": 1, "itm": 1, "vqa": 0, "cls": 0, "irtr": 0}, mim_layer=1, mim_decoder_hidden_size=128,
+                mim_decoder_num_layers=2, mim_decoder_num_heads=2)
+T5_DIMS = dict(d_model=512, d_kv=64, d_ff=2048, num_layers=2, num_decoder_layers=2, num_heads=8)
+
+
+def batch(pretrain=False):
+    return to_dev(synth.synthetic_batch(2, text_len=32, image_size=64, vocab_size=1000, rank=0, pretrain=pretrain))
+
+
+def m3ae(mode, **over):
+    m = M3AETransformerSS(tiny_config(compute_dtype=mode, **over))
+    synth.fill_deterministic(m)
+    return m.finalize("cuda", mode)
+
+
+def cls_train(mode, xattn):
+    ops.XATTN, ops.XATTN_TRAIN_MIN_BATCH = xattn, 0
+    m = m3ae(mode, drop_rate=0.1, num_top_layer=2, **WIDE)
+    m.train()
+    m.store.zero_grad()
+    m.training_step(batch()).backward()
+    m.store.adamw_step(max_steps=100, lr_factor=1.0)
+
+
+def cls_eval(mode, attns, xattn):
+    ops.XATTN = xattn
+    m = m3ae(mode, num_top_layer=2, **WIDE)
+    m.eval()
+    with torch.no_grad():
+        m.infer(batch(), output_attentions=attns)
+
+
+def pretrain(mode):
+    ops.XATTN_TRAIN_MIN_BATCH = 0
+    m = m3ae(mode, drop_rate=0.1, **PRETRAIN)
+    m.train()
+    b = batch(pretrain=True)
+    b["itm_labels"] = torch.tensor([1.0, 0.0])
+    m.store.zero_grad()
+    m.training_step(b).backward()
+
+
+def t5(mode, enc_layers, dec_layers):
+    m = T5VQA_MMEncoderInput(tiny_config(compute_dtype=mode), t5_vocab=1100, t5_dims=T5_DIMS)
+    m.unfreeze_top_layers(enc_layers, dec_layers)
+    synth.fill_deterministic(m)
+    m.finalize("cuda", mode)
+    b = batch()
+    b["t5_labels"] = synth.det_randint("t5_labels", 2, 1100, (2, 6)).cuda()
+    return m, b
+
+
+def t5_train(mode, enc_layers, dec_layers):
+    m, b = t5(mode, enc_layers, dec_layers)
+    m.train()
+    m.store.zero_grad()
+    m.training_step(b)["loss"].backward()
+
+
+def t5_generate(mode):
+    m, b = t5(mode, 1, 1)
+    m.eval()
+    m.current_tasks, m.max_answer_length = [], 6
+    m(b)
+
+
+def decoder(mode):
+    m = DecoderModel(tiny_config(compute_dtype=mode, num_top_layer=1, mm_encoder_inputs_include_cls_feats=True,
+                                 mm_encoder_inputs_include_imagetext_feats=False, **WIDE), vocab_size=1200)
+    synth.fill_deterministic(m)
+    m.finalize("cuda", mode)
+    b = batch()
+    tok = synth.det_randint("decoder_tokens", 103, 1200, (2, 8))
+    tok[:, 0], tok[:, -1] = 101, 102
+    b["decoder_tokens"] = tok.cuda()
+    return m, b
+
+
+def dec_train(mode):
+    m, b = decoder(mode)
+    m.train()
+    m.store.zero_grad()
+    m.training_step(b)["loss"].backward()
+
+
+def dec_greedy(mode):
+    m, b = decoder(mode)
+    m.eval()
+    m.decoder.max_len = 8
+    m.decoder.search_path(m.features(b))
+
+
+XATTN = ("auto", "always", "off")
+WORKLOADS = [("cls_train_xattn_" + x, lambda mode, x=x: cls_train(mode, x)) for x in XATTN] + [
+    ("cls_eval_xattn_" + x, lambda mode, x=x: cls_eval(mode, False, x)) for x in XATTN] + [
+    ("cls_eval_attention_maps_xattn_" + x, lambda mode, x=x: cls_eval(mode, True, x)) for x in XATTN] + [
+    ("pretrain", pretrain),
+    ("t5_train", lambda mode: t5_train(mode, 1, 1)),
+    ("t5_train_position_bias", lambda mode: t5_train(mode, 4, 4)),     # every block trainable, the bias table with them
+    ("t5_train_frozen_below", lambda mode: t5_train(mode, 0, 1)),       # no input / encoder-side gradient asked of the top block
+    ("t5_generate", t5_generate),
+    ("dec_train", dec_train),
+    ("dec_greedy", dec_greedy),
+]
+
+_lib.lib()
+_lib._lib = Recorder(_lib._lib)
+defaults = (ops.XATTN, ops.XATTN_TRAIN_MIN_BATCH)
+out = open(args.out, "w") if args.out else None
+print("# m3ae_amd from", os.path.relpath(os.path.dirname(ops.__file__)), flush=True)
+for name, run in WORKLOADS:
+    for mode in ("bf16", "fp32", "fp32x3"):
+        tag = f"{name}[{mode}]"
+        if args.only not in tag:
+            continue
+        del TRACE[:]
+        ops.XATTN, ops.XATTN_TRAIN_MIN_BATCH = defaults
+        ops.set_dropout_seed(1)
+        torch.manual_seed(0)
+        run(mode)
+        torch.cuda.synchronize()
+        text = "\n".join(TRACE)
+        print(f"{hashlib.sha256(text.encode()).hexdigest()}  {tag}  ({len(TRACE)} calls)", flush=True)
+        if out:
+            out.write(f"## {tag}\n{text}\n")
