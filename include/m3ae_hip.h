@@ -30,6 +30,8 @@ extern "C" {
  *    m3ae_dropout take it as an argument: an optional DEVICE pointer to a 32-bit value the kernels fold into the mask key, so a
  *    step captured in a hipGraph (kernel arguments frozen, seeds included) draws new masks at every replay once the caller bumps
  *    that value; m3ae_adamw takes `hyper_dev` (device {lr, step size} of the step) for the same reason. */
+/* 4 (additive): deterministic mode.  M3AE_GEMM_DETERMINISTIC + m3ae_gemm_det / m3ae_gemm_det_workspace_bytes (ordered split-K of the
+ *    wgrad kernels) and the *_det forms of the small reductions, all taking a caller-owned workspace; no descriptor changed. */
 /* 4: attention maps.  m3ae_attn_probs (the probabilities of an m3ae_attn_fwd call, recomputed from its log-sum-exp table) and
  *    m3ae_xattn_probs_export (the probabilities a fused cross-attention call left in `probs` / `probs_drop`), both as fp32
  *    [B][H][Lq][Lk]; no descriptor changed. */
@@ -64,7 +66,9 @@ const char* m3ae_last_gemm_path(void);
  * (A = dY^T) that is the bias gradient, so no separate column-sum pass over dY is needed.
  * Dispatch: bf16 A,B with K-contiguous operands (a_sk == b_sk == 1) -> MFMA "NT" kernel;
  *           bf16 A,B with reduction-strided operands (a_sm == b_sn == 1), fp32 C, accumulate -> MFMA "TN" (wgrad)
- *           kernel with split-K fp32 atomics; anything else (fp32 operands, odd shapes, batched) -> generic kernel;
+ *           kernel, split over the reduction: the splits are added into C with fp32 atomics (m3ae_gemm: the order of arrival
+ *           decides the rounding), or written as partial tiles to a workspace and folded in ascending split order
+ *           (m3ae_gemm_det, deterministic mode); anything else (fp32 operands, odd shapes, batched) -> generic kernel;
  *           fp32 A, B, C with launch_flags & M3AE_GEMM_F32_X3 (and not force_generic) -> fp32x3 kernel, any layout.
  */
 typedef struct {
@@ -95,12 +99,14 @@ typedef struct {
     const void* dropout_salt; /* NULL, or device uint32: folded into the dropout mask key at kernel entry (ABI 3, above) */
 } m3ae_gemm_desc;
 enum { M3AE_GEMM_NO_PERSISTENT = 1,
-       M3AE_GEMM_F32_X3 = 2   /* fp32x3 mode (ABI 4, additive): fp32 A, B and C run csrc/gemm_f32x3.hip, which splits every operand
+       M3AE_GEMM_F32_X3 = 2,  /* fp32x3 mode (ABI 4, additive): fp32 A, B and C run csrc/gemm_f32x3.hip, which splits every operand
                                * element into bf16 hi + lo and forms a_hi b_hi + a_hi b_lo + a_lo b_hi on the bf16 MFMA with fp32
                                * accumulation: |C - C_exact| <= 3 (2^-16 + K 2^-23) (|A||B|)_mn before the epilogue, which is
                                * gemm_generic's.  The whole descriptor contract holds (strides, batches, every epilogue, dropout
                                * masks, a_rowsum over the fp32 A values); m3ae_last_gemm_path() = "f32x3".  force_generic wins;
-                               * with bf16 operands or output the call returns M3AE_ERR_UNSUPPORTED. */ };
+                               * with bf16 operands or output the call returns M3AE_ERR_UNSUPPORTED. */
+       M3AE_GEMM_DETERMINISTIC = 4 /* deterministic mode (ABI 4, additive): no fp32 atomics.  Only m3ae_gemm_det accepts it (it needs a
+                               * workspace); m3ae_gemm returns M3AE_ERR_UNSUPPORTED rather than run the atomic kernels. */ };
 /* Diagnostic selectors in launch_flags (0 in the product path = kernel chosen by shape): tests pin the kernel variants
  * per call to compare them bit for bit, tools time them against each other.  The library keeps no tuning state.
  *   NT variant v: 0 = 128x128 tile, 4 = 256x256 2-stage, 7 = 256x256 ping-pong, 8 = its persistent form;
@@ -112,6 +118,18 @@ enum { M3AE_GEMM_NO_PERSISTENT = 1,
 #define M3AE_GEMM_TN_VARIANT(v) ((((v) + 1) & 0xf) << 12)
 #define M3AE_GEMM_COL_GROUP(g) (((g) & 0xf) << 16)
 int m3ae_gemm(const m3ae_gemm_desc* d, void* stream);
+/* Deterministic mode of the TN (wgrad) family: the same kernels, tiles, split-K fan-out and accumulation order inside a split
+ * (M3AE_GEMM_TN_VARIANT pins them as before), but every (tile, split) workgroup stores its fp32 accumulators -- and its partial
+ * a_rowsum rows -- to `workspace` with 16-byte stores, and a streaming kernel behind it performs, with one writer per element,
+ *     C (+)= alpha * (((p_0 + p_1) + p_2) + ...)        a_rowsum += ((r_0 + r_1) + ...)          in ascending split index.
+ * Two calls with the same descriptor contents therefore give the same bits, whatever else runs on the device.
+ * m3ae_gemm_det_workspace_bytes: bytes m3ae_gemm_det needs for this descriptor (splits * (M * N + M) fp32); 0 if the descriptor
+ *   does not dispatch to the TN family (every other family has one writer per output element: call m3ae_gemm with the flag clear).
+ *   Reads shapes, strides, dtypes, flags and the alignment of the pointers that are set; touches no device.
+ * m3ae_gemm_det: launch_flags must carry M3AE_GEMM_DETERMINISTIC; M3AE_ERR_UNSUPPORTED for a descriptor whose size query is 0,
+ *   M3AE_ERR_WORKSPACE for a missing, misaligned (16 B) or short workspace.  m3ae_last_gemm_path() = "mfma_tn". */
+int64_t m3ae_gemm_det_workspace_bytes(const m3ae_gemm_desc* d);
+int m3ae_gemm_det(const m3ae_gemm_desc* d, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Scaled-dot-product attention, forward and backward (flash-style in bf16, materialised in fp32).
@@ -374,6 +392,40 @@ int m3ae_mim_loss_fwd(const void* x, const float* target, const float* mask, flo
                       int64_t D, int dtype, void* stream);
 int m3ae_mim_loss_bwd(const void* x, const float* target, const float* mask, const float* acc, const float* gout, void* dx,
                       int64_t B, int64_t L, int64_t D, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Deterministic mode: ordered forms of the reductions that more than one workgroup feeds.  Same arguments and results as the
+ * entry points they are named after (which keep their kernels and their fp32 atomics), plus a caller-owned workspace where
+ * noted: every workgroup stores its partial to a workspace row of its own and a second kernel adds the rows in an order
+ * that depends on the shapes alone.  m3ae_det_workspace_bytes(op, rows, cols) gives the size (touches no device):
+ *   M3AE_DET_COLSUM (M, N); M3AE_DET_EMBED_BWD (B * S, D); M3AE_DET_BCE (B, C); M3AE_DET_XENT (rows, C) -- this workspace
+ *   replaces m3ae_xent's float[1]; M3AE_DET_MIM (B * L, D).
+ * m3ae_layernorm_bwd_det / _drop_det: the dgamma / dbeta fold walks all partial rows of `workspace` (sized as for
+ *   m3ae_layernorm_bwd) in one workgroup per 32 columns.
+ * m3ae_roberta_embed_bwd_det: the first token that carries a word id (position id) owns that table row and adds the rows of
+ *   all tokens with the same id in ascending token order, then adds the sum into the table: no atomics, any duplicates.
+ *   D <= 2048.
+ */
+enum { M3AE_DET_COLSUM = 0, M3AE_DET_EMBED_BWD = 1, M3AE_DET_BCE = 2, M3AE_DET_XENT = 3, M3AE_DET_MIM = 4 };
+int64_t m3ae_det_workspace_bytes(int op, int64_t rows, int64_t cols);
+int m3ae_colsum_det(const void* x, float* out, int64_t M, int64_t N, int64_t ldx, int dtype, int accumulate, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+int m3ae_layernorm_bwd_det(const void* dy, const void* x, const float* gamma, const float* beta, const float* mean,
+                           const float* rstd, void* dx, const void* dx_add, float* dgamma, float* dbeta, float* workspace,
+                           int64_t M, int64_t D, int dtype, int act, int rms, void* stream);
+int m3ae_layernorm_bwd_drop_det(const void* dy, const void* x, const float* gamma, const float* beta, const float* mean,
+                                const float* rstd, void* dx, void* dx_drop, float dropout_p, uint64_t dropout_seed,
+                                const void* dropout_salt, float* dgamma, float* dbeta, float* workspace, int64_t M, int64_t D,
+                                int dtype, void* stream);
+int m3ae_roberta_embed_bwd_det(const int64_t* ids, const void* d_out, float* d_word, float* d_pos, float* d_type, int64_t B,
+                               int64_t S, int64_t D, int64_t pad_id, int dtype, void* workspace, int64_t workspace_bytes,
+                               void* stream);
+int m3ae_bce_logits_det(const void* logits, const float* targets, float* loss, void* d_logits, int64_t B, int64_t C,
+                        float grad_scale, int dtype, void* workspace, int64_t workspace_bytes, void* stream);
+int m3ae_xent_det(const void* logits, const int64_t* labels, float* loss, void* d_logits, int64_t rows, int64_t C, int64_t ld,
+                  float grad_scale, int dtype, void* workspace, int64_t workspace_bytes, void* stream);
+int m3ae_mim_loss_fwd_det(const void* x, const float* target, const float* mask, float* acc, float* loss, int64_t B, int64_t L,
+                          int64_t D, int dtype, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* self-test of hardware idioms the kernels rely on (MFMA fragment maps, ds_read_b64_tr_b16, accumulator-as-
  * operand k-order).  out: int32[8 + 256] device buffer (tail = scratch), out[0] = number of mismatches. */

@@ -4,7 +4,8 @@
 //        transposed bf16 weight shadow), both operands K-contiguous.
 //   TN : C[N1,N2] += alpha * A[Mr,N1]^T . B[Mr,N2] -- wgrad (dY^T . X): the reduction runs over the ROWS of both
 //        operands, so MFMA fragments are fetched with the hardware transposing LDS read ds_read_b64_tr_b16;
-//        split over the reduction with fp32 atomics into the (fp32) gradient buffer.
+//        split over the reduction with fp32 atomics into the (fp32) gradient buffer, or (deterministic mode, m3ae_gemm_det)
+//        with partial tiles in a workspace that a streaming kernel folds in ascending split order.
 //
 // Structure (both): 128x128 output tile per 256-thread workgroup (4 waves as 2x2, 64x64 per wave = 4x4 MFMA
 // 16x16x32 tiles, 64 fp32 accumulators/lane), 64-deep reduction step, operands staged global->LDS with
@@ -122,7 +123,12 @@ __global__ __launch_bounds__((BM_ / WM) * (BN_ / 64) * 64, 2) void gemm_nt_bf16_
 // ---------------------------------------------------------------------------------------------------------
 // C[n1][n2] (+)= alpha * sum_r A[r][n1] * B[r][n2];  a.M = N1, a.N = N2, a.K = reduction rows.
 // BM_ x BN_ output tile, one WM x 64 sub-tile per wave, 64 reduction rows per step, 2-stage ring.
-template <int BM_, int BN_, int WM, int BKR, int NST>
+// DET (deterministic mode, M3AE_GEMM_DETERMINISTIC): the workgroup of (tile, split) stores its raw fp32 accumulators -- and its
+// partial a_rowsum rows -- into the caller's workspace instead of adding them into C with atomics: a.C / a.a_rowsum then point
+// at the partial planes, laid out in accumulator order ([split][tile][wave][i][j][lane] f32x4: every store instruction of a
+// wave writes 1 KiB of consecutive bytes), and tn_det_fold_kernel sums the planes in ascending split order.  The main loop is
+// the same code, so the order of accumulation inside a split is the atomic form's.
+template <int BM_, int BN_, int WM, int BKR, int NST, bool DET = false>
 __global__ __launch_bounds__((BM_ / WM) * (BN_ / 64) * 64, 2) void gemm_tn_bf16_kernel(MfmaArgs a) {
     constexpr int WAVES_N = BN_ / 64, NWAVES = (BM_ / WM) * WAVES_N, MI = WM / 16;
     constexpr int A_BYTES = BM_ * BKR * 2, ST_BYTES = (BM_ + BN_) * BKR * 2;
@@ -206,6 +212,19 @@ __global__ __launch_bounds__((BM_ / WM) * (BN_ / 64) * 64, 2) void gemm_tn_bf16_
         asm volatile("" ::: "memory");
         cur_s = cur_s + 1 == NST ? 0 : cur_s + 1;
         nxt_s = nxt_s + 1 == NST ? 0 : nxt_s + 1;
+    }
+    if constexpr (DET) {
+        if (do_rowsum && (lane & 15) == 0) {
+            float* rs = a.a_rowsum + (int64_t)split * a.M + m0 + wr * WM + 4 * (lane >> 4);
+#pragma unroll
+            for (int i = 0; i < MI; ++i) *(f32x4*)(rs + i * 16) = rsum[i];
+        }
+        float* P = (float*)a.C + ((int64_t)split * tiles + tile_id) * (BM_ * BN_) + ((int64_t)wave * MI * 4 * 64 + lane) * 4;
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) *(f32x4*)(P + (i * 4 + j) * 256) = acc[i][j];
+        return;
     }
     if (do_rowsum && (lane & 15) == 0) {
 #pragma unroll
@@ -768,6 +787,7 @@ extern "C" int m3ae_tn_trace_dump(uint64_t* out) {
 #else
 #define TN_STAMP(k) do { } while (0)
 #endif
+template <bool DET>   // DET: partial planes instead of atomics, see gemm_tn_bf16_kernel
 __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(MfmaArgs a) {
     constexpr int CK = 32, NW = 8, A_BYTES = 256 * CK * 2, SLOT = 2 * A_BYTES;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -900,6 +920,19 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(MfmaArgs a) {
     }
     if (wr == 0) { __builtin_amdgcn_s_barrier(); PP_FENCE(); }
 
+    if constexpr (DET) {
+        if (do_rowsum && (lane & 15) == 0) {
+            float* rs = a.a_rowsum + (int64_t)split * a.M + m0 + wr * 128 + 4 * (lane >> 4);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) *(f32x4*)(rs + i * 16) = rsum[i];
+        }
+        float* P = (float*)a.C + ((int64_t)split * tiles + tile_id) * (256 * 256) + ((int64_t)wave * 8 * 4 * 64 + lane) * 4;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) *(f32x4*)(P + (i * 4 + j) * 256) = acc[i][j];
+        return;
+    }
     if (do_rowsum && (lane & 15) == 0) {
 #pragma unroll
         for (int i = 0; i < 8; ++i)
@@ -929,8 +962,46 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(MfmaArgs a) {
             }
 }
 
-static int launch_tn_pp(MfmaArgs a, const m3ae_gemm_desc& d, hipStream_t s) {
-    constexpr int lds = 4 * (256 + 256) * 32 * 2;
+// Deterministic mode: fold the partial planes the DET kernels wrote (accumulator order, see gemm_tn_bf16_kernel) into C in
+// ASCENDING SPLIT ORDER, one thread per accumulator quad (16 B per lane and plane, consecutive lanes consecutive bytes), and
+// the partial a_rowsum rows into a_rowsum:  C (+)= alpha * (((p_0 + p_1) + p_2) + ...).  One writer per output element.
+__global__ __launch_bounds__(256) void tn_det_fold_kernel(const float* __restrict__ part, const float* __restrict__ rs_part,
+                                                          float* __restrict__ C, float* __restrict__ rowsum, int64_t ldc,
+                                                          int64_t M, int64_t N, int splits, int bm, int wm, float alpha,
+                                                          int accumulate) {
+    const int64_t plane = M * N, quads = plane / 4;
+    const int waves_n = bm / 64, mi = wm / 16;           // square tiles: bm x bm, one wm x 64 sub-tile per wave
+    const int64_t tile_quads = (int64_t)bm * bm / 4, tiles_n = N / bm;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < quads; e += stride) {
+        f32x4 v = *(const f32x4*)(part + e * 4);
+#pragma unroll 4
+        for (int sp = 1; sp < splits; ++sp) {
+            const f32x4 p = *(const f32x4*)(part + sp * plane + e * 4);
+            v[0] += p[0]; v[1] += p[1]; v[2] += p[2]; v[3] += p[3];
+        }
+        const int64_t tile = e / tile_quads;
+        const int w = (int)(e - tile * tile_quads);
+        const int lane = w & 63, j = (w >> 6) & 3, i = (w >> 8) % mi, wave = (w >> 8) / mi;
+        const int64_t n1 = (tile / tiles_n) * bm + (wave / waves_n) * wm + i * 16 + 4 * (lane >> 4);
+        const int64_t n2 = (tile % tiles_n) * bm + (wave % waves_n) * 64 + j * 16 + (lane & 15);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float* p = C + (n1 + r) * ldc + n2;
+            *p = accumulate ? *p + v[r] * alpha : v[r] * alpha;
+        }
+    }
+    if (rowsum) {
+        for (int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; m < M; m += stride) {
+            float t = rs_part[m];
+            for (int sp = 1; sp < splits; ++sp) t += rs_part[sp * M + m];
+            rowsum[m] += t;
+        }
+    }
+}
+
+// split-K fan-out of the 256 x 256 ping-pong TN kernel
+static int64_t tn_pp_splits(const m3ae_gemm_desc& d, int64_t* k_chunk) {
     const int64_t tiles = (d.M / 256) * (d.N / 256);
     const int64_t ksteps = cdiv(d.K, 64);
     int64_t splits = 256 / tiles;  // one workgroup per CU, one round
@@ -938,23 +1009,51 @@ static int launch_tn_pp(MfmaArgs a, const m3ae_gemm_desc& d, hipStream_t s) {
     if (splits < 1) splits = 1;
     if (!d.accumulate) splits = 1;
     const int64_t steps_per = cdiv(ksteps, splits);
-    a.k_chunk = steps_per * 64;
-    splits = cdiv(ksteps, steps_per);
-    a.splits = (int)splits;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_pp_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(gemm_tn_pp_kernel, dim3((unsigned)(tiles * splits)), dim3(512), lds, s, a);
+    *k_chunk = steps_per * 64;
+    return cdiv(ksteps, steps_per);
+}
+
+// the partial planes of a deterministic call: [splits][M * N] accumulators, then [splits][M] a_rowsum rows
+static int64_t tn_det_bytes(const m3ae_gemm_desc& d, int64_t splits) { return splits * (d.M * d.N + d.M) * (int64_t)sizeof(float); }
+
+static int tn_det_fold(const MfmaArgs& part, const m3ae_gemm_desc& d, int bm, int wm, hipStream_t s) {
+    int64_t grid = cdiv(d.M * d.N / 4, 256);
+    if (grid > 8192) grid = 8192;
+    hipLaunchKernelGGL(tn_det_fold_kernel, dim3((unsigned)grid), dim3(256), 0, s, (const float*)part.C, part.a_rowsum, (float*)d.C,
+                       d.a_rowsum, d.c_sm, d.M, d.N, part.splits, bm, wm, d.alpha, d.accumulate);
     return hip_launch_status();
 }
 
-template <int BM_, int BN_, int WM, int BKR, int NST>
-static int launch_tn_t(MfmaArgs a, const m3ae_gemm_desc& d, hipStream_t s) {
-    constexpr int lds = NST * (BM_ + BN_) * BKR * 2;
-    constexpr int threads = (BM_ / WM) * (BN_ / 64) * 64;
-    const int64_t tiles = (d.M / BM_) * (d.N / BN_);
+// det_ws != nullptr: deterministic mode (M3AE_GEMM_DETERMINISTIC), the caller's workspace of tn_det_bytes(d, splits) bytes
+static int launch_tn_pp(MfmaArgs a, const m3ae_gemm_desc& d, hipStream_t s, float* det_ws = nullptr) {
+    constexpr int lds = 4 * (256 + 256) * 32 * 2;
+    const int64_t tiles = (d.M / 256) * (d.N / 256);
+    const int64_t splits = tn_pp_splits(d, &a.k_chunk);
+    a.splits = (int)splits;
+    if (det_ws) {
+        a.C = det_ws;
+        a.a_rowsum = d.a_rowsum ? det_ws + splits * d.M * d.N : nullptr;
+        static bool det_attr_set = false;
+        if (!det_attr_set) {
+            hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_pp_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            det_attr_set = true;
+        }
+        hipLaunchKernelGGL(gemm_tn_pp_kernel<true>, dim3((unsigned)(tiles * splits)), dim3(512), lds, s, a);
+        const int rc = hip_launch_status();
+        return rc ? rc : tn_det_fold(a, d, 256, 128, s);
+    }
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_pp_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(gemm_tn_pp_kernel<false>, dim3((unsigned)(tiles * splits)), dim3(512), lds, s, a);
+    return hip_launch_status();
+}
+
+// split-K fan-out of the 128 x 128 TN kernels (lds = their LDS bytes)
+static int64_t tn_t_splits(const m3ae_gemm_desc& d, int lds, int64_t* k_chunk) {
+    const int64_t tiles = (d.M / 128) * (d.N / 128);
     const int64_t ksteps = cdiv(d.K, 64);
 #ifdef M3AE_EXP_TN_TARGET   // timing experiment: split-K fan-out of the 128 x 128 kernel (workgroups per launch)
     const int64_t target = M3AE_EXP_TN_TARGET;
@@ -973,9 +1072,32 @@ static int launch_tn_t(MfmaArgs a, const m3ae_gemm_desc& d, hipStream_t s) {
     if (splits < 1) splits = 1;
     if (!d.accumulate) splits = 1;
     const int64_t steps_per = cdiv(ksteps, splits);
-    a.k_chunk = steps_per * 64;
-    splits = cdiv(ksteps, steps_per);
+    *k_chunk = steps_per * 64;
+    return cdiv(ksteps, steps_per);
+}
+
+template <int BM_, int BN_, int WM, int BKR, int NST>
+static int launch_tn_t(MfmaArgs a, const m3ae_gemm_desc& d, hipStream_t s, float* det_ws = nullptr) {
+    static_assert(BM_ == 128 && BN_ == 128, "tn_t_splits and tn_det_fold assume the 128 x 128 tile");
+    constexpr int lds = NST * (BM_ + BN_) * BKR * 2;
+    constexpr int threads = (BM_ / WM) * (BN_ / 64) * 64;
+    const int64_t tiles = (d.M / BM_) * (d.N / BN_);
+    const int64_t splits = tn_t_splits(d, lds, &a.k_chunk);
     a.splits = (int)splits;
+    if (det_ws) {
+        a.C = det_ws;
+        a.a_rowsum = d.a_rowsum ? det_ws + splits * d.M * d.N : nullptr;
+        static bool det_attr_set = false;
+        if (!det_attr_set) {
+            hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel<BM_, BN_, WM, BKR, NST, true>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+            det_attr_set = true;
+        }
+        hipLaunchKernelGGL((gemm_tn_bf16_kernel<BM_, BN_, WM, BKR, NST, true>), dim3((unsigned)(tiles * splits)), dim3(threads),
+                           lds, s, a);
+        const int rc = hip_launch_status();
+        return rc ? rc : tn_det_fold(a, d, BM_, WM, s);
+    }
     static bool attr_set = false;
     if (!attr_set) {
         hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel<BM_, BN_, WM, BKR, NST>,
@@ -987,18 +1109,12 @@ static int launch_tn_t(MfmaArgs a, const m3ae_gemm_desc& d, hipStream_t s) {
     return hip_launch_status();
 }
 
-static int launch_tn(const m3ae_gemm_desc& d, hipStream_t s) {
-    // C[M=N1][N=N2] += alpha * sum_k A[m][k] B[k][n] with a_sm == 1 (A stored [K][N1]) and b_sn == 1
-    MfmaArgs a{};
-    a.A = (const bf16_t*)d.A; a.lda = d.a_sk;
-    a.B = (const bf16_t*)d.B; a.ldb = d.b_sk;
-    a.C = d.C; a.ldc = d.c_sm;
-    a.M = d.M; a.N = d.N; a.K = d.K;
-    a.c_f32 = 1; a.alpha = d.alpha; a.accumulate = d.accumulate; a.a_rowsum = d.a_rowsum;
+// which TN kernel a descriptor takes: 5 = 256 x 256 ping-pong, 2 = 128 x 128 with 32-row steps, 0 = with 64-row steps
+static int tn_kernel_choice(const m3ae_gemm_desc& d) {
     // variant 1: 256x256 tile, 8 waves x (128x64): half the operand re-read traffic of the 128x128 tile
     const bool pp_ok = d.M % 256 == 0 && d.N % 256 == 0 && d.K >= 4096;
     const int g_tn_variant = ((d.launch_flags >> 12) & 0xf) - 1;
-    if (g_tn_variant == 5 && pp_ok) return launch_tn_pp(a, d, s);
+    if (g_tn_variant == 5 && pp_ok) return 5;
     if (g_tn_variant < 0 || g_tn_variant == 6) {
         // auto (default).  Re-measured in round 4 after both kernels' LDS-DMA moved to inline asm (mfma_tiles.h: the 128 x 128 kernel
         // gained as much as the ping-pong one): the 256 x 256 ping-pong kernel wins on the 768 x 3072 / 3072 x 768 outputs from 65536
@@ -1007,11 +1123,25 @@ static int launch_tn(const m3ae_gemm_desc& d, hipStream_t s) {
         // (profiles/r04_tn_kernel_choice_by_batch.log).  Variant 6 = the rule of rounds 1-3, kept for A/B runs.
         const bool r3_rule = pp_ok && (d.K >= 65536 || (d.K >= 32768 && d.M * d.N >= 768 * 3072));
         const bool r4_rule = pp_ok && d.K >= 65536 && d.M * d.N >= 768 * 3072;
-        if (g_tn_variant == 6 ? r3_rule : r4_rule) return launch_tn_pp(a, d, s);
-        return launch_tn_t<128, 128, 64, 32, 2>(a, d, s);
+        if (g_tn_variant == 6 ? r3_rule : r4_rule) return 5;
+        return 2;
     }
-    if (g_tn_variant == 2) return launch_tn_t<128, 128, 64, 32, 2>(a, d, s);  // 32 KiB LDS: 3 workgroups / CU
-    return launch_tn_t<128, 128, 64, 64, 2>(a, d, s);
+    if (g_tn_variant == 2) return 2;  // 32 KiB LDS: 3 workgroups / CU
+    return 0;
+}
+
+static int launch_tn(const m3ae_gemm_desc& d, hipStream_t s, float* det_ws = nullptr) {
+    // C[M=N1][N=N2] += alpha * sum_k A[m][k] B[k][n] with a_sm == 1 (A stored [K][N1]) and b_sn == 1
+    MfmaArgs a{};
+    a.A = (const bf16_t*)d.A; a.lda = d.a_sk;
+    a.B = (const bf16_t*)d.B; a.ldb = d.b_sk;
+    a.C = d.C; a.ldc = d.c_sm;
+    a.M = d.M; a.N = d.N; a.K = d.K;
+    a.c_f32 = 1; a.alpha = d.alpha; a.accumulate = d.accumulate; a.a_rowsum = d.a_rowsum;
+    const int k = tn_kernel_choice(d);
+    if (k == 5) return launch_tn_pp(a, d, s, det_ws);
+    if (k == 2) return launch_tn_t<128, 128, 64, 32, 2>(a, d, s, det_ws);
+    return launch_tn_t<128, 128, 64, 64, 2>(a, d, s, det_ws);
 }
 
 #ifdef M3AE_NT_TRACE
@@ -1024,6 +1154,9 @@ extern "C" int m3ae_gemm(const m3ae_gemm_desc* dp, void* stream) {
     if (!dp || !dp->A || !dp->B || !dp->C) return M3AE_ERR_ARG;
     const m3ae_gemm_desc& d = *dp;
     if (d.M <= 0 || d.N <= 0 || d.K <= 0 || d.batch1 <= 0 || d.batch2 <= 0) return M3AE_ERR_ARG;
+    // deterministic mode needs a workspace for its partial planes: m3ae_gemm_det takes one, this call cannot, and it never
+    // runs the atomic kernels under that flag
+    if (d.launch_flags & M3AE_GEMM_DETERMINISTIC) return M3AE_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     if ((d.launch_flags & M3AE_GEMM_F32_X3) && !d.force_generic) {   // fp32x3 mode (csrc/gemm_f32x3.hip): fp32 operands only
         if (d.dtype_a != M3AE_F32 || d.dtype_b != M3AE_F32 || d.dtype_c != M3AE_F32) return M3AE_ERR_UNSUPPORTED;
@@ -1052,4 +1185,43 @@ extern "C" int m3ae_gemm(const m3ae_gemm_desc* dp, void* stream) {
     }
     g_last_path = "generic";
     return m3ae_gemm_generic(d, s);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Deterministic mode (M3AE_GEMM_DETERMINISTIC): the TN kernels with ordered split-K.  tn_takes() repeats m3ae_gemm's dispatch
+// conditions for the "mfma_tn" family (pointers are checked only where given, so the size query needs no device).
+// ---------------------------------------------------------------------------------------------------------
+static bool tn_takes(const m3ae_gemm_desc& d) {
+    if (d.M <= 0 || d.N <= 0 || d.K <= 0 || d.batch1 != 1 || d.batch2 != 1) return false;
+    if ((d.launch_flags & M3AE_GEMM_F32_X3) && !d.force_generic) return false;
+    if (d.dtype_a != M3AE_BF16 || d.dtype_b != M3AE_BF16 || d.force_generic || d.c_sn != 1) return false;
+    const bool ptr_ok = aligned16(d.A) && aligned16(d.B) && aligned16(d.C) && (!d.preact || aligned16(d.preact)) &&
+                        (!d.residual || aligned16(d.residual)) && (!d.dact_aux || aligned16(d.dact_aux)) &&
+                        (!d.bias || aligned16(d.bias));
+    if (!ptr_ok) return false;
+    if (!d.a_rowsum && d.a_sk == 1 && d.b_sk == 1 && d.K % BK == 0 && d.N % 4 == 0 && d.a_sm % 8 == 0 && d.b_sn % 8 == 0 &&
+        d.c_sm % 4 == 0)
+        return false;   // the NT family comes first
+    return d.a_sm == 1 && d.b_sn == 1 && d.dtype_c == M3AE_F32 && d.M % BM == 0 && d.N % BN == 0 && d.a_sk % 8 == 0 &&
+           d.b_sk % 8 == 0 && !d.bias && d.act == M3AE_ACT_NONE && !d.preact && !d.residual && !d.dact_aux;
+}
+
+extern "C" int64_t m3ae_gemm_det_workspace_bytes(const m3ae_gemm_desc* dp) {
+    if (!dp) return M3AE_ERR_ARG;
+    const m3ae_gemm_desc& d = *dp;
+    if (!tn_takes(d)) return 0;   // every other kernel family has one writer per output element already
+    int64_t k_chunk = 0;
+    const int k = tn_kernel_choice(d);
+    const int64_t splits = k == 5 ? tn_pp_splits(d, &k_chunk) : tn_t_splits(d, k == 2 ? 2 * 256 * 32 * 2 : 2 * 256 * 64 * 2, &k_chunk);
+    return tn_det_bytes(d, splits);
+}
+
+extern "C" int m3ae_gemm_det(const m3ae_gemm_desc* dp, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!dp || !dp->A || !dp->B || !dp->C) return M3AE_ERR_ARG;
+    const m3ae_gemm_desc& d = *dp;
+    if (!(d.launch_flags & M3AE_GEMM_DETERMINISTIC)) return M3AE_ERR_ARG;
+    if (!tn_takes(d)) return M3AE_ERR_UNSUPPORTED;   // (such a descriptor needs no ordered form: plain m3ae_gemm, flag clear)
+    if (!workspace || !aligned16(workspace) || workspace_bytes < m3ae_gemm_det_workspace_bytes(dp)) return M3AE_ERR_WORKSPACE;
+    g_last_path = "mfma_tn";
+    return launch_tn(d, (hipStream_t)stream, (float*)workspace);
 }

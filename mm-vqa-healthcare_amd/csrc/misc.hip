@@ -322,6 +322,219 @@ __global__ __launch_bounds__(256) void xent_kernel(const T* x, const int64_t* la
     }
 }
 
+// ---- deterministic mode: ordered forms of the reductions above ---------------------------------------------------------
+// Every workgroup stores its partial into a workspace row of its own instead of adding it with an atomic; det_fold_kernel
+// then sums the rows in an order that depends on the row count alone.  One writer per output element.
+//
+// out[i] (+)= scale * sum_b part[b][i], i < n (out1 != nullptr: columns >= n0 go to out1[i - n0]).  CL column lanes x
+// (256 / CL) row lanes per workgroup: row lane r adds rows r, r + RL, r + 2 RL, ... in ascending order, lane 0 adds the RL
+// lane sums in ascending order.
+template <int CL>
+__global__ __launch_bounds__(256) void det_fold_kernel(const float* __restrict__ part, float* __restrict__ out0,
+                                                       float* __restrict__ out1, int64_t count, int64_t n, int64_t n0,
+                                                       float scale, int accumulate) {
+    constexpr int RL = 256 / CL;
+    __shared__ float red[RL][CL + 1];
+    const int cl = threadIdx.x % CL, rl = threadIdx.x / CL;
+    const int64_t i = (int64_t)blockIdx.x * CL + cl;
+    float s = 0.f;
+    if (i < n)
+        for (int64_t b = rl; b < count; b += RL) s += part[b * n + i];
+    red[rl][cl] = s;
+    __syncthreads();
+    if (rl == 0 && i < n) {
+        float t = 0.f;
+#pragma unroll
+        for (int r = 0; r < RL; ++r) t += red[r][cl];
+        float* o = (out1 && i >= n0) ? out1 + (i - n0) : out0 + i;
+        *o = accumulate ? *o + t * scale : t * scale;
+    }
+}
+inline void det_fold(const float* part, float* out0, float* out1, int64_t count, int64_t n, int64_t n0, float scale,
+                     int accumulate, hipStream_t s) {
+    if (n <= 2) hipLaunchKernelGGL(det_fold_kernel<2>, dim3(1), dim3(256), 0, s, part, out0, out1, count, n, n0, scale, accumulate);
+    else hipLaunchKernelGGL(det_fold_kernel<32>, dim3((unsigned)cdiv(n, 32)), dim3(256), 0, s, part, out0, out1, count, n, n0, scale, accumulate);
+}
+
+// column sum: colsum_kernel's walk over a row chunk, the chunk's sums stored to part[chunk][N]
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void colsum_det_kernel(const T* x, float* part, int64_t M, int64_t N, int64_t ldx,
+                                                         int64_t rows_per) {
+    __shared__ float red[8][32][9];
+    const int cg = threadIdx.x & 31, rl = threadIdx.x >> 5;
+    const int64_t n0 = (int64_t)blockIdx.x * 256 + cg * 8;
+    const int64_t r0 = (int64_t)blockIdx.y * rows_per;
+    int64_t r1 = r0 + rows_per;
+    if (r1 > M) r1 = M;
+    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (n0 < N) {
+        int64_t r = r0 + rl;
+        if (VEC) {
+            for (; r + 24 < r1; r += 32) {
+                float v[4][8];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) ld8<T>(x + (r + 8 * u) * ldx + n0, v[u]);
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) acc[t] += v[u][t];
+            }
+        }
+        for (; r < r1; r += 8) {
+            if (VEC) {
+                float v[8];
+                ld8<T>(x + r * ldx + n0, v);
+#pragma unroll
+                for (int t = 0; t < 8; ++t) acc[t] += v[t];
+            } else {
+#pragma unroll
+                for (int t = 0; t < 8; ++t)
+                    if (n0 + t < N) acc[t] += Elem<T>::ld(x + r * ldx + n0 + t);
+            }
+        }
+    }
+#pragma unroll
+    for (int t = 0; t < 8; ++t) red[rl][cg][t] = acc[t];
+    __syncthreads();
+    if (rl == 0 && n0 < N) {
+#pragma unroll
+        for (int t = 0; t < 8; ++t) {
+            float s = 0.f;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) s += red[r][cg][t];
+            if (n0 + t < N) part[(int64_t)blockIdx.y * N + n0 + t] = s;
+        }
+    }
+}
+inline int64_t colsum_det_chunks(int64_t M, int64_t N, int64_t* rows_per) {
+    const int64_t col_blocks = cdiv(N, 256);
+    int64_t chunks = cdiv(1024, col_blocks);  // ~1024 workgroups in flight, as m3ae_colsum's 256-column form
+    if (chunks > cdiv(M, 64)) chunks = cdiv(M, 64);
+    if (chunks < 1) chunks = 1;
+    *rows_per = cdiv(M, chunks);
+    return cdiv(M, *rows_per);
+}
+
+// RoBERTa embedding backward with duplicate ids.  keys[0][t] = word id, keys[1][t] = position id of token t (flat [B * S]).
+// Workgroup (t, table): token t OWNS its table row if no earlier token carries the same key; the owner adds the d_out rows of
+// every token with that key in ASCENDING TOKEN ORDER (itself first) in registers and then adds the sum into the table row;
+// every other workgroup leaves at once.  (The rank-by-counting idea of mask_ranks_kernel: no sort, no atomics.)
+__global__ void roberta_embed_keys_kernel(const int64_t* ids, int* keys, int64_t S, int64_t BS, int64_t pad_id) {
+    const int64_t b = blockIdx.x;
+    if (threadIdx.x == 0) {
+        int run = 0;
+        for (int64_t s = 0; s < S; ++s) {
+            const int64_t id = ids[b * S + s];
+            const int ne = id != pad_id;
+            run += ne;
+            keys[b * S + s] = (int)id;
+            keys[BS + b * S + s] = run * ne + (int)pad_id;
+        }
+    }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void roberta_embed_bwd_det_kernel(const int* __restrict__ keys, const T* __restrict__ d_out,
+                                                                    float* d_word, float* d_pos, int64_t BS, int64_t D) {
+    __shared__ unsigned long long masks[4];
+    __shared__ int dup;
+    const int64_t t = blockIdx.x;
+    const int* k = keys + (int64_t)blockIdx.y * BS;
+    float* table = blockIdx.y == 0 ? d_word : d_pos;
+    const int key = k[t];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) dup = 0;
+    __syncthreads();
+    int found = 0;
+    for (int64_t u = threadIdx.x; u < t; u += 256) found |= k[u] == key;
+    if (found) dup = 1;
+    __syncthreads();
+    if (dup) return;   // an earlier token owns this row (whole workgroup: uniform)
+    constexpr int MAXV = 8;   // D <= 256 * MAXV columns per thread in registers
+    float acc[MAXV];
+#pragma unroll
+    for (int v = 0; v < MAXV; ++v) acc[v] = 0.f;
+    for (int64_t base = t - t % 256; base < BS; base += 256) {
+        const int64_t u = base + threadIdx.x;
+        const unsigned long long m = __ballot(u >= t && u < BS && k[u] == key);
+        if (lane == 0) masks[wave] = m;
+        __syncthreads();
+        for (int w = 0; w < 4; ++w) {
+            unsigned long long mm = masks[w];
+            while (mm) {
+                const int bit = __ffsll((long long)mm) - 1;
+                mm &= mm - 1;
+                const T* row = d_out + (base + w * 64 + bit) * D;
+#pragma unroll
+                for (int v = 0; v < MAXV; ++v) {
+                    const int64_t d = threadIdx.x + 256 * v;
+                    if (d < D) acc[v] += Elem<T>::ld(row + d);
+                }
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int v = 0; v < MAXV; ++v) {
+        const int64_t d = threadIdx.x + 256 * v;
+        if (d < D) table[(int64_t)key * D + d] += acc[v];
+    }
+}
+
+// losses: one partial per workgroup (BCE, MIM) or per row (cross entropy), folded by det_fold_kernel
+template <typename T>
+__global__ __launch_bounds__(256) void bce_det_kernel(const T* x, const float* z, float* part, T* dx, int64_t n, float inv_n,
+                                                      float C, float grad_scale) {
+    __shared__ float red[4];
+    float acc = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float xi = Elem<T>::ld(x + i), zi = z[i];
+        acc += fmaxf(xi, 0.f) - xi * zi + log1pf(expf(-fabsf(xi)));
+        const float sig = 1.0f / (1.0f + expf(-xi));
+        if (dx) Elem<T>::st(dx + i, (sig - zi) * inv_n * C * grad_scale);
+    }
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc * inv_n * C;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+template <typename T>
+__global__ __launch_bounds__(256) void xent_det_kernel(const T* x, const int64_t* labels, float* part, T* dx, const float* ws,
+                                                       int64_t C, int64_t ld, float grad_scale) {
+    __shared__ float red[4];
+    const int64_t row = blockIdx.x;
+    const int64_t lab = labels[row];
+    const T* xr = x + row * ld;
+    T* dr = dx ? dx + row * ld : nullptr;
+    if (lab == -100) {
+        if (threadIdx.x == 0) part[row] = 0.f;
+        if (dr) for (int64_t j = threadIdx.x; j < C; j += 256) Elem<T>::st(dr + j, 0.f);
+        return;
+    }
+    float mx = -INFINITY;
+    for (int64_t j = threadIdx.x; j < C; j += 256) mx = fmaxf(mx, Elem<T>::ld(xr + j));
+    mx = wave_max(mx);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    __syncthreads();
+    float sum = 0.f;
+    for (int64_t j = threadIdx.x; j < C; j += 256) sum += expf(Elem<T>::ld(xr + j) - mx);
+    sum = wave_sum(sum);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    sum = red[0] + red[1] + red[2] + red[3];
+    const float inv_valid = 1.0f / ws[0];
+    const float lse = mx + logf(sum);
+    if (threadIdx.x == 0) part[row] = (lse - Elem<T>::ld(xr + lab)) * inv_valid;
+    if (dr) {
+        const float gs = grad_scale * inv_valid;
+        for (int64_t j = threadIdx.x; j < C; j += 256) {
+            const float p = expf(Elem<T>::ld(xr + j) - lse);
+            Elem<T>::st(dr + j, (p - (j == lab ? 1.f : 0.f)) * gs);
+        }
+    }
+}
+
 // ---- AdamW (transformers 4.6.0 semantics) -----------------------------------------------------------------
 __global__ void adamw_kernel(float* p, const float* g, float* m, float* v, bf16_t* shadow, int64_t n4, float lr,
                              float b1, float b2, float eps, float wd, float step_size, float grad_scale,
@@ -829,6 +1042,30 @@ __global__ void mim_loss_fwd_kernel(const T* __restrict__ x, const float* __rest
     }
 }
 __global__ void mim_loss_finalize_kernel(const float* __restrict__ acc, float* __restrict__ loss) { loss[0] = acc[0] / acc[1]; }
+// deterministic mode: part[workgroup][2] instead of the two atomics
+template <typename T>
+__global__ void mim_loss_fwd_det_kernel(const T* __restrict__ x, const float* __restrict__ t, const float* __restrict__ mask,
+                                        float* __restrict__ part, int64_t N, int L, int D) {
+    __shared__ float red[4][2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float num = 0.f, den = 0.f;
+    for (int64_t n = (int64_t)blockIdx.x * 4 + wave; n < N; n += (int64_t)gridDim.x * 4) {
+        const float m = mask[n];
+        if (m == 0.f) continue;
+        const T* xr = x + ((n / L) * (L + 1) + 1 + n % L) * (int64_t)D;
+        const float* tr = t + n * (int64_t)D;
+        float ss = 0.f;
+        for (int d = lane; d < D; d += 64) { const float e = Elem<T>::ld(xr + d) - tr[d]; ss += e * e; }
+        num += m * wave_sum(ss) / (float)D;
+        den += m;
+    }
+    if (lane == 0) { red[wave][0] = num; red[wave][1] = den; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        part[2 * blockIdx.x] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+        part[2 * blockIdx.x + 1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+    }
+}
 // dx[b][0][:] = 0 ;  dx[b][1 + l][d] = gout * 2 (x - t) mask / (D * sum mask)
 template <typename T>
 __global__ void mim_loss_bwd_kernel(const T* __restrict__ x, const float* __restrict__ t, const float* __restrict__ mask,
@@ -885,5 +1122,102 @@ extern "C" int m3ae_mim_loss_bwd(const void* x, const float* target, const float
     hipStream_t s = (hipStream_t)stream;
     DT_SWITCH(dtype, hipLaunchKernelGGL(mim_loss_bwd_kernel<T>, dim3((unsigned)cdiv(B * (L + 1), 4)), dim3(256), 0, s,
                                         (const T*)x, target, mask, acc, gout, (T*)dx, B * (L + 1), (int)L, (int)D));
+    return hip_launch_status();
+}
+
+// ---- deterministic mode: entry points (include/m3ae_hip.h) ---------------------------------------------------------------
+static int64_t det_align(int64_t bytes) { return (bytes + 255) / 256 * 256; }
+static int64_t mim_fwd_blocks(int64_t rows) { return cdiv(rows, 4) < 1024 ? cdiv(rows, 4) : 1024; }
+
+extern "C" int64_t m3ae_det_workspace_bytes(int op, int64_t rows, int64_t cols) {
+    if (rows <= 0 || cols <= 0) return M3AE_ERR_ARG;
+    int64_t rows_per = 0;
+    switch (op) {
+    case M3AE_DET_COLSUM: return det_align(colsum_det_chunks(rows, cols, &rows_per) * cols * (int64_t)sizeof(float));
+    case M3AE_DET_EMBED_BWD:   // rows = B * S tokens, cols = D: two key rows, then the token-type column sum's partials
+        return det_align(2 * rows * (int64_t)sizeof(int)) + m3ae_det_workspace_bytes(M3AE_DET_COLSUM, rows, cols);
+    case M3AE_DET_BCE: return det_align(64 * (int64_t)sizeof(float));
+    case M3AE_DET_XENT: return det_align((1 + rows) * (int64_t)sizeof(float));   // the count of m3ae_xent's workspace, then one partial per row
+    case M3AE_DET_MIM: return det_align(2 * mim_fwd_blocks(rows) * (int64_t)sizeof(float));   // rows = B * L
+    default: return M3AE_ERR_ARG;
+    }
+}
+
+extern "C" int m3ae_colsum_det(const void* x, float* out, int64_t M, int64_t N, int64_t ldx, int dtype, int accumulate,
+                               void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!x || !out || M <= 0 || N <= 0) return M3AE_ERR_ARG;
+    if (!workspace || workspace_bytes < m3ae_det_workspace_bytes(M3AE_DET_COLSUM, M, N)) return M3AE_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    int64_t rows_per = 0;
+    const int64_t chunks = colsum_det_chunks(M, N, &rows_per);
+    dim3 grid((unsigned)cdiv(N, 256), (unsigned)chunks);
+    float* part = (float*)workspace;
+    const bool vec = (N % 8 == 0) && (ldx % 8 == 0) && ((((uintptr_t)x) & 15) == 0);
+    if (vec) { DT_SWITCH(dtype, hipLaunchKernelGGL((colsum_det_kernel<T, true>), grid, dim3(256), 0, s, (const T*)x, part, M, N, ldx, rows_per)); }
+    else { DT_SWITCH(dtype, hipLaunchKernelGGL((colsum_det_kernel<T, false>), grid, dim3(256), 0, s, (const T*)x, part, M, N, ldx, rows_per)); }
+    int rc = hip_launch_status();
+    if (rc) return rc;
+    det_fold(part, out, nullptr, chunks, N, N, 1.0f, accumulate, s);
+    return hip_launch_status();
+}
+
+extern "C" int m3ae_roberta_embed_bwd_det(const int64_t* ids, const void* d_out, float* d_word, float* d_pos, float* d_type,
+                                          int64_t B, int64_t S, int64_t D, int64_t pad_id, int dtype, void* workspace,
+                                          int64_t workspace_bytes, void* stream) {
+    if (!ids || !d_out || !d_word || !d_pos || B <= 0 || S <= 0 || S > 4096) return M3AE_ERR_ARG;
+    if (D <= 0 || D > 2048 || B * S > 0x7fffffff) return M3AE_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < m3ae_det_workspace_bytes(M3AE_DET_EMBED_BWD, B * S, D)) return M3AE_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t BS = B * S;
+    int* keys = (int*)workspace;
+    hipLaunchKernelGGL(roberta_embed_keys_kernel, dim3((unsigned)B), dim3(64), 0, s, ids, keys, S, BS, pad_id);
+    DT_SWITCH(dtype, hipLaunchKernelGGL(roberta_embed_bwd_det_kernel<T>, dim3((unsigned)BS, 2), dim3(256), 0, s, keys,
+                                        (const T*)d_out, d_word, d_pos, BS, D));
+    int rc = hip_launch_status();
+    if (rc) return rc;
+    if (d_type) {   // token_type 0 for every token
+        const int64_t off = det_align(2 * BS * (int64_t)sizeof(int));
+        return m3ae_colsum_det(d_out, d_type, BS, D, D, dtype, 1, (char*)workspace + off, workspace_bytes - off, stream);
+    }
+    return 0;
+}
+
+extern "C" int m3ae_bce_logits_det(const void* logits, const float* targets, float* loss, void* d_logits, int64_t B, int64_t C,
+                                   float grad_scale, int dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!logits || !targets || !loss || B <= 0 || C <= 0) return M3AE_ERR_ARG;
+    if (!workspace || workspace_bytes < m3ae_det_workspace_bytes(M3AE_DET_BCE, B, C)) return M3AE_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = B * C;
+    unsigned grid = ew_grid(n);
+    if (grid > 64) grid = 64;
+    DT_SWITCH(dtype, hipLaunchKernelGGL(bce_det_kernel<T>, dim3(grid), dim3(EW_BLOCK), 0, s, (const T*)logits, targets,
+                                        (float*)workspace, (T*)d_logits, n, 1.0f / (float)n, (float)C, grad_scale));
+    det_fold((const float*)workspace, loss, nullptr, grid, 1, 1, 1.0f, 0, s);
+    return hip_launch_status();
+}
+
+extern "C" int m3ae_xent_det(const void* logits, const int64_t* labels, float* loss, void* d_logits, int64_t rows, int64_t C,
+                             int64_t ld, float grad_scale, int dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!logits || !labels || !loss || rows <= 0 || C <= 0) return M3AE_ERR_ARG;
+    if (!workspace || workspace_bytes < m3ae_det_workspace_bytes(M3AE_DET_XENT, rows, C)) return M3AE_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    hipLaunchKernelGGL(xent_count_kernel, dim3(1), dim3(256), 0, s, labels, ws, rows);
+    DT_SWITCH(dtype, hipLaunchKernelGGL(xent_det_kernel<T>, dim3((unsigned)rows), dim3(256), 0, s, (const T*)logits, labels,
+                                        ws + 1, (T*)d_logits, ws, C, ld, grad_scale));
+    det_fold(ws + 1, loss, nullptr, rows, 1, 1, 1.0f, 0, s);
+    return hip_launch_status();
+}
+
+extern "C" int m3ae_mim_loss_fwd_det(const void* x, const float* target, const float* mask, float* acc, float* loss, int64_t B,
+                                     int64_t L, int64_t D, int dtype, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!x || !target || !mask || !acc || !loss || B <= 0 || L <= 0 || D <= 0) return M3AE_ERR_ARG;
+    if (!workspace || workspace_bytes < m3ae_det_workspace_bytes(M3AE_DET_MIM, B * L, D)) return M3AE_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t fwd_blocks = mim_fwd_blocks(B * L);
+    DT_SWITCH(dtype, hipLaunchKernelGGL(mim_loss_fwd_det_kernel<T>, dim3((unsigned)fwd_blocks), dim3(256), 0, s, (const T*)x,
+                                        target, mask, (float*)workspace, B * L, (int)L, (int)D));
+    det_fold((const float*)workspace, acc, nullptr, fwd_blocks, 2, 2, 1.0f, 0, s);
+    hipLaunchKernelGGL(mim_loss_finalize_kernel, dim3(1), dim3(1), 0, s, acc, loss);
     return hip_launch_status();
 }

@@ -346,6 +346,38 @@ __global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(const float* part, f
     }
 }
 
+// deterministic mode: the same fold with ONE workgroup per column block walking all nblk partial rows (row lane r adds rows
+// r, r + 8, ... in ascending order, lane 0 adds the eight lane sums in ascending order), so every column has one writer and
+// the order of the sum depends on nblk alone
+__global__ __launch_bounds__(256) void ln_bwd_reduce_det_kernel(const float* part, float* dgamma, float* dbeta, int nblk, int D) {
+    __shared__ float red[8][33];
+    const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
+    const int i = blockIdx.x * 32 + cl;  // index into [2][D]
+    float s = 0.f;
+    if (i < 2 * D) {
+        const int which = i / D, col = i - which * D;
+        for (int b = rl; b < nblk; b += 8) s += part[((int64_t)b * 2 + which) * D + col];
+    }
+    red[rl][cl] = s;
+    __syncthreads();
+    if (rl == 0 && i < 2 * D) {
+        float t = 0.f;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) t += red[r][cl];
+        const int which = i / D, col = i - which * D;
+        if (which == 0) dgamma[col] += t;
+        else if (dbeta) dbeta[col] += t;
+    }
+}
+inline int ln_bwd_fold(const float* part, float* dgamma, float* dbeta, int nblk, int D, int det, hipStream_t s) {
+    if (det)
+        hipLaunchKernelGGL(ln_bwd_reduce_det_kernel, dim3((unsigned)cdiv(2 * D, 32)), dim3(256), 0, s, part, dgamma, dbeta, nblk, D);
+    else
+        hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((unsigned)cdiv(2 * D, 32), (unsigned)cdiv(nblk, 64)), dim3(256), 0, s, part, dgamma,
+                           dbeta, nblk, D);
+    return hip_launch_status();
+}
+
 // workgroups that can be resident at once (every wave walks its rows in a grid-stride loop: a workgroup that has to wait for
 // a free slot would start a second round with a full share of the rows)
 template <typename K> int resident_blocks(K kernel, size_t lds) {
@@ -440,10 +472,9 @@ extern "C" int64_t m3ae_layernorm_bwd_blocks(int64_t M) {
     return n < 1024 ? n : 1024;
 }
 
-extern "C" int m3ae_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* beta,
-                                  const float* mean, const float* rstd, void* dx, const void* dx_add, float* dgamma,
-                                  float* dbeta, float* workspace, int64_t M, int64_t D, int dtype, int act, int rms,
-                                  void* stream) {
+static int layernorm_bwd_impl(const void* dy, const void* x, const float* gamma, const float* beta, const float* mean,
+                              const float* rstd, void* dx, const void* dx_add, float* dgamma, float* dbeta, float* workspace,
+                              int64_t M, int64_t D, int dtype, int act, int rms, void* stream, int det) {
     if (!dy || !x || !gamma || !rstd || !dx || !workspace || M <= 0) return M3AE_ERR_ARG;
     if (D % 4 != 0 || D > 2048) return M3AE_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
@@ -459,15 +490,25 @@ extern "C" int m3ae_layernorm_bwd(const void* dy, const void* x, const float* ga
     rc = run();
     if (rc) return rc;
     if (!dgamma) return 0;
-    hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((unsigned)cdiv(2 * D, 32), (unsigned)cdiv(nblk, 64)), dim3(256), 0, s, workspace, dgamma,
-                       dbeta, nblk, (int)D);
-    return hip_launch_status();
+    return ln_bwd_fold(workspace, dgamma, dbeta, nblk, (int)D, det, s);
+}
+extern "C" int m3ae_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* beta,
+                                  const float* mean, const float* rstd, void* dx, const void* dx_add, float* dgamma,
+                                  float* dbeta, float* workspace, int64_t M, int64_t D, int dtype, int act, int rms,
+                                  void* stream) {
+    return layernorm_bwd_impl(dy, x, gamma, beta, mean, rstd, dx, dx_add, dgamma, dbeta, workspace, M, D, dtype, act, rms, stream, 0);
+}
+extern "C" int m3ae_layernorm_bwd_det(const void* dy, const void* x, const float* gamma, const float* beta,
+                                      const float* mean, const float* rstd, void* dx, const void* dx_add, float* dgamma,
+                                      float* dbeta, float* workspace, int64_t M, int64_t D, int dtype, int act, int rms,
+                                      void* stream) {
+    return layernorm_bwd_impl(dy, x, gamma, beta, mean, rstd, dx, dx_add, dgamma, dbeta, workspace, M, D, dtype, act, rms, stream, 1);
 }
 
-extern "C" int m3ae_layernorm_bwd_drop(const void* dy, const void* x, const float* gamma, const float* beta,
-                                       const float* mean, const float* rstd, void* dx, void* dx_drop, float dropout_p,
-                                       uint64_t dropout_seed, const void* dropout_salt, float* dgamma, float* dbeta,
-                                       float* workspace, int64_t M, int64_t D, int dtype, void* stream) {
+static int layernorm_bwd_drop_impl(const void* dy, const void* x, const float* gamma, const float* beta, const float* mean,
+                                   const float* rstd, void* dx, void* dx_drop, float dropout_p, uint64_t dropout_seed,
+                                   const void* dropout_salt, float* dgamma, float* dbeta, float* workspace, int64_t M, int64_t D,
+                                   int dtype, void* stream, int det) {
     if (!dy || !x || !gamma || !rstd || !dx || !dx_drop || !workspace || M <= 0) return M3AE_ERR_ARG;
     if (D % 4 != 0 || D > 2048) return M3AE_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
@@ -483,7 +524,19 @@ extern "C" int m3ae_layernorm_bwd_drop(const void* dy, const void* x, const floa
     int rc = run();
     if (rc) return rc;
     if (!dgamma) return 0;
-    hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((unsigned)cdiv(2 * D, 32), (unsigned)cdiv(nblk, 64)), dim3(256), 0, s,
-                       workspace, dgamma, dbeta, nblk, (int)D);
-    return hip_launch_status();
+    return ln_bwd_fold(workspace, dgamma, dbeta, nblk, (int)D, det, s);
+}
+extern "C" int m3ae_layernorm_bwd_drop(const void* dy, const void* x, const float* gamma, const float* beta,
+                                       const float* mean, const float* rstd, void* dx, void* dx_drop, float dropout_p,
+                                       uint64_t dropout_seed, const void* dropout_salt, float* dgamma, float* dbeta,
+                                       float* workspace, int64_t M, int64_t D, int dtype, void* stream) {
+    return layernorm_bwd_drop_impl(dy, x, gamma, beta, mean, rstd, dx, dx_drop, dropout_p, dropout_seed, dropout_salt, dgamma, dbeta,
+                                   workspace, M, D, dtype, stream, 0);
+}
+extern "C" int m3ae_layernorm_bwd_drop_det(const void* dy, const void* x, const float* gamma, const float* beta,
+                                           const float* mean, const float* rstd, void* dx, void* dx_drop, float dropout_p,
+                                           uint64_t dropout_seed, const void* dropout_salt, float* dgamma, float* dbeta,
+                                           float* workspace, int64_t M, int64_t D, int dtype, void* stream) {
+    return layernorm_bwd_drop_impl(dy, x, gamma, beta, mean, rstd, dx, dx_drop, dropout_p, dropout_seed, dropout_salt, dgamma, dbeta,
+                                   workspace, M, D, dtype, stream, 1);
 }

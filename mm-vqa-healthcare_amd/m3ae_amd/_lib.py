@@ -56,7 +56,8 @@ class XattnDesc(C.Structure):
     ]
 
 
-GEMM_NO_PERSISTENT, GEMM_F32_X3 = 1, 2           # m3ae_gemm_desc.launch_flags
+GEMM_NO_PERSISTENT, GEMM_F32_X3, GEMM_DETERMINISTIC = 1, 2, 4   # m3ae_gemm_desc.launch_flags
+DET_COLSUM, DET_EMBED_BWD, DET_BCE, DET_XENT, DET_MIM = 0, 1, 2, 3, 4   # m3ae_det_workspace_bytes op
 ATTN_LEGACY_KERNELS, ATTN_F32_X3 = 1, 2           # m3ae_attn_desc.launch_flags
 XATTN_NO_PERSISTENT, XATTN_LEGACY_CHAIN = 1, 2    # m3ae_xattn_desc.launch_flags
 ABI_VERSION = 4
@@ -107,6 +108,17 @@ _SIGS = {
     "m3ae_mim_loss_fwd": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, C.c_int, vp]),
     "m3ae_mim_loss_bwd": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, i64, C.c_int, vp]),
     "m3ae_selftest": (C.c_int, [vp, vp]),
+    # deterministic mode (ABI 4, additive)
+    "m3ae_gemm_det_workspace_bytes": (i64, [C.POINTER(GemmDesc)]),
+    "m3ae_gemm_det": (C.c_int, [C.POINTER(GemmDesc), vp, i64, vp]),
+    "m3ae_det_workspace_bytes": (i64, [C.c_int, i64, i64]),
+    "m3ae_colsum_det": (C.c_int, [vp, vp, i64, i64, i64, C.c_int, C.c_int, vp, i64, vp]),
+    "m3ae_layernorm_bwd_det": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, C.c_int, C.c_int, C.c_int, vp]),
+    "m3ae_layernorm_bwd_drop_det": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, f32, C.c_uint64, vp, vp, vp, vp, i64, i64, C.c_int, vp]),
+    "m3ae_roberta_embed_bwd_det": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, i64, C.c_int, vp, i64, vp]),
+    "m3ae_bce_logits_det": (C.c_int, [vp, vp, vp, vp, i64, i64, f32, C.c_int, vp, i64, vp]),
+    "m3ae_xent_det": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, f32, C.c_int, vp, i64, vp]),
+    "m3ae_mim_loss_fwd_det": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, C.c_int, vp, i64, vp]),
 }
 
 EXPORTS = tuple(_SIGS)

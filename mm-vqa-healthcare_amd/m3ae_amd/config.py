@@ -41,6 +41,10 @@ DEFAULTS = dict(
     gpu_device_number=0, label_column_name="",
     # build extensions (not in the reference): compute mode of the HIP path
     compute_dtype="bf16",  # "bf16" (perf mode) | "fp32" (parity mode) | "fp32x3" (parity mode's storage, GEMMs on the split-bf16 MFMA)
+    # bit-reproducible training steps (ops.set_deterministic): every gradient and loss reduction in a fixed order instead of fp32
+    # atomics.  The reference's trainer runs with deterministic=True (main.py:64); here the default is False -- the one deliberate
+    # difference from that flag -- because the ordered split-K weight gradients cost step time.
+    deterministic=False,
 )
 
 NAMED = {

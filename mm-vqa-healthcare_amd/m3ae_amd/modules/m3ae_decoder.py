@@ -158,6 +158,7 @@ class _DecoderEmbedFn(ops.Function):
         (ids,) = ctx.saved_tensors
         w = ctx.weight
         if w.requires_grad:
+            ops._no_ordered_form("the gradient of the decoder's trainable target embedding (torch index_add_)")
             d = dout.float().contiguous()
             d2 = torch.empty_like(d)
             ops.check(ops._lib.lib().m3ae_add(ops._p(d), ops._p(d), ops._p(d2), d.numel(), ops._dt(d), ops._stream()),

@@ -131,6 +131,10 @@ class M3AETransformerSS(_Base):
         self.store = None
         self._dtype = torch.bfloat16 if cfg.get("compute_dtype", "bf16") == "bf16" else torch.float32
         self._x3 = cfg.get("compute_dtype") == "fp32x3"   # fp32x3 mode: fp32 storage, fp32 GEMMs on the split-bf16 MFMA kernel
+        # deterministic=True (the reference trainer's flag, main.py:64): ordered reductions in every backward from here on.  The
+        # switch is process-wide (ops.set_deterministic), as the reference's is; ops.set_deterministic(False) takes it back.
+        if cfg.get("deterministic", False):
+            ops.set_deterministic(True)
 
     @property
     def f32x3(self):

@@ -75,6 +75,57 @@ def model_mode(fn):
     return run
 
 
+# Deterministic mode (config key `deterministic`): every reduction of a training step that more than one workgroup feeds -- the
+# split-K weight gradients, bias / LayerNorm / embedding gradients, the loss scalars -- takes its ordered form (m3ae_gemm_det and
+# the *_det entry points: partials in a workspace, folded in a fixed order) instead of fp32 atomics, so two runs of a step from
+# the same state, seeds and masks give the same bits.  The switch is process-wide, like torch.use_deterministic_algorithms
+# (autograd runs backward on a thread of its own, and the mode must hold there too), and is read at every call: off (the
+# default), no helper below makes one call more than before.  An op that has no ordered form raises DeterministicError when
+# its backward is asked with the mode on; it never runs the atomic kernel quietly.
+class DeterministicError(_lib.M3AEHipError):
+    pass
+
+
+_DETERMINISTIC = False
+
+
+def set_deterministic(on):
+    global _DETERMINISTIC
+    _DETERMINISTIC = bool(on)
+
+
+def deterministic():
+    return _DETERMINISTIC
+
+
+@contextlib.contextmanager
+def deterministic_mode(on=True):
+    prev = deterministic()
+    set_deterministic(on)
+    try:
+        yield
+    finally:
+        set_deterministic(prev)
+
+
+def _no_ordered_form(op):
+    if _DETERMINISTIC:
+        raise DeterministicError(f"{op} has no deterministic form (it adds with fp32 atomics) and ops.deterministic() is on: "
+                                 f"switch the mode off for this op with ops.set_deterministic(False)")
+
+
+def _det_ws(nbytes, device):
+    """Workspace of a deterministic call: allocated on the caller's stream like every other temporary of the step."""
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
+
+
+def _small_ws(op, rows, cols, device):
+    n = _lib.lib().m3ae_det_workspace_bytes(op, rows, cols)
+    if n < 0:
+        check(int(n), "m3ae_det_workspace_bytes")
+    return _det_ws(n, device), n
+
+
 class Function(torch.autograd.Function):
     """torch.autograd.Function whose backward runs in the fp32x3 mode its forward ran in (saved on ctx)."""
 
@@ -231,7 +282,16 @@ def gemm(a, a_sm, a_sk, b, b_sk, b_sn, c, c_sm, M, N, K, *, alpha=1.0, accumulat
         d.a_rowsum = a_rowsum.data_ptr()
     _set_dropout(d, dropout)
     e0 = _prof_begin()
-    check(_lib.lib().m3ae_gemm(C.byref(d), _stream()), "m3ae_gemm")
+    # deterministic mode: a descriptor of the split-K wgrad family (the only GEMM family that adds with atomics) takes the
+    # ordered form; the size query is 0 for every other descriptor
+    nws = _lib.lib().m3ae_gemm_det_workspace_bytes(C.byref(d)) if _DETERMINISTIC else 0
+    if nws > 0:
+        d.launch_flags |= _lib.GEMM_DETERMINISTIC
+        ws = _det_ws(nws, c.device)
+        check(_lib.lib().m3ae_gemm_det(C.byref(d), _p(ws), nws, _stream()), "m3ae_gemm_det")
+        del ws
+    else:
+        check(_lib.lib().m3ae_gemm(C.byref(d), _stream()), "m3ae_gemm")
     if e0 is not None:
         _prof_end(e0, "gemm:" + last_gemm_path(), (M, N, K, batch[0] * batch[1]))
 
@@ -325,12 +385,21 @@ def mm_wgrad(dy, x2, ldx, w_param, b_param=None, alpha=1.0):
         _done(b_param)
 
 
+def colsum(x, out, accumulate):
+    """out[n] (+)= sum_m x[m][n]; the ordered form in deterministic mode."""
+    M, N = x.shape
+    if _DETERMINISTIC:
+        ws, n = _small_ws(_lib.DET_COLSUM, M, N, x.device)
+        check(_lib.lib().m3ae_colsum_det(_p(x), _p(out), M, N, x.stride(0), _dt(x), int(accumulate), _p(ws), n, _stream()),
+              "m3ae_colsum_det")
+        return
+    check(_lib.lib().m3ae_colsum(_p(x), _p(out), M, N, x.stride(0), _dt(x), int(accumulate), _stream()), "m3ae_colsum")
+
+
 def bias_grad(dy, b_param):
     if b_param is None or not b_param.requires_grad:
         return
-    g = _grad_buf(b_param)
-    M, N = dy.shape
-    check(_lib.lib().m3ae_colsum(_p(dy), _p(g), M, N, dy.stride(0), _dt(dy), 1, _stream()), "m3ae_colsum")
+    colsum(dy, _grad_buf(b_param), True)
     _done(b_param)
 
 
@@ -433,8 +502,7 @@ class LinearFn(Function):
         if ctx.extra_needs:
             mm_wgrad(dz, x2, ctx.ldx, ctx.weight, alpha=ctx.alpha)
             dextra = torch.empty(N, dtype=torch.float32, device=dz.device)
-            check(_lib.lib().m3ae_colsum(_p(dz), _p(dextra), dz.shape[0], N, dz.stride(0), _dt(dz), 0, _stream()),
-                  "m3ae_colsum")
+            colsum(dz, dextra, False)
             if ctx.bias is not None and ctx.bias.requires_grad:
                 _grad_buf(ctx.bias).add_(dextra)
                 _done(ctx.bias)
@@ -537,8 +605,9 @@ class LayerNormFn(Function):
         ws = torch.empty(2 * nblk * D, dtype=torch.float32, device=xc.device)
         gg = _grad_buf(ctx.gamma)
         gb = _grad_buf(ctx.beta) if ctx.beta is not None else None
-        check(L.m3ae_layernorm_bwd(_p(dyc), _p(xc), _p(ctx.gamma), _p(ctx.beta), _p(mean), _p(rstd), _p(dx), None,
-                                   _p(gg), _p(gb), _p(ws), M, D, _dt(xc), ctx.act, int(ctx.rms), _stream()),
+        ln_bwd = L.m3ae_layernorm_bwd_det if _DETERMINISTIC else L.m3ae_layernorm_bwd
+        check(ln_bwd(_p(dyc), _p(xc), _p(ctx.gamma), _p(ctx.beta), _p(mean), _p(rstd), _p(dx), None,
+                     _p(gg), _p(gb), _p(ws), M, D, _dt(xc), ctx.act, int(ctx.rms), _stream()),
               "m3ae_layernorm_bwd")
         _done(ctx.gamma)
         _done(ctx.beta)
@@ -576,15 +645,17 @@ def ln_bwd_raw(dy, x2, ln, mean, rstd, dx_add=None, act=ACT_NONE, rms=False, dro
     if drop is not None and drop[0] > 0:
         assert dx_add is None and act == ACT_NONE and not rms
         dxd = torch.empty_like(x2)
-        check(L.m3ae_layernorm_bwd_drop(_p(dy), _p(x2), _p(ln.weight), _p(ln.bias), _p(mean), _p(rstd), _p(dx), _p(dxd),
-                                        drop[0], drop[1], _salt(), _p(gg), _p(gb), _p(ws), M, D, _dt(x2), _stream()),
+        ln_bwd_drop = L.m3ae_layernorm_bwd_drop_det if _DETERMINISTIC else L.m3ae_layernorm_bwd_drop
+        check(ln_bwd_drop(_p(dy), _p(x2), _p(ln.weight), _p(ln.bias), _p(mean), _p(rstd), _p(dx), _p(dxd),
+                          drop[0], drop[1], _salt(), _p(gg), _p(gb), _p(ws), M, D, _dt(x2), _stream()),
               "m3ae_layernorm_bwd_drop")
         if train:
             _done(ln.weight)
             _done(ln.bias)
         return dx, dxd
-    check(L.m3ae_layernorm_bwd(_p(dy), _p(x2), _p(ln.weight), _p(ln.bias), _p(mean), _p(rstd), _p(dx), _p(dx_add),
-                               _p(gg), _p(gb), _p(ws), M, D, _dt(x2), act, int(rms), _stream()), "m3ae_layernorm_bwd")
+    ln_bwd = L.m3ae_layernorm_bwd_det if _DETERMINISTIC else L.m3ae_layernorm_bwd
+    check(ln_bwd(_p(dy), _p(x2), _p(ln.weight), _p(ln.bias), _p(mean), _p(rstd), _p(dx), _p(dx_add),
+                 _p(gg), _p(gb), _p(ws), M, D, _dt(x2), act, int(rms), _stream()), "m3ae_layernorm_bwd")
     if train:
         _done(ln.weight)
         _done(ln.bias)
@@ -650,6 +721,8 @@ def attn_forward(q, k, v, heads, key_mask=None, pos_bias=None, scale=None, causa
 
 def attn_backward(q, k, v, o, lse, do, dq, dk, dv, heads, key_mask=None, pos_bias=None, scale=None, causal=False,
                   d_pos_bias=None, dropout=None):
+    if d_pos_bias is not None:
+        _no_ordered_form("the relative-position-bias gradient of m3ae_attn_bwd (d_pos_bias, T5 attention)")
     B, Lq, D = q.shape
     Lk = k.shape[1]
     Dh = D // heads
@@ -815,6 +888,8 @@ def xattn_supported(h2, L, other2, Lo, mask, P, backward=False):
         return bool(_lib.lib().m3ae_xattn_supported(C.byref(d)))
     if not all(p.requires_grad for p in (P.w_q, P.w_kv, P.w_o, P.b_q, P.b_kv, P.b_o)):
         return False
+    if _DETERMINISTIC:   # m3ae_xattn_bwd sums its weight and bias gradients over the samples with fp32 atomics: training calls
+        return False     # take the composition, whose wgrads and reductions have ordered forms
     return bool(_lib.lib().m3ae_xattn_bwd_supported(C.byref(d)))
 
 
@@ -885,6 +960,7 @@ def xattn_probs(saved):
 
 def xattn_bwd(dy, saved, B, L, Lo, P, need_dother=True):
     """Backward of xattn_fwd (m3ae_xattn_bwd): returns (dx, dother); parameter gradients accumulate in place."""
+    _no_ordered_form("the fused cross-attention backward (m3ae_xattn_bwd; its forward ran before the mode was switched on)")
     _, h2, other2, mask, t, seeds, pdrop = saved
     dev, D, H = h2.device, h2.shape[1], P.heads
     d = _xattn_desc(h2, B, L, other2, Lo, mask, P, pdrop, seeds)
@@ -1296,6 +1372,7 @@ class EmbedRowsFn(Function):
     def backward(ctx, dout):
         (ids,) = ctx.saved_tensors
         if ctx.weight.requires_grad:  # rare path: the embedding is frozen in the reference's recipe
+            _no_ordered_form("the gradient of a trainable embedding lookup (EmbedRowsFn: torch index_add_)")
             _grad_buf(ctx.weight).index_add_(0, ids, dout.float())
             _done(ctx.weight)
         return None, None, None
@@ -1324,9 +1401,15 @@ class RobertaEmbedFn(Function):
         B, S = ids.shape
         D = word.shape[1]
         d = dout.contiguous()
-        check(_lib.lib().m3ae_roberta_embed_bwd(_p(ids), _p(d), _p(_grad_buf(word)), _p(_grad_buf(pos)),
-                                                _p(_grad_buf(typ)), B, S, D, ctx.pad_id, _dt(d), _stream()),
-              "m3ae_roberta_embed_bwd")
+        if _DETERMINISTIC:
+            ws, n = _small_ws(_lib.DET_EMBED_BWD, B * S, D, d.device)
+            check(_lib.lib().m3ae_roberta_embed_bwd_det(_p(ids), _p(d), _p(_grad_buf(word)), _p(_grad_buf(pos)),
+                                                        _p(_grad_buf(typ)), B, S, D, ctx.pad_id, _dt(d), _p(ws), n, _stream()),
+                  "m3ae_roberta_embed_bwd_det")
+        else:
+            check(_lib.lib().m3ae_roberta_embed_bwd(_p(ids), _p(d), _p(_grad_buf(word)), _p(_grad_buf(pos)),
+                                                    _p(_grad_buf(typ)), B, S, D, ctx.pad_id, _dt(d), _stream()),
+                  "m3ae_roberta_embed_bwd")
         for p in (word, pos, typ):
             _done(p)
         return None, None, None, None, None, None
@@ -1398,8 +1481,13 @@ class BCELossFn(Function):
         B, Cc = x.shape
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         dx = torch.empty_like(x)
-        check(_lib.lib().m3ae_bce_logits(_p(x), _p(targets), _p(loss), _p(dx), B, Cc, 1.0, _dt(x), _stream()),
-              "m3ae_bce_logits")
+        if _DETERMINISTIC:
+            ws, n = _small_ws(_lib.DET_BCE, B, Cc, x.device)
+            check(_lib.lib().m3ae_bce_logits_det(_p(x), _p(targets), _p(loss), _p(dx), B, Cc, 1.0, _dt(x), _p(ws), n, _stream()),
+                  "m3ae_bce_logits_det")
+        else:
+            check(_lib.lib().m3ae_bce_logits(_p(x), _p(targets), _p(loss), _p(dx), B, Cc, 1.0, _dt(x), _stream()),
+                  "m3ae_bce_logits")
         ctx.save_for_backward(dx)
         return loss[0]
 
@@ -1431,8 +1519,13 @@ class XentFn(Function):
         loss = torch.zeros(1, dtype=torch.float32, device=x.device)
         ws = torch.empty(4, dtype=torch.float32, device=x.device)
         dx = (torch.zeros if ld != Cc else torch.empty)((rows, ld), dtype=x.dtype, device=x.device)
-        check(_lib.lib().m3ae_xent(_p(x), _p(lab), _p(loss), _p(dx), _p(ws), rows, Cc, ld, 1.0, _dt(x), _stream()),
-              "m3ae_xent")
+        if _DETERMINISTIC:
+            ws, n = _small_ws(_lib.DET_XENT, rows, Cc, x.device)
+            check(_lib.lib().m3ae_xent_det(_p(x), _p(lab), _p(loss), _p(dx), rows, Cc, ld, 1.0, _dt(x), _p(ws), n, _stream()),
+                  "m3ae_xent_det")
+        else:
+            check(_lib.lib().m3ae_xent(_p(x), _p(lab), _p(loss), _p(dx), _p(ws), rows, Cc, ld, 1.0, _dt(x), _stream()),
+                  "m3ae_xent")
         ctx.save_for_backward(dx)
         ctx.shape, ctx.cols = logits.shape, Cc
         return loss[0]
@@ -1614,8 +1707,13 @@ class MimLossFn(Function):
         t, m = target.contiguous().float(), mask.contiguous().float()
         acc = torch.empty(2, dtype=torch.float32, device=x.device)
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
-        check(_lib.lib().m3ae_mim_loss_fwd(_p(xc), _p(t), _p(m), _p(acc), _p(loss), B, L1 - 1, D, _dt(xc), _stream()),
-              "m3ae_mim_loss_fwd")
+        if _DETERMINISTIC:
+            ws, n = _small_ws(_lib.DET_MIM, B * (L1 - 1), D, x.device)
+            check(_lib.lib().m3ae_mim_loss_fwd_det(_p(xc), _p(t), _p(m), _p(acc), _p(loss), B, L1 - 1, D, _dt(xc), _p(ws), n,
+                                                   _stream()), "m3ae_mim_loss_fwd_det")
+        else:
+            check(_lib.lib().m3ae_mim_loss_fwd(_p(xc), _p(t), _p(m), _p(acc), _p(loss), B, L1 - 1, D, _dt(xc), _stream()),
+                  "m3ae_mim_loss_fwd")
         ctx.save_for_backward(xc, t, m, acc)
         return loss[0]
 

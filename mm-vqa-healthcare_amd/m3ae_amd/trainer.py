@@ -213,7 +213,9 @@ class Trainer:
             return self._fit()
         prev = ops.use_launch_stream()
         try:
-            return self._fit()
+            # config key `deterministic` (the reference trainer's deterministic=True, main.py:64): ordered reductions for the run
+            with ops.deterministic_mode(ops.deterministic() or bool(self.cfg.get("deterministic", False))):
+                return self._fit()
         finally:
             torch.cuda.synchronize()
             torch.cuda.set_stream(prev)

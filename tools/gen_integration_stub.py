@@ -28,6 +28,9 @@ def struct_stub(cls, c_name):
 
 
 MAP_ENTRIES = ("m3ae_attn_probs", "m3ae_xattn_probs_export")
+DET_ENTRIES = ("m3ae_gemm_det_workspace_bytes", "m3ae_gemm_det", "m3ae_det_workspace_bytes", "m3ae_colsum_det",
+               "m3ae_layernorm_bwd_det", "m3ae_layernorm_bwd_drop_det", "m3ae_roberta_embed_bwd_det", "m3ae_bce_logits_det",
+               "m3ae_xent_det", "m3ae_mim_loss_fwd_det")
 
 
 def _ctype_name(t):
@@ -50,6 +53,14 @@ def block():
     out.append("")
     out.append("# attention maps (ABI 4): fp32 [B, H, Lq, Lk] out of an m3ae_attn_fwd / m3ae_xattn_fwd call")
     for name in MAP_ENTRIES:
+        res, args = _lib._SIGS[name]
+        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
+    out.append("")
+    out.append("# deterministic mode (ABI 4, additive): ordered reductions, caller-owned workspaces")
+    out.append(f"GEMM_DETERMINISTIC = {_lib.GEMM_DETERMINISTIC}     # m3ae_gemm_desc.launch_flags, accepted by m3ae_gemm_det only")
+    out.append(f"DET_COLSUM, DET_EMBED_BWD, DET_BCE, DET_XENT, DET_MIM = {_lib.DET_COLSUM}, {_lib.DET_EMBED_BWD}, {_lib.DET_BCE}, "
+               f"{_lib.DET_XENT}, {_lib.DET_MIM}     # m3ae_det_workspace_bytes(op, rows, cols)")
+    for name in DET_ENTRIES:
         res, args = _lib._SIGS[name]
         out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
     out.append("```")
