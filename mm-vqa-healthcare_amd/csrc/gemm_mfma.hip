@@ -1024,31 +1024,33 @@ static int tn_det_fold(const MfmaArgs& part, const m3ae_gemm_desc& d, int bm, in
     return hip_launch_status();
 }
 
-// det_ws != nullptr: deterministic mode (M3AE_GEMM_DETERMINISTIC), the caller's workspace of tn_det_bytes(d, splits) bytes
+// Launch one TN kernel instance over grid = tiles * splits workgroups.  det_ws != nullptr (KERNEL is then a DET instance):
+// deterministic mode, the kernel writes its partial planes into the caller's workspace of tn_det_bytes(d, a.splits) bytes and
+// tn_det_fold sums them into C and a_rowsum.
+template <void (*KERNEL)(MfmaArgs)>
+static int tn_run(MfmaArgs a, const m3ae_gemm_desc& d, int64_t grid, int threads, int lds, int bm, int wm, float* det_ws,
+                  hipStream_t s) {
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        attr_set = true;
+    }
+    if (det_ws) {
+        a.C = det_ws;
+        a.a_rowsum = d.a_rowsum ? det_ws + a.splits * d.M * d.N : nullptr;
+    }
+    hipLaunchKernelGGL(KERNEL, dim3((unsigned)grid), dim3(threads), lds, s, a);
+    const int rc = hip_launch_status();
+    return rc || !det_ws ? rc : tn_det_fold(a, d, bm, wm, s);
+}
+
 static int launch_tn_pp(MfmaArgs a, const m3ae_gemm_desc& d, hipStream_t s, float* det_ws = nullptr) {
     constexpr int lds = 4 * (256 + 256) * 32 * 2;
     const int64_t tiles = (d.M / 256) * (d.N / 256);
     const int64_t splits = tn_pp_splits(d, &a.k_chunk);
     a.splits = (int)splits;
-    if (det_ws) {
-        a.C = det_ws;
-        a.a_rowsum = d.a_rowsum ? det_ws + splits * d.M * d.N : nullptr;
-        static bool det_attr_set = false;
-        if (!det_attr_set) {
-            hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_pp_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            det_attr_set = true;
-        }
-        hipLaunchKernelGGL(gemm_tn_pp_kernel<true>, dim3((unsigned)(tiles * splits)), dim3(512), lds, s, a);
-        const int rc = hip_launch_status();
-        return rc ? rc : tn_det_fold(a, d, 256, 128, s);
-    }
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_pp_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(gemm_tn_pp_kernel<false>, dim3((unsigned)(tiles * splits)), dim3(512), lds, s, a);
-    return hip_launch_status();
+    if (det_ws) return tn_run<gemm_tn_pp_kernel<true>>(a, d, tiles * splits, 512, lds, 256, 128, det_ws, s);
+    return tn_run<gemm_tn_pp_kernel<false>>(a, d, tiles * splits, 512, lds, 256, 128, nullptr, s);
 }
 
 // split-K fan-out of the 128 x 128 TN kernels (lds = their LDS bytes)
@@ -1084,29 +1086,8 @@ static int launch_tn_t(MfmaArgs a, const m3ae_gemm_desc& d, hipStream_t s, float
     const int64_t tiles = (d.M / BM_) * (d.N / BN_);
     const int64_t splits = tn_t_splits(d, lds, &a.k_chunk);
     a.splits = (int)splits;
-    if (det_ws) {
-        a.C = det_ws;
-        a.a_rowsum = d.a_rowsum ? det_ws + splits * d.M * d.N : nullptr;
-        static bool det_attr_set = false;
-        if (!det_attr_set) {
-            hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel<BM_, BN_, WM, BKR, NST, true>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            det_attr_set = true;
-        }
-        hipLaunchKernelGGL((gemm_tn_bf16_kernel<BM_, BN_, WM, BKR, NST, true>), dim3((unsigned)(tiles * splits)), dim3(threads),
-                           lds, s, a);
-        const int rc = hip_launch_status();
-        return rc ? rc : tn_det_fold(a, d, BM_, WM, s);
-    }
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel<BM_, BN_, WM, BKR, NST>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((gemm_tn_bf16_kernel<BM_, BN_, WM, BKR, NST>), dim3((unsigned)(tiles * splits)), dim3(threads), lds,
-                       s, a);
-    return hip_launch_status();
+    if (det_ws) return tn_run<gemm_tn_bf16_kernel<BM_, BN_, WM, BKR, NST, true>>(a, d, tiles * splits, threads, lds, BM_, WM, det_ws, s);
+    return tn_run<gemm_tn_bf16_kernel<BM_, BN_, WM, BKR, NST>>(a, d, tiles * splits, threads, lds, BM_, WM, nullptr, s);
 }
 
 // which TN kernel a descriptor takes: 5 = 256 x 256 ping-pong, 2 = 128 x 128 with 32-row steps, 0 = with 64-row steps
@@ -1150,19 +1131,14 @@ extern "C" int m3ae_nt_trace_dump(uint64_t* host_out) {   // diagnostic build on
 }
 #endif
 
-extern "C" int m3ae_gemm(const m3ae_gemm_desc* dp, void* stream) {
-    if (!dp || !dp->A || !dp->B || !dp->C) return M3AE_ERR_ARG;
-    const m3ae_gemm_desc& d = *dp;
-    if (d.M <= 0 || d.N <= 0 || d.K <= 0 || d.batch1 <= 0 || d.batch2 <= 0) return M3AE_ERR_ARG;
-    // deterministic mode needs a workspace for its partial planes: m3ae_gemm_det takes one, this call cannot, and it never
-    // runs the atomic kernels under that flag
-    if (d.launch_flags & M3AE_GEMM_DETERMINISTIC) return M3AE_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
-    if ((d.launch_flags & M3AE_GEMM_F32_X3) && !d.force_generic) {   // fp32x3 mode (csrc/gemm_f32x3.hip): fp32 operands only
-        if (d.dtype_a != M3AE_F32 || d.dtype_b != M3AE_F32 || d.dtype_c != M3AE_F32) return M3AE_ERR_UNSUPPORTED;
-        g_last_path = "f32x3";
-        return m3ae_gemm_f32x3(d, s);
-    }
+// The routing rule, in one place: which kernel family takes a descriptor.  m3ae_gemm dispatches on it; deterministic mode
+// (m3ae_gemm_det, m3ae_gemm_det_workspace_bytes) asks it whether the descriptor is one of the split-K TN family, the only one
+// with several writers per output element.  Pointers are looked at for alignment only, so a size query with null operands and
+// no device classifies like the call it precedes.
+enum GemmRoute { ROUTE_BAD_DIMS, ROUTE_F32X3, ROUTE_NT, ROUTE_TN, ROUTE_GENERIC };
+static GemmRoute gemm_route(const m3ae_gemm_desc& d) {
+    if (d.M <= 0 || d.N <= 0 || d.K <= 0 || d.batch1 <= 0 || d.batch2 <= 0) return ROUTE_BAD_DIMS;
+    if ((d.launch_flags & M3AE_GEMM_F32_X3) && !d.force_generic) return ROUTE_F32X3;   // fp32x3 mode (csrc/gemm_f32x3.hip)
     const bool bf = d.dtype_a == M3AE_BF16 && d.dtype_b == M3AE_BF16;
     const bool single = d.batch1 == 1 && d.batch2 == 1;
     if (bf && single && !d.force_generic && d.c_sn == 1) {
@@ -1171,45 +1147,50 @@ extern "C" int m3ae_gemm(const m3ae_gemm_desc* dp, void* stream) {
                             (!d.dact_aux || aligned16(d.dact_aux)) && (!d.bias || aligned16(d.bias));
         // NT: both operands K-contiguous
         if (ptr_ok && !d.a_rowsum && d.a_sk == 1 && d.b_sk == 1 && d.K % BK == 0 && d.N % 4 == 0 && d.a_sm % 8 == 0 &&
-            d.b_sn % 8 == 0 && d.c_sm % 4 == 0 && d.M >= 1) {
-            g_last_path = "mfma_nt";
-            return launch_nt(d, s);
-        }
+            d.b_sn % 8 == 0 && d.c_sm % 4 == 0)
+            return ROUTE_NT;
         // TN: both operands reduction-strided (wgrad), fp32 output
         if (ptr_ok && d.a_sm == 1 && d.b_sn == 1 && d.dtype_c == M3AE_F32 && d.M % BM == 0 && d.N % BN == 0 &&
             d.a_sk % 8 == 0 && d.b_sk % 8 == 0 && !d.bias && d.act == M3AE_ACT_NONE && !d.preact && !d.residual &&
-            !d.dact_aux) {
-            g_last_path = "mfma_tn";
-            return launch_tn(d, s);
-        }
+            !d.dact_aux)
+            return ROUTE_TN;
     }
-    g_last_path = "generic";
-    return m3ae_gemm_generic(d, s);
+    return ROUTE_GENERIC;
+}
+
+extern "C" int m3ae_gemm(const m3ae_gemm_desc* dp, void* stream) {
+    if (!dp || !dp->A || !dp->B || !dp->C) return M3AE_ERR_ARG;
+    const m3ae_gemm_desc& d = *dp;
+    const GemmRoute route = gemm_route(d);
+    if (route == ROUTE_BAD_DIMS) return M3AE_ERR_ARG;
+    // deterministic mode needs a workspace for its partial planes: m3ae_gemm_det takes one, this call cannot, and it never
+    // runs the atomic kernels under that flag
+    if (d.launch_flags & M3AE_GEMM_DETERMINISTIC) return M3AE_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    switch (route) {
+    case ROUTE_F32X3:   // fp32 operands only
+        if (d.dtype_a != M3AE_F32 || d.dtype_b != M3AE_F32 || d.dtype_c != M3AE_F32) return M3AE_ERR_UNSUPPORTED;
+        g_last_path = "f32x3";
+        return m3ae_gemm_f32x3(d, s);
+    case ROUTE_NT:
+        g_last_path = "mfma_nt";
+        return launch_nt(d, s);
+    case ROUTE_TN:
+        g_last_path = "mfma_tn";
+        return launch_tn(d, s);
+    default:
+        g_last_path = "generic";
+        return m3ae_gemm_generic(d, s);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// Deterministic mode (M3AE_GEMM_DETERMINISTIC): the TN kernels with ordered split-K.  tn_takes() repeats m3ae_gemm's dispatch
-// conditions for the "mfma_tn" family (pointers are checked only where given, so the size query needs no device).
+// Deterministic mode (M3AE_GEMM_DETERMINISTIC): the TN kernels with ordered split-K.
 // ---------------------------------------------------------------------------------------------------------
-static bool tn_takes(const m3ae_gemm_desc& d) {
-    if (d.M <= 0 || d.N <= 0 || d.K <= 0 || d.batch1 != 1 || d.batch2 != 1) return false;
-    if ((d.launch_flags & M3AE_GEMM_F32_X3) && !d.force_generic) return false;
-    if (d.dtype_a != M3AE_BF16 || d.dtype_b != M3AE_BF16 || d.force_generic || d.c_sn != 1) return false;
-    const bool ptr_ok = aligned16(d.A) && aligned16(d.B) && aligned16(d.C) && (!d.preact || aligned16(d.preact)) &&
-                        (!d.residual || aligned16(d.residual)) && (!d.dact_aux || aligned16(d.dact_aux)) &&
-                        (!d.bias || aligned16(d.bias));
-    if (!ptr_ok) return false;
-    if (!d.a_rowsum && d.a_sk == 1 && d.b_sk == 1 && d.K % BK == 0 && d.N % 4 == 0 && d.a_sm % 8 == 0 && d.b_sn % 8 == 0 &&
-        d.c_sm % 4 == 0)
-        return false;   // the NT family comes first
-    return d.a_sm == 1 && d.b_sn == 1 && d.dtype_c == M3AE_F32 && d.M % BM == 0 && d.N % BN == 0 && d.a_sk % 8 == 0 &&
-           d.b_sk % 8 == 0 && !d.bias && d.act == M3AE_ACT_NONE && !d.preact && !d.residual && !d.dact_aux;
-}
-
 extern "C" int64_t m3ae_gemm_det_workspace_bytes(const m3ae_gemm_desc* dp) {
     if (!dp) return M3AE_ERR_ARG;
     const m3ae_gemm_desc& d = *dp;
-    if (!tn_takes(d)) return 0;   // every other kernel family has one writer per output element already
+    if (gemm_route(d) != ROUTE_TN) return 0;   // every other kernel family has one writer per output element already
     int64_t k_chunk = 0;
     const int k = tn_kernel_choice(d);
     const int64_t splits = k == 5 ? tn_pp_splits(d, &k_chunk) : tn_t_splits(d, k == 2 ? 2 * 256 * 32 * 2 : 2 * 256 * 64 * 2, &k_chunk);
@@ -1220,7 +1201,7 @@ extern "C" int m3ae_gemm_det(const m3ae_gemm_desc* dp, void* workspace, int64_t 
     if (!dp || !dp->A || !dp->B || !dp->C) return M3AE_ERR_ARG;
     const m3ae_gemm_desc& d = *dp;
     if (!(d.launch_flags & M3AE_GEMM_DETERMINISTIC)) return M3AE_ERR_ARG;
-    if (!tn_takes(d)) return M3AE_ERR_UNSUPPORTED;   // (such a descriptor needs no ordered form: plain m3ae_gemm, flag clear)
+    if (gemm_route(d) != ROUTE_TN) return M3AE_ERR_UNSUPPORTED;   // (such a descriptor needs no ordered form: plain m3ae_gemm, flag clear)
     if (!workspace || !aligned16(workspace) || workspace_bytes < m3ae_gemm_det_workspace_bytes(dp)) return M3AE_ERR_WORKSPACE;
     g_last_path = "mfma_tn";
     return launch_tn(d, (hipStream_t)stream, (float*)workspace);

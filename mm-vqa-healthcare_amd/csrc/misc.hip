@@ -2,6 +2,7 @@
 // column sums, losses, the fused AdamW update and dtype / layout conversions.  All are HBM-streaming kernels:
 // coalesced 4-16 B per lane, grid-stride, fp32 arithmetic.
 #include "common.h"
+#include "det_fold.h"
 
 namespace {
 
@@ -23,7 +24,8 @@ inline unsigned ew_grid(int64_t n) {
 
 // ---- column sum ------------------------------------------------------------------------------------------
 // workgroup = 32 column-groups (8 columns = 16 B bf16 / 2 x 16 B fp32 per lane per row) x 8 row-lanes; grid
-// (cdiv(N, 256), row_chunks); LDS-combine the row-lanes, one fp32 atomic per column per workgroup.
+// (cdiv(N, 256), row_chunks); LDS-combine the row-lanes, one fp32 atomic per column per workgroup.  DET (deterministic mode):
+// the workgroup stores its sums to row blockIdx.y of out = part[row_chunks][N] instead, for det_fold (det_fold.h).
 template <typename T> DEVINL void ld8(const T* p, float* x);
 template <> DEVINL void ld8<float>(const float* p, float* x) {
     const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
@@ -34,7 +36,7 @@ template <> DEVINL void ld8<bf16_t>(const bf16_t* p, float* x) {
 #pragma unroll
     for (int t = 0; t < 4; ++t) { x[2 * t] = __uint_as_float(v[t] << 16); x[2 * t + 1] = __uint_as_float(v[t] & 0xffff0000u); }
 }
-template <typename T, bool VEC>
+template <typename T, bool VEC, bool DET = false>
 __global__ __launch_bounds__(256) void colsum_kernel(const T* x, float* out, int64_t M, int64_t N, int64_t ldx,
                                                      int64_t rows_per) {
     __shared__ float red[8][32][9];
@@ -79,7 +81,10 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* x, float* out, int
             float s = 0.f;
 #pragma unroll
             for (int r = 0; r < 8; ++r) s += red[r][cg][t];
-            if (n0 + t < N) atomicAdd(out + n0 + t, s);
+            if (n0 + t < N) {
+                if constexpr (DET) out[(int64_t)blockIdx.y * N + n0 + t] = s;
+                else atomicAdd(out + n0 + t, s);
+            }
         }
     }
 }
@@ -261,9 +266,10 @@ __global__ void vit_tokens_bwd_kernel(const T* d_out, T* d_patch, float* d_cls, 
 }
 
 // ---- losses -----------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void bce_kernel(const T* x, const float* z, float* loss, T* dx, int64_t n, float inv_n, float C,
-                           float grad_scale) {
+// one fp32 atomic per wave; DET: one partial per workgroup in loss = part[workgroups]
+template <typename T, bool DET = false>
+__global__ __launch_bounds__(DET ? 256 : 1024) void bce_kernel(const T* x, const float* z, float* loss, T* dx, int64_t n,
+                                                               float inv_n, float C, float grad_scale) {
     float acc = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float xi = Elem<T>::ld(x + i), zi = z[i];
@@ -272,7 +278,14 @@ __global__ void bce_kernel(const T* x, const float* z, float* loss, T* dx, int64
         if (dx) Elem<T>::st(dx + i, (sig - zi) * inv_n * C * grad_scale);
     }
     acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) atomicAdd(loss, acc * inv_n * C);
+    if constexpr (DET) {
+        __shared__ float red[4];
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc * inv_n * C;
+        __syncthreads();
+        if (threadIdx.x == 0) loss[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    } else {
+        if ((threadIdx.x & 63) == 0) atomicAdd(loss, acc * inv_n * C);
+    }
 }
 
 // cross entropy: ws[0] = number of rows with label != -100 ; one workgroup per row
@@ -285,7 +298,8 @@ __global__ void xent_count_kernel(const int64_t* labels, float* ws, int64_t rows
     __syncthreads();
     if (threadIdx.x == 0) ws[0] = part[0] + part[1] + part[2] + part[3];
 }
-template <typename T>
+// DET: one partial per row in loss = part[rows] (0 for an ignored label) instead of the atomic
+template <typename T, bool DET = false>
 __global__ __launch_bounds__(256) void xent_kernel(const T* x, const int64_t* labels, float* loss, T* dx, const float* ws,
                                                    int64_t C, int64_t ld, float grad_scale) {
     __shared__ float red[4];
@@ -294,6 +308,7 @@ __global__ __launch_bounds__(256) void xent_kernel(const T* x, const int64_t* la
     const T* xr = x + row * ld;
     T* dr = dx ? dx + row * ld : nullptr;
     if (lab == -100) {
+        if (DET && threadIdx.x == 0) loss[row] = 0.f;
         if (dr) for (int64_t j = threadIdx.x; j < C; j += 256) Elem<T>::st(dr + j, 0.f);
         return;
     }
@@ -312,7 +327,10 @@ __global__ __launch_bounds__(256) void xent_kernel(const T* x, const int64_t* la
     sum = red[0] + red[1] + red[2] + red[3];
     const float inv_valid = 1.0f / ws[0];
     const float lse = mx + logf(sum);
-    if (threadIdx.x == 0) atomicAdd(loss, (lse - Elem<T>::ld(xr + lab)) * inv_valid);
+    if (threadIdx.x == 0) {
+        if constexpr (DET) loss[row] = (lse - Elem<T>::ld(xr + lab)) * inv_valid;
+        else atomicAdd(loss, (lse - Elem<T>::ld(xr + lab)) * inv_valid);
+    }
     if (dr) {
         const float gs = grad_scale * inv_valid;
         for (int64_t j = threadIdx.x; j < C; j += 256) {
@@ -322,99 +340,10 @@ __global__ __launch_bounds__(256) void xent_kernel(const T* x, const int64_t* la
     }
 }
 
-// ---- deterministic mode: ordered forms of the reductions above ---------------------------------------------------------
-// Every workgroup stores its partial into a workspace row of its own instead of adding it with an atomic; det_fold_kernel
-// then sums the rows in an order that depends on the row count alone.  One writer per output element.
+// ---- deterministic mode ---------------------------------------------------------------------------------------------------
+// The column sum and the three loss kernels carry their ordered form as a DET instance of the one kernel body (partials to a
+// workspace row per workgroup, folded by det_fold, det_fold.h).  The embedding backward is an algorithm of its own:
 //
-// out[i] (+)= scale * sum_b part[b][i], i < n (out1 != nullptr: columns >= n0 go to out1[i - n0]).  CL column lanes x
-// (256 / CL) row lanes per workgroup: row lane r adds rows r, r + RL, r + 2 RL, ... in ascending order, lane 0 adds the RL
-// lane sums in ascending order.
-template <int CL>
-__global__ __launch_bounds__(256) void det_fold_kernel(const float* __restrict__ part, float* __restrict__ out0,
-                                                       float* __restrict__ out1, int64_t count, int64_t n, int64_t n0,
-                                                       float scale, int accumulate) {
-    constexpr int RL = 256 / CL;
-    __shared__ float red[RL][CL + 1];
-    const int cl = threadIdx.x % CL, rl = threadIdx.x / CL;
-    const int64_t i = (int64_t)blockIdx.x * CL + cl;
-    float s = 0.f;
-    if (i < n)
-        for (int64_t b = rl; b < count; b += RL) s += part[b * n + i];
-    red[rl][cl] = s;
-    __syncthreads();
-    if (rl == 0 && i < n) {
-        float t = 0.f;
-#pragma unroll
-        for (int r = 0; r < RL; ++r) t += red[r][cl];
-        float* o = (out1 && i >= n0) ? out1 + (i - n0) : out0 + i;
-        *o = accumulate ? *o + t * scale : t * scale;
-    }
-}
-inline void det_fold(const float* part, float* out0, float* out1, int64_t count, int64_t n, int64_t n0, float scale,
-                     int accumulate, hipStream_t s) {
-    if (n <= 2) hipLaunchKernelGGL(det_fold_kernel<2>, dim3(1), dim3(256), 0, s, part, out0, out1, count, n, n0, scale, accumulate);
-    else hipLaunchKernelGGL(det_fold_kernel<32>, dim3((unsigned)cdiv(n, 32)), dim3(256), 0, s, part, out0, out1, count, n, n0, scale, accumulate);
-}
-
-// column sum: colsum_kernel's walk over a row chunk, the chunk's sums stored to part[chunk][N]
-template <typename T, bool VEC>
-__global__ __launch_bounds__(256) void colsum_det_kernel(const T* x, float* part, int64_t M, int64_t N, int64_t ldx,
-                                                         int64_t rows_per) {
-    __shared__ float red[8][32][9];
-    const int cg = threadIdx.x & 31, rl = threadIdx.x >> 5;
-    const int64_t n0 = (int64_t)blockIdx.x * 256 + cg * 8;
-    const int64_t r0 = (int64_t)blockIdx.y * rows_per;
-    int64_t r1 = r0 + rows_per;
-    if (r1 > M) r1 = M;
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (n0 < N) {
-        int64_t r = r0 + rl;
-        if (VEC) {
-            for (; r + 24 < r1; r += 32) {
-                float v[4][8];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) ld8<T>(x + (r + 8 * u) * ldx + n0, v[u]);
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int t = 0; t < 8; ++t) acc[t] += v[u][t];
-            }
-        }
-        for (; r < r1; r += 8) {
-            if (VEC) {
-                float v[8];
-                ld8<T>(x + r * ldx + n0, v);
-#pragma unroll
-                for (int t = 0; t < 8; ++t) acc[t] += v[t];
-            } else {
-#pragma unroll
-                for (int t = 0; t < 8; ++t)
-                    if (n0 + t < N) acc[t] += Elem<T>::ld(x + r * ldx + n0 + t);
-            }
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 8; ++t) red[rl][cg][t] = acc[t];
-    __syncthreads();
-    if (rl == 0 && n0 < N) {
-#pragma unroll
-        for (int t = 0; t < 8; ++t) {
-            float s = 0.f;
-#pragma unroll
-            for (int r = 0; r < 8; ++r) s += red[r][cg][t];
-            if (n0 + t < N) part[(int64_t)blockIdx.y * N + n0 + t] = s;
-        }
-    }
-}
-inline int64_t colsum_det_chunks(int64_t M, int64_t N, int64_t* rows_per) {
-    const int64_t col_blocks = cdiv(N, 256);
-    int64_t chunks = cdiv(1024, col_blocks);  // ~1024 workgroups in flight, as m3ae_colsum's 256-column form
-    if (chunks > cdiv(M, 64)) chunks = cdiv(M, 64);
-    if (chunks < 1) chunks = 1;
-    *rows_per = cdiv(M, chunks);
-    return cdiv(M, *rows_per);
-}
-
 // RoBERTa embedding backward with duplicate ids.  keys[0][t] = word id, keys[1][t] = position id of token t (flat [B * S]).
 // Workgroup (t, table): token t OWNS its table row if no earlier token carries the same key; the owner adds the d_out rows of
 // every token with that key in ASCENDING TOKEN ORDER (itself first) in registers and then adds the sum into the table row;
@@ -477,61 +406,6 @@ __global__ __launch_bounds__(256) void roberta_embed_bwd_det_kernel(const int* _
     for (int v = 0; v < MAXV; ++v) {
         const int64_t d = threadIdx.x + 256 * v;
         if (d < D) table[(int64_t)key * D + d] += acc[v];
-    }
-}
-
-// losses: one partial per workgroup (BCE, MIM) or per row (cross entropy), folded by det_fold_kernel
-template <typename T>
-__global__ __launch_bounds__(256) void bce_det_kernel(const T* x, const float* z, float* part, T* dx, int64_t n, float inv_n,
-                                                      float C, float grad_scale) {
-    __shared__ float red[4];
-    float acc = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float xi = Elem<T>::ld(x + i), zi = z[i];
-        acc += fmaxf(xi, 0.f) - xi * zi + log1pf(expf(-fabsf(xi)));
-        const float sig = 1.0f / (1.0f + expf(-xi));
-        if (dx) Elem<T>::st(dx + i, (sig - zi) * inv_n * C * grad_scale);
-    }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc * inv_n * C;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-template <typename T>
-__global__ __launch_bounds__(256) void xent_det_kernel(const T* x, const int64_t* labels, float* part, T* dx, const float* ws,
-                                                       int64_t C, int64_t ld, float grad_scale) {
-    __shared__ float red[4];
-    const int64_t row = blockIdx.x;
-    const int64_t lab = labels[row];
-    const T* xr = x + row * ld;
-    T* dr = dx ? dx + row * ld : nullptr;
-    if (lab == -100) {
-        if (threadIdx.x == 0) part[row] = 0.f;
-        if (dr) for (int64_t j = threadIdx.x; j < C; j += 256) Elem<T>::st(dr + j, 0.f);
-        return;
-    }
-    float mx = -INFINITY;
-    for (int64_t j = threadIdx.x; j < C; j += 256) mx = fmaxf(mx, Elem<T>::ld(xr + j));
-    mx = wave_max(mx);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    __syncthreads();
-    float sum = 0.f;
-    for (int64_t j = threadIdx.x; j < C; j += 256) sum += expf(Elem<T>::ld(xr + j) - mx);
-    sum = wave_sum(sum);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
-    __syncthreads();
-    sum = red[0] + red[1] + red[2] + red[3];
-    const float inv_valid = 1.0f / ws[0];
-    const float lse = mx + logf(sum);
-    if (threadIdx.x == 0) part[row] = (lse - Elem<T>::ld(xr + lab)) * inv_valid;
-    if (dr) {
-        const float gs = grad_scale * inv_valid;
-        for (int64_t j = threadIdx.x; j < C; j += 256) {
-            const float p = expf(Elem<T>::ld(xr + j) - lse);
-            Elem<T>::st(dr + j, (p - (j == lab ? 1.f : 0.f)) * gs);
-        }
     }
 }
 
@@ -726,36 +600,53 @@ extern "C" void m3ae_desc_sizes(int64_t out3[3]) {
     out3[0] = (int64_t)sizeof(m3ae_gemm_desc); out3[1] = (int64_t)sizeof(m3ae_attn_desc); out3[2] = (int64_t)sizeof(m3ae_xattn_desc);
 }
 
+// row chunking of the 256-column form: ~1024 workgroups in flight, at least 64 rows each; returns the chunk count
+static int64_t colsum_chunks(int64_t M, int64_t N, int64_t* rows_per) {
+    int64_t chunks = cdiv(1024, cdiv(N, 256));
+    if (chunks > cdiv(M, 64)) chunks = cdiv(M, 64);
+    if (chunks < 1) chunks = 1;
+    *rows_per = cdiv(M, chunks);
+    return cdiv(M, *rows_per);
+}
+// part == nullptr: fp32 atomics into out; else deterministic mode, part[chunks][N] folded into out in chunk order
+static int colsum_impl(const void* x, float* out, int64_t M, int64_t N, int64_t ldx, int dtype, int accumulate, float* part,
+                       hipStream_t s) {
+    if (!part) {
+        if (!accumulate) {
+            hipError_t e = hipMemsetAsync(out, 0, N * sizeof(float), s);
+            if (e != hipSuccess) return (int)e;
+        }
+        if (N % 8 == 0 && ldx == N && N / 8 <= 512 && M >= 4096 && ((((uintptr_t)x) & 15) == 0) &&
+            (dtype == M3AE_BF16 || dtype == M3AE_F32)) {
+            const int P = (int)(N / 8), R = 512 / P;
+            int64_t nwg = 2048;                      // 8 workgroups per CU
+            int64_t rows_per = cdiv(cdiv(M, nwg), (int64_t)4 * R) * 4 * R;   // whole unrolled passes
+            nwg = cdiv(M, rows_per);
+            const size_t lds = (size_t)R * N * sizeof(float);
+            DT_SWITCH(dtype, hipLaunchKernelGGL((colsum_rows_kernel<T>), dim3((unsigned)nwg), dim3((unsigned)(P * R)), lds, s,
+                                                (const T*)x, out, M, P, R, rows_per));
+            return hip_launch_status();
+        }
+    }
+    int64_t rows_per = 0;
+    const int64_t chunks = colsum_chunks(M, N, &rows_per);
+    dim3 grid((unsigned)cdiv(N, 256), (unsigned)chunks);
+    const bool vec = (N % 8 == 0) && (ldx % 8 == 0) && ((((uintptr_t)x) & 15) == 0);
+#define COLSUM_LAUNCH(VEC, DET, DST) \
+    DT_SWITCH(dtype, hipLaunchKernelGGL((colsum_kernel<T, VEC, DET>), grid, dim3(256), 0, s, (const T*)x, DST, M, N, ldx, rows_per))
+    if (!part) { if (vec) COLSUM_LAUNCH(true, false, out); else COLSUM_LAUNCH(false, false, out); }
+    else if (vec) COLSUM_LAUNCH(true, true, part);
+    else COLSUM_LAUNCH(false, true, part);
+#undef COLSUM_LAUNCH
+    const int rc = hip_launch_status();
+    if (rc || !part) return rc;
+    det_fold(part, out, nullptr, chunks, N, N, N, 1.0f, accumulate, s);
+    return hip_launch_status();
+}
 extern "C" int m3ae_colsum(const void* x, float* out, int64_t M, int64_t N, int64_t ldx, int dtype, int accumulate,
                            void* stream) {
     if (!x || !out || M <= 0 || N <= 0) return M3AE_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    if (!accumulate) {
-        hipError_t e = hipMemsetAsync(out, 0, N * sizeof(float), s);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (N % 8 == 0 && ldx == N && N / 8 <= 512 && M >= 4096 && ((((uintptr_t)x) & 15) == 0) &&
-        (dtype == M3AE_BF16 || dtype == M3AE_F32)) {
-        const int P = (int)(N / 8), R = 512 / P;
-        int64_t nwg = 2048;                      // 8 workgroups per CU
-        int64_t rows_per = cdiv(cdiv(M, nwg), (int64_t)4 * R) * 4 * R;   // whole unrolled passes
-        nwg = cdiv(M, rows_per);
-        const size_t lds = (size_t)R * N * sizeof(float);
-        DT_SWITCH(dtype, hipLaunchKernelGGL((colsum_rows_kernel<T>), dim3((unsigned)nwg), dim3((unsigned)(P * R)), lds, s,
-                                            (const T*)x, out, M, P, R, rows_per));
-        return hip_launch_status();
-    }
-    const int64_t col_blocks = cdiv(N, 256);
-    int64_t chunks = cdiv(1024, col_blocks);  // ~1024 workgroups in flight
-    if (chunks > cdiv(M, 64)) chunks = cdiv(M, 64);
-    if (chunks < 1) chunks = 1;
-    const int64_t rows_per = cdiv(M, chunks);
-    chunks = cdiv(M, rows_per);
-    dim3 grid((unsigned)col_blocks, (unsigned)chunks);
-    const bool vec = (N % 8 == 0) && (ldx % 8 == 0) && ((((uintptr_t)x) & 15) == 0);
-    if (vec) { DT_SWITCH(dtype, hipLaunchKernelGGL((colsum_kernel<T, true>), grid, dim3(256), 0, s, (const T*)x, out, M, N, ldx, rows_per)); }
-    else { DT_SWITCH(dtype, hipLaunchKernelGGL((colsum_kernel<T, false>), grid, dim3(256), 0, s, (const T*)x, out, M, N, ldx, rows_per)); }
-    return hip_launch_status();
+    return colsum_impl(x, out, M, N, ldx, dtype, accumulate, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int m3ae_roberta_embed_fwd(const int64_t* ids, const float* word, const float* pos, const float* type,
@@ -823,30 +714,53 @@ extern "C" int m3ae_vit_tokens_bwd(const void* d_out, void* d_patch, float* d_cl
     return hip_launch_status();
 }
 
-extern "C" int m3ae_bce_logits(const void* logits, const float* targets, float* loss, void* d_logits, int64_t B,
-                               int64_t C, float grad_scale, int dtype, void* stream) {
-    if (!logits || !targets || !loss || B <= 0 || C <= 0) return M3AE_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
+// part == nullptr: one fp32 atomic per wave into loss; else deterministic mode, part[workgroups] folded into loss
+constexpr unsigned BCE_MAX_GRID = 64;
+static int bce_impl(const void* logits, const float* targets, float* loss, void* d_logits, int64_t B, int64_t C, float grad_scale,
+                    int dtype, float* part, hipStream_t s) {
+    const int64_t n = B * C;
+    const unsigned grid = ew_grid(n) > BCE_MAX_GRID ? BCE_MAX_GRID : ew_grid(n);
+    if (part) {
+        DT_SWITCH(dtype, hipLaunchKernelGGL((bce_kernel<T, true>), dim3(grid), dim3(EW_BLOCK), 0, s, (const T*)logits, targets, part,
+                                            (T*)d_logits, n, 1.0f / (float)n, (float)C, grad_scale));
+        det_fold(part, loss, nullptr, grid, 1, 1, 1, 1.0f, 0, s);
+        return hip_launch_status();
+    }
     hipError_t e = hipMemsetAsync(loss, 0, sizeof(float), s);
     if (e != hipSuccess) return (int)e;
-    const int64_t n = B * C;
-    unsigned grid = ew_grid(n);
-    if (grid > 64) grid = 64;
     DT_SWITCH(dtype, hipLaunchKernelGGL(bce_kernel<T>, dim3(grid), dim3(EW_BLOCK), 0, s, (const T*)logits, targets, loss,
                                         (T*)d_logits, n, 1.0f / (float)n, (float)C, grad_scale));
     return hip_launch_status();
 }
+extern "C" int m3ae_bce_logits(const void* logits, const float* targets, float* loss, void* d_logits, int64_t B,
+                               int64_t C, float grad_scale, int dtype, void* stream) {
+    if (!logits || !targets || !loss || B <= 0 || C <= 0) return M3AE_ERR_ARG;
+    return bce_impl(logits, targets, loss, d_logits, B, C, grad_scale, dtype, nullptr, (hipStream_t)stream);
+}
 
+// count[0] = number of labelled rows; part == nullptr: one fp32 atomic per row into loss; else deterministic mode, part[rows]
+// folded into loss
+static int xent_impl(const void* logits, const int64_t* labels, float* loss, void* d_logits, float* count, int64_t rows, int64_t C,
+                     int64_t ld, float grad_scale, int dtype, float* part, hipStream_t s) {
+    if (!part) {
+        hipError_t e = hipMemsetAsync(loss, 0, sizeof(float), s);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(xent_count_kernel, dim3(1), dim3(256), 0, s, labels, count, rows);
+    if (part) {
+        DT_SWITCH(dtype, hipLaunchKernelGGL((xent_kernel<T, true>), dim3((unsigned)rows), dim3(256), 0, s, (const T*)logits, labels,
+                                            part, (T*)d_logits, count, C, ld, grad_scale));
+        det_fold(part, loss, nullptr, rows, 1, 1, 1, 1.0f, 0, s);
+    } else {
+        DT_SWITCH(dtype, hipLaunchKernelGGL(xent_kernel<T>, dim3((unsigned)rows), dim3(256), 0, s, (const T*)logits, labels,
+                                            loss, (T*)d_logits, count, C, ld, grad_scale));
+    }
+    return hip_launch_status();
+}
 extern "C" int m3ae_xent(const void* logits, const int64_t* labels, float* loss, void* d_logits, float* workspace,
                          int64_t rows, int64_t C, int64_t ld, float grad_scale, int dtype, void* stream) {
     if (!logits || !labels || !loss || !workspace || rows <= 0 || C <= 0) return M3AE_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(loss, 0, sizeof(float), s);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(xent_count_kernel, dim3(1), dim3(256), 0, s, labels, workspace, rows);
-    DT_SWITCH(dtype, hipLaunchKernelGGL(xent_kernel<T>, dim3((unsigned)rows), dim3(256), 0, s, (const T*)logits, labels,
-                                        loss, (T*)d_logits, workspace, C, ld, grad_scale));
-    return hip_launch_status();
+    return xent_impl(logits, labels, loss, d_logits, workspace, rows, C, ld, grad_scale, dtype, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int m3ae_adamw(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr,
@@ -1015,8 +929,8 @@ __global__ void mim_targets_kernel(const float* __restrict__ img, float* __restr
 
 // objectives.py:58-62: loss = sum_n mask[n] mean_d (x[n][d] - t[n][d])^2 / sum_n mask[n].  x is the decoder output WITH its
 // class row ([B, L + 1, D], row 0 of every sample skipped: prediction_heads.py:86), t / mask are [B, L, ...].
-// acc[0] += masked per-patch errors, acc[1] += mask (fp32 atomics, one per wave).
-template <typename T>
+// acc[0] += masked per-patch errors, acc[1] += mask (fp32 atomics); DET: acc = part[workgroups][2] instead.
+template <typename T, bool DET = false>
 __global__ void mim_loss_fwd_kernel(const T* __restrict__ x, const float* __restrict__ t, const float* __restrict__ mask,
                                     float* __restrict__ acc, int64_t N, int L, int D) {
     // grid-stride over rows, sums kept per wave, one pair of atomics per WORKGROUP (one pair per row serialised 55 k
@@ -1037,35 +951,16 @@ __global__ void mim_loss_fwd_kernel(const T* __restrict__ x, const float* __rest
     if (lane == 0) { red[wave][0] = num; red[wave][1] = den; }
     __syncthreads();
     if (threadIdx.x == 0) {
-        atomicAdd(acc, (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]));
-        atomicAdd(acc + 1, (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]));
+        if constexpr (DET) {
+            acc[2 * blockIdx.x] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
+            acc[2 * blockIdx.x + 1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
+        } else {
+            atomicAdd(acc, (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]));
+            atomicAdd(acc + 1, (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]));
+        }
     }
 }
 __global__ void mim_loss_finalize_kernel(const float* __restrict__ acc, float* __restrict__ loss) { loss[0] = acc[0] / acc[1]; }
-// deterministic mode: part[workgroup][2] instead of the two atomics
-template <typename T>
-__global__ void mim_loss_fwd_det_kernel(const T* __restrict__ x, const float* __restrict__ t, const float* __restrict__ mask,
-                                        float* __restrict__ part, int64_t N, int L, int D) {
-    __shared__ float red[4][2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float num = 0.f, den = 0.f;
-    for (int64_t n = (int64_t)blockIdx.x * 4 + wave; n < N; n += (int64_t)gridDim.x * 4) {
-        const float m = mask[n];
-        if (m == 0.f) continue;
-        const T* xr = x + ((n / L) * (L + 1) + 1 + n % L) * (int64_t)D;
-        const float* tr = t + n * (int64_t)D;
-        float ss = 0.f;
-        for (int d = lane; d < D; d += 64) { const float e = Elem<T>::ld(xr + d) - tr[d]; ss += e * e; }
-        num += m * wave_sum(ss) / (float)D;
-        den += m;
-    }
-    if (lane == 0) { red[wave][0] = num; red[wave][1] = den; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = (red[0][0] + red[1][0]) + (red[2][0] + red[3][0]);
-        part[2 * blockIdx.x + 1] = (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]);
-    }
-}
 // dx[b][0][:] = 0 ;  dx[b][1 + l][d] = gout * 2 (x - t) mask / (D * sum mask)
 template <typename T>
 __global__ void mim_loss_bwd_kernel(const T* __restrict__ x, const float* __restrict__ t, const float* __restrict__ mask,
@@ -1105,16 +1000,27 @@ extern "C" int m3ae_mim_targets(const float* img, float* out, int64_t B, int64_t
                        (int)C, (int)H, (int)W, (int)P, norm_pix);
     return hip_launch_status();
 }
+static int64_t mim_fwd_blocks(int64_t rows) { return cdiv(rows, 4) < 1024 ? cdiv(rows, 4) : 1024; }
+// part == nullptr: two fp32 atomics per workgroup into acc; else deterministic mode, part[workgroups][2] folded into acc
+static int mim_loss_fwd_impl(const void* x, const float* target, const float* mask, float* acc, float* loss, int64_t B, int64_t L,
+                             int64_t D, int dtype, float* part, hipStream_t s) {
+    const int64_t fwd_blocks = mim_fwd_blocks(B * L);
+    if (part) {
+        DT_SWITCH(dtype, hipLaunchKernelGGL((mim_loss_fwd_kernel<T, true>), dim3((unsigned)fwd_blocks), dim3(256), 0, s, (const T*)x,
+                                            target, mask, part, B * L, (int)L, (int)D));
+        det_fold(part, acc, nullptr, fwd_blocks, 2, 2, 2, 1.0f, 0, s);
+    } else {
+        { const hipError_t e = hipMemsetAsync(acc, 0, 2 * sizeof(float), s); if (e != hipSuccess) return (int)e; }
+        DT_SWITCH(dtype, hipLaunchKernelGGL(mim_loss_fwd_kernel<T>, dim3((unsigned)fwd_blocks), dim3(256), 0, s, (const T*)x,
+                                            target, mask, acc, B * L, (int)L, (int)D));
+    }
+    hipLaunchKernelGGL(mim_loss_finalize_kernel, dim3(1), dim3(1), 0, s, acc, loss);
+    return hip_launch_status();
+}
 extern "C" int m3ae_mim_loss_fwd(const void* x, const float* target, const float* mask, float* acc, float* loss, int64_t B,
                                  int64_t L, int64_t D, int dtype, void* stream) {
     if (!x || !target || !mask || !acc || !loss || B <= 0 || L <= 0 || D <= 0) return M3AE_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    { const hipError_t e = hipMemsetAsync(acc, 0, 2 * sizeof(float), s); if (e != hipSuccess) return (int)e; }
-    const int64_t fwd_blocks = cdiv(B * L, 4) < 1024 ? cdiv(B * L, 4) : 1024;
-    DT_SWITCH(dtype, hipLaunchKernelGGL(mim_loss_fwd_kernel<T>, dim3((unsigned)fwd_blocks), dim3(256), 0, s, (const T*)x,
-                                        target, mask, acc, B * L, (int)L, (int)D));
-    hipLaunchKernelGGL(mim_loss_finalize_kernel, dim3(1), dim3(1), 0, s, acc, loss);
-    return hip_launch_status();
+    return mim_loss_fwd_impl(x, target, mask, acc, loss, B, L, D, dtype, nullptr, (hipStream_t)stream);
 }
 extern "C" int m3ae_mim_loss_bwd(const void* x, const float* target, const float* mask, const float* acc, const float* gout,
                                  void* dx, int64_t B, int64_t L, int64_t D, int dtype, void* stream) {
@@ -1127,16 +1033,15 @@ extern "C" int m3ae_mim_loss_bwd(const void* x, const float* target, const float
 
 // ---- deterministic mode: entry points (include/m3ae_hip.h) ---------------------------------------------------------------
 static int64_t det_align(int64_t bytes) { return (bytes + 255) / 256 * 256; }
-static int64_t mim_fwd_blocks(int64_t rows) { return cdiv(rows, 4) < 1024 ? cdiv(rows, 4) : 1024; }
 
 extern "C" int64_t m3ae_det_workspace_bytes(int op, int64_t rows, int64_t cols) {
     if (rows <= 0 || cols <= 0) return M3AE_ERR_ARG;
     int64_t rows_per = 0;
     switch (op) {
-    case M3AE_DET_COLSUM: return det_align(colsum_det_chunks(rows, cols, &rows_per) * cols * (int64_t)sizeof(float));
+    case M3AE_DET_COLSUM: return det_align(colsum_chunks(rows, cols, &rows_per) * cols * (int64_t)sizeof(float));
     case M3AE_DET_EMBED_BWD:   // rows = B * S tokens, cols = D: two key rows, then the token-type column sum's partials
         return det_align(2 * rows * (int64_t)sizeof(int)) + m3ae_det_workspace_bytes(M3AE_DET_COLSUM, rows, cols);
-    case M3AE_DET_BCE: return det_align(64 * (int64_t)sizeof(float));
+    case M3AE_DET_BCE: return det_align(BCE_MAX_GRID * (int64_t)sizeof(float));
     case M3AE_DET_XENT: return det_align((1 + rows) * (int64_t)sizeof(float));   // the count of m3ae_xent's workspace, then one partial per row
     case M3AE_DET_MIM: return det_align(2 * mim_fwd_blocks(rows) * (int64_t)sizeof(float));   // rows = B * L
     default: return M3AE_ERR_ARG;
@@ -1147,18 +1052,7 @@ extern "C" int m3ae_colsum_det(const void* x, float* out, int64_t M, int64_t N, 
                                void* workspace, int64_t workspace_bytes, void* stream) {
     if (!x || !out || M <= 0 || N <= 0) return M3AE_ERR_ARG;
     if (!workspace || workspace_bytes < m3ae_det_workspace_bytes(M3AE_DET_COLSUM, M, N)) return M3AE_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    int64_t rows_per = 0;
-    const int64_t chunks = colsum_det_chunks(M, N, &rows_per);
-    dim3 grid((unsigned)cdiv(N, 256), (unsigned)chunks);
-    float* part = (float*)workspace;
-    const bool vec = (N % 8 == 0) && (ldx % 8 == 0) && ((((uintptr_t)x) & 15) == 0);
-    if (vec) { DT_SWITCH(dtype, hipLaunchKernelGGL((colsum_det_kernel<T, true>), grid, dim3(256), 0, s, (const T*)x, part, M, N, ldx, rows_per)); }
-    else { DT_SWITCH(dtype, hipLaunchKernelGGL((colsum_det_kernel<T, false>), grid, dim3(256), 0, s, (const T*)x, part, M, N, ldx, rows_per)); }
-    int rc = hip_launch_status();
-    if (rc) return rc;
-    det_fold(part, out, nullptr, chunks, N, N, 1.0f, accumulate, s);
-    return hip_launch_status();
+    return colsum_impl(x, out, M, N, ldx, dtype, accumulate, (float*)workspace, (hipStream_t)stream);
 }
 
 extern "C" int m3ae_roberta_embed_bwd_det(const int64_t* ids, const void* d_out, float* d_word, float* d_pos, float* d_type,
@@ -1186,38 +1080,20 @@ extern "C" int m3ae_bce_logits_det(const void* logits, const float* targets, flo
                                    float grad_scale, int dtype, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!logits || !targets || !loss || B <= 0 || C <= 0) return M3AE_ERR_ARG;
     if (!workspace || workspace_bytes < m3ae_det_workspace_bytes(M3AE_DET_BCE, B, C)) return M3AE_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t n = B * C;
-    unsigned grid = ew_grid(n);
-    if (grid > 64) grid = 64;
-    DT_SWITCH(dtype, hipLaunchKernelGGL(bce_det_kernel<T>, dim3(grid), dim3(EW_BLOCK), 0, s, (const T*)logits, targets,
-                                        (float*)workspace, (T*)d_logits, n, 1.0f / (float)n, (float)C, grad_scale));
-    det_fold((const float*)workspace, loss, nullptr, grid, 1, 1, 1.0f, 0, s);
-    return hip_launch_status();
+    return bce_impl(logits, targets, loss, d_logits, B, C, grad_scale, dtype, (float*)workspace, (hipStream_t)stream);
 }
 
 extern "C" int m3ae_xent_det(const void* logits, const int64_t* labels, float* loss, void* d_logits, int64_t rows, int64_t C,
                              int64_t ld, float grad_scale, int dtype, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!logits || !labels || !loss || rows <= 0 || C <= 0) return M3AE_ERR_ARG;
     if (!workspace || workspace_bytes < m3ae_det_workspace_bytes(M3AE_DET_XENT, rows, C)) return M3AE_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    float* ws = (float*)workspace;
-    hipLaunchKernelGGL(xent_count_kernel, dim3(1), dim3(256), 0, s, labels, ws, rows);
-    DT_SWITCH(dtype, hipLaunchKernelGGL(xent_det_kernel<T>, dim3((unsigned)rows), dim3(256), 0, s, (const T*)logits, labels,
-                                        ws + 1, (T*)d_logits, ws, C, ld, grad_scale));
-    det_fold(ws + 1, loss, nullptr, rows, 1, 1, 1.0f, 0, s);
-    return hip_launch_status();
+    float* ws = (float*)workspace;   // the count of m3ae_xent's workspace, then one partial per row
+    return xent_impl(logits, labels, loss, d_logits, ws, rows, C, ld, grad_scale, dtype, ws + 1, (hipStream_t)stream);
 }
 
 extern "C" int m3ae_mim_loss_fwd_det(const void* x, const float* target, const float* mask, float* acc, float* loss, int64_t B,
                                      int64_t L, int64_t D, int dtype, void* workspace, int64_t workspace_bytes, void* stream) {
     if (!x || !target || !mask || !acc || !loss || B <= 0 || L <= 0 || D <= 0) return M3AE_ERR_ARG;
     if (!workspace || workspace_bytes < m3ae_det_workspace_bytes(M3AE_DET_MIM, B * L, D)) return M3AE_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t fwd_blocks = mim_fwd_blocks(B * L);
-    DT_SWITCH(dtype, hipLaunchKernelGGL(mim_loss_fwd_det_kernel<T>, dim3((unsigned)fwd_blocks), dim3(256), 0, s, (const T*)x,
-                                        target, mask, (float*)workspace, B * L, (int)L, (int)D));
-    det_fold((const float*)workspace, acc, nullptr, fwd_blocks, 2, 2, 1.0f, 0, s);
-    hipLaunchKernelGGL(mim_loss_finalize_kernel, dim3(1), dim3(1), 0, s, acc, loss);
-    return hip_launch_status();
+    return mim_loss_fwd_impl(x, target, mask, acc, loss, B, L, D, dtype, (float*)workspace, (hipStream_t)stream);
 }

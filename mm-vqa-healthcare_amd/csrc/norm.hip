@@ -6,6 +6,7 @@
 // Backward keeps per-lane partial dgamma/dbeta over the rows a wave walks, combines the 4 waves of a workgroup in
 // LDS, writes one partial row per workgroup, and a second kernel folds the partials into the fp32 gradients.
 #include "common.h"
+#include "det_fold.h"
 
 namespace {
 
@@ -346,32 +347,13 @@ __global__ __launch_bounds__(256) void ln_bwd_reduce_kernel(const float* part, f
     }
 }
 
-// deterministic mode: the same fold with ONE workgroup per column block walking all nblk partial rows (row lane r adds rows
-// r, r + 8, ... in ascending order, lane 0 adds the eight lane sums in ascending order), so every column has one writer and
-// the order of the sum depends on nblk alone
-__global__ __launch_bounds__(256) void ln_bwd_reduce_det_kernel(const float* part, float* dgamma, float* dbeta, int nblk, int D) {
-    __shared__ float red[8][33];
-    const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
-    const int i = blockIdx.x * 32 + cl;  // index into [2][D]
-    float s = 0.f;
-    if (i < 2 * D) {
-        const int which = i / D, col = i - which * D;
-        for (int b = rl; b < nblk; b += 8) s += part[((int64_t)b * 2 + which) * D + col];
-    }
-    red[rl][cl] = s;
-    __syncthreads();
-    if (rl == 0 && i < 2 * D) {
-        float t = 0.f;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) t += red[r][cl];
-        const int which = i / D, col = i - which * D;
-        if (which == 0) dgamma[col] += t;
-        else if (dbeta) dbeta[col] += t;
-    }
-}
+// deterministic mode: det_fold (det_fold.h) over the same partial rows, [nblk] rows of [2][D]: ONE workgroup per column block
+// walks all nblk rows (row lane r adds rows r, r + 8, ... in ascending order, lane 0 adds the eight lane sums in ascending
+// order), so every column has one writer and the order of the sum depends on nblk alone.  Without dbeta (RMS norm) only the
+// dgamma half of every row is folded.
 inline int ln_bwd_fold(const float* part, float* dgamma, float* dbeta, int nblk, int D, int det, hipStream_t s) {
     if (det)
-        hipLaunchKernelGGL(ln_bwd_reduce_det_kernel, dim3((unsigned)cdiv(2 * D, 32)), dim3(256), 0, s, part, dgamma, dbeta, nblk, D);
+        det_fold(part, dgamma, dbeta, nblk, dbeta ? 2 * D : D, 2 * D, D, 1.0f, 1, s);
     else
         hipLaunchKernelGGL(ln_bwd_reduce_kernel, dim3((unsigned)cdiv(2 * D, 32), (unsigned)cdiv(nblk, 64)), dim3(256), 0, s, part, dgamma,
                            dbeta, nblk, D);
