@@ -35,6 +35,8 @@ extern "C" {
 /* 4: attention maps.  m3ae_attn_probs (the probabilities of an m3ae_attn_fwd call, recomputed from its log-sum-exp table) and
  *    m3ae_xattn_probs_export (the probabilities a fused cross-attention call left in `probs` / `probs_drop`), both as fp32
  *    [B][H][Lq][Lk]; no descriptor changed. */
+/* 4 (additive): device image transform.  m3ae_image_resample_u8 / m3ae_image_resample_workspace_bytes (Pillow-exact bicubic resize +
+ *    centre crop + ToTensor / Normalize from the decoded source bytes); no descriptor changed. */
 #define M3AE_ABI_VERSION 4
 
 enum { M3AE_F32 = 0, M3AE_BF16 = 1 };
@@ -320,6 +322,30 @@ int m3ae_patchify(const float* img, void* out, int64_t B, int64_t R, int64_t P, 
  * fp32 [B, 3, H, W] with out = (u / 255 - mean[c]) / std[c], the same two IEEE divisions torch performs. */
 int m3ae_image_normalize_u8(const uint8_t* in, float* out, int64_t B, int64_t H, int64_t W, const float* mean3,
                             const float* std3, void* stream);
+/* Device image transform (csrc/image.hip): transforms/transform.py:60-67 whole -- Resize(size, BICUBIC) on the 8-bit image,
+ * CenterCrop(size), ToTensor, Normalize -- for a batch of B decoded, OPAQUE sources of any sizes, in two launches.  The resize is
+ * Pillow's fixed-point arithmetic (libImaging/Resample.c, 8 bits per channel): per pass and channel
+ *     out = clamp((2^21 + sum_t pixel[xmin + t] * k[t]) >> 22, 0, 255)      (int32, arithmetic shift),
+ * horizontal pass first into a uint8 intermediate (its rounding is part of the result), then the vertical pass; the bounds
+ * (xmin, taps) and the 22-bit coefficients k of every output column / row come from the caller (m3ae_amd/resample.py builds them
+ * in float64 in Pillow's operation order; |k| < 2^23), with the centre crop folded in: `size` outputs per axis.  The result is
+ * the bytes PIL produces, and `out` is bit-equal to m3ae_image_normalize_u8 of them.
+ *   src   bytes of the B sources, RGB interleaved, each starting at a 16-byte aligned offset
+ *   plan  int64 [B][16] per image: 0 byte offset in src, 1 w, 2 h, 3 row pitch in bytes, 4 row0, 5 nrows (the source rows the
+ *         surviving output rows read: the horizontal pass runs on these alone), 6 ksize_x, 7 ksize_y (row lengths of the two
+ *         coefficient tables), 8..11 offsets (in int32) into tab of: x bounds [size][2], x coefficients [size][ksize_x], y bounds
+ *         [size][2] (absolute source rows), y coefficients [size][ksize_y], 12 first intermediate row of this image (running sum
+ *         of nrows), 13..15 zero.  w <= 8192.
+ *   tab   int32 tables as addressed by plan
+ *   workspace  uint8 intermediates [sum nrows][size * 3 rounded up to 4]; m3ae_image_resample_workspace_bytes(sum nrows, size)
+ *   out   fp32 [B][3][size][size] = (u / 255 - mean[c]) / std[c];  out_u8: NULL, or uint8 [B][size][size][3] (the crop itself)
+ *   mean3 / std3: HOST arrays, as for m3ae_image_normalize_u8.
+ * src_bytes / tab_ints / workspace_bytes are the sizes of src (bytes), tab (int32) and workspace (bytes): the kernels check every
+ * plan record and table bound against them and leave an image whose record points outside unwritten. */
+int64_t m3ae_image_resample_workspace_bytes(int64_t total_rows, int64_t size);
+int m3ae_image_resample_u8(const uint8_t* src, int64_t src_bytes, const int64_t* plan, const int32_t* tab, int64_t tab_ints, int64_t B,
+                           int64_t size, uint8_t* workspace, int64_t workspace_bytes, float* out, uint8_t* out_u8,
+                           const float* mean3, const float* std3, void* stream);
 int m3ae_vit_tokens_fwd(const void* patch, const float* cls, const float* pos, void* out, int64_t B, int64_t G,
                         int64_t D, int dtype, void* stream);
 int m3ae_vit_tokens_bwd(const void* d_out, void* d_patch, float* d_cls, float* d_pos, int64_t B, int64_t G,

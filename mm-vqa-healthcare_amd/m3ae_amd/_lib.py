@@ -119,6 +119,9 @@ _SIGS = {
     "m3ae_bce_logits_det": (C.c_int, [vp, vp, vp, vp, i64, i64, f32, C.c_int, vp, i64, vp]),
     "m3ae_xent_det": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, f32, C.c_int, vp, i64, vp]),
     "m3ae_mim_loss_fwd_det": (C.c_int, [vp, vp, vp, vp, vp, i64, i64, i64, C.c_int, vp, i64, vp]),
+    # device image transform (ABI 4, additive)
+    "m3ae_image_resample_workspace_bytes": (i64, [i64, i64]),
+    "m3ae_image_resample_u8": (C.c_int, [vp, i64, vp, vp, i64, i64, i64, vp, i64, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -45,6 +45,9 @@ DEFAULTS = dict(
     # atomics.  The reference's trainer runs with deterministic=True (main.py:64); here the default is False -- the one deliberate
     # difference from that flag -- because the ordered split-K weight gradients cost step time.
     deterministic=False,
+    # where the CLIP transform's bicubic resize + centre crop run for arrow data (m3ae_amd/data.py): "host" (PIL, on the loader's
+    # threads) | "device" (csrc/image.hip from the decoded source bytes; bit-identical batches)
+    image_transform="host",
 )
 
 NAMED = {

@@ -15,10 +15,19 @@ Reference pieces restated (host side, Python like the reference's):
     `DataCollatorForWholeWordMask` / `DataCollatorForLanguageModeling`; the reference vendors the same file as
     m3ae/utils/data_collator.py:290-496) -> `MLMCollator`.
 
-MI355X side: decode + bicubic resize stay on host cores (PIL releases the GIL; a thread pool of `num_workers`), the
-crop is handed over as uint8 NHWC in PINNED memory (a quarter of the fp32 bytes over PCIe), copied on a side HIP
-stream, and ToTensor + Normalize run in one kernel on the GPU (`m3ae_image_normalize_u8`, same IEEE arithmetic as
-torch: bit-equal to the reference's tensor).  `ArrowDataModule.train_batches` keeps `prefetch` batches in flight.
+MI355X side, `image_transform="host"` (the default): decode + bicubic resize run on host cores (PIL releases the GIL; a
+thread pool of `num_workers`), the crop is handed over as uint8 NHWC in PINNED memory (a quarter of the fp32 bytes over
+PCIe), copied on a side HIP stream, and ToTensor + Normalize run in one kernel on the GPU (`m3ae_image_normalize_u8`,
+same IEEE arithmetic as torch: bit-equal to the reference's tensor).  `ArrowDataModule.train_batches` keeps `prefetch`
+batches in flight.
+
+`image_transform="device"`: only the decode stays on the host.  The workers hand over the decoded RGB bytes of every
+opaque image, `collate_host` packs a batch's sources with their resample plan and coefficient tables
+(m3ae_amd/resample.py) into one pinned upload, and `m3ae_image_resample_u8` (csrc/image.hip) runs Pillow's fixed-point
+bicubic resize, the centre crop and ToTensor + Normalize on the GPU: the same integer arithmetic, so the batch is
+bit-identical to the host path's.  An image with real transparency (Pillow premultiplies it around the resize) or beyond
+the staging caps is transformed on the host as before and joins the batch as a size x size source with identity tables;
+`ArrowDataModule.transform_stats` counts both routes.
 """
 import ctypes as C
 import io
@@ -31,7 +40,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, resample
 from .synth import CLIP_MEAN, CLIP_STD
 
 
@@ -52,6 +61,32 @@ def clip_resize_crop(img, size):
     top, left = int(round((nh - size) / 2.0)), int(round((nw - size) / 2.0))
     img = img.crop((left, top, left + size, top + size)).convert("RGB")
     return np.array(img, dtype=np.uint8)  # a writable copy (torch.from_numpy)
+
+
+class TransformStats(dict):
+    """{"device": n, "fallback": n}: images the device transform took from their source bytes / images the host transformed
+    (real transparency, or beyond the staging caps); counted from the loader's worker threads."""
+
+    def __init__(self):
+        super().__init__(device=0, fallback=0)
+        self._lock = threading.Lock()
+
+    def count(self, route):
+        with self._lock:
+            self[route] += 1
+
+
+def load_image_u8(raw, size, image_transform="host", stats=None):
+    """Encoded image bytes -> uint8 [size, size, 3] (the finished crop, "host") or the source the device transform resizes
+    ("device": uint8 [h, w, 3], or the host-made crop of an image it does not take)."""
+    from PIL import Image
+    img = Image.open(io.BytesIO(raw))
+    if image_transform != "device":
+        return clip_resize_crop(img, size)
+    route, a = resample.prepare(img, size)
+    if stats is not None:
+        stats.count(route)
+    return a
 
 
 def normalize_on_device(u8_nhwc, stream=None):
@@ -163,8 +198,9 @@ class MLMCollator:
 class ArrowVQADataset:
     """BaseDataset + VQAVQARADDataset for `{data_dir}/vqa_vqa_rad_{split}.arrow` (or any `names`)."""
 
-    def __init__(self, data_dir, split, image_size, max_text_len, tokenizer, names=None):
+    def __init__(self, data_dir, split, image_size, max_text_len, tokenizer, names=None, image_transform="host", stats=None):
         import pyarrow as pa
+        self.image_transform, self.stats = image_transform, stats
         self.names = names or [f"vqa_vqa_rad_{split}"]
         tables = []
         for name in self.names:
@@ -182,8 +218,7 @@ class ArrowVQADataset:
         return len(self.index_mapper)
 
     def image_u8(self, row):
-        from PIL import Image
-        return clip_resize_crop(Image.open(io.BytesIO(self.table["image"][row].as_py())), self.image_size)
+        return load_image_u8(self.table["image"][row].as_py(), self.image_size, self.image_transform, self.stats)
 
     def __getitem__(self, index):
         row, qi = self.index_mapper[index]
@@ -211,8 +246,10 @@ class ArrowCaptionDataset:
     (`get_false_image`, :107-111) -- Python's `random` stream, as the reference consumes it, so a seeded run reproduces the
     reference's draws.  A sample that fails to decode is replaced by a random one (:158-160)."""
 
-    def __init__(self, data_dir, name, split, image_size, max_text_len, tokenizer, draw_false_image=0):
+    def __init__(self, data_dir, name, split, image_size, max_text_len, tokenizer, draw_false_image=0, image_transform="host",
+                 stats=None):
         import pyarrow as pa
+        self.image_transform, self.stats = image_transform, stats
         assert split in ("train", "val", "test")
         self.names = [f"{name}_{split}"]
         path = os.path.join(data_dir, f"{self.names[0]}.arrow")
@@ -229,8 +266,7 @@ class ArrowCaptionDataset:
         return len(self.index_mapper)
 
     def image_u8(self, row):
-        from PIL import Image
-        return clip_resize_crop(Image.open(io.BytesIO(self.table["image"][row].as_py())), self.image_size)
+        return load_image_u8(self.table["image"][row].as_py(), self.image_size, self.image_transform, self.stats)
 
     def get_suite(self, index):
         while True:
@@ -269,13 +305,18 @@ class ConcatDataset:
         raise IndexError(index)
 
 
-def collate_host(samples, pin=True, mlm_collator=None):
+def collate_host(samples, pin=True, mlm_collator=None, resample_size=None, pmap=map):
     """base_dataset.py:165-228: images stacked as uint8 NHWC, ids / masks as int64 tensors; with `mlm_collator` also
     `text_ids_mlm` / `text_labels_mlm` (:202-209; the reference always computes them, the fine-tuning step never reads
-    them)."""
+    them).  `resample_size` (image_transform="device"): the samples carry sources of any sizes; each image key becomes a
+    pack (resample.pack_batch: source bytes, plan, tables) for the device transform to that size, its copies run through `pmap`."""
     B = len(samples)
     S = max(len(s["input_ids"]) for s in samples)
-    img = torch.from_numpy(np.stack([s["image_u8"] for s in samples]))
+    if resample_size:
+        stack = lambda k: resample.pack_batch([s[k] for s in samples], resample_size, pin=pin, pmap=pmap)
+    else:
+        stack = lambda k: torch.from_numpy(np.stack([s[k] for s in samples]))
+    img = stack("image_u8")
     ids = torch.zeros((B, S), dtype=torch.long)
     mask = torch.zeros((B, S), dtype=torch.long)
     for i, s in enumerate(samples):
@@ -287,10 +328,11 @@ def collate_host(samples, pin=True, mlm_collator=None):
         extra = {"text_ids_mlm": m["input_ids"], "text_labels_mlm": m["labels"]}
     for k in sorted(samples[0]):   # the negatives of the image-text matching objective (base_dataset.py:107-111, :173-195)
         if k.startswith("false_image_u8_"):
-            extra[k] = torch.from_numpy(np.stack([s[k] for s in samples]))
+            extra[k] = stack(k)
     if pin and torch.cuda.is_available():
-        img, ids, mask = img.pin_memory(), ids.pin_memory(), mask.pin_memory()
-        extra = {k: v.pin_memory() for k, v in extra.items()}
+        _pin = lambda v: v.pin_memory() if isinstance(v, torch.Tensor) else v   # a pack is pinned as it is built
+        img, ids, mask = _pin(img), ids.pin_memory(), mask.pin_memory()
+        extra = {k: _pin(v) for k, v in extra.items()}
     out = {"image_u8": img, "text_ids": ids, "text_masks": mask, **extra, "text": [s["text"] for s in samples]}
     for k in ("vqa_answer", "vqa_labels", "vqa_scores", "answer_types", "qid", "img_index", "cap_index", "raw_index",
               "replica"):
@@ -303,13 +345,14 @@ def to_device_batch(hb, device, copy_stream=None):
     """Upload a host batch (pinned) and finish the transform on the GPU -> the 8b batch dict."""
     cur = torch.cuda.current_stream()
     cs = copy_stream or cur
+    _up = lambda v: v.to(device, non_blocking=True) if isinstance(v, torch.Tensor) else resample.upload(v, device)
     with torch.cuda.stream(cs):
-        u8 = hb["image_u8"].to(device, non_blocking=True)
+        u8 = _up(hb["image_u8"])
         ids = hb["text_ids"].to(device, non_blocking=True)
         mask = hb["text_masks"].to(device, non_blocking=True)
         ev = torch.cuda.Event()
         mlm = {k: hb[k].to(device, non_blocking=True) for k in ("text_ids_mlm", "text_labels_mlm") if k in hb}
-        fal = {"_" + k: hb[k].to(device, non_blocking=True) for k in hb if k.startswith("false_image_u8_")}
+        fal = {"_" + k: _up(hb[k]) for k in hb if k.startswith("false_image_u8_")}
         ev.record(cs)
     out = {k: v for k, v in hb.items() if k not in ("image_u8", "text_ids", "text_masks", "text_ids_mlm", "text_labels_mlm")
            and not k.startswith("false_image_u8_")}
@@ -317,18 +360,25 @@ def to_device_batch(hb, device, copy_stream=None):
     return out
 
 
+def _finish_image(u8, cur):
+    """The uploaded crop -- or, under image_transform="device", the uploaded pack -- to the fp32 image, on the compute stream."""
+    if isinstance(u8, torch.Tensor):
+        u8.record_stream(cur)
+        return normalize_on_device(u8)
+    for k in ("src", "plan", "tab"):   # uploaded on the copy stream, read here
+        u8[k].record_stream(cur)
+    return resample.resample_on_device(u8)
+
+
 def finish_batch(db):
-    """Called on the compute stream right before the step: wait for the upload, normalise, build labels."""
-    torch.cuda.current_stream().wait_event(db.pop("_ready"))
-    u8 = db.pop("_u8")
-    db["image"] = [normalize_on_device(u8)]
-    for k in [k for k in db if k.startswith("_false_image_u8_")]:
-        f8 = db.pop(k)
-        f8.record_stream(torch.cuda.current_stream())
-        db["false_image_" + k[len("_false_image_u8_"):]] = [normalize_on_device(f8)]
-    db["text_labels"] = torch.full_like(db["text_ids"], -100)
+    """Called on the compute stream right before the step: wait for the upload, resize (device transform) / normalise,
+    build labels."""
     cur = torch.cuda.current_stream()
-    u8.record_stream(cur)
+    cur.wait_event(db.pop("_ready"))
+    db["image"] = [_finish_image(db.pop("_u8"), cur)]
+    for k in [k for k in db if k.startswith("_false_image_u8_")]:
+        db["false_image_" + k[len("_false_image_u8_"):]] = [_finish_image(db.pop(k), cur)]
+    db["text_labels"] = torch.full_like(db["text_ids"], -100)
     for t in db.values():   # every tensor uploaded on the copy stream (text_ids_mlm / text_labels_mlm included) is now used here
         if isinstance(t, torch.Tensor) and t.is_cuda:
             t.record_stream(cur)
@@ -348,12 +398,17 @@ class ArrowDataModule:
         self.tokenizer = tokenizer or load_tokenizer(cfg)
         root = cfg["data_root"]
         names = list(cfg.get("datasets") or ["vqa_vqa_rad"])
+        self.image_transform = cfg.get("image_transform", "host")
+        if self.image_transform not in ("host", "device"):
+            raise ValueError(f"image_transform must be 'host' or 'device', not {self.image_transform!r}")
+        self.transform_stats = TransformStats()
+        tf = dict(image_transform=self.image_transform, stats=self.transform_stats)
         if any(n in ("roco", "medicat") for n in names):   # the pre-training caption tables (config.py:22,31: draw_false_image = 1)
             mk = lambda split: ConcatDataset([ArrowCaptionDataset(root, n, split, cfg["image_size"], cfg["max_text_len"],
-                                                                  self.tokenizer, cfg.get("draw_false_image", 0))
+                                                                  self.tokenizer, cfg.get("draw_false_image", 0), **tf)
                                               for n in names])
         else:
-            mk = lambda split: ArrowVQADataset(root, split, cfg["image_size"], cfg["max_text_len"], self.tokenizer)
+            mk = lambda split: ArrowVQADataset(root, split, cfg["image_size"], cfg["max_text_len"], self.tokenizer, **tf)
         self.train_set = mk("train")
         self.val_set = self._try(mk, "val") or self.train_set
         self.test_set = self._try(mk, "test") or self.val_set
@@ -394,7 +449,8 @@ class ArrowDataModule:
                 for c in chunks:
                     if stop.is_set():
                         break
-                    q.put(collate_host(list(pool.map(ds.__getitem__, c)), mlm_collator=self.mlm_collator))
+                    q.put(collate_host(list(pool.map(ds.__getitem__, c)), mlm_collator=self.mlm_collator, pmap=pool.map,
+                                       resample_size=self.cfg["image_size"] if self.image_transform == "device" else None))
             q.put(None)
 
         th = threading.Thread(target=producer, daemon=True)

@@ -21,7 +21,8 @@ arithmetic around `training_step`:
 
 Data: `data_root=<dir with vqa_vqa_rad_{train,val,test}.arrow>` runs the arrow input pipeline (m3ae_amd/data.py, SURVEY
 8f-2: host decode + bicubic resize in a thread pool, pinned uint8 upload on a side stream, ToTensor + Normalize on
-the GPU); `data_root=synthetic` (or empty) selects `SyntheticDataModule`, which serves deterministic batches with the
+the GPU; with `image_transform=device` the resize and the crop run on the GPU too, from the decoded bytes, and give
+bit-identical batches); `data_root=synthetic` (or empty) selects `SyntheticDataModule`, which serves deterministic batches with the
 same collate schema (base_dataset.py:165-228).
 """
 import json

@@ -1,0 +1,133 @@
+"""Device image transform, host half (m3ae_amd/resample.py): the tables and the numpy model of the two kernels against
+Pillow itself, the folded crop, the 24-bit coefficient bound, eligibility, and the declarations of the new entry points."""
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from resample_cases import SIZES, TARGETS, kind_of, source  # noqa: E402
+
+from m3ae_amd import _lib, resample  # noqa: E402
+from m3ae_amd.config import compose  # noqa: E402
+from m3ae_amd.data import clip_resize_crop  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _pil(a):
+    from PIL import Image
+    return Image.fromarray(a, "L" if a.ndim == 2 else {3: "RGB", 4: "RGBA"}[a.shape[2]])
+
+
+@pytest.mark.parametrize("size", TARGETS)
+@pytest.mark.parametrize("wh", SIZES, ids=lambda wh: f"{wh[0]}x{wh[1]}")
+def test_numpy_model_equals_pillow_bit_for_bit(wh, size):
+    w, h = wh
+    for kind in ("noise", "smooth"):
+        a = source(w, h, kind)
+        want = clip_resize_crop(_pil(a), size)
+        state, src = resample.prepare(_pil(a), size)
+        assert state == "device" and np.array_equal(src, a)
+        got = resample.resample_model(src, size)
+        assert got.shape == (size, size, 3) and got.dtype == np.uint8
+        assert np.array_equal(got, want), (wh, size, kind, int(np.abs(got.astype(int) - want.astype(int)).max()))
+
+
+@pytest.mark.parametrize("size", TARGETS)
+def test_gray_source_equals_pillow(size):
+    a = source(333, 280, "noise", channels=1)
+    want = clip_resize_crop(_pil(a), size)
+    state, src = resample.prepare(_pil(a), size)
+    assert state == "device" and src.shape == (280, 333, 3)
+    assert np.array_equal(resample.resample_model(src, size), want)
+
+
+@pytest.mark.parametrize("size", TARGETS)
+@pytest.mark.parametrize("wh", SIZES, ids=lambda wh: f"{wh[0]}x{wh[1]}")
+def test_crop_is_folded_and_coefficients_fit_24_bits(wh, size):
+    w, h = wh
+    t = resample.tables(w, h, size)
+    nw, nh, left, top = resample.output_geometry(w, h, size)
+    assert t.xb.shape == (size, 2) and t.yb.shape == (size, 2)
+    assert t.xk.shape == (size, t.ksx) and t.yk.shape == (size, t.ksy)
+    # the surviving outputs are rows left .. left + size - 1 of the full table of the axis
+    fb, fk = resample.axis_table(w, nw, 0, nw)
+    assert np.array_equal(fb[left:left + size], t.xb) and np.array_equal(fk[left:left + size], t.xk)
+    fb, fk = resample.axis_table(h, nh, 0, nh)
+    assert np.array_equal(fb[top:top + size], t.yb) and np.array_equal(fk[top:top + size], t.yk)
+    # row0 / nrows: exactly the source rows the vertical pass reads -- none missing, none spare at either end
+    read = np.zeros(h, dtype=bool)
+    for ymin, cnt in t.yb.tolist():
+        read[ymin:ymin + cnt] = True
+    rows = np.flatnonzero(read)
+    assert t.row0 == rows[0] and t.row0 + t.nrows == rows[-1] + 1
+    assert read[t.row0:t.row0 + t.nrows].all()   # neighbouring outputs' taps overlap: no row inside the range is spare
+    for k in (t.xk, t.yk):
+        assert np.abs(k.astype(np.int64)).max() < 2 ** 23
+    # every row of coefficients sums to one within the rounding of its taps
+    for b, k in ((t.xb, t.xk), (t.yb, t.yk)):
+        assert (np.abs(k.sum(1).astype(np.int64) - 2 ** 22) <= b[:, 1]).all()
+    # the cache returns the same object
+    assert resample.tables(w, h, size) is t
+
+
+def test_packed_batch_stays_inside_its_buffers():
+    size = 224
+    srcs = [source(w, h, "noise") for (w, h) in [(300, 200), (97, 130), (224, 224), (300, 200)]]
+    p = resample.pack_batch(srcs, size)
+    plan, tab, src = p["plan"].numpy(), p["tab"].numpy(), p["src"].numpy()
+    assert plan.shape == (4, resample.PLAN_FIELDS) and tab.dtype == np.int32
+    assert np.array_equal(plan[0, resample.PLAN_XB:resample.PLAN_YK + 1], plan[3, resample.PLAN_XB:resample.PLAN_YK + 1])  # shared tables
+    rows = 0
+    for i, s in enumerate(srcs):
+        off, w, h, pitch, row0, nrows, ksx, ksy, xb, xk, yb, yk, irow0 = plan[i, :13].tolist()
+        assert off % 16 == 0 and (h, w) == s.shape[:2] and pitch == 3 * w and irow0 == rows
+        assert np.array_equal(src[off:off + s.size].reshape(s.shape), s)
+        b = tab[xb:xb + 2 * size].reshape(size, 2)
+        assert b[:, 0].min() >= 0 and (b[:, 0] + b[:, 1]).max() <= w and b[:, 1].max() <= ksx
+        b = tab[yb:yb + 2 * size].reshape(size, 2)
+        assert b[:, 0].min() >= row0 and (b[:, 0] + b[:, 1]).max() <= row0 + nrows <= h and b[:, 1].max() <= ksy
+        assert xk + size * ksx <= yb and yk + size * ksy <= tab.size
+        rows += nrows
+    assert p["rows"] == rows
+
+
+def test_eligibility():
+    from PIL import Image
+    size = 64
+    rgb = source(90, 70, "noise")
+    rgba = np.concatenate([rgb, np.full((70, 90, 1), 255, dtype=np.uint8)], -1)
+    assert resample.prepare(_pil(rgb), size)[0] == "device"
+    assert resample.prepare(_pil(source(90, 70, "noise", channels=1)), size)[0] == "device"
+    state, src = resample.prepare(_pil(rgba), size)
+    assert state == "device" and np.array_equal(src, rgb)
+    holed = rgba.copy()
+    holed[11, 13, 3] = 254
+    state, crop = resample.prepare(_pil(holed), size)
+    assert state == "fallback" and np.array_equal(crop, clip_resize_crop(_pil(holed), size))
+    pal = _pil(rgb).convert("P", palette=Image.ADAPTIVE, colors=16)
+    pal.info["transparency"] = 3
+    state, crop = resample.prepare(pal, size)
+    assert state == "fallback" and np.array_equal(crop, clip_resize_crop(pal, size))
+    assert resample.prepare(_pil(rgb).convert("P", palette=Image.ADAPTIVE, colors=16), size)[0] == "device"
+    # beyond the staging caps: host path
+    wide = Image.new("RGB", (resample.MAX_SOURCE_WIDTH + 1, 8), (1, 2, 3))
+    assert resample.prepare(wide, size)[0] == "fallback"
+    # a fallback crop goes through identity tables unchanged
+    t = resample.tables(size, size, size)
+    assert t.ksx == t.ksy == 1 and (t.xk == 2 ** 22).all() and t.row0 == 0 and t.nrows == size
+    assert np.array_equal(resample.resample_model(crop, size), crop)
+
+
+def test_entry_points_are_declared_and_bound_and_the_default_is_host():
+    hdr = open(os.path.join(ROOT, "include", "m3ae_hip.h")).read()
+    for name in ("m3ae_image_resample_u8", "m3ae_image_resample_workspace_bytes"):
+        assert re.search(r"\b%s\s*\(" % name, hdr), name
+        assert name in _lib.EXPORTS
+    assert re.search(r"#define\s+M3AE_ABI_VERSION\s+4\b", hdr) and _lib.ABI_VERSION == 4
+    assert os.path.exists(os.path.join(ROOT, "mm-vqa-healthcare_amd", "csrc", "image.hip"))
+    assert compose()["image_transform"] == "host"
+    assert compose("task_finetune_vqa_vqa_rad", image_transform="device")["image_transform"] == "device"

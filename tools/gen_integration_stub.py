@@ -31,6 +31,7 @@ MAP_ENTRIES = ("m3ae_attn_probs", "m3ae_xattn_probs_export")
 DET_ENTRIES = ("m3ae_gemm_det_workspace_bytes", "m3ae_gemm_det", "m3ae_det_workspace_bytes", "m3ae_colsum_det",
                "m3ae_layernorm_bwd_det", "m3ae_layernorm_bwd_drop_det", "m3ae_roberta_embed_bwd_det", "m3ae_bce_logits_det",
                "m3ae_xent_det", "m3ae_mim_loss_fwd_det")
+IMAGE_ENTRIES = ("m3ae_image_resample_workspace_bytes", "m3ae_image_resample_u8")
 
 
 def _ctype_name(t):
@@ -61,6 +62,11 @@ def block():
     out.append(f"DET_COLSUM, DET_EMBED_BWD, DET_BCE, DET_XENT, DET_MIM = {_lib.DET_COLSUM}, {_lib.DET_EMBED_BWD}, {_lib.DET_BCE}, "
                f"{_lib.DET_XENT}, {_lib.DET_MIM}     # m3ae_det_workspace_bytes(op, rows, cols)")
     for name in DET_ENTRIES:
+        res, args = _lib._SIGS[name]
+        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
+    out.append("")
+    out.append("# device image transform (ABI 4, additive): Pillow-exact bicubic resize + centre crop + normalize from the source bytes")
+    for name in IMAGE_ENTRIES:
         res, args = _lib._SIGS[name]
         out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
     out.append("```")
