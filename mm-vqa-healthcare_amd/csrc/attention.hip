@@ -511,9 +511,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_coop_kernel(AttnArgs a) {
     put_tr_img(lds + RIMG, kreg, t);
     put_row_img(lds + RIMG + TILE_LDS, vreg, t);
     // global prefetch distance: two tiles.  (Round 4 measured ONE tile at three waves per SIMD -- 168 registers with one prefetch set
-    // less and 4-8 spilled registers: dQ 583 -> 730-745 us, profiles/r04_attn_bwd_experiments.log; PF2 = false is that form.)
-    constexpr bool PF2 = true;
-    if (PF2 && nkt > 1) {
+    // less and 4-8 spilled registers: dQ 583 -> 730-745 us, profiles/r04_attn_bwd_experiments.log.)
+    if (nkt > 1) {
         kreg = coop_load(kbase, a.k_sl, 32, a.Lk, t);
         vreg = coop_load(vbase, a.v_sl, 32, a.Lk, t);
     }
@@ -521,14 +520,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_coop_kernel(AttnArgs a) {
     for (int kt = 0; kt < nkt; ++kt) {
         const bool last = kt + 1 == nkt;
         s16x8 kreg2 = kreg, vreg2 = vreg;
-        if (PF2) {
-            if (kt + 2 < nkt) {
-                kreg2 = coop_load(kbase, a.k_sl, (int64_t)(kt + 2) * 32, a.Lk, t);
-                vreg2 = coop_load(vbase, a.v_sl, (int64_t)(kt + 2) * 32, a.Lk, t);
-            }
-        } else if (!last) {   // tile kt + 1: requested here, written to LDS behind this tile's MFMAs
-            kreg = coop_load(kbase, a.k_sl, (int64_t)(kt + 1) * 32, a.Lk, t);
-            vreg = coop_load(vbase, a.v_sl, (int64_t)(kt + 1) * 32, a.Lk, t);
+        if (kt + 2 < nkt) {
+            kreg2 = coop_load(kbase, a.k_sl, (int64_t)(kt + 2) * 32, a.Lk, t);
+            vreg2 = coop_load(vbase, a.v_sl, (int64_t)(kt + 2) * 32, a.Lk, t);
         }
         const char* kimg = lds + (kt & 1) * BUF;
         const char* ktr = kimg + RIMG;
@@ -591,7 +585,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_coop_kernel(AttnArgs a) {
             put_tr_img(nb + RIMG, kreg, t);
             put_row_img(nb + RIMG + TILE_LDS, vreg, t);
         }
-        if (PF2) { kreg = kreg2; vreg = vreg2; }
+        kreg = kreg2; vreg = vreg2;
         coop_barrier();
     }
     if (active && qi < a.Lq) store_rows(a.dq + b * a.q_sb + qi * a.q_sl + head * 64, g0, g1, a.scale, h);
@@ -1071,32 +1065,22 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(AttnArgs a) {
 // profiles/r04_attn_generation_check.log: the forward reads each image one way only, so the dual layout saves no staging stores
 // there, and at 32 KiB of LDS and 167 registers it loses the fourth wave per SIMD the round-3 kernel runs with.  Not kept.)
 
-// coop kernels: mask / bias / causal as below plus the dropout instances: BERT layers (optional key mask) and T5 layers
-// (relative-position bias, optionally causal)
-#define ATTN_DISPATCH_COOP(rc, KERNEL, grid, s, a, ...)                                                                  \
-    do {                                                                                                                 \
-        const int f = (a.key_mask ? 1 : 0) | (a.pos_bias ? 2 : 0) | (a.causal ? 4 : 0);                                  \
-        if (a.has_drop) {                                                                                                \
-            if (f == 0) hipLaunchKernelGGL((KERNEL<__VA_ARGS__ false, false, false, true>), grid, dim3(256), 0, s, a);   \
-            else if (f == 1) hipLaunchKernelGGL((KERNEL<__VA_ARGS__ true, false, false, true>), grid, dim3(256), 0, s, a); \
-            else if (f == 2) hipLaunchKernelGGL((KERNEL<__VA_ARGS__ false, true, false, true>), grid, dim3(256), 0, s, a); \
-            else if (f == 6) hipLaunchKernelGGL((KERNEL<__VA_ARGS__ false, true, true, true>), grid, dim3(256), 0, s, a);  \
-            else rc = M3AE_ERR_UNSUPPORTED;                                                                              \
-            break;                                                                                                       \
-        }                                                                                                                \
-        switch (f) {                                                                                                     \
-            case 0: hipLaunchKernelGGL((KERNEL<__VA_ARGS__ false, false, false, false>), grid, dim3(256), 0, s, a); break; \
-            case 1: hipLaunchKernelGGL((KERNEL<__VA_ARGS__ true, false, false, false>), grid, dim3(256), 0, s, a); break;  \
-            case 2: hipLaunchKernelGGL((KERNEL<__VA_ARGS__ false, true, false, false>), grid, dim3(256), 0, s, a); break;  \
-            case 3: hipLaunchKernelGGL((KERNEL<__VA_ARGS__ true, true, false, false>), grid, dim3(256), 0, s, a); break;   \
-            case 4: hipLaunchKernelGGL((KERNEL<__VA_ARGS__ false, false, true, false>), grid, dim3(256), 0, s, a); break;  \
-            case 5: hipLaunchKernelGGL((KERNEL<__VA_ARGS__ true, false, true, false>), grid, dim3(256), 0, s, a); break;   \
-            case 6: hipLaunchKernelGGL((KERNEL<__VA_ARGS__ false, true, true, false>), grid, dim3(256), 0, s, a); break;   \
-            default: hipLaunchKernelGGL((KERNEL<__VA_ARGS__ true, true, true, false>), grid, dim3(256), 0, s, a); break;   \
-        }                                                                                                                \
-    } while (0)
+// Flag dispatch (mask / bias / causal / dropout are wave-uniform launch properties): launch(MASK, BIAS, CAUSAL, DROP) is called with
+// the four flags of `a` as std::bool_constants and instantiated for the supported combinations only: every combination of key
+// mask, relative-position bias and causal without dropout; with dropout no flag or a key mask (BERT layers), a bias or a causal
+// bias (T5 layers).
+template <class F> int pick(bool on, F&& f) { return on ? f(std::true_type{}) : f(std::false_type{}); }
+template <class L> int attn_dispatch(const AttnArgs& a, L&& launch) {
+    return pick(a.key_mask != nullptr, [&](auto mask) {
+    return pick(a.pos_bias != nullptr, [&](auto bias) {
+    return pick(a.causal != 0, [&](auto causal) {
+    return pick(a.has_drop != 0, [&](auto drop) -> int {
+        constexpr int f = (decltype(mask)::value ? 1 : 0) | (decltype(bias)::value ? 2 : 0) | (decltype(causal)::value ? 4 : 0);
+        if constexpr (!decltype(drop)::value || f == 0 || f == 1 || f == 2 || f == 6) return launch(mask, bias, causal, drop);
+        else return M3AE_ERR_UNSUPPORTED;
+    }); }); }); });
+}
 
-// flag dispatch (mask / bias / causal are wave-uniform launch properties)
 // ---------------------------------------------------------------------------------------------------------
 // fp32 reference-shaped path: row softmax kernels over the materialised score matrix
 // ---------------------------------------------------------------------------------------------------------
@@ -1153,11 +1137,24 @@ __global__ void pos_bias_grad_kernel(const float* dS, float* dpb, int64_t B, int
     dpb[i] += acc;
 }
 
-m3ae_gemm_desc bgemm(const m3ae_attn_desc& d) {
+// One operand of the fp32 path's products: a rows x cols matrix per (sample, head).
+struct Mat { const void* p; int64_t rows, cols, s_row, s_col, s_b, s_h; };
+Mat tr(const Mat& m) { return Mat{m.p, m.cols, m.rows, m.s_col, m.s_row, m.s_b, m.s_h}; }
+// a score-shaped workspace matrix, dense [B][H][Lq][Lk]
+Mat scores(const m3ae_attn_desc& d, const float* S) { return Mat{S, d.Lq, d.Lk, d.Lk, 1, d.H * d.Lq * d.Lk, d.Lq * d.Lk}; }
+// q, k, v, o or a gradient of one of them: L rows of Dh per head, the heads of a row side by side
+Mat heads(const m3ae_attn_desc& d, const void* p, int64_t L, int64_t s_l, int64_t s_b) { return Mat{p, L, d.Dh, s_l, 1, s_b, d.Dh}; }
+
+// C = alpha * A . B for every (sample, head)
+m3ae_gemm_desc bgemm(const m3ae_attn_desc& d, float alpha, const Mat& A, const Mat& B, const Mat& C) {
     m3ae_gemm_desc g{};
     g.batch1 = d.B; g.batch2 = d.H;
     g.dtype_a = g.dtype_b = g.dtype_c = M3AE_F32;
-    g.alpha = 1.0f;
+    g.alpha = alpha;
+    g.M = A.rows; g.N = B.cols; g.K = A.cols;
+    g.A = A.p; g.a_sm = A.s_row; g.a_sk = A.s_col; g.a_sb1 = A.s_b; g.a_sb2 = A.s_h;
+    g.B = B.p; g.b_sk = B.s_row; g.b_sn = B.s_col; g.b_sb1 = B.s_b; g.b_sb2 = B.s_h;
+    g.C = const_cast<void*>(C.p); g.c_sm = C.s_row; g.c_sn = C.s_col; g.c_sb1 = C.s_b; g.c_sb2 = C.s_h;
     return g;
 }
 
@@ -1167,13 +1164,9 @@ int attn_gemm(const m3ae_attn_desc& d, const m3ae_gemm_desc& g, hipStream_t s) {
 }
 
 int attn_f32_scores(const m3ae_attn_desc& d, float* S, hipStream_t s) {
-    const int64_t QK = d.Lq * d.Lk;
-    m3ae_gemm_desc g = bgemm(d);
-    g.M = d.Lq; g.N = d.Lk; g.K = d.Dh; g.alpha = d.scale;
-    g.A = d.q; g.a_sm = d.q_sl; g.a_sk = 1; g.a_sb1 = d.q_sb; g.a_sb2 = d.Dh;
-    g.B = d.k; g.b_sk = 1; g.b_sn = d.k_sl; g.b_sb1 = d.k_sb; g.b_sb2 = d.Dh;
-    g.C = S; g.c_sm = d.Lk; g.c_sn = 1; g.c_sb1 = d.H * QK; g.c_sb2 = QK;
-    int rc = attn_gemm(d, g, s);
+    // S = scale * Q . K^T
+    const Mat Q = heads(d, d.q, d.Lq, d.q_sl, d.q_sb), K = heads(d, d.k, d.Lk, d.k_sl, d.k_sb);
+    int rc = attn_gemm(d, bgemm(d, d.scale, Q, tr(K), scores(d, S)), s);
     if (rc) return rc;
     const int64_t rows = d.B * d.H * d.Lq;
     hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, s, S, d.key_mask, d.pos_bias,
@@ -1198,13 +1191,15 @@ AttnArgs to_args(const m3ae_attn_desc& d) {
     return a;
 }
 
-bool bf16_layout_ok(const m3ae_attn_desc& d, bool bwd) {
+// what the bf16 kernels need of the operands a call reads: q, k and lse (the probabilities), + v and o (forward), + gradients (backward)
+enum Layout { LAYOUT_QK, LAYOUT_FWD, LAYOUT_BWD };
+bool bf16_layout_ok(const m3ae_attn_desc& d, Layout need) {
     auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
     auto st = [](int64_t x) { return x % 8 == 0; };
-    bool ok = d.Dh == 64 && al(d.q) && al(d.k) && al(d.v) && al(d.o) && st(d.q_sl) && st(d.k_sl) && st(d.v_sl) &&
-              st(d.o_sl) && st(d.q_sb) && st(d.k_sb) && st(d.v_sb) && st(d.o_sb) && d.lse && d.lse_stride >= d.Lq &&
+    bool ok = d.Dh == 64 && al(d.q) && al(d.k) && st(d.q_sl) && st(d.k_sl) && st(d.q_sb) && st(d.k_sb) && d.lse && d.lse_stride >= d.Lq &&
               d.lse_stride % 32 == 0;
-    if (bwd) ok = ok && al(d.d_o) && al(d.dq) && al(d.dk) && al(d.dv) && d.delta;
+    if (need >= LAYOUT_FWD) ok = ok && al(d.v) && al(d.o) && st(d.v_sl) && st(d.o_sl) && st(d.v_sb) && st(d.o_sb);
+    if (need == LAYOUT_BWD) ok = ok && al(d.d_o) && al(d.dq) && al(d.dk) && al(d.dv) && d.delta;
     return ok;
 }
 
@@ -1224,16 +1219,16 @@ extern "C" int m3ae_attn_fwd(const m3ae_attn_desc* dp, void* stream) {
     if (d.B <= 0 || d.H <= 0 || d.Lq <= 0 || d.Lk <= 0 || d.Dh <= 0) return M3AE_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (d.dtype == M3AE_BF16) {
-        if (!bf16_layout_ok(d, false)) return M3AE_ERR_UNSUPPORTED;
+        if (!bf16_layout_ok(d, LAYOUT_FWD)) return M3AE_ERR_UNSUPPORTED;
         if (d.H > 65535 || d.B > 65535) return M3AE_ERR_UNSUPPORTED;
         AttnArgs a = to_args(d);
         // 32 query rows per wave everywhere (577 = 18 x 32 + 1: finer blocks waste less, occupancy 4: 188 -> 135 us at B = 64
         // against 64 rows per wave on the long sequences)
-        int rc = 0;
         dim3 grid((unsigned)cdiv(d.Lq, 128), (unsigned)d.H, (unsigned)d.B);
-        ATTN_DISPATCH_COOP(rc, attn_fwd_coop_kernel, grid, s, a, 1, );
-        if (rc) return rc;
-        return hip_launch_status();
+        return attn_dispatch(a, [&](auto mask, auto bias, auto causal, auto drop) {
+            hipLaunchKernelGGL((attn_fwd_coop_kernel<1, mask.value, bias.value, causal.value, drop.value>), grid, dim3(256), 0, s, a);
+            return hip_launch_status();
+        });
     }
     if (d.dtype != M3AE_F32) return M3AE_ERR_UNSUPPORTED;
     if (!d.workspace || d.workspace_bytes < m3ae_attn_workspace_bytes(dp, 0)) return M3AE_ERR_WORKSPACE;
@@ -1243,13 +1238,9 @@ extern "C" int m3ae_attn_fwd(const m3ae_attn_desc* dp, void* stream) {
     if (d.dropout_p > 0.f &&  // P is [B H Lq][Lk]: rows x cols of the same mask index the bf16 kernels use
         (rc = m3ae_dropout(S, S, nullptr, d.B * d.H * d.Lq, d.Lk, d.dropout_p, d.dropout_seed, d.dropout_salt, M3AE_F32, stream)))
         return rc;
-    const int64_t QK = d.Lq * d.Lk;
-    m3ae_gemm_desc g = bgemm(d);
-    g.M = d.Lq; g.N = d.Dh; g.K = d.Lk;
-    g.A = S; g.a_sm = d.Lk; g.a_sk = 1; g.a_sb1 = d.H * QK; g.a_sb2 = QK;
-    g.B = d.v; g.b_sk = d.v_sl; g.b_sn = 1; g.b_sb1 = d.v_sb; g.b_sb2 = d.Dh;
-    g.C = d.o; g.c_sm = d.o_sl; g.c_sn = 1; g.c_sb1 = d.o_sb; g.c_sb2 = d.Dh;
-    return attn_gemm(d, g, s);
+    // O = P . V
+    const Mat V = heads(d, d.v, d.Lk, d.v_sl, d.v_sb), O = heads(d, d.o, d.Lq, d.o_sl, d.o_sb);
+    return attn_gemm(d, bgemm(d, 1.0f, scores(d, S), V, O), s);
 }
 
 extern "C" int m3ae_attn_probs(const m3ae_attn_desc* dp, float* probs, int64_t p_sb, int64_t p_sh, int64_t p_sq, void* stream) {
@@ -1260,22 +1251,14 @@ extern "C" int m3ae_attn_probs(const m3ae_attn_desc* dp, float* probs, int64_t p
     if (d.pos_bias || d.causal) return M3AE_ERR_UNSUPPORTED;   // BERT layers only (no T5 relative-position bias, no causal mask)
     hipStream_t s = (hipStream_t)stream;
     if (d.dtype == M3AE_BF16) {
-        auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
-        auto st = [](int64_t x) { return x % 8 == 0; };
-        if (d.Dh != 64 || !al(d.q) || !al(d.k) || !st(d.q_sl) || !st(d.k_sl) || !st(d.q_sb) || !st(d.k_sb) || !d.lse ||
-            d.lse_stride < d.Lq || d.lse_stride % 32 != 0)
-            return M3AE_ERR_UNSUPPORTED;
+        if (!bf16_layout_ok(d, LAYOUT_QK)) return M3AE_ERR_UNSUPPORTED;
         if (d.H > 65535 || d.B > 65535) return M3AE_ERR_UNSUPPORTED;
         AttnArgs a = to_args(d);
         dim3 grid((unsigned)cdiv(d.Lq, 128), (unsigned)d.H, (unsigned)d.B);
-        if (a.key_mask) {
-            if (a.has_drop) hipLaunchKernelGGL((attn_probs_kernel<true, true>), grid, dim3(256), 0, s, a, probs, p_sb, p_sh, p_sq);
-            else hipLaunchKernelGGL((attn_probs_kernel<true, false>), grid, dim3(256), 0, s, a, probs, p_sb, p_sh, p_sq);
-        } else {
-            if (a.has_drop) hipLaunchKernelGGL((attn_probs_kernel<false, true>), grid, dim3(256), 0, s, a, probs, p_sb, p_sh, p_sq);
-            else hipLaunchKernelGGL((attn_probs_kernel<false, false>), grid, dim3(256), 0, s, a, probs, p_sb, p_sh, p_sq);
-        }
-        return hip_launch_status();
+        return attn_dispatch(a, [&](auto mask, auto, auto, auto drop) {   // (no bias, not causal: refused above)
+            hipLaunchKernelGGL((attn_probs_kernel<mask.value, drop.value>), grid, dim3(256), 0, s, a, probs, p_sb, p_sh, p_sq);
+            return hip_launch_status();
+        });
     }
     if (d.dtype != M3AE_F32) return M3AE_ERR_UNSUPPORTED;
     // parity mode: the forward's scores GEMM, row softmax and dropout run once more, straight into a dense [B][H][Lq][Lk] output
@@ -1293,30 +1276,25 @@ extern "C" int m3ae_attn_bwd(const m3ae_attn_desc* dp, void* stream) {
     const m3ae_attn_desc& d = *dp;
     hipStream_t s = (hipStream_t)stream;
     if (d.dtype == M3AE_BF16) {
-        if (!bf16_layout_ok(d, true)) return M3AE_ERR_UNSUPPORTED;
+        if (!bf16_layout_ok(d, LAYOUT_BWD)) return M3AE_ERR_UNSUPPORTED;
         AttnArgs a = to_args(d);
         dim3 gq((unsigned)cdiv(cdiv(d.Lq, 32), 4), (unsigned)d.H, (unsigned)d.B);
         dim3 gk((unsigned)cdiv(cdiv(d.Lk, 32), 4), (unsigned)d.H, (unsigned)d.B);
-        int rc = 0;
+        // round-4 kernels: one LDS image per operand, two tiles per barrier.  Either dQ kernel also publishes delta = rowsum(dO * O)
         const bool gen4 = !a.pos_bias && !a.causal && !(d.launch_flags & M3AE_ATTN_LEGACY_KERNELS);
-        if (gen4) {   // round-4 kernels: one LDS image per operand, two tiles per barrier; also publishes delta = rowsum(dO * O)
-            if (a.key_mask) { if (a.has_drop) hipLaunchKernelGGL((attn_bwd_dq2_kernel<true, true, 2>), gq, dim3(256), 0, s, a);
-                              else hipLaunchKernelGGL((attn_bwd_dq2_kernel<true, false, TPS_PLAIN>), gq, dim3(256), 0, s, a); }
-            else { if (a.has_drop) hipLaunchKernelGGL((attn_bwd_dq2_kernel<false, true, 2>), gq, dim3(256), 0, s, a);
-                   else hipLaunchKernelGGL((attn_bwd_dq2_kernel<false, false, TPS_PLAIN>), gq, dim3(256), 0, s, a); }
-        } else {
-            ATTN_DISPATCH_COOP(rc, attn_bwd_dq_coop_kernel, gq, s, a, );   // also computes (and publishes) delta = rowsum(dO * O)
-        }
-        if (gen4) {
-            if (a.key_mask) { if (a.has_drop) hipLaunchKernelGGL((attn_bwd_dkdv2_kernel<true, true, 2>), gk, dim3(256), 0, s, a);
-                              else hipLaunchKernelGGL((attn_bwd_dkdv2_kernel<true, false, TPS_PLAIN>), gk, dim3(256), 0, s, a); }
-            else { if (a.has_drop) hipLaunchKernelGGL((attn_bwd_dkdv2_kernel<false, true, 2>), gk, dim3(256), 0, s, a);
-                   else hipLaunchKernelGGL((attn_bwd_dkdv2_kernel<false, false, TPS_PLAIN>), gk, dim3(256), 0, s, a); }
-        } else {
-            ATTN_DISPATCH_COOP(rc, attn_bwd_dkdv_coop_kernel, gk, s, a, );
-        }
-        if (rc) return rc;
-        return hip_launch_status();
+        return attn_dispatch(a, [&](auto mask, auto bias, auto causal, auto drop) {
+            constexpr bool M = mask.value, Bi = bias.value, C = causal.value, D = drop.value;
+            if constexpr (!Bi && !C) {
+                if (gen4) {
+                    hipLaunchKernelGGL((attn_bwd_dq2_kernel<M, D, D ? 2 : TPS_PLAIN>), gq, dim3(256), 0, s, a);
+                    hipLaunchKernelGGL((attn_bwd_dkdv2_kernel<M, D, D ? 2 : TPS_PLAIN>), gk, dim3(256), 0, s, a);
+                    return hip_launch_status();
+                }
+            }
+            hipLaunchKernelGGL((attn_bwd_dq_coop_kernel<M, Bi, C, D>), gq, dim3(256), 0, s, a);
+            hipLaunchKernelGGL((attn_bwd_dkdv_coop_kernel<M, Bi, C, D>), gk, dim3(256), 0, s, a);
+            return hip_launch_status();
+        });
     }
     if (d.dtype != M3AE_F32) return M3AE_ERR_UNSUPPORTED;
     if (!d.workspace || d.workspace_bytes < m3ae_attn_workspace_bytes(dp, 1)) return M3AE_ERR_WORKSPACE;
@@ -1328,20 +1306,13 @@ extern "C" int m3ae_attn_bwd(const m3ae_attn_desc* dp, void* stream) {
     if (rc) return rc;
     if (drop && (rc = m3ae_dropout(P, P, nullptr, d.B * d.H * d.Lq, d.Lk, d.dropout_p, d.dropout_seed, d.dropout_salt, M3AE_F32, stream)))
         return rc;  // dV below needs the dropped P that multiplied V in the forward pass
+    const Mat Q = heads(d, d.q, d.Lq, d.q_sl, d.q_sb), K = heads(d, d.k, d.Lk, d.k_sl, d.k_sb), V = heads(d, d.v, d.Lk, d.v_sl, d.v_sb);
+    const Mat dQ = heads(d, d.dq, d.Lq, d.q_sl, d.q_sb), dK = heads(d, d.dk, d.Lk, d.k_sl, d.k_sb), dV = heads(d, d.dv, d.Lk, d.v_sl, d.v_sb);
+    const Mat dO = heads(d, d.d_o, d.Lq, d.o_sl, d.o_sb);
     // dP = dO . V^T
-    m3ae_gemm_desc g = bgemm(d);
-    g.M = d.Lq; g.N = d.Lk; g.K = d.Dh;
-    g.A = d.d_o; g.a_sm = d.o_sl; g.a_sk = 1; g.a_sb1 = d.o_sb; g.a_sb2 = d.Dh;
-    g.B = d.v; g.b_sk = 1; g.b_sn = d.v_sl; g.b_sb1 = d.v_sb; g.b_sb2 = d.Dh;
-    g.C = dS; g.c_sm = d.Lk; g.c_sn = 1; g.c_sb1 = d.H * QK; g.c_sb2 = QK;
-    if ((rc = attn_gemm(d, g, s))) return rc;
+    if ((rc = attn_gemm(d, bgemm(d, 1.0f, dO, tr(V), scores(d, dS)), s))) return rc;
     // dV = P^T . dO   (before dS overwrites nothing of P)
-    g = bgemm(d);
-    g.M = d.Lk; g.N = d.Dh; g.K = d.Lq;
-    g.A = P; g.a_sm = 1; g.a_sk = d.Lk; g.a_sb1 = d.H * QK; g.a_sb2 = QK;
-    g.B = d.d_o; g.b_sk = d.o_sl; g.b_sn = 1; g.b_sb1 = d.o_sb; g.b_sb2 = d.Dh;
-    g.C = d.dv; g.c_sm = d.v_sl; g.c_sn = 1; g.c_sb1 = d.v_sb; g.c_sb2 = d.Dh;
-    if ((rc = attn_gemm(d, g, s))) return rc;
+    if ((rc = attn_gemm(d, bgemm(d, 1.0f, tr(scores(d, P)), dO, dV), s))) return rc;
     const int64_t rows = d.B * d.H * d.Lq;
     if (drop) {  // the softmax backward needs the un-dropped P and dP wrt it
         if ((rc = attn_f32_scores(d, P, s))) return rc;
@@ -1355,18 +1326,8 @@ extern "C" int m3ae_attn_bwd(const m3ae_attn_desc* dp, void* stream) {
                            d.B, HQK);
     }
     // dQ = scale * dS . K
-    g = bgemm(d);
-    g.M = d.Lq; g.N = d.Dh; g.K = d.Lk; g.alpha = d.scale;
-    g.A = dS; g.a_sm = d.Lk; g.a_sk = 1; g.a_sb1 = d.H * QK; g.a_sb2 = QK;
-    g.B = d.k; g.b_sk = d.k_sl; g.b_sn = 1; g.b_sb1 = d.k_sb; g.b_sb2 = d.Dh;
-    g.C = d.dq; g.c_sm = d.q_sl; g.c_sn = 1; g.c_sb1 = d.q_sb; g.c_sb2 = d.Dh;
-    if ((rc = attn_gemm(d, g, s))) return rc;
+    if ((rc = attn_gemm(d, bgemm(d, d.scale, scores(d, dS), K, dQ), s))) return rc;
     // dK = scale * dS^T . Q
-    g = bgemm(d);
-    g.M = d.Lk; g.N = d.Dh; g.K = d.Lq; g.alpha = d.scale;
-    g.A = dS; g.a_sm = 1; g.a_sk = d.Lk; g.a_sb1 = d.H * QK; g.a_sb2 = QK;
-    g.B = d.q; g.b_sk = d.q_sl; g.b_sn = 1; g.b_sb1 = d.q_sb; g.b_sb2 = d.Dh;
-    g.C = d.dk; g.c_sm = d.k_sl; g.c_sn = 1; g.c_sb1 = d.k_sb; g.c_sb2 = d.Dh;
-    if ((rc = attn_gemm(d, g, s))) return rc;
+    if ((rc = attn_gemm(d, bgemm(d, d.scale, tr(scores(d, dS)), Q, dK), s))) return rc;
     return hip_launch_status();
 }

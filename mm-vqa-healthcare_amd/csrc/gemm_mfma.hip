@@ -14,6 +14,7 @@
 // (the LDS-DMA destination is lane-linear) with the same involution on the read, so ds_read_b128 / tr reads are
 // bank-conflict free.  Workgroup ids are remapped so that each XCD (own L2) walks a contiguous range of tiles.
 #include "gemm_nt_common.h"
+#include "launch.h"
 #include <stdlib.h>
 
 namespace {
@@ -276,16 +277,8 @@ static int launch_nt_t(const MfmaArgs& a, hipStream_t s) {
     constexpr int ring = NST * (BM_ + BN_) * BKT * 2, slabs = nwaves * 32 * 68 * 4;
     constexpr int lds = ring > slabs ? ring : slabs;
     constexpr int threads = nwaves * 64;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)gemm_nt_bf16_kernel<BM_, BN_, BKT, NST, WM, EPI>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_set = true;
-    }
     const int64_t tiles = cdiv(a.M, BM_) * cdiv(a.N, BN_);
-    hipLaunchKernelGGL((gemm_nt_bf16_kernel<BM_, BN_, BKT, NST, WM, EPI>), dim3((unsigned)tiles), dim3(threads), lds, s,
-                       a);
-    return hip_launch_status();
+    return launch_dyn<gemm_nt_bf16_kernel<BM_, BN_, BKT, NST, WM, EPI>>(dim3((unsigned)tiles), dim3(threads), lds, s, a);
 }
 
 
@@ -450,16 +443,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(MfmaArgs a) {
 template <int EPI>
 static int launch_nt_pp(const MfmaArgs& a, hipStream_t s) {
     constexpr int lds = 4 * (256 + 256) * 32 * 2;  // 128 KiB ring; the epilogue slabs (8 x 8704 B) reuse it
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_pp_kernel<EPI>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_set = true;
-    }
     const int64_t tiles = cdiv(a.M, 256) * cdiv(a.N, 256);
     g_last_path = "mfma_nt_pp";
-    hipLaunchKernelGGL((gemm_nt_pp_kernel<EPI>), dim3((unsigned)tiles), dim3(512), lds, s, a);
-    return hip_launch_status();
+    return launch_dyn<gemm_nt_pp_kernel<EPI>>(dim3((unsigned)tiles), dim3(512), lds, s, a);
 }
 
 
@@ -637,20 +623,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_persistent_kernel(MfmaArgs 
 template <int EPI>
 static int launch_nt_pp_persistent(const MfmaArgs& a, hipStream_t s) {
     constexpr int lds = 4 * (256 + 256) * 32 * 2;
-    static bool attr_set = false;
-    static int cus = 256;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_pp_persistent_kernel<EPI>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            cus = prop.multiProcessorCount / 8 * 8;
-        attr_set = true;
-    }
     g_last_path = "mfma_nt_pp";
-    hipLaunchKernelGGL((gemm_nt_pp_persistent_kernel<EPI>), dim3((unsigned)cus), dim3(512), lds, s, a);
-    return hip_launch_status();
+    const int dev = current_device();
+    return launch_dyn_on<gemm_nt_pp_persistent_kernel<EPI>>(dev, dim3((unsigned)device_cus8(dev)), dim3(512), lds, s, a);
 }
 
 // variants (launch_flags: M3AE_GEMM_NT_VARIANT(v)):
@@ -1030,17 +1005,11 @@ static int tn_det_fold(const MfmaArgs& part, const m3ae_gemm_desc& d, int bm, in
 template <void (*KERNEL)(MfmaArgs)>
 static int tn_run(MfmaArgs a, const m3ae_gemm_desc& d, int64_t grid, int threads, int lds, int bm, int wm, float* det_ws,
                   hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_set = true;
-    }
     if (det_ws) {
         a.C = det_ws;
         a.a_rowsum = d.a_rowsum ? det_ws + a.splits * d.M * d.N : nullptr;
     }
-    hipLaunchKernelGGL(KERNEL, dim3((unsigned)grid), dim3(threads), lds, s, a);
-    const int rc = hip_launch_status();
+    const int rc = launch_dyn<KERNEL>(dim3((unsigned)grid), dim3(threads), lds, s, a);
     return rc || !det_ws ? rc : tn_det_fold(a, d, bm, wm, s);
 }
 
@@ -1052,6 +1021,9 @@ static int launch_tn_pp(MfmaArgs a, const m3ae_gemm_desc& d, hipStream_t s, floa
     if (det_ws) return tn_run<gemm_tn_pp_kernel<true>>(a, d, tiles * splits, 512, lds, 256, 128, det_ws, s);
     return tn_run<gemm_tn_pp_kernel<false>>(a, d, tiles * splits, 512, lds, 256, 128, nullptr, s);
 }
+
+// LDS bytes of the 128 x 128 TN kernels: an NST-deep ring of BKR-row bf16 slices of both operand tiles
+constexpr int tn_t_lds(int nst, int bkr) { return nst * (128 + 128) * bkr * 2; }
 
 // split-K fan-out of the 128 x 128 TN kernels (lds = their LDS bytes)
 static int64_t tn_t_splits(const m3ae_gemm_desc& d, int lds, int64_t* k_chunk) {
@@ -1081,7 +1053,7 @@ static int64_t tn_t_splits(const m3ae_gemm_desc& d, int lds, int64_t* k_chunk) {
 template <int BM_, int BN_, int WM, int BKR, int NST>
 static int launch_tn_t(MfmaArgs a, const m3ae_gemm_desc& d, hipStream_t s, float* det_ws = nullptr) {
     static_assert(BM_ == 128 && BN_ == 128, "tn_t_splits and tn_det_fold assume the 128 x 128 tile");
-    constexpr int lds = NST * (BM_ + BN_) * BKR * 2;
+    constexpr int lds = tn_t_lds(NST, BKR);
     constexpr int threads = (BM_ / WM) * (BN_ / 64) * 64;
     const int64_t tiles = (d.M / BM_) * (d.N / BN_);
     const int64_t splits = tn_t_splits(d, lds, &a.k_chunk);
@@ -1193,7 +1165,7 @@ extern "C" int64_t m3ae_gemm_det_workspace_bytes(const m3ae_gemm_desc* dp) {
     if (gemm_route(d) != ROUTE_TN) return 0;   // every other kernel family has one writer per output element already
     int64_t k_chunk = 0;
     const int k = tn_kernel_choice(d);
-    const int64_t splits = k == 5 ? tn_pp_splits(d, &k_chunk) : tn_t_splits(d, k == 2 ? 2 * 256 * 32 * 2 : 2 * 256 * 64 * 2, &k_chunk);
+    const int64_t splits = k == 5 ? tn_pp_splits(d, &k_chunk) : tn_t_splits(d, tn_t_lds(2, k == 2 ? 32 : 64), &k_chunk);
     return tn_det_bytes(d, splits);
 }
 

@@ -19,6 +19,7 @@
 //    it two chunks into the next main loop; now the first chunk behind the stores is chunk 4.
 //  * One kernel for both launch forms: grid = CUs (persistent, tiles v = block, block + grid, ...) or grid = tiles.
 #include "gemm_nt_common.h"
+#include "launch.h"
 
 using namespace m3g;
 
@@ -371,21 +372,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp2_kernel(MfmaArgs a) {
 template <int EPI>
 int launch_pp2_t(const MfmaArgs& a, bool persistent, hipStream_t s) {
     constexpr int lds = 4 * (256 + 256) * 32 * 2 + 8 * 4096;   // 128-KiB ring + 8 slabs = all 160 KiB
-    static bool attr_set = false;
-    static int cus = 256;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_nt_pp2_kernel<EPI>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-            cus = prop.multiProcessorCount / 8 * 8;
-        attr_set = true;
-    }
-    const int64_t tiles = cdiv(a.M, 256) * cdiv(a.N, 256);
+    const int dev = current_device();
+    const int64_t tiles = cdiv(a.M, 256) * cdiv(a.N, 256), cus = device_cus8(dev);
     const unsigned grid = (unsigned)(persistent && tiles > cus ? cus : tiles);
-    hipLaunchKernelGGL((gemm_nt_pp2_kernel<EPI>), dim3(grid), dim3(512), lds, s, a);
-    return hip_launch_status();
+    return launch_dyn_on<gemm_nt_pp2_kernel<EPI>>(dev, dim3(grid), dim3(512), lds, s, a);
 }
 
 int launch_pp2_e(const MfmaArgs& a, int epi, bool persistent, hipStream_t s) {

@@ -7,6 +7,7 @@
 // LDS, writes one partial row per workgroup, and a second kernel folds the partials into the fp32 gradients.
 #include "common.h"
 #include "det_fold.h"
+#include "launch.h"
 
 namespace {
 
@@ -361,13 +362,13 @@ inline int ln_bwd_fold(const float* part, float* dgamma, float* dbeta, int nblk,
 }
 
 // workgroups that can be resident at once (every wave walks its rows in a grid-stride loop: a workgroup that has to wait for
-// a free slot would start a second round with a full share of the rows)
+// a free slot would start a second round with a full share of the rows).  The launchers below keep the answer per PROCESS, from
+// the device of their first call: the kernels are grid-stride, so on a second device with another CU count the cap costs
+// speed at most, never rows.
 template <typename K> int resident_blocks(K kernel, size_t lds) {
-    int per_cu = 0, dev = 0;
-    hipDeviceProp_t prop;
+    int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) != hipSuccess || per_cu <= 0) return 1 << 30;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 1 << 30;
-    return per_cu * prop.multiProcessorCount;
+    return per_cu * device_cus();
 }
 template <typename T, int CPL>
 int launch_fwd(const void* x, const float* g, const float* b, void* y, float* mean, float* rstd, int64_t M, int D,

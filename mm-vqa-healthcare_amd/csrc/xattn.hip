@@ -23,6 +23,7 @@
 // counted vmcnt), with the tile shape, the operand forms (K-contiguous rows or reduction-strided [K][cols] read with
 // ds_read_b64_tr_b16) and the epilogue as template parameters.
 #include "xattn_common.h"
+#include "launch.h"
 
 namespace {
 
@@ -749,20 +750,13 @@ template <int BM, int BN, int WAVES_M, int NSLOT, int NLOAD, int AFORM, int BFOR
 int launch_xg(XgArgs a, int nbatch, hipStream_t s) {
     if (!GEN && (a.a_div || a.b_div || a.k_switch || a.A2 || a.B2)) return M3AE_ERR_ARG;   // needs the GEN = 1 instantiation
     constexpr int lds = NSLOT * (BM + BN) * 64;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&xg_kernel<BM, BN, WAVES_M, NSLOT, NLOAD, AFORM, BFORM, EPI, GEN>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_set = true;
-    }
     a.tiles_m = (a.M + BM - 1) / BM;
     a.tiles_n = (a.N + BN - 1) / BN;
 #ifdef M3AE_XG_TRACE
     a.trace_slot = g_trace_next++ & 7;
 #endif
     const unsigned grid = (unsigned)(nbatch * a.tiles_m * a.tiles_n * (a.ksplit > 1 ? a.ksplit : 1));
-    hipLaunchKernelGGL((xg_kernel<BM, BN, WAVES_M, NSLOT, NLOAD, AFORM, BFORM, EPI, GEN>), dim3(grid), dim3(NLOAD ? 768 : 512), lds, s, a);
-    return hip_launch_status();
+    return launch_dyn<xg_kernel<BM, BN, WAVES_M, NSLOT, NLOAD, AFORM, BFORM, EPI, GEN>>(dim3(grid), dim3(NLOAD ? 768 : 512), lds, s, a);
 }
 
 // ---- the per-head "absorbed operand" builds (K', V', Q', dZ): C[map(m)][n] = alpha * sum_{d < 64} A[m][h dh + d] B[n][h dh + d], one
@@ -888,15 +882,9 @@ template <int BM, int BN, int WAVES_M, int OCC, int PAIR>
 int launch_xbuild_t(XgArgs a, const XbPair& pr, int nbatch, hipStream_t s) {
     if (a.K != 64 || a.bias || a.rowscale || a.accumulate || a.a_div || a.b_div || a.k_switch) return M3AE_ERR_ARG;
     constexpr int lds = 2 * (BM + BN) * 64;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&xbuild_kernel<BM, BN, WAVES_M, OCC, PAIR>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        attr_set = true;
-    }
     a.tiles_m = (a.M + BM - 1) / BM;
     a.tiles_n = (a.N + BN - 1) / BN;
-    hipLaunchKernelGGL((xbuild_kernel<BM, BN, WAVES_M, OCC, PAIR>), dim3((unsigned)(nbatch * a.tiles_m * a.tiles_n)), dim3(256), lds, s, a, pr);
-    return hip_launch_status();
+    return launch_dyn<xbuild_kernel<BM, BN, WAVES_M, OCC, PAIR>>(dim3((unsigned)(nbatch * a.tiles_m * a.tiles_n)), dim3(256), lds, s, a, pr);
 }
 // K = dh = 64 is the only head size of the one-launch image-query path (m3ae_xattn_supported); other head sizes keep the general template
 int launch_xbuild(const XgArgs& a, int nbatch, hipStream_t s) {
@@ -1064,6 +1052,42 @@ extern "C" int64_t m3ae_xattn_probs_ld(const m3ae_xattn_desc* d) {   // row stri
 
 #define XCHK(e) do { const int rc_ = (e); if (rc_ != 0) return rc_; } while (0)
 
+namespace {
+// The m3ae_gemm descriptors of the dense layers around the fused attention.  Every operand is row-major over the B*T text rows
+// (text = queries in dir 0, keys in dir 1) or a weight with D input features; bf16 operands, M3AE_XATTN_NO_PERSISTENT passed on.
+m3ae_gemm_desc dense_desc(const m3ae_xattn_desc& d, const void* A, const void* B, void* C) {
+    m3ae_gemm_desc g{};
+    g.batch1 = g.batch2 = 1;
+    g.dtype_a = g.dtype_b = g.dtype_c = M3AE_BF16;
+    g.alpha = 1.0f;
+    g.launch_flags = (d.launch_flags & M3AE_XATTN_NO_PERSISTENT) ? M3AE_GEMM_NO_PERSISTENT : 0;
+    g.A = A; g.B = B; g.C = C; g.c_sn = 1;
+    return g;
+}
+int64_t text_rows(const m3ae_xattn_desc& d) { return d.B * (d.dir == 0 ? d.Lq : d.Lk); }
+// forward (NT): Y[rows][N] = X[rows][D] W[N][D]^T + bias; the caller adds residual and dropout
+m3ae_gemm_desc dense_fwd(const m3ae_xattn_desc& d, int64_t N, const void* X, const void* W, const float* bias, void* Y) {
+    m3ae_gemm_desc g = dense_desc(d, X, W, Y);
+    g.M = text_rows(d); g.N = N; g.K = d.D;
+    g.a_sm = d.D; g.a_sk = 1; g.b_sk = 1; g.b_sn = d.D; g.c_sm = N; g.bias = bias;
+    return g;
+}
+// weight gradient (TN, fp32, accumulating): dW[N][D] += dY[rows][N]^T X[rows][D], db[N] += column sums of dY
+m3ae_gemm_desc dense_wgrad(const m3ae_xattn_desc& d, int64_t N, const void* dY, const void* X, float* dW, float* db) {
+    m3ae_gemm_desc g = dense_desc(d, dY, X, dW);
+    g.M = N; g.N = d.D; g.K = text_rows(d);
+    g.a_sm = 1; g.a_sk = N; g.b_sk = d.D; g.b_sn = 1; g.c_sm = d.D; g.dtype_c = M3AE_F32; g.accumulate = 1; g.a_rowsum = db;
+    return g;
+}
+// input gradient (NT on the transposed weight): dX[rows][D] = dY[rows][K] Wt[D][K]^T (+ residual)
+m3ae_gemm_desc dense_dgrad(const m3ae_xattn_desc& d, int64_t K, const void* dY, const void* Wt, void* dX, const void* residual = nullptr) {
+    m3ae_gemm_desc g = dense_desc(d, dY, Wt, dX);
+    g.M = text_rows(d); g.N = d.D; g.K = K;
+    g.a_sm = K; g.a_sk = 1; g.b_sk = 1; g.b_sn = K; g.c_sm = d.D; g.residual = residual;
+    return g;
+}
+}  // namespace
+
 extern "C" int m3ae_xattn_fwd(const m3ae_xattn_desc* dp, void* stream) {
     if (!dp || !m3ae_xattn_supported(dp)) return M3AE_ERR_UNSUPPORTED;
     const m3ae_xattn_desc& d = *dp;
@@ -1075,19 +1099,14 @@ extern "C" int m3ae_xattn_fwd(const m3ae_xattn_desc* dp, void* stream) {
     if (!d.x || !d.y || !d.proj || !d.prime || !d.s || !d.out) return M3AE_ERR_ARG;
     if (d.dir == 0 && (!d.probs || (drop && !d.probs_drop))) return M3AE_ERR_ARG;
 
-    m3ae_gemm_desc g{};
-    g.batch1 = g.batch2 = 1;
-    g.dtype_a = g.dtype_b = g.dtype_c = M3AE_BF16;
-    g.alpha = 1.0f;
-    g.a_sk = g.b_sk = g.c_sn = 1;
-    g.launch_flags = (d.launch_flags & M3AE_XATTN_NO_PERSISTENT) ? M3AE_GEMM_NO_PERSISTENT : 0;
+    const DropState drop_attn = make_drop(d.dropout_p, d.seed_attn, d.dropout_salt);
+    const DropState drop_hidden = make_drop(d.dropout_p, d.seed_hidden, d.dropout_salt);
 
     if (d.dir == 0) {
         const int T = Lq, I = Lk, R = T * H;
         if (!d.zctx || !d.ctx || (drop && !d.rowsum)) return M3AE_ERR_ARG;
         // q = x Wq^T + bq                                                         (bert_model.py:263)
-        g.M = (int64_t)B * T; g.N = D; g.K = D;
-        g.A = d.x; g.a_sm = D; g.B = d.wq; g.b_sn = D; g.C = d.proj; g.c_sm = D; g.bias = d.bq;
+        const m3ae_gemm_desc g = dense_fwd(d, D, d.x, d.wq, d.bq, d.proj);
         XCHK(m3ae_gemm(&g, stream));
         {   // Q'[b, t*H + h, :] = scale * q_h Wk_h: one batch item per head, M = B*T rows
             XgArgs a{};
@@ -1109,7 +1128,7 @@ extern "C" int m3ae_xattn_fwd(const m3ae_xattn_desc* dp, void* stream) {
             a.colbias = d.key_mask; a.cb_sb = I;
             a.rowsum_out = drop ? d.rowsum : nullptr;
             a.n_valid = I;
-            a.has_drop = drop; a.drop = make_drop(d.dropout_p, d.seed_attn, d.dropout_salt);
+            a.has_drop = drop; a.drop = drop_attn;
             a.H = H; a.Lq = T; a.drop_ld = (int)drop_ld(I);
             XCHK((launch_xg<128, 640, 2, 3, 0, FORM_K, FORM_K, XE_SOFTMAXROW>(a, B, s)));
         }
@@ -1134,17 +1153,15 @@ extern "C" int m3ae_xattn_fwd(const m3ae_xattn_desc* dp, void* stream) {
             XCHK((launch_xg<384, 128, 4, 4, 4, FORM_K, FORM_K, XE_STORE>(a, H, s)));
         }
         // s = dropout(ctx Wo^T + bo) + x                                          (bert_model.py:361-363)
-        m3ae_gemm_desc o = g;
-        o.M = (int64_t)B * T; o.N = D; o.K = D;
-        o.A = d.ctx; o.a_sm = D; o.B = d.wo; o.b_sn = D; o.C = d.s; o.c_sm = D; o.bias = d.bo; o.residual = d.x;
+        m3ae_gemm_desc o = dense_fwd(d, D, d.ctx, d.wo, d.bo, d.s);
+        o.residual = d.x;
         o.dropout_p = d.dropout_p; o.dropout_seed = d.seed_hidden; o.dropout_salt = d.dropout_salt;
         XCHK(m3ae_gemm(&o, stream));
     } else {
         const int I = Lq, T = Lk, R = H * T;
         if (!d.colbias) return M3AE_ERR_ARG;
         // k | v = y Wkv^T + bkv                                                   (bert_model.py:276-277)
-        g.M = (int64_t)B * T; g.N = 2 * D; g.K = D;
-        g.A = d.y; g.a_sm = D; g.B = d.wkv; g.b_sn = D; g.C = d.proj; g.c_sm = 2 * D; g.bias = d.bkv;
+        const m3ae_gemm_desc g = dense_fwd(d, 2 * D, d.y, d.wkv, d.bkv, d.proj);
         XCHK(m3ae_gemm(&g, stream));
         bf16_t* Kp = (bf16_t*)d.prime;
         bf16_t* Vp = Kp + (int64_t)B * R * D;
@@ -1187,7 +1204,7 @@ extern "C" int m3ae_xattn_fwd(const m3ae_xattn_desc* dp, void* stream) {
             f.X = (const bf16_t*)d.x; f.Kp = Kp; f.Vp = Vp; f.colbias = d.colbias; f.bo = d.bo;
             f.S = (bf16_t*)d.s; f.P = (bf16_t*)d.probs; f.Pd = drop ? (bf16_t*)d.probs_drop : nullptr;
             f.B = B; f.I = I; f.D = D; f.H = H;
-            f.has_drop = drop; f.drop_a = make_drop(d.dropout_p, d.seed_attn, d.dropout_salt); f.drop_h = make_drop(d.dropout_p, d.seed_hidden, d.dropout_salt);
+            f.has_drop = drop; f.drop_a = drop_attn; f.drop_h = drop_hidden;
             f.drop_ld = (int)drop_ld(T);
             // (LayerNorm inside this launch -- single-pass statistics in the pass epilogues, a cross-wave exchange, a normalise
             // pass over the tile's own stores -- was built and measured in round 3: kernel 340 -> 487 us against 89 us for the
@@ -1204,7 +1221,7 @@ extern "C" int m3ae_xattn_fwd(const m3ae_xattn_desc* dp, void* stream) {
                 a.C2 = drop ? (bf16_t*)d.probs_drop : nullptr;
                 a.alpha = 1.0f;
                 a.colbias = d.colbias; a.cb_sb = R;
-                a.has_drop = drop; a.drop = make_drop(d.dropout_p, d.seed_attn, d.dropout_salt);
+                a.has_drop = drop; a.drop = drop_attn;
                 a.H = H; a.Lq = I; a.drop_ld = (int)drop_ld(T);
                 XCHK((launch_xg<128, 384, 2, 4, 4, FORM_K, FORM_K, XE_SOFTMAX32>(a, B, s)));
             }
@@ -1216,7 +1233,7 @@ extern "C" int m3ae_xattn_fwd(const m3ae_xattn_desc* dp, void* stream) {
                 a.C = (bf16_t*)d.s; a.ldc = D;
                 a.bias = d.bo;
                 a.residual = (const bf16_t*)d.x;
-                a.has_drop = drop; a.drop = make_drop(d.dropout_p, d.seed_hidden, d.dropout_salt);
+                a.has_drop = drop; a.drop = drop_hidden;
                 XCHK((launch_xg<128, 384, 2, 4, 4, FORM_K, FORM_T, XE_DENSE>(a, B, s)));
             }
         }
@@ -1261,11 +1278,7 @@ extern "C" int m3ae_xattn_bwd(const m3ae_xattn_desc* dp, void* stream) {
                                 M3AE_BF16, M3AE_ACT_NONE, 0, stream));
     }
     const bf16_t* Pd = (const bf16_t*)(drop ? d.probs_drop : d.probs);
-    m3ae_gemm_desc g{};
-    g.batch1 = g.batch2 = 1;
-    g.dtype_a = g.dtype_b = M3AE_BF16;
-    g.alpha = 1.0f;
-    g.launch_flags = (d.launch_flags & M3AE_XATTN_NO_PERSISTENT) ? M3AE_GEMM_NO_PERSISTENT : 0;
+    const DropState drop_attn = make_drop(d.dropout_p, d.seed_attn, d.dropout_salt);
 
     if (d.dir == 1) {
         const int I = Lq, T = Lk, R = H * T;
@@ -1285,7 +1298,7 @@ extern "C" int m3ae_xattn_bwd(const m3ae_xattn_desc* dp, void* stream) {
             a.M = I; a.N = R; a.K = D;
             a.C = dS; a.ldc = R; a.c_sb = (int64_t)I * R;
             a.P = (const bf16_t*)d.probs;
-            a.has_drop = drop; a.drop = make_drop(d.dropout_p, d.seed_attn, d.dropout_salt);
+            a.has_drop = drop; a.drop = drop_attn;
             a.drop_mode = 1; a.H = H; a.Lq = I; a.drop_ld = (int)drop_ld(T); a.tkeys = T;
             // a wave's columns must hold whole heads: 96 = 3 x 32 (384-wide tile) or 64 (256-wide tile)
             if (T == 32) XCHK((launch_xg<128, 384, 2, 4, 4, FORM_K, FORM_K, XE_DSOFT>(a, B, s)));
@@ -1348,15 +1361,10 @@ extern "C" int m3ae_xattn_bwd(const m3ae_xattn_desc* dp, void* stream) {
                            (const bf16_t*)d.proj, (int64_t)2 * D, d.g_bq, B * T, T, R, 1, T, dh);
         XCHK(hip_launch_status());
         // dWkv += dkv^T y (+ bias gradient), dy = dkv Wkv                                     (bert_model.py:276-277 backward)
-        g.M = 2 * D; g.N = D; g.K = (int64_t)B * T;
-        g.A = dkv; g.a_sm = 1; g.a_sk = 2 * D; g.B = d.y; g.b_sk = D; g.b_sn = 1;
-        g.C = d.g_wkv; g.c_sm = D; g.c_sn = 1; g.dtype_c = M3AE_F32; g.accumulate = 1; g.a_rowsum = d.g_bkv;
-        XCHK(m3ae_gemm(&g, stream));
+        const m3ae_gemm_desc w = dense_wgrad(d, 2 * D, dkv, d.y, d.g_wkv, d.g_bkv);
+        XCHK(m3ae_gemm(&w, stream));
         if (d.dy) {
-            m3ae_gemm_desc y = g;
-            y.M = (int64_t)B * T; y.N = D; y.K = 2 * D;
-            y.A = dkv; y.a_sm = 2 * D; y.a_sk = 1; y.B = d.wkv_t; y.b_sk = 1; y.b_sn = 2 * D;
-            y.C = d.dy; y.c_sm = D; y.dtype_c = M3AE_BF16; y.accumulate = 0; y.a_rowsum = nullptr;
+            const m3ae_gemm_desc y = dense_dgrad(d, 2 * D, dkv, d.wkv_t, d.dy);
             XCHK(m3ae_gemm(&y, stream));
         }
         return 0;
@@ -1373,17 +1381,9 @@ extern "C" int m3ae_xattn_bwd(const m3ae_xattn_desc* dp, void* stream) {
     float* delta = d.ws_vec;
     float* radd = drop ? d.ws_vec + (int64_t)B * R : nullptr;
     // output dense: dWo += dsd^T ctx (+ dbo), dctx = dsd Wo                                         (bert_model.py:361 backward)
-    g.M = D; g.N = D; g.K = Mq;
-    g.A = dsd; g.a_sm = 1; g.a_sk = D; g.B = d.ctx; g.b_sk = D; g.b_sn = 1;
-    g.C = d.g_wo; g.c_sm = D; g.c_sn = 1; g.dtype_c = M3AE_F32; g.accumulate = 1; g.a_rowsum = d.g_bo;
-    XCHK(m3ae_gemm(&g, stream));
-    {
-        m3ae_gemm_desc y = g;
-        y.M = Mq; y.N = D; y.K = D;
-        y.A = dsd; y.a_sm = D; y.a_sk = 1; y.B = d.wo_t; y.b_sk = 1; y.b_sn = D;
-        y.C = dctx; y.c_sm = D; y.dtype_c = M3AE_BF16; y.accumulate = 0; y.a_rowsum = nullptr;
-        XCHK(m3ae_gemm(&y, stream));
-    }
+    const m3ae_gemm_desc wo_grad = dense_wgrad(d, D, dsd, d.ctx, d.g_wo, d.g_bo), dctx_grad = dense_dgrad(d, D, dsd, d.wo_t, dctx);
+    XCHK(m3ae_gemm(&wo_grad, stream));
+    XCHK(m3ae_gemm(&dctx_grad, stream));
     {   // dZ[b, t*H + h, :] = dctx_h Wv_h ; dWv[h] += dctx_h^T Z_h ; dbv
         XgArgs a{};
         a.A = dctx; a.lda = D; a.a_sb = dh;
@@ -1412,7 +1412,7 @@ extern "C" int m3ae_xattn_bwd(const m3ae_xattn_desc* dp, void* stream) {
         a.M = R; a.N = 640; a.K = D;
         a.C = dS; a.ldc = 640; a.c_sb = (int64_t)R * 640;
         a.P = (const bf16_t*)d.probs; a.delta = delta; a.radd = radd;
-        a.has_drop = drop; a.drop = make_drop(d.dropout_p, d.seed_attn, d.dropout_salt);
+        a.has_drop = drop; a.drop = drop_attn;
         a.drop_mode = 0; a.H = H; a.Lq = T; a.drop_ld = (int)drop_ld(I);
         XCHK((launch_xg<128, 640, 2, 3, 0, FORM_K, FORM_K, XE_DSOFT>(a, B, s)));
     }
@@ -1449,17 +1449,9 @@ extern "C" int m3ae_xattn_bwd(const m3ae_xattn_desc* dp, void* stream) {
         XCHK((launch_xg<128, 384, 2, 4, 4, FORM_T, FORM_T, XE_ATOMIC>(w, H, s)));
     }
     // query projection: dWq += dq^T x (+ dbq), dx = dq Wq + ds                                   (bert_model.py:263 backward)
-    g.M = D; g.N = D; g.K = Mq;
-    g.A = dq; g.a_sm = 1; g.a_sk = D; g.B = d.x; g.b_sk = D; g.b_sn = 1;
-    g.C = d.g_wq; g.c_sm = D; g.c_sn = 1; g.dtype_c = M3AE_F32; g.accumulate = 1; g.a_rowsum = d.g_bq;
-    XCHK(m3ae_gemm(&g, stream));
-    {
-        m3ae_gemm_desc y = g;
-        y.M = Mq; y.N = D; y.K = D;
-        y.A = dq; y.a_sm = D; y.a_sk = 1; y.B = d.wq_t; y.b_sk = 1; y.b_sn = D;
-        y.C = d.dx; y.c_sm = D; y.dtype_c = M3AE_BF16; y.accumulate = 0; y.a_rowsum = nullptr; y.residual = d.ws_ds;
-        XCHK(m3ae_gemm(&y, stream));
-    }
+    const m3ae_gemm_desc wq_grad = dense_wgrad(d, D, dq, d.x, d.g_wq, d.g_bq), dx_grad = dense_dgrad(d, D, dq, d.wq_t, d.dx, d.ws_ds);
+    XCHK(m3ae_gemm(&wq_grad, stream));
+    XCHK(m3ae_gemm(&dx_grad, stream));
     return 0;
 }
 

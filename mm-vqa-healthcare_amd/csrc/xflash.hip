@@ -21,6 +21,7 @@
 // Measured (profiles/r03_xflash_*.txt): 337-363 us at B = 256 for 174 GFLOP; 256 us of it with no operand staged at
 // all (the barrier-coupled structure), a tile's 66 us = prologue 5 + product 1 24 + softmax / image 5 + product 2 24 + epilogues 6.
 #include "xattn_common.h"
+#include "launch.h"
 #include <type_traits>
 
 #ifndef XF_ST_AUX
@@ -497,15 +498,9 @@ __global__ __launch_bounds__(768, 3) void xf1_kernel(XfArgs a) {
 
 template <int BM, int R, int T>
 int launch_xf1(XfArgs a, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&xf1_kernel<BM, R, T>), hipFuncAttributeMaxDynamicSharedMemorySize, XF_LDS);
-        attr_set = true;
-    }
     a.tiles_m = (a.I + BM - 1) / BM;
     const unsigned grid = (unsigned)(a.B * a.tiles_m);
-    hipLaunchKernelGGL((xf1_kernel<BM, R, T>), dim3(grid), dim3(768), XF_LDS, s, a);
-    return hip_launch_status();
+    return launch_dyn<xf1_kernel<BM, R, T>>(dim3(grid), dim3(768), XF_LDS, s, a);
 }
 
 }  // namespace

@@ -767,3 +767,68 @@ def test_attention_backward_generations_agree_bit_for_bit(shape, drop):
         ops.ATTN_LEGACY = False
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
     assert outs[0][0].float().abs().max().item() > 0
+
+
+@pytest.mark.parametrize("flags", [3, 4, 5, 7])
+def test_attention_dropout_refuses_the_flag_combinations_without_an_instance(flags):
+    """Dropout instances of the bf16 attention kernels exist for no flag, a key mask (1), a position bias (2) and a causal bias
+    (6).  Every other combination of key mask (1) | position bias (2) | causal (4) under dropout is refused with the library's
+    unsupported error, forward and backward, before any launch: the outputs keep what they held."""
+    from m3ae_amd._lib import M3AEHipError
+    B, H, L, dh = 1, 1, 33, 64
+    dt = torch.bfloat16
+    q, k, v, do = (rnd(B, L, H * dh, dtype=dt, seed=s_) for s_ in (201, 202, 203, 204))
+    mask = torch.zeros(B, L, device=dev()) if flags & 1 else None
+    bias = rnd(H, L, L, seed=205) if flags & 2 else None
+    causal = bool(flags & 4)
+    with pytest.raises(M3AEHipError, match="unsupported"):
+        ops.attn_forward(q, k, v, H, mask, bias, scale=1.0, causal=causal, dropout=(0.1, 99))
+    o, lse = torch.zeros_like(q), torch.zeros(B, H, 64, device=dev())
+    dq, dk, dv = (torch.full_like(q, 7.0) for _ in range(3))
+    with pytest.raises(M3AEHipError, match="unsupported"):
+        ops.attn_backward(q, k, v, o, lse, do, dq, dk, dv, H, mask, bias, scale=1.0, causal=causal, dropout=(0.1, 99))
+    torch.cuda.synchronize()
+    assert all(bool((t == 7.0).all()) for t in (dq, dk, dv))
+    # the same flags without dropout have an instance
+    ops.attn_forward(q, k, v, H, mask, bias, scale=1.0, causal=causal)
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two devices in one process")
+def test_large_lds_kernels_on_a_second_device_of_the_same_process():
+    """The kernels that ask for more than 64 KiB of dynamic LDS opt in per device: the same bf16 NT GEMM (256^3, pinned to the
+    160-KiB second-generation ping-pong kernel) and the same split-K wgrad (256 x 256 over 4096 rows, pinned to the 128-KiB
+    ping-pong TN kernel) run on device 0, then on device 1 of one process, and give the same bits.  The wgrad runs in
+    deterministic mode for the comparison (its atomic form rounds by order of arrival) and once in its atomic form.
+    (ops caches the device index of its stream lookup, one process driving one GPU: the test clears that cache per device.)"""
+    x, w = rnd(256, 256, dtype=torch.bfloat16, seed=211).cpu(), rnd(256, 256, dtype=torch.bfloat16, scale=1 / 16, seed=212).cpu()
+    dy, a = rnd(4096, 256, dtype=torch.bfloat16, seed=213).cpu(), rnd(4096, 256, dtype=torch.bfloat16, seed=214).cpu()
+    before, cached = torch.cuda.current_device(), ops._dev_index
+    ops.GEMM_NT_VARIANT, ops.GEMM_TN_VARIANT = 9, 5
+    # last_gemm_path() names the TN family, not the kernel: variant 5 is honoured for outputs of whole 256 x 256 tiles over at
+    # least 4096 rows (tn_kernel_choice in gemm_mfma.hip) and falls back to a 128 x 128 kernel otherwise
+    assert dy.shape[1] % 256 == 0 and a.shape[1] % 256 == 0 and dy.shape[0] >= 4096
+    out = []
+    try:
+        for i in (0, 1):
+            torch.cuda.set_device(i)
+            ops._dev_index = None
+            xd, wd, dyd, ad = (t.to(f"cuda:{i}") for t in (x, w, dy, a))
+            y, _ = ops.mm_nt(xd, 256, 256, wd)
+            assert ops.last_gemm_path() == "mfma_nt_pp2"
+            g, gdet = (torch.ones(256, 256, dtype=torch.float32, device=f"cuda:{i}") for _ in range(2))
+            ops.gemm(dyd, 1, 256, ad, 256, 1, g, 256, 256, 256, 4096, accumulate=True)
+            assert ops.last_gemm_path() == "mfma_tn"
+            with ops.deterministic_mode():
+                ops.gemm(dyd, 1, 256, ad, 256, 1, gdet, 256, 256, 256, 4096, accumulate=True)
+            torch.cuda.synchronize(i)
+            out.append((y.cpu(), gdet.cpu(), g.cpu()))
+    finally:
+        ops.GEMM_NT_VARIANT = ops.GEMM_TN_VARIANT = -1
+        torch.cuda.set_device(before)
+        ops._dev_index = cached
+    ref = 1.0 + dy.float().t() @ a.float()
+    for y, gdet, g in out:
+        close(y, x.float() @ w.float().t(), 2e-2, 2e-2, msg="nt")
+        close(gdet, ref, 1e-4, 1e-3 * math.sqrt(4096), msg="wgrad, ordered")
+        close(g, ref, 1e-4, 1e-3 * math.sqrt(4096), msg="wgrad, atomic")
+    assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
