@@ -37,6 +37,9 @@ extern "C" {
  *    [B][H][Lq][Lk]; no descriptor changed. */
 /* 4 (additive): device image transform.  m3ae_image_resample_u8 / m3ae_image_resample_workspace_bytes (Pillow-exact bicubic resize +
  *    centre crop + ToTensor / Normalize from the decoded source bytes); no descriptor changed. */
+/* 4 (additive): dropout row map.  m3ae_gemm_rows, m3ae_attn_fwd_rows / m3ae_attn_bwd_rows, m3ae_layernorm_bwd_drop_rows and
+ *    m3ae_dropout_rows: the entry points they are named after with (row_base, row_step), so that a call on a subset of a tensor's
+ *    rows draws the dropout masks of the full tensor (see m3ae_dropout); no descriptor changed. */
 #define M3AE_ABI_VERSION 4
 
 enum { M3AE_F32 = 0, M3AE_BF16 = 1 };
@@ -120,6 +123,12 @@ enum { M3AE_GEMM_NO_PERSISTENT = 1,
 #define M3AE_GEMM_TN_VARIANT(v) ((((v) + 1) & 0xf) << 12)
 #define M3AE_GEMM_COL_GROUP(g) (((g) & 0xf) << 16)
 int m3ae_gemm(const m3ae_gemm_desc* d, void* stream);
+/* m3ae_gemm with a dropout row map: row m of the call is row row_base + m * row_step of the dropout mask (every other index of
+ * the call is unchanged).  A call on rows r0, r0 + s, ... of a larger product (A addressed through a_sm, the outputs compact)
+ * then applies the mask the full product applies to those rows.  (0, 1) is m3ae_gemm.  M3AE_ERR_ARG before any launch for
+ * row_step < 1, row_base < 0 or a mapped index (row_base + (M - 1) row_step + 1) * ld(N) beyond 2^63 - 1; M3AE_ERR_UNSUPPORTED
+ * for a wgrad (TN) descriptor that asks for dropout under a map.  ABI 4, additive. */
+int m3ae_gemm_rows(const m3ae_gemm_desc* d, int64_t row_base, int64_t row_step, void* stream);
 /* Deterministic mode of the TN (wgrad) family: the same kernels, tiles, split-K fan-out and accumulation order inside a split
  * (M3AE_GEMM_TN_VARIANT pins them as before), but every (tile, split) workgroup stores its fp32 accumulators -- and its partial
  * a_rowsum rows -- to `workspace` with 16-byte stores, and a streaming kernel behind it performs, with one writer per element,
@@ -177,6 +186,11 @@ enum { M3AE_ATTN_LEGACY_KERNELS = 1,
 int64_t m3ae_attn_workspace_bytes(const m3ae_attn_desc* d, int backward);
 int m3ae_attn_fwd(const m3ae_attn_desc* d, void* stream);
 int m3ae_attn_bwd(const m3ae_attn_desc* d, void* stream);
+/* The same with a row map of the probability-dropout mask: mask row row_base + ((b*H + h)*Lq + q) * row_step.  A call on query 0
+ * alone (Lq = 1, q_sb = the batch stride of the full tensor) with row_step = Lq_full draws the masks query 0 has in the call on
+ * all Lq_full queries.  Argument checks as m3ae_gemm_rows (rows = B*H*Lq, cols = Lk).  ABI 4, additive. */
+int m3ae_attn_fwd_rows(const m3ae_attn_desc* d, int64_t row_base, int64_t row_step, void* stream);
+int m3ae_attn_bwd_rows(const m3ae_attn_desc* d, int64_t row_base, int64_t row_step, void* stream);
 /* The attention probabilities of the m3ae_attn_fwd call made with the same descriptor (the visualisation maps of
  * bert_model.py:346): probs[b * p_sb + h * p_sh + q * p_sq + k] (fp32, strides in elements, p_sq >= Lk) for q < Lq, k < Lk,
  *   = softmax_k(q.k / sqrt(dh) + key_mask[b][k])                    with dropout_p == 0,
@@ -290,6 +304,11 @@ int m3ae_layernorm_bwd_drop(const void* dy, const void* x, const float* gamma, c
                             const float* rstd, void* dx, void* dx_drop, float dropout_p, uint64_t dropout_seed,
                             const void* dropout_salt, float* dgamma, float* dbeta, float* workspace, int64_t M, int64_t D,
                             int dtype, void* stream);
+/* the same on rows row_base + m * row_step of the mask (m3ae_gemm_rows); ABI 4, additive */
+int m3ae_layernorm_bwd_drop_rows(const void* dy, const void* x, const float* gamma, const float* beta, const float* mean,
+                                 const float* rstd, void* dx, void* dx_drop, float dropout_p, uint64_t dropout_seed,
+                                 const void* dropout_salt, float* dgamma, float* dbeta, float* workspace, int64_t M, int64_t D,
+                                 int dtype, int64_t row_base, int64_t row_step, void* stream);
 /* out = dropout(x) on a dense [rows][cols] array with the library's counter-hash mask (forward and backward are
  * the same map).  Every dropout site of the library -- this call, the GEMM epilogue (rows = M, cols = N), the
  * LayerNorm backward second output, and attention probabilities (rows = (b*H + h)*Lq + q, cols = Lk) -- uses the mask
@@ -297,6 +316,11 @@ int m3ae_layernorm_bwd_drop(const void* dy, const void* x, const float* gamma, c
  * [rows][cols], optional) is the mask those kernels apply for the same (p, seed). */
 int m3ae_dropout(const void* x, void* out, uint8_t* keep_mask, int64_t rows, int64_t cols, float p, uint64_t seed,
                  const void* salt, int dtype, void* stream);
+/* Row map (ABI 4, additive): the *_rows entry points take (row_base, row_step) and use mask row row_base + row * row_step in that
+ * index, so a call on every row_step-th row of a site draws the masks of the call on all rows; (0, 1) is the plain entry point.
+ * Checked on the host before any launch: row_step >= 1, row_base >= 0, last mapped index < 2^63 (else M3AE_ERR_ARG). */
+int m3ae_dropout_rows(const void* x, void* out, uint8_t* keep_mask, int64_t rows, int64_t cols, float p, uint64_t seed,
+                      const void* salt, int dtype, int64_t row_base, int64_t row_step, void* stream);
 
 /* out[n] (+)= sum_m x[m][n]  (bias gradients; x has row stride ldx elements). */
 int m3ae_colsum(const void* x, float* out, int64_t M, int64_t N, int64_t ldx, int dtype, int accumulate,

@@ -18,8 +18,8 @@
 #include <stdlib.h>
 #include <type_traits>
 
-int m3ae_gemm_generic(const m3ae_gemm_desc& d, hipStream_t s);
-int m3ae_gemm_f32x3(const m3ae_gemm_desc& d, hipStream_t s);
+int m3ae_gemm_generic(const m3ae_gemm_desc& d, hipStream_t s, DropRows rows = DropRows{0, 1});
+int m3ae_gemm_f32x3(const m3ae_gemm_desc& d, hipStream_t s, DropRows rows = DropRows{0, 1});
 
 namespace {
 
@@ -42,7 +42,7 @@ struct AttnArgs {
     bf16_t* dq; bf16_t* dk; bf16_t* dv;
     float* delta;
     float* d_pos_bias;
-    DropState drop;  // attention-probability dropout (bert_model.py:334); mask index ((b H + h) Lq + q) * ld(Lk) + k
+    DropState drop;  // attention-probability dropout (bert_model.py:334); mask index row * ld(Lk) + k, row = drop_row((b H + h) Lq + q)
     int has_drop;
 };
 DEVINL int64_t drop_ldk(int64_t Lk) { return (Lk + 3) & ~(int64_t)3; }
@@ -343,7 +343,7 @@ __global__ __launch_bounds__(256, (NQ == 1 && !MASK && !BIAS && !CAUSAL && !DROP
             const int64_t key0 = (int64_t)kt * 32;
 #pragma unroll
             for (int n = 0; n < NQ; ++n) {
-                const uint64_t drow = (uint64_t)(((b * a.H + head) * a.Lq + qi[n]) * drop_ldk(a.Lk));
+                const uint64_t drow = (uint64_t)(drop_row(a.drop, (b * a.H + head) * a.Lq + qi[n]) * drop_ldk(a.Lk));
                 if (last) score_to_prob<MASK, BIAS, CAUSAL, true, DROP>(s[n], m[n], l[n], o[n][0], o[n][1], a, mrow, brow[n], key0, qi[n], h, drow);
                 else score_to_prob<MASK, BIAS, CAUSAL, false, DROP>(s[n], m[n], l[n], o[n][0], o[n][1], a, mrow, brow[n], key0, qi[n], h, drow);
             }
@@ -418,7 +418,7 @@ __global__ __launch_bounds__(256, 2) void attn_probs_kernel(AttnArgs a, float* _
         nl[reg] = -lrow[q < a.Lq ? q : a.Lq - 1];
     }
     float* prow = P + b * p_sb + head * p_sh;
-    const uint64_t drow0 = (uint64_t)((b * a.H + head) * a.Lq) * drop_ldk(a.Lk);
+    const uint64_t drow0 = (uint64_t)drop_row(a.drop, (b * a.H + head) * a.Lq) * drop_ldk(a.Lk);
     const bf16_t* kbase = a.k + b * a.k_sb + head * 64;
     const float* mrow = MASK ? a.key_mask + b * a.Lk : nullptr;
     const int nkt = (int)((a.Lk + 31) / 32);
@@ -443,7 +443,7 @@ __global__ __launch_bounds__(256, 2) void attn_probs_kernel(AttnArgs a, float* _
             for (int reg = 0; reg < 16; ++reg) {
                 const int64_t q = q0 + crow(reg, h);
                 float p = fast_exp2(fmaf(s[reg], a.scale_log2, madd) + nl[reg]);
-                if (DROP) p = drop_keep(a.drop, drow0 + (uint64_t)q * drop_ldk(a.Lk) + (uint64_t)key) ? p * a.drop.inv_keep : 0.f;
+                if (DROP) p = drop_keep(a.drop, drow0 + (uint64_t)(q * a.drop.row_step) * drop_ldk(a.Lk) + (uint64_t)key) ? p * a.drop.inv_keep : 0.f;
                 if (kin && q < a.Lq) prow[q * p_sq + key] = p;
             }
         }
@@ -504,7 +504,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_coop_kernel(AttnArgs a) {
 
     f32x16 g0 = zero16(), g1 = zero16();
     const int nkt = (int)((a.Lk + 31) / 32);
-    const uint64_t drow = (uint64_t)(((b * a.H + head) * a.Lq + qi) * drop_ldk(a.Lk));
+    const uint64_t drow = (uint64_t)(drop_row(a.drop, (b * a.H + head) * a.Lq + qi) * drop_ldk(a.Lk));
     s16x8 kreg = coop_load(kbase, a.k_sl, 0, a.Lk, t);
     s16x8 vreg = coop_load(vbase, a.v_sl, 0, a.Lk, t);
     put_row_img(lds, kreg, t);
@@ -687,10 +687,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_coop_kernel(AttnArgs a) 
             uint32_t hq[4] = {0u, 0u, 0u, 0u};
             if (DROP) {
                 const uint64_t ldq = (uint64_t)(drop_ldk(a.Lk) >> 2);
-                const uint64_t g0 = (uint64_t)((b * a.H + head) * a.Lq + (int64_t)qt * 32 + 4 * h + (lane & 3)) * ldq +
+                const uint64_t g0 = (uint64_t)drop_row(a.drop, (b * a.H + head) * a.Lq + (int64_t)qt * 32 + 4 * h + (lane & 3)) * ldq +
                                     (uint64_t)((k0 + (r & ~3)) >> 2);
 #pragma unroll
-                for (int g = 0; g < 4; ++g) hq[g] = drop_hash(a.drop, g0 + (uint64_t)(8 * g) * ldq);
+                for (int g = 0; g < 4; ++g) hq[g] = drop_hash(a.drop, g0 + (uint64_t)(8 * g * a.drop.row_step) * ldq);
             }
             const uint32_t rot = 8u * ((uint32_t)r & 3u);
             auto elements = [&](auto last_c) {   // the row-bounds select only exists in the instantiation of the last query tile
@@ -886,10 +886,10 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv2_kernel(AttnArgs a) {
                 uint32_t hq[4] = {0u, 0u, 0u, 0u};
                 if (DROP) {   // (the quad-shared hashes of attn_bwd_dkdv_coop_kernel)
                     const uint64_t ldq = (uint64_t)(drop_ldk(a.Lk) >> 2);
-                    const uint64_t g0 = (uint64_t)((b * a.H + head) * a.Lq + (int64_t)qt * 32 + 4 * h + (lane & 3)) * ldq +
+                    const uint64_t g0 = (uint64_t)drop_row(a.drop, (b * a.H + head) * a.Lq + (int64_t)qt * 32 + 4 * h + (lane & 3)) * ldq +
                                         (uint64_t)((k0 + (r & ~3)) >> 2);
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) hq[g] = drop_hash(a.drop, g0 + (uint64_t)(8 * g) * ldq);
+                    for (int g = 0; g < 4; ++g) hq[g] = drop_hash(a.drop, g0 + (uint64_t)(8 * g * a.drop.row_step) * ldq);
                 }
                 const uint32_t rot = 8u * ((uint32_t)r & 3u);
                 auto elements = [&](auto last_c) {
@@ -985,7 +985,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq2_kernel(AttnArgs a) {
     f32x16 g0 = zero16(), g1 = zero16();
     const int nkt = (int)((a.Lk + 31) / 32);
     const int nst = (nkt + TPS - 1) / TPS;
-    const uint64_t drow = (uint64_t)(((b * a.H + head) * a.Lq + qi) * drop_ldk(a.Lk));
+    const uint64_t drow = (uint64_t)(drop_row(a.drop, (b * a.H + head) * a.Lq + qi) * drop_ldk(a.Lk));
     s16x8 kreg[TPS], vreg[TPS];
     auto fetch = [&](int st) {
 #pragma unroll
@@ -1174,7 +1174,7 @@ int attn_f32_scores(const m3ae_attn_desc& d, float* S, hipStream_t s) {
     return hip_launch_status();
 }
 
-AttnArgs to_args(const m3ae_attn_desc& d) {
+AttnArgs to_args(const m3ae_attn_desc& d, DropRows rows = DropRows{0, 1}) {
     AttnArgs a{};
     a.q = (const bf16_t*)d.q; a.q_sb = d.q_sb; a.q_sl = d.q_sl;
     a.k = (const bf16_t*)d.k; a.k_sb = d.k_sb; a.k_sl = d.k_sl;
@@ -1187,7 +1187,7 @@ AttnArgs to_args(const m3ae_attn_desc& d) {
     a.d_o = (const bf16_t*)d.d_o; a.dq = (bf16_t*)d.dq; a.dk = (bf16_t*)d.dk; a.dv = (bf16_t*)d.dv;
     a.delta = d.delta; a.d_pos_bias = d.d_pos_bias;
     a.has_drop = d.dropout_p > 0.f;
-    a.drop = make_drop(d.dropout_p, d.dropout_seed, d.dropout_salt);
+    a.drop = make_drop(d.dropout_p, d.dropout_seed, d.dropout_salt, rows);
     return a;
 }
 
@@ -1203,6 +1203,13 @@ bool bf16_layout_ok(const m3ae_attn_desc& d, Layout need) {
     return ok;
 }
 
+// row map of the probability-dropout mask: the call's mask rows are (b H + h) Lq + q, B H Lq of them, Lk columns
+bool attn_rows_ok(const m3ae_attn_desc& d, DropRows rows) {
+    if (d.B <= 0 || d.H <= 0 || d.Lq <= 0 || d.Lk <= 0) return rows.step >= 1 && rows.base >= 0;
+    if (d.B > INT64_MAX / d.H || d.B * d.H > INT64_MAX / d.Lq) return false;
+    return drop_rows_ok(rows, d.B * d.H * d.Lq, d.Lk);
+}
+
 }  // namespace
 
 
@@ -1213,15 +1220,19 @@ extern "C" int64_t m3ae_attn_workspace_bytes(const m3ae_attn_desc* d, int backwa
     return backward ? 2 * one : one;
 }
 
-extern "C" int m3ae_attn_fwd(const m3ae_attn_desc* dp, void* stream) {
+extern "C" int m3ae_attn_fwd(const m3ae_attn_desc* dp, void* stream) { return m3ae_attn_fwd_rows(dp, 0, 1, stream); }
+
+extern "C" int m3ae_attn_fwd_rows(const m3ae_attn_desc* dp, int64_t row_base, int64_t row_step, void* stream) {
     if (!dp || !dp->q || !dp->k || !dp->v || !dp->o) return M3AE_ERR_ARG;
     const m3ae_attn_desc& d = *dp;
     if (d.B <= 0 || d.H <= 0 || d.Lq <= 0 || d.Lk <= 0 || d.Dh <= 0) return M3AE_ERR_ARG;
+    const DropRows map{row_base, row_step};
+    if (!attn_rows_ok(d, map)) return M3AE_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (d.dtype == M3AE_BF16) {
         if (!bf16_layout_ok(d, LAYOUT_FWD)) return M3AE_ERR_UNSUPPORTED;
         if (d.H > 65535 || d.B > 65535) return M3AE_ERR_UNSUPPORTED;
-        AttnArgs a = to_args(d);
+        AttnArgs a = to_args(d, map);
         // 32 query rows per wave everywhere (577 = 18 x 32 + 1: finer blocks waste less, occupancy 4: 188 -> 135 us at B = 64
         // against 64 rows per wave on the long sequences)
         dim3 grid((unsigned)cdiv(d.Lq, 128), (unsigned)d.H, (unsigned)d.B);
@@ -1236,7 +1247,8 @@ extern "C" int m3ae_attn_fwd(const m3ae_attn_desc* dp, void* stream) {
     int rc = attn_f32_scores(d, S, s);
     if (rc) return rc;
     if (d.dropout_p > 0.f &&  // P is [B H Lq][Lk]: rows x cols of the same mask index the bf16 kernels use
-        (rc = m3ae_dropout(S, S, nullptr, d.B * d.H * d.Lq, d.Lk, d.dropout_p, d.dropout_seed, d.dropout_salt, M3AE_F32, stream)))
+        (rc = m3ae_dropout_rows(S, S, nullptr, d.B * d.H * d.Lq, d.Lk, d.dropout_p, d.dropout_seed, d.dropout_salt, M3AE_F32, row_base,
+                                row_step, stream)))
         return rc;
     // O = P . V
     const Mat V = heads(d, d.v, d.Lk, d.v_sl, d.v_sb), O = heads(d, d.o, d.Lq, d.o_sl, d.o_sb);
@@ -1270,14 +1282,18 @@ extern "C" int m3ae_attn_probs(const m3ae_attn_desc* dp, float* probs, int64_t p
     return 0;
 }
 
-extern "C" int m3ae_attn_bwd(const m3ae_attn_desc* dp, void* stream) {
+extern "C" int m3ae_attn_bwd(const m3ae_attn_desc* dp, void* stream) { return m3ae_attn_bwd_rows(dp, 0, 1, stream); }
+
+extern "C" int m3ae_attn_bwd_rows(const m3ae_attn_desc* dp, int64_t row_base, int64_t row_step, void* stream) {
     if (!dp || !dp->q || !dp->k || !dp->v || !dp->o || !dp->d_o || !dp->dq || !dp->dk || !dp->dv)
         return M3AE_ERR_ARG;
     const m3ae_attn_desc& d = *dp;
+    const DropRows map{row_base, row_step};
+    if (!attn_rows_ok(d, map)) return M3AE_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (d.dtype == M3AE_BF16) {
         if (!bf16_layout_ok(d, LAYOUT_BWD)) return M3AE_ERR_UNSUPPORTED;
-        AttnArgs a = to_args(d);
+        AttnArgs a = to_args(d, map);
         dim3 gq((unsigned)cdiv(cdiv(d.Lq, 32), 4), (unsigned)d.H, (unsigned)d.B);
         dim3 gk((unsigned)cdiv(cdiv(d.Lk, 32), 4), (unsigned)d.H, (unsigned)d.B);
         // round-4 kernels: one LDS image per operand, two tiles per barrier.  Either dQ kernel also publishes delta = rowsum(dO * O)
@@ -1304,7 +1320,8 @@ extern "C" int m3ae_attn_bwd(const m3ae_attn_desc* dp, void* stream) {
     float* dS = P + d.B * d.H * QK;
     int rc = attn_f32_scores(d, P, s);
     if (rc) return rc;
-    if (drop && (rc = m3ae_dropout(P, P, nullptr, d.B * d.H * d.Lq, d.Lk, d.dropout_p, d.dropout_seed, d.dropout_salt, M3AE_F32, stream)))
+    if (drop && (rc = m3ae_dropout_rows(P, P, nullptr, d.B * d.H * d.Lq, d.Lk, d.dropout_p, d.dropout_seed, d.dropout_salt, M3AE_F32,
+                                        row_base, row_step, stream)))
         return rc;  // dV below needs the dropped P that multiplied V in the forward pass
     const Mat Q = heads(d, d.q, d.Lq, d.q_sl, d.q_sb), K = heads(d, d.k, d.Lk, d.k_sl, d.k_sb), V = heads(d, d.v, d.Lk, d.v_sl, d.v_sb);
     const Mat dQ = heads(d, d.dq, d.Lq, d.q_sl, d.q_sb), dK = heads(d, d.dk, d.Lk, d.k_sl, d.k_sb), dV = heads(d, d.dv, d.Lk, d.v_sl, d.v_sb);
@@ -1316,7 +1333,8 @@ extern "C" int m3ae_attn_bwd(const m3ae_attn_desc* dp, void* stream) {
     const int64_t rows = d.B * d.H * d.Lq;
     if (drop) {  // the softmax backward needs the un-dropped P and dP wrt it
         if ((rc = attn_f32_scores(d, P, s))) return rc;
-        if ((rc = m3ae_dropout(dS, dS, nullptr, d.B * d.H * d.Lq, d.Lk, d.dropout_p, d.dropout_seed, d.dropout_salt, M3AE_F32, stream)))
+        if ((rc = m3ae_dropout_rows(dS, dS, nullptr, d.B * d.H * d.Lq, d.Lk, d.dropout_p, d.dropout_seed, d.dropout_salt, M3AE_F32,
+                                    row_base, row_step, stream)))
             return rc;
     }
     hipLaunchKernelGGL(softmax_bwd_rows_kernel, dim3((unsigned)cdiv(rows, 4)), dim3(256), 0, s, P, dS, rows, d.Lk);

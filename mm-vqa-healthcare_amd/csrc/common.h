@@ -196,10 +196,15 @@ DEVINL uint32_t lowbias32(uint32_t x) {
 // salt (ABI 3): optional DEVICE pointer to a 32-bit per-step value folded into the key by drop_resolve() at kernel entry.  A step
 // captured in a hipGraph replays with the SAME kernel arguments (seeds included); the caller bumps *salt between replays and every
 // site draws a fresh mask.  NULL (eager runs: the host draws a fresh seed per site and step) leaves the key as it is.
-struct DropState { uint32_t key_lo, key_hi, thr; float inv_keep; const uint32_t* salt; };
-static inline DropState make_drop(float p, uint64_t seed, const void* salt = nullptr) {
+// Row map (the *_rows entry points): a call on a subset of a tensor's rows draws the masks of the FULL tensor.  Row r of the call
+// is mask row row_base + r * row_step; (0, 1), the value every other entry point passes, is the identity.  Both values are
+// kernel arguments (wave-uniform scalars): drop_row() is the only place that applies them.
+struct DropState { uint32_t key_lo, key_hi, thr; float inv_keep; const uint32_t* salt; int64_t row_base, row_step; };
+struct DropRows { int64_t base, step; };   // host side: the row map of one call, identity by default
+static inline DropState make_drop(float p, uint64_t seed, const void* salt = nullptr, DropRows rows = DropRows{0, 1}) {
     DropState d;
     d.salt = (const uint32_t*)salt;
+    d.row_base = rows.base; d.row_step = rows.step;
     d.key_lo = (uint32_t)seed; d.key_hi = (uint32_t)(seed >> 32);
     double t = (double)p * 4294967296.0;
     d.thr = t >= 4294967295.0 ? 4294967295U : (uint32_t)t;
@@ -209,9 +214,10 @@ static inline DropState make_drop(float p, uint64_t seed, const void* salt = nul
 DEVINL void drop_resolve(DropState& d) {   // once per kernel, before the first hash (wave-uniform scalar load)
     if (d.salt) d.key_hi += *d.salt * 0x85EBCA6BU;
 }
-DEVINL DropState make_drop_dev(float p, uint64_t seed, const void* salt = nullptr) {  // same as make_drop, callable on the device
+DEVINL DropState make_drop_dev(float p, uint64_t seed, const void* salt = nullptr, int64_t row_base = 0, int64_t row_step = 1) {  // same as make_drop, callable on the device
     DropState d;
     d.salt = (const uint32_t*)salt;
+    d.row_base = row_base; d.row_step = row_step;
     d.key_lo = (uint32_t)seed; d.key_hi = (uint32_t)(seed >> 32);
     const float t = p * 4294967296.0f;
     d.thr = t >= 4294967040.0f ? 4294967295U : (uint32_t)t;
@@ -219,6 +225,16 @@ DEVINL DropState make_drop_dev(float p, uint64_t seed, const void* salt = nullpt
     return d;
 }
 __host__ __device__ static inline int64_t drop_ld(int64_t cols) { return (cols + 3) & ~(int64_t)3; }
+DEVINL int64_t drop_row(const DropState& d, int64_t row) { return d.row_base + row * d.row_step; }   // mask row of the call's row
+// Host check of a row map before any launch: step >= 1, base >= 0, and the index of the last element of the last mapped row,
+// (base + (rows - 1) step) ld + ld - 1, fits the 63 bits the kernels' int64 index arithmetic has.
+static inline bool drop_rows_ok(DropRows m, int64_t rows, int64_t cols) {
+    if (m.step < 1 || m.base < 0 || rows < 0 || cols < 0) return false;
+    if (rows == 0 || cols == 0) return true;
+    const unsigned __int128 last = (unsigned __int128)m.base + (unsigned __int128)(rows - 1) * (unsigned __int128)m.step;
+    const unsigned __int128 end = (last + 1) * (unsigned __int128)drop_ld(cols);
+    return end <= (unsigned __int128)INT64_MAX;
+}
 DEVINL uint32_t drop_hash(const DropState& d, uint64_t group) {
     return lowbias32((((uint32_t)group) ^ d.key_lo) + (uint32_t)(group >> 32) * 0x9E3779B9U + d.key_hi);
 }

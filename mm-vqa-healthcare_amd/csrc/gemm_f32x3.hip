@@ -131,7 +131,7 @@ DEVINL f32x4 mfma16(s16x8 a, s16x8 b, f32x4 c) {
 }
 
 template <int AM, int BM>
-__global__ __launch_bounds__(256, 2) void gemm_f32x3_kernel(m3ae_gemm_desc d, X3Operand oa, X3Operand ob) {
+__global__ __launch_bounds__(256, 2) void gemm_f32x3_kernel(m3ae_gemm_desc d, X3Operand oa, X3Operand ob, int64_t row_base, int64_t row_step) {
     __shared__ __attribute__((aligned(16))) char smem[2 * X3_STAGE];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -227,7 +227,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32x3_kernel(m3ae_gemm_desc d, X3
             }
     __syncthreads();
 
-    DropState drop = make_drop_dev(d.dropout_p, d.dropout_seed, d.dropout_salt);
+    DropState drop = make_drop_dev(d.dropout_p, d.dropout_seed, d.dropout_salt, row_base, row_step);
     drop_resolve(drop);
     const int64_t coff = b1 * d.c_sb1 + b2 * d.c_sb2;
     float* C = (float*)d.C + coff;
@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256, 2) void gemm_f32x3_kernel(m3ae_gemm_desc d, X3
         if (d.bias) x += bias;
         if (P) P[off] = d.preact_grad ? act_bwd(x, d.act) : x;
         x = act_fwd(x, d.act);
-        if (d.dropout_p > 0.f) x = drop_apply(drop, (uint64_t)(gm * drop_ld(d.N) + gn), x);
+        if (d.dropout_p > 0.f) x = drop_apply(drop, (uint64_t)(drop_row(drop, gm) * drop_ld(d.N) + gn), x);
         if (R) x += R[off];
         if (X) x *= act_bwd(X[off], d.dact);
         if (d.accumulate) x += C[off];
@@ -269,22 +269,22 @@ X3Operand x3_operand(const void* p, int64_t s_r, int64_t s_k, int64_t rows, int6
 }
 
 template <int AM, int BM>
-int launch_x3(const m3ae_gemm_desc& d, const X3Operand& oa, const X3Operand& ob, hipStream_t s) {
+int launch_x3(const m3ae_gemm_desc& d, const X3Operand& oa, const X3Operand& ob, hipStream_t s, DropRows rows) {
     dim3 grid((unsigned)cdiv(d.N, X3_BN), (unsigned)cdiv(d.M, X3_BM), (unsigned)(d.batch1 * d.batch2));
-    hipLaunchKernelGGL((gemm_f32x3_kernel<AM, BM>), grid, dim3(256), 0, s, d, oa, ob);
+    hipLaunchKernelGGL((gemm_f32x3_kernel<AM, BM>), grid, dim3(256), 0, s, d, oa, ob, rows.base, rows.step);
     return hip_launch_status();
 }
 
 }  // namespace
 
-int m3ae_gemm_f32x3(const m3ae_gemm_desc& d, hipStream_t s) {
+int m3ae_gemm_f32x3(const m3ae_gemm_desc& d, hipStream_t s, DropRows rows) {
     if (d.dtype_a != M3AE_F32 || d.dtype_b != M3AE_F32 || d.dtype_c != M3AE_F32) return M3AE_ERR_UNSUPPORTED;
     if (cdiv(d.M, X3_BM) > 65535 || d.batch1 * d.batch2 > 65535 || cdiv(d.N, X3_BN) > 0x7fffffff) return M3AE_ERR_UNSUPPORTED;
     int am, bm;
     const X3Operand oa = x3_operand(d.A, d.a_sm, d.a_sk, d.M, d.a_sb1, d.a_sb2, am);
     const X3Operand ob = x3_operand(d.B, d.b_sn, d.b_sk, d.N, d.b_sb1, d.b_sb2, bm);
-    if (am == X3_KFAST && bm == X3_KFAST) return launch_x3<X3_KFAST, X3_KFAST>(d, oa, ob, s);
-    if (am == X3_KFAST && bm == X3_RFAST) return launch_x3<X3_KFAST, X3_RFAST>(d, oa, ob, s);
-    if (am == X3_RFAST && bm == X3_KFAST) return launch_x3<X3_RFAST, X3_KFAST>(d, oa, ob, s);
-    return launch_x3<X3_RFAST, X3_RFAST>(d, oa, ob, s);
+    if (am == X3_KFAST && bm == X3_KFAST) return launch_x3<X3_KFAST, X3_KFAST>(d, oa, ob, s, rows);
+    if (am == X3_KFAST && bm == X3_RFAST) return launch_x3<X3_KFAST, X3_RFAST>(d, oa, ob, s, rows);
+    if (am == X3_RFAST && bm == X3_KFAST) return launch_x3<X3_RFAST, X3_KFAST>(d, oa, ob, s, rows);
+    return launch_x3<X3_RFAST, X3_RFAST>(d, oa, ob, s, rows);
 }

@@ -11,7 +11,7 @@ namespace {
 constexpr int TM = 64, TN = 64, TK = 16, PAD = 4;
 
 template <typename TA, typename TB, typename TC>
-__global__ __launch_bounds__(256) void gemm_generic_kernel(m3ae_gemm_desc d) {
+__global__ __launch_bounds__(256) void gemm_generic_kernel(m3ae_gemm_desc d, int64_t row_base, int64_t row_step) {
     __shared__ float As[TK][TM + PAD];
     __shared__ float Bs[TK][TN + PAD];
     const int tid = threadIdx.x;
@@ -79,7 +79,7 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(m3ae_gemm_desc d) {
         }
     }
 
-    DropState drop = make_drop_dev(d.dropout_p, d.dropout_seed, d.dropout_salt);
+    DropState drop = make_drop_dev(d.dropout_p, d.dropout_seed, d.dropout_salt, row_base, row_step);
     drop_resolve(drop);
     TC* C = (TC*)d.C + coff;
     TC* P = d.preact ? (TC*)d.preact + coff : nullptr;
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(m3ae_gemm_desc d) {
             if (d.bias) x += d.bias[gn];
             if (P) Elem<TC>::st(P + off, d.preact_grad ? act_bwd(x, d.act) : x);
             x = act_fwd(x, d.act);
-            if (d.dropout_p > 0.f) x = drop_apply(drop, (uint64_t)(gm * drop_ld(d.N) + gn), x);
+            if (d.dropout_p > 0.f) x = drop_apply(drop, (uint64_t)(drop_row(drop, gm) * drop_ld(d.N) + gn), x);
             if (R) x += Elem<TC>::ld(R + off);
             if (X) x *= act_bwd(Elem<TC>::ld(X + off), d.dact);
             if (d.accumulate) x += Elem<TC>::ld(C + off);
@@ -108,19 +108,19 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(m3ae_gemm_desc d) {
 }
 
 template <typename TA, typename TB, typename TC>
-int launch(const m3ae_gemm_desc& d, hipStream_t s) {
+int launch(const m3ae_gemm_desc& d, hipStream_t s, DropRows rows) {
     dim3 grid((unsigned)cdiv(d.N, TN), (unsigned)cdiv(d.M, TM), (unsigned)(d.batch1 * d.batch2));
     if (grid.y > 65535u || grid.z > 65535u) return M3AE_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL((gemm_generic_kernel<TA, TB, TC>), grid, dim3(256), 0, s, d);
+    hipLaunchKernelGGL((gemm_generic_kernel<TA, TB, TC>), grid, dim3(256), 0, s, d, rows.base, rows.step);
     return hip_launch_status();
 }
 
 }  // namespace
 
-int m3ae_gemm_generic(const m3ae_gemm_desc& d, hipStream_t s) {
+int m3ae_gemm_generic(const m3ae_gemm_desc& d, hipStream_t s, DropRows rows) {
     if (d.dtype_a != d.dtype_b) return M3AE_ERR_UNSUPPORTED;
-    if (d.dtype_a == M3AE_F32 && d.dtype_c == M3AE_F32) return launch<float, float, float>(d, s);
-    if (d.dtype_a == M3AE_BF16 && d.dtype_c == M3AE_BF16) return launch<bf16_t, bf16_t, bf16_t>(d, s);
-    if (d.dtype_a == M3AE_BF16 && d.dtype_c == M3AE_F32) return launch<bf16_t, bf16_t, float>(d, s);
+    if (d.dtype_a == M3AE_F32 && d.dtype_c == M3AE_F32) return launch<float, float, float>(d, s, rows);
+    if (d.dtype_a == M3AE_BF16 && d.dtype_c == M3AE_BF16) return launch<bf16_t, bf16_t, bf16_t>(d, s, rows);
+    if (d.dtype_a == M3AE_BF16 && d.dtype_c == M3AE_F32) return launch<bf16_t, bf16_t, float>(d, s, rows);
     return M3AE_ERR_UNSUPPORTED;
 }

@@ -258,8 +258,8 @@ __global__ __launch_bounds__((BM_ / WM) * (BN_ / 64) * 64, 2) void gemm_tn_bf16_
 static thread_local const char* g_last_path = "none";
 const char* m3ae_last_gemm_path(void) { return g_last_path; }
 
-int m3ae_gemm_generic(const m3ae_gemm_desc& d, hipStream_t s);
-int m3ae_gemm_f32x3(const m3ae_gemm_desc& d, hipStream_t s);
+int m3ae_gemm_generic(const m3ae_gemm_desc& d, hipStream_t s, DropRows rows = DropRows{0, 1});
+int m3ae_gemm_f32x3(const m3ae_gemm_desc& d, hipStream_t s, DropRows rows = DropRows{0, 1});
 
 static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
@@ -684,7 +684,7 @@ static int launch_nt_v(const MfmaArgs& a, hipStream_t s) {
     return launch_nt_t<128, 128, 64, 2, 64, EPI>(a, s);
 }
 
-static int launch_nt(const m3ae_gemm_desc& d, hipStream_t s) {
+static int launch_nt(const m3ae_gemm_desc& d, hipStream_t s, DropRows rows) {
     MfmaArgs a{};
     a.A = (const bf16_t*)d.A; a.lda = d.a_sm;
     a.B = (const bf16_t*)d.B; a.ldb = d.b_sn;
@@ -702,7 +702,7 @@ static int launch_nt(const m3ae_gemm_desc& d, hipStream_t s) {
         a.col_group = g_nt_col_group > 0 ? g_nt_col_group : (tiles_n <= 9 ? tiles_n : 6);
     }
     a.has_drop = d.dropout_p > 0.f;
-    a.drop = make_drop(d.dropout_p, d.dropout_seed, d.dropout_salt);
+    a.drop = make_drop(d.dropout_p, d.dropout_seed, d.dropout_salt, rows);
     a.no_persist = (d.launch_flags & M3AE_GEMM_NO_PERSISTENT) ? 1 : 0;
     a.nt_variant = ((d.launch_flags >> 8) & 0xf) - 1;
     a.st_policy = (d.launch_flags >> 20) & 0x3;
@@ -1130,11 +1130,17 @@ static GemmRoute gemm_route(const m3ae_gemm_desc& d) {
     return ROUTE_GENERIC;
 }
 
-extern "C" int m3ae_gemm(const m3ae_gemm_desc* dp, void* stream) {
+extern "C" int m3ae_gemm(const m3ae_gemm_desc* dp, void* stream) { return m3ae_gemm_rows(dp, 0, 1, stream); }
+
+extern "C" int m3ae_gemm_rows(const m3ae_gemm_desc* dp, int64_t row_base, int64_t row_step, void* stream) {
     if (!dp || !dp->A || !dp->B || !dp->C) return M3AE_ERR_ARG;
     const m3ae_gemm_desc& d = *dp;
     const GemmRoute route = gemm_route(d);
     if (route == ROUTE_BAD_DIMS) return M3AE_ERR_ARG;
+    const DropRows rows{row_base, row_step};
+    if (!drop_rows_ok(rows, d.M, d.N)) return M3AE_ERR_ARG;
+    // the split-K wgrad kernels have no dropout site: a mapped call that asks for one is refused, not run without it
+    if (route == ROUTE_TN && d.dropout_p > 0.f && (row_base != 0 || row_step != 1)) return M3AE_ERR_UNSUPPORTED;
     // deterministic mode needs a workspace for its partial planes: m3ae_gemm_det takes one, this call cannot, and it never
     // runs the atomic kernels under that flag
     if (d.launch_flags & M3AE_GEMM_DETERMINISTIC) return M3AE_ERR_UNSUPPORTED;
@@ -1143,16 +1149,16 @@ extern "C" int m3ae_gemm(const m3ae_gemm_desc* dp, void* stream) {
     case ROUTE_F32X3:   // fp32 operands only
         if (d.dtype_a != M3AE_F32 || d.dtype_b != M3AE_F32 || d.dtype_c != M3AE_F32) return M3AE_ERR_UNSUPPORTED;
         g_last_path = "f32x3";
-        return m3ae_gemm_f32x3(d, s);
+        return m3ae_gemm_f32x3(d, s, rows);
     case ROUTE_NT:
         g_last_path = "mfma_nt";
-        return launch_nt(d, s);
+        return launch_nt(d, s, rows);
     case ROUTE_TN:
         g_last_path = "mfma_tn";
         return launch_tn(d, s);
     default:
         g_last_path = "generic";
-        return m3ae_gemm_generic(d, s);
+        return m3ae_gemm_generic(d, s, rows);
     }
 }
 

@@ -95,7 +95,7 @@ DEVINL void epilogue4(const MfmaArgs& a, int64_t m, int64_t n, f32x4 v) {
         }
     }
     if ((EPI == EPI_PLAIN || EPI == EPI_ANY || EPI == EPI_RELU || EPI == EPI_DMUL) && a.has_drop) {  // dropout follows a plain dense layer on this path
-        drop_apply4(a.drop, (uint64_t)(m * a.N + n), x);  // N % 4 == 0 on this path: ld = N
+        drop_apply4(a.drop, (uint64_t)(drop_row(a.drop, m) * a.N + n), x);  // N % 4 == 0 on this path: ld = N
     }
     if (a.residual) {
         Vec4<TC>::ld((const TC*)a.residual + off, y);
@@ -191,8 +191,9 @@ DEVINL void epilogue8(const MfmaArgs& a, int64_t m, int64_t n, float* x, const f
         }
     }
     if ((EPI == EPI_PLAIN || EPI == EPI_ANY || EPI == EPI_RELU || EPI == EPI_DMUL) && a.has_drop) {  // dropout follows a plain dense layer on this path
-        drop_apply4(a.drop, (uint64_t)(m * a.N + n), x);
-        drop_apply4(a.drop, (uint64_t)(m * a.N + n + 4), x + 4);
+        const uint64_t di = (uint64_t)(drop_row(a.drop, m) * a.N + n);
+        drop_apply4(a.drop, di, x);
+        drop_apply4(a.drop, di + 4, x + 4);
     }
     if (a.residual) {
         if (has_pre && !PRE_IS_AUX) Vec8<TC>::unpack(pre, y);

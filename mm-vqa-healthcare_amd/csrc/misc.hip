@@ -568,7 +568,7 @@ __global__ void dropout_kernel(const T* x, T* out, uint8_t* keep, int64_t n, int
     drop_resolve(ds);
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = i / cols;
-        const bool k = drop_keep(ds, (uint64_t)(r * ld + (i - r * cols)));
+        const bool k = drop_keep(ds, (uint64_t)(drop_row(ds, r) * ld + (i - r * cols)));
         if (out) Elem<T>::st(out + i, k ? Elem<T>::ld(x + i) * ds.inv_keep : 0.f);
         if (keep) keep[i] = k ? 1 : 0;
     }
@@ -843,10 +843,15 @@ extern "C" int m3ae_act_bwd(const void* dy, const void* x_pre, void* dx, int64_t
 }
 extern "C" int m3ae_dropout(const void* x, void* out, uint8_t* keep_mask, int64_t rows, int64_t cols, float p,
                             uint64_t seed, const void* salt, int dtype, void* stream) {
+    return m3ae_dropout_rows(x, out, keep_mask, rows, cols, p, seed, salt, dtype, 0, 1, stream);
+}
+extern "C" int m3ae_dropout_rows(const void* x, void* out, uint8_t* keep_mask, int64_t rows, int64_t cols, float p,
+                                 uint64_t seed, const void* salt, int dtype, int64_t row_base, int64_t row_step, void* stream) {
     if (rows <= 0 || cols <= 0 || p < 0.f || p >= 1.f || (!out && !keep_mask) || (out && !x)) return M3AE_ERR_ARG;
+    if (!drop_rows_ok(DropRows{row_base, row_step}, rows, cols)) return M3AE_ERR_ARG;
     const int64_t n = rows * cols;
     hipStream_t s = (hipStream_t)stream;
-    const DropState ds = make_drop(p, seed, salt);
+    const DropState ds = make_drop(p, seed, salt, DropRows{row_base, row_step});
     DT_SWITCH(dtype, hipLaunchKernelGGL(dropout_kernel<T>, dim3(ew_grid(n)), dim3(EW_BLOCK), 0, s, (const T*)x, (T*)out,
                                         keep_mask, n, cols, drop_ld(cols), ds));
     return hip_launch_status();

@@ -287,7 +287,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* dy, const T* x, co
                     float od[4];
 #pragma unroll
                     for (int t = 0; t < 4; ++t) od[t] = o[t];
-                    drop_apply4(drop, (uint64_t)(row * D + ch * 4), od);  // D % 4 == 0: ld = D
+                    drop_apply4(drop, (uint64_t)(drop_row(drop, row) * D + ch * 4), od);  // D % 4 == 0: ld = D
                     st4<T>(dx_drop + row * D + ch * 4, od);
                 }
                 if (dx_add) {
@@ -491,12 +491,13 @@ extern "C" int m3ae_layernorm_bwd_det(const void* dy, const void* x, const float
 static int layernorm_bwd_drop_impl(const void* dy, const void* x, const float* gamma, const float* beta, const float* mean,
                                    const float* rstd, void* dx, void* dx_drop, float dropout_p, uint64_t dropout_seed,
                                    const void* dropout_salt, float* dgamma, float* dbeta, float* workspace, int64_t M, int64_t D,
-                                   int dtype, void* stream, int det) {
+                                   int dtype, void* stream, int det, DropRows rows = DropRows{0, 1}) {
     if (!dy || !x || !gamma || !rstd || !dx || !dx_drop || !workspace || M <= 0) return M3AE_ERR_ARG;
+    if (!drop_rows_ok(rows, M, D)) return M3AE_ERR_ARG;
     if (D % 4 != 0 || D > 2048) return M3AE_ERR_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
     int nblk = (int)m3ae_layernorm_bwd_blocks(M);
-    const DropState drop = make_drop(dropout_p, dropout_seed, dropout_salt);
+    const DropState drop = make_drop(dropout_p, dropout_seed, dropout_salt, rows);
     auto run = [&]() -> int {
         if (dtype == M3AE_F32)
             DISPATCH_CPL(launch_bwd, float, dy, x, gamma, beta, mean, rstd, dx, nullptr, workspace, &nblk, M, (int)D, 0, 0, s, dx_drop, drop);
@@ -515,6 +516,14 @@ extern "C" int m3ae_layernorm_bwd_drop(const void* dy, const void* x, const floa
                                        float* workspace, int64_t M, int64_t D, int dtype, void* stream) {
     return layernorm_bwd_drop_impl(dy, x, gamma, beta, mean, rstd, dx, dx_drop, dropout_p, dropout_seed, dropout_salt, dgamma, dbeta,
                                    workspace, M, D, dtype, stream, 0);
+}
+extern "C" int m3ae_layernorm_bwd_drop_rows(const void* dy, const void* x, const float* gamma, const float* beta,
+                                            const float* mean, const float* rstd, void* dx, void* dx_drop, float dropout_p,
+                                            uint64_t dropout_seed, const void* dropout_salt, float* dgamma, float* dbeta,
+                                            float* workspace, int64_t M, int64_t D, int dtype, int64_t row_base, int64_t row_step,
+                                            void* stream) {
+    return layernorm_bwd_drop_impl(dy, x, gamma, beta, mean, rstd, dx, dx_drop, dropout_p, dropout_seed, dropout_salt, dgamma, dbeta,
+                                   workspace, M, D, dtype, stream, 0, DropRows{row_base, row_step});
 }
 extern "C" int m3ae_layernorm_bwd_drop_det(const void* dy, const void* x, const float* gamma, const float* beta,
                                            const float* mean, const float* rstd, void* dx, void* dx_drop, float dropout_p,

@@ -149,16 +149,20 @@ class BertCrossLayer(nn.Module):
         self._bp = None
 
     def forward(self, hidden_states, encoder_hidden_states, attention_mask=None, encoder_attention_mask=None,
-                output_attentions=False):
+                output_attentions=False, cls_only=False):
         """Returns the layer output; with output_attentions the reference's tuple (output, self-attention probabilities
         [B, H, L, L], cross-attention probabilities [B, H, L, Lo]) (bert_model.py:457-498): fp32, contiguous, detached (the
-        reference's gradient hook on them is disabled, :328); in training mode the dropped P the layer used (:334)."""
+        reference's gradient hook on them is disabled, :328); in training mode the dropped P the layer used (:334).
+        cls_only: the caller reads token 0 of the output alone; the layer computes that row ([B, 1, D], equal to row 0 of the
+        full output: ops.BertCrossLayerFn's live-row form).  Attention maps are full-layer outputs: output_attentions wins."""
         if self._bp is None:
             self._bp = NS(attn=self.attention.block_params(), cross=self.crossattention.block_params(),
                           ffn=_ffn_params(self))
             self._anchors = tuple(self.parameters())
         self._bp.want_probs = self._bp.cross.want_probs = bool(output_attentions)
         self._bp.pdrop = self.drop_rate if self.training else 0.0
+        # (deterministic mode keeps the full layer: the live form's LayerNorm backward has no ordered entry point)
+        self._bp.cls_only = bool(cls_only) and not output_attentions and not ops.deterministic()
         # forward-only calls always take the fused cross-attention sub-block; training takes it with its fused backward
         self._bp.fused_cross = (not torch.is_grad_enabled()) or (ops.XATTN_TRAIN != "off" and
                                                                  hidden_states.shape[0] >= ops.XATTN_TRAIN_MIN_BATCH)

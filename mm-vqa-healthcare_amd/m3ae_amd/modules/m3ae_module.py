@@ -197,7 +197,7 @@ class M3AETransformerSS(_Base):
                 warn_off(False)
         return self._side_stream
 
-    def _fusion_two_streams(self, text_tower, v, mt, mv, mask_image, ret, main, side, ev_inputs, attns=None):
+    def _fusion_two_streams(self, text_tower, v, mt, mv, mask_image, ret, main, side, ev_inputs, attns=None, live=False):
         """The text tower and the text half of every fusion layer on a second HIP stream.  The towers are independent until the
         fusion layers and a fusion layer's two halves read only the PREVIOUS layer's outputs, so the short text-side kernels
         (B*32 rows: half-empty grids) fill the tail rounds of the image-side launches instead of running alone.  Events order
@@ -222,12 +222,13 @@ class M3AETransformerSS(_Base):
             ya, yb = ops.fork2(y)
             side.wait_event(ev_y)
             y.record_stream(side)
+            last = live and layer_idx == len(self.multi_modal_language_layers) - 1   # (live: token 0 of the last pair only)
             with torch.cuda.stream(side):
-                x1 = text_layer(xa, yb, mt, mv, output_attentions=attns is not None)
+                x1 = text_layer(xa, yb, mt, mv, output_attentions=attns is not None, cls_only=last)
                 ev_x1 = side.record_event()
             main.wait_event(ev_x)
             x.record_stream(main)
-            y1 = image_layer(ya, xb, mv, mt, output_attentions=attns is not None)
+            y1 = image_layer(ya, xb, mv, mt, output_attentions=attns is not None, cls_only=last)
             if attns is not None:   # (the layers' reference-shaped tuples: output, self-attention map, cross-attention map)
                 (x1, *tmaps), (y1, *imaps) = x1, y1
                 attns["text2image_attns"].append(tuple(tmaps))
@@ -267,8 +268,10 @@ class M3AETransformerSS(_Base):
 
     @ops.model_mode
     def infer(self, batch, mask_text=False, mask_image=False, image_token_type_idx=1, img=None,
-              output_attentions=False, unimodal=False):
-        """m3ae_module.py:203-312."""
+              output_attentions=False, unimodal=False, cls_only=False):
+        """m3ae_module.py:203-312.  cls_only: the caller reads `multi_modal_cls_feats` alone (the VQA and ITM heads): the last fusion
+        pair then computes only its token-0 rows (ops.CLS_ONLY) and the two full-sequence feature entries are left out of the
+        result.  Attention maps (output_attentions) and deterministic mode keep the full computation."""
         if self.store is None:
             raise RuntimeError("call finalize(device) before the first forward")
         ret = dict()
@@ -319,6 +322,8 @@ class M3AETransformerSS(_Base):
 
         # m3ae_module.py:266,280-283: per fusion layer the (self, cross) attention maps of each direction
         attns = {"text2image_attns": [], "image2text_attns": []} if output_attentions else None
+        live = bool(cls_only) and ops.CLS_ONLY and not output_attentions and not ops.deterministic()
+        n_fusion = len(self.multi_modal_language_layers)
         if side is None:
             t = text_tower()
             # == Multi-Modal Fusion (m3ae_module.py:266-285): both streams read the PRE-update x, y ==
@@ -328,15 +333,16 @@ class M3AETransformerSS(_Base):
                 if mask_image and self.hparams.config["mim_layer"] == layer_idx:
                     ret[f"multi_modal_text_feats_{layer_idx}"], ret[f"multi_modal_image_feats_{layer_idx}"] = x, y
                 (xa, xb), (ya, yb) = ops.fork2(x), ops.fork2(y)
-                x1 = text_layer(xa, yb, mt, mv, output_attentions=output_attentions)
-                y1 = image_layer(ya, xb, mv, mt, output_attentions=output_attentions)
+                last = live and layer_idx == n_fusion - 1
+                x1 = text_layer(xa, yb, mt, mv, output_attentions=output_attentions, cls_only=last)
+                y1 = image_layer(ya, xb, mv, mt, output_attentions=output_attentions, cls_only=last)
                 if output_attentions:
                     (x1, *tmaps), (y1, *imaps) = x1, y1
                     attns["text2image_attns"].append(tuple(tmaps))
                     attns["image2text_attns"].append(tuple(imaps))
                 x, y = x1, y1
         else:
-            x, y = self._fusion_two_streams(text_tower, v, mt, mv, mask_image, ret, main, side, ev_inputs, attns)
+            x, y = self._fusion_two_streams(text_tower, v, mt, mv, mask_image, ret, main, side, ev_inputs, attns, live)
         # == Output (m3ae_module.py:287-297) ==
         cls_t = self.multi_modal_language_pooler(x)
         cls_v = self.multi_modal_vision_pooler(y)
@@ -348,10 +354,10 @@ class M3AETransformerSS(_Base):
             "text_masks": text_masks,
             "extended_image_masks": mv,
             "extended_text_masks": mt,
-            "multi_modal_text_feats": x,
-            "multi_modal_image_feats": y,
             "multi_modal_cls_feats": cls,
         })
+        if not live:   # (live: x and y are the token-0 rows alone; a consumer that needs the sequences fails on the missing key)
+            ret["multi_modal_text_feats"], ret["multi_modal_image_feats"] = x, y
         if mask_image:  # only MIM needs it (the reference recomputes it on every call, m3ae_module.py:301)
             ret["patched_images"] = self.patchify(img)
         ret["attentions"] = attns

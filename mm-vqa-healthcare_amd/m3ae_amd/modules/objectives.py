@@ -24,7 +24,7 @@ def build_vqa_targets(batch, label_size, device):
 
 def compute_vqa_m3ae(pl_module, batch, test=False):
     """objectives.py:176-201."""
-    infer = pl_module.infer(batch, mask_text=False, mask_image=False)
+    infer = pl_module.infer(batch, mask_text=False, mask_image=False, cls_only=True)   # the head reads the class features alone
     vqa_logits = pl_module.vqa_head_forward(infer["multi_modal_cls_feats"])
     vqa_targets = build_vqa_targets(batch, pl_module.hparams.config["vqa_label_size"], vqa_logits.device)
     vqa_loss = ops.bce_with_logits_loss(vqa_logits, vqa_targets)
@@ -78,7 +78,7 @@ def compute_itm(pl_module, batch, itm_labels=None):
     itm_images = [torch.where(sel, ti, fi) for ti, fi in zip(batch["image"], batch["false_image_0"])]
     batch = dict(batch)
     batch["image"] = itm_images
-    infer = pl_module.infer(batch, mask_text=False, mask_image=False)
+    infer = pl_module.infer(batch, mask_text=False, mask_image=False, cls_only=True)
     itm_logits = pl_module.itm_head(infer["multi_modal_cls_feats"])
     itm_loss = ops.cross_entropy(itm_logits, itm_labels.long())
     return {"itm_loss": itm_loss, "itm_logits": itm_logits, "itm_labels": itm_labels}

@@ -252,7 +252,8 @@ def compute_weight(w):
 # ----------------------------------------------------------------------------------------------------------
 def gemm(a, a_sm, a_sk, b, b_sk, b_sn, c, c_sm, M, N, K, *, alpha=1.0, accumulate=False, bias=None, act=ACT_NONE,
          preact=None, residual=None, dact_aux=None, dact=ACT_NONE, force_generic=False, batch=(1, 1),
-         a_sb=(0, 0), b_sb=(0, 0), c_sb=(0, 0), a_rowsum=None, dropout=None, preact_grad=False):
+         a_sb=(0, 0), b_sb=(0, 0), c_sb=(0, 0), a_rowsum=None, dropout=None, preact_grad=False, rows=None):
+    """rows = (row_base, row_step): the dropout mask row of output row m is row_base + m * row_step (m3ae_gemm_rows)."""
     _need_cuda(c)
     d = GemmDesc()
     d.M, d.N, d.K = M, N, K
@@ -290,6 +291,8 @@ def gemm(a, a_sm, a_sk, b, b_sk, b_sn, c, c_sm, M, N, K, *, alpha=1.0, accumulat
         ws = _det_ws(nws, c.device)
         check(_lib.lib().m3ae_gemm_det(C.byref(d), _p(ws), nws, _stream()), "m3ae_gemm_det")
         del ws
+    elif rows is not None:
+        check(_lib.lib().m3ae_gemm_rows(C.byref(d), rows[0], rows[1], _stream()), "m3ae_gemm_rows")
     else:
         check(_lib.lib().m3ae_gemm(C.byref(d), _stream()), "m3ae_gemm")
     if e0 is not None:
@@ -338,7 +341,7 @@ def use_launch_stream():
 
 
 def mm_nt(x2, ldx, M, w, bias=None, act=ACT_NONE, residual=None, want_preact=False, out_dtype=None, dact_aux=None,
-          dact=ACT_NONE, force_generic=False, alpha=1.0, dropout=None, preact_grad=False):
+          dact=ACT_NONE, force_generic=False, alpha=1.0, dropout=None, preact_grad=False, rows=None):
     """y[M,N] = epi(alpha * x2[M,K] . w[N,K]^T).  want_preact + preact_grad: the second output is act'(pre-activation)
     (consumed by a backward GEMM with dact=ACT_MULAUX) instead of the pre-activation itself."""
     N, K = w.shape
@@ -346,11 +349,11 @@ def mm_nt(x2, ldx, M, w, bias=None, act=ACT_NONE, residual=None, want_preact=Fal
     pre = torch.empty_like(y) if want_preact else None
     gemm(x2, ldx, 1, w, 1, w.stride(0), y, N, M, N, K, bias=bias, act=act, preact=pre, residual=residual,
          dact_aux=dact_aux, dact=dact, force_generic=force_generic, alpha=alpha, dropout=dropout,
-         preact_grad=preact_grad and want_preact)
+         preact_grad=preact_grad and want_preact, rows=rows)
     return y, pre
 
 
-def mm_dgrad(dy, w_param, dact_aux=None, dact=ACT_NONE, residual=None, alpha=1.0, dropout=None, out=None, ld_out=None):
+def mm_dgrad(dy, w_param, dact_aux=None, dact=ACT_NONE, residual=None, alpha=1.0, dropout=None, out=None, ld_out=None, rows=None):
     """dx[M,K] = dy[M,N] . W[N,K]  (bf16: NT against the transposed shadow; fp32: strided generic).  out / ld_out: write
     the rows into this preallocated tensor at this row stride instead of a fresh [M, K]."""
     M, N = dy.shape
@@ -363,7 +366,7 @@ def mm_dgrad(dy, w_param, dact_aux=None, dact=ACT_NONE, residual=None, alpha=1.0
     if out is None:
         out, ld_out = torch.empty((M, K), dtype=dy.dtype, device=dy.device), K
     gemm(dy, dy.stride(0), 1, b, b_sk, b_sn, out, ld_out, M, K, N, dact_aux=dact_aux, dact=dact, residual=residual,
-         alpha=alpha, dropout=dropout)
+         alpha=alpha, dropout=dropout, rows=rows)
     return out
 
 
@@ -631,7 +634,7 @@ def ln_fwd_raw(x2, ln, act=ACT_NONE, rms=False):
     return y, mean, rstd
 
 
-def ln_bwd_raw(dy, x2, ln, mean, rstd, dx_add=None, act=ACT_NONE, rms=False, drop=None):
+def ln_bwd_raw(dy, x2, ln, mean, rstd, dx_add=None, act=ACT_NONE, rms=False, drop=None, rows=None):
     """dx = LN'(dy) (+ dx_add); ln.weight.grad / ln.bias.grad accumulate in place.  With drop = (p, seed) returns
     (dx, dx_drop): dx_drop is dx under the dropout mask of the dense layer that fed this LayerNorm."""
     M, D = x2.shape
@@ -645,6 +648,14 @@ def ln_bwd_raw(dy, x2, ln, mean, rstd, dx_add=None, act=ACT_NONE, rms=False, dro
     if drop is not None and drop[0] > 0:
         assert dx_add is None and act == ACT_NONE and not rms
         dxd = torch.empty_like(x2)
+        if rows is not None:   # (the live-row form is not taken in deterministic mode)
+            check(L.m3ae_layernorm_bwd_drop_rows(_p(dy), _p(x2), _p(ln.weight), _p(ln.bias), _p(mean), _p(rstd), _p(dx), _p(dxd),
+                                                 drop[0], drop[1], _salt(), _p(gg), _p(gb), _p(ws), M, D, _dt(x2), rows[0], rows[1],
+                                                 _stream()), "m3ae_layernorm_bwd_drop_rows")
+            if train:
+                _done(ln.weight)
+                _done(ln.bias)
+            return dx, dxd
         ln_bwd_drop = L.m3ae_layernorm_bwd_drop_det if _DETERMINISTIC else L.m3ae_layernorm_bwd_drop
         check(ln_bwd_drop(_p(dy), _p(x2), _p(ln.weight), _p(ln.bias), _p(mean), _p(rstd), _p(dx), _p(dxd),
                           drop[0], drop[1], _salt(), _p(gg), _p(gb), _p(ws), M, D, _dt(x2), _stream()),
@@ -693,8 +704,9 @@ def _attn_ws(d, backward, device):
     return ws
 
 
-def attn_forward(q, k, v, heads, key_mask=None, pos_bias=None, scale=None, causal=False, dropout=None):
-    """q [B,Lq,D] / k,v [B,Lk,D] (last dim contiguous, any batch/token strides) -> o [B,Lq,D], lse."""
+def attn_forward(q, k, v, heads, key_mask=None, pos_bias=None, scale=None, causal=False, dropout=None, rows=None):
+    """q [B,Lq,D] / k,v [B,Lk,D] (last dim contiguous, any batch/token strides) -> o [B,Lq,D], lse.
+    rows = (row_base, row_step): row map of the probability-dropout mask (m3ae_attn_fwd_rows)."""
     _need_cuda(q)
     B, Lq, D = q.shape
     Lk = k.shape[1]
@@ -702,7 +714,7 @@ def attn_forward(q, k, v, heads, key_mask=None, pos_bias=None, scale=None, causa
     if q.dtype == torch.bfloat16 and Dh != 64:
         # the MFMA attention kernels are specialised for 64-wide heads; other widths (the decoder head's 96) take the fp32
         # materialised-softmax kernels on fp32 copies of the projections: short sequences, a few % of that head's work
-        o32, lse = attn_forward(q.float(), k.float(), v.float(), heads, key_mask, pos_bias, scale, causal, dropout)
+        o32, lse = attn_forward(q.float(), k.float(), v.float(), heads, key_mask, pos_bias, scale, causal, dropout, rows)
         return o32.to(torch.bfloat16), lse
     scale = (1.0 / math.sqrt(Dh)) if scale is None else scale
     o = torch.empty((B, Lq, D), dtype=q.dtype, device=q.device)
@@ -713,14 +725,17 @@ def attn_forward(q, k, v, heads, key_mask=None, pos_bias=None, scale=None, causa
     _set_dropout(d, dropout)
     ws = _attn_ws(d, False, q.device)
     e0 = _prof_begin()
-    check(_lib.lib().m3ae_attn_fwd(C.byref(d), _stream()), "m3ae_attn_fwd")
+    if rows is not None:
+        check(_lib.lib().m3ae_attn_fwd_rows(C.byref(d), rows[0], rows[1], _stream()), "m3ae_attn_fwd_rows")
+    else:
+        check(_lib.lib().m3ae_attn_fwd(C.byref(d), _stream()), "m3ae_attn_fwd")
     _prof_end(e0, "attn_fwd", (B, heads, Lq, Lk, Dh))
     del ws
     return o, lse
 
 
 def attn_backward(q, k, v, o, lse, do, dq, dk, dv, heads, key_mask=None, pos_bias=None, scale=None, causal=False,
-                  d_pos_bias=None, dropout=None):
+                  d_pos_bias=None, dropout=None, rows=None):
     if d_pos_bias is not None:
         _no_ordered_form("the relative-position-bias gradient of m3ae_attn_bwd (d_pos_bias, T5 attention)")
     B, Lq, D = q.shape
@@ -730,7 +745,7 @@ def attn_backward(q, k, v, o, lse, do, dq, dk, dv, heads, key_mask=None, pos_bia
         f = [t.float() for t in (q, k, v, o, do)]
         g = [torch.empty_like(t) for t in f[:3]]
         attn_backward(f[0], f[1], f[2], f[3].contiguous(), lse, f[4].contiguous(), g[0], g[1], g[2], heads, key_mask,
-                      pos_bias, scale, causal, d_pos_bias, dropout)
+                      pos_bias, scale, causal, d_pos_bias, dropout, rows)
         for dst, src in zip((dq, dk, dv), g):
             dst.copy_(src)
         return
@@ -744,7 +759,10 @@ def attn_backward(q, k, v, o, lse, do, dq, dk, dv, heads, key_mask=None, pos_bia
     _set_dropout(d, dropout)
     ws = _attn_ws(d, True, q.device)
     e0 = _prof_begin()
-    check(_lib.lib().m3ae_attn_bwd(C.byref(d), _stream()), "m3ae_attn_bwd")
+    if rows is not None:
+        check(_lib.lib().m3ae_attn_bwd_rows(C.byref(d), rows[0], rows[1], _stream()), "m3ae_attn_bwd_rows")
+    else:
+        check(_lib.lib().m3ae_attn_bwd(C.byref(d), _stream()), "m3ae_attn_bwd")
     _prof_end(e0, "attn_bwd", (B, heads, Lq, Lk, Dh))
     del ws, delta
 
@@ -849,6 +867,9 @@ XATTN_TRAIN = os.environ.get("M3AE_XATTN_TRAIN", "auto")
 XATTN_TRAIN_MIN_BATCH = int(os.environ.get("M3AE_XATTN_TRAIN_MIN_BATCH", 96))
 # A/B measurements (tools/, tests): the round-2 dir-1 forward chain (P through HBM) instead of the one-launch kernel
 XATTN_LEGACY_CHAIN = False
+# CLS-head steps (VQA, ITM) read token 0 of the last fusion pair's outputs only: with the switch on, infer(cls_only=True) runs that
+# pair on its live rows (BertCrossLayerFn's live-row form below); M3AE_CLS_ONLY=0 restores the full computation (tests, A/B runs)
+CLS_ONLY = os.environ.get("M3AE_CLS_ONLY", "1") != "0"
 
 
 def _xattn_desc(h2, B, L, other2, Lo, mask, P, pdrop, seeds):
@@ -1050,20 +1071,20 @@ def _attn_core_bwd(dctx, x2, src2, proj, o, lse, B, P, mask=None, pos_bias=None,
     return dx, (mm_dgrad(dkv, P.w_kv) if need_dsrc else None)
 
 
-def _ffn_core_fwd(x2, P, act, residual, mid_drop=None, out_drop=None):
+def _ffn_core_fwd(x2, P, act, residual, mid_drop=None, out_drop=None, rows=None):
     """y = dropout_out(dropout_mid(act(x2 W1^T + b1)) W2^T + b2) + residual.  Returns (y, u, g): g the (dropped) activation,
     u what the backward GEMM needs of the pre-activation (its act' when SAVE_DACT, else itself)."""
     M, D = x2.shape
     g, u = mm_nt(x2, D, M, compute_weight(P.w1), bias=_bdata(P.b1), act=act, want_preact=True, preact_grad=SAVE_DACT,
-                 dropout=mid_drop)
-    y, _ = mm_nt(g, g.shape[1], M, compute_weight(P.w2), bias=_bdata(P.b2), residual=residual, dropout=out_drop)
+                 dropout=mid_drop, rows=rows)
+    y, _ = mm_nt(g, g.shape[1], M, compute_weight(P.w2), bias=_bdata(P.b2), residual=residual, dropout=out_drop, rows=rows)
     return y, u, g
 
 
-def _ffn_core_bwd(dy, x2, u, g, P, act, mid_drop=None, residual=None):
+def _ffn_core_bwd(dy, x2, u, g, P, act, mid_drop=None, residual=None, rows=None):
     """Backward of _ffn_core_fwd from dy = d(W2 output, before the residual join): returns dx (+ residual, in the epilogue)."""
     mm_wgrad(dy, g, g.shape[1], P.w2, P.b2)
-    du = mm_dgrad(dy, P.w2, dact_aux=u, dact=ACT_MULAUX if SAVE_DACT else act, dropout=mid_drop)   # dU = (dY W2) * act'(U)
+    du = mm_dgrad(dy, P.w2, dact_aux=u, dact=ACT_MULAUX if SAVE_DACT else act, dropout=mid_drop, rows=rows)   # dU = (dY W2) * act'(U)
     mm_wgrad(du, x2, x2.shape[1], P.w1, P.b1)
     return mm_dgrad(du, P.w1, residual=residual)
 
@@ -1094,11 +1115,11 @@ def _attn_sub_probs(saved, B, L, Lo, P):
     return attn_probs(q3, k3, lse, P.heads, mask, dropout=da)
 
 
-def _post_ln_bwd(dy, s, ln, mean, rstd, dh):
+def _post_ln_bwd(dy, s, ln, mean, rstd, dh, rows=None):
     """Backward of the post-LayerNorm of a BERT sub-block whose dense output was dropped with dh = (p, seed) or None:
     (ds, dsd) = the gradient of the LayerNorm input (residual branch) and of the dense output before its dropout."""
     if dh is not None:
-        return ln_bwd_raw(dy, s, ln, mean, rstd, drop=dh)
+        return ln_bwd_raw(dy, s, ln, mean, rstd, drop=dh, rows=rows)
     ds = ln_bwd_raw(dy, s, ln, mean, rstd)
     return ds, ds
 
@@ -1115,18 +1136,118 @@ def _attn_sub_bwd(dy, saved, B, L, Lo, P, need_dother=True):
     return _attn_core_bwd(dctx, h2, other2, proj, o, lse, B, P, mask=mask, dropout=da, residual=ds, need_dsrc=need_dother)
 
 
-def _ffn_sub_fwd(h2, P, pdrop=0.0):
-    """BertIntermediate + BertOutput (bert_model.py:416-442, 500-503); pdrop: hidden dropout on the output dense (:440)."""
+def _ffn_sub_fwd(h2, P, pdrop=0.0, rows=None):
+    """BertIntermediate + BertOutput (bert_model.py:416-442, 500-503); pdrop: hidden dropout on the output dense (:440).
+    rows: h2 holds the rows row_base + m * row_step of the full activation (live-row form): their dropout masks are drawn."""
     dh = dropout_pair(pdrop)
-    s, u, g = _ffn_core_fwd(h2, P, ACT_GELU, h2, out_drop=dh)
+    s, u, g = _ffn_core_fwd(h2, P, ACT_GELU, h2, out_drop=dh, rows=rows)
     y, mean, rstd = ln_fwd_raw(s, P.ln)
-    return y, (h2, u, g, s, mean, rstd, dh)
+    return y, (h2, u, g, s, mean, rstd, dh, rows)
 
 
 def _ffn_sub_bwd(dy, saved, P):
-    h2, u, g, s, mean, rstd, dh = saved
-    ds, dsd = _post_ln_bwd(dy, s, P.ln, mean, rstd, dh)
-    return _ffn_core_bwd(dsd, h2, u, g, P, ACT_GELU, residual=ds)
+    h2, u, g, s, mean, rstd, dh, rows = saved
+    ds, dsd = _post_ln_bwd(dy, s, P.ln, mean, rstd, dh, rows)
+    return _ffn_core_bwd(dsd, h2, u, g, P, ACT_GELU, residual=ds, rows=rows)
+
+
+# ---- live-row form of the BERT attention sub-block: the queries are token 0 of every sample, the keys all tokens -------------
+class _ProjRows:
+    """Rows r0:r1 of a projection parameter (the Q or the K | V slice of a packed Q | K | V weight, or a whole weight): the views
+    mm_nt / dgrad / wgrad read and write -- weight, bias, transposed shadow, gradient -- without a copy."""
+
+    def __init__(self, w_param, b_param, r0=None, r1=None):
+        self.w_param, self.b_param, self.sl = w_param, b_param, slice(r0, r1)
+
+    @property
+    def w(self):
+        return compute_weight(self.w_param)[self.sl]
+
+    @property
+    def b(self):
+        return _bdata(self.b_param)[self.sl]
+
+    def dgrad(self, dy, residual=None):
+        """dx[M, K] = dy[M, n] . W[r0:r1] (+ residual)"""
+        M, n = dy.shape
+        wt = getattr(self.w_param, "m3ae_t", None)
+        if wt is not None:
+            b = wt[:, self.sl]
+            b_sk, b_sn, K = 1, wt.stride(0), wt.shape[0]
+        else:
+            b = self.w
+            b_sk, b_sn, K = b.stride(0), 1, b.shape[1]
+        out = torch.empty((M, K), dtype=dy.dtype, device=dy.device)
+        gemm(dy, dy.stride(0), 1, b, b_sk, b_sn, out, K, M, K, n, residual=residual)
+        return out
+
+    def wgrad(self, dy, x2, ldx):
+        """W.grad[r0:r1] += dy^T . x2, b.grad[r0:r1] += colsum(dy); the caller reports the parameter done (ops._done) once all its
+        slices are in."""
+        want_b = self.b_param is not None and self.b_param.requires_grad
+        if not self.w_param.requires_grad:
+            if want_b:
+                colsum(dy, _grad_buf(self.b_param)[self.sl], True)
+            return
+        g = _grad_buf(self.w_param)[self.sl]
+        M, n = dy.shape
+        gemm(dy, 1, dy.stride(0), x2, ldx, 1, g, g.stride(0), n, g.shape[1], M, accumulate=True,
+             a_rowsum=_grad_buf(self.b_param)[self.sl] if want_b else None)
+
+
+def _live_proj(P, D):
+    """(q, kv) projection slices of a BertAttention parameter set: of the packed Q | K | V weight (self-attention) or the separate
+    Q and K | V weights (cross-attention)."""
+    if hasattr(P, "w_qkv"):
+        return _ProjRows(P.w_qkv, P.b_qkv, 0, D), _ProjRows(P.w_qkv, P.b_qkv, D, 3 * D)
+    return _ProjRows(P.w_q, P.b_q), _ProjRows(P.w_kv, P.b_kv)
+
+
+def _attn_sub_fwd_live(hq, src2, B, Ls, Lfull, mask, P, pdrop=0.0):
+    """_attn_sub_fwd for the queries hq [B, D] = token 0 of each of the B samples (compact), keys / values from all B Ls rows of
+    src2 (the sample's own rows: self-attention; the other modality's: cross-attention).  Lfull: query rows per sample of the
+    full call, whose dropout masks (rows b Lfull of the dense sites, (b H + h) Lfull of the probabilities) this call draws, with
+    seeds taken in the same order.  Returns (y [B, D], saved)."""
+    D = hq.shape[1]
+    da, dh = dropout_pair(pdrop), dropout_pair(pdrop)
+    pq, pkv = _live_proj(P, D)
+    kv, _ = mm_nt(src2, src2.shape[1], B * Ls, pkv.w, bias=pkv.b)
+    q, _ = mm_nt(hq, D, B, pq.w, bias=pq.b)
+    n = q.shape[1]
+    kv3 = kv.view(B, Ls, 2 * n)
+    o, lse = attn_forward(q.view(B, 1, n), kv3[..., :n], kv3[..., n:], P.heads, mask, dropout=da, rows=(0, Lfull))
+    s, _ = mm_nt(o.view(B, n), n, B, compute_weight(P.w_o), bias=_bdata(P.b_o), residual=hq, dropout=dh, rows=(0, Lfull))
+    y, mean, rstd = ln_fwd_raw(s, P.ln)
+    return y, (hq, src2, q, kv, o, lse, s, mean, rstd, mask, da, dh, Ls, Lfull)
+
+
+def _attn_sub_bwd_live(dy, saved, B, P, need_dsrc=True):
+    """Backward of _attn_sub_fwd_live: (dhq [B, D], dsrc [B Ls, Ds] or None), the gradients of the query rows and of the key /
+    value rows.  Self-attention (token 0 is query and key): (None, dh [B Ls, D]) with both joined in the token-0 rows."""
+    hq, src2, q, kv, o, lse, s, mean, rstd, mask, da, dh, Ls, Lfull = saved
+    D, n = hq.shape[1], q.shape[1]
+    ds, dsd = _post_ln_bwd(dy, s, P.ln, mean, rstd, dh, rows=(0, Lfull))
+    mm_wgrad(dsd, o.view(B, n), n, P.w_o, P.b_o)
+    dctx = mm_dgrad(dsd, P.w_o)
+    dq, dkv = torch.empty_like(q), torch.empty_like(kv)
+    kv3, dkv3 = kv.view(B, Ls, 2 * n), dkv.view(B, Ls, 2 * n)
+    attn_backward(q.view(B, 1, n), kv3[..., :n], kv3[..., n:], o, lse, dctx.view(o.shape), dq.view(B, 1, n), dkv3[..., :n],
+                  dkv3[..., n:], P.heads, mask, dropout=da, rows=(0, Lfull))
+    pq, pkv = _live_proj(P, D)
+    pq.wgrad(dq, hq, D)
+    pkv.wgrad(dkv, src2, src2.shape[1])
+    for prm in {id(p): p for p in (pq.w_param, pq.b_param, pkv.w_param, pkv.b_param)}.values():
+        if prm.requires_grad:
+            _done(prm)
+    if pq.w_param is pkv.w_param:
+        # token 0's gradient is the full layer's product for that row, d(q | k | v) . W_qkv + ds in ONE accumulation and one
+        # rounding (the same bits as the full call's row, so the layers below see the same gradient): B packed rows
+        dh = pkv.dgrad(dkv)
+        dqkv0 = torch.cat([dq, dkv3[:, 0]], dim=1)
+        dh.view(B, Ls, D)[:, 0] = mm_dgrad(dqkv0, pq.w_param, residual=ds)
+        return None, dh
+    dhq = pq.dgrad(dq, residual=ds)   # + the residual-branch gradient, in the epilogue
+    return dhq, (pkv.dgrad(dkv) if need_dsrc else None)
 
 
 class BertCrossLayerFn(Function):
@@ -1139,6 +1260,18 @@ class BertCrossLayerFn(Function):
         h2 = h.contiguous().view(B * L, D)
         other2 = other.contiguous().view(B * Lo, other.shape[2])
         pd = getattr(P, "pdrop", 0.0)
+        ctx.live = bool(getattr(P, "cls_only", False))
+        if ctx.live:
+            # live rows = token 0: only that row of the output is read (CLS heads).  K | V of both attentions for all rows, every
+            # other product on the B token-0 rows; the dropout sites draw the full call's seeds and masks.  Returns [B, 1, D].
+            hq = h2.view(B, L, D)[:, 0].contiguous()
+            a, s1 = _attn_sub_fwd_live(hq, h2, B, L, L, mask_self, P.attn, pd)
+            c, s2 = _attn_sub_fwd_live(a, other2, B, Lo, L, mask_other, P.cross, pd)
+            y, s3 = _ffn_sub_fwd(c, P.ffn, pd, rows=(0, L))
+            ctx.saved = (s1, s2, s3)
+            ctx.P, ctx.dims, ctx.n_anchor = P, (B, L, Lo, D), len(anchors)
+            ctx.need_other = other.requires_grad
+            return y.view(B, 1, D)
         a, s1 = _attn_sub_fwd(h2, B, L, None, L, mask_self, P.attn, pd)
         # the fused cross-attention sub-block (csrc/xattn.hip) where the shapes are covered: forward-only calls always,
         # training with its fused backward (ops.XATTN_TRAIN)
@@ -1160,6 +1293,12 @@ class BertCrossLayerFn(Function):
         s1, s2, s3 = ctx.saved
         ctx.saved = None
         P = ctx.P
+        if ctx.live:
+            dc = _ffn_sub_bwd(dy.contiguous().view(B, D), s3, P.ffn)
+            da, dother = _attn_sub_bwd_live(dc, s2, B, P.cross, need_dsrc=ctx.need_other)
+            _, dh = _attn_sub_bwd_live(da, s1, B, P.attn)
+            return (dh.view(B, L, D), None if dother is None else dother.view(B, Lo, -1), None, None, None) + \
+                   (None,) * ctx.n_anchor
         dc = _ffn_sub_bwd(dy.contiguous().view(B * L, D), s3, P.ffn)
         da, dother = _attn_sub_bwd(dc, s2, B, L, Lo, P.cross, need_dother=ctx.need_other)
         dh, _ = _attn_sub_bwd(da, s1, B, L, L, P.attn)

@@ -32,6 +32,7 @@ DET_ENTRIES = ("m3ae_gemm_det_workspace_bytes", "m3ae_gemm_det", "m3ae_det_works
                "m3ae_layernorm_bwd_det", "m3ae_layernorm_bwd_drop_det", "m3ae_roberta_embed_bwd_det", "m3ae_bce_logits_det",
                "m3ae_xent_det", "m3ae_mim_loss_fwd_det")
 IMAGE_ENTRIES = ("m3ae_image_resample_workspace_bytes", "m3ae_image_resample_u8")
+ROWS_ENTRIES = ("m3ae_gemm_rows", "m3ae_attn_fwd_rows", "m3ae_attn_bwd_rows", "m3ae_layernorm_bwd_drop_rows", "m3ae_dropout_rows")
 
 
 def _ctype_name(t):
@@ -67,6 +68,11 @@ def block():
     out.append("")
     out.append("# device image transform (ABI 4, additive): Pillow-exact bicubic resize + centre crop + normalize from the source bytes")
     for name in IMAGE_ENTRIES:
+        res, args = _lib._SIGS[name]
+        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
+    out.append("")
+    out.append("# dropout row map (ABI 4, additive): mask row = row_base + row * row_step, (row_base, row_step) before the stream")
+    for name in ROWS_ENTRIES:
         res, args = _lib._SIGS[name]
         out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
     out.append("```")
