@@ -40,6 +40,8 @@ extern "C" {
 /* 4 (additive): dropout row map.  m3ae_gemm_rows, m3ae_attn_fwd_rows / m3ae_attn_bwd_rows, m3ae_layernorm_bwd_drop_rows and
  *    m3ae_dropout_rows: the entry points they are named after with (row_base, row_step), so that a call on a subset of a tensor's
  *    rows draws the dropout masks of the full tensor (see m3ae_dropout); no descriptor changed. */
+/* 4 (additive): device-resident beam search.  m3ae_beam_topk (+ m3ae_beam_topk_workspace_bytes), m3ae_beam_step and
+ *    m3ae_beam_finalize (csrc/beam.hip); no descriptor changed. */
 #define M3AE_ABI_VERSION 4
 
 enum { M3AE_F32 = 0, M3AE_BF16 = 1 };
@@ -476,6 +478,43 @@ int m3ae_xent_det(const void* logits, const int64_t* labels, float* loss, void* 
                   float grad_scale, int dtype, void* workspace, int64_t workspace_bytes, void* stream);
 int m3ae_mim_loss_fwd_det(const void* x, const float* target, const float* mask, float* acc, float* loss, int64_t B, int64_t L,
                           int64_t D, int dtype, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Device-resident beam search (csrc/beam.hip; ABI 4, additive): transformers-4.6.0 `beam_search` + `BeamSearchScorer` as
+ * T5ForConditionalGeneration.generate restates them (the reference runs HF `generate` at m3ae_t5_mm_encoder_input.py:209-218,
+ * 252-261), with the per-step bookkeeping on device state.  R = B * nb beam rows, nb <= 8; no atomics anywhere: two calls on the
+ * same inputs give the same bits.
+ *
+ * m3ae_beam_topk: logits fp32 [R][V] with row stride ld >= V, beam_scores fp32 [R].  Per row m = max x, lse = log sum exp(x - m)
+ *   (fp32, summation order fixed by V and chunk), score = fl(fl(fl(x - m) - lse) + beam_score); per sample the best 2 nb of its
+ *   nb * V candidates into top_s fp32 [B][2 nb] / top_i int32 [B][2 nb], ordered by (rounded score descending, flat index
+ *   beam * V + token ascending).  top_i entries are distinct and in [0, nb * V) whatever the logits hold (NaN ranks somewhere).
+ *   Rows are split over vocabulary chunks of `chunk` elements (0 = 2048; at most 4096), one workgroup per (row, chunk), partial
+ *   lists merged by a second stage.  workspace: m3ae_beam_topk_workspace_bytes(B, nb, V, chunk) bytes, 8-byte aligned.
+ *   M3AE_ERR_UNSUPPORTED unless 1 <= nb <= 8, V >= 2 nb + 1, nb * V < 2^31 and chunk <= 4096.
+ * m3ae_beam_step: one scorer step at prefix length cur_len (1 <= cur_len < max_length) from the candidates of m3ae_beam_topk.
+ *   Per sample, in rank order: an EOS candidate at rank >= nb is skipped; at rank < nb it pushes (score / div, source prefix) into
+ *   the sample's hypothesis list -- double arithmetic, div = cur_len ** length_penalty computed by the caller; the list stays
+ *   sorted descending with a new entry AFTER equal scores and is cut to nb; other candidates fill the next nb beams.  A sample is
+ *   done once it holds nb hypotheses; a done sample gets source row b * nb, pad tokens and score 0 for all its beams.
+ *   ids_in / ids_out int64 [R][max_length] (different buffers: a row may feed several rows), last_tok int64 [R] (the new column),
+ *   beam_scores fp32 [R], order int64 [R] (source rows, for m3ae_gather_rows of the key / value caches), done / n_hyp int32 [B],
+ *   hyp_score double [B][nb], hyp_len int32 [B][nb], hyp_tok int64 [B][nb][max_length]; open_count int32 [1] receives the number
+ *   of samples not done after the step; err int64 [1] is set to 1 when a top_i entry is outside [0, nb * V) (the entry is
+ *   skipped, never turned into an address).
+ * m3ae_beam_finalize: samples not done push their nb open beams (ids [R][max_length], prefix length cur_len) with
+ *   beam_score / div, div = (cur_len - len_offset) ** length_penalty; then seq int64 [B][max_length] = the best hypothesis, EOS
+ *   appended when shorter than max_length, pad after it, and len int64 [B] = its length. */
+int64_t m3ae_beam_topk_workspace_bytes(int64_t B, int64_t nb, int64_t V, int64_t chunk);
+int m3ae_beam_topk(const float* logits, int64_t ld, const float* beam_scores, int64_t B, int64_t nb, int64_t V, int64_t chunk,
+                   void* workspace, int64_t workspace_bytes, float* top_s, int32_t* top_i, void* stream);
+int m3ae_beam_step(const float* top_s, const int32_t* top_i, const int64_t* ids_in, int64_t* ids_out, int64_t* last_tok,
+                   float* beam_scores, int64_t* order, int32_t* done, int32_t* n_hyp, double* hyp_score, int32_t* hyp_len,
+                   int64_t* hyp_tok, int32_t* open_count, int64_t* err, int64_t B, int64_t nb, int64_t V, int64_t max_length,
+                   int64_t cur_len, int64_t eos, int64_t pad, double div, void* stream);
+int m3ae_beam_finalize(const int64_t* ids, const float* beam_scores, const int32_t* done, int32_t* n_hyp, double* hyp_score,
+                       int32_t* hyp_len, int64_t* hyp_tok, int64_t* seq, int64_t* len, int64_t B, int64_t nb, int64_t max_length,
+                       int64_t cur_len, int64_t eos, int64_t pad, double div, void* stream);
 
 /* self-test of hardware idioms the kernels rely on (MFMA fragment maps, ds_read_b64_tr_b16, accumulator-as-
  * operand k-order).  out: int32[8 + 256] device buffer (tail = scratch), out[0] = number of mismatches. */

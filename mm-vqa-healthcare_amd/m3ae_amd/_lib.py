@@ -128,6 +128,11 @@ _SIGS = {
     "m3ae_attn_bwd_rows": (C.c_int, [C.POINTER(AttnDesc), i64, i64, vp]),
     "m3ae_layernorm_bwd_drop_rows": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, f32, C.c_uint64, vp, vp, vp, vp, i64, i64, C.c_int, i64, i64, vp]),
     "m3ae_dropout_rows": (C.c_int, [vp, vp, vp, i64, i64, f32, C.c_uint64, vp, C.c_int, i64, i64, vp]),
+    # device-resident beam search (ABI 4, additive)
+    "m3ae_beam_topk_workspace_bytes": (i64, [i64, i64, i64, i64]),
+    "m3ae_beam_topk": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, i64, vp, vp, vp]),
+    "m3ae_beam_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, C.c_double, vp]),
+    "m3ae_beam_finalize": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, C.c_double, vp]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -48,6 +48,9 @@ DEFAULTS = dict(
     # where the CLIP transform's bicubic resize + centre crop run for arrow data (m3ae_amd/data.py): "host" (PIL, on the loader's
     # threads) | "device" (csrc/image.hip from the decoded source bytes; bit-identical batches)
     image_transform="host",
+    # where the beam-search bookkeeping of the T5 head's generate runs (m3ae_amd/modules/t5.py): "host" (one small copy and a Python
+    # loop per step) | "device" (csrc/beam.hip, no host round trip per step; same tokens)
+    t5_beam_search="host",
 )
 
 NAMED = {

@@ -51,6 +51,7 @@ class T5VQA_MMEncoderInput(_Base):
         for p in self.feature_projection.parameters():
             p.requires_grad = False                       # never reached by a gradient in the reference either
         self.max_answer_length = m3ae_config.get("t5_max_length", 25)
+        self.beam_search = m3ae_config.get("t5_beam_search", "host")   # build extension: "host" | "device" (t5.generate)
         self.prefix_ids = [822, 10]                       # "question:"
         self.current_tasks = list()
         self.store = None
@@ -121,7 +122,8 @@ class T5VQA_MMEncoderInput(_Base):
         if len(self.current_tasks) == 0 or test:  # inference / test: beam search (:207-218)
             with torch.no_grad():
                 enc = self.t5.encoder(inputs["inputs_embeds"])
-            return {"generated_ids": self.t5.generate(enc, num_beams=4, max_length=self.max_answer_length)}
+            return {"generated_ids": self.t5.generate(enc, num_beams=4, max_length=self.max_answer_length,
+                                                      beam_search=self.beam_search)}
         out = self.t5(inputs["inputs_embeds"], self.labels_of(batch))
         return {"vqa_loss": out.loss, "vqa_logits": out.logits}
 

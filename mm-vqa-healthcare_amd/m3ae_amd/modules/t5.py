@@ -284,14 +284,82 @@ class T5ForConditionalGeneration(nn.Module):
         return ops.linear(dec[:, -1].contiguous(), self.shared.weight, None, alpha=self.config.d_model ** -0.5).float()
 
     @torch.no_grad()
+    def generate_async(self, enc, num_beams=4, max_length=12, eos_token_id=1, pad_token_id=0, length_penalty=1.0,
+                       len_offset=0, lookahead=2, topk_chunk=0):
+        """The beam search of `generate` with its bookkeeping on the device (csrc/beam.hip): per step the decoder row, the
+        vocabulary GEMM, ops.beam_topk, ops.beam_step and the cache re-ordering are enqueued with no blocking host call, and
+        the result stays on the device.  Returns a namespace with `seq` int64 [B, max_length] (pad-filled), `len` int64 [B]
+        (length of the best hypothesis, before the EOS), `err` int64 [1] (nonzero: a candidate index left its range), `out`
+        (the three in one buffer), `steps` (decoding steps enqueued) and `state` (ops.BeamState).
+
+        Early exit: steps after every sample is done change no token, so leaving the loop is an optimisation only.  The count
+        of open samples after each step is copied to pinned host memory behind the step, with an event; the host runs at most
+        `lookahead` steps past the newest step whose event has completed (it waits on the event of the step `lookahead` back,
+        so the device always has work queued) and stops enqueuing once a completed step reports zero open samples.
+        lookahead=None always runs max_length - 1 steps."""
+        if lookahead is not None and lookahead < 1:
+            raise ValueError("lookahead must be >= 1 or None")
+        B, nb, dev = enc.shape[0], num_beams, enc.device
+        R = B * nb
+        enc_r = enc.repeat_interleave(nb, dim=0).contiguous()
+        Ls = enc.shape[1]
+        cross_kv = [kv.view(B, Ls, -1).repeat_interleave(nb, dim=0).reshape(R * Ls, -1) for kv in self.decoder.cross_kv(enc)]
+        self_cache = self.decoder.new_self_cache(R, max_length, enc.dtype, dev)
+        st = ops.BeamState(B, nb, max_length, dev, self.config.decoder_start_token_id, pad_token_id)
+        ws = None
+        top = (torch.empty((B, 2 * nb), dtype=torch.float32, device=dev), torch.empty((B, 2 * nb), dtype=torch.int32, device=dev))
+        if lookahead is not None:
+            open_host = torch.empty(max_length, dtype=torch.int32, pin_memory=True)
+            open_np = open_host.numpy()      # read through numpy: plain host memory, filled by the copies below
+            events = {}
+        seen = 0                             # newest step whose event is known to have completed
+        steps, cur_len = 0, 1
+        while cur_len < max_length:
+            logits = self.next_token_logits_cached(enc_r, st.last_tok.view(R, 1), cross_kv, self_cache, cur_len - 1)
+            if ws is None:
+                V = logits.shape[-1]
+                ws = ops.beam_topk_workspace(B, nb, V, dev, topk_chunk)
+            ops.beam_topk(logits, st.beam_scores, B, nb, topk_chunk, ws, top)
+            ops.beam_step(st, top[0], top[1], V, cur_len, eos_token_id, pad_token_id, length_penalty)
+            self_cache = [ops.gather_rows(c.view(R, -1), st.order).view_as(c) for c in self_cache]
+            steps += 1
+            if lookahead is not None:
+                open_host[cur_len:cur_len + 1].copy_(st.open_count[cur_len:cur_len + 1], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record()
+                events[cur_len] = ev
+                if cur_len + 1 - lookahead >= 1:     # step cur_len + 1 may be enqueued once step cur_len + 1 - lookahead is through
+                    events[cur_len + 1 - lookahead].synchronize()
+                    seen = max(seen, cur_len + 1 - lookahead)
+                while seen < cur_len and events[seen + 1].query():
+                    seen += 1
+                if any(open_np[s] == 0 for s in range(1, seen + 1)):
+                    cur_len += 1
+                    break
+            cur_len += 1
+        ops.beam_finalize(st, cur_len, eos_token_id, pad_token_id, length_penalty, len_offset)
+        return NS(seq=st.seq, len=st.len, err=st.err, out=st.out, steps=steps, state=st)
+
+    @torch.no_grad()
     def generate(self, enc, num_beams=4, max_length=12, eos_token_id=1, pad_token_id=0, length_penalty=1.0,
-                 len_offset=0):
+                 len_offset=0, beam_search="host", lookahead=2):
         """HF `generate(encoder_outputs=..., num_beams, early_stopping=True, max_length)` as the reference calls it
         (m3ae_t5_mm_encoder_input.py:209-218,252-260): transformers-4.6.0 `beam_search` + `BeamSearchScorer`
         semantics, restated in oracle/m3ae_oracle.py::t5_beam_search (pinned against the installed release's
         `generate`; `len_offset` documents the one convention that changed between the two releases).
-        The model runs on the GPU; the per-step candidate bookkeeping (2 * beams scores and tokens per sample) is
-        host logic on one small device->host copy per step."""
+        beam_search="host" (default): the model runs on the GPU; the per-step candidate bookkeeping (2 * beams scores and
+        tokens per sample) is host logic on one small device->host copy per step.  beam_search="device": `generate_async`
+        plus one copy of its result at the end; same tokens."""
+        if beam_search == "device":
+            r = self.generate_async(enc, num_beams, max_length, eos_token_id, pad_token_id, length_penalty, len_offset, lookahead)
+            out = r.out.cpu()
+            if int(out[-1]) != 0:
+                raise ops._lib.M3AEHipError("device beam search: a candidate index left [0, num_beams * vocab_size)")
+            B = enc.shape[0]
+            L = min(int(out[B * max_length:-1].max()) + 1, max_length)
+            return out[:B * max_length].view(B, max_length)[:, :L].contiguous().to(enc.device)
+        if beam_search != "host":
+            raise ValueError(f"beam_search must be 'host' or 'device', got {beam_search!r}")
         B, nb, dev = enc.shape[0], num_beams, enc.device
         enc_r = enc.repeat_interleave(nb, dim=0).contiguous()
         # encoder-side keys / values once per call; the beams of a sample share their encoder rows, so re-ordering beams

@@ -1809,6 +1809,88 @@ def selftest():
 
 
 # ------------------------------------------------------------------------------------------------------------
+# device-resident beam search (csrc/beam.hip): T5ForConditionalGeneration.generate_async
+# ------------------------------------------------------------------------------------------------------------
+BEAM_TOPK_CHUNK = 2048   # vocabulary elements per workgroup of m3ae_beam_topk when the caller passes chunk=0
+
+
+def beam_topk_workspace(B, nb, V, device, chunk=0):
+    n = _lib.lib().m3ae_beam_topk_workspace_bytes(B, nb, V, chunk)
+    return torch.empty(max(n, 8) // 8, dtype=torch.int64, device=device)
+
+
+def beam_topk(logits, beam_scores, B, nb, chunk=0, ws=None, out=None):
+    """logits fp32 [B * nb, V] (row stride >= V), beam_scores fp32 [B * nb] -> top_s fp32 [B, 2 nb], top_i int32 [B, 2 nb]: the best
+    2 nb of every sample's nb * V values of fl(log_softmax(x) + beam_score), by (score descending, beam * V + token ascending)."""
+    _need_cuda(logits)
+    _need_cuda(beam_scores)
+    if logits.dtype != torch.float32 or beam_scores.dtype != torch.float32:
+        raise TypeError("beam_topk takes fp32 logits and beam scores")
+    R, V = logits.shape
+    if R != B * nb or beam_scores.numel() != R or logits.stride(1) != 1 or not beam_scores.is_contiguous():
+        raise ValueError(f"beam_topk: logits {tuple(logits.shape)} / beam_scores {tuple(beam_scores.shape)} for B={B}, nb={nb}")
+    if ws is None:
+        ws = beam_topk_workspace(B, nb, V, logits.device, chunk)
+    top_s, top_i = out if out is not None else (torch.empty((B, 2 * nb), dtype=torch.float32, device=logits.device),
+                                                torch.empty((B, 2 * nb), dtype=torch.int32, device=logits.device))
+    check(_lib.lib().m3ae_beam_topk(_p(logits), logits.stride(0), _p(beam_scores), B, nb, V, chunk, _p(ws), ws.numel() * 8,
+                                    _p(top_s), _p(top_i), _stream()), "m3ae_beam_topk")
+    return top_s, top_i
+
+
+class BeamState:
+    """The device state of one beam search (include/m3ae_hip.h, m3ae_beam_step): allocated once per generate call."""
+
+    def __init__(self, B, nb, max_length, device, start_id=0, pad_id=0):
+        R = B * nb
+        z = functools.partial(torch.zeros, device=device)
+        self.B, self.nb, self.max_length = B, nb, max_length
+        self.ids = torch.full((2, R, max_length), pad_id, dtype=torch.int64, device=device)   # ping-pong: a row may feed several rows
+        self.ids[0, :, 0] = start_id
+        self.cur = 0                                   # which half of `ids` holds the prefixes
+        self.last_tok = torch.full((R,), start_id, dtype=torch.int64, device=device)
+        self.beam_scores = z((B, nb), dtype=torch.float32)
+        self.beam_scores[:, 1:] = -1e9
+        self.beam_scores = self.beam_scores.view(-1)
+        self.order = z((R,), dtype=torch.int64)
+        self.done, self.n_hyp = z((B,), dtype=torch.int32), z((B,), dtype=torch.int32)
+        self.hyp_score = z((B, nb), dtype=torch.float64)
+        self.hyp_len = z((B, nb), dtype=torch.int32)
+        self.hyp_tok = z((B, nb, max_length), dtype=torch.int64)
+        self.open_count = z((max_length,), dtype=torch.int32)
+        self.out = z((B * max_length + B + 1,), dtype=torch.int64)   # seq | len | error word: one copy brings all three to the host
+        self.seq, self.len, self.err = self.out[:B * max_length].view(B, max_length), self.out[B * max_length:-1], self.out[-1:]
+
+
+def beam_step(st, top_s, top_i, V, cur_len, eos_id, pad_id, length_penalty=1.0):
+    """One BeamSearchScorer step on `st` at prefix length cur_len; st.open_count[cur_len] = samples still open afterwards."""
+    for t in (top_s, top_i, st.ids):
+        _need_cuda(t)
+    if top_s.dtype != torch.float32 or top_i.dtype != torch.int32 or tuple(top_s.shape) != (st.B, 2 * st.nb) \
+            or top_i.shape != top_s.shape or not top_s.is_contiguous() or not top_i.is_contiguous():
+        raise ValueError("beam_step: top_s fp32 / top_i int32 [B, 2 nb], contiguous")
+    if not 1 <= cur_len < st.max_length:
+        raise ValueError(f"beam_step: cur_len {cur_len} outside [1, {st.max_length})")
+    check(_lib.lib().m3ae_beam_step(_p(top_s), _p(top_i), _p(st.ids[st.cur]), _p(st.ids[1 - st.cur]), _p(st.last_tok), _p(st.beam_scores),
+                                    _p(st.order), _p(st.done), _p(st.n_hyp), _p(st.hyp_score), _p(st.hyp_len), _p(st.hyp_tok),
+                                    _p(st.open_count[cur_len:]), _p(st.err), st.B, st.nb, V, st.max_length, cur_len, eos_id, pad_id,
+                                    float(cur_len) ** length_penalty, _stream()), "m3ae_beam_step")
+    st.cur = 1 - st.cur
+
+
+def beam_finalize(st, cur_len, eos_id, pad_id, length_penalty=1.0, len_offset=0):
+    """Open beams of the samples not done join their hypothesis lists; st.seq / st.len = the best hypothesis per sample."""
+    _need_cuda(st.ids)
+    if not 1 <= cur_len <= st.max_length or cur_len - len_offset < 1:
+        raise ValueError(f"beam_finalize: cur_len {cur_len}, len_offset {len_offset}")
+    check(_lib.lib().m3ae_beam_finalize(_p(st.ids[st.cur]), _p(st.beam_scores), _p(st.done), _p(st.n_hyp), _p(st.hyp_score),
+                                        _p(st.hyp_len), _p(st.hyp_tok), _p(st.seq), _p(st.len), st.B, st.nb, st.max_length, cur_len,
+                                        eos_id, pad_id, float(cur_len - len_offset) ** length_penalty, _stream()),
+          "m3ae_beam_finalize")
+    return st.seq, st.len
+
+
+# ------------------------------------------------------------------------------------------------------------
 # masked-image-modelling bookkeeping (pre-training, SURVEY 8a13)
 # ------------------------------------------------------------------------------------------------------------
 def mask_ranks(noise, len_keep):
