@@ -516,6 +516,23 @@ int m3ae_beam_finalize(const int64_t* ids, const float* beam_scores, const int32
                        int32_t* hyp_len, int64_t* hyp_tok, int64_t* seq, int64_t* len, int64_t B, int64_t nb, int64_t max_length,
                        int64_t cur_len, int64_t eos, int64_t pad, double div, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Sample expansion of a de-duplicated image batch (csrc/samples.hip; ABI 4, additive): the image tower runs once per distinct
+ * image of a batch and its [n_in][R] output (R = tokens * width elements per image, fp32 or bf16) is expanded to the batch's
+ * samples.  Row bases are 64-bit element offsets; rows move in 16-byte units when R * sizeof(element) is a multiple of 16 and
+ * both base pointers are 16-byte aligned, element by element otherwise.
+ *
+ * m3ae_expand_samples: out[b] = in[src[b]], b < n_out; src int64 [n_out] with values in [0, n_in) (a value outside is never
+ *   dereferenced: that output row is left untouched).
+ * m3ae_segment_sum_rows: its backward, d_in[u] = sum of d_out[members[j]] for offsets[u] <= j < offsets[u + 1]; offsets int64
+ *   [n_in + 1], members int64 [n_out] (a CSR of the samples of every image, each list in ascending sample order).  One lane owns
+ *   an output element: it adds the members in list order in an fp32 register, starting from the first member, and rounds once to
+ *   the storage dtype (bf16: round-to-nearest-even).  No atomics: the same bits on every run, a group of one is a copy. */
+int m3ae_expand_samples(const void* in, const int64_t* src, void* out, int64_t n_out, int64_t n_in, int64_t R, int dtype,
+                        void* stream);
+int m3ae_segment_sum_rows(const void* d_out, const int64_t* offsets, const int64_t* members, void* d_in, int64_t n_in,
+                          int64_t n_out, int64_t R, int dtype, void* stream);
+
 /* self-test of hardware idioms the kernels rely on (MFMA fragment maps, ds_read_b64_tr_b16, accumulator-as-
  * operand k-order).  out: int32[8 + 256] device buffer (tail = scratch), out[0] = number of mismatches. */
 int m3ae_selftest(int32_t* out, void* stream);

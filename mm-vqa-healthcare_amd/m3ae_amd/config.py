@@ -51,6 +51,10 @@ DEFAULTS = dict(
     # where the beam-search bookkeeping of the T5 head's generate runs (m3ae_amd/modules/t5.py): "host" (one small copy and a Python
     # loop per step) | "device" (csrc/beam.hip, no host round trip per step; same tokens)
     t5_beam_search="host",
+    # arrow VQA batches collated per distinct image (m3ae_amd/data.py: collate_dedup): every distinct image of a batch is decoded,
+    # uploaded and run through the image tower once, and ops.expand_samples hands its tokens to the samples that ask about it
+    # (batch["image_index"]).  Same samples, same arithmetic per sample; not available with the mim / itm objectives.
+    image_dedup=False,
 )
 
 NAMED = {

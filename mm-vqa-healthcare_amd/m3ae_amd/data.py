@@ -28,6 +28,12 @@ bicubic resize, the centre crop and ToTensor + Normalize on the GPU: the same in
 bit-identical to the host path's.  An image with real transparency (Pillow premultiplies it around the resize) or beyond
 the staging caps is transformed on the host as before and joins the batch as a size x size source with identity tables;
 `ArrowDataModule.transform_stats` counts both routes.
+
+`image_dedup=True` (VQA tables; off by default): Med-VQA data asks many questions about few images, so a batch is collated per
+distinct (table, image row) -- `collate_dedup`: the workers decode and transform every distinct image of the batch once,
+`image_u8` is [U, ...] (the device transform receives U sources), and the batch carries `image_index` (int64 [B]: the image row
+of every sample) with the index tables `M3AETransformerSS.infer` needs (`image_groups`, ops.ImageGroups; pinned, uploaded with
+the batch).  The samples of a batch and their order are those of the plain path.  `transform_stats.decodes` counts the decodes.
 """
 import ctypes as C
 import io
@@ -70,10 +76,15 @@ class TransformStats(dict):
     def __init__(self):
         super().__init__(device=0, fallback=0)
         self._lock = threading.Lock()
+        self.decodes = 0   # images decoded, either transform (an attribute: the dict holds the device transform's routes alone)
 
     def count(self, route):
         with self._lock:
             self[route] += 1
+
+    def count_decode(self):
+        with self._lock:
+            self.decodes += 1
 
 
 def load_image_u8(raw, size, image_transform="host", stats=None):
@@ -81,6 +92,8 @@ def load_image_u8(raw, size, image_transform="host", stats=None):
     ("device": uint8 [h, w, 3], or the host-made crop of an image it does not take)."""
     from PIL import Image
     img = Image.open(io.BytesIO(raw))
+    if stats is not None:
+        stats.count_decode()
     if image_transform != "device":
         return clip_resize_crop(img, size)
     route, a = resample.prepare(img, size)
@@ -221,12 +234,17 @@ class ArrowVQADataset:
         return load_image_u8(self.table["image"][row].as_py(), self.image_size, self.image_transform, self.stats)
 
     def __getitem__(self, index):
+        sample, (_, row) = self.sample_without_image(index)
+        return {"image_u8": self.image_u8(row), **sample}
+
+    def sample_without_image(self, index):
+        """(the sample of `__getitem__` without its "image_u8", its image key): samples with equal keys show the same image, which
+        `image_by_key` loads (collate_dedup: one decode per distinct key of a batch)."""
         row, qi = self.index_mapper[index]
         text = self.all_texts[row][qi]
         enc = self.tokenizer(text, padding="max_length", truncation=True, max_length=self.max_text_len)
         t = self.table
         return {
-            "image_u8": self.image_u8(row),
             "text": text,
             "input_ids": list(enc["input_ids"]),
             "attention_mask": list(enc["attention_mask"]),
@@ -235,7 +253,10 @@ class ArrowVQADataset:
             "vqa_scores": t["answer_scores"][row][qi].as_py(),
             "answer_types": t["answer_type"][row][qi].as_py(),
             "qid": t["question_id"][row][qi].as_py(),
-        }
+        }, ("+".join(self.names), row)
+
+    def image_by_key(self, key):
+        return self.image_u8(key[1])
 
 
 class ArrowCaptionDataset:
@@ -305,18 +326,21 @@ class ConcatDataset:
         raise IndexError(index)
 
 
-def collate_host(samples, pin=True, mlm_collator=None, resample_size=None, pmap=map):
+def collate_host(samples, pin=True, mlm_collator=None, resample_size=None, pmap=map, images=None, image_index=None):
     """base_dataset.py:165-228: images stacked as uint8 NHWC, ids / masks as int64 tensors; with `mlm_collator` also
     `text_ids_mlm` / `text_labels_mlm` (:202-209; the reference always computes them, the fine-tuning step never reads
     them).  `resample_size` (image_transform="device"): the samples carry sources of any sizes; each image key becomes a
-    pack (resample.pack_batch: source bytes, plan, tables) for the device transform to that size, its copies run through `pmap`."""
+    pack (resample.pack_batch: source bytes, plan, tables) for the device transform to that size, its copies run through `pmap`.
+    `images` + `image_index` (collate_dedup): the samples carry no image; `image_u8` is built from the U distinct `images` and the
+    batch gets `image_index` (sample -> image row) and `image_groups` (ops.image_groups: the tables infer() reads)."""
     B = len(samples)
     S = max(len(s["input_ids"]) for s in samples)
     if resample_size:
-        stack = lambda k: resample.pack_batch([s[k] for s in samples], resample_size, pin=pin, pmap=pmap)
+        stack_list = lambda arrays: resample.pack_batch(arrays, resample_size, pin=pin, pmap=pmap)
     else:
-        stack = lambda k: torch.from_numpy(np.stack([s[k] for s in samples]))
-    img = stack("image_u8")
+        stack_list = lambda arrays: torch.from_numpy(np.stack(arrays))
+    stack = lambda k: stack_list([s[k] for s in samples])
+    img = stack("image_u8") if images is None else stack_list(list(images))
     ids = torch.zeros((B, S), dtype=torch.long)
     mask = torch.zeros((B, S), dtype=torch.long)
     for i, s in enumerate(samples):
@@ -334,11 +358,28 @@ def collate_host(samples, pin=True, mlm_collator=None, resample_size=None, pmap=
         img, ids, mask = _pin(img), ids.pin_memory(), mask.pin_memory()
         extra = {k: _pin(v) for k, v in extra.items()}
     out = {"image_u8": img, "text_ids": ids, "text_masks": mask, **extra, "text": [s["text"] for s in samples]}
+    if images is not None:
+        from . import ops
+        groups = ops.image_groups(np.asarray(image_index, dtype=np.int64), n_images=len(images), pin=pin)
+        out["image_index"], out["image_groups"] = groups.index, groups
     for k in ("vqa_answer", "vqa_labels", "vqa_scores", "answer_types", "qid", "img_index", "cap_index", "raw_index",
               "replica"):
         if k in samples[0]:
             out[k] = [s[k] for s in samples]
     return out
+
+
+def collate_dedup(ds, indices, pmap=map, **collate_kw):
+    """`collate_host` of the samples `indices` of a dataset with `sample_without_image` / `image_by_key` (ArrowVQADataset), per
+    distinct image: every distinct (table, image row) of the batch is loaded ONCE (through `pmap`: the loader's thread pool), in
+    the order of its first sample.  Same samples, same order, same keys as the plain collate plus `image_index` / `image_groups`;
+    `image_u8[image_index]` is the plain batch's `image_u8`."""
+    metas = list(pmap(ds.sample_without_image, indices))
+    rows, index = {}, []
+    for _, key in metas:
+        index.append(rows.setdefault(key, len(rows)))
+    images = list(pmap(ds.image_by_key, list(rows)))
+    return collate_host([m[0] for m in metas], pmap=pmap, images=images, image_index=index, **collate_kw)
 
 
 def to_device_batch(hb, device, copy_stream=None):
@@ -353,10 +394,15 @@ def to_device_batch(hb, device, copy_stream=None):
         ev = torch.cuda.Event()
         mlm = {k: hb[k].to(device, non_blocking=True) for k in ("text_ids_mlm", "text_labels_mlm") if k in hb}
         fal = {"_" + k: _up(hb[k]) for k in hb if k.startswith("false_image_u8_")}
+        grp = {}
+        if "image_groups" in hb:   # de-duplicated batch: the pinned index tables ride with the upload
+            g = hb["image_groups"].to(device)
+            grp = {"image_index": g.index, "image_groups": g}
         ev.record(cs)
-    out = {k: v for k, v in hb.items() if k not in ("image_u8", "text_ids", "text_masks", "text_ids_mlm", "text_labels_mlm")
+    out = {k: v for k, v in hb.items() if k not in ("image_u8", "text_ids", "text_masks", "text_ids_mlm", "text_labels_mlm",
+                                                     "image_index", "image_groups")
            and not k.startswith("false_image_u8_")}
-    out.update(_u8=u8, text_ids=ids, text_masks=mask, text_labels=None, _ready=ev, **mlm, **fal)
+    out.update(_u8=u8, text_ids=ids, text_masks=mask, text_labels=None, _ready=ev, **mlm, **fal, **grp)
     return out
 
 
@@ -382,6 +428,9 @@ def finish_batch(db):
     for t in db.values():   # every tensor uploaded on the copy stream (text_ids_mlm / text_labels_mlm included) is now used here
         if isinstance(t, torch.Tensor) and t.is_cuda:
             t.record_stream(cur)
+    if "image_groups" in db:
+        for t in db["image_groups"].tensors():
+            t.record_stream(cur)
     return db
 
 
@@ -402,6 +451,11 @@ class ArrowDataModule:
         if self.image_transform not in ("host", "device"):
             raise ValueError(f"image_transform must be 'host' or 'device', not {self.image_transform!r}")
         self.transform_stats = TransformStats()
+        self.image_dedup = bool(cfg.get("image_dedup", False))
+        loss_names = cfg.get("loss_names", {})
+        if self.image_dedup and any(loss_names.get(k, 0) > 0 for k in ("mim", "itm")):
+            raise ValueError("image_dedup=True cannot be combined with the mim / itm objectives (loss_names): they read the image "
+                             "pixels per sample")
         tf = dict(image_transform=self.image_transform, stats=self.transform_stats)
         if any(n in ("roco", "medicat") for n in names):   # the pre-training caption tables (config.py:22,31: draw_false_image = 1)
             mk = lambda split: ConcatDataset([ArrowCaptionDataset(root, n, split, cfg["image_size"], cfg["max_text_len"],
@@ -444,13 +498,19 @@ class ArrowDataModule:
         q = queue.Queue(maxsize=self.prefetch)
         stop = threading.Event()
 
+        dedup = self.image_dedup and hasattr(ds, "sample_without_image")   # (the caption tables ignore the flag)
+
         def producer():
+            kw = dict(mlm_collator=self.mlm_collator,
+                      resample_size=self.cfg["image_size"] if self.image_transform == "device" else None)
             with ThreadPoolExecutor(self.workers) as pool:
                 for c in chunks:
                     if stop.is_set():
                         break
-                    q.put(collate_host(list(pool.map(ds.__getitem__, c)), mlm_collator=self.mlm_collator, pmap=pool.map,
-                                       resample_size=self.cfg["image_size"] if self.image_transform == "device" else None))
+                    if dedup:
+                        q.put(collate_dedup(ds, c, pmap=pool.map, **kw))
+                    else:
+                        q.put(collate_host(list(pool.map(ds.__getitem__, c)), pmap=pool.map, **kw))
             q.put(None)
 
         th = threading.Thread(target=producer, daemon=True)

@@ -24,6 +24,11 @@ from . import ops
 
 class GraphedStep:
     def __init__(self, model, batch, max_steps, grad_scale=1.0):
+        if batch.get("image_index") is not None:
+            # the number of distinct images changes from batch to batch and with it the shapes of the image tower's launches:
+            # a captured step cannot be replayed on the next batch
+            raise ValueError('GraphedStep does not take a de-duplicated batch (batch["image_index"]): its static inputs need '
+                             'one image row per sample')
         self.model, self.store, self.batch = model, model.store, batch
         self.max_steps, self.grad_scale = max_steps, grad_scale
         dev = self.store.flat.device

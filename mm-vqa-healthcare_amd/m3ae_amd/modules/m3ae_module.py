@@ -266,20 +266,44 @@ class M3AETransformerSS(_Base):
         """m3ae_module.py:185-192 (`m3ae_mim_targets` without the standardisation)."""
         return ops.mim_targets(imgs, self.hparams.config["patch_size"], False)
 
+    @staticmethod
+    def _image_groups(batch, img, n_samples):
+        """The index tables of a batch with `image_index` (ops.ImageGroups on the image's device).  A datamodule batch brings them
+        in `batch["image_groups"]`, uploaded from pinned memory with the batch: no host call here.  A hand-built batch without
+        them pays ONE blocking copy of a device `image_index` to the host, where the tables are built (ops.image_groups)."""
+        groups = batch.get("image_groups")
+        if groups is None:
+            groups = ops.image_groups(batch["image_index"].cpu(), n_images=img.shape[0])
+        if groups.index.device != img.device:
+            groups = groups.to(img.device)
+        if groups.n_images != img.shape[0]:
+            raise ValueError(f'batch["image_groups"] is for {groups.n_images} images, batch["image"][0] has {img.shape[0]} rows')
+        if groups.n_samples != n_samples:
+            raise ValueError(f'batch["image_index"] has {groups.n_samples} entries for {n_samples} samples')
+        return groups
+
     @ops.model_mode
     def infer(self, batch, mask_text=False, mask_image=False, image_token_type_idx=1, img=None,
               output_attentions=False, unimodal=False, cls_only=False):
-        """m3ae_module.py:203-312.  cls_only: the caller reads `multi_modal_cls_feats` alone (the VQA and ITM heads): the last fusion
+        """m3ae_module.py:203-312.  With `batch["image_index"]` (int64 [B]) the image tensor holds one row per DISTINCT image
+        ([U, 3, H, W], U <= B, every row used): the tower runs on the U images and `ops.expand_samples` hands sample b the tokens
+        of image image_index[b] before the fusion layers; image_index == arange(B) is the path without the key.  cls_only: the caller reads `multi_modal_cls_feats` alone (the VQA and ITM heads): the last fusion
         pair then computes only its token-0 rows (ops.CLS_ONLY) and the two full-sequence feature entries are left out of the
         result.  Attention maps (output_attentions) and deterministic mode keep the full computation."""
         if self.store is None:
             raise RuntimeError("call finalize(device) before the first forward")
         ret = dict()
+        dedup = batch.get("image_index") is not None
+        if dedup and (mask_image or img is not None):
+            raise ValueError('batch["image_index"] (one image row per DISTINCT image) cannot be combined with '
+                             f'{"mask_image=True" if mask_image else "an explicit img= argument"}: that path reads the image '
+                             'pixels per sample; pass the expanded [B, 3, H, W] images without the key')
         if img is None:
             img_key = f"image_{image_token_type_idx - 1}" if f"image_{image_token_type_idx - 1}" in batch else "image"
             img = batch[img_key][0]
         do_mlm = "_mlm" if mask_text else ""
         text_ids = batch[f"text_ids{do_mlm}"]
+        groups = self._image_groups(batch, img, text_ids.shape[0]) if dedup else None
         text_labels = batch[f"text_labels{do_mlm}"]
         text_masks = batch["text_masks"]
         dt = self._dtype
@@ -300,6 +324,10 @@ class M3AETransformerSS(_Base):
             v = self.vision_encoder(img, dt)
         v = ops.linear(v, self.multi_modal_vision_proj.weight, self.multi_modal_vision_proj.bias,
                        extra_bias=type_emb[image_token_type_idx])
+        if groups is not None and not groups.identity:
+            # the tower and the projection ran on the U distinct images: [U, L, D] -> [B, L, D] on this (the image-side) stream,
+            # before the fusion layers; one autograd node, whose backward adds the samples' gradients per image in a fixed order
+            v = ops.expand_samples(v, groups)
         # == Text Encoding (m3ae_module.py:229-236) ==
         # The two towers are independent until the fusion layers.  The reference runs the text tower first; here it runs SECOND, so
         # that autograd (latest-created nodes first) runs its short backward FIRST: the 154-MB word-embedding gradient is then
@@ -356,6 +384,8 @@ class M3AETransformerSS(_Base):
             "extended_text_masks": mt,
             "multi_modal_cls_feats": cls,
         })
+        if dedup:   # ("images" stays the [U, 3, H, W] tensor that was passed in)
+            ret["image_index"] = batch["image_index"]
         if not live:   # (live: x and y are the token-0 rows alone; a consumer that needs the sequences fails on the missing key)
             ret["multi_modal_text_feats"], ret["multi_modal_image_feats"] = x, y
         if mask_image:  # only MIM needs it (the reference recomputes it on every call, m3ae_module.py:301)

@@ -54,8 +54,17 @@ def mim_targets(pl_module, images):
     return ops.mim_targets(images, cfg["patch_size"], cfg["norm_pix_loss"])
 
 
+def _needs_per_sample_images(name, batch):
+    """compute_mim / compute_itm read image pixels sample by sample: a de-duplicated batch (infer's `image_index`) would be
+    mis-indexed, so it is refused here."""
+    if batch.get("image_index") is not None:
+        raise ValueError(f'{name} reads the image pixels per sample and does not take batch["image_index"] (one image row per '
+                         'distinct image): build the batch with image_dedup=False')
+
+
 def compute_mim(pl_module, batch):
     """objectives.py:41-62."""
+    _needs_per_sample_images("compute_mim", batch)
     infer = pl_module.infer(batch, mask_text=False, mask_image=True)
     layer_idx = pl_module.hparams.config["mim_layer"]
     feats = infer["multi_modal_image_feats"] if layer_idx == -1 else infer[f"multi_modal_image_feats_{layer_idx}"]
@@ -68,6 +77,7 @@ def compute_mim(pl_module, batch):
 def compute_itm(pl_module, batch, itm_labels=None):
     """objectives.py:79-101.  `itm_labels` (0/1 per sample) may be supplied for reproducibility; default is the
     reference's random half/half permutation."""
+    _needs_per_sample_images("compute_itm", batch)
     n = batch["text_ids"].shape[0]
     dev = batch["text_ids"].device
     if itm_labels is None:

@@ -1765,6 +1765,101 @@ def gather_rows(src, flat_idx):
     return GatherRowsFn.apply(src, flat_idx)
 
 
+# ----------------------------------------------------------------------------------------------------------
+# de-duplicated image batches (batch["image_index"]): one image-tower pass per distinct image, expanded to the samples
+# ----------------------------------------------------------------------------------------------------------
+class ImageGroups:
+    """The index tables of a de-duplicated image batch, as the two kernels read them: `index` int64 [B] (sample b uses image
+    index[b]) and the samples of every image as a CSR -- `offsets` int64 [U + 1], `members` int64 [B], each image's samples in
+    ascending order.  `identity`: index == arange(B) with U == B (nothing to expand).  Built on the host by `image_groups`;
+    `to(device)` uploads the three tables without blocking when they are pinned."""
+
+    __slots__ = ("index", "offsets", "members", "n_images", "identity")
+
+    def __init__(self, index, offsets, members, n_images, identity):
+        self.index, self.offsets, self.members, self.n_images, self.identity = index, offsets, members, n_images, identity
+
+    @property
+    def n_samples(self):
+        return self.index.numel()
+
+    def tensors(self):
+        return self.index, self.offsets, self.members
+
+    def to(self, device):
+        return ImageGroups(*(t.to(device, non_blocking=True) for t in self.tensors()), self.n_images, self.identity)
+
+
+def image_groups(image_index, n_images=None, pin=True):
+    """Host tables for `batch["image_groups"]` from a CPU `image_index` (any int sequence / tensor, [B]); pinned when a GPU is
+    there so that `.to(device)` does not block.  n_images: rows of the image tensor (default: the largest index + 1).  Raises
+    ValueError for an index outside [0, n_images) and for an image row that no sample uses."""
+    import numpy as np
+    if isinstance(image_index, torch.Tensor):
+        if image_index.is_cuda:
+            raise ValueError("image_groups builds its tables on the host: pass image_index.cpu()")
+        image_index = image_index.numpy()
+    idx = np.asarray(image_index)
+    if idx.ndim != 1 or idx.size == 0 or idx.dtype.kind not in "iu":
+        raise ValueError(f"image_index must be a non-empty 1-D integer array, got shape {idx.shape} dtype {idx.dtype}")
+    idx = idx.astype(np.int64)
+    U = int(idx.max()) + 1 if n_images is None else int(n_images)
+    if idx.min() < 0 or idx.max() >= U:
+        raise ValueError(f"image_index has values outside [0, {U}): min {idx.min()}, max {idx.max()}")
+    counts = np.bincount(idx, minlength=U)
+    if (counts == 0).any():
+        raise ValueError(f"image rows {np.flatnonzero(counts == 0).tolist()} are used by no sample (image_index must cover "
+                         f"every row of the [{U}, ...] image tensor)")
+    offsets = np.zeros(U + 1, dtype=np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    members = np.argsort(idx, kind="stable").astype(np.int64)   # per image, its samples in ascending order
+    identity = U == idx.size and bool((idx == np.arange(U)).all())
+    ts = [torch.from_numpy(a) for a in (idx, offsets, members)]
+    if pin and torch.cuda.is_available():
+        ts = [t.pin_memory() for t in ts]
+    return ImageGroups(*ts, U, identity)
+
+
+class ExpandSamplesFn(Function):
+    """out[b] = x[index[b]] over whole [L, D] blocks (m3ae_expand_samples); backward: the ordered per-image sum of the samples'
+    gradients (m3ae_segment_sum_rows: fp32 adds in ascending sample order, one rounding; no atomics, so deterministic mode takes
+    the same kernel)."""
+
+    @staticmethod
+    def forward(ctx, x, groups):
+        xc = x.contiguous()
+        U, B = xc.shape[0], groups.n_samples
+        R = xc.numel() // U
+        out = torch.empty((B, *xc.shape[1:]), dtype=xc.dtype, device=xc.device)
+        check(_lib.lib().m3ae_expand_samples(_p(xc), _p(groups.index), _p(out), B, U, R, _dt(xc), _stream()),
+              "m3ae_expand_samples")
+        ctx.groups, ctx.in_shape = groups, xc.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        g, d = ctx.groups, dout.contiguous()
+        U = ctx.in_shape[0]
+        dx = torch.empty(ctx.in_shape, dtype=d.dtype, device=d.device)
+        check(_lib.lib().m3ae_segment_sum_rows(_p(d), _p(g.offsets), _p(g.members), _p(dx), U, g.n_samples, dx.numel() // U,
+                                               _dt(d), _stream()), "m3ae_segment_sum_rows")
+        return dx, None
+
+
+def expand_samples(x, groups):
+    """x [U, ...] -> [B, ...] by `groups` (an ImageGroups on x's device): sample b gets x[groups.index[b]].  One autograd node."""
+    _need_cuda(x)
+    if x.shape[0] != groups.n_images:
+        raise ValueError(f"expand_samples: {x.shape[0]} rows for tables of {groups.n_images} images")
+    for t in groups.tensors():
+        if t.device != x.device or t.dtype != torch.int64 or not t.is_contiguous():
+            raise ValueError("expand_samples: the group tables must be contiguous int64 tensors on the input's device "
+                             "(ops.image_groups(...).to(device))")
+    if groups.offsets.numel() != groups.n_images + 1 or groups.members.numel() != groups.n_samples:
+        raise ValueError("expand_samples: inconsistent group tables")
+    return ExpandSamplesFn.apply(x, groups)
+
+
 class DropoutFn(Function):
     """nn.Dropout as a standalone op (RoBERTa embeddings, HF RobertaEmbeddings.dropout; m3ae_module.py:230)."""
 

@@ -22,7 +22,8 @@ arithmetic around `training_step`:
 Data: `data_root=<dir with vqa_vqa_rad_{train,val,test}.arrow>` runs the arrow input pipeline (m3ae_amd/data.py, SURVEY
 8f-2: host decode + bicubic resize in a thread pool, pinned uint8 upload on a side stream, ToTensor + Normalize on
 the GPU; with `image_transform=device` the resize and the crop run on the GPU too, from the decoded bytes, and give
-bit-identical batches); `data_root=synthetic` (or empty) selects `SyntheticDataModule`, which serves deterministic batches with the
+bit-identical batches; with `image_dedup=True` a batch carries each distinct image once and the image tower runs once per distinct
+image); `data_root=synthetic` (or empty) selects `SyntheticDataModule`, which serves deterministic batches with the
 same collate schema (base_dataset.py:165-228).
 """
 import json
@@ -328,6 +329,9 @@ def run(argv, head="cls", tokenizer=None):
                          f"process per GPU with `python -m torch.distributed.run --nproc-per-node {expect} ...`")
     if cfg["per_gpu_batchsize"] <= 0:
         raise SystemExit("per_gpu_batchsize must be set (run_scripts/*.sh pass it explicitly)")
+    if cfg.get("image_dedup") and any(cfg["loss_names"].get(k, 0) > 0 for k in ("mim", "itm")):
+        raise SystemExit("image_dedup=True cannot be combined with the mim / itm objectives: they read the image pixels per "
+                         "sample (loss_names: " + ", ".join(k for k, v in cfg["loss_names"].items() if v > 0) + ")")
     torch.manual_seed(cfg["seed"])  # pl.seed_everything (main.py:19)
     root = cfg["data_root"]
     model = build_model(cfg, head, dev)

@@ -32,6 +32,7 @@ DET_ENTRIES = ("m3ae_gemm_det_workspace_bytes", "m3ae_gemm_det", "m3ae_det_works
                "m3ae_layernorm_bwd_det", "m3ae_layernorm_bwd_drop_det", "m3ae_roberta_embed_bwd_det", "m3ae_bce_logits_det",
                "m3ae_xent_det", "m3ae_mim_loss_fwd_det")
 IMAGE_ENTRIES = ("m3ae_image_resample_workspace_bytes", "m3ae_image_resample_u8")
+SAMPLES_ENTRIES = ("m3ae_expand_samples", "m3ae_segment_sum_rows")
 ROWS_ENTRIES = ("m3ae_gemm_rows", "m3ae_attn_fwd_rows", "m3ae_attn_bwd_rows", "m3ae_layernorm_bwd_drop_rows", "m3ae_dropout_rows")
 
 
@@ -73,6 +74,11 @@ def block():
     out.append("")
     out.append("# dropout row map (ABI 4, additive): mask row = row_base + row * row_step, (row_base, row_step) before the stream")
     for name in ROWS_ENTRIES:
+        res, args = _lib._SIGS[name]
+        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
+    out.append("")
+    out.append("# de-duplicated image batches (ABI 4, additive): out[b] = in[src[b]] over whole rows, and the ordered per-image sum back")
+    for name in SAMPLES_ENTRIES:
         res, args = _lib._SIGS[name]
         out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
     out.append("```")
