@@ -311,6 +311,23 @@ int m3ae_layernorm_bwd_drop_rows(const void* dy, const void* x, const float* gam
                                  const float* rstd, void* dx, void* dx_drop, float dropout_p, uint64_t dropout_seed,
                                  const void* dropout_salt, float* dgamma, float* dbeta, float* workspace, int64_t M, int64_t D,
                                  int dtype, int64_t row_base, int64_t row_step, void* stream);
+/* fp32 residual stream of a bf16 model (ABI 4, additive): the LayerNorm between fp32 rows and bf16 GEMM operands, plain LayerNorm
+ * only (no activation, no RMS mode), D % 4 == 0, D <= 2048; x / dx / dx_add 16-byte aligned, the bf16 arrays 8-byte aligned
+ * (M3AE_ERR_ALIGN otherwise).
+ * fwd_mixed: x fp32 [M][D] -> y bf16 [M][D] = rne_bf16 of what m3ae_layernorm_fwd (M3AE_F32) writes for x, from the same fp32
+ *   arithmetic in the same order; mean / rstd are that call's, bit for bit.
+ * bwd_mixed: dy bf16 (what a dgrad GEMM wrote), x fp32 (the saved stream), dx_add fp32 (the stream's gradient, may be NULL) ->
+ *   dx fp32 = what m3ae_layernorm_bwd (M3AE_F32) writes for the widened dy, and, when dx_lo is not NULL, dx_lo bf16 =
+ *   rne_bf16(dx) in the same pass (the operand of the GEMMs below).  dgamma / dbeta / workspace as for m3ae_layernorm_bwd;
+ *   _det folds them in the fixed order of m3ae_layernorm_bwd_det. */
+int m3ae_layernorm_fwd_mixed(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
+                             int64_t M, int64_t D, float eps, void* stream);
+int m3ae_layernorm_bwd_mixed(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                             float* dx, const float* dx_add, void* dx_lo, float* dgamma, float* dbeta, float* workspace,
+                             int64_t M, int64_t D, void* stream);
+int m3ae_layernorm_bwd_mixed_det(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                                 float* dx, const float* dx_add, void* dx_lo, float* dgamma, float* dbeta, float* workspace,
+                                 int64_t M, int64_t D, void* stream);
 /* out = dropout(x) on a dense [rows][cols] array with the library's counter-hash mask (forward and backward are
  * the same map).  Every dropout site of the library -- this call, the GEMM epilogue (rows = M, cols = N), the
  * LayerNorm backward second output, and attention probabilities (rows = (b*H + h)*Lq + q, cols = Lk) -- uses the mask

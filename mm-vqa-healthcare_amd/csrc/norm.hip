@@ -8,6 +8,7 @@
 #include "common.h"
 #include "det_fold.h"
 #include "launch.h"
+#include <type_traits>
 
 namespace {
 
@@ -42,8 +43,10 @@ template <> DEVINL void st4<bf16_t>(bf16_t* p, const float* x) {
     *(u32x2*)p = (u32x2){pack2bf(x[0], x[1]), pack2bf(x[2], x[3])};
 }
 
-template <typename T, int CPL>
-__global__ __launch_bounds__(256) void ln_fwd_kernel(const T* x, const float* gamma, const float* beta, T* y,
+// TO: the type of the output rows.  TO = bf16 with T = float is the fp32 residual stream of a bf16 model (the row is read in
+// fp32, normalised by this very arithmetic and rounded once, to nearest even, into a GEMM operand).
+template <typename T, int CPL, typename TO = T>
+__global__ __launch_bounds__(256) void ln_fwd_kernel(const T* x, const float* gamma, const float* beta, TO* y,
                                                      float* mean_o, float* rstd_o, int64_t M, int D, float eps,
                                                      int act, int rms) {
     const int lane = threadIdx.x & 63;
@@ -100,7 +103,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* x, const float* ga
             if (mean_o) mean_o[row] = mean;
             if (rstd_o) rstd_o[row] = rstd;
         }
-        T* yr = y + row * D;
+        TO* yr = y + row * D;
 #pragma unroll
         for (int c = 0; c < CPL; ++c) {
             const int ch = lane + c * 64;
@@ -110,7 +113,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const T* x, const float* ga
                 if (beta) ld4<float>(beta + ch * 4, b);
 #pragma unroll
                 for (int t = 0; t < 4; ++t) o[t] = act_fwd((v[c][t] - mean) * rstd * g[t] + b[t], act);
-                st4<T>(yr + ch * 4, o);
+                st4<TO>(yr + ch * 4, o);
             }
         }
     }
@@ -196,11 +199,14 @@ __global__ __launch_bounds__(256) void ln_fwd_pair_kernel(const bf16_t* x, const
     }
 }
 
-template <typename T, int CPL, bool ACT>
-__global__ __launch_bounds__(256) void ln_bwd_kernel(const T* dy, const T* x, const float* gamma, const float* beta,
+// TD: the type of dy.  TD = bf16 with T = float is the fp32 residual stream of a bf16 model: dy is what a dgrad GEMM wrote, x /
+// dx / dx_add are the stream and its gradient, and dx_lo (that form only, may be null) receives dx rounded to bf16 in the same
+// pass -- the operand of the GEMMs below this LayerNorm.
+template <typename T, int CPL, bool ACT, typename TD = T>
+__global__ __launch_bounds__(256) void ln_bwd_kernel(const TD* dy, const T* x, const float* gamma, const float* beta,
                                                      const float* mean_i, const float* rstd_i, T* dx, const T* dx_add,
                                                      float* part, int64_t M, int D, int act, int rms, T* dx_drop,
-                                                     DropState drop) {
+                                                     DropState drop, bf16_t* dx_lo) {
     if (dx_drop) drop_resolve(drop);
     extern __shared__ float red[];  // [4 waves][2][D]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -223,7 +229,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* dy, const T* x, co
     // and the stores of a row run under the next row's HBM latency.
     const int64_t stride = (int64_t)gridDim.x * 4;
     int64_t row = (int64_t)blockIdx.x * 4 + wave;
-    Raw4<T> xr[CPL], dr[CPL];
+    Raw4<T> xr[CPL];
+    Raw4<TD> dr[CPL];
     float mean_n = 0.f, rstd_n = 0.f;
     if (row < M) {
 #pragma unroll
@@ -297,6 +304,9 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* dy, const T* x, co
                     for (int t = 0; t < 4; ++t) o[t] += e[t];
                 }
                 st4<T>(dx + row * D + ch * 4, o);
+                if constexpr (!std::is_same<TD, T>::value) {
+                    if (dx_lo) st4<bf16_t>(dx_lo + row * D + ch * 4, o);
+                }
             }
         }
     }
@@ -370,38 +380,56 @@ template <typename K> int resident_blocks(K kernel, size_t lds) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) != hipSuccess || per_cu <= 0) return 1 << 30;
     return per_cu * device_cus();
 }
-template <typename T, int CPL>
+template <typename T, int CPL, typename TO = T>
 int launch_fwd(const void* x, const float* g, const float* b, void* y, float* mean, float* rstd, int64_t M, int D,
                float eps, int act, int rms, hipStream_t s) {
-    static const int cap = resident_blocks(ln_fwd_kernel<T, CPL>, 0);
+    static const int cap = resident_blocks(ln_fwd_kernel<T, CPL, TO>, 0);
     const int64_t want = cdiv(M, 4);
-    hipLaunchKernelGGL((ln_fwd_kernel<T, CPL>), dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, s, (const T*)x, g, b,
-                       (T*)y, mean, rstd, M, D, eps, act, rms);
+    hipLaunchKernelGGL((ln_fwd_kernel<T, CPL, TO>), dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, s, (const T*)x, g, b,
+                       (TO*)y, mean, rstd, M, D, eps, act, rms);
     return hip_launch_status();
 }
-template <typename T, int CPL>
+template <typename T, int CPL, typename TD = T>
 int launch_bwd(const void* dy, const void* x, const float* g, const float* b, const float* mean, const float* rstd,
                void* dx, const void* dx_add, float* part, int* nblk_io, int64_t M, int D, int act, int rms, hipStream_t s,
-               void* dx_drop = nullptr, DropState drop = DropState{}) {
+               void* dx_drop = nullptr, DropState drop = DropState{}, void* dx_lo = nullptr) {
     const size_t lds = (size_t)8 * D * sizeof(float);
     static int cap_act = 0, cap_plain = 0, cap_d = -1;   // per instantiation; the LDS size follows D
+    constexpr bool MIXED = !std::is_same<TD, T>::value;   // the fp32-stream form is plain LayerNorm: no ACT instantiation of it
     if (cap_d != D) {
-        cap_act = resident_blocks(ln_bwd_kernel<T, CPL, true>, lds);
-        cap_plain = resident_blocks(ln_bwd_kernel<T, CPL, false>, lds);
+        if constexpr (!MIXED) cap_act = resident_blocks(ln_bwd_kernel<T, CPL, true, TD>, lds);
+        cap_plain = resident_blocks(ln_bwd_kernel<T, CPL, false, TD>, lds);
         cap_d = D;
     }
     const int cap = act != M3AE_ACT_NONE ? cap_act : cap_plain;
     const int nblk = *nblk_io < cap ? *nblk_io : cap;
     *nblk_io = nblk;
-    if (act != M3AE_ACT_NONE)
-        hipLaunchKernelGGL((ln_bwd_kernel<T, CPL, true>), dim3((unsigned)nblk), dim3(256), lds, s,
-                           (const T*)dy, (const T*)x, g, b, mean, rstd, (T*)dx, (const T*)dx_add, part, M, D, act, rms,
-                           (T*)dx_drop, drop);
-    else
-        hipLaunchKernelGGL((ln_bwd_kernel<T, CPL, false>), dim3((unsigned)nblk), dim3(256), lds, s,
-                           (const T*)dy, (const T*)x, g, b, mean, rstd, (T*)dx, (const T*)dx_add, part, M, D, act, rms,
-                           (T*)dx_drop, drop);
+    if constexpr (MIXED) {
+        if (act != M3AE_ACT_NONE) return M3AE_ERR_UNSUPPORTED;
+    }
+    if (act != M3AE_ACT_NONE) {
+        if constexpr (!MIXED)
+            hipLaunchKernelGGL((ln_bwd_kernel<T, CPL, true, TD>), dim3((unsigned)nblk), dim3(256), lds, s,
+                               (const TD*)dy, (const T*)x, g, b, mean, rstd, (T*)dx, (const T*)dx_add, part, M, D, act, rms,
+                               (T*)dx_drop, drop, (bf16_t*)dx_lo);
+    } else
+        hipLaunchKernelGGL((ln_bwd_kernel<T, CPL, false, TD>), dim3((unsigned)nblk), dim3(256), lds, s,
+                           (const TD*)dy, (const T*)x, g, b, mean, rstd, (T*)dx, (const T*)dx_add, part, M, D, act, rms,
+                           (T*)dx_drop, drop, (bf16_t*)dx_lo);
     return hip_launch_status();
+}
+
+// the fp32-stream forms as launchers of the DISPATCH_CPL shape (T = float throughout)
+template <typename T, int CPL>
+int launch_fwd_mixed(const void* x, const float* g, const float* b, void* y, float* mean, float* rstd, int64_t M, int D, float eps,
+                     hipStream_t s) {
+    return launch_fwd<T, CPL, bf16_t>(x, g, b, y, mean, rstd, M, D, eps, M3AE_ACT_NONE, 0, s);
+}
+template <typename T, int CPL>
+int launch_bwd_mixed(const void* dy, const void* x, const float* g, const float* mean, const float* rstd, void* dx, const void* dx_add,
+                     void* dx_lo, float* part, int* nblk_io, int64_t M, int D, hipStream_t s) {
+    return launch_bwd<T, CPL, bf16_t>(dy, x, g, nullptr, mean, rstd, dx, dx_add, part, nblk_io, M, D, M3AE_ACT_NONE, 0, s, nullptr,
+                                      DropState{}, dx_lo);
 }
 
 #define DISPATCH_CPL(FN, T, ...)                                                  \
@@ -531,4 +559,43 @@ extern "C" int m3ae_layernorm_bwd_drop_det(const void* dy, const void* x, const 
                                            float* workspace, int64_t M, int64_t D, int dtype, void* stream) {
     return layernorm_bwd_drop_impl(dy, x, gamma, beta, mean, rstd, dx, dx_drop, dropout_p, dropout_seed, dropout_salt, dgamma, dbeta,
                                    workspace, M, D, dtype, stream, 1);
+}
+
+// fp32 residual stream of a bf16 model: fp32 rows in, bf16 rows out (plain LayerNorm; the arithmetic of the fp32 kernel, rounded once)
+extern "C" int m3ae_layernorm_fwd_mixed(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
+                                        int64_t M, int64_t D, float eps, void* stream) {
+    if (!x || !gamma || !y || M <= 0 || D <= 0) return M3AE_ERR_ARG;
+    if (D % 4 != 0 || D > 2048) return M3AE_ERR_UNSUPPORTED;
+    if (((((uintptr_t)x) | ((uintptr_t)gamma) | ((uintptr_t)beta)) & 15) != 0 || (((uintptr_t)y) & 7) != 0) return M3AE_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    DISPATCH_CPL(launch_fwd_mixed, float, x, gamma, beta, y, mean, rstd, M, (int)D, eps, s);
+}
+
+static int layernorm_bwd_mixed_impl(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                                    float* dx, const float* dx_add, void* dx_lo, float* dgamma, float* dbeta, float* workspace,
+                                    int64_t M, int64_t D, void* stream, int det) {
+    if (!dy || !x || !gamma || !mean || !rstd || !dx || !workspace || M <= 0) return M3AE_ERR_ARG;
+    if (D % 4 != 0 || D > 2048) return M3AE_ERR_UNSUPPORTED;
+    if (((((uintptr_t)x) | ((uintptr_t)dx) | ((uintptr_t)dx_add) | ((uintptr_t)gamma)) & 15) != 0 ||
+        ((((uintptr_t)dy) | ((uintptr_t)dx_lo)) & 7) != 0)
+        return M3AE_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    int nblk = (int)m3ae_layernorm_bwd_blocks(M);
+    auto run = [&]() -> int {
+        DISPATCH_CPL(launch_bwd_mixed, float, dy, x, gamma, mean, rstd, dx, dx_add, dx_lo, workspace, &nblk, M, (int)D, s);
+    };
+    int rc = run();
+    if (rc) return rc;
+    if (!dgamma) return 0;
+    return ln_bwd_fold(workspace, dgamma, dbeta, nblk, (int)D, det, s);
+}
+extern "C" int m3ae_layernorm_bwd_mixed(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                                        float* dx, const float* dx_add, void* dx_lo, float* dgamma, float* dbeta, float* workspace,
+                                        int64_t M, int64_t D, void* stream) {
+    return layernorm_bwd_mixed_impl(dy, x, gamma, mean, rstd, dx, dx_add, dx_lo, dgamma, dbeta, workspace, M, D, stream, 0);
+}
+extern "C" int m3ae_layernorm_bwd_mixed_det(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
+                                            float* dx, const float* dx_add, void* dx_lo, float* dgamma, float* dbeta,
+                                            float* workspace, int64_t M, int64_t D, void* stream) {
+    return layernorm_bwd_mixed_impl(dy, x, gamma, mean, rstd, dx, dx_add, dx_lo, dgamma, dbeta, workspace, M, D, stream, 1);
 }

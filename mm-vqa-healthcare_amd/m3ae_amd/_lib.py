@@ -136,6 +136,10 @@ _SIGS = {
     # sample expansion of a de-duplicated image batch (ABI 4, additive)
     "m3ae_expand_samples": (C.c_int, [vp, vp, vp, i64, i64, i64, C.c_int, vp]),
     "m3ae_segment_sum_rows": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, C.c_int, vp]),
+    # fp32 residual stream of a bf16 model (ABI 4, additive): LayerNorm fp32 rows -> bf16 rows, and its backward
+    "m3ae_layernorm_fwd_mixed": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, f32, vp]),
+    "m3ae_layernorm_bwd_mixed": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp]),
+    "m3ae_layernorm_bwd_mixed_det": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp]),
 }
 
 EXPORTS = tuple(_SIGS)

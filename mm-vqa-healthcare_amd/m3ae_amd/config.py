@@ -55,6 +55,11 @@ DEFAULTS = dict(
     # uploaded and run through the image tower once, and ops.expand_samples hands its tokens to the samples that ask about it
     # (batch["image_index"]).  Same samples, same arithmetic per sample; not available with the mim / itm objectives.
     image_dedup=False,
+    # dtype of the image tower's residual stream in bf16 mode (m3ae_amd/modules/clip_model.py): "bf16" (the stream is rounded at
+    # every join, 2 roundings per block) | "fp32" (stream and its gradient in fp32 from the token assembly to the input of
+    # ln_post, as under the reference's autocast, config.py:146 precision=16; every GEMM and attention operand stays bf16).  No
+    # effect under compute_dtype "fp32" / "fp32x3", whose stream is fp32 already.  Not available with graph.GraphedStep.
+    clip_residual_dtype="bf16",
 )
 
 NAMED = {
@@ -96,9 +101,21 @@ _ARCH_TEXT = {
 }
 
 
+CLIP_RESIDUAL_DTYPES = ("bf16", "fp32")
+
+
+def clip_residual_dtype(cfg):
+    """The validated clip_residual_dtype of a config dict (default "bf16")."""
+    v = cfg.get("clip_residual_dtype", "bf16")
+    if v not in CLIP_RESIDUAL_DTYPES:
+        raise ValueError(f"clip_residual_dtype must be one of {CLIP_RESIDUAL_DTYPES}, got {v!r}")
+    return v
+
+
 def resolve_arch(cfg):
     """Fill vit_width/vit_layers/text_* from the `vit` / `tokenizer` names unless given explicitly."""
     cfg = dict(cfg)
+    clip_residual_dtype(cfg)
     vit = _ARCH_VIT.get(cfg["vit"], _ARCH_VIT["ViT-B/16"])
     for k, v in vit.items():
         cfg.setdefault(k, v)

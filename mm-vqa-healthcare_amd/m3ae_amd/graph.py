@@ -29,6 +29,10 @@ class GraphedStep:
             # a captured step cannot be replayed on the next batch
             raise ValueError('GraphedStep does not take a de-duplicated batch (batch["image_index"]): its static inputs need '
                              'one image row per sample')
+        core = getattr(model, "m3ae", model)   # (the T5 / decoder wrappers hold the model in .m3ae)
+        visual = getattr(getattr(core, "vision_encoder", None), "visual", None)
+        if visual is not None and visual.stream_dtype(core._dtype) != core._dtype:
+            raise ValueError('GraphedStep does not cover clip_residual_dtype="fp32" in bf16 mode: run the step eagerly')
         self.model, self.store, self.batch = model, model.store, batch
         self.max_steps, self.grad_scale = max_steps, grad_scale
         dev = self.store.flat.device

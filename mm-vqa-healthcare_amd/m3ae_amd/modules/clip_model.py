@@ -4,6 +4,8 @@ m3ae/modules/vision_encoders/clip_model.py:27-196 (weights of upstream M3AE / CL
 Pre-LN block = LayerNorm(fp32 stats) -> packed in-proj GEMM -> flash attention -> out-proj GEMM (+residual)
             -> LayerNorm -> GEMM(+bias+QuickGELU) -> GEMM(+bias+residual).
 Activations stay [B, L, D] (the reference's NLD->LND permutes at clip_model.py:102-104 are layout only).
+With `residual_dtype="fp32"` in bf16 mode the residual stream (tokens, ln_pre, the block joins) and its gradient are fp32 up to
+the input of ln_post, as under the reference's autocast (config.py:146 precision=16); every GEMM / attention operand stays bf16.
 The tower runs `layers - 1` blocks (clip_model.py:71) -- the METER/M3AE quirk the checkpoints depend on.
 """
 from types import SimpleNamespace as NS
@@ -13,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..config import clip_residual_dtype
 
 
 class LayerNorm(nn.LayerNorm):
@@ -60,11 +63,14 @@ class ResidualAttentionBlock(nn.Module):
         return ops.ClipBlockFn.apply(x, self._bp, *self._anchors)
 
     def forward_unfused(self, x):
-        h = ops.layer_norm(x, self.ln_1.weight, self.ln_1.bias, self.ln_1.eps)
+        """The op-level composition of ClipBlockFn.  An fp32 x over bf16 weight copies is the fp32 residual stream: the LayerNorms
+        write the operands' dtype, the two residual joins stay in x's."""
+        lo = ops.compute_weight(self.attn.in_proj_weight).dtype
+        h = ops.layer_norm(x, self.ln_1.weight, self.ln_1.bias, self.ln_1.eps, out_dtype=lo)
         qkv = ops.linear(h, self.attn.in_proj_weight, self.attn.in_proj_bias)
         ctx = ops.self_attention(qkv, None, self.attn.num_heads)
         x = ops.linear(ctx, self.attn.out_proj.weight, self.attn.out_proj.bias, residual=x)
-        h = ops.layer_norm(x, self.ln_2.weight, self.ln_2.bias, self.ln_2.eps)
+        h = ops.layer_norm(x, self.ln_2.weight, self.ln_2.bias, self.ln_2.eps, out_dtype=lo)
         return ops.mlp(h, self.mlp.c_fc.weight, self.mlp.c_fc.bias, self.mlp.c_proj.weight, self.mlp.c_proj.bias,
                        ops.ACT_QUICKGELU, residual=x)
 
@@ -95,8 +101,9 @@ class Transformer(nn.Module):
 class VisualTransformer(nn.Module):
     """clip_model.py:79-128."""
 
-    def __init__(self, patch_size, width, layers, heads, resolution_after):
+    def __init__(self, patch_size, width, layers, heads, resolution_after, residual_dtype="bf16"):
         super().__init__()
+        self.residual_dtype = clip_residual_dtype({"clip_residual_dtype": residual_dtype})   # (raises on any other value)
         self.conv1 = nn.Conv2d(3, width, kernel_size=patch_size, stride=patch_size, bias=False)
         scale = width ** -0.5
         self.class_embedding = nn.Parameter(scale * torch.randn(width))
@@ -105,17 +112,24 @@ class VisualTransformer(nn.Module):
         self.transformer = Transformer(width, layers, heads)
         self.ln_post = LayerNorm(width)
 
-    def forward_patch_embed(self, x, dtype):
-        return ops.vit_tokens(x, self.conv1.weight, self.class_embedding, self.positional_embedding, dtype, add_pos=False)
+    def stream_dtype(self, dtype):
+        """The residual stream's dtype for compute dtype `dtype` (fp32 compute: the stream is fp32 whatever the key says)."""
+        return torch.float32 if self.residual_dtype == "fp32" else dtype
 
-    def forward_trans(self, x):
+    def forward_patch_embed(self, x, dtype):
+        return ops.vit_tokens(x, self.conv1.weight, self.class_embedding, self.positional_embedding, dtype, add_pos=False,
+                              out_dtype=self.stream_dtype(dtype))
+
+    def forward_trans(self, x, dtype=None):
+        """x in the stream's dtype; dtype: the compute dtype ln_post writes (default: x's)."""
         x = ops.layer_norm(x, self.ln_pre.weight, self.ln_pre.bias, self.ln_pre.eps)
         x = self.transformer(x)
-        return ops.layer_norm(x, self.ln_post.weight, self.ln_post.bias, self.ln_post.eps)
+        return ops.layer_norm(x, self.ln_post.weight, self.ln_post.bias, self.ln_post.eps, out_dtype=dtype)
 
     def forward(self, x, dtype):
-        x = ops.vit_tokens(x, self.conv1.weight, self.class_embedding, self.positional_embedding, dtype, add_pos=True)
-        return self.forward_trans(x)
+        x = ops.vit_tokens(x, self.conv1.weight, self.class_embedding, self.positional_embedding, dtype, add_pos=True,
+                           out_dtype=self.stream_dtype(dtype))
+        return self.forward_trans(x, dtype)
 
     def weight_units(self):
         return [self.conv1.weight] + self.transformer.weight_units()
@@ -126,10 +140,10 @@ class CLIP(nn.Module):
     that state_dict keys match the reference; they never receive a gradient."""
 
     def __init__(self, vision_layers, vision_width, vision_patch_size, resolution_after, context_length=77,
-                 vocab_size=49408, transformer_width=512):
+                 vocab_size=49408, transformer_width=512, residual_dtype="bf16"):
         super().__init__()
         self.visual = VisualTransformer(vision_patch_size, vision_width, vision_layers, vision_width // 64,
-                                        resolution_after)
+                                        resolution_after, residual_dtype)
         self.token_embedding = nn.Embedding(vocab_size, transformer_width)
         self.positional_embedding = nn.Parameter(torch.empty(context_length, transformer_width))
         self.ln_final = LayerNorm(transformer_width)
@@ -155,8 +169,8 @@ class CLIP(nn.Module):
     def forward_patch_embed(self, image, dtype):
         return self.visual.forward_patch_embed(image, dtype)
 
-    def forward_trans(self, x):
-        return self.visual.forward_trans(x)
+    def forward_trans(self, x, dtype=None):
+        return self.visual.forward_trans(x, dtype)
 
     def weight_units(self):
         return self.visual.weight_units()
@@ -185,7 +199,8 @@ def adapt_position_encoding(model, patch_size=32, after=384, suffix="visual.posi
     return model
 
 
-def build_model(name, resolution_after=224, vision_width=768, vision_layers=12, patch_size=16):
+def build_model(name, resolution_after=224, vision_width=768, vision_layers=12, patch_size=16, residual_dtype="bf16"):
     """Counterpart of clip_model.py:259-313 without the URL download: the architecture is given by the config
-    (`m3ae_amd.config.resolve_arch`); weights arrive through `load_state_dict` (checkpoint) or synth init."""
-    return CLIP(vision_layers, vision_width, patch_size, resolution_after)
+    (`m3ae_amd.config.resolve_arch`); weights arrive through `load_state_dict` (checkpoint) or synth init.
+    residual_dtype: the config's clip_residual_dtype."""
+    return CLIP(vision_layers, vision_width, patch_size, resolution_after, residual_dtype=residual_dtype)

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..config import resolve_arch
+from ..config import clip_residual_dtype, resolve_arch
 from ..param_store import ParamStore
 from . import objectives, prediction_heads
 from .bert_model import BertCrossLayer, RobertaModel
@@ -88,7 +88,8 @@ class M3AETransformerSS(_Base):
             raise NotImplementedError("swin backbones are unreachable in the reference (SURVEY 2 #14)")
         # == 1. Build Models (m3ae_module.py:21-89) ==
         self.vision_encoder = build_model(cfg["vit"], resolution_after=cfg["image_size"], vision_width=cfg["vit_width"],
-                                          vision_layers=cfg["vit_layers"], patch_size=cfg["patch_size"])
+                                          vision_layers=cfg["vit_layers"], patch_size=cfg["patch_size"],
+                                          residual_dtype=clip_residual_dtype(cfg))
         self.language_encoder = RobertaModel(cfg["vocab_size"], cfg["text_hidden"], cfg["text_layers"],
                                              cfg["text_heads"], cfg["text_inter"], cfg["text_max_pos"])
         self.multi_modal_language_proj = nn.Linear(cfg["input_text_embed_size"], hs)
@@ -318,7 +319,7 @@ class M3AETransformerSS(_Base):
             v = self.vision_encoder.forward_patch_embed(img, dt)
             v, mim_masks, mim_ids_restore = self.random_masking(v, self.hparams.config["mim_prob"],
                                                                 batch.get("mim_noise"))
-            v = self.vision_encoder.forward_trans(v)
+            v = self.vision_encoder.forward_trans(v, dt)
             ret["mim_masks"], ret["mim_ids_restore"] = mim_masks, mim_ids_restore
         else:
             v = self.vision_encoder(img, dt)

@@ -445,6 +445,17 @@ def add(a, b, out=None):
     return out
 
 
+def cast(x, dtype):
+    """x in `dtype` on the library's streaming cast (fp32 -> bf16 rounds to nearest even); x itself when it already is."""
+    if x.dtype == dtype:
+        return x
+    _need_cuda(x)
+    x = x.contiguous()
+    out = torch.empty_like(x, dtype=dtype)
+    check(_lib.lib().m3ae_cast(_p(x), _p(out), x.numel(), _dt(x), _dt(out), _stream()), "m3ae_cast")
+    return out
+
+
 class Fork2Fn(Function):
     """Identity with two outputs for a tensor that feeds two consumers (a fusion layer's x / y feed the text layer AND the image
     layer of the pair, m3ae_module.py:269-278): the two gradients meet here and are summed by the library's add instead of by
@@ -482,7 +493,9 @@ class LinearFn(Function):
         res2 = None
         if residual is not None:
             res2 = residual.contiguous().view(M, -1)
-        y, pre = mm_nt(x2, ldx, M, w, bias=b, act=act, residual=res2, want_preact=(act != ACT_NONE), alpha=alpha)
+        # a residual of another dtype than x (the fp32 stream of a bf16 CLIP tower) sets the output's dtype: the join stays in it
+        y, pre = mm_nt(x2, ldx, M, w, bias=b, act=act, residual=res2, want_preact=(act != ACT_NONE), alpha=alpha,
+                       out_dtype=None if res2 is None else res2.dtype)
         ctx.save_for_backward(x2, pre)
         ctx.weight, ctx.bias, ctx.act, ctx.ldx, ctx.alpha = weight, bias, act, ldx, alpha
         ctx.x_shape, ctx.has_res = x.shape, residual is not None
@@ -495,7 +508,7 @@ class LinearFn(Function):
     def backward(ctx, dy):
         x2, pre = ctx.saved_tensors
         N = dy.shape[-1]
-        dy2 = dy.contiguous().view(-1, N)
+        dy2 = cast(dy.contiguous().view(-1, N), x2.dtype)   # (a cast only below an fp32 residual join of bf16 operands)
         dres = dy if ctx.has_res else None
         dz = act_bwd(dy2, pre, ctx.act) if ctx.act != ACT_NONE else dy2
         dextra = None
@@ -548,7 +561,7 @@ class MLPFn(Function):
         x2, M, K, ldx = _rows(x)
         g, u = mm_nt(x2, ldx, M, compute_weight(w1), bias=b1, act=act, want_preact=True, preact_grad=SAVE_DACT)
         res2 = residual.contiguous().view(M, -1) if residual is not None else None
-        y, _ = mm_nt(g, g.stride(0), M, compute_weight(w2), bias=b2, residual=res2)
+        y, _ = mm_nt(g, g.stride(0), M, compute_weight(w2), bias=b2, residual=res2, out_dtype=None if res2 is None else res2.dtype)
         ctx.save_for_backward(x2, u, g)
         ctx.p = (w1, b1, w2, b2)
         ctx.act, ctx.ldx, ctx.x_shape, ctx.has_res = act, ldx, x.shape, residual is not None
@@ -558,7 +571,7 @@ class MLPFn(Function):
     def backward(ctx, dy):
         x2, u, g = ctx.saved_tensors
         w1, b1, w2, b2 = ctx.p
-        dy2 = dy.contiguous().view(-1, dy.shape[-1])
+        dy2 = cast(dy.contiguous().view(-1, dy.shape[-1]), g.dtype)
         dres = dy if ctx.has_res else None
         mm_wgrad(dy2, g, g.stride(0), w2, b2)
         du = mm_dgrad(dy2, w2, dact_aux=u, dact=ACT_MULAUX if SAVE_DACT else ctx.act)  # dU = (dY W2) * act'(U), act'(U) saved by the forward
@@ -583,15 +596,20 @@ def mlp(x, w1, b1, w2, b2, act, residual=None):
 # ----------------------------------------------------------------------------------------------------------
 class LayerNormFn(Function):
     @staticmethod
-    def forward(ctx, x, gamma, beta, eps, act, rms):
+    def forward(ctx, x, gamma, beta, eps, act, rms, out_dtype=None):
         xc = x.contiguous()
         D = xc.shape[-1]
         M = xc.numel() // D
-        y = torch.empty_like(xc)
+        y = torch.empty_like(xc, dtype=out_dtype or xc.dtype)
         mean = torch.empty(M, dtype=torch.float32, device=x.device)
         rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-        check(_lib.lib().m3ae_layernorm_fwd(_p(xc), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), M, D, eps, _dt(xc),
-                                            act, int(rms), _stream()), "m3ae_layernorm_fwd")
+        if y.dtype != xc.dtype:   # fp32 rows -> bf16 rows (the fp32 residual stream of a bf16 CLIP tower)
+            _ln_mixed_ok(xc, y, act, rms)
+            check(_lib.lib().m3ae_layernorm_fwd_mixed(_p(xc), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), M, D, eps, _stream()),
+                  "m3ae_layernorm_fwd_mixed")
+        else:
+            check(_lib.lib().m3ae_layernorm_fwd(_p(xc), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), M, D, eps, _dt(xc),
+                                                act, int(rms), _stream()), "m3ae_layernorm_fwd")
         ctx.save_for_backward(xc, mean, rstd)
         ctx.gamma, ctx.beta, ctx.act, ctx.rms = gamma, beta, act, rms
         return y
@@ -608,35 +626,54 @@ class LayerNormFn(Function):
         ws = torch.empty(2 * nblk * D, dtype=torch.float32, device=xc.device)
         gg = _grad_buf(ctx.gamma)
         gb = _grad_buf(ctx.beta) if ctx.beta is not None else None
-        ln_bwd = L.m3ae_layernorm_bwd_det if _DETERMINISTIC else L.m3ae_layernorm_bwd
-        check(ln_bwd(_p(dyc), _p(xc), _p(ctx.gamma), _p(ctx.beta), _p(mean), _p(rstd), _p(dx), None,
-                     _p(gg), _p(gb), _p(ws), M, D, _dt(xc), ctx.act, int(ctx.rms), _stream()),
-              "m3ae_layernorm_bwd")
+        if dyc.dtype != xc.dtype:
+            ln_bwd = L.m3ae_layernorm_bwd_mixed_det if _DETERMINISTIC else L.m3ae_layernorm_bwd_mixed
+            check(ln_bwd(_p(dyc), _p(xc), _p(ctx.gamma), _p(mean), _p(rstd), _p(dx), None, None, _p(gg), _p(gb), _p(ws), M, D,
+                         _stream()), "m3ae_layernorm_bwd_mixed")
+        else:
+            ln_bwd = L.m3ae_layernorm_bwd_det if _DETERMINISTIC else L.m3ae_layernorm_bwd
+            check(ln_bwd(_p(dyc), _p(xc), _p(ctx.gamma), _p(ctx.beta), _p(mean), _p(rstd), _p(dx), None,
+                         _p(gg), _p(gb), _p(ws), M, D, _dt(xc), ctx.act, int(ctx.rms), _stream()),
+                  "m3ae_layernorm_bwd")
         _done(ctx.gamma)
         _done(ctx.beta)
-        return dx, None, None, None, None, None
+        return dx, None, None, None, None, None, None
 
 
-def layer_norm(x, gamma, beta, eps, act=ACT_NONE, rms=False):
-    return LayerNormFn.apply(x, gamma, beta, eps, act, rms)
+def layer_norm(x, gamma, beta, eps, act=ACT_NONE, rms=False, out_dtype=None):
+    """out_dtype=torch.bfloat16 on fp32 rows: the LayerNorm between an fp32 residual stream and bf16 GEMM operands (the fp32
+    kernel's arithmetic, rounded once; its backward takes the bf16 gradient and returns the fp32 one)."""
+    return LayerNormFn.apply(x, gamma, beta, eps, act, rms, out_dtype)
+
+
+def _ln_mixed_ok(x, y, act, rms):
+    if not (x.dtype == torch.float32 and y.dtype == torch.bfloat16 and act == ACT_NONE and not rms):
+        raise _lib.M3AEHipError(f"LayerNorm from {x.dtype} rows to {y.dtype} rows: only plain LayerNorm from float32 to bfloat16 "
+                                "has a kernel")
 
 
 # ----------------------------------------------------------------------------------------------------------
 # raw LayerNorm helpers (no autograd) for the fused block functions
 # ----------------------------------------------------------------------------------------------------------
-def ln_fwd_raw(x2, ln, act=ACT_NONE, rms=False):
+def ln_fwd_raw(x2, ln, act=ACT_NONE, rms=False, out_dtype=None):
     M, D = x2.shape
-    y = torch.empty_like(x2)
+    y = torch.empty_like(x2, dtype=out_dtype or x2.dtype)
     mean = None if rms else torch.empty(M, dtype=torch.float32, device=x2.device)
     rstd = torch.empty(M, dtype=torch.float32, device=x2.device)
+    if y.dtype != x2.dtype:
+        _ln_mixed_ok(x2, y, act, rms)
+        check(_lib.lib().m3ae_layernorm_fwd_mixed(_p(x2), _p(ln.weight), _p(ln.bias), _p(y), _p(mean), _p(rstd), M, D, ln.eps,
+                                                  _stream()), "m3ae_layernorm_fwd_mixed")
+        return y, mean, rstd
     check(_lib.lib().m3ae_layernorm_fwd(_p(x2), _p(ln.weight), _p(ln.bias), _p(y), _p(mean), _p(rstd), M, D, ln.eps,
                                         _dt(x2), act, int(rms), _stream()), "m3ae_layernorm_fwd")
     return y, mean, rstd
 
 
-def ln_bwd_raw(dy, x2, ln, mean, rstd, dx_add=None, act=ACT_NONE, rms=False, drop=None, rows=None):
+def ln_bwd_raw(dy, x2, ln, mean, rstd, dx_add=None, act=ACT_NONE, rms=False, drop=None, rows=None, want_lo=False):
     """dx = LN'(dy) (+ dx_add); ln.weight.grad / ln.bias.grad accumulate in place.  With drop = (p, seed) returns
-    (dx, dx_drop): dx_drop is dx under the dropout mask of the dense layer that fed this LayerNorm."""
+    (dx, dx_drop): dx_drop is dx under the dropout mask of the dense layer that fed this LayerNorm.  bf16 dy on fp32 x2 (the
+    fp32 residual stream of a bf16 CLIP tower): dx and dx_add are fp32, and want_lo returns (dx, dx rounded to bf16)."""
     M, D = x2.shape
     L = _lib.lib()
     dx = torch.empty_like(x2)
@@ -664,13 +701,23 @@ def ln_bwd_raw(dy, x2, ln, mean, rstd, dx_add=None, act=ACT_NONE, rms=False, dro
             _done(ln.weight)
             _done(ln.bias)
         return dx, dxd
-    ln_bwd = L.m3ae_layernorm_bwd_det if _DETERMINISTIC else L.m3ae_layernorm_bwd
-    check(ln_bwd(_p(dy), _p(x2), _p(ln.weight), _p(ln.bias), _p(mean), _p(rstd), _p(dx), _p(dx_add),
-                 _p(gg), _p(gb), _p(ws), M, D, _dt(x2), act, int(rms), _stream()), "m3ae_layernorm_bwd")
+    dx_lo = None
+    if dy.dtype != x2.dtype:
+        _ln_mixed_ok(x2, dy, act, rms)
+        assert dx_add is None or dx_add.dtype == torch.float32
+        dx_lo = torch.empty_like(dy) if want_lo else None
+        ln_bwd = L.m3ae_layernorm_bwd_mixed_det if _DETERMINISTIC else L.m3ae_layernorm_bwd_mixed
+        check(ln_bwd(_p(dy), _p(x2), _p(ln.weight), _p(mean), _p(rstd), _p(dx), _p(dx_add), _p(dx_lo), _p(gg), _p(gb), _p(ws), M, D,
+                     _stream()), "m3ae_layernorm_bwd_mixed")
+    else:
+        assert not want_lo
+        ln_bwd = L.m3ae_layernorm_bwd_det if _DETERMINISTIC else L.m3ae_layernorm_bwd
+        check(ln_bwd(_p(dy), _p(x2), _p(ln.weight), _p(ln.bias), _p(mean), _p(rstd), _p(dx), _p(dx_add),
+                     _p(gg), _p(gb), _p(ws), M, D, _dt(x2), act, int(rms), _stream()), "m3ae_layernorm_bwd")
     if train:
         _done(ln.weight)
         _done(ln.bias)
-    return dx
+    return (dx, dx_lo) if want_lo else dx
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -1077,7 +1124,8 @@ def _ffn_core_fwd(x2, P, act, residual, mid_drop=None, out_drop=None, rows=None)
     M, D = x2.shape
     g, u = mm_nt(x2, D, M, compute_weight(P.w1), bias=_bdata(P.b1), act=act, want_preact=True, preact_grad=SAVE_DACT,
                  dropout=mid_drop, rows=rows)
-    y, _ = mm_nt(g, g.shape[1], M, compute_weight(P.w2), bias=_bdata(P.b2), residual=residual, dropout=out_drop, rows=rows)
+    y, _ = mm_nt(g, g.shape[1], M, compute_weight(P.w2), bias=_bdata(P.b2), residual=residual, dropout=out_drop, rows=rows,
+                 out_dtype=None if residual is None else residual.dtype)   # (an fp32 residual stream stays fp32 through the join)
     return y, u, g
 
 
@@ -1331,17 +1379,24 @@ class BertSelfLayerFn(Function):
 
 
 class ClipBlockFn(Function):
-    """ResidualAttentionBlock.forward (clip_model.py:60-63), pre-LN: x += MHA(LN1(x)); x += MLP(LN2(x))."""
+    """ResidualAttentionBlock.forward (clip_model.py:60-63), pre-LN: x += MHA(LN1(x)); x += MLP(LN2(x)).
+
+    fp32 residual stream (clip_residual_dtype="fp32" in bf16 mode): x arrives in fp32 while the weights' compute copies are bf16.
+    The two LayerNorms then read fp32 rows and write the bf16 GEMM operands, the two joins (out-proj and fc2 epilogues) add the
+    fp32 stream and write fp32, and the backward carries the stream's gradient in fp32: one cast of the incoming dy for the fc2
+    wgrad / dgrad, and LN2's backward hands the out-proj GEMMs their bf16 operand from the same pass.  Every GEMM and attention
+    operand is bf16 as in the bf16 stream; x in the weights' dtype is the path of before, launch for launch."""
 
     @staticmethod
     def forward(ctx, x, P, *anchors):
         B, L, D = x.shape
         M = B * L
         x2 = x.contiguous().view(M, D)
-        h1, m1, r1 = ln_fwd_raw(x2, P.ln1)
+        lo = compute_weight(P.w_qkv).dtype   # the GEMM operands' dtype; x2.dtype is the stream's
+        h1, m1, r1 = ln_fwd_raw(x2, P.ln1, out_dtype=lo)
         o, lse, proj = _attn_core_fwd(h1, B, P)
-        xa, _ = mm_nt(o.view(M, D), D, M, compute_weight(P.w_o), bias=_bdata(P.b_o), residual=x2)
-        h2, m2, r2 = ln_fwd_raw(xa, P.ln2)
+        xa, _ = mm_nt(o.view(M, D), D, M, compute_weight(P.w_o), bias=_bdata(P.b_o), residual=x2, out_dtype=x2.dtype)
+        h2, m2, r2 = ln_fwd_raw(xa, P.ln2, out_dtype=lo)
         y, u, g = _ffn_core_fwd(h2, P, ACT_QUICKGELU, xa)
         ctx.saved = (x2, m1, r1, h1, proj, o, lse, xa, m2, r2, h2, u, g)
         ctx.P, ctx.dims, ctx.n_anchor = P, (B, L, D), len(anchors)
@@ -1355,12 +1410,16 @@ class ClipBlockFn(Function):
         ctx.saved = None
         P = ctx.P
         dy2 = dy.contiguous().view(M, D)
-        dh2 = _ffn_core_bwd(dy2, h2, u, g, P, ACT_QUICKGELU)
-        dxa = ln_bwd_raw(dh2, xa, P.ln2, m2, r2, dx_add=dy2)  # + residual branch, fused into LN backward
+        mixed = h2.dtype != xa.dtype   # fp32 stream, bf16 operands
+        dh2 = _ffn_core_bwd(cast(dy2, h2.dtype), h2, u, g, P, ACT_QUICKGELU)
+        if mixed:
+            dxa_s, dxa = ln_bwd_raw(dh2, xa, P.ln2, m2, r2, dx_add=dy2, want_lo=True)   # the stream's gradient and its bf16 rounding
+        else:
+            dxa_s = dxa = ln_bwd_raw(dh2, xa, P.ln2, m2, r2, dx_add=dy2)  # + residual branch, fused into LN backward
         mm_wgrad(dxa, o.view(M, D), D, P.w_o, P.b_o)
         dctx = mm_dgrad(dxa, P.w_o)
         dh1, _ = _attn_core_bwd(dctx, h1, None, proj, o, lse, B, P)
-        dx = ln_bwd_raw(dh1, x2, P.ln1, m1, r1, dx_add=dxa)
+        dx = ln_bwd_raw(dh1, x2, P.ln1, m1, r1, dx_add=dxa_s)
         return (dx.view(B, L, D), None) + (None,) * ctx.n_anchor
 
 
@@ -1563,7 +1622,7 @@ class VitTokensFn(Function):
     (clip_model.py:94-99 / :110-116)."""
 
     @staticmethod
-    def forward(ctx, img, conv_w, cls, pos, dtype, add_pos):
+    def forward(ctx, img, conv_w, cls, pos, dtype, add_pos, out_dtype=None):
         _need_cuda(img)
         L = _lib.lib()
         B, _, R, _ = img.shape
@@ -1574,8 +1633,9 @@ class VitTokensFn(Function):
         patches = torch.empty((B * G, 3 * P * P), dtype=dtype, device=img.device)
         check(L.m3ae_patchify(_p(imgc), _p(patches), B, R, P, _dt(patches), _stream()), "m3ae_patchify")
         w2 = compute_weight(conv_w).view(width, -1)
-        pe, _ = mm_nt(patches, patches.stride(0), B * G, w2)
-        out = torch.empty((B, G + 1, width), dtype=dtype, device=img.device)
+        out_dtype = out_dtype or dtype   # float32 with dtype bfloat16: the fp32 residual stream starts here (bf16 operands, fp32 C)
+        pe, _ = mm_nt(patches, patches.stride(0), B * G, w2, out_dtype=out_dtype)
+        out = torch.empty((B, G + 1, width), dtype=out_dtype, device=img.device)
         posz = pos if add_pos else torch.zeros_like(pos)
         check(L.m3ae_vit_tokens_fwd(_p(pe), _p(cls), _p(posz), _p(out), B, G, width, _dt(out), _stream()),
               "m3ae_vit_tokens_fwd")
@@ -1598,14 +1658,16 @@ class VitTokensFn(Function):
             _done(pos)
         if conv_w.requires_grad:
             g = _grad_buf(conv_w).view(width, -1)
+            dpe = cast(dpe, patches.dtype)   # (fp32 stream: one cast for the conv wgrad's bf16 operand)
             gemm(dpe, 1, dpe.stride(0), patches, patches.stride(0), 1, g, g.stride(0), width, g.shape[1], B * G,
                  accumulate=True)
             _done(conv_w)
-        return None, None, None, None, None, None
+        return None, None, None, None, None, None, None
 
 
-def vit_tokens(img, conv_w, cls, pos, dtype, add_pos=True):
-    return VitTokensFn.apply(img, conv_w, cls, pos, dtype, add_pos)
+def vit_tokens(img, conv_w, cls, pos, dtype, add_pos=True, out_dtype=None):
+    """dtype: the GEMM operands' (patches, conv weight copy); out_dtype: the tokens' (default dtype)."""
+    return VitTokensFn.apply(img, conv_w, cls, pos, dtype, add_pos, out_dtype)
 
 
 # ----------------------------------------------------------------------------------------------------------

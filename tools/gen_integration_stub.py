@@ -33,6 +33,7 @@ DET_ENTRIES = ("m3ae_gemm_det_workspace_bytes", "m3ae_gemm_det", "m3ae_det_works
                "m3ae_xent_det", "m3ae_mim_loss_fwd_det")
 IMAGE_ENTRIES = ("m3ae_image_resample_workspace_bytes", "m3ae_image_resample_u8")
 SAMPLES_ENTRIES = ("m3ae_expand_samples", "m3ae_segment_sum_rows")
+MIXED_LN_ENTRIES = ("m3ae_layernorm_fwd_mixed", "m3ae_layernorm_bwd_mixed", "m3ae_layernorm_bwd_mixed_det")
 ROWS_ENTRIES = ("m3ae_gemm_rows", "m3ae_attn_fwd_rows", "m3ae_attn_bwd_rows", "m3ae_layernorm_bwd_drop_rows", "m3ae_dropout_rows")
 
 
@@ -79,6 +80,11 @@ def block():
     out.append("")
     out.append("# de-duplicated image batches (ABI 4, additive): out[b] = in[src[b]] over whole rows, and the ordered per-image sum back")
     for name in SAMPLES_ENTRIES:
+        res, args = _lib._SIGS[name]
+        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
+    out.append("")
+    out.append("# fp32 residual stream of a bf16 model (ABI 4, additive): LayerNorm from fp32 rows to bf16 rows and its backward")
+    for name in MIXED_LN_ENTRIES:
         res, args = _lib._SIGS[name]
         out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
     out.append("```")
