@@ -42,6 +42,8 @@ extern "C" {
  *    rows draws the dropout masks of the full tensor (see m3ae_dropout); no descriptor changed. */
 /* 4 (additive): device-resident beam search.  m3ae_beam_topk (+ m3ae_beam_topk_workspace_bytes), m3ae_beam_step and
  *    m3ae_beam_finalize (csrc/beam.hip); no descriptor changed. */
+/* 4 (additive): tiled weight operand of the NT GEMMs.  M3AE_GEMM_B_TILED in m3ae_gemm_desc.launch_flags and m3ae_tile_bf16_batched,
+ *    which writes the tiled copies (layout: csrc/tiled_b.h); no descriptor changed. */
 #define M3AE_ABI_VERSION 4
 
 enum { M3AE_F32 = 0, M3AE_BF16 = 1 };
@@ -112,8 +114,14 @@ enum { M3AE_GEMM_NO_PERSISTENT = 1,
                                * gemm_generic's.  The whole descriptor contract holds (strides, batches, every epilogue, dropout
                                * masks, a_rowsum over the fp32 A values); m3ae_last_gemm_path() = "f32x3".  force_generic wins;
                                * with bf16 operands or output the call returns M3AE_ERR_UNSUPPORTED. */
-       M3AE_GEMM_DETERMINISTIC = 4 /* deterministic mode (ABI 4, additive): no fp32 atomics.  Only m3ae_gemm_det accepts it (it needs a
-                               * workspace); m3ae_gemm returns M3AE_ERR_UNSUPPORTED rather than run the atomic kernels. */ };
+       M3AE_GEMM_DETERMINISTIC = 4, /* deterministic mode (ABI 4, additive): no fp32 atomics.  Only m3ae_gemm_det accepts it (it needs a
+                               * workspace); m3ae_gemm returns M3AE_ERR_UNSUPPORTED rather than run the atomic kernels. */
+       M3AE_GEMM_B_TILED = 8   /* tiled weight operand (ABI 4, additive): B points at the tiled copy of a K-contiguous bf16 weight
+                               * W[N][K] (csrc/tiled_b.h; built by m3ae_tile_bf16_batched: N padded to a multiple of 256, times K elements); b_sk
+                               * must be 1 and b_sn = K as for the row-major weight.  The NT kernels then stage B from contiguous
+                               * 1-KiB pieces; results are bit for bit those of the row-major call.  M3AE_ERR_UNSUPPORTED, before
+                               * any launch, for a B that is not bf16, reduction-strided (b_sk != 1) or batched, for K % 32 != 0,
+                               * b_sn != K, a B that is not 16-byte aligned, and together with M3AE_GEMM_F32_X3. */ };
 /* Diagnostic selectors in launch_flags (0 in the product path = kernel chosen by shape): tests pin the kernel variants
  * per call to compare them bit for bit, tools time them against each other.  The library keeps no tuning state.
  *   NT variant v: 0 = 128x128 tile, 4 = 256x256 2-stage, 7 = 256x256 ping-pong, 8 = its persistent form;
@@ -425,6 +433,16 @@ int m3ae_cast_transpose_batched(const void* jobs_dev, int njobs, int64_t total_t
  * (the reference has no counterpart: weights are used transposed-on-the-fly by torch.nn.functional.linear's backward,
  * /root/reference/m3ae/modules/language_encoders/bert_model.py:419-441) */
 int m3ae_transpose_bf16_batched(const void* jobs_dev, int njobs, int64_t total_tiles, void* stream);
+/* The tiled copies the NT GEMMs read under M3AE_GEMM_B_TILED (layout: csrc/tiled_b.h), in one pass over the bf16 sources.
+ * jobs_dev = device array of {const bf16* in; bf16* out_tiled; bf16* out_t; bf16* out_t_tiled; int64 R, C, first_tile}: per unit
+ * in[R][C], any of
+ *   out_tiled   -- tiled copy of in   (forward operand: N = R, K = C; needs C % 32 == 0; pad256(R) * C elements),
+ *   out_t       -- row-major in^T [C][R], what m3ae_transpose_bf16_batched writes,
+ *   out_t_tiled -- tiled copy of in^T (dgrad operand: N = C, K = R; needs R % 32 == 0; pad256(C) * R elements);
+ * NULL = not wanted.  Padding rows of the tiled copies are written as zeros.  R % 8 == 0, C % 8 == 0 and 16-byte aligned pointers
+ * are preconditions of every unit.  first_tile = running sum of ceil(Rp / 64) * ceil(Cp / 64) with Rp = pad256(R) if out_tiled else
+ * R and Cp = pad256(C) if out_t_tiled else C; total_tiles = the final sum.  ABI 4, additive. */
+int m3ae_tile_bf16_batched(const void* jobs_dev, int njobs, int64_t total_tiles, void* stream);
 /* elementwise: out = cast(in) (dtype_in -> dtype_out), n elements */
 int m3ae_cast(const void* in, void* out, int64_t n, int dtype_in, int dtype_out, void* stream);
 /* out = a + b (same dtype) */

@@ -22,6 +22,7 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(m3ae_gemm_desc d, int
     const TB* B = (const TB*)d.B + b1 * d.b_sb1 + b2 * d.b_sb2;
     const int64_t coff = b1 * d.c_sb1 + b2 * d.c_sb2;
     const bool a_kfast = (d.a_sk == 1), b_nfast = (d.b_sn == 1);
+    const bool b_tiled = (d.launch_flags & M3AE_GEMM_B_TILED) != 0;   // B is the tiled copy (tiled_b.h): same values, same order of use
 
     float acc[4][4];
 #pragma unroll
@@ -49,7 +50,8 @@ __global__ __launch_bounds__(256) void gemm_generic_kernel(m3ae_gemm_desc d, int
             if (b_nfast) { nn = e & 63; kk = e >> 6; } else { kk = e & 15; nn = e >> 4; }
             int64_t gn = n0 + nn, gk = k0 + kk;
             float v = 0.f;
-            if (gn < d.N && gk < d.K) v = Elem<TB>::ld(B + gk * d.b_sk + gn * d.b_sn);
+            if (gn < d.N && gk < d.K)
+                v = Elem<TB>::ld(b_tiled ? B + m3ae_tiled_b_index(gn, gk, d.K) : B + gk * d.b_sk + gn * d.b_sn);
             Bs[kk][nn] = v;
         }
         __syncthreads();

@@ -58,7 +58,8 @@ __global__ __launch_bounds__((BM_ / WM) * (BN_ / 64) * 64, 2) void gemm_nt_bf16_
     for (int s = 0; s < NST - 1; ++s) {
         if (s < nt) {
             nt_stage<BKT, A_SEGS, NWAVES>(a.A, a.lda, m0, a.M, (int64_t)s * BKT, smem + s * ST_BYTES, wave, lane);
-            nt_stage<BKT, B_SEGS, NWAVES>(a.B, a.ldb, n0, a.N, (int64_t)s * BKT, smem + s * ST_BYTES + A_BYTES, wave, lane);
+            if (a.b_tiled) nt_stage_tiled<BKT, B_SEGS, NWAVES>(a.B, a.K, n0, (int64_t)s * BKT, smem + s * ST_BYTES + A_BYTES, wave, lane);
+            else nt_stage<BKT, B_SEGS, NWAVES>(a.B, a.ldb, n0, a.N, (int64_t)s * BKT, smem + s * ST_BYTES + A_BYTES, wave, lane);
         }
     }
 
@@ -73,7 +74,8 @@ __global__ __launch_bounds__((BM_ / WM) * (BN_ / 64) * 64, 2) void gemm_nt_bf16_
         if (t + NST - 1 < nt) {
             char* nxt = smem + nxt_s * ST_BYTES;
             nt_stage<BKT, A_SEGS, NWAVES>(a.A, a.lda, m0, a.M, (int64_t)(t + NST - 1) * BKT, nxt, wave, lane);
-            nt_stage<BKT, B_SEGS, NWAVES>(a.B, a.ldb, n0, a.N, (int64_t)(t + NST - 1) * BKT, nxt + A_BYTES, wave, lane);
+            if (a.b_tiled) nt_stage_tiled<BKT, B_SEGS, NWAVES>(a.B, a.K, n0, (int64_t)(t + NST - 1) * BKT, nxt + A_BYTES, wave, lane);
+            else nt_stage<BKT, B_SEGS, NWAVES>(a.B, a.ldb, n0, a.N, (int64_t)(t + NST - 1) * BKT, nxt + A_BYTES, wave, lane);
         }
         const char* At = smem + cur_s * ST_BYTES;
         const char* Bt = At + A_BYTES;
@@ -297,7 +299,7 @@ static int launch_nt_t(const MfmaArgs& a, hipStream_t s) {
 //              barrier; chunk c+1 is first read in phase 2c+2, i.e. after a barrier every wave passed post-wait.
 // ---------------------------------------------------------------------------------------------------------
 // M3AE_EXP_NT_*: timing-only experiments on the ping-pong kernels (tools/nt_exp.sh; wrong results, never in the product build):
-// operands left unstaged / staged from contiguous 1-KiB source pieces (as if stored reduction-chunk-major) / stores dropped
+// operands left unstaged / staged from contiguous 1-KiB source pieces (as if stored reduction-chunk-major; _CONTIG_B: B only) / stores dropped
 #if defined(M3AE_EXP_NT_NODMA)
 #define PP_STAGE(G, ld, r0, nr, k0, tile) do { } while (0)
 #elif defined(M3AE_EXP_NT_CONTIG)
@@ -323,6 +325,23 @@ DEVINL void nt_stage_contig(const bf16_t* G, int64_t ld, int64_t row0, int64_t n
 #else
 #define PP_STAGE(G, ld, r0, nr, k0, tile) nt_stage<CK, 2, NW>(G, ld, r0, nr, k0, tile, wave, lane)
 #endif
+
+// M3AE_EXP_NT_CONTIG_B (with M3AE_EXP_NT_CONTIG): the contiguous pieces for the B operand only -- A keeps its row-shaped pieces (what a
+// tiled WEIGHT alone can buy: profiles/r09_nt_tiled_weights_probe.log)
+#if defined(M3AE_EXP_NT_CONTIG) && defined(M3AE_EXP_NT_CONTIG_B)
+#ifdef M3AE_EXP_NT_L2HOT
+#define PP_STAGE_A(G, ld, r0, nr, k0, tile) nt_stage<CK, 2, NW>(G, ld, 0, nr, k0, tile, wave, lane)
+#else
+#define PP_STAGE_A(G, ld, r0, nr, k0, tile) nt_stage<CK, 2, NW>(G, ld, r0, nr, k0, tile, wave, lane)
+#endif
+#else
+#define PP_STAGE_A(G, ld, r0, nr, k0, tile) PP_STAGE(G, ld, r0, nr, k0, tile)
+#endif
+// the B operand of a chunk: from the tiled copy of the weight under M3AE_GEMM_B_TILED (one lane-linear 1-KiB block per piece)
+#define PP_STAGE_B(k0, tile) do { \
+        if (a.b_tiled) nt_stage_tiled32<2, NW>(a.B, a.K, n0, k0, tile, wave, lane); \
+        else PP_STAGE(a.B, a.ldb, n0, a.N, k0, tile); \
+    } while (0)
 
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(MfmaArgs a) {
@@ -350,8 +369,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(MfmaArgs a) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         if (c < nc) {
-            PP_STAGE(a.B, a.ldb, n0, a.N, (int64_t)c * CK, smem + c * SLOT + A_BYTES);
-            PP_STAGE(a.A, a.lda, m0, a.M, (int64_t)c * CK, smem + c * SLOT);
+            PP_STAGE_B((int64_t)c * CK, smem + c * SLOT + A_BYTES);
+            PP_STAGE_A(a.A, a.lda, m0, a.M, (int64_t)c * CK, smem + c * SLOT);
         }
     }
     if (nc >= 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
@@ -374,7 +393,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(MfmaArgs a) {
         for (int j = 0; j < 4; ++j) bfr[j] = nt_frag<CK>(Bt, wc * 64 + j * 16 + frow, fchunk);
 #pragma unroll
         for (int i = 0; i < 4; ++i) af[i] = nt_frag<CK>(At, wr * 128 + i * 16 + frow, fchunk);
-        if (more) PP_STAGE(a.B, a.ldb, n0, a.N, (int64_t)(c + 3) * CK, nxt + A_BYTES);
+        if (more) PP_STAGE_B((int64_t)(c + 3) * CK, nxt + A_BYTES);
         PP_FENCE();
         __builtin_amdgcn_s_barrier();
         PP_FENCE();
@@ -394,7 +413,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(MfmaArgs a) {
         // ---------------- phase 2c + 1: rows 64..127 (the B fragments stay in registers)
 #pragma unroll
         for (int i = 0; i < 4; ++i) af[i] = nt_frag<CK>(At, wr * 128 + 64 + i * 16 + frow, fchunk);
-        if (more) PP_STAGE(a.A, a.lda, m0, a.M, (int64_t)(c + 3) * CK, nxt);
+        if (more) PP_STAGE_A(a.A, a.lda, m0, a.M, (int64_t)(c + 3) * CK, nxt);
         {
             const int rem = nc - 1 - c;  // chunks after this one; chunk c + 1 must have landed before the next phase
             if (rem >= 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
@@ -487,8 +506,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_persistent_kernel(MfmaArgs 
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         char* sl = smem + ((c + 2) & 3) * SLOT;
-        PP_STAGE(a.B, a.ldb, n0, a.N, (int64_t)c * CK, sl + A_BYTES);
-        PP_STAGE(a.A, a.lda, m0, a.M, (int64_t)c * CK, sl);
+        PP_STAGE_B((int64_t)c * CK, sl + A_BYTES);
+        PP_STAGE_A(a.A, a.lda, m0, a.M, (int64_t)c * CK, sl);
     }
     int top_wait = 0;
 #ifdef M3AE_NT_TRACE
@@ -527,7 +546,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_persistent_kernel(MfmaArgs 
 #pragma unroll
             for (int i = 0; i < 4; ++i) af[i] = nt_frag<CK>(At, wr * 128 + i * 16 + frow, fchunk);
             NT_ACC(0);
-            if (more) PP_STAGE(a.B, a.ldb, n0, a.N, (int64_t)(c + 3) * CK, nxt + A_BYTES);
+            if (more) PP_STAGE_B((int64_t)(c + 3) * CK, nxt + A_BYTES);
             NT_ACC(1);
             PP_FENCE();
             __builtin_amdgcn_s_barrier();
@@ -552,7 +571,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_persistent_kernel(MfmaArgs 
 #pragma unroll
             for (int i = 0; i < 4; ++i) af[i] = nt_frag<CK>(At, wr * 128 + 64 + i * 16 + frow, fchunk);
             NT_ACC(0);
-            if (more) PP_STAGE(a.A, a.lda, m0, a.M, (int64_t)(c + 3) * CK, nxt);
+            if (more) PP_STAGE_A(a.A, a.lda, m0, a.M, (int64_t)(c + 3) * CK, nxt);
             NT_ACC(1);
             {
                 const int rem = nc - 1 - c;
@@ -596,8 +615,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_persistent_kernel(MfmaArgs 
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 char* sl = smem + ((c + 2) & 3) * SLOT;
-                PP_STAGE(a.B, a.ldb, n0, a.N, (int64_t)c * CK, sl + A_BYTES);
-                PP_STAGE(a.A, a.lda, m0, a.M, (int64_t)c * CK, sl);
+                PP_STAGE_B((int64_t)c * CK, sl + A_BYTES);
+                PP_STAGE_A(a.A, a.lda, m0, a.M, (int64_t)c * CK, sl);
             }
         }
         if (a.c_f32) epilogue_rows<float, EPI, 8, 1>(a, smem, wave, lane, m_cur + wr * 128, n_cur + wc * 64, acc);
@@ -613,8 +632,8 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_persistent_kernel(MfmaArgs 
         PP_FENCE();
         {
             char* sl = smem + ((2 + 2) & 3) * SLOT;
-            PP_STAGE(a.B, a.ldb, n0, a.N, (int64_t)2 * CK, sl + A_BYTES);
-            PP_STAGE(a.A, a.lda, m0, a.M, (int64_t)2 * CK, sl);
+            PP_STAGE_B((int64_t)2 * CK, sl + A_BYTES);
+            PP_STAGE_A(a.A, a.lda, m0, a.M, (int64_t)2 * CK, sl);
         }
         v = vn;
     }
@@ -705,6 +724,7 @@ static int launch_nt(const m3ae_gemm_desc& d, hipStream_t s, DropRows rows) {
     a.drop = make_drop(d.dropout_p, d.dropout_seed, d.dropout_salt, rows);
     a.no_persist = (d.launch_flags & M3AE_GEMM_NO_PERSISTENT) ? 1 : 0;
     a.nt_variant = ((d.launch_flags >> 8) & 0xf) - 1;
+    a.b_tiled = (d.launch_flags & M3AE_GEMM_B_TILED) ? 1 : 0;
     a.st_policy = (d.launch_flags >> 20) & 0x3;
     // by shape: outputs of 32 MB and more (the image-side GEMMs: 113-900 MB at per-GPU batch 256) are written -- and their residual /
     // derivative operands read -- with the streaming policy: with the default one they evict the weight panel and the activation rows
@@ -1139,6 +1159,11 @@ extern "C" int m3ae_gemm_rows(const m3ae_gemm_desc* dp, int64_t row_base, int64_
     if (route == ROUTE_BAD_DIMS) return M3AE_ERR_ARG;
     const DropRows rows{row_base, row_step};
     if (!drop_rows_ok(rows, d.M, d.N)) return M3AE_ERR_ARG;
+    // the tiled weight copy (tiled_b.h) is defined for one K-contiguous bf16 matrix with K % 32 == 0; the NT and the generic kernels read it
+    if ((d.launch_flags & M3AE_GEMM_B_TILED) &&
+        (d.dtype_a != M3AE_BF16 || d.dtype_b != M3AE_BF16 || d.b_sk != 1 || d.b_sn != d.K || d.K % 32 != 0 || d.batch1 != 1 ||
+         d.batch2 != 1 || (d.launch_flags & M3AE_GEMM_F32_X3) || !aligned16(d.B)))
+        return M3AE_ERR_UNSUPPORTED;
     // the split-K wgrad kernels have no dropout site: a mapped call that asks for one is refused, not run without it
     if (route == ROUTE_TN && d.dropout_p > 0.f && (row_base != 0 || row_step != 1)) return M3AE_ERR_UNSUPPORTED;
     // deterministic mode needs a workspace for its partial planes: m3ae_gemm_det takes one, this call cannot, and it never
@@ -1179,6 +1204,7 @@ extern "C" int m3ae_gemm_det(const m3ae_gemm_desc* dp, void* workspace, int64_t 
     if (!dp || !dp->A || !dp->B || !dp->C) return M3AE_ERR_ARG;
     const m3ae_gemm_desc& d = *dp;
     if (!(d.launch_flags & M3AE_GEMM_DETERMINISTIC)) return M3AE_ERR_ARG;
+    if (d.launch_flags & M3AE_GEMM_B_TILED) return M3AE_ERR_UNSUPPORTED;   // the wgrad family's B is reduction-strided
     if (gemm_route(d) != ROUTE_TN) return M3AE_ERR_UNSUPPORTED;   // (such a descriptor needs no ordered form: plain m3ae_gemm, flag clear)
     if (!workspace || !aligned16(workspace) || workspace_bytes < m3ae_gemm_det_workspace_bytes(dp)) return M3AE_ERR_WORKSPACE;
     g_last_path = "mfma_tn";

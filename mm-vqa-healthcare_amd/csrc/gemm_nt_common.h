@@ -36,6 +36,7 @@ struct MfmaArgs {
     int nt_variant;     // desc.launch_flags selector (-1: by shape)
     int st_policy;      // cache policy of the epilogue's streams: 1 plain; 2 output stores nt; 3 stores nt + residual / aux loads nt
                         // (launch_nt resolves the desc.launch_flags selector 0 = by shape)
+    int b_tiled;        // desc.launch_flags & M3AE_GEMM_B_TILED: B is the tiled copy of the weight (tiled_b.h)
 };
 
 // Tile order inside the (XCD-contiguous) id range: column tiles in groups of GC, row-major inside a group.  An XCD then

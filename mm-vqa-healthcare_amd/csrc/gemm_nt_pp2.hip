@@ -181,7 +181,9 @@ DEVINL void epi_finish(const MfmaArgs& a, float* slab, int lane, int64_t m_base,
 // profiles/r04_nt_in_kernel_clock.log): it holds 1.81-1.94 GHz on random data (2.38 GHz on zero-filled operands, +20 % TF/s at the same
 // cycle count), i.e. the kernel delivers 0.52 (K = 768) to 0.62 (K = 3072) of the bf16 MFMA rate AT THE CLOCK IT RUNS AT, and cycles
 // saved in the loop come back partly as a lower clock (MI355X_MICROARCH.md, 'DVFS give-back').
-template <int EPI>
+// TILED: B is the tiled copy of the weight (M3AE_GEMM_B_TILED, tiled_b.h).  A template parameter, not a run-time branch: the
+// row-major instantiation keeps the code it had (a run-time stride and pointer select cost 13 more spilled SGPRs in this kernel).
+template <int EPI, bool TILED>
 __global__ __launch_bounds__(512, 2) void gemm_nt_pp2_kernel(MfmaArgs a) {
     if (a.has_drop) drop_resolve(a.drop);
     constexpr int CK = 32, A_BYTES = 256 * CK * 2, SLOT = 2 * A_BYTES, RING = 4 * SLOT;
@@ -222,18 +224,26 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp2_kernel(MfmaArgs a) {
         const unsigned c0 = (unsigned)(((lane_p & 3) ^ nt_swz<CK>(r0)) * 16), c1 = (unsigned)(((lane_p & 3) ^ nt_swz<CK>(r1)) * 16);
         const int ma = (int)(a.M - 1 - m0 < 255 ? a.M - 1 - m0 : 255), mb = (int)(a.N - 1 - n0 < 255 ? a.N - 1 - n0 : 255);
         abase = a.A + m0 * a.lda;
-        bbase = a.B + n0 * a.ldb;
         va0 = (unsigned)(r0 < ma ? r0 : ma) * (unsigned)a.lda * 2u + c0;
         va1 = (unsigned)(r1 < ma ? r1 : ma) * (unsigned)a.lda * 2u + c1;
-        vb0 = (unsigned)(r0 < mb ? r0 : mb) * (unsigned)a.ldb * 2u + c0;
-        vb1 = (unsigned)(r1 < mb ? r1 : mb) * (unsigned)a.ldb * 2u + c1;
+        if (TILED) {   // tiled copy of the weight (tiled_b.h): the wave's pieces are blocks `wave` and `wave + 8` of the tile's chunk,
+                           // lane-linear (the swizzle is in the layout); rows past N are the copy's zero padding
+            bbase = a.B + (n0 >> 8) * (int64_t)nc * M3AE_TB_CHUNK_ELEMS;
+            vb0 = (unsigned)wave * 1024u + (unsigned)lane_p * 16u;
+            vb1 = vb0 + 8192u;
+        } else {
+            bbase = a.B + n0 * a.ldb;
+            vb0 = (unsigned)(r0 < mb ? r0 : mb) * (unsigned)a.ldb * 2u + c0;
+            vb1 = (unsigned)(r1 < mb ? r1 : mb) * (unsigned)a.ldb * 2u + c1;
+        }
     };
+    constexpr int b_cstep = TILED ? M3AE_TB_CHUNK_ELEMS : CK;   // elements between two chunks of the B operand
     // (nt on these loads was measured too: -30 % -- the tiles of an XCD share both operands through its L2,
     // profiles/r04_nt_dma_nt_policy_measured.log)
     auto issue_b = [&](int c) {
         const unsigned dst = lds_wave + (unsigned)(c & 3) * SLOT + A_BYTES;
-        glds16_asm(bbase + (int64_t)c * CK, vb0, dst);
-        glds16_asm(bbase + (int64_t)c * CK, vb1, dst + 8192u);
+        glds16_asm(bbase + (int64_t)c * b_cstep, vb0, dst);
+        glds16_asm(bbase + (int64_t)c * b_cstep, vb1, dst + 8192u);
     };
     auto issue_a = [&](int c) {
         const unsigned dst = lds_wave + (unsigned)(c & 3) * SLOT;
@@ -375,7 +385,8 @@ int launch_pp2_t(const MfmaArgs& a, bool persistent, hipStream_t s) {
     const int dev = current_device();
     const int64_t tiles = cdiv(a.M, 256) * cdiv(a.N, 256), cus = device_cus8(dev);
     const unsigned grid = (unsigned)(persistent && tiles > cus ? cus : tiles);
-    return launch_dyn_on<gemm_nt_pp2_kernel<EPI>>(dev, dim3(grid), dim3(512), lds, s, a);
+    if (a.b_tiled) return launch_dyn_on<gemm_nt_pp2_kernel<EPI, true>>(dev, dim3(grid), dim3(512), lds, s, a);
+    return launch_dyn_on<gemm_nt_pp2_kernel<EPI, false>>(dev, dim3(grid), dim3(512), lds, s, a);
 }
 
 int launch_pp2_e(const MfmaArgs& a, int epi, bool persistent, hipStream_t s) {

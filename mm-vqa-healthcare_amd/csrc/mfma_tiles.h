@@ -59,6 +59,30 @@ DEVINL void nt_stage(const bf16_t* G, int64_t ld, int64_t row0, int64_t nrows, i
     }
 }
 
+// The same LDS image of a B tile staged from the tiled copy of the weight (tiled_b.h; K = the weight's row length).  The 16-B unit a
+// lane fetches is the one nt_stage fetches; only its address differs.  Rows past N are the copy's zero padding (no clamp).
+template <int BKT, int SEGS_PER_WAVE, int NWAVES>
+DEVINL void nt_stage_tiled(const bf16_t* Bt, int64_t K, int64_t row0, int64_t k0, char* tile, int wave, int lane) {
+    constexpr int CPR = BKT / 8, RPS = 64 / CPR;
+#pragma unroll
+    for (int q = 0; q < SEGS_PER_WAVE; ++q) {
+        const int seg = q * NWAVES + wave;
+        const int row = seg * RPS + lane / CPR;
+        const int chunk = (lane % CPR) ^ nt_swz<BKT>(row);
+        glds16(Bt + m3ae_tiled_b_index(row0 + row, k0 + chunk * 8, K), tile + seg * 1024);
+    }
+}
+// 32-deep chunks of a 256-row tile (row0 % 256 == 0): piece seg of the chunk is one block of the copy, lane-linear
+template <int SEGS_PER_WAVE, int NWAVES>
+DEVINL void nt_stage_tiled32(const bf16_t* Bt, int64_t K, int64_t row0, int64_t k0, char* tile, int wave, int lane) {
+    const bf16_t* src = Bt + ((row0 >> 8) * (K >> 5) + (k0 >> 5)) * M3AE_TB_CHUNK_ELEMS + lane * 8;
+#pragma unroll
+    for (int q = 0; q < SEGS_PER_WAVE; ++q) {
+        const int seg = q * NWAVES + wave;
+        glds16(src + seg * M3AE_TB_BLOCK_ELEMS, tile + seg * 1024);
+    }
+}
+
 template <int BKT> DEVINL s16x8 nt_frag(const char* tile, int row, int chunk) {
     return *(const s16x8*)(tile + row * (BKT * 2) + ((chunk ^ nt_swz<BKT>(row)) << 4));
 }

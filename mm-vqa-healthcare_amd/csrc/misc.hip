@@ -531,6 +531,51 @@ __global__ __launch_bounds__(256) void transpose_bf16_batched_kernel(const Trans
     }
 }
 
+// The tiled copies the NT GEMMs stage their weight operand from (tiled_b.h), in the same pass as the transpose above: a 64 x 64
+// tile of in[R][C] is read once (16 B per lane) and written as its piece of the tiled copy of in, of the row-major in^T and of the
+// tiled copy of in^T (whichever the job asks for).  Tiles past R / C exist only to fill the tiled copies' padding rows with zeros.
+// Preconditions per unit: R % 8 == 0, C % 8 == 0, 16-byte aligned pointers; out_tiled needs C % 32 == 0, out_t_tiled R % 32 == 0.
+struct TileJob16 { const bf16_t* in; bf16_t* out_tiled; bf16_t* out_t; bf16_t* out_t_tiled; int64_t R, C; int64_t first_tile; };
+__global__ __launch_bounds__(256) void tile_bf16_batched_kernel(const TileJob16* jobs, int njobs) {
+    __shared__ __attribute__((aligned(16))) bf16_t tile[64][66];
+    const int64_t tid = blockIdx.x;
+    int lo = 0, hi = njobs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (jobs[mid].first_tile <= tid) lo = mid; else hi = mid - 1;
+    }
+    const TileJob16 j = jobs[lo];
+    const int64_t local = tid - j.first_tile;
+    const int64_t Rp = j.out_tiled ? m3ae_tiled_b_rows(j.R) : j.R, Cp = j.out_t_tiled ? m3ae_tiled_b_rows(j.C) : j.C;
+    const int64_t tiles_c = (Cp + 63) / 64;
+    const int64_t c0 = (local % tiles_c) * 64, r0 = (local / tiles_c) * 64;
+    const int t = threadIdx.x, q = t >> 3, ch = t & 7;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const int r = q + 32 * p;
+        const int64_t gr = r0 + r, gc = c0 + ch * 8;   // C % 8 == 0: a lane's 8 columns are all inside or all outside
+        u32x4 v = (u32x4){0u, 0u, 0u, 0u};
+        if (gr < j.R && gc < j.C) v = *(const u32x4*)(j.in + gr * j.C + gc);
+        uint32_t* d = (uint32_t*)&tile[r][ch * 8];
+        d[0] = v[0]; d[1] = v[1]; d[2] = v[2]; d[3] = v[3];
+        if (j.out_tiled && gr < Rp && gc < j.C) *(u32x4*)(j.out_tiled + m3ae_tiled_b_index(gr, gc, j.C)) = v;
+    }
+    if (!j.out_t && !j.out_t_tiled) return;
+    __syncthreads();
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        const int c = q + 32 * p;
+        const int64_t gc = c0 + c, gr = r0 + ch * 8;   // row gc of in^T, its columns gr .. gr + 7 (R % 8 == 0)
+        if (gr >= j.R) continue;
+        u32x4 v;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            v[i] = (uint32_t)tile[ch * 8 + 2 * i][c] | ((uint32_t)tile[ch * 8 + 2 * i + 1][c] << 16);
+        if (j.out_t && gc < j.C) *(u32x4*)(j.out_t + gc * j.R + gr) = v;
+        if (j.out_t_tiled && gc < Cp) *(u32x4*)(j.out_t_tiled + m3ae_tiled_b_index(gc, gr, j.R)) = v;
+    }
+}
+
 template <typename TI, typename TO>
 __global__ void cast_kernel(const TI* in, TO* out, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
@@ -796,6 +841,13 @@ extern "C" int m3ae_transpose_bf16_batched(const void* jobs_dev, int njobs, int6
     if (!jobs_dev || njobs <= 0 || total_tiles <= 0) return M3AE_ERR_ARG;
     hipLaunchKernelGGL(transpose_bf16_batched_kernel, dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream,
                        (const TransposeJob16*)jobs_dev, njobs);
+    return hip_launch_status();
+}
+
+extern "C" int m3ae_tile_bf16_batched(const void* jobs_dev, int njobs, int64_t total_tiles, void* stream) {
+    if (!jobs_dev || njobs <= 0 || total_tiles <= 0 || total_tiles > 0x7fffffffLL) return M3AE_ERR_ARG;
+    hipLaunchKernelGGL(tile_bf16_batched_kernel, dim3((unsigned)total_tiles), dim3(256), 0, (hipStream_t)stream,
+                       (const TileJob16*)jobs_dev, njobs);
     return hip_launch_status();
 }
 

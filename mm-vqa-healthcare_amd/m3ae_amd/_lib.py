@@ -56,7 +56,7 @@ class XattnDesc(C.Structure):
     ]
 
 
-GEMM_NO_PERSISTENT, GEMM_F32_X3, GEMM_DETERMINISTIC = 1, 2, 4   # m3ae_gemm_desc.launch_flags
+GEMM_NO_PERSISTENT, GEMM_F32_X3, GEMM_DETERMINISTIC, GEMM_B_TILED = 1, 2, 4, 8   # m3ae_gemm_desc.launch_flags
 DET_COLSUM, DET_EMBED_BWD, DET_BCE, DET_XENT, DET_MIM = 0, 1, 2, 3, 4   # m3ae_det_workspace_bytes op
 ATTN_LEGACY_KERNELS, ATTN_F32_X3 = 1, 2           # m3ae_attn_desc.launch_flags
 XATTN_NO_PERSISTENT, XATTN_LEGACY_CHAIN = 1, 2    # m3ae_xattn_desc.launch_flags
@@ -96,6 +96,7 @@ _SIGS = {
     "m3ae_cast_transpose": (C.c_int, [vp, vp, vp, i64, i64, vp]),
     "m3ae_cast_transpose_batched": (C.c_int, [vp, C.c_int, i64, vp]),
     "m3ae_transpose_bf16_batched": (C.c_int, [vp, C.c_int, i64, vp]),
+    "m3ae_tile_bf16_batched": (C.c_int, [vp, C.c_int, i64, vp]),
     "m3ae_cast": (C.c_int, [vp, vp, i64, C.c_int, C.c_int, vp]),
     "m3ae_zero": (C.c_int, [vp, i64, vp]),
     "m3ae_add": (C.c_int, [vp, vp, vp, i64, C.c_int, vp]),

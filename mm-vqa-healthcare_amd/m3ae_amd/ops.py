@@ -33,6 +33,11 @@ GEMM_NT_VARIANT, GEMM_TN_VARIANT, GEMM_COL_GROUP = int(os.environ.get("M3AE_GEMM
 
 ATTN_LEGACY = os.environ.get("M3AE_ATTN_LEGACY", "0") == "1"   # round-3 attention kernels (tests / tools compare the generations)
 GEMM_ST_POLICY = int(os.environ.get("M3AE_GEMM_ST_POLICY", 0))   # output-store cache policy selector (0: the kernel's default)
+# Weight operand of the NT GEMMs from the tiled copies ParamStore keeps beside the shadows (m3ae_amd/tiled_b.py, M3AE_GEMM_B_TILED):
+# bit-identical results.  Read when a ParamStore is built (it allocates the copies) and at every mm_nt / mm_dgrad call.
+# On by default: -1.2 % on the step at per-GPU batch 256 (three alternating runs each against the parent commit, DESIGN.md 6e,
+# profiles/r09_nt_tiled_weights_ab.log).  M3AE_TILED_B=0 turns it off (A/B runs): no copies are kept, every GEMM reads the shadows.
+TILED_B = os.environ.get("M3AE_TILED_B", "1") != "0"
 
 
 def _gemm_flags():
@@ -252,8 +257,9 @@ def compute_weight(w):
 # ----------------------------------------------------------------------------------------------------------
 def gemm(a, a_sm, a_sk, b, b_sk, b_sn, c, c_sm, M, N, K, *, alpha=1.0, accumulate=False, bias=None, act=ACT_NONE,
          preact=None, residual=None, dact_aux=None, dact=ACT_NONE, force_generic=False, batch=(1, 1),
-         a_sb=(0, 0), b_sb=(0, 0), c_sb=(0, 0), a_rowsum=None, dropout=None, preact_grad=False, rows=None):
-    """rows = (row_base, row_step): the dropout mask row of output row m is row_base + m * row_step (m3ae_gemm_rows)."""
+         a_sb=(0, 0), b_sb=(0, 0), c_sb=(0, 0), a_rowsum=None, dropout=None, preact_grad=False, rows=None, b_tiled=False):
+    """rows = (row_base, row_step): the dropout mask row of output row m is row_base + m * row_step (m3ae_gemm_rows).
+    b_tiled: `b` is the tiled copy (tiled_b.py) of the K-contiguous bf16 weight [N, K]; b_sk = 1 and b_sn = K as for the weight."""
     _need_cuda(c)
     d = GemmDesc()
     d.M, d.N, d.K = M, N, K
@@ -274,7 +280,7 @@ def gemm(a, a_sm, a_sk, b, b_sk, b_sn, c, c_sm, M, N, K, *, alpha=1.0, accumulat
             setattr(d, name, t.data_ptr())
     d.dact = dact
     d.preact_grad = int(preact_grad)
-    d.launch_flags = _gemm_flags()
+    d.launch_flags = _gemm_flags() | (_lib.GEMM_B_TILED if b_tiled else 0)
     if _MODE.x3 and d.dtype_a == F32 and d.dtype_b == F32 and d.dtype_c == F32:
         d.launch_flags |= _lib.GEMM_F32_X3
     d.force_generic = int(force_generic)
@@ -347,9 +353,10 @@ def mm_nt(x2, ldx, M, w, bias=None, act=ACT_NONE, residual=None, want_preact=Fal
     N, K = w.shape
     y = torch.empty((M, N), dtype=out_dtype or x2.dtype, device=x2.device)
     pre = torch.empty_like(y) if want_preact else None
-    gemm(x2, ldx, 1, w, 1, w.stride(0), y, N, M, N, K, bias=bias, act=act, preact=pre, residual=residual,
+    tb = getattr(w, "m3ae_tb", None) if TILED_B and x2.dtype == torch.bfloat16 and w.stride(0) == K else None
+    gemm(x2, ldx, 1, w if tb is None else tb, 1, w.stride(0), y, N, M, N, K, bias=bias, act=act, preact=pre, residual=residual,
          dact_aux=dact_aux, dact=dact, force_generic=force_generic, alpha=alpha, dropout=dropout,
-         preact_grad=preact_grad and want_preact, rows=rows)
+         preact_grad=preact_grad and want_preact, rows=rows, b_tiled=tb is not None)
     return y, pre
 
 
@@ -358,7 +365,10 @@ def mm_dgrad(dy, w_param, dact_aux=None, dact=ACT_NONE, residual=None, alpha=1.0
     the rows into this preallocated tensor at this row stride instead of a fresh [M, K]."""
     M, N = dy.shape
     wt = getattr(w_param, "m3ae_t", None)
-    if wt is not None:
+    wtt = getattr(w_param, "m3ae_tt", None) if TILED_B and wt is not None and dy.dtype == torch.bfloat16 else None
+    if wtt is not None:   # the tiled copy of the transposed shadow [K, N]: row length N
+        b, b_sk, b_sn, K = wtt, 1, N, wt.shape[0]
+    elif wt is not None:
         b, b_sk, b_sn, K = wt, 1, wt.stride(0), wt.shape[0]
     else:
         b = compute_weight(w_param)
@@ -366,7 +376,7 @@ def mm_dgrad(dy, w_param, dact_aux=None, dact=ACT_NONE, residual=None, alpha=1.0
     if out is None:
         out, ld_out = torch.empty((M, K), dtype=dy.dtype, device=dy.device), K
     gemm(dy, dy.stride(0), 1, b, b_sk, b_sn, out, ld_out, M, K, N, dact_aux=dact_aux, dact=dact, residual=residual,
-         alpha=alpha, dropout=dropout, rows=rows)
+         alpha=alpha, dropout=dropout, rows=rows, b_tiled=wtt is not None)
     return out
 
 

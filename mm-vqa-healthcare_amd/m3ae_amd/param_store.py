@@ -57,6 +57,7 @@ class PackedParam:
         rows = sum(m.shape[0] for m in self.members)
         self.shape = (rows,) + tuple(m0.shape[1:])
         self.m3ae_t = None
+        self.m3ae_tb = self.m3ae_tt = None   # tiled copies of the packed weight and of its transpose (ParamStore, tiled_b.py)
         self._check_adjacent()
 
     def _check_adjacent(self):
@@ -78,7 +79,10 @@ class PackedParam:
     @property
     def m3ae_c(self):
         m0 = self.members[0]
-        return self._view(getattr(m0, "m3ae_c", m0.data))
+        v = self._view(getattr(m0, "m3ae_c", m0.data))
+        if self.m3ae_tb is not None:
+            v.m3ae_tb = self.m3ae_tb
+        return v
 
     @property
     def requires_grad(self):
@@ -164,18 +168,42 @@ class ParamStore:
                 t = torch.empty((cols, rows), dtype=torch.bfloat16, device=device)
                 u.m3ae_t = t
                 self._t_bufs.append((u, rows, cols, t))
+            # Tiled copies (tiled_b.py, ops.TILED_B): the NT GEMMs stage their weight operand from 1-KiB blocks instead of strided
+            # 64-B row pieces.  A unit that qualifies gets the tiled copy of its shadow (forward operand) and of its transpose (dgrad
+            # operand); one kernel then writes them AND the row-major transpose (other readers: the fused cross-attention kernels,
+            # sliced projections) from one read of the shadow.  Every other unit stays with the one-launch transposer.
+            from . import ops as _ops, tiled_b as _tb
+            self._tile_jobs, tiled, plain = None, [], []
+            for (u, rows, cols, t) in self._t_bufs:
+                off = (u.data.data_ptr() - self.flat.data_ptr()) // 4
+                assert 0 <= off < self.total
+                ok = _ops.TILED_B and len(u.shape) == 2 and rows % 8 == 0 and cols % 8 == 0 and (rows % 32 == 0 or cols % 32 == 0)
+                if not ok:
+                    plain.append((u, rows, cols, t))
+                    continue
+                src = self.shadow[off:off + rows * cols].view(rows, cols)
+                fwd = torch.empty(_tb.tiled_rows(rows) * cols, dtype=torch.bfloat16, device=device) if cols % 32 == 0 else None
+                tt = torch.empty(_tb.tiled_rows(cols) * rows, dtype=torch.bfloat16, device=device) if rows % 32 == 0 else None
+                tiled.append((src, fwd, t, tt))
+                u.m3ae_tt = tt
+                if isinstance(u, PackedParam):
+                    u.m3ae_tb = fwd
+                elif fwd is not None:
+                    u.m3ae_c.m3ae_tb = fwd
+            if tiled:
+                self._tile_jobs = _tb.job_table(tiled, device)
             # job table for the one-launch transposer
             import numpy as np
-            tab = np.zeros((len(self._t_bufs), 5), dtype=np.int64)
+            tab = np.zeros((len(plain), 5), dtype=np.int64)
             first = 0
-            for i, (u, rows, cols, t) in enumerate(self._t_bufs):
+            for i, (u, rows, cols, t) in enumerate(plain):
                 # source = the unit's bf16 shadow (same element offset as its fp32 master in the flat buffer)
                 off = (u.data.data_ptr() - self.flat.data_ptr()) // 4
                 assert 0 <= off < self.total
                 tab[i] = (self.shadow.data_ptr() + 2 * off, t.data_ptr(), rows, cols, first)
                 first += ((rows + 63) // 64) * ((cols + 63) // 64)
-            self._t_tiles = first
-            self._t_jobs = torch.from_numpy(tab).to(device)
+            self._t_tiles, self._t_njobs = first, len(plain)
+            self._t_jobs = torch.from_numpy(tab).to(device) if plain else None
         self.sync_shadows()
 
     # ---- shadows -------------------------------------------------------------------------------------------
@@ -190,9 +218,12 @@ class ParamStore:
         if cast:
             _lib.check(L.m3ae_cast(C.c_void_p(self.flat.data_ptr()), C.c_void_p(self.shadow.data_ptr()), self.total,
                                    _lib.F32, _lib.BF16, s), "m3ae_cast")
-        if self._t_bufs:
-            _lib.check(L.m3ae_transpose_bf16_batched(C.c_void_p(self._t_jobs.data_ptr()), len(self._t_bufs),
+        if self._t_bufs and self._t_jobs is not None:
+            _lib.check(L.m3ae_transpose_bf16_batched(C.c_void_p(self._t_jobs.data_ptr()), self._t_njobs,
                                                      self._t_tiles, s), "m3ae_transpose_bf16_batched")
+        if self._t_bufs and self._tile_jobs is not None:   # tiled copies + the row-major transposes of their units, one pass
+            from . import tiled_b as _tb
+            _tb.run(*self._tile_jobs, stream=s)
 
     # ---- optimizer -----------------------------------------------------------------------------------------
     def zero_grad(self):

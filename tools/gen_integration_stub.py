@@ -34,6 +34,7 @@ DET_ENTRIES = ("m3ae_gemm_det_workspace_bytes", "m3ae_gemm_det", "m3ae_det_works
 IMAGE_ENTRIES = ("m3ae_image_resample_workspace_bytes", "m3ae_image_resample_u8")
 SAMPLES_ENTRIES = ("m3ae_expand_samples", "m3ae_segment_sum_rows")
 MIXED_LN_ENTRIES = ("m3ae_layernorm_fwd_mixed", "m3ae_layernorm_bwd_mixed", "m3ae_layernorm_bwd_mixed_det")
+TILED_ENTRIES = ("m3ae_tile_bf16_batched",)
 ROWS_ENTRIES = ("m3ae_gemm_rows", "m3ae_attn_fwd_rows", "m3ae_attn_bwd_rows", "m3ae_layernorm_bwd_drop_rows", "m3ae_dropout_rows")
 
 
@@ -85,6 +86,12 @@ def block():
     out.append("")
     out.append("# fp32 residual stream of a bf16 model (ABI 4, additive): LayerNorm from fp32 rows to bf16 rows and its backward")
     for name in MIXED_LN_ENTRIES:
+        res, args = _lib._SIGS[name]
+        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
+    out.append("")
+    out.append("# tiled weight operand of the NT GEMMs (ABI 4, additive): B = the tiled copy of W[N][K] (csrc/tiled_b.h), same results")
+    out.append(f"GEMM_B_TILED = {_lib.GEMM_B_TILED}     # m3ae_gemm_desc.launch_flags; b_sk = 1, b_sn = K, B 16-byte aligned, K % 32 == 0")
+    for name in TILED_ENTRIES:
         res, args = _lib._SIGS[name]
         out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
     out.append("```")

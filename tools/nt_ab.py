@@ -3,6 +3,7 @@
 2-stage kernel with the same accumulation order).
 
     B=256 VARS=8,10 ROUNDS=5 python tools/nt_ab.py [tag]      (M=8192: other row counts; SHAPES=2304x768,...: a subset)
+    VARS=-1,999: by shape with the row-major weight against by shape with the tiled weight (v + 1000: variant v, B from the tiled copy)
 """
 import os
 import sys
@@ -11,9 +12,19 @@ import statistics
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mm-vqa-healthcare_amd"))
 import torch  # noqa: E402
-from m3ae_amd import ops  # noqa: E402
+from m3ae_amd import ops, tiled_b  # noqa: E402
 
 VARS = tuple(int(v) for v in os.environ.get("VARS", "8,10").split(","))   # v + 100 * p: variant v with output-store policy p (1 plain, 2 nt, 3 sc1)
+                                                                          # + 1000: B is the tiled copy of the weight (999 = by shape, tiled)
+
+
+def select(v):
+    """Set the kernel selectors of variant code v; returns whether the call reads the tiled weight."""
+    tiled = v >= 900
+    if tiled:
+        v -= 1000
+    ops.GEMM_NT_VARIANT, ops.GEMM_ST_POLICY = (v % 100 if v >= 0 else -1), (v // 100 if v >= 0 else 0)
+    return tiled
 ROUNDS = int(os.environ.get("ROUNDS", 5))
 ITERS = int(os.environ.get("ITERS", 10))
 SHAPES = os.environ.get("SHAPES", "")
@@ -62,14 +73,16 @@ def main():
             kw = dict(dact_aux=aux, dact=ops.ACT_MULAUX)
         elif kind == "dgelu":
             kw = dict(dact_aux=aux, dact=ops.ACT_GELU)
-        fn = lambda: ops.gemm(x, k, 1, w, 1, k, y, n, m, n, k, **kw)
+        wt = tiled_b.tile_reference(w) if any(v >= 900 for v in VARS) else None
+        tiled = False
+        fn = lambda: ops.gemm(x, k, 1, wt if tiled else w, 1, k, y, n, m, n, k, b_tiled=tiled, **kw)
         # bit identity against variant 4
         ops.GEMM_NT_VARIANT = 4
         fn()
         ref, ref_pre = y.clone(), pre.clone()
         ident = {}
         for v in VARS:
-            ops.GEMM_NT_VARIANT, ops.GEMM_ST_POLICY = (v % 100 if v >= 0 else -1), (v // 100 if v >= 0 else 0)
+            tiled = select(v)
             y.fill_(float("nan")); pre.fill_(float("nan"))
             fn()
             torch.cuda.synchronize()
@@ -80,7 +93,7 @@ def main():
         res = {v: [] for v in VARS}
         for r in range(ROUNDS):
             for v in VARS:
-                ops.GEMM_NT_VARIANT, ops.GEMM_ST_POLICY = (v % 100 if v >= 0 else -1), (v // 100 if v >= 0 else 0)
+                tiled = select(v)
                 res[v].append(time_it(fn))
         line = []
         for v in VARS:
@@ -88,7 +101,7 @@ def main():
             tot[v] += md
             line.append(f"v{v}: {mn * 1e3:7.1f} / {md * 1e3:7.1f} us {2.0 * m * n * k / md / 1e9:6.0f} TF/s {'==' if ident[v] else 'DIFF'}")
         print(f"  {n:5d}x{k:5d} {kind:14s} " + " | ".join(line), flush=True)
-        del x, w, y, aux, pre
+        del x, w, wt, y, aux, pre
     ops.GEMM_NT_VARIANT, ops.GEMM_ST_POLICY = -1, 0
     print(f"[{tag}] sum of medians: " + "  ".join(f"v{v}: {tot[v] * 1e3:8.1f} us" for v in VARS), flush=True)
 
