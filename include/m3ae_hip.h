@@ -37,6 +37,8 @@ extern "C" {
  *    [B][H][Lq][Lk]; no descriptor changed. */
 /* 4 (additive): device image transform.  m3ae_image_resample_u8 / m3ae_image_resample_workspace_bytes (Pillow-exact bicubic resize +
  *    centre crop + ToTensor / Normalize from the decoded source bytes); no descriptor changed. */
+/* 4 (additive): m3ae_image_resample_tables builds the tables of m3ae_image_resample_u8 on the device (random resized crop: a
+ *    resample of its own per image); plan field 13 marks the records it writes; no descriptor changed. */
 /* 4 (additive): dropout row map.  m3ae_gemm_rows, m3ae_attn_fwd_rows / m3ae_attn_bwd_rows, m3ae_layernorm_bwd_drop_rows and
  *    m3ae_dropout_rows: the entry points they are named after with (row_base, row_step), so that a call on a subset of a tensor's
  *    rows draws the dropout masks of the full tensor (see m3ae_dropout); no descriptor changed. */
@@ -386,7 +388,7 @@ int m3ae_image_normalize_u8(const uint8_t* in, float* out, int64_t B, int64_t H,
  *         surviving output rows read: the horizontal pass runs on these alone), 6 ksize_x, 7 ksize_y (row lengths of the two
  *         coefficient tables), 8..11 offsets (in int32) into tab of: x bounds [size][2], x coefficients [size][ksize_x], y bounds
  *         [size][2] (absolute source rows), y coefficients [size][ksize_y], 12 first intermediate row of this image (running sum
- *         of nrows), 13..15 zero.  w <= 8192.
+ *         of nrows), 13 read by m3ae_image_resample_tables alone, 14..15 zero.  w <= 8192.
  *   tab   int32 tables as addressed by plan
  *   workspace  uint8 intermediates [sum nrows][size * 3 rounded up to 4]; m3ae_image_resample_workspace_bytes(sum nrows, size)
  *   out   fp32 [B][3][size][size] = (u / 255 - mean[c]) / std[c];  out_u8: NULL, or uint8 [B][size][size][3] (the crop itself)
@@ -397,6 +399,16 @@ int64_t m3ae_image_resample_workspace_bytes(int64_t total_rows, int64_t size);
 int m3ae_image_resample_u8(const uint8_t* src, int64_t src_bytes, const int64_t* plan, const int32_t* tab, int64_t tab_ints, int64_t B,
                            int64_t size, uint8_t* workspace, int64_t workspace_bytes, float* out, uint8_t* out_u8,
                            const float* mean3, const float* std3, void* stream);
+/* Coefficient tables of m3ae_image_resample_u8 built on the device (csrc/image.hip), for plans whose every image has a resample of
+ * its own: transforms/transform.py:70-77, RandomResizedCrop(size, scale=(0.9, 1.0), BICUBIC) -- image b is the box (plan w x h at
+ * plan offset, the full image's pitch) resized to size x size, row0 = 0, nrows = h.  For every plan record with field 13 != 0 the
+ * kernel writes the four tables at the record's offsets 8..11: bounds [size][2] and coefficients [size][ksize] (zero-filled past
+ * the taps) of the resamples w -> size and h -> size, outputs 0 .. size - 1, in float64 in Pillow's operation order without
+ * contraction: bit-equal to m3ae_amd/resample.py's axis_table.  Records that share tables mark one owner.  A record whose
+ * extents do not lie inside tab, or whose ksize_x / ksize_y is smaller than Pillow's ksize of its axis, is left unwritten whole.
+ * Call it in front of m3ae_image_resample_u8 on the same stream.  Returns as m3ae_image_resample_u8: M3AE_ERR_ARG for a null
+ * pointer or a non-positive B / size / tab_ints, M3AE_ERR_UNSUPPORTED for B > 65535 or size > 4096. */
+int m3ae_image_resample_tables(const int64_t* plan, int64_t B, int64_t size, int32_t* tab, int64_t tab_ints, void* stream);
 int m3ae_vit_tokens_fwd(const void* patch, const float* cls, const float* pos, void* out, int64_t B, int64_t G,
                         int64_t D, int dtype, void* stream);
 int m3ae_vit_tokens_bwd(const void* d_out, void* d_patch, float* d_cls, float* d_pos, int64_t B, int64_t G,

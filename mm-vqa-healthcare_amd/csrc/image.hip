@@ -15,6 +15,14 @@
 // Images of different sizes share a launch: blockIdx.y is the image, workgroups beyond an image's extent leave at once.
 // Every plan field and table bound is checked against the buffer sizes before it is used as an address: a wrong plan leaves its
 // image unwritten instead of reading or writing outside the caller's buffers.
+//
+// Tables built on the device (train transform "clip_resizedcrop": a random crop box per image and epoch, so every image has its
+// own tables and the host's Python loop per output cannot keep up).  resample_tables_kernel restates resample.axis_table --
+// Pillow's precompute_coeffs + normalize_coeffs_8bpc -- one float64 operation per source operation, in the source's order, under
+// `#pragma clang fp contract(off)`: no multiply-add is fused, division is the IEEE one, conversions truncate.  With every
+// operation correctly rounded there is one answer again, and the tables equal the host's bit for bit.  One thread per (image, axis,
+// output); the weights are not kept (ksize reaches 149): one loop over the taps sums them, a second recomputes each, divides,
+// rounds to 22 bits and stores.
 #include "common.h"
 
 namespace {
@@ -24,7 +32,9 @@ constexpr int RS_LDS_PIX = 8192;    // staged pixels (32 KiB): the widest source
 constexpr int RS_ROWS = 8;          // source rows per workgroup pass (accumulators: 8 rows x 3 channels)
 constexpr int RV_THREADS = 256;
 constexpr int RV_ROWS = 4;          // output rows per workgroup of pass 2
+constexpr int RT_THREADS = 256;     // table build: threads along (axis, output index)
 constexpr int PLAN_FIELDS = 16;
+constexpr int PLAN_BUILD = 13;      // plan field: this record owns a table set the table kernel writes
 constexpr int PREC = 22;
 
 struct Img {
@@ -156,6 +166,68 @@ __global__ __launch_bounds__(RV_THREADS) void resample_v_kernel(const int64_t* _
     }
 }
 
+// Pillow's bicubic_filter, a = -0.5, in its two Horner forms (resample._bicubic)
+DEVINL double bicubic_weight(double x) {
+#pragma clang fp contract(off)
+    const double a = -0.5;
+    x = __builtin_fabs(x);
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
+// row length Pillow gives the coefficients of in -> out (resample.axis_ksize); in < 2^24, out >= 1: fits an int
+DEVINL int axis_ksize(int in, int out) {
+#pragma clang fp contract(off)
+    if (in == out) return 1;
+    const double scale = (double)in / (double)out;
+    return (int)__builtin_ceil(2.0 * (scale < 1.0 ? 1.0 : scale)) * 2 + 1;
+}
+
+__global__ __launch_bounds__(RT_THREADS) void resample_tables_kernel(const int64_t* __restrict__ plan, int size,
+                                                                     int32_t* __restrict__ tab, int64_t tab_ints) {
+#pragma clang fp contract(off)
+    const int64_t* p = plan + (int64_t)blockIdx.y * PLAN_FIELDS;
+    if (p[PLAN_BUILD] == 0) return;
+    const int64_t w = p[1], h = p[2], ksx = p[6], ksy = p[7], xb = p[8], xk = p[9], yb = p[10], yk = p[11];
+    // the whole record or nothing (wave-uniform): sizes, row lengths and the four extents inside tab, as load_plan checks them
+    if (!(w > 0 && w < (1 << 24) && h > 0 && h < (1 << 24) && ksx > 0 && ksx < (1 << 20) && ksy > 0 && ksy < (1 << 20) && xb >= 0 &&
+          xb + 2 * size <= tab_ints && xk >= 0 && xk + size * ksx <= tab_ints && yb >= 0 && yb + 2 * size <= tab_ints && yk >= 0 &&
+          yk + size * ksy <= tab_ints))
+        return;
+    if (axis_ksize((int)w, size) > ksx || axis_ksize((int)h, size) > ksy) return;   // a row of taps would not fit the plan's rows
+    const int idx = blockIdx.x * RT_THREADS + threadIdx.x;
+    if (idx >= 2 * size) return;
+    const int axis = idx >= size, i = idx - axis * size;
+    const int in = (int)(axis ? h : w), ks = (int)(axis ? ksy : ksx);
+    int32_t* bounds = tab + (axis ? yb : xb) + 2 * i;
+    int32_t* k = tab + (axis ? yk : xk) + (int64_t)i * ks;
+    int xmin = i, xmax = 1;
+    if (in == size) {   // Pillow skips the pass: the identity row
+        k[0] = 1 << PREC;
+    } else {
+        const double scale = (double)in / (double)size;
+        const double filterscale = scale < 1.0 ? 1.0 : scale;
+        const double support = 2.0 * filterscale, ss = 1.0 / filterscale;
+        const double center = (i + 0.5) * scale;
+        xmin = (int)(center - support + 0.5);
+        if (xmin < 0) xmin = 0;
+        xmax = (int)(center + support + 0.5);
+        if (xmax > in) xmax = in;
+        xmax -= xmin;
+        if (xmax > ks) return;   // cannot happen: xmax <= axis_ksize(in, size) <= ks
+        double ww = 0.0;
+        for (int x = 0; x < xmax; ++x) ww += bicubic_weight((x + xmin - center + 0.5) * ss);   // ascending x
+        for (int x = 0; x < xmax; ++x) {
+            double v = bicubic_weight((x + xmin - center + 0.5) * ss);
+            if (ww != 0.0) v = v / ww;
+            k[x] = (int)(v < 0 ? -0.5 + v * (double)(1 << PREC) : 0.5 + v * (double)(1 << PREC));
+        }
+    }
+    for (int x = xmax; x < ks; ++x) k[x] = 0;
+    bounds[0] = xmin;
+    bounds[1] = xmax;
+}
+
 inline int64_t inter_pitch(int64_t size) { return (size * 3 + 3) & ~(int64_t)3; }
 
 }  // namespace
@@ -184,5 +256,13 @@ extern "C" int m3ae_image_resample_u8(const uint8_t* src, int64_t src_bytes, con
     hipLaunchKernelGGL(resample_v_kernel, dim3((unsigned)cdiv(size, RV_ROWS), (unsigned)B), dim3(RV_THREADS),
                        (size_t)(RV_ROWS * ipitch), s, plan, tab, tab_ints, (int)size, (int)ipitch, workspace, ws_rows, out, out_u8,
                        mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+    return hip_launch_status();
+}
+
+extern "C" int m3ae_image_resample_tables(const int64_t* plan, int64_t B, int64_t size, int32_t* tab, int64_t tab_ints, void* stream) {
+    if (!plan || !tab || B <= 0 || size <= 0 || tab_ints <= 0) return M3AE_ERR_ARG;
+    if (B > 65535 || size > 4096) return M3AE_ERR_UNSUPPORTED;   // grid.y; the size cap of m3ae_image_resample_u8
+    hipLaunchKernelGGL(resample_tables_kernel, dim3((unsigned)cdiv(2 * size, RT_THREADS), (unsigned)B), dim3(RT_THREADS), 0,
+                       (hipStream_t)stream, plan, (int)size, tab, tab_ints);
     return hip_launch_status();
 }

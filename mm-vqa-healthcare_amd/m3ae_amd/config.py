@@ -60,6 +60,10 @@ DEFAULTS = dict(
     # ln_post, as under the reference's autocast, config.py:146 precision=16; every GEMM and attention operand stays bf16).  No
     # effect under compute_dtype "fp32" / "fp32x3", whose stream is fp32 already.  Not available with graph.GraphedStep.
     clip_residual_dtype="bf16",
+    # image transform per split (reference config.py:41-42; m3ae_amd/data.py).  Train: "clip" | "clip_resizedcrop"
+    # (RandomResizedCrop(size, scale=(0.9, 1.0), BICUBIC) in front of the CLIP tail, transform.py:70-77: one crop box per image
+    # and epoch, resample.random_resized_crop_box).  Every other split runs "clip" (base_dataset.py:39-41 strips the suffix).
+    train_transform_keys=["clip"], val_transform_keys=["clip"],
 )
 
 NAMED = {
@@ -86,6 +90,7 @@ NAMED = {
     "clip16_large": dict(vit="ViT-L/16", image_size=224, patch_size=16, input_image_embed_size=1024),  # extension
     "text_roberta": dict(tokenizer="roberta-base", vocab_size=50265, input_text_embed_size=768),
     "text_roberta_large": dict(tokenizer="roberta-large", vocab_size=50265, input_text_embed_size=1024),
+    "clip_resizedcrop": dict(train_transform_keys=["clip_resizedcrop"]),   # config.py:280-282
 }
 
 # widths the reference reads out of downloaded checkpoints
@@ -112,10 +117,30 @@ def clip_residual_dtype(cfg):
     return v
 
 
+TRAIN_TRANSFORM_KEYS = ("clip", "clip_resizedcrop")
+VAL_TRANSFORM_KEYS = ("clip",)
+
+
+def transform_keys(cfg):
+    """The validated (train, val) transform names of a config dict (defaults "clip").  Each key is a list of one name, as on the
+    reference's command line; a split other than train drops the "_resizedcrop" suffix first (base_dataset.py:39-41).  The
+    reference's other names ("clip_randaug", "imagenet*": RandAugment) are not available."""
+    out = []
+    for name, allowed, strip in (("train_transform_keys", TRAIN_TRANSFORM_KEYS, False), ("val_transform_keys", VAL_TRANSFORM_KEYS, True)):
+        v = cfg.get(name, ["clip"])
+        ok = isinstance(v, (list, tuple)) and len(v) == 1 and isinstance(v[0], str)
+        key = v[0].replace("_resizedcrop", "") if ok and strip else (v[0] if ok else None)
+        if key not in allowed:
+            raise ValueError(f"{name} must be a list of one of {allowed}, got {v!r}")
+        out.append(key)
+    return tuple(out)
+
+
 def resolve_arch(cfg):
     """Fill vit_width/vit_layers/text_* from the `vit` / `tokenizer` names unless given explicitly."""
     cfg = dict(cfg)
     clip_residual_dtype(cfg)
+    transform_keys(cfg)
     vit = _ARCH_VIT.get(cfg["vit"], _ARCH_VIT["ViT-B/16"])
     for k, v in vit.items():
         cfg.setdefault(k, v)

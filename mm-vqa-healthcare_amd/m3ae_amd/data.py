@@ -34,6 +34,14 @@ distinct (table, image row) -- `collate_dedup`: the workers decode and transform
 `image_u8` is [U, ...] (the device transform receives U sources), and the batch carries `image_index` (int64 [B]: the image row
 of every sample) with the index tables `M3AETransformerSS.infer` needs (`image_groups`, ops.ImageGroups; pinned, uploaded with
 the batch).  The samples of a batch and their order are those of the plain path.  `transform_stats.decodes` counts the decodes.
+
+`train_transform_keys=["clip_resizedcrop"]` (named config `clip_resizedcrop`; transforms/transform.py:70-77): every image a TRAIN
+split loads under `train_batches(epoch)` is cropped to a box of `resample.random_resized_crop_box` and the box resized to size x
+size (`clip_resized_crop`), under either `image_transform`; the device transform gets the whole source plus the box and builds the
+box's coefficient tables on the GPU (`m3ae_image_resample_tables`).  The box is drawn from a `random.Random` keyed by (seed, epoch,
+global sample index, slot) -- slot 0 the sample's image, 1 + i its i-th false image; the reference, too, draws per loaded image --
+or, under `image_dedup`, by (seed, epoch, image key): one box per distinct image and epoch (the datasets' `box_key`).  No global
+generator is read, so epoch e gives the same batches whenever it runs.  `val_batches` and the val / test sets never crop.
 """
 import ctypes as C
 import io
@@ -69,6 +77,15 @@ def clip_resize_crop(img, size):
     return np.array(img, dtype=np.uint8)  # a writable copy (torch.from_numpy)
 
 
+def clip_resized_crop(img, size, box):
+    """PIL image, box (left, top, cw, ch) -> uint8 [size, size, 3]: transform.py:70-74 with the box given -- torchvision's
+    `resized_crop` (crop, then resize to size x size, BICUBIC) on the RGBA image; CenterCrop(size) is then the identity; RGB."""
+    from PIL import Image
+    left, top, cw, ch = box
+    img = img.convert("RGBA").crop((left, top, left + cw, top + ch)).resize((size, size), Image.BICUBIC).convert("RGB")
+    return np.array(img, dtype=np.uint8)
+
+
 class TransformStats(dict):
     """{"device": n, "fallback": n}: images the device transform took from their source bytes / images the host transformed
     (real transparency, or beyond the staging caps); counted from the loader's worker threads."""
@@ -87,19 +104,23 @@ class TransformStats(dict):
             self.decodes += 1
 
 
-def load_image_u8(raw, size, image_transform="host", stats=None):
+def load_image_u8(raw, size, image_transform="host", stats=None, box_key=None):
     """Encoded image bytes -> uint8 [size, size, 3] (the finished crop, "host") or the source the device transform resizes
-    ("device": uint8 [h, w, 3], or the host-made crop of an image it does not take)."""
+    ("device": uint8 [h, w, 3], or the host-made crop of an image it does not take).
+    `box_key` (a train split under "clip_resizedcrop"; a tuple of ints / strings): the image is cropped to the box that key draws
+    (resample.box_rng, random_resized_crop_box) and the box resized; the device route then returns (source, box) for
+    `resample.pack_batch(..., boxes=)`."""
     from PIL import Image
     img = Image.open(io.BytesIO(raw))
     if stats is not None:
         stats.count_decode()
+    box = None if box_key is None else resample.random_resized_crop_box(*img.size, resample.box_rng(*box_key))
     if image_transform != "device":
-        return clip_resize_crop(img, size)
-    route, a = resample.prepare(img, size)
+        return clip_resize_crop(img, size) if box is None else clip_resized_crop(img, size, box)
+    route, *a = resample.prepare(img, size, box)
     if stats is not None:
         stats.count(route)
-    return a
+    return a[0] if box is None else tuple(a)
 
 
 def normalize_on_device(u8_nhwc, stream=None):
@@ -211,9 +232,12 @@ class MLMCollator:
 class ArrowVQADataset:
     """BaseDataset + VQAVQARADDataset for `{data_dir}/vqa_vqa_rad_{split}.arrow` (or any `names`)."""
 
-    def __init__(self, data_dir, split, image_size, max_text_len, tokenizer, names=None, image_transform="host", stats=None):
+    def __init__(self, data_dir, split, image_size, max_text_len, tokenizer, names=None, image_transform="host", stats=None,
+                 train_transform="clip", seed=0, box_key="sample"):
         import pyarrow as pa
         self.image_transform, self.stats = image_transform, stats
+        # the random resized crop: train split only (base_dataset.py:39-41), and only for a fetch that names its epoch
+        self.augment, self.seed, self.box_key = split == "train" and train_transform == "clip_resizedcrop", seed, box_key
         self.names = names or [f"vqa_vqa_rad_{split}"]
         tables = []
         for name in self.names:
@@ -230,12 +254,21 @@ class ArrowVQADataset:
     def __len__(self):
         return len(self.index_mapper)
 
-    def image_u8(self, row):
-        return load_image_u8(self.table["image"][row].as_py(), self.image_size, self.image_transform, self.stats)
+    def image_u8(self, row, box_key=None):
+        return load_image_u8(self.table["image"][row].as_py(), self.image_size, self.image_transform, self.stats, box_key)
+
+    def get(self, index, epoch=None, key_index=None):
+        """Sample `index`; with `epoch` (train_batches) on an augmenting dataset its image is cropped to the box of (seed, epoch,
+        key_index or index, slot 0) -- or of its image key, `box_key == "image"`."""
+        sample, key = self.sample_without_image(index)
+        if not self.augment or epoch is None:
+            return {"image_u8": self.image_u8(key[1]), **sample}
+        if self.box_key == "image":
+            return {"image_u8": self.image_by_key(key, epoch), **sample}
+        return {"image_u8": self.image_u8(key[1], (self.seed, epoch, index if key_index is None else key_index, 0)), **sample}
 
     def __getitem__(self, index):
-        sample, (_, row) = self.sample_without_image(index)
-        return {"image_u8": self.image_u8(row), **sample}
+        return self.get(index)
 
     def sample_without_image(self, index):
         """(the sample of `__getitem__` without its "image_u8", its image key): samples with equal keys show the same image, which
@@ -255,8 +288,11 @@ class ArrowVQADataset:
             "qid": t["question_id"][row][qi].as_py(),
         }, ("+".join(self.names), row)
 
-    def image_by_key(self, key):
-        return self.image_u8(key[1])
+    def image_by_key(self, key, epoch=None):
+        """The image of an image key; with `epoch` on an augmenting dataset, cropped to that image's box of the epoch."""
+        if not self.augment or epoch is None:
+            return self.image_u8(key[1])
+        return self.image_u8(key[1], (self.seed, epoch, key))
 
 
 class ArrowCaptionDataset:
@@ -268,9 +304,10 @@ class ArrowCaptionDataset:
     reference's draws.  A sample that fails to decode is replaced by a random one (:158-160)."""
 
     def __init__(self, data_dir, name, split, image_size, max_text_len, tokenizer, draw_false_image=0, image_transform="host",
-                 stats=None):
+                 stats=None, train_transform="clip", seed=0, box_key="sample"):
         import pyarrow as pa
         self.image_transform, self.stats = image_transform, stats
+        self.augment, self.seed, self.box_key = split == "train" and train_transform == "clip_resizedcrop", seed, box_key
         assert split in ("train", "val", "test")
         self.names = [f"{name}_{split}"]
         path = os.path.join(data_dir, f"{self.names[0]}.arrow")
@@ -286,27 +323,39 @@ class ArrowCaptionDataset:
     def __len__(self):
         return len(self.index_mapper)
 
-    def image_u8(self, row):
-        return load_image_u8(self.table["image"][row].as_py(), self.image_size, self.image_transform, self.stats)
+    def image_u8(self, row, box_key=None):
+        return load_image_u8(self.table["image"][row].as_py(), self.image_size, self.image_transform, self.stats, box_key)
 
-    def get_suite(self, index):
+    def get_suite(self, index, epoch=None, key_index=None):
+        """`epoch` (train_batches) on an augmenting dataset: every image loaded is cropped to a box of its own -- (seed, epoch,
+        key_index or index, slot), slot 0 the sample's image and 1 + i its i-th false image; per image key, `box_key == "image"`."""
+        if not self.augment or epoch is None:
+            load = lambda row, slot: self.image_u8(row)
+        elif self.box_key == "image":
+            load = lambda row, slot: self.image_u8(row, (self.seed, epoch, (self.names[0], row)))
+        else:
+            key = index if key_index is None else key_index
+            load = lambda row, slot: self.image_u8(row, (self.seed, epoch, key, slot))
         while True:
             try:
                 row, ci = self.index_mapper[index]
                 text = self.all_texts[row][ci]
                 enc = self.tokenizer(text, padding="max_length", truncation=True, max_length=self.max_text_len)
-                ret = {"image_u8": self.image_u8(row), "text": text, "input_ids": list(enc["input_ids"]),
+                ret = {"image_u8": load(row, 0), "text": text, "input_ids": list(enc["input_ids"]),
                        "attention_mask": list(enc["attention_mask"]), "img_index": row, "cap_index": ci,
                        "raw_index": index, "replica": ci > 0}
                 for rep in range(self.draw_false_image):
                     frow, _ = self.index_mapper[random.randint(0, len(self.index_mapper) - 1)]
-                    ret[f"false_image_u8_{rep}"] = self.image_u8(frow)
+                    ret[f"false_image_u8_{rep}"] = load(frow, 1 + rep)
                 return ret
             except Exception as e:  # noqa: BLE001  (base_dataset.py:158-160)
                 print(f"Error while read file idx {index} in {self.names[0]} -> {e}")
                 index = random.randint(0, len(self.index_mapper) - 1)
 
-    __getitem__ = get_suite
+    get = get_suite
+
+    def __getitem__(self, index):
+        return self.get_suite(index)
 
 
 class ConcatDataset:
@@ -314,16 +363,21 @@ class ConcatDataset:
 
     def __init__(self, parts):
         self.parts = list(parts)
+        self.augment = any(getattr(p, "augment", False) for p in self.parts)
         self.ends = np.cumsum([len(p) for p in self.parts]).tolist()
 
     def __len__(self):
         return self.ends[-1] if self.ends else 0
 
-    def __getitem__(self, index):
+    def get(self, index, epoch=None):
+        """Sample `index`; `epoch` reaches the part with the GLOBAL index as the key of its crop boxes."""
         for p, end in zip(self.parts, self.ends):
             if index < end:
-                return p[index - (end - len(p))]
+                return p.get(index - (end - len(p)), epoch, key_index=index)
         raise IndexError(index)
+
+    def __getitem__(self, index):
+        return self.get(index)
 
 
 def collate_host(samples, pin=True, mlm_collator=None, resample_size=None, pmap=map, images=None, image_index=None):
@@ -336,7 +390,9 @@ def collate_host(samples, pin=True, mlm_collator=None, resample_size=None, pmap=
     B = len(samples)
     S = max(len(s["input_ids"]) for s in samples)
     if resample_size:
-        stack_list = lambda arrays: resample.pack_batch(arrays, resample_size, pin=pin, pmap=pmap)
+        def stack_list(arrays):   # (source, box) pairs under "clip_resizedcrop"
+            boxes = [a[1] for a in arrays] if isinstance(arrays[0], tuple) else None
+            return resample.pack_batch([a[0] for a in arrays] if boxes else arrays, resample_size, pin=pin, pmap=pmap, boxes=boxes)
     else:
         stack_list = lambda arrays: torch.from_numpy(np.stack(arrays))
     stack = lambda k: stack_list([s[k] for s in samples])
@@ -369,16 +425,17 @@ def collate_host(samples, pin=True, mlm_collator=None, resample_size=None, pmap=
     return out
 
 
-def collate_dedup(ds, indices, pmap=map, **collate_kw):
+def collate_dedup(ds, indices, pmap=map, epoch=None, **collate_kw):
     """`collate_host` of the samples `indices` of a dataset with `sample_without_image` / `image_by_key` (ArrowVQADataset), per
     distinct image: every distinct (table, image row) of the batch is loaded ONCE (through `pmap`: the loader's thread pool), in
     the order of its first sample.  Same samples, same order, same keys as the plain collate plus `image_index` / `image_groups`;
-    `image_u8[image_index]` is the plain batch's `image_u8`."""
+    `image_u8[image_index]` is the plain batch's `image_u8`.  `epoch` (train_batches): an augmenting dataset crops every distinct
+    image to its box of that epoch -- the plain batch of a dataset with `box_key == "image"`."""
     metas = list(pmap(ds.sample_without_image, indices))
     rows, index = {}, []
     for _, key in metas:
         index.append(rows.setdefault(key, len(rows)))
-    images = list(pmap(ds.image_by_key, list(rows)))
+    images = list(pmap(ds.image_by_key if epoch is None else (lambda key: ds.image_by_key(key, epoch)), list(rows)))
     return collate_host([m[0] for m in metas], pmap=pmap, images=images, image_index=index, **collate_kw)
 
 
@@ -411,8 +468,9 @@ def _finish_image(u8, cur):
     if isinstance(u8, torch.Tensor):
         u8.record_stream(cur)
         return normalize_on_device(u8)
-    for k in ("src", "plan", "tab"):   # uploaded on the copy stream, read here
-        u8[k].record_stream(cur)
+    for k in ("src", "plan", "tab"):   # uploaded on the copy stream, read here (a pack with boxes has no uploaded tables)
+        if k in u8:
+            u8[k].record_stream(cur)
     return resample.resample_on_device(u8)
 
 
@@ -456,7 +514,11 @@ class ArrowDataModule:
         if self.image_dedup and any(loss_names.get(k, 0) > 0 for k in ("mim", "itm")):
             raise ValueError("image_dedup=True cannot be combined with the mim / itm objectives (loss_names): they read the image "
                              "pixels per sample")
-        tf = dict(image_transform=self.image_transform, stats=self.transform_stats)
+        from .config import transform_keys
+        self.train_transform = transform_keys(cfg)[0]
+        # one crop box per distinct image and epoch under image_dedup, else one per loaded image (the reference's rule)
+        tf = dict(image_transform=self.image_transform, stats=self.transform_stats, train_transform=self.train_transform,
+                  seed=cfg["seed"], box_key="image" if self.image_dedup else "sample")
         if any(n in ("roco", "medicat") for n in names):   # the pre-training caption tables (config.py:22,31: draw_false_image = 1)
             mk = lambda split: ConcatDataset([ArrowCaptionDataset(root, n, split, cfg["image_size"], cfg["max_text_len"],
                                                                   self.tokenizer, cfg.get("draw_false_image", 0), **tf)
@@ -490,8 +552,9 @@ class ArrowDataModule:
         idx += idx[: total - len(idx)]
         return idx[self.rank::self.world]
 
-    def _stream(self, ds, idx, drop_last):
-        """Generator of device batches; host decode runs `prefetch` batches ahead in a thread pool."""
+    def _stream(self, ds, idx, drop_last, epoch=None):
+        """Generator of device batches; host decode runs `prefetch` batches ahead in a thread pool.  `epoch`: the training epoch
+        the samples are fetched for (the key of the random resized crop's boxes); None never crops."""
         chunks = [idx[i:i + self.B] for i in range(0, len(idx), self.B)]
         if drop_last:
             chunks = [c for c in chunks if len(c) == self.B]
@@ -499,6 +562,9 @@ class ArrowDataModule:
         stop = threading.Event()
 
         dedup = self.image_dedup and hasattr(ds, "sample_without_image")   # (the caption tables ignore the flag)
+        if not getattr(ds, "augment", False):
+            epoch = None
+        fetch = ds.__getitem__ if epoch is None else (lambda i: ds.get(i, epoch))
 
         def producer():
             kw = dict(mlm_collator=self.mlm_collator,
@@ -508,9 +574,9 @@ class ArrowDataModule:
                     if stop.is_set():
                         break
                     if dedup:
-                        q.put(collate_dedup(ds, c, pmap=pool.map, **kw))
+                        q.put(collate_dedup(ds, c, pmap=pool.map, epoch=epoch, **kw))
                     else:
-                        q.put(collate_host(list(pool.map(ds.__getitem__, c)), pmap=pool.map, **kw))
+                        q.put(collate_host(list(pool.map(fetch, c)), pmap=pool.map, **kw))
             q.put(None)
 
         th = threading.Thread(target=producer, daemon=True)
@@ -534,7 +600,7 @@ class ArrowDataModule:
                     th.join(timeout=0.05)
 
     def train_batches(self, epoch):
-        return self._stream(self.train_set, self._indices(self.train_set, epoch, True), drop_last=False)
+        return self._stream(self.train_set, self._indices(self.train_set, epoch, True), drop_last=False, epoch=epoch)
 
     def val_batches(self):
         return self._stream(self.val_set, self._indices(self.val_set, 0, False), drop_last=False)

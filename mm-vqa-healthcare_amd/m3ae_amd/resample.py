@@ -14,8 +14,18 @@ contract a multiply-add and move a weight by one unit), and uploaded as data.
 
 Folding the crop: only the `size` output columns / rows that survive `CenterCrop` get a table row, and `row0` / `nrows`
 name the source rows those output rows read -- the horizontal pass runs on them alone.
+
+Train transform "clip_resizedcrop" (transforms/transform.py:70-77): `RandomResizedCrop(size, scale=(0.9, 1.0), BICUBIC)` =
+`img.crop(box).resize((size, size), BICUBIC)` with a box drawn per image and epoch (`random_resized_crop_box`).  To the kernels
+a box is a plan record: the source offset of its corner, w = cw, h = ch and the full image's pitch.  Every image then has
+tables of its own (two axes of Python loops per image, under the GIL), so a pack made with `boxes` carries no tables:
+`m3ae_image_resample_tables` (csrc/image.hip) builds them on the GPU from the plan in front of the two passes, `axis_table`'s
+float64 operations one by one with contraction off -- bit-equal tables, tests/test_gpu_resized_crop.py.
 """
 import ctypes as C
+import hashlib
+import math
+import random
 import threading
 
 import numpy as np
@@ -23,7 +33,7 @@ import numpy as np
 PRECISION_BITS = 22                # 32 - 8 - 2 (Resample.c)
 PLAN_FIELDS = 16                   # int64 per image, see PLAN_* below; must match csrc/image.hip
 (PLAN_SRC, PLAN_W, PLAN_H, PLAN_PITCH, PLAN_ROW0, PLAN_NROWS, PLAN_KSX, PLAN_KSY, PLAN_XB, PLAN_XK, PLAN_YB, PLAN_YK,
- PLAN_IROW0) = range(13)
+ PLAN_IROW0, PLAN_BUILD) = range(14)   # PLAN_BUILD: 1 = m3ae_image_resample_tables writes this record's tables
 # Eligibility caps of the device path.  The horizontal pass stages whole source rows in LDS (one dword per pixel, 32 KiB),
 # so a row may hold at most MAX_SOURCE_WIDTH pixels; MAX_SOURCE_PIXELS bounds one image's share of the pinned staging
 # buffer (48 MiB of RGB).  Larger sources take the host path.
@@ -80,6 +90,45 @@ def axis_table(in_size, out_size, first, count):
         bounds[i] = (xmin, xmax)
         coeffs[i, :xmax] = k
     return bounds, coeffs
+
+
+def axis_ksize(in_size, out_size):
+    """Row length of `axis_table`'s coefficients (Pillow's ksize; 1 for the identity table)."""
+    if in_size == out_size:
+        return 1
+    return int(np.ceil(2.0 * max(in_size / out_size, 1.0))) * 2 + 1
+
+
+# ------------------------------------------------------------------------------------------------------------
+# the crop box of RandomResizedCrop
+# ------------------------------------------------------------------------------------------------------------
+def box_rng(*key):
+    """`random.Random` seeded from an integer digest of `key` (ints, strings, tuples of them): the same key draws the same box in
+    any process, and no global or torch generator state is read or advanced."""
+    return random.Random(int.from_bytes(hashlib.blake2b(repr(key).encode(), digest_size=8).digest(), "little"))
+
+
+def random_resized_crop_box(w, h, rng, scale=(0.9, 1.0), ratio=(3 / 4, 4 / 3)):
+    """(left, top, cw, ch): torchvision's `RandomResizedCrop.get_params` restated on a `random.Random`.  Ten tries of an area
+    uniform in scale * w * h and an aspect ratio log-uniform in `ratio`; the first box that fits gets a uniform position.
+    If none fits: the central box of the nearest allowed ratio (the whole image when its ratio is allowed).  The reference's
+    own draws depend on its worker processes, so it is the distribution that is restated, not a stream."""
+    log_lo, log_hi = math.log(ratio[0]), math.log(ratio[1])
+    for _ in range(10):
+        target = w * h * rng.uniform(scale[0], scale[1])
+        aspect = math.exp(rng.uniform(log_lo, log_hi))
+        cw, ch = int(round(math.sqrt(target * aspect))), int(round(math.sqrt(target / aspect)))
+        if 0 < cw <= w and 0 < ch <= h:
+            top = rng.randint(0, h - ch)
+            left = rng.randint(0, w - cw)
+            return left, top, cw, ch
+    if w / h < min(ratio):
+        cw, ch = w, int(round(w / min(ratio)))
+    elif w / h > max(ratio):
+        cw, ch = int(round(h * max(ratio))), h
+    else:
+        cw, ch = w, h
+    return (w - cw) // 2, (h - ch) // 2, cw, ch
 
 
 class Tables:
@@ -143,19 +192,27 @@ def resample_model(rgb, size, t=None):
 # ------------------------------------------------------------------------------------------------------------
 # eligibility
 # ------------------------------------------------------------------------------------------------------------
-def prepare(img, size):
+def prepare(img, size, box=None):
     """PIL image -> ("device", uint8 [h, w, 3] RGB source) if the image is opaque and within the caps, else
     ("fallback", uint8 [size, size, 3]): the finished `clip_resize_crop` of the host path, which the device path then
-    carries through identity tables."""
-    from .data import clip_resize_crop
+    carries through identity tables.
+    With `box` (left, top, cw, ch; train transform "clip_resizedcrop") the answer has a third element, the box the device
+    transform applies to the array: `box` itself next to the whole source, (0, 0, size, size) next to the finished
+    `clip_resized_crop` of the fallback route."""
+    from .data import clip_resize_crop, clip_resized_crop
+    def with_box(route, a, b):
+        return (route, a) if box is None else (route, a, b)
+
     w, h = img.size
     if w <= MAX_SOURCE_WIDTH and w * h <= MAX_SOURCE_PIXELS:
         if img.mode == "RGB" and "transparency" not in img.info:
-            return "device", np.asarray(img, dtype=np.uint8)          # convert("RGBA") would set alpha to 255
+            return with_box("device", np.asarray(img, dtype=np.uint8), box)   # convert("RGBA") would set alpha to 255
         rgba = img.convert("RGBA")                                    # base_dataset.py:92-93, as the host path
         if rgba.getextrema()[3] == (255, 255):
-            return "device", np.asarray(rgba.convert("RGB"), dtype=np.uint8)
+            return with_box("device", np.asarray(rgba.convert("RGB"), dtype=np.uint8), box)
         img = rgba
+    if box is not None:
+        return "fallback", clip_resized_crop(img, size, box), (0, 0, size, size)
     return "fallback", clip_resize_crop(img, size)
 
 
@@ -166,11 +223,15 @@ def _align16(n):
     return (n + 15) & ~15
 
 
-def pack_batch(sources, size, pin=False, pmap=map):
+def pack_batch(sources, size, pin=False, pmap=map, boxes=None):
     """uint8 [h_i, w_i, 3] sources -> the three host tensors the kernels read: `src` (bytes, every image at a 16-byte
     aligned offset, rows packed), `plan` (int64 [B, PLAN_FIELDS]) and `tab` (int32; one set of tables per distinct source
     size), plus `rows`, the number of intermediate rows of the batch (the workspace size).  `pmap`: a `map` that may run the copies into the staging buffer
-    on several threads (numpy releases the GIL for them); a batch of 1024 x 1024 sources is 805 MB."""
+    on several threads (numpy releases the GIL for them); a batch of 1024 x 1024 sources is 805 MB.
+    `boxes` (one (left, top, cw, ch) per source; "clip_resizedcrop"): image i is `sources[i][top:top + ch, left:left + cw]`
+    resized to size x size.  The plan names the box inside the whole source, images with equal (cw, ch) share a table set and
+    PLAN_BUILD marks its first owner; the tables themselves are built on the device, so the pack has `tab_ints` (their length)
+    in place of `tab`."""
     import torch
     offs, total = [], 0
     for s in sources:
@@ -181,6 +242,21 @@ def pack_batch(sources, size, pin=False, pmap=map):
     tabs, tab_at, tab_len, rows = [], {}, 0, 0
     for i, s in enumerate(sources):
         h, w, _ = s.shape
+        if boxes is not None:
+            left, top, cw, ch = (int(v) for v in boxes[i])
+            assert 0 <= left and 0 <= top and 0 < cw and 0 < ch and left + cw <= w and top + ch <= h, (boxes[i], (w, h))
+            ksx, ksy = axis_ksize(cw, size), axis_ksize(ch, size)
+            if (cw, ch) not in tab_at:
+                tab_at[(cw, ch)] = tab_len
+                tab_len += size * (2 + ksx) + size * (2 + ksy)
+                plan[i, PLAN_BUILD] = 1
+            xb = tab_at[(cw, ch)]
+            xk, yb = xb + 2 * size, xb + size * (2 + ksx)
+            yk = yb + 2 * size
+            plan[i, :13] = (offs[i] + top * w * 3 + 3 * left, cw, ch, w * 3, 0, ch, ksx, ksy, xb, xk, yb, yk, rows)
+            rows += ch
+            assert plan[i, PLAN_SRC] + (ch - 1) * w * 3 + 3 * cw <= total and yk + size * ksy <= tab_len
+            continue
         t = tables(w, h, size)
         if (w, h) not in tab_at:
             tab_at[(w, h)] = tab_len
@@ -196,7 +272,10 @@ def pack_batch(sources, size, pin=False, pmap=map):
     def put(so):
         flat[so[1]:so[1] + so[0].size] = so[0].reshape(-1)
     list(pmap(put, zip(sources, offs)))
-    plan_t, tab_t = torch.from_numpy(plan), torch.from_numpy(np.concatenate(tabs).astype(np.int32))
+    plan_t = torch.from_numpy(plan)
+    if boxes is not None:
+        return {"src": src, "plan": plan_t.pin_memory() if use_pin else plan_t, "tab_ints": tab_len, "rows": rows, "size": int(size)}
+    tab_t = torch.from_numpy(np.concatenate(tabs).astype(np.int32))
     if use_pin:
         plan_t, tab_t = plan_t.pin_memory(), tab_t.pin_memory()
     return {"src": src, "plan": plan_t, "tab": tab_t, "rows": rows, "size": int(size)}
@@ -204,7 +283,7 @@ def pack_batch(sources, size, pin=False, pmap=map):
 
 def upload(pack, device):
     """The pack's tensors on `device` (non-blocking: call it under the copy stream)."""
-    return {**pack, **{k: pack[k].to(device, non_blocking=True) for k in ("src", "plan", "tab")}}
+    return {**pack, **{k: pack[k].to(device, non_blocking=True) for k in ("src", "plan", "tab") if k in pack}}
 
 
 def workspace_bytes(rows, size):
@@ -212,13 +291,30 @@ def workspace_bytes(rows, size):
     return int(_lib.lib().m3ae_image_resample_workspace_bytes(rows, size))
 
 
+def build_tables_on_device(plan, size, tab, stream=None):
+    """`m3ae_image_resample_tables`: fills int32 `tab` (device) with the tables of every plan record marked PLAN_BUILD."""
+    import torch
+    from . import _lib
+    s = C.c_void_p((stream or torch.cuda.current_stream()).cuda_stream)
+    _lib.check(_lib.lib().m3ae_image_resample_tables(C.c_void_p(plan.data_ptr()), plan.shape[0], size, C.c_void_p(tab.data_ptr()),
+                                                     tab.numel(), s), "m3ae_image_resample_tables")
+    return tab
+
+
 def resample_on_device(dpack, want_u8=False, stream=None):
     """Device pack -> fp32 [B, 3, size, size] (ToTensor + Normalize of the resized crop; bit-equal to
-    `normalize_on_device(clip_resize_crop(...))`), and with want_u8 also the uint8 [B, size, size, 3] crop."""
+    `normalize_on_device(clip_resize_crop(...))`), and with want_u8 also the uint8 [B, size, size, 3] crop.
+    A pack made with boxes has no tables: they are built here, on the same stream, in front of the two passes (a record
+    the table kernel refuses keeps zero tap counts)."""
     import torch
     from . import _lib
     from .synth import CLIP_MEAN, CLIP_STD
-    src, plan, tab, size = dpack["src"], dpack["plan"], dpack["tab"], dpack["size"]
+    src, plan, size = dpack["src"], dpack["plan"], dpack["size"]
+    tab = dpack.get("tab")
+    if tab is None:
+        with torch.cuda.stream(stream or torch.cuda.current_stream()):
+            tab = torch.zeros(max(dpack["tab_ints"], 1), dtype=torch.int32, device=src.device)
+        build_tables_on_device(plan, size, tab, stream)
     B = plan.shape[0]
     out = torch.empty((B, 3, size, size), dtype=torch.float32, device=src.device)
     u8 = torch.empty((B, size, size, 3), dtype=torch.uint8, device=src.device) if want_u8 else None

@@ -31,7 +31,7 @@ MAP_ENTRIES = ("m3ae_attn_probs", "m3ae_xattn_probs_export")
 DET_ENTRIES = ("m3ae_gemm_det_workspace_bytes", "m3ae_gemm_det", "m3ae_det_workspace_bytes", "m3ae_colsum_det",
                "m3ae_layernorm_bwd_det", "m3ae_layernorm_bwd_drop_det", "m3ae_roberta_embed_bwd_det", "m3ae_bce_logits_det",
                "m3ae_xent_det", "m3ae_mim_loss_fwd_det")
-IMAGE_ENTRIES = ("m3ae_image_resample_workspace_bytes", "m3ae_image_resample_u8")
+IMAGE_ENTRIES = ("m3ae_image_resample_workspace_bytes", "m3ae_image_resample_u8", "m3ae_image_resample_tables")
 SAMPLES_ENTRIES = ("m3ae_expand_samples", "m3ae_segment_sum_rows")
 MIXED_LN_ENTRIES = ("m3ae_layernorm_fwd_mixed", "m3ae_layernorm_bwd_mixed", "m3ae_layernorm_bwd_mixed_det")
 TILED_ENTRIES = ("m3ae_tile_bf16_batched",)

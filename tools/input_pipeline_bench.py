@@ -15,6 +15,11 @@ temporary directory, one per source size, then per table:
    `m3ae_image_resample_u8` (median of `--iters`), with the bytes the passes must move (source rows read once, the uint8
    intermediate written and read, the fp32 output written) against the HBM rate of MI355X_MICROARCH.md.
 
+4. the same for the train transform `clip_resizedcrop` (a random crop box per image and epoch, so a table set per image):
+   producer images/s of the host and the device transform, every window a new epoch, and the device time of one batch split into
+   `m3ae_image_resample_tables` (the coefficient tables built on the GPU) and the two passes, next to the `clip` figures above;
+   nothing is asserted about these.
+
 A run without a GPU fails; nothing here falls back."""
 import argparse
 import io
@@ -62,11 +67,11 @@ def write_table(root, side, rows):
     return sum(len(b) for b in imgs) / len(imgs)
 
 
-def producer_window(dm):
+def producer_window(dm, epoch=None):
     idx = dm._indices(dm.train_set, 0, True)
     torch.cuda.synchronize()
     t0, n = time.perf_counter(), 0
-    for b in dm._stream(dm.train_set, idx, drop_last=True):
+    for b in dm._stream(dm.train_set, idx, drop_last=True, epoch=epoch):
         torch.cuda.synchronize()
         n += b["image"][0].shape[0]
     return n / (time.perf_counter() - t0)
@@ -181,7 +186,44 @@ def main():
                 failed.append(f"{side}: the transform is slower than the upload of its input")
             if not md > mh:
                 failed.append(f"{side}: the device path's producer is not faster than the host path's")
-            del dms, dst, dpack
+
+            # ---- train transform clip_resizedcrop: a box, and so a table set, per image and epoch
+            crop = {}
+            for mode in ("host", "device"):
+                cfg = finetune_vqa_rad_config(data_root=root, per_gpu_batchsize=a.batch, num_workers=a.workers, image_size=a.size,
+                                              image_transform=mode, train_transform_keys=["clip_resizedcrop"])
+                crop[mode] = data.ArrowDataModule(cfg, 0, 1, dev, tokenizer=HashTokenizer())
+            rates = {"host": [], "device": []}
+            for w in range(a.windows + 1):
+                for mode in ("host", "device"):
+                    r = producer_window(crop[mode], epoch=w)
+                    if w > 0:
+                        rates[mode].append(r)
+                    say(f"clip_resizedcrop producer {'warm-up window' if w == 0 else f'window {w}      '} {mode:6s} {r:9.1f} images/s")
+            ch, cd = statistics.median(rates["host"]), statistics.median(rates["device"])
+            say(f"clip_resizedcrop producer throughput (median of {a.windows} windows): host {ch:.1f} images/s, device {cd:.1f} "
+                f"images/s, device / host = {cd / ch:.2f}x;  against clip: host {ch / mh:.2f}x, device {cd / md:.2f}x")
+            boxes = [resample.random_resized_crop_box(s.shape[1], s.shape[0], resample.box_rng(0, 0, i, 0)) for i, s in enumerate(srcs)]
+            t0 = time.perf_counter()
+            bpack = resample.pack_batch(srcs, a.size, pin=True, boxes=boxes)
+            t_pack = time.perf_counter() - t0
+            n_sets = int(bpack["plan"][:, resample.PLAN_BUILD].sum())
+            say(f"clip_resizedcrop: packing one batch of {a.batch} with boxes {t_pack * 1e3:.1f} ms; {n_sets} table sets, "
+                f"{bpack['tab_ints'] * 4 / 1e6:.2f} MB of tables built on the device (none uploaded)")
+            dbpack = resample.upload(bpack, dev)
+            tab = torch.zeros(bpack["tab_ints"], dtype=torch.int32, device=dev)
+            resample.build_tables_on_device(dbpack["plan"], a.size, tab)
+            torch.cuda.synchronize()
+            with_tab = {**dbpack, "tab": tab}
+            resample.resample_on_device(with_tab)
+            resample.resample_on_device(dbpack)
+            t_med, t_min = event_ms(lambda: resample.build_tables_on_device(dbpack["plan"], a.size, tab), a.iters)
+            p_med, p_min = event_ms(lambda: resample.resample_on_device(with_tab), a.iters)
+            b_med, b_min = event_ms(lambda: resample.resample_on_device(dbpack), a.iters)
+            say(f"clip_resizedcrop, {a.batch} images: m3ae_image_resample_tables median {t_med:.3f} ms, min {t_min:.3f} ms; the two "
+                f"passes on built tables median {p_med:.3f} ms, min {p_min:.3f} ms (clip: {k_med:.3f} ms); tables + memset + passes as "
+                f"resample_on_device runs them median {b_med:.3f} ms, min {b_min:.3f} ms")
+            del dms, dst, dpack, crop, dbpack, with_tab, tab
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         f.write("\n".join(lines) + "\n")
