@@ -126,7 +126,8 @@ enum { M3AE_GEMM_NO_PERSISTENT = 1,
                                * b_sn != K, a B that is not 16-byte aligned, and together with M3AE_GEMM_F32_X3. */ };
 /* Diagnostic selectors in launch_flags (0 in the product path = kernel chosen by shape): tests pin the kernel variants
  * per call to compare them bit for bit, tools time them against each other.  The library keeps no tuning state.
- *   NT variant v: 0 = 128x128 tile, 4 = 256x256 2-stage, 7 = 256x256 ping-pong, 8 = its persistent form;
+ *   NT variant v: 0 = 128x128 tile, 4 = 256x256 2-stage, 7 = 256x256 ping-pong (8, once its persistent form, is unassigned:
+ *   like every unassigned value it runs the 128x128 kernel);
  *   TN (wgrad) variant v: 0 / 2 = 128x128 tile with 64- / 32-row steps, 5 = 256x256 ping-pong;
  *   column-tile group width g (1..12) of the ping-pong kernels' tile order;
  *   bits 20-21: cache policy of the NT epilogue's streams (1 plain, 2 output stores nt, 3 + residual / aux loads nt; 0 = by size).

@@ -265,13 +265,13 @@ int m3ae_gemm_f32x3(const m3ae_gemm_desc& d, hipStream_t s, DropRows rows = Drop
 
 static bool aligned16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
 
-// Kernel selection is by shape (the "auto" rules below).  A caller may pin a variant PER CALL through the selector fields of
-// m3ae_gemm_desc.launch_flags (M3AE_GEMM_NT_VARIANT / _TN_VARIANT / _COL_GROUP: tests compare the variants bit for bit, tools
+// Kernel selection is by shape (nt_kernel_choice / tn_kernel_choice below).  A caller may pin a variant PER CALL through the selector
+// fields of m3ae_gemm_desc.launch_flags (M3AE_GEMM_NT_VARIANT / _TN_VARIANT / _COL_GROUP: tests compare the variants bit for bit, tools
 // time them against each other); the library keeps no tuning state and reads no environment variable.
-// The persistent form of the ping-pong kernel (static tile lists, one workgroup per CU) is never taken under
-// M3AE_GEMM_NO_PERSISTENT (data-parallel runs): when RCCL's kernels hold some CUs the persistent workgroups that found no CU only
-// start after others have walked their whole tile list (the kernel's time doubles); the one-tile-per-workgroup launch just runs
-// on the CUs that are free.
+// The persistent launch of the second-generation ping-pong kernel (gemm_nt_pp2.hip: static tile lists, one workgroup per CU) is never
+// taken under M3AE_GEMM_NO_PERSISTENT (data-parallel runs): when RCCL's kernels hold some CUs the persistent workgroups that found no
+// CU only start after others have walked their whole tile list (the kernel's time doubles); the one-tile-per-workgroup launch just
+// runs on the CUs that are free.
 
 template <int BM_, int BN_, int BKT, int NST, int WM, int EPI>
 static int launch_nt_t(const MfmaArgs& a, hipStream_t s) {
@@ -297,52 +297,8 @@ static int launch_nt_t(const MfmaArgs& a, hipStream_t s) {
 //   phase 2c+1 issues A(c+3)                   -- A(c-1) was last read in phase 2c-1;
 //   phase 2c+1 waits (counted vmcnt: the 8 loads of chunks c+2, c+3 stay in flight) for chunk c+1 BEFORE its first
 //              barrier; chunk c+1 is first read in phase 2c+2, i.e. after a barrier every wave passed post-wait.
+// The B operand of a chunk comes from the tiled copy of the weight under M3AE_GEMM_B_TILED (one lane-linear 1-KiB block per piece).
 // ---------------------------------------------------------------------------------------------------------
-// M3AE_EXP_NT_*: timing-only experiments on the ping-pong kernels (tools/nt_exp.sh; wrong results, never in the product build):
-// operands left unstaged / staged from contiguous 1-KiB source pieces (as if stored reduction-chunk-major; _CONTIG_B: B only) / stores dropped
-#if defined(M3AE_EXP_NT_NODMA)
-#define PP_STAGE(G, ld, r0, nr, k0, tile) do { } while (0)
-#elif defined(M3AE_EXP_NT_CONTIG)
-template <int BKT, int SEGS_PER_WAVE, int NWAVES>
-DEVINL void nt_stage_contig(const bf16_t* G, int64_t ld, int64_t row0, int64_t nrows, int64_t k0, char* tile, int wave, int lane) {
-    constexpr int CPR = BKT / 8, RPS = 64 / CPR;
-#pragma unroll
-    for (int q = 0; q < SEGS_PER_WAVE; ++q) {
-        const int seg = q * NWAVES + wave;
-        const int row = seg * RPS + lane / CPR;
-        int64_t grow = row0 + row;
-        grow = grow < nrows ? grow : nrows - 1;
-        glds16(G + (k0 / BKT) * nrows * BKT + grow * BKT + (lane % CPR) * 8, tile + seg * 1024);
-    }
-}
-#ifdef M3AE_EXP_NT_L2HOT
-#define PP_STAGE(G, ld, r0, nr, k0, tile) nt_stage_contig<CK, 2, NW>(G, ld, 0, nr, k0, tile, wave, lane)
-#else
-#define PP_STAGE(G, ld, r0, nr, k0, tile) nt_stage_contig<CK, 2, NW>(G, ld, r0, nr, k0, tile, wave, lane)
-#endif
-#elif defined(M3AE_EXP_NT_L2HOT)   // every tile stages rows 0..255 of both operands: the sources stay L2-resident (true hits)
-#define PP_STAGE(G, ld, r0, nr, k0, tile) nt_stage<CK, 2, NW>(G, ld, 0, nr, k0, tile, wave, lane)
-#else
-#define PP_STAGE(G, ld, r0, nr, k0, tile) nt_stage<CK, 2, NW>(G, ld, r0, nr, k0, tile, wave, lane)
-#endif
-
-// M3AE_EXP_NT_CONTIG_B (with M3AE_EXP_NT_CONTIG): the contiguous pieces for the B operand only -- A keeps its row-shaped pieces (what a
-// tiled WEIGHT alone can buy: profiles/r09_nt_tiled_weights_probe.log)
-#if defined(M3AE_EXP_NT_CONTIG) && defined(M3AE_EXP_NT_CONTIG_B)
-#ifdef M3AE_EXP_NT_L2HOT
-#define PP_STAGE_A(G, ld, r0, nr, k0, tile) nt_stage<CK, 2, NW>(G, ld, 0, nr, k0, tile, wave, lane)
-#else
-#define PP_STAGE_A(G, ld, r0, nr, k0, tile) nt_stage<CK, 2, NW>(G, ld, r0, nr, k0, tile, wave, lane)
-#endif
-#else
-#define PP_STAGE_A(G, ld, r0, nr, k0, tile) PP_STAGE(G, ld, r0, nr, k0, tile)
-#endif
-// the B operand of a chunk: from the tiled copy of the weight under M3AE_GEMM_B_TILED (one lane-linear 1-KiB block per piece)
-#define PP_STAGE_B(k0, tile) do { \
-        if (a.b_tiled) nt_stage_tiled32<2, NW>(a.B, a.K, n0, k0, tile, wave, lane); \
-        else PP_STAGE(a.B, a.ldb, n0, a.N, k0, tile); \
-    } while (0)
-
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(MfmaArgs a) {
     if (a.has_drop) drop_resolve(a.drop);
@@ -369,8 +325,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(MfmaArgs a) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         if (c < nc) {
-            PP_STAGE_B((int64_t)c * CK, smem + c * SLOT + A_BYTES);
-            PP_STAGE_A(a.A, a.lda, m0, a.M, (int64_t)c * CK, smem + c * SLOT);
+            if (a.b_tiled) nt_stage_tiled32<2, NW>(a.B, a.K, n0, (int64_t)c * CK, smem + c * SLOT + A_BYTES, wave, lane);
+            else nt_stage<CK, 2, NW>(a.B, a.ldb, n0, a.N, (int64_t)c * CK, smem + c * SLOT + A_BYTES, wave, lane);
+            nt_stage<CK, 2, NW>(a.A, a.lda, m0, a.M, (int64_t)c * CK, smem + c * SLOT, wave, lane);
         }
     }
     if (nc >= 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
@@ -393,7 +350,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(MfmaArgs a) {
         for (int j = 0; j < 4; ++j) bfr[j] = nt_frag<CK>(Bt, wc * 64 + j * 16 + frow, fchunk);
 #pragma unroll
         for (int i = 0; i < 4; ++i) af[i] = nt_frag<CK>(At, wr * 128 + i * 16 + frow, fchunk);
-        if (more) PP_STAGE_B((int64_t)(c + 3) * CK, nxt + A_BYTES);
+        if (more) {
+            if (a.b_tiled) nt_stage_tiled32<2, NW>(a.B, a.K, n0, (int64_t)(c + 3) * CK, nxt + A_BYTES, wave, lane);
+            else nt_stage<CK, 2, NW>(a.B, a.ldb, n0, a.N, (int64_t)(c + 3) * CK, nxt + A_BYTES, wave, lane);
+        }
         PP_FENCE();
         __builtin_amdgcn_s_barrier();
         PP_FENCE();
@@ -413,7 +373,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(MfmaArgs a) {
         // ---------------- phase 2c + 1: rows 64..127 (the B fragments stay in registers)
 #pragma unroll
         for (int i = 0; i < 4; ++i) af[i] = nt_frag<CK>(At, wr * 128 + 64 + i * 16 + frow, fchunk);
-        if (more) PP_STAGE_A(a.A, a.lda, m0, a.M, (int64_t)(c + 3) * CK, nxt);
+        if (more) nt_stage<CK, 2, NW>(a.A, a.lda, m0, a.M, (int64_t)(c + 3) * CK, nxt, wave, lane);
         {
             const int rem = nc - 1 - c;  // chunks after this one; chunk c + 1 must have landed before the next phase
             if (rem >= 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
@@ -463,196 +423,20 @@ template <int EPI>
 static int launch_nt_pp(const MfmaArgs& a, hipStream_t s) {
     constexpr int lds = 4 * (256 + 256) * 32 * 2;  // 128 KiB ring; the epilogue slabs (8 x 8704 B) reuse it
     const int64_t tiles = cdiv(a.M, 256) * cdiv(a.N, 256);
-    g_last_path = "mfma_nt_pp";
     return launch_dyn<gemm_nt_pp_kernel<EPI>>(dim3((unsigned)tiles), dim3(512), lds, s, a);
 }
 
-
-// ---------------------------------------------------------------------------------------------------------
-// Persistent form of gemm_nt_pp_kernel: one workgroup per CU walks tiles v = block, block + grid, ... (grid a multiple of
-// 8, so every tile of a workgroup maps to the same XCD range as in the one-tile-per-workgroup launch).  A K = 768 tile
-// spends ~12 % of its time waiting for its first chunks and ~16-30 % in the epilogue: here the NEXT tile's chunks 0 and 1
-// are requested before the epilogue of the current one (ring slots 2, 3; the epilogue's 16-row slabs live in slots
-// 0, 1), chunk 2 right after it, so the main loop of the next tile starts on landed data.
-// Ring slot of chunk c is (c + 2) & 3; everything else is the schedule of gemm_nt_pp_kernel.
-// ---------------------------------------------------------------------------------------------------------
-#ifdef M3AE_NT_TRACE   // diagnostic build only (tools/nt_trace.py): shader clocks per section of the main loop, summed per workgroup
-__device__ uint64_t g_nt_trace[1024 * 2 * 8];   // [block][wave row][fragment reads, DMA issue, barrier 1, lgkmcnt wait, MFMA issue, barrier 2, chunks, -]
-#define NT_CLK() ({ __builtin_amdgcn_sched_barrier(0); uint64_t t_ = __builtin_readcyclecounter(); __builtin_amdgcn_sched_barrier(0); t_; })
-#define NT_ACC(i) do { const uint64_t n_ = NT_CLK(); nt_acc[i] += n_ - nt_t; nt_t = n_; } while (0)
-#else
-#define NT_ACC(i) do { } while (0)
-#endif
-
-template <int EPI>
-__global__ __launch_bounds__(512, 2) void gemm_nt_pp_persistent_kernel(MfmaArgs a) {
-    if (a.has_drop) drop_resolve(a.drop);
-    constexpr int CK = 32, NW = 8, A_BYTES = 256 * CK * 2, SLOT = 2 * A_BYTES;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave >> 2, wc = wave & 3;
-    const unsigned tiles_n = (unsigned)((a.N + 255) / 256);
-    const unsigned tiles_m = (unsigned)((a.M + 255) / 256);
-    const unsigned total = tiles_m * tiles_n;
-    const int nc = (int)(a.K / CK);   // >= 3 (host check)
-    const int frow = lane & 15, fchunk = lane >> 4;
-
-    unsigned v = blockIdx.x;
-    unsigned tm, tn;
-    nt_tile_coords(xcd_remap(v, total), tiles_m, tiles_n, tm, tn, (unsigned)a.col_group);
-    int64_t m0 = (int64_t)tm * 256, n0 = (int64_t)tn * 256;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        char* sl = smem + ((c + 2) & 3) * SLOT;
-        PP_STAGE_B((int64_t)c * CK, sl + A_BYTES);
-        PP_STAGE_A(a.A, a.lda, m0, a.M, (int64_t)c * CK, sl);
-    }
-    int top_wait = 0;
-#ifdef M3AE_NT_TRACE
-    uint64_t nt_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, nt_t = 0;
-#endif
-    // stores per wave of an interior tile's epilogue: 16 row groups x (C [+ pre-activation / derivative]); bf16 only
-    const int interior_wait = a.c_f32 ? 1 : (a.preact ? 3 : 2);
-    for (;;) {
-        f32x4 acc[8][4];
-#pragma unroll
-        for (int i = 0; i < 8; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        // chunks 0 (and 1) of this tile have landed.  vmcnt retires in order, so the wait names how many YOUNGER operations
-        // may stay in flight: chunks 1, 2 on the first tile; afterwards chunk 2 plus -- when the previous tile was an
-        // interior one, whose epilogue issued a known number of stores -- those stores (no store drain before the main loop)
-        if (top_wait == 0) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (top_wait == 2) asm volatile("s_waitcnt vmcnt(20)" ::: "memory");
-        else if (top_wait == 3) asm volatile("s_waitcnt vmcnt(36)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        PP_FENCE();
-        __builtin_amdgcn_s_barrier();
-        PP_FENCE();
-        if (wr == 1) { __builtin_amdgcn_s_barrier(); PP_FENCE(); }
-#ifdef M3AE_NT_TRACE
-        nt_t = NT_CLK();
-#endif
-        for (int c = 0; c < nc; ++c) {
-            const char* At = smem + ((c + 2) & 3) * SLOT;
-            const char* Bt = At + A_BYTES;
-            char* nxt = smem + ((c + 5) & 3) * SLOT;
-            const bool more = c + 3 < nc;
-            s16x8 bfr[4], af[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bfr[j] = nt_frag<CK>(Bt, wc * 64 + j * 16 + frow, fchunk);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = nt_frag<CK>(At, wr * 128 + i * 16 + frow, fchunk);
-            NT_ACC(0);
-            if (more) PP_STAGE_B((int64_t)(c + 3) * CK, nxt + A_BYTES);
-            NT_ACC(1);
-            PP_FENCE();
-            __builtin_amdgcn_s_barrier();
-            PP_FENCE();
-            NT_ACC(2);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            NT_ACC(3);
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        __builtin_bit_cast(bf16x8_t, bfr[j]), __builtin_bit_cast(bf16x8_t, af[i]), acc[i][j], 0, 0, 0);
-            __builtin_amdgcn_s_setprio(0);
-            NT_ACC(4);
-            PP_FENCE();
-            __builtin_amdgcn_s_barrier();
-            PP_FENCE();
-            NT_ACC(5);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) af[i] = nt_frag<CK>(At, wr * 128 + 64 + i * 16 + frow, fchunk);
-            NT_ACC(0);
-            if (more) PP_STAGE_A(a.A, a.lda, m0, a.M, (int64_t)(c + 3) * CK, nxt);
-            NT_ACC(1);
-            {
-                const int rem = nc - 1 - c;
-                if (rem >= 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-                else if (rem == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            }
-            NT_ACC(6);
-            PP_FENCE();
-            __builtin_amdgcn_s_barrier();
-            PP_FENCE();
-            NT_ACC(2);
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-            NT_ACC(3);
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    acc[4 + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-                        __builtin_bit_cast(bf16x8_t, bfr[j]), __builtin_bit_cast(bf16x8_t, af[i]), acc[4 + i][j], 0, 0, 0);
-            __builtin_amdgcn_s_setprio(0);
-            NT_ACC(4);
-            PP_FENCE();
-            __builtin_amdgcn_s_barrier();
-            PP_FENCE();
-            NT_ACC(5);
-        }
-#ifdef M3AE_NT_TRACE
-        nt_acc[7] += (uint64_t)nc;
-#endif
-        if (wr == 0) { __builtin_amdgcn_s_barrier(); PP_FENCE(); }
-        // every fragment read of this tile is retired, no DMA outstanding: request the next tile's chunks 0, 1 (slots 2, 3)
-        const unsigned vn = v + gridDim.x;
-        const bool again = vn < total;
-        const int64_t m_cur = m0, n_cur = n0;
-        if (again) {
-            nt_tile_coords(xcd_remap(vn, total), tiles_m, tiles_n, tm, tn, (unsigned)a.col_group);
-            m0 = (int64_t)tm * 256; n0 = (int64_t)tn * 256;
-#pragma unroll
-            for (int c = 0; c < 2; ++c) {
-                char* sl = smem + ((c + 2) & 3) * SLOT;
-                PP_STAGE_B((int64_t)c * CK, sl + A_BYTES);
-                PP_STAGE_A(a.A, a.lda, m0, a.M, (int64_t)c * CK, sl);
-            }
-        }
-        if (a.c_f32) epilogue_rows<float, EPI, 8, 1>(a, smem, wave, lane, m_cur + wr * 128, n_cur + wc * 64, acc);
-        else epilogue_rows<bf16_t, EPI, 8, 1>(a, smem, wave, lane, m_cur + wr * 128, n_cur + wc * 64, acc);
-#ifdef M3AE_NT_TRACE
-        if (!again && lane == 0 && (wave & 3) == 0 && blockIdx.x < 1024)
-            for (int q_ = 0; q_ < 8; ++q_) g_nt_trace[((size_t)blockIdx.x * 2 + wr) * 8 + q_] = nt_acc[q_];
-#endif
-        if (!again) break;
-        top_wait = (m_cur + 256 <= a.M && n_cur + 256 <= a.N) ? interior_wait : 1;
-        PP_FENCE();
-        __builtin_amdgcn_s_barrier();   // every wave is done with its slab (slots 0, 1): chunk 2 may land in slot 0
-        PP_FENCE();
-        {
-            char* sl = smem + ((2 + 2) & 3) * SLOT;
-            PP_STAGE_B((int64_t)2 * CK, sl + A_BYTES);
-            PP_STAGE_A(a.A, a.lda, m0, a.M, (int64_t)2 * CK, sl);
-        }
-        v = vn;
-    }
-}
-
-template <int EPI>
-static int launch_nt_pp_persistent(const MfmaArgs& a, hipStream_t s) {
-    constexpr int lds = 4 * (256 + 256) * 32 * 2;
-    g_last_path = "mfma_nt_pp";
-    const int dev = current_device();
-    return launch_dyn_on<gemm_nt_pp_persistent_kernel<EPI>>(dev, dim3((unsigned)device_cus8(dev)), dim3(512), lds, s, a);
-}
-
-// variants (launch_flags: M3AE_GEMM_NT_VARIANT(v)):
-//   0: 128x128 tile, BK 64, 2 stages, 4 waves x (64x64)   -- 64 KiB LDS, 2 workgroups / CU (small / few-tile shapes)
-//   4: 256x256 tile, BK 64, 2 stages, 8 waves x (128x64)  -- 128 KiB LDS, 1 workgroup / CU (the ping-pong kernel's
+// NT kernels (launch_flags: M3AE_GEMM_NT_VARIANT(v) pins one; every other value of v runs the 128 x 128 kernel):
+//   NT_T128 (v = 0): 128x128 tile, BK 64, 2 stages, 4 waves x (64x64)  -- 64 KiB LDS, 2 workgroups / CU (small / few-tile shapes)
+//   NT_T256 (v = 4): 256x256 tile, BK 64, 2 stages, 8 waves x (128x64) -- 128 KiB LDS, 1 workgroup / CU (the ping-pong kernels'
 //      bit-exact reference in tools/gemm_race.py)
-//   7: 256x256 tile, 32-deep chunks in a 4-slot ring, 8 waves in two staggered rows (ping-pong, gemm_nt_pp_kernel)
-//   8: the persistent form of 7 (static tile lists, one workgroup per CU; >= 512 tiles)
+//   NT_PP (v = 7): 256x256 tile, 32-deep chunks in a 4-slot ring, 8 waves in two staggered rows (ping-pong, gemm_nt_pp_kernel): the
+//      256 tile of the shapes the second generation does not take (K < 256, or an output that is not row-epilogue capable)
+//   NT_PP2 / NT_PP2_PERSISTENT (v = 9 / 10): the second-generation ping-pong kernel (gemm_nt_pp2.hip), one workgroup per tile /
+//      persistent (grid = CUs)
+//   v = 8 was the persistent form of gemm_nt_pp_kernel (static tile lists, one workgroup per CU; >= 512 tiles); retired: the class
+//      it still served by shape (K in {128, 192}, >= 512 tiles, row-epilogue capable) is one no model configuration produces
+//      (DESIGN.md 6).  Last present in commit 8532550.
 // Tilings tried and dropped (measured slower on every shape of the path, r01 logs): a 128x256 "dual" kernel (4 waves, two
 // workgroups per CU so that one's main loop runs under the other's epilogue; bit-identical, 3-9 % slower, removed in r02);
 // 256x128 with BK 64 / 3 stages,
@@ -661,47 +445,56 @@ static int launch_nt_pp_persistent(const MfmaArgs& a, hipStream_t s) {
 // software-pipelined in registers, 33 % fewer LDS fragment bytes per MFMA): bit-identical, 1143 vs 1281 TF/s at 8192^3
 // and 12-25 % slower on the path's shapes (profiles/r01_nt_w4_probe.log) -- one wave per SIMD does not keep the MFMA
 // pipe as busy as the two staggered wave rows do.
+enum NtKernel { NT_T128, NT_T256, NT_PP, NT_PP2, NT_PP2_PERSISTENT };
+
+static NtKernel nt_kernel_choice(const MfmaArgs& a) {
+    const bool both = a.M > 128 && a.N > 128;               // a 256 x 256 tile needs more than 128 rows and columns to fill
+    const bool pp2_ok = both && a.rows_epi && a.K >= 256;   // gemm_nt_pp2.hip
+    if (a.nt_variant >= 0) {                                // pinned
+        switch (a.nt_variant) {
+        case 9: return pp2_ok ? NT_PP2 : NT_T128;
+        case 10: return pp2_ok ? NT_PP2_PERSISTENT : NT_T128;
+        case 7: return both ? NT_PP : NT_T128;
+        case 4: return both ? NT_T256 : NT_T128;
+        default: return NT_T128;
+        }
+    }
+    // by shape (default): measured on MI355X, profiles/r01_gemm_shapes.log
+    // 256 x 256 ping-pong kernel (one workgroup per CU, 256 slots) or 128 x 128 kernel (two per CU, 512 slots)?  What
+    // decides is how full the last round of tiles is: efficiency = tiles / (rounds * slots).  The ping-pong kernel is
+    // ~12 % faster per FLOP on full rounds, so it is taken when eff256 >= 0.88 eff128.  Fits every measured pair
+    // (MI355X, K = 768 / 3072): 8192 x 3072 (0.75 vs 1.00: 66 vs 47 us -> 128), 8192 x 768 (0.38 vs 0.75 -> 128),
+    // 36928 x 768 (0.85 vs 0.85: 54 vs 57 us, 164 vs 181 us -> 256), 3072 x 3072 (0.56 vs 0.56: 25.7 vs 26.0 us),
+    // 2048 x 3072 (0.38 vs 0.75: 23.5 vs 17.1 us -> 128); profiles/r01_gemm_shapes.log, r01_nt_tile_rule.log.
+    const int64_t t256 = cdiv(a.M, 256) * cdiv(a.N, 256), t128 = cdiv(a.M, 128) * cdiv(a.N, 128);
+    const double eff256 = (double)t256 / (double)(cdiv(t256, 256) * 256);
+    const double eff128 = (double)t128 / (double)(cdiv(t128, 512) * 512);
+    // (round 4, pp2 against the 128 x 128 kernel at 18464 rows: N = 3072 (0.855 vs 0.971) is 5-13 % faster on the 128 x 128 kernel,
+    // N = 768 / 2304 (0.855 vs 0.85) 4-19 % faster on pp2: the threshold moved from 0.88 to 0.93, profiles/r04_nt_kernel_choice_small_batch.log)
+    if (!both || eff256 < 0.93 * eff128) return NT_T128;
+    if (!pp2_ok) return NT_PP;
+    // second-generation ping-pong kernel (gemm_nt_pp2.hip): -2.2 % against the persistent first-generation kernel (retired, see above)
+    // over the step's eleven shape / epilogue classes at per-GPU batch 256, -3.6 % against the one-tile-per-workgroup form
+    // data-parallel runs take (profiles/r04_nt_pp2_second_ab.log).  Its persistent launch (grid = CUs) is 0.9 % faster than one
+    // workgroup per tile on the kernels alone and 0.8 % on the whole step (1303 vs 1293 pairs/s,
+    // profiles/r04_nt_pp2_stagger_and_persistent_ab.log), from two full rounds of tiles on; data-parallel runs
+    // (M3AE_GEMM_NO_PERSISTENT) take the per-tile launch: static tile lists start late beside RCCL's kernels.
+    return t256 >= 512 && !a.no_persist ? NT_PP2_PERSISTENT : NT_PP2;
+}
+
 template <int EPI>
 static int launch_nt_v(const MfmaArgs& a, hipStream_t s) {
-    const int g_nt_variant = a.nt_variant;
-    if (g_nt_variant < 0) {  // auto (default): measured on MI355X, profiles/r01_gemm_shapes.log
-        // 256 x 256 ping-pong kernel (one workgroup per CU, 256 slots) or 128 x 128 kernel (two per CU, 512 slots)?  What
-        // decides is how full the last round of tiles is: efficiency = tiles / (rounds * slots).  The ping-pong kernel is
-        // ~12 % faster per FLOP on full rounds, so it is taken when eff256 >= 0.88 eff128.  Fits every measured pair
-        // (MI355X, K = 768 / 3072): 8192 x 3072 (0.75 vs 1.00: 66 vs 47 us -> 128), 8192 x 768 (0.38 vs 0.75 -> 128),
-        // 36928 x 768 (0.85 vs 0.85: 54 vs 57 us, 164 vs 181 us -> 256), 3072 x 3072 (0.56 vs 0.56: 25.7 vs 26.0 us),
-        // 2048 x 3072 (0.38 vs 0.75: 23.5 vs 17.1 us -> 128); profiles/r01_gemm_shapes.log, r01_nt_tile_rule.log.
-        const int64_t t256 = cdiv(a.M, 256) * cdiv(a.N, 256), t128 = cdiv(a.M, 128) * cdiv(a.N, 128);
-        const double eff256 = (double)t256 / (double)(cdiv(t256, 256) * 256);
-        const double eff128 = (double)t128 / (double)(cdiv(t128, 512) * 512);
-        // (round 4, pp2 against the 128 x 128 kernel at 18464 rows: N = 3072 (0.855 vs 0.971) is 5-13 % faster on the 128 x 128 kernel,
-        // N = 768 / 2304 (0.855 vs 0.85) 4-19 % faster on pp2: the threshold moved from 0.88 to 0.93, profiles/r04_nt_kernel_choice_small_batch.log)
-        const bool big = a.M > 128 && a.N > 128 && eff256 >= 0.93 * eff128;
-        const bool persist_ok = t256 >= 512;   // the persistent form pays from two full rounds on (+1..3 %)
-        // second-generation ping-pong kernel (gemm_nt_pp2.hip): -2.2 % against the persistent kernel below over the step's eleven
-        // shape / epilogue classes at per-GPU batch 256, -3.6 % against the one-tile-per-workgroup form data-parallel runs take
-        // (profiles/r04_nt_pp2_second_ab.log).  Its persistent launch (grid = CUs) is 0.9 % faster than one workgroup per tile on
-        // the kernels alone and 0.8 % on the whole step (1303 vs 1293 pairs/s, profiles/r04_nt_pp2_stagger_and_persistent_ab.log);
-        // data-parallel runs (M3AE_GEMM_NO_PERSISTENT) take the per-tile launch: static tile lists start late beside RCCL's kernels.
-        if (big && a.rows_epi && a.K >= 256) {
-            g_last_path = "mfma_nt_pp2";
-            return launch_nt_pp2(a, EPI, persist_ok && !a.no_persist, s);
-        }
-        if (big && persist_ok && !a.no_persist && a.rows_epi && a.K >= 96) return launch_nt_pp_persistent<EPI>(a, s);  // +1..3 % (next tile's
-        if (big) return launch_nt_pp<EPI>(a, s);                                                  // chunks under the epilogue)
-        return launch_nt_t<128, 128, 64, 2, 64, EPI>(a, s);
+    const NtKernel k = nt_kernel_choice(a);
+    g_last_path = k == NT_PP ? "mfma_nt_pp" : (k == NT_PP2 || k == NT_PP2_PERSISTENT) ? "mfma_nt_pp2" : "mfma_nt";
+    switch (k) {
+    case NT_PP2: return launch_nt_pp2(a, EPI, false, s);
+    case NT_PP2_PERSISTENT: return launch_nt_pp2(a, EPI, true, s);
+    case NT_PP: return launch_nt_pp<EPI>(a, s);
+    case NT_T256: return launch_nt_t<256, 256, 64, 2, 128, EPI>(a, s);
+    default: return launch_nt_t<128, 128, 64, 2, 64, EPI>(a, s);
     }
-    if ((g_nt_variant == 9 || g_nt_variant == 10) && a.M > 128 && a.N > 128 && a.rows_epi && a.K >= 256) {   // gemm_nt_pp2.hip
-        g_last_path = "mfma_nt_pp2";   // 9: grid = tiles; 10: persistent (grid = CUs)
-        return launch_nt_pp2(a, EPI, g_nt_variant == 10, s);
-    }
-    if (g_nt_variant == 7 && a.M > 128 && a.N > 128) return launch_nt_pp<EPI>(a, s);  // ping-pong 8-phase
-    if (g_nt_variant == 8 && a.rows_epi && a.K >= 96 && cdiv(a.M, 256) * cdiv(a.N, 256) >= 512)
-        return launch_nt_pp_persistent<EPI>(a, s);                                    // persistent ping-pong
-    if (g_nt_variant == 8 && a.M > 128 && a.N > 128) return launch_nt_pp<EPI>(a, s);
-    if (g_nt_variant == 4 && a.M > 128 && a.N > 128) return launch_nt_t<256, 256, 64, 2, 128, EPI>(a, s);
-    return launch_nt_t<128, 128, 64, 2, 64, EPI>(a, s);
 }
+
 
 static int launch_nt(const m3ae_gemm_desc& d, hipStream_t s, DropRows rows) {
     MfmaArgs a{};
@@ -1117,11 +910,6 @@ static int launch_tn(const m3ae_gemm_desc& d, hipStream_t s, float* det_ws = nul
     return launch_tn_t<128, 128, 64, 64, 2>(a, d, s, det_ws);
 }
 
-#ifdef M3AE_NT_TRACE
-extern "C" int m3ae_nt_trace_dump(uint64_t* host_out) {   // diagnostic build only
-    return (int)hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_nt_trace), sizeof(uint64_t) * 1024 * 2 * 8);
-}
-#endif
 
 // The routing rule, in one place: which kernel family takes a descriptor.  m3ae_gemm dispatches on it; deterministic mode
 // (m3ae_gemm_det, m3ae_gemm_det_workspace_bytes) asks it whether the descriptor is one of the split-K TN family, the only one
@@ -1176,8 +964,7 @@ extern "C" int m3ae_gemm_rows(const m3ae_gemm_desc* dp, int64_t row_base, int64_
         g_last_path = "f32x3";
         return m3ae_gemm_f32x3(d, s, rows);
     case ROUTE_NT:
-        g_last_path = "mfma_nt";
-        return launch_nt(d, s, rows);
+        return launch_nt(d, s, rows);   // (launch_nt_v names the path)
     case ROUTE_TN:
         g_last_path = "mfma_tn";
         return launch_tn(d, s);

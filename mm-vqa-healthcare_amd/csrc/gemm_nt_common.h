@@ -233,13 +233,13 @@ DEVINL void epilogue8(const MfmaArgs& a, int64_t m, int64_t n, float* x, const f
 // 68-float rows: conflict-free ds_write_b128 / ds_read_b128) so that every global access of the epilogue is
 // 8 lanes x 16 B = one whole 128-B line per row (the direct fragment layout touches 16 lines per instruction, 32 B
 // each, and made the N = 3072 GELU GEMMs store-issue bound).
-template <typename TC, int EPI, int MI, int RT = 2>   // RT: 16-row tiles per slab pass (slab = 16 RT rows x 68 floats)
+template <typename TC, int EPI, int MI>   // slab = 32 rows (two 16-row accumulator tiles) x 68 floats
 DEVINL void epilogue_rows(const MfmaArgs& a, char* smem, int wave, int lane, int64_t m_base, int64_t n_base,
                           f32x4 (&acc)[MI][4]) {
     constexpr int LDW = 68;
     constexpr bool BF = sizeof(TC) == 2;
     constexpr bool PRE_IS_AUX = (EPI == EPI_DGELU || EPI == EPI_DQGELU || EPI == EPI_DMUL);
-    float* t = (float*)smem + wave * (16 * RT) * LDW;
+    float* t = (float*)smem + wave * 32 * LDW;
     int64_t ncol = n_base + (lane & 7) * 8;
     ncol = ncol < a.N ? ncol : 0;   // N % 8 == 0 on this path: a lane's 8 columns are all inside or all outside
     // Everything the epilogue reads from global memory is requested up front, from inline asm, and waited for ONCE (gload16_asm):
@@ -253,11 +253,11 @@ DEVINL void epilogue_rows(const MfmaArgs& a, char* smem, int wave, int lane, int
     u32x4 bias_v[2] = {(u32x4){0u, 0u, 0u, 0u}, (u32x4){0u, 0u, 0u, 0u}};
     const TC* src = (const TC*)(PRE_IS_AUX ? a.dact_aux : a.residual);
     const bool has_pre = BF && src != nullptr;
-    u32x4 pre[MI / RT][2 * RT];
+    u32x4 pre[MI / 2][4];
 #pragma unroll
-    for (int half = 0; half < MI / RT; ++half)
+    for (int half = 0; half < MI / 2; ++half)
 #pragma unroll
-        for (int pass = 0; pass < 2 * RT; ++pass) pre[half][pass] = (u32x4){0u, 0u, 0u, 0u};
+        for (int pass = 0; pass < 4; ++pass) pre[half][pass] = (u32x4){0u, 0u, 0u, 0u};
     if (ASM_LOADS) {
         if (a.bias) {
             gload16_asm(bias_v[0], a.bias + ncol);
@@ -266,10 +266,10 @@ DEVINL void epilogue_rows(const MfmaArgs& a, char* smem, int wave, int lane, int
         if (has_pre) {
             const int64_t m_last = a.M - 1;
 #pragma unroll
-            for (int half = 0; half < MI / RT; ++half)
+            for (int half = 0; half < MI / 2; ++half)
 #pragma unroll
-                for (int pass = 0; pass < 2 * RT; ++pass) {
-                    const int64_t m = m_base + 16 * RT * half + pass * 8 + (lane >> 3);
+                for (int pass = 0; pass < 4; ++pass) {
+                    const int64_t m = m_base + 32 * half + pass * 8 + (lane >> 3);
                     gload16_asm(pre[half][pass], src + (m < m_last ? m : m_last) * a.ldc + ncol);
                 }
         }
@@ -280,30 +280,30 @@ DEVINL void epilogue_rows(const MfmaArgs& a, char* smem, int wave, int lane, int
         }
         if (has_pre) {
 #pragma unroll
-            for (int half = 0; half < MI / RT; ++half)
+            for (int half = 0; half < MI / 2; ++half)
 #pragma unroll
-                for (int pass = 0; pass < 2 * RT; ++pass) {
-                    const int64_t m = m_base + 16 * RT * half + pass * 8 + (lane >> 3);
+                for (int pass = 0; pass < 4; ++pass) {
+                    const int64_t m = m_base + 32 * half + pass * 8 + (lane >> 3);
                     if (m < a.M) pre[half][pass] = *(const u32x4*)(src + m * a.ldc + ncol);
                 }
         }
     }
     float bias8[8];
 #pragma unroll
-    for (int half = 0; half < MI / RT; ++half) {
+    for (int half = 0; half < MI / 2; ++half) {
 #pragma unroll
-        for (int ii = 0; ii < RT; ++ii)
+        for (int ii = 0; ii < 2; ++ii)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
-                *(f32x4*)(t + (16 * ii + (lane & 15)) * LDW + 16 * j + 4 * (lane >> 4)) = acc[RT * half + ii][j];
+                *(f32x4*)(t + (16 * ii + (lane & 15)) * LDW + 16 * j + 4 * (lane >> 4)) = acc[2 * half + ii][j];
         if (half == 0) {   // the loads' latency runs under the first slab writes
             if (ASM_LOADS) {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 asm volatile("" : "+v"(bias_v[0]), "+v"(bias_v[1]));   // "redefined" behind the wait: no reader can be scheduled in front of it
 #pragma unroll
-                for (int hh = 0; hh < MI / RT; ++hh)
+                for (int hh = 0; hh < MI / 2; ++hh)
 #pragma unroll
-                    for (int pass = 0; pass < 2 * RT; ++pass) asm volatile("" : "+v"(pre[hh][pass]));
+                    for (int pass = 0; pass < 4; ++pass) asm volatile("" : "+v"(pre[hh][pass]));
             }
 #pragma unroll
             for (int q = 0; q < 8; ++q) {   // (through a copy: __builtin_bit_cast of a vector-element lvalue reads element 0, hipcc 7.2)
@@ -313,12 +313,12 @@ DEVINL void epilogue_rows(const MfmaArgs& a, char* smem, int wave, int lane, int
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
-        for (int pass = 0; pass < 2 * RT; ++pass) {
+        for (int pass = 0; pass < 4; ++pass) {
             const int row = pass * 8 + (lane >> 3), col = (lane & 7) * 8;
             const f32x4 v0 = *(const f32x4*)(t + row * LDW + col);
             const f32x4 v1 = *(const f32x4*)(t + row * LDW + col + 4);
             float x[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-            const int64_t m = m_base + 16 * RT * half + row, n = n_base + col;
+            const int64_t m = m_base + 32 * half + row, n = n_base + col;
             if (m < a.M && n < a.N) epilogue8<TC, EPI>(a, m, n, x, bias8, has_pre, pre[half][pass]);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

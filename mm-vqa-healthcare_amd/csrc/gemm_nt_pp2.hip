@@ -201,7 +201,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp2_kernel(MfmaArgs a) {
     const unsigned lds_wave = (unsigned)(uintptr_t)(lds_void*)smem + (unsigned)wave * 1024u;
     unsigned v = blockIdx.x;
     if (v >= total) return;
-#ifdef M3AE_EXP_PP2_STAGGER   // timing experiment (tools/nt_exp.sh): de-phase the workgroups' tile boundaries by quarter tiles
+#ifdef M3AE_EXP_PP2_STAGGER   // timing experiment (tools/nt_exp.py): de-phase the workgroups' tile boundaries by quarter tiles
     {
         const unsigned k = (blockIdx.x >> 3) & 3u;   // same XCD (blockIdx & 7), neighbouring workgroups differ
         const uint64_t t0 = __builtin_readcyclecounter();

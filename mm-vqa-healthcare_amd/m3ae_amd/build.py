@@ -29,7 +29,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 # gload16_asm): between such a load and its wait the destination registers are in flight, and a register spill there would save
 # garbage.  hipcc cannot know; this build checks instead: every instantiation of these kernels except the catch-all epilogue class
 # (EPI_ANY = 5, which keeps compiler-visible loads) must come out without scratch memory.
-ASM_LOAD_SOURCES = {"gemm_nt_pp2.hip": r"gemm_nt_pp2_kernel", "gemm_mfma.hip": r"gemm_nt_(bf16|pp|pp_persistent)_kernel"}
+ASM_LOAD_SOURCES = {"gemm_nt_pp2.hip": r"gemm_nt_pp2_kernel", "gemm_mfma.hip": r"gemm_nt_(bf16|pp)_kernel"}
 REMARK = "-Rpass-analysis=kernel-resource-usage"
 
 

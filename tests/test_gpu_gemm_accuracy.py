@@ -42,7 +42,7 @@ def cdiv(a, b):
 
 
 def expected_nt_path(M, N, K, ldc, variant):
-    """launch_nt_v's rules (csrc/gemm_mfma.hip)."""
+    """nt_kernel_choice's rules (csrc/gemm_mfma.hip)."""
     rows_epi = N % 8 == 0 and ldc % 8 == 0
     both = M > 128 and N > 128
     t256, t128 = cdiv(M, 256) * cdiv(N, 256), cdiv(M, 128) * cdiv(N, 128)
@@ -55,8 +55,6 @@ def expected_nt_path(M, N, K, ldc, variant):
     if variant in (9, 10) and both and rows_epi and K >= 256:
         return "mfma_nt_pp2"
     if variant == 7 and both:
-        return "mfma_nt_pp"
-    if variant == 8 and ((rows_epi and K >= 96 and t256 >= 512) or both):
         return "mfma_nt_pp"
     return "mfma_nt"
 
@@ -134,7 +132,7 @@ def test_nt_exact(shape, variant):
     if (M, N) == (5125, 3336):
         assert M * N >= 16 << 20 and cdiv(M, 256) * cdiv(N, 256) == 294   # by-size streaming stores; more tiles than one round of CUs
     if (M, N) == (43557, 520):
-        assert cdiv(M, 256) * cdiv(N, 256) == 513                          # the persistent ping-pong kernel's threshold is 512
+        assert cdiv(M, 256) * cdiv(N, 256) == 513                          # more than 512 tiles: two full rounds of one workgroup per CU
     exact_nt(shape, variant)
 
 

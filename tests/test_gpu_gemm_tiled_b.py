@@ -180,11 +180,12 @@ def test_gemm_tiled_b_128_tile_shapes(N, K):
     _tiled_against_row_major(200, N, K, (-1, 0), "mfma_nt" if K % 64 == 0 else "generic")
 
 
-@pytest.mark.parametrize("variant", [4, 7, 8])
-def test_gemm_tiled_b_on_the_other_256_tile_kernels(variant):
-    """The kernels a selector (or a shape the second-generation kernel does not take) can still reach: 2-stage (4), first-generation
-    ping-pong (7) and its persistent form (8, >= 512 tiles)."""
-    M, N, K = (300, 384, 256) if variant != 8 else (64 * 256 + 11, 8 * 256 + 40, 128)
+@pytest.mark.parametrize("variant,shape", [(4, (300, 384, 256)), (7, (300, 384, 256)), (7, (64 * 256 + 11, 8 * 256 + 40, 128))],
+                         ids=["4", "7", "7-585tiles"])
+def test_gemm_tiled_b_on_the_other_256_tile_kernels(variant, shape):
+    """The kernels a selector (or a shape the second-generation kernel does not take) can still reach: 2-stage (4) and first-generation
+    ping-pong (7); the latter also at a short reduction with more than 512 tiles (65 x 9, four chunks, ragged in M and N)."""
+    M, N, K = shape
     x, w = rnd(M, K, seed=7), rnd(N, K, seed=8, scale=K ** -0.5)
     wt, b, aux = tb.tile_reference(w), rnd(N, seed=9, dtype=F32), rnd(M, N, seed=10)
     ops.GEMM_NT_VARIANT = variant

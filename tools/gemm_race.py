@@ -9,7 +9,7 @@ import torch  # noqa: E402
 from m3ae_amd import _lib, ops  # noqa: E402
 
 ITERS = int(os.environ.get("ITERS", 30))
-VAR = int(os.environ.get("VAR", 7))   # 7: ping-pong kernel, 8: its persistent form (shapes with >= 512 tiles)
+VAR = int(os.environ.get("VAR", 7))   # 7: first-generation ping-pong kernel, 9 / 10: the second-generation kernel per tile / persistent
 SHAPES = [(147712, 768, 768), (73856, 768, 3072), (36928, 768, 768), (36928, 3072, 768), (36928, 768, 3072), (4096, 4096, 4096), (2308, 2304, 768), (1000, 520, 64),
           (777, 1288, 128), (8192, 8192, 1024), (5000, 768, 192)]
 

@@ -2,7 +2,7 @@
 (rounds x variants), min and median per variant; every variant's output is first compared bit for bit with variant 4 (the
 2-stage kernel with the same accumulation order).
 
-    B=256 VARS=8,10 ROUNDS=5 python tools/nt_ab.py [tag]      (M=8192: other row counts; SHAPES=2304x768,...: a subset)
+    B=256 VARS=7,10 ROUNDS=5 python tools/nt_ab.py [tag]      (M=8192: other row counts; SHAPES=2304x768,...: a subset)
     VARS=-1,999: by shape with the row-major weight against by shape with the tiled weight (v + 1000: variant v, B from the tiled copy)
 """
 import os
@@ -14,7 +14,7 @@ sys.path.insert(0, os.path.join(ROOT, "mm-vqa-healthcare_amd"))
 import torch  # noqa: E402
 from m3ae_amd import ops, tiled_b  # noqa: E402
 
-VARS = tuple(int(v) for v in os.environ.get("VARS", "8,10").split(","))   # v + 100 * p: variant v with output-store policy p (1 plain, 2 nt, 3 sc1)
+VARS = tuple(int(v) for v in os.environ.get("VARS", "7,10").split(","))   # v + 100 * p: variant v with output-store policy p (1 plain, 2 nt, 3 sc1)
                                                                           # + 1000: B is the tiled copy of the weight (999 = by shape, tiled)
 
 

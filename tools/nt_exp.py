@@ -1,5 +1,11 @@
-"""Times the dominant NT GEMM (auto = persistent ping-pong kernel) on the step's shapes at per-GPU batch B (default 256):
-plain, bias + residual, GELU + saved derivative, derivative multiply.   B=256 python tools/nt_exp.py [tag]"""
+"""Times the dominant NT GEMM (by shape: the second-generation ping-pong kernel, persistent launch) on the step's shapes at per-GPU
+batch B (default 256): plain, bias + residual, GELU + saved derivative, derivative multiply.   B=256 python tools/nt_exp.py [tag]
+
+Timing-only experiment builds (wrong results; -DM3AE_EXP_NT_NOSTORE: output stores dropped, -DM3AE_EXP_PP2_HALFREADS,
+-DM3AE_EXP_PP2_STAGGER=<clocks>) go to m3ae_amd/lib_diag/ and never touch the product library:
+    (cd mm-vqa-healthcare_amd && M3AE_EXTRA_HIPCC_FLAGS="-DM3AE_EXP_NT_NOSTORE" python -m m3ae_amd.build)
+    M3AE_DIAGNOSTIC_LIB=1 python tools/nt_exp.py "flags: -DM3AE_EXP_NT_NOSTORE"
+"""
 import os
 import sys
 
