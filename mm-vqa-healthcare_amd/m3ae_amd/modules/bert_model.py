@@ -159,16 +159,16 @@ class BertCrossLayer(nn.Module):
             self._bp = NS(attn=self.attention.block_params(), cross=self.crossattention.block_params(),
                           ffn=_ffn_params(self))
             self._anchors = tuple(self.parameters())
-        self._bp.want_probs = self._bp.cross.want_probs = bool(output_attentions)
-        self._bp.pdrop = self.drop_rate if self.training else 0.0
-        # (deterministic mode keeps the full layer: the live form's LayerNorm backward has no ordered entry point)
-        self._bp.cls_only = bool(cls_only) and not output_attentions and not ops.deterministic()
-        # forward-only calls always take the fused cross-attention sub-block; training takes it with its fused backward
-        self._bp.fused_cross = (not torch.is_grad_enabled()) or (ops.XATTN_TRAIN != "off" and
-                                                                 hidden_states.shape[0] >= ops.XATTN_TRAIN_MIN_BATCH)
-        self._bp.cross.need_bwd = torch.is_grad_enabled()
+        opts = ops.BlockOpts(
+            pdrop=self.drop_rate if self.training else 0.0,
+            # (deterministic mode keeps the full layer: the live form's LayerNorm backward has no ordered entry point)
+            cls_only=bool(cls_only) and not output_attentions and not ops.deterministic(),
+            # forward-only calls always take the fused cross-attention sub-block; training takes it with its fused backward
+            fused_cross=(not torch.is_grad_enabled()) or (ops.XATTN_TRAIN != "off" and
+                                                          hidden_states.shape[0] >= ops.XATTN_TRAIN_MIN_BATCH),
+            want_probs=bool(output_attentions), need_bwd=torch.is_grad_enabled())
         return ops.BertCrossLayerFn.apply(hidden_states, encoder_hidden_states, attention_mask, encoder_attention_mask,
-                                          self._bp, *self._anchors)
+                                          self._bp, opts, *self._anchors)
 
     def forward_unfused(self, hidden_states, encoder_hidden_states, attention_mask=None, encoder_attention_mask=None):
         """Op-level composition (one autograd node per kernel group); kept for A/B checks against the fused node."""
@@ -197,8 +197,8 @@ class BertSelfLayer(nn.Module):
         if self._bp is None:
             self._bp = NS(attn=self.attention.block_params(), ffn=_ffn_params(self))
             self._anchors = tuple(self.parameters())
-        self._bp.pdrop = self.drop_rate if self.training else 0.0
-        return ops.BertSelfLayerFn.apply(hidden_states, attention_mask, self._bp, *self._anchors)
+        opts = ops.BlockOpts(pdrop=self.drop_rate if self.training else 0.0)
+        return ops.BertSelfLayerFn.apply(hidden_states, attention_mask, self._bp, opts, *self._anchors)
 
     def forward_unfused(self, hidden_states, attention_mask=None):
         pd = self.drop_rate if self.training else 0.0

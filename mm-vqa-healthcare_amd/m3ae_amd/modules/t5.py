@@ -140,10 +140,10 @@ class T5Block(nn.Module):
 
     def forward(self, h, pos_bias, enc=None):
         P = self.params()
-        P.pdrop = self.dropout_rate if self.training else 0.0
+        opts = ops.BlockOpts(pdrop=self.dropout_rate if self.training else 0.0)
         if self.is_decoder:
-            return ops.T5DecBlockFn.apply(h, enc, pos_bias, P, *self._anchors)
-        return ops.T5EncBlockFn.apply(h, pos_bias, P, *self._anchors)
+            return ops.T5DecBlockFn.apply(h, enc, pos_bias, P, opts, *self._anchors)
+        return ops.T5EncBlockFn.apply(h, pos_bias, P, opts, *self._anchors)
 
     def weight_units(self):
         sa = self.layer[0].SelfAttention

@@ -12,6 +12,7 @@ import functools
 import math
 import os
 import threading
+from typing import NamedTuple
 
 import torch
 
@@ -347,31 +348,37 @@ def use_launch_stream():
 
 
 def mm_nt(x2, ldx, M, w, bias=None, act=ACT_NONE, residual=None, want_preact=False, out_dtype=None, dact_aux=None,
-          dact=ACT_NONE, force_generic=False, alpha=1.0, dropout=None, preact_grad=False, rows=None):
+          dact=ACT_NONE, force_generic=False, alpha=1.0, dropout=None, preact_grad=False, rows=None, sl=None):
     """y[M,N] = epi(alpha * x2[M,K] . w[N,K]^T).  want_preact + preact_grad: the second output is act'(pre-activation)
-    (consumed by a backward GEMM with dact=ACT_MULAUX) instead of the pre-activation itself."""
+    (consumed by a backward GEMM with dact=ACT_MULAUX) instead of the pre-activation itself.  sl: a slice of the rows of w
+    and of bias (the Q or the K | V part of a packed projection): read in place with the weight's strides, never from the
+    tiled copy -- also when the slice is the whole range."""
+    if sl is not None:
+        w, bias = w[sl], None if bias is None else bias[sl]
     N, K = w.shape
     y = torch.empty((M, N), dtype=out_dtype or x2.dtype, device=x2.device)
     pre = torch.empty_like(y) if want_preact else None
-    tb = getattr(w, "m3ae_tb", None) if TILED_B and x2.dtype == torch.bfloat16 and w.stride(0) == K else None
+    tb = getattr(w, "m3ae_tb", None) if TILED_B and sl is None and x2.dtype == torch.bfloat16 and w.stride(0) == K else None
     gemm(x2, ldx, 1, w if tb is None else tb, 1, w.stride(0), y, N, M, N, K, bias=bias, act=act, preact=pre, residual=residual,
          dact_aux=dact_aux, dact=dact, force_generic=force_generic, alpha=alpha, dropout=dropout,
          preact_grad=preact_grad and want_preact, rows=rows, b_tiled=tb is not None)
     return y, pre
 
 
-def mm_dgrad(dy, w_param, dact_aux=None, dact=ACT_NONE, residual=None, alpha=1.0, dropout=None, out=None, ld_out=None, rows=None):
+def mm_dgrad(dy, w_param, dact_aux=None, dact=ACT_NONE, residual=None, alpha=1.0, dropout=None, out=None, ld_out=None, rows=None,
+             sl=None):
     """dx[M,K] = dy[M,N] . W[N,K]  (bf16: NT against the transposed shadow; fp32: strided generic).  out / ld_out: write
-    the rows into this preallocated tensor at this row stride instead of a fresh [M, K]."""
+    the rows into this preallocated tensor at this row stride instead of a fresh [M, K].  sl: W = rows `sl` of the parameter
+    (columns of its transposed shadow), as in mm_nt."""
     M, N = dy.shape
     wt = getattr(w_param, "m3ae_t", None)
-    wtt = getattr(w_param, "m3ae_tt", None) if TILED_B and wt is not None and dy.dtype == torch.bfloat16 else None
+    wtt = getattr(w_param, "m3ae_tt", None) if TILED_B and sl is None and wt is not None and dy.dtype == torch.bfloat16 else None
     if wtt is not None:   # the tiled copy of the transposed shadow [K, N]: row length N
         b, b_sk, b_sn, K = wtt, 1, N, wt.shape[0]
     elif wt is not None:
-        b, b_sk, b_sn, K = wt, 1, wt.stride(0), wt.shape[0]
+        b, b_sk, b_sn, K = (wt if sl is None else wt[:, sl]), 1, wt.stride(0), wt.shape[0]
     else:
-        b = compute_weight(w_param)
+        b = compute_weight(w_param) if sl is None else compute_weight(w_param)[sl]
         b_sk, b_sn, K = b.stride(0), 1, b.shape[1]
     if out is None:
         out, ld_out = torch.empty((M, K), dtype=dy.dtype, device=dy.device), K
@@ -380,22 +387,24 @@ def mm_dgrad(dy, w_param, dact_aux=None, dact=ACT_NONE, residual=None, alpha=1.0
     return out
 
 
-def mm_wgrad(dy, x2, ldx, w_param, b_param=None, alpha=1.0):
+def mm_wgrad(dy, x2, ldx, w_param, b_param=None, alpha=1.0, sl=None):
     """w.grad[N,K] += dy[M,N]^T . x2[M,K]  (fp32 accumulate in place); with b_param also b.grad[N] += colsum(dy),
-    fused into the same kernel (row sums of the A operand dy^T)."""
+    fused into the same kernel (row sums of the A operand dy^T).  sl: into rows `sl` of both gradients; the parameters are
+    then NOT reported done: the caller does that (_done) once all slices of a parameter are in."""
     want_b = b_param is not None and b_param.requires_grad
+    gb = None if not want_b else _grad_buf(b_param) if sl is None else _grad_buf(b_param)[sl]
     if not w_param.requires_grad:
         if want_b:
-            bias_grad(dy, b_param)
-        return
-    g = _grad_buf(w_param)
-    M, N = dy.shape
-    K = g.shape[1]
-    gemm(dy, 1, dy.stride(0), x2, ldx, 1, g, g.stride(0), N, K, M, accumulate=True, alpha=alpha,
-         a_rowsum=_grad_buf(b_param) if want_b else None)
-    _done(w_param)
-    if want_b:
-        _done(b_param)
+            colsum(dy, gb, True)
+    else:
+        g = _grad_buf(w_param) if sl is None else _grad_buf(w_param)[sl]
+        M, N = dy.shape
+        gemm(dy, 1, dy.stride(0), x2, ldx, 1, g, g.stride(0), N, g.shape[1], M, accumulate=True, alpha=alpha, a_rowsum=gb)
+    if sl is None:
+        if w_param.requires_grad:
+            _done(w_param)
+        if want_b:
+            _done(b_param)
 
 
 def colsum(x, out, accumulate):
@@ -407,13 +416,6 @@ def colsum(x, out, accumulate):
               "m3ae_colsum_det")
         return
     check(_lib.lib().m3ae_colsum(_p(x), _p(out), M, N, x.stride(0), _dt(x), int(accumulate), _stream()), "m3ae_colsum")
-
-
-def bias_grad(dy, b_param):
-    if b_param is None or not b_param.requires_grad:
-        return
-    colsum(dy, _grad_buf(b_param), True)
-    _done(b_param)
 
 
 def act_bwd(dy, pre, act):
@@ -608,46 +610,19 @@ class LayerNormFn(Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, act, rms, out_dtype=None):
         xc = x.contiguous()
-        D = xc.shape[-1]
-        M = xc.numel() // D
-        y = torch.empty_like(xc, dtype=out_dtype or xc.dtype)
-        mean = torch.empty(M, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(M, dtype=torch.float32, device=x.device)
-        if y.dtype != xc.dtype:   # fp32 rows -> bf16 rows (the fp32 residual stream of a bf16 CLIP tower)
-            _ln_mixed_ok(xc, y, act, rms)
-            check(_lib.lib().m3ae_layernorm_fwd_mixed(_p(xc), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), M, D, eps, _stream()),
-                  "m3ae_layernorm_fwd_mixed")
-        else:
-            check(_lib.lib().m3ae_layernorm_fwd(_p(xc), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), M, D, eps, _dt(xc),
-                                                act, int(rms), _stream()), "m3ae_layernorm_fwd")
+        ln = (gamma, beta, eps)
+        y, mean, rstd = ln_fwd_raw(xc.view(-1, xc.shape[-1]), ln, act, rms, out_dtype, rms_mean=True)
         ctx.save_for_backward(xc, mean, rstd)
-        ctx.gamma, ctx.beta, ctx.act, ctx.rms = gamma, beta, act, rms
-        return y
+        ctx.ln, ctx.act, ctx.rms = ln, act, rms
+        return y.view(xc.shape)
 
     @staticmethod
     def backward(ctx, dy):
         xc, mean, rstd = ctx.saved_tensors
         D = xc.shape[-1]
-        M = xc.numel() // D
-        dyc = dy.contiguous()
-        dx = torch.empty_like(xc)
-        L = _lib.lib()
-        nblk = L.m3ae_layernorm_bwd_blocks(M)
-        ws = torch.empty(2 * nblk * D, dtype=torch.float32, device=xc.device)
-        gg = _grad_buf(ctx.gamma)
-        gb = _grad_buf(ctx.beta) if ctx.beta is not None else None
-        if dyc.dtype != xc.dtype:
-            ln_bwd = L.m3ae_layernorm_bwd_mixed_det if _DETERMINISTIC else L.m3ae_layernorm_bwd_mixed
-            check(ln_bwd(_p(dyc), _p(xc), _p(ctx.gamma), _p(mean), _p(rstd), _p(dx), None, None, _p(gg), _p(gb), _p(ws), M, D,
-                         _stream()), "m3ae_layernorm_bwd_mixed")
-        else:
-            ln_bwd = L.m3ae_layernorm_bwd_det if _DETERMINISTIC else L.m3ae_layernorm_bwd
-            check(ln_bwd(_p(dyc), _p(xc), _p(ctx.gamma), _p(ctx.beta), _p(mean), _p(rstd), _p(dx), None,
-                         _p(gg), _p(gb), _p(ws), M, D, _dt(xc), ctx.act, int(ctx.rms), _stream()),
-                  "m3ae_layernorm_bwd")
-        _done(ctx.gamma)
-        _done(ctx.beta)
-        return dx, None, None, None, None, None, None
+        # (train=True: the op accumulates into the gamma / beta it was given, whatever their requires_grad)
+        dx = ln_bwd_raw(dy.contiguous().view(-1, D), xc.view(-1, D), ctx.ln, mean, rstd, act=ctx.act, rms=ctx.rms, train=True)
+        return dx.view(xc.shape), None, None, None, None, None, None
 
 
 def layer_norm(x, gamma, beta, eps, act=ACT_NONE, rms=False, out_dtype=None):
@@ -663,71 +638,81 @@ def _ln_mixed_ok(x, y, act, rms):
 
 
 # ----------------------------------------------------------------------------------------------------------
-# raw LayerNorm helpers (no autograd) for the fused block functions
+# raw LayerNorm helpers (no autograd): the fused block functions and LayerNormFn.  The ONE place that picks a LayerNorm entry
+# point of the library.  `ln`: a LayerNorm module (weight, bias, eps) or the triple (gamma, beta, eps) itself.
 # ----------------------------------------------------------------------------------------------------------
-def ln_fwd_raw(x2, ln, act=ACT_NONE, rms=False, out_dtype=None):
+def _ln_params(ln):
+    return ln if isinstance(ln, tuple) else (ln.weight, ln.bias, ln.eps)
+
+
+def ln_fwd_raw(x2, ln, act=ACT_NONE, rms=False, out_dtype=None, rms_mean=False):
+    """(y, mean, rstd) of rows x2 [M, D].  rms: no mean is kept (None), unless rms_mean (LayerNormFn hands the kernel a buffer
+    all the same)."""
     M, D = x2.shape
+    gamma, beta, eps = _ln_params(ln)
     y = torch.empty_like(x2, dtype=out_dtype or x2.dtype)
-    mean = None if rms else torch.empty(M, dtype=torch.float32, device=x2.device)
+    mean = None if rms and not rms_mean else torch.empty(M, dtype=torch.float32, device=x2.device)
     rstd = torch.empty(M, dtype=torch.float32, device=x2.device)
-    if y.dtype != x2.dtype:
+    if y.dtype != x2.dtype:   # fp32 rows -> bf16 rows (the fp32 residual stream of a bf16 CLIP tower)
         _ln_mixed_ok(x2, y, act, rms)
-        check(_lib.lib().m3ae_layernorm_fwd_mixed(_p(x2), _p(ln.weight), _p(ln.bias), _p(y), _p(mean), _p(rstd), M, D, ln.eps,
-                                                  _stream()), "m3ae_layernorm_fwd_mixed")
-        return y, mean, rstd
-    check(_lib.lib().m3ae_layernorm_fwd(_p(x2), _p(ln.weight), _p(ln.bias), _p(y), _p(mean), _p(rstd), M, D, ln.eps,
-                                        _dt(x2), act, int(rms), _stream()), "m3ae_layernorm_fwd")
+        check(_lib.lib().m3ae_layernorm_fwd_mixed(_p(x2), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), M, D, eps, _stream()),
+              "LayerNorm forward (mixed form)")
+    else:
+        check(_lib.lib().m3ae_layernorm_fwd(_p(x2), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), M, D, eps, _dt(x2), act,
+                                            int(rms), _stream()), "LayerNorm forward")
     return y, mean, rstd
 
 
-def ln_bwd_raw(dy, x2, ln, mean, rstd, dx_add=None, act=ACT_NONE, rms=False, drop=None, rows=None, want_lo=False):
-    """dx = LN'(dy) (+ dx_add); ln.weight.grad / ln.bias.grad accumulate in place.  With drop = (p, seed) returns
-    (dx, dx_drop): dx_drop is dx under the dropout mask of the dense layer that fed this LayerNorm.  bf16 dy on fp32 x2 (the
-    fp32 residual stream of a bf16 CLIP tower): dx and dx_add are fp32, and want_lo returns (dx, dx rounded to bf16)."""
+def ln_bwd_raw(dy, x2, ln, mean, rstd, dx_add=None, act=ACT_NONE, rms=False, drop=None, rows=None, want_lo=False, train=None):
+    """dx = LN'(dy) (+ dx_add); gamma.grad / beta.grad accumulate in place (train: whether they do; default gamma.requires_grad).
+    With drop = (p, seed) returns (dx, dx_drop): dx_drop is dx under the dropout mask of the dense layer that fed this LayerNorm,
+    rows = (row_base, row_step) the row map of that mask.  bf16 dy on fp32 x2 (the fp32 residual stream of a bf16 CLIP tower): dx
+    and dx_add are fp32, and want_lo returns (dx, dx rounded to bf16).
+    The entry point follows from (dropout, row map, mixed dtypes, deterministic mode); a row map in deterministic mode has none
+    and raises DeterministicError."""
     M, D = x2.shape
-    L = _lib.lib()
-    dx = torch.empty_like(x2)
-    nblk = L.m3ae_layernorm_bwd_blocks(M)
-    ws = torch.empty(2 * nblk * D, dtype=torch.float32, device=x2.device)
-    train = ln.weight.requires_grad
-    gg = _grad_buf(ln.weight) if train else None
-    gb = _grad_buf(ln.bias) if (train and ln.bias is not None) else None
-    if drop is not None and drop[0] > 0:
-        assert dx_add is None and act == ACT_NONE and not rms
-        dxd = torch.empty_like(x2)
-        if rows is not None:   # (the live-row form is not taken in deterministic mode)
-            check(L.m3ae_layernorm_bwd_drop_rows(_p(dy), _p(x2), _p(ln.weight), _p(ln.bias), _p(mean), _p(rstd), _p(dx), _p(dxd),
-                                                 drop[0], drop[1], _salt(), _p(gg), _p(gb), _p(ws), M, D, _dt(x2), rows[0], rows[1],
-                                                 _stream()), "m3ae_layernorm_bwd_drop_rows")
-            if train:
-                _done(ln.weight)
-                _done(ln.bias)
-            return dx, dxd
-        ln_bwd_drop = L.m3ae_layernorm_bwd_drop_det if _DETERMINISTIC else L.m3ae_layernorm_bwd_drop
-        check(ln_bwd_drop(_p(dy), _p(x2), _p(ln.weight), _p(ln.bias), _p(mean), _p(rstd), _p(dx), _p(dxd),
-                          drop[0], drop[1], _salt(), _p(gg), _p(gb), _p(ws), M, D, _dt(x2), _stream()),
-              "m3ae_layernorm_bwd_drop")
-        if train:
-            _done(ln.weight)
-            _done(ln.bias)
-        return dx, dxd
-    dx_lo = None
-    if dy.dtype != x2.dtype:
+    gamma, beta, eps = _ln_params(ln)
+    drop = drop if drop is not None and drop[0] > 0 else None
+    mixed = dy.dtype != x2.dtype
+    rows = rows if drop is not None else None   # (only the dropout mask has rows to map)
+    if rows is not None:
+        _no_ordered_form("the LayerNorm backward under a dropout row map (the live-row form)")
+    if drop is not None:
+        assert dx_add is None and act == ACT_NONE and not rms and not mixed and not want_lo
+    elif mixed:
         _ln_mixed_ok(x2, dy, act, rms)
         assert dx_add is None or dx_add.dtype == torch.float32
-        dx_lo = torch.empty_like(dy) if want_lo else None
-        ln_bwd = L.m3ae_layernorm_bwd_mixed_det if _DETERMINISTIC else L.m3ae_layernorm_bwd_mixed
-        check(ln_bwd(_p(dy), _p(x2), _p(ln.weight), _p(mean), _p(rstd), _p(dx), _p(dx_add), _p(dx_lo), _p(gg), _p(gb), _p(ws), M, D,
-                     _stream()), "m3ae_layernorm_bwd_mixed")
     else:
         assert not want_lo
-        ln_bwd = L.m3ae_layernorm_bwd_det if _DETERMINISTIC else L.m3ae_layernorm_bwd
-        check(ln_bwd(_p(dy), _p(x2), _p(ln.weight), _p(ln.bias), _p(mean), _p(rstd), _p(dx), _p(dx_add),
-                     _p(gg), _p(gb), _p(ws), M, D, _dt(x2), act, int(rms), _stream()), "m3ae_layernorm_bwd")
+    L = _lib.lib()
+    if drop is not None:
+        fn = L.m3ae_layernorm_bwd_drop_rows if rows is not None else \
+            L.m3ae_layernorm_bwd_drop_det if _DETERMINISTIC else L.m3ae_layernorm_bwd_drop
+    elif mixed:
+        fn = L.m3ae_layernorm_bwd_mixed_det if _DETERMINISTIC else L.m3ae_layernorm_bwd_mixed
+    else:
+        fn = L.m3ae_layernorm_bwd_det if _DETERMINISTIC else L.m3ae_layernorm_bwd
+    dx = torch.empty_like(x2)
+    ws = torch.empty(2 * L.m3ae_layernorm_bwd_blocks(M) * D, dtype=torch.float32, device=x2.device)
+    train = gamma.requires_grad if train is None else train
+    gg = _grad_buf(gamma) if train else None
+    gb = _grad_buf(beta) if (train and beta is not None) else None
+    second = None   # the second output: dx under the dropout mask, or dx rounded to bf16
+    if drop is not None:
+        second = torch.empty_like(x2)
+        check(fn(_p(dy), _p(x2), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dx), _p(second), drop[0], drop[1], _salt(), _p(gg),
+                 _p(gb), _p(ws), M, D, _dt(x2), *(rows or ()), _stream()), "LayerNorm backward (dropout form)")
+    elif mixed:
+        second = torch.empty_like(dy) if want_lo else None
+        check(fn(_p(dy), _p(x2), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dx_add), _p(second), _p(gg), _p(gb), _p(ws), M, D,
+                 _stream()), "LayerNorm backward (mixed form)")
+    else:
+        check(fn(_p(dy), _p(x2), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dx), _p(dx_add), _p(gg), _p(gb), _p(ws), M, D,
+                 _dt(x2), act, int(rms), _stream()), "LayerNorm backward")
     if train:
-        _done(ln.weight)
-        _done(ln.bias)
-    return (dx, dx_lo) if want_lo else dx
+        _done(gamma)
+        _done(beta)
+    return (dx, second) if (drop is not None or want_lo) else dx
 
 
 # ----------------------------------------------------------------------------------------------------------
@@ -1091,41 +1076,76 @@ def _qkv_views(bufs, B):
     return q.view(B, -1, n), kv3[..., :n], kv3[..., n:]
 
 
-def _attn_core_fwd(x2, B, P, src2=None, kv=None, mask=None, pos_bias=None, scale=None, causal=False, dropout=None):
-    """Projections + attention product of every block family.  x2 [B L, D]: the rows the queries come from; keys / values from
-    x2 too (packed P.w_qkv), or from the other stream's rows src2 [B Ls, Ds] (P.w_q, P.w_kv), or ready-made in kv [B Ls,
-    2 inner].  dropout = (p, seed) of the attention probabilities.  Returns (o [B, L, inner], lse, proj), proj = (qkv,) or (q, kv)."""
-    M, D = x2.shape
-    if src2 is None and kv is None:
-        proj = (mm_nt(x2, D, M, compute_weight(P.w_qkv), bias=_bdata(P.b_qkv))[0],)
+class _ProjRows(NamedTuple):
+    """One projection of an attention parameter set: weight, bias (or None) and the slice of their rows it takes (None: all
+    of them, through mm_nt / mm_dgrad / mm_wgrad without `sl`)."""
+    w: object
+    b: object
+    sl: object = None
+
+
+def _attn_proj(P, live=False):
+    """(Q, K | V) projections of an attention parameter set: the two slices of the packed Q | K | V weight, or the separate Q
+    and K | V weights (cross-attention; live-row form: as whole-range slices, which keeps its B-row GEMMs on the shadows)."""
+    if hasattr(P, "w_qkv"):
+        n = P.w_qkv.shape[0] // 3
+        return _ProjRows(P.w_qkv, P.b_qkv, slice(0, n)), _ProjRows(P.w_qkv, P.b_qkv, slice(n, 3 * n))
+    sl = slice(None) if live else None
+    return _ProjRows(P.w_q, P.b_q, sl), _ProjRows(P.w_kv, P.b_kv, sl)
+
+
+def _attn_core_fwd(xq, xkv, B, P, kv=None, mask=None, pos_bias=None, scale=None, causal=False, dropout=None, rows=None):
+    """Projections + attention product of every block family.  xq [B Lq, D]: the rows the queries come from; xkv [B Ls, Ds]: the
+    rows the keys / values come from.  xkv is xq: packed self-attention, Q | K | V in one GEMM (P.w_qkv).  Other rows: two GEMMs,
+    P.w_q and P.w_kv (cross-attention), or the Q and the K | V slice of P.w_qkv (live-row self-attention: xq = token 0 of the
+    samples of xkv).  kv [B Ls, 2 inner]: ready-made keys / values (xkv is then None).  dropout = (p, seed) of the attention
+    probabilities, rows their row map (live-row form).  Returns (o [B, Lq, inner], lse, proj), proj = (qkv,) or (q, kv)."""
+    M, D = xq.shape
+    if xkv is xq:
+        proj = (mm_nt(xq, D, M, compute_weight(P.w_qkv), bias=_bdata(P.b_qkv))[0],)
     else:
-        q, _ = mm_nt(x2, D, M, compute_weight(P.w_q), bias=_bdata(P.b_q))
+        pq, pkv = _attn_proj(P, live=rows is not None)
+        q, _ = mm_nt(xq, D, M, compute_weight(pq.w), bias=_bdata(pq.b), sl=pq.sl)
         if kv is None:
-            kv, _ = mm_nt(src2, src2.shape[1], src2.shape[0], compute_weight(P.w_kv), bias=_bdata(P.b_kv))
+            kv, _ = mm_nt(xkv, xkv.shape[1], xkv.shape[0], compute_weight(pkv.w), bias=_bdata(pkv.b), sl=pkv.sl)
         proj = (q, kv)
     q3, k3, v3 = _qkv_views(proj, B)
-    o, lse = attn_forward(q3, k3, v3, P.heads, mask, pos_bias, scale, causal, dropout)
+    o, lse = attn_forward(q3, k3, v3, P.heads, mask, pos_bias, scale, causal, dropout, rows)
     return o, lse, proj
 
 
-def _attn_core_bwd(dctx, x2, src2, proj, o, lse, B, P, mask=None, pos_bias=None, scale=None, causal=False, dropout=None,
-                   d_pos_bias=None, residual=None, need_dx=True, need_dsrc=True):
-    """Backward of _attn_core_fwd from dctx = d(o) [B L, inner]: attention backward into a packed gradient buffer, the weight
-    gradients, then the input gradients.  Returns (dx, dsrc); `residual` is added to dx in the dgrad epilogue.  Self or cross is
-    read off `proj`, i.e. off what the forward did."""
+def _attn_core_bwd(dctx, xq, xkv, proj, o, lse, B, P, mask=None, pos_bias=None, scale=None, causal=False, dropout=None,
+                   d_pos_bias=None, residual=None, need_dx=True, need_dsrc=True, rows=None):
+    """Backward of _attn_core_fwd from dctx = d(o) [B Lq, inner]: attention backward into a packed gradient buffer, the weight
+    gradients, then the input gradients.  Returns (dx, dsrc); `residual` is added to dx in the dgrad epilogue.  Packed or not is
+    read off `proj`, i.e. off what the forward did.  Live-row self-attention: (dx [B Ls, D], None), the gradient of ALL rows of
+    the stream (xkv), token 0's with its query part and `residual` in."""
     dproj = tuple(torch.empty_like(t) for t in proj)
     attn_backward(*_qkv_views(proj, B), o, lse, dctx.view(o.shape), *_qkv_views(dproj, B), P.heads, mask, pos_bias, scale,
-                  causal, d_pos_bias, dropout)
-    D = x2.shape[1]
+                  causal, d_pos_bias, dropout, rows)
+    D = xq.shape[1]
     if len(proj) == 1:
-        mm_wgrad(dproj[0], x2, D, P.w_qkv, P.b_qkv)
+        mm_wgrad(dproj[0], xq, D, P.w_qkv, P.b_qkv)
         return (mm_dgrad(dproj[0], P.w_qkv, residual=residual) if need_dx else None), None
-    assert src2 is not None, "the forward was given ready-made kv (inference only): there is no source to differentiate"
+    assert xkv is not None, "the forward was given ready-made kv (inference only): there is no source to differentiate"
+    pq, pkv = _attn_proj(P, live=rows is not None)
     dq, dkv = dproj
-    mm_wgrad(dq, x2, D, P.w_q, P.b_q)
-    mm_wgrad(dkv, src2, src2.shape[1], P.w_kv, P.b_kv)
-    dx = mm_dgrad(dq, P.w_q, residual=residual) if need_dx else None
-    return dx, (mm_dgrad(dkv, P.w_kv) if need_dsrc else None)
+    mm_wgrad(dq, xq, D, pq.w, pq.b, sl=pq.sl)
+    mm_wgrad(dkv, xkv, xkv.shape[1], pkv.w, pkv.b, sl=pkv.sl)
+    if pq.sl is not None:   # sliced weight gradients report nothing: every distinct parameter once, now that its slices are in
+        for prm in {id(p): p for p in (pq.w, pq.b, pkv.w, pkv.b) if p is not None}.values():
+            if prm.requires_grad:
+                _done(prm)
+    if pq.w is pkv.w:
+        # LIVE-ROW SELF-ATTENTION: token 0 is query and key.  Its gradient is the full layer's product for that row, d(q | k | v)
+        # . W_qkv + residual in ONE accumulation and one rounding (the same bits as the full call's row, so the layers below see
+        # the same gradient): B packed rows, written over row 0 of the key / value rows' gradient
+        dx = mm_dgrad(dkv, pkv.w, sl=pkv.sl)
+        dqkv0 = torch.cat([dq, dkv.view(B, -1, dkv.shape[1])[:, 0]], dim=1)
+        dx.view(B, -1, D)[:, 0] = mm_dgrad(dqkv0, pq.w, residual=residual)
+        return dx, None
+    dx = mm_dgrad(dq, pq.w, residual=residual, sl=pq.sl) if need_dx else None
+    return dx, (mm_dgrad(dkv, pkv.w, sl=pkv.sl) if need_dsrc else None)
 
 
 def _ffn_core_fwd(x2, P, act, residual, mid_drop=None, out_drop=None, rows=None):
@@ -1147,20 +1167,25 @@ def _ffn_core_bwd(dy, x2, u, g, P, act, mid_drop=None, residual=None, rows=None)
     return mm_dgrad(du, P.w1, residual=residual)
 
 
-def _attn_sub_fwd(h2, B, L, other2, Lo, mask, P, pdrop=0.0, fused_cross=False):
+def _attn_sub_fwd(h2, B, L, other2, Lo, mask, P, pdrop=0.0, fused_cross=False, need_bwd=True, want_probs=False, live=False):
     """BertAttention (bert_model.py:367-413) on 2-D token-major activations. Returns (y, saved).
     pdrop > 0 (training): attention-probability dropout (:334) and hidden dropout on the output dense (:362).
-    P.want_probs: the attention map will be asked of `saved` (_attn_sub_probs): a forward-only fused call copies it out."""
-    if other2 is not None and fused_cross:
-        need_bwd = getattr(P, "need_bwd", True)
-        if xattn_supported(h2, L, other2, Lo, mask, P, backward=need_bwd):
-            return xattn_fwd(h2, B, L, other2, Lo, mask, P, pdrop, need_bwd=need_bwd, want_probs=getattr(P, "want_probs", False))
+    fused_cross: take the fused cross-attention sub-block where it covers the shapes (need_bwd: and its backward does).
+    want_probs: the attention map will be asked of `saved` (_attn_sub_probs): a forward-only fused call copies it out.
+    live: the live-row form.  h2 [B, D] is token 0 of each sample (compact) and the only row computed; other2 [B Lo, Ds] the rows
+    of the keys / values -- the other stream's, or for self-attention all rows of the samples themselves.  L stays the query rows
+    per sample of the full call, whose dropout masks (rows b L of the dense sites, (b H + h) L of the probabilities) this call
+    draws, with seeds taken in the same order."""
+    if other2 is not None and fused_cross and not live and xattn_supported(h2, L, other2, Lo, mask, P, backward=need_bwd):
+        return xattn_fwd(h2, B, L, other2, Lo, mask, P, pdrop, need_bwd=need_bwd, want_probs=want_probs)
     da, dh = dropout_pair(pdrop), dropout_pair(pdrop)
-    o, lse, proj = _attn_core_fwd(h2, B, P, src2=other2, mask=mask, dropout=da)
-    D = h2.shape[1]
-    s, _ = mm_nt(o.view(B * L, D), D, B * L, compute_weight(P.w_o), bias=_bdata(P.b_o), residual=h2, dropout=dh)
+    rows = (0, L) if live else None
+    xkv = h2 if other2 is None else other2
+    o, lse, proj = _attn_core_fwd(h2, xkv, B, P, mask=mask, dropout=da, rows=rows)
+    M, n = h2.shape[0], o.shape[2]
+    s, _ = mm_nt(o.view(M, n), n, M, compute_weight(P.w_o), bias=_bdata(P.b_o), residual=h2, dropout=dh, rows=rows)
     y, mean, rstd = ln_fwd_raw(s, P.ln)
-    return y, (h2, other2, proj, o, lse, s, mean, rstd, mask, da, dh)
+    return y, (h2, xkv, proj, o, lse, s, mean, rstd, mask, da, dh, rows)
 
 
 def _attn_sub_probs(saved, B, L, Lo, P):
@@ -1168,8 +1193,8 @@ def _attn_sub_probs(saved, B, L, Lo, P):
     or the composition's projections and log-sum-exp table."""
     if isinstance(saved[0], str):
         return xattn_probs(saved)
-    h2, other2, proj, o, lse, s, mean, rstd, mask, da, dh = saved
-    q3, k3, _ = _qkv_views(proj, B)
+    q3, k3, _ = _qkv_views(saved[2], B)
+    lse, mask, da = saved[4], saved[8], saved[9]
     return attn_probs(q3, k3, lse, P.heads, mask, dropout=da)
 
 
@@ -1183,15 +1208,17 @@ def _post_ln_bwd(dy, s, ln, mean, rstd, dh, rows=None):
 
 
 def _attn_sub_bwd(dy, saved, B, L, Lo, P, need_dother=True):
+    """Backward of _attn_sub_fwd: (dh, dother).  Live-row form: dh is the gradient of the token-0 rows [B, D]; of self-attention,
+    whose key / value rows are the stream itself, the gradient of all its rows [B L, D]."""
     if isinstance(saved[0], str):   # ("xattn", ...): the fused sub-block
         return xattn_bwd(dy, saved, B, L, Lo, P, need_dother)
-    h2, other2, proj, o, lse, s, mean, rstd, mask, da, dh = saved
-    D = h2.shape[1]
-    ds, dsd = _post_ln_bwd(dy, s, P.ln, mean, rstd, dh)
-    mm_wgrad(dsd, o.view(B * L, D), D, P.w_o, P.b_o)
+    h2, xkv, proj, o, lse, s, mean, rstd, mask, da, dh, rows = saved
+    M, n = h2.shape[0], o.shape[2]
+    ds, dsd = _post_ln_bwd(dy, s, P.ln, mean, rstd, dh, rows)
+    mm_wgrad(dsd, o.view(M, n), n, P.w_o, P.b_o)
     dctx = mm_dgrad(dsd, P.w_o)
     # ds: the residual-branch gradient, joined in the last dgrad's epilogue
-    return _attn_core_bwd(dctx, h2, other2, proj, o, lse, B, P, mask=mask, dropout=da, residual=ds, need_dsrc=need_dother)
+    return _attn_core_bwd(dctx, h2, xkv, proj, o, lse, B, P, mask=mask, dropout=da, residual=ds, need_dsrc=need_dother, rows=rows)
 
 
 def _ffn_sub_fwd(h2, P, pdrop=0.0, rows=None):
@@ -1209,141 +1236,45 @@ def _ffn_sub_bwd(dy, saved, P):
     return _ffn_core_bwd(dsd, h2, u, g, P, ACT_GELU, residual=ds, rows=rows)
 
 
-# ---- live-row form of the BERT attention sub-block: the queries are token 0 of every sample, the keys all tokens -------------
-class _ProjRows:
-    """Rows r0:r1 of a projection parameter (the Q or the K | V slice of a packed Q | K | V weight, or a whole weight): the views
-    mm_nt / dgrad / wgrad read and write -- weight, bias, transposed shadow, gradient -- without a copy."""
-
-    def __init__(self, w_param, b_param, r0=None, r1=None):
-        self.w_param, self.b_param, self.sl = w_param, b_param, slice(r0, r1)
-
-    @property
-    def w(self):
-        return compute_weight(self.w_param)[self.sl]
-
-    @property
-    def b(self):
-        return _bdata(self.b_param)[self.sl]
-
-    def dgrad(self, dy, residual=None):
-        """dx[M, K] = dy[M, n] . W[r0:r1] (+ residual)"""
-        M, n = dy.shape
-        wt = getattr(self.w_param, "m3ae_t", None)
-        if wt is not None:
-            b = wt[:, self.sl]
-            b_sk, b_sn, K = 1, wt.stride(0), wt.shape[0]
-        else:
-            b = self.w
-            b_sk, b_sn, K = b.stride(0), 1, b.shape[1]
-        out = torch.empty((M, K), dtype=dy.dtype, device=dy.device)
-        gemm(dy, dy.stride(0), 1, b, b_sk, b_sn, out, K, M, K, n, residual=residual)
-        return out
-
-    def wgrad(self, dy, x2, ldx):
-        """W.grad[r0:r1] += dy^T . x2, b.grad[r0:r1] += colsum(dy); the caller reports the parameter done (ops._done) once all its
-        slices are in."""
-        want_b = self.b_param is not None and self.b_param.requires_grad
-        if not self.w_param.requires_grad:
-            if want_b:
-                colsum(dy, _grad_buf(self.b_param)[self.sl], True)
-            return
-        g = _grad_buf(self.w_param)[self.sl]
-        M, n = dy.shape
-        gemm(dy, 1, dy.stride(0), x2, ldx, 1, g, g.stride(0), n, g.shape[1], M, accumulate=True,
-             a_rowsum=_grad_buf(self.b_param)[self.sl] if want_b else None)
-
-
-def _live_proj(P, D):
-    """(q, kv) projection slices of a BertAttention parameter set: of the packed Q | K | V weight (self-attention) or the separate
-    Q and K | V weights (cross-attention)."""
-    if hasattr(P, "w_qkv"):
-        return _ProjRows(P.w_qkv, P.b_qkv, 0, D), _ProjRows(P.w_qkv, P.b_qkv, D, 3 * D)
-    return _ProjRows(P.w_q, P.b_q), _ProjRows(P.w_kv, P.b_kv)
-
-
-def _attn_sub_fwd_live(hq, src2, B, Ls, Lfull, mask, P, pdrop=0.0):
-    """_attn_sub_fwd for the queries hq [B, D] = token 0 of each of the B samples (compact), keys / values from all B Ls rows of
-    src2 (the sample's own rows: self-attention; the other modality's: cross-attention).  Lfull: query rows per sample of the
-    full call, whose dropout masks (rows b Lfull of the dense sites, (b H + h) Lfull of the probabilities) this call draws, with
-    seeds taken in the same order.  Returns (y [B, D], saved)."""
-    D = hq.shape[1]
-    da, dh = dropout_pair(pdrop), dropout_pair(pdrop)
-    pq, pkv = _live_proj(P, D)
-    kv, _ = mm_nt(src2, src2.shape[1], B * Ls, pkv.w, bias=pkv.b)
-    q, _ = mm_nt(hq, D, B, pq.w, bias=pq.b)
-    n = q.shape[1]
-    kv3 = kv.view(B, Ls, 2 * n)
-    o, lse = attn_forward(q.view(B, 1, n), kv3[..., :n], kv3[..., n:], P.heads, mask, dropout=da, rows=(0, Lfull))
-    s, _ = mm_nt(o.view(B, n), n, B, compute_weight(P.w_o), bias=_bdata(P.b_o), residual=hq, dropout=dh, rows=(0, Lfull))
-    y, mean, rstd = ln_fwd_raw(s, P.ln)
-    return y, (hq, src2, q, kv, o, lse, s, mean, rstd, mask, da, dh, Ls, Lfull)
-
-
-def _attn_sub_bwd_live(dy, saved, B, P, need_dsrc=True):
-    """Backward of _attn_sub_fwd_live: (dhq [B, D], dsrc [B Ls, Ds] or None), the gradients of the query rows and of the key /
-    value rows.  Self-attention (token 0 is query and key): (None, dh [B Ls, D]) with both joined in the token-0 rows."""
-    hq, src2, q, kv, o, lse, s, mean, rstd, mask, da, dh, Ls, Lfull = saved
-    D, n = hq.shape[1], q.shape[1]
-    ds, dsd = _post_ln_bwd(dy, s, P.ln, mean, rstd, dh, rows=(0, Lfull))
-    mm_wgrad(dsd, o.view(B, n), n, P.w_o, P.b_o)
-    dctx = mm_dgrad(dsd, P.w_o)
-    dq, dkv = torch.empty_like(q), torch.empty_like(kv)
-    kv3, dkv3 = kv.view(B, Ls, 2 * n), dkv.view(B, Ls, 2 * n)
-    attn_backward(q.view(B, 1, n), kv3[..., :n], kv3[..., n:], o, lse, dctx.view(o.shape), dq.view(B, 1, n), dkv3[..., :n],
-                  dkv3[..., n:], P.heads, mask, dropout=da, rows=(0, Lfull))
-    pq, pkv = _live_proj(P, D)
-    pq.wgrad(dq, hq, D)
-    pkv.wgrad(dkv, src2, src2.shape[1])
-    for prm in {id(p): p for p in (pq.w_param, pq.b_param, pkv.w_param, pkv.b_param)}.values():
-        if prm.requires_grad:
-            _done(prm)
-    if pq.w_param is pkv.w_param:
-        # token 0's gradient is the full layer's product for that row, d(q | k | v) . W_qkv + ds in ONE accumulation and one
-        # rounding (the same bits as the full call's row, so the layers below see the same gradient): B packed rows
-        dh = pkv.dgrad(dkv)
-        dqkv0 = torch.cat([dq, dkv3[:, 0]], dim=1)
-        dh.view(B, Ls, D)[:, 0] = mm_dgrad(dqkv0, pq.w_param, residual=ds)
-        return None, dh
-    dhq = pq.dgrad(dq, residual=ds)   # + the residual-branch gradient, in the epilogue
-    return dhq, (pkv.dgrad(dkv) if need_dsrc else None)
+class BlockOpts(NamedTuple):
+    """The per-call options of the fused block functions, built by the module at every call and passed beside `P` (which holds
+    parameters only).  pdrop: dropout probability of this call (0 in eval mode).  cls_only: BertCrossLayerFn's live-row form.
+    fused_cross / need_bwd / want_probs: see _attn_sub_fwd."""
+    pdrop: float = 0.0
+    cls_only: bool = False
+    fused_cross: bool = False
+    want_probs: bool = False
+    need_bwd: bool = True
 
 
 class BertCrossLayerFn(Function):
-    """BertCrossLayer.forward (bert_model.py:457-498): self-attn -> cross-attn -> FFN as one node."""
+    """BertCrossLayer.forward (bert_model.py:457-498): self-attn -> cross-attn -> FFN as one node.
+    opts.cls_only, the live-row form: only token 0 of the output is read (CLS heads).  K | V of both attentions for all rows,
+    every other product on the B token-0 rows; the dropout sites draw the full call's seeds and masks.  Returns [B, 1, D]."""
 
     @staticmethod
-    def forward(ctx, h, other, mask_self, mask_other, P, *anchors):
+    def forward(ctx, h, other, mask_self, mask_other, P, opts, *anchors):
         B, L, D = h.shape
         Lo = other.shape[1]
         h2 = h.contiguous().view(B * L, D)
         other2 = other.contiguous().view(B * Lo, other.shape[2])
-        pd = getattr(P, "pdrop", 0.0)
-        ctx.live = bool(getattr(P, "cls_only", False))
-        if ctx.live:
-            # live rows = token 0: only that row of the output is read (CLS heads).  K | V of both attentions for all rows, every
-            # other product on the B token-0 rows; the dropout sites draw the full call's seeds and masks.  Returns [B, 1, D].
-            hq = h2.view(B, L, D)[:, 0].contiguous()
-            a, s1 = _attn_sub_fwd_live(hq, h2, B, L, L, mask_self, P.attn, pd)
-            c, s2 = _attn_sub_fwd_live(a, other2, B, Lo, L, mask_other, P.cross, pd)
-            y, s3 = _ffn_sub_fwd(c, P.ffn, pd, rows=(0, L))
-            ctx.saved = (s1, s2, s3)
-            ctx.P, ctx.dims, ctx.n_anchor = P, (B, L, Lo, D), len(anchors)
-            ctx.need_other = other.requires_grad
-            return y.view(B, 1, D)
-        a, s1 = _attn_sub_fwd(h2, B, L, None, L, mask_self, P.attn, pd)
+        pd, live = opts.pdrop, opts.cls_only
+        q2, kv2 = (h2.view(B, L, D)[:, 0].contiguous(), h2) if live else (h2, None)
+        a, s1 = _attn_sub_fwd(q2, B, L, kv2, L, mask_self, P.attn, pd, live=live)
         # the fused cross-attention sub-block (csrc/xattn.hip) where the shapes are covered: forward-only calls always,
         # training with its fused backward (ops.XATTN_TRAIN)
-        c, s2 = _attn_sub_fwd(a, B, L, other2, Lo, mask_other, P.cross, pd, fused_cross=getattr(P, "fused_cross", False))
-        y, s3 = _ffn_sub_fwd(c, P.ffn, pd)
+        c, s2 = _attn_sub_fwd(a, B, L, other2, Lo, mask_other, P.cross, pd, fused_cross=opts.fused_cross, need_bwd=opts.need_bwd,
+                              want_probs=opts.want_probs, live=live)
+        y, s3 = _ffn_sub_fwd(c, P.ffn, pd, rows=(0, L) if live else None)
         ctx.saved = (s1, s2, s3)
         ctx.P, ctx.dims, ctx.n_anchor = P, (B, L, Lo, D), len(anchors)
         ctx.need_other = other.requires_grad
-        if getattr(P, "want_probs", False):
+        if opts.want_probs:
             # the two attention maps (bert_model.py:346 of the self- and the cross-attention), read-only outputs
             maps = (_attn_sub_probs(s1, B, L, L, P.attn), _attn_sub_probs(s2, B, L, Lo, P.cross))
             ctx.mark_non_differentiable(*maps)
             return (y.view(B, L, D),) + maps
-        return y.view(B, L, D)
+        return y.view(B, -1, D)
 
     @staticmethod
     def backward(ctx, dy, *_maps):   # (the maps, when returned, carry no gradient)
@@ -1351,16 +1282,10 @@ class BertCrossLayerFn(Function):
         s1, s2, s3 = ctx.saved
         ctx.saved = None
         P = ctx.P
-        if ctx.live:
-            dc = _ffn_sub_bwd(dy.contiguous().view(B, D), s3, P.ffn)
-            da, dother = _attn_sub_bwd_live(dc, s2, B, P.cross, need_dsrc=ctx.need_other)
-            _, dh = _attn_sub_bwd_live(da, s1, B, P.attn)
-            return (dh.view(B, L, D), None if dother is None else dother.view(B, Lo, -1), None, None, None) + \
-                   (None,) * ctx.n_anchor
-        dc = _ffn_sub_bwd(dy.contiguous().view(B * L, D), s3, P.ffn)
+        dc = _ffn_sub_bwd(dy.contiguous().view(-1, D), s3, P.ffn)
         da, dother = _attn_sub_bwd(dc, s2, B, L, Lo, P.cross, need_dother=ctx.need_other)
-        dh, _ = _attn_sub_bwd(da, s1, B, L, L, P.attn)
-        return (dh.view(B, L, D), None if dother is None else dother.view(B, Lo, -1), None, None, None) + \
+        dh, _ = _attn_sub_bwd(da, s1, B, L, L, P.attn)   # (live-row form too: all rows of the stream)
+        return (dh.view(B, L, D), None if dother is None else dother.view(B, Lo, -1), None, None, None, None) + \
                (None,) * ctx.n_anchor
 
 
@@ -1368,12 +1293,11 @@ class BertSelfLayerFn(Function):
     """BertSelfLayer == HF RobertaLayer (bert_model.py:506-546; m3ae_module.py:233-234)."""
 
     @staticmethod
-    def forward(ctx, h, mask, P, *anchors):
+    def forward(ctx, h, mask, P, opts, *anchors):
         B, L, D = h.shape
         h2 = h.contiguous().view(B * L, D)
-        pd = getattr(P, "pdrop", 0.0)
-        a, s1 = _attn_sub_fwd(h2, B, L, None, L, mask, P.attn, pd)
-        y, s3 = _ffn_sub_fwd(a, P.ffn, pd)
+        a, s1 = _attn_sub_fwd(h2, B, L, None, L, mask, P.attn, opts.pdrop)
+        y, s3 = _ffn_sub_fwd(a, P.ffn, opts.pdrop)
         ctx.saved = (s1, s3)
         ctx.P, ctx.dims, ctx.n_anchor = P, (B, L, D), len(anchors)
         return y.view(B, L, D)
@@ -1385,7 +1309,7 @@ class BertSelfLayerFn(Function):
         ctx.saved = None
         da = _ffn_sub_bwd(dy.contiguous().view(B * L, D), s3, ctx.P.ffn)
         dh, _ = _attn_sub_bwd(da, s1, B, L, L, ctx.P.attn)
-        return (dh.view(B, L, D), None, None) + (None,) * ctx.n_anchor
+        return (dh.view(B, L, D), None, None, None) + (None,) * ctx.n_anchor
 
 
 class ClipBlockFn(Function):
@@ -1404,7 +1328,7 @@ class ClipBlockFn(Function):
         x2 = x.contiguous().view(M, D)
         lo = compute_weight(P.w_qkv).dtype   # the GEMM operands' dtype; x2.dtype is the stream's
         h1, m1, r1 = ln_fwd_raw(x2, P.ln1, out_dtype=lo)
-        o, lse, proj = _attn_core_fwd(h1, B, P)
+        o, lse, proj = _attn_core_fwd(h1, h1, B, P)
         xa, _ = mm_nt(o.view(M, D), D, M, compute_weight(P.w_o), bias=_bdata(P.b_o), residual=x2, out_dtype=x2.dtype)
         h2, m2, r2 = ln_fwd_raw(xa, P.ln2, out_dtype=lo)
         y, u, g = _ffn_core_fwd(h2, P, ACT_QUICKGELU, xa)
@@ -1428,7 +1352,7 @@ class ClipBlockFn(Function):
             dxa_s = dxa = ln_bwd_raw(dh2, xa, P.ln2, m2, r2, dx_add=dy2)  # + residual branch, fused into LN backward
         mm_wgrad(dxa, o.view(M, D), D, P.w_o, P.b_o)
         dctx = mm_dgrad(dxa, P.w_o)
-        dh1, _ = _attn_core_bwd(dctx, h1, None, proj, o, lse, B, P)
+        dh1, _ = _attn_core_bwd(dctx, h1, h1, proj, o, lse, B, P)
         dx = ln_bwd_raw(dh1, x2, P.ln1, m1, r1, dx_add=dxa_s)
         return (dx.view(B, L, D), None) + (None,) * ctx.n_anchor
 
@@ -1454,10 +1378,11 @@ def t5_attn_fwd(h2, B, P, bias, causal, pdrop=0.0, src2=None, kv=None):
     projected keys / values computed earlier ([B Ls, 2 inner]; generation re-uses them every step).  Returns (y, saved)."""
     da, dh = dropout_pair(pdrop), dropout_pair(pdrop)
     n, _, rstd = ln_fwd_raw(h2, P.ln, rms=True)
-    o, lse, proj = _attn_core_fwd(n, B, P, src2=src2, kv=kv, pos_bias=bias, scale=1.0, causal=causal, dropout=da)
+    xkv = n if (src2 is None and kv is None) else src2   # self-attention reads its own normalised rows
+    o, lse, proj = _attn_core_fwd(n, xkv, B, P, kv=kv, pos_bias=bias, scale=1.0, causal=causal, dropout=da)
     M, inner = h2.shape[0], o.shape[2]
     y, _ = mm_nt(o.view(M, inner), inner, M, compute_weight(P.w_o), residual=h2, dropout=dh)
-    return y, (h2, rstd, n, proj, o, lse, src2, da, dh)
+    return y, (h2, rstd, n, proj, o, lse, xkv, da, dh)
 
 
 def t5_self_attn_step(h2, B, P, bias_row, cache, t, pdrop=0.0):
@@ -1478,13 +1403,13 @@ def t5_self_attn_step(h2, B, P, bias_row, cache, t, pdrop=0.0):
 
 
 def _t5_attn_bwd(dy, saved, B, P, bias, causal, dbias, need_dh=True, need_dsrc=True):
-    h2, rstd, n, proj, o, lse, src2, da, dh_drop = saved
+    h2, rstd, n, proj, o, lse, xkv, da, dh_drop = saved
     need_dh = need_dh or P.ln.weight.requires_grad  # the RMSNorm scale gradient comes out of the same kernel
     M, inner = h2.shape[0], o.shape[2]
     dyd = _drop_raw(dy, dh_drop)  # gradient of the (dropped) sub-layer output; the residual branch keeps dy itself
     mm_wgrad(dyd, o.view(M, inner), inner, P.w_o)
     dctx = mm_dgrad(dyd, P.w_o)
-    dn, dsrc = _attn_core_bwd(dctx, n, src2, proj, o, lse, B, P, pos_bias=bias, scale=1.0, causal=causal, dropout=da,
+    dn, dsrc = _attn_core_bwd(dctx, n, xkv, proj, o, lse, B, P, pos_bias=bias, scale=1.0, causal=causal, dropout=da,
                               d_pos_bias=dbias, need_dx=need_dh, need_dsrc=need_dsrc)
     dh = ln_bwd_raw(dn, h2, P.ln, None, rstd, dx_add=dy, rms=True) if need_dh else None
     return dh, dsrc
@@ -1506,11 +1431,11 @@ def _t5_ff_bwd(dy, saved, P):
 
 class T5EncBlockFn(Function):
     @staticmethod
-    def forward(ctx, h, pos_bias, P, *anchors):
+    def forward(ctx, h, pos_bias, P, opts, *anchors):
         B, L, D = h.shape
         h2 = h.contiguous().view(B * L, D)
         bias = pos_bias.detach() if pos_bias is not None else None
-        pd = getattr(P, "pdrop", 0.0)
+        pd = opts.pdrop
         a, s1 = t5_attn_fwd(h2, B, P.attn, bias, False, pd)
         y, s2 = t5_ff_fwd(a, P.ffn, pd)
         ctx.saved = (s1, s2, bias)
@@ -1527,18 +1452,18 @@ class T5EncBlockFn(Function):
         dbias = torch.zeros_like(bias) if ctx.need_bias else None
         da = _t5_ff_bwd(dy.contiguous().view(B * L, D), s2, ctx.P.ffn)
         dh, _ = _t5_attn_bwd(da, s1, B, ctx.P.attn, bias, False, dbias, need_dh=ctx.need_h)
-        return (None if dh is None else dh.view(B, L, D), dbias, None) + (None,) * ctx.n_anchor
+        return (None if dh is None else dh.view(B, L, D), dbias, None, None) + (None,) * ctx.n_anchor
 
 
 class T5DecBlockFn(Function):
     @staticmethod
-    def forward(ctx, h, enc, pos_bias, P, *anchors):
+    def forward(ctx, h, enc, pos_bias, P, opts, *anchors):
         B, T, D = h.shape
         Ls = enc.shape[1]
         h2 = h.contiguous().view(B * T, D)
         enc2 = enc.contiguous().view(B * Ls, enc.shape[2])
         bias = pos_bias.detach() if pos_bias is not None else None
-        pd = getattr(P, "pdrop", 0.0)
+        pd = opts.pdrop
         a, s1 = t5_attn_fwd(h2, B, P.attn, bias, True, pd)
         c, s2 = t5_attn_fwd(a, B, P.cross, None, False, pd, src2=enc2)
         y, s3 = t5_ff_fwd(c, P.ffn, pd)
@@ -1559,7 +1484,7 @@ class T5DecBlockFn(Function):
         da, denc = _t5_attn_bwd(dc, s2, B, P.cross, None, False, None, need_dsrc=ctx.need_enc)
         dh, _ = _t5_attn_bwd(da, s1, B, P.attn, bias, True, dbias, need_dh=ctx.need_h)
         return (None if dh is None else dh.view(B, T, D), None if denc is None else denc.view(B, Ls, -1), dbias,
-                None) + (None,) * ctx.n_anchor
+                None, None) + (None,) * ctx.n_anchor
 
 
 class EmbedRowsFn(Function):

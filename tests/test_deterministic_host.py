@@ -119,6 +119,29 @@ def test_model_config_switches_the_mode_on():
         ops.set_deterministic(False)
 
 
+def test_layernorm_backward_with_a_row_map_is_refused_in_the_mode_before_the_library(monkeypatch):
+    """The LayerNorm backward under a dropout row map (the live-row form) has no ordered entry point: with the mode on,
+    ops.ln_bwd_raw raises DeterministicError where it picks the entry point -- before any library call and before any pointer is
+    taken (CPU tensors; the library handle is a stub that fails on every attribute)."""
+    import torch
+
+    class NoLibrary:
+        def __getattr__(self, name):
+            raise AssertionError(f"the library was reached: {name}")
+
+    monkeypatch.setattr(_lib, "_lib", NoLibrary())
+    monkeypatch.setattr(_lib, "lib", lambda: _lib._lib)
+    ln = torch.nn.LayerNorm(64)
+    x, dy = torch.randn(2, 64), torch.randn(2, 64)
+    mean, rstd = torch.zeros(2), torch.ones(2)
+    with ops.deterministic_mode():
+        with pytest.raises(ops.DeterministicError, match="row map"):
+            ops.ln_bwd_raw(dy, x, ln, mean, rstd, drop=(0.1, 7), rows=(0, 33))
+    assert ln.weight.grad is None and ln.bias.grad is None     # refused before a gradient buffer was made
+    with pytest.raises(AssertionError, match="the library was reached"):   # mode off: the call goes on to the library (the stub)
+        ops.ln_bwd_raw(dy, x, ln, mean, rstd, drop=(0.1, 7), rows=(0, 33))
+
+
 def _wgrad_desc(N1, N2, rows, flags=0):
     """dW[N1, N2] += dY[rows, N1]^T X[rows, N2], bf16 operands, fp32 accumulate: mm_wgrad's descriptor (no pointers)."""
     d = _lib.GemmDesc()

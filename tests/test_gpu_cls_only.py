@@ -49,7 +49,8 @@ def test_block_live_rows_equal_row_0_of_the_full_layer(L, Lo, pdrop, composition
     the text side (32 masked queries over 33 keys).  Output: bit equal to row 0.  Backward with dy zero outside row 0: dother is
     one product (d(k | v) . W_kv) on both sides; so are the rows >= 1 of dh (the full call's packed d(q | k | v) . W_qkv has
     exact zeros in its q part there) and row 0 of dh (the live form runs the packed product on that row): all bit equal.
-    Parameter gradients: the atomics-order tolerance."""
+    Parameter gradients: the atomics-order tolerance, on the flat gradient and on each member of the packed self-attention
+    projection (a slice written at a wrong offset moves a whole member)."""
     from m3ae_amd.modules.bert_model import BertCrossLayer
     torch.manual_seed(11)
     layer = BertCrossLayer(D, H, 4 * D, drop_rate=pdrop)
@@ -91,6 +92,14 @@ def test_block_live_rows_equal_row_0_of_the_full_layer(L, Lo, pdrop, composition
     assert rel(gl, gf) <= ATOMICS_REL, rel(gl, gf)
     for n in pf:   # no parameter lost its gradient: the Q and the K | V slice of the packed weight among them
         assert (pl[n].abs().max() > 0) == (pf[n].abs().max() > 0), n
+    # the members of the packed Q | K | V weight and bias of the self-attention, which the live form writes slice by slice (Q
+    # rows, then K | V rows) and the full layer in one product: each member on its own, to the same tolerance (key.bias is zero
+    # in exact arithmetic -- softmax is invariant to it -- and rounding noise on both sides: not a relative comparison)
+    packed = [n for n in pf if n.startswith("attention.self.") and n != "attention.self.key.bias"]
+    assert len(packed) == 5, packed
+    for n in packed:
+        print(f"{n}: rel {rel(pl[n], pf[n]):.3e}")
+        assert rel(pl[n], pf[n]) <= ATOMICS_REL, (n, rel(pl[n], pf[n]))
 
 
 def _tiny(loss_names=None):

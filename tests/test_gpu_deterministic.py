@@ -488,7 +488,10 @@ def test_ops_without_an_ordered_form_raise_by_name():
 def test_fused_cross_attention_backward_raises_when_the_mode_comes_on_after_its_forward(monkeypatch):
     """With the mode on, training calls of the cross-attention sub-block take the composition (the bit-equal steps above would
     raise otherwise).  A fused forward taken with the mode OFF cannot be differentiated with the mode ON: m3ae_xattn_bwd sums its
-    weight gradients with fp32 atomics, so the backward raises instead of running it."""
+    weight gradients with fp32 atomics, so the backward raises instead of running it.  (Full last fusion pair, ops.CLS_ONLY off:
+    the fused backward is then the first op of the backward without an ordered form.)  The same holds for the live-row form of
+    the last pair: its LayerNorm backward under a dropout row map has no ordered form either, and raises where it used to run
+    the atomic kernel."""
     cfg = finetune_vqa_rad_config(compute_dtype="bf16")
     b = to_dev(synth.synthetic_batch(2, text_len=32, image_size=384, rank=0))
     m = build(cfg, torch.bfloat16)
@@ -498,6 +501,7 @@ def test_fused_cross_attention_backward_raises_when_the_mode_comes_on_after_its_
     calls = []
     real = ops.xattn_fwd
     monkeypatch.setattr(ops, "xattn_fwd", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+    monkeypatch.setattr(ops, "CLS_ONLY", False)
     loss = m.training_step(b)
     assert len(calls) > 0                       # mode off: the fused training path (the suite lowers its batch threshold to 0)
     ops.set_deterministic(True)
@@ -509,6 +513,14 @@ def test_fused_cross_attention_backward_raises_when_the_mode_comes_on_after_its_
     m.training_step(b).backward()               # mode on from the forward on: the composition, no fused call, no error
     torch.cuda.synchronize()
     assert len(calls) == n
+    ops.set_deterministic(False)
+    monkeypatch.setattr(ops, "CLS_ONLY", True)
+    m.store.zero_grad()
+    loss = m.training_step(b)                   # mode off: the last pair in its live-row form
+    ops.set_deterministic(True)
+    with pytest.raises(ops.DeterministicError, match="row map"):
+        loss.backward()
+    torch.cuda.synchronize()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -263,13 +263,18 @@ def test_fused_cross_attention_backward_matches_the_composition(stream, I, pdrop
         assert rel(gf[n], gu[n]) < tol, (n, rel(gf[n], gu[n]))
 
 
-def test_fused_training_path_batch_rule():
+def test_fused_training_path_batch_rule(monkeypatch):
     """Training takes the fused sub-block from ops.XATTN_TRAIN_MIN_BATCH samples per call on (default 96: measured slower than
-    the composition at 32 / 64, faster at 128 / 256, profiles/r02_xattn_batch_rule.log); forward-only calls always take it."""
+    the composition at 32 / 64, faster at 128 / 256, profiles/r02_xattn_batch_rule.log); forward-only calls always take it.
+    Read off the options the layer hands ops.BertCrossLayerFn with each call."""
     from m3ae_amd.modules.bert_model import BertCrossLayer
     layer = BertCrossLayer(D, H, 4 * D, drop_rate=0.0)
     cfg = dict(learning_rate=1e-3, weight_decay=0.01, lr_multiplier_head=1, lr_multiplier_multi_modal=1)
     ParamStore(layer, cfg, "cuda", torch.bfloat16, weight_units=layer.weight_units)
+    seen = []
+    real = ops.BertCrossLayerFn.apply
+    monkeypatch.setattr(ops.BertCrossLayerFn, "apply",
+                        lambda *a: (seen.append([o for o in a if isinstance(o, ops.BlockOpts)]), real(*a))[1])
     old = ops.XATTN_TRAIN_MIN_BATCH
     try:
         ops.XATTN_TRAIN_MIN_BATCH = 96
@@ -277,10 +282,13 @@ def test_fused_training_path_batch_rule():
             xt = torch.randn(B, 32, D, device="cuda").to(torch.bfloat16).requires_grad_(True)
             xi = torch.randn(B, 145, D, device="cuda").to(torch.bfloat16)
             layer(xt, xi, None, None)
-            assert layer._bp.fused_cross is want, (B, layer._bp.fused_cross)
+            (opts,) = seen.pop()
+            assert opts.fused_cross is want, (B, opts.fused_cross)
             with torch.no_grad():
                 layer(xt, xi, None, None)
-            assert layer._bp.fused_cross is True
+            (opts,) = seen.pop()
+            assert opts.fused_cross is True
+        assert not seen
     finally:
         ops.XATTN_TRAIN_MIN_BATCH = old
 

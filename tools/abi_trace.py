@@ -3,7 +3,10 @@ that print the same digests drive the library identically (same entry points, sa
    python tools/abi_trace.py [--pkg DIR] [--out FILE] [--only SUBSTR]
 Recorded per call: the entry point, every integer / float argument, null or set for every pointer, and for a descriptor passed
 by reference each of its fields the same way.  Addresses are never recorded.  --pkg DIR: import m3ae_amd from DIR (the
-`mm-vqa-healthcare_amd` directory of another checkout); --out FILE: the full trace, for `diff`."""
+`mm-vqa-healthcare_amd` directory of another checkout); --out FILE: the full trace, for `diff`.
+Every C entry point the Python package chooses among by call options should appear in at least one workload: the row-map forms
+(live-row CLS steps with and without dropout), the ordered forms (deterministic=True), the mixed-dtype LayerNorms (fp32 CLIP
+residual stream) and the op-level composition (forward_unfused)."""
 import argparse
 import ctypes as C
 import hashlib
@@ -83,13 +86,35 @@ def m3ae(mode, **over):
     return m.finalize("cuda", mode)
 
 
-def cls_train(mode, xattn):
+def cls_train(mode, xattn, drop_rate=0.1, **over):
+    """A CLS-head training step: the last fusion pair runs its live-row form (ops.CLS_ONLY) unless `deterministic`."""
     ops.XATTN, ops.XATTN_TRAIN_MIN_BATCH = xattn, 0
-    m = m3ae(mode, drop_rate=0.1, num_top_layer=2, **WIDE)
-    m.train()
-    m.store.zero_grad()
-    m.training_step(batch()).backward()
-    m.store.adamw_step(max_steps=100, lr_factor=1.0)
+    try:
+        m = m3ae(mode, drop_rate=drop_rate, num_top_layer=2, **WIDE, **over)   # (deterministic=True switches the mode on)
+        m.train()
+        m.store.zero_grad()
+        m.training_step(batch()).backward()
+        m.store.adamw_step(max_steps=100, lr_factor=1.0)
+    finally:
+        ops.set_deterministic(False)
+
+
+def unfused_layers(mode):
+    """One training step through the op-level composition of a fusion layer and of a text layer (forward_unfused: one autograd
+    node per kernel group, LayerNorm through ops.layer_norm)."""
+    from m3ae_amd.modules.bert_model import BertCrossLayer, BertSelfLayer
+    from m3ae_amd.param_store import ParamStore
+    dtype = torch.bfloat16 if mode == "bf16" else torch.float32
+    cfg = dict(learning_rate=1e-3, weight_decay=0.01, lr_multiplier_head=1, lr_multiplier_multi_modal=1)
+    with ops.f32x3_mode(mode == "fp32x3"):
+        for layer, cross in ((BertCrossLayer(768, 12, 3072, drop_rate=0.1), True), (BertSelfLayer(768, 12, 3072, drop_rate=0.1), False)):
+            ParamStore(layer, cfg, "cuda", dtype, weight_units=layer.weight_units)
+            layer.train()
+            h = torch.randn(2, 33, 768, device="cuda").to(dtype).requires_grad_(True)
+            e = torch.randn(2, 32, 768, device="cuda").to(dtype).requires_grad_(True)
+            mask = torch.zeros(2, 32, device="cuda")
+            y = layer.forward_unfused(h, e, None, mask) if cross else layer.forward_unfused(h)
+            y.backward(torch.ones_like(y))
 
 
 def cls_eval(mode, attns, xattn):
@@ -164,6 +189,10 @@ XATTN = ("auto", "always", "off")
 WORKLOADS = [("cls_train_xattn_" + x, lambda mode, x=x: cls_train(mode, x)) for x in XATTN] + [
     ("cls_eval_xattn_" + x, lambda mode, x=x: cls_eval(mode, False, x)) for x in XATTN] + [
     ("cls_eval_attention_maps_xattn_" + x, lambda mode, x=x: cls_eval(mode, True, x)) for x in XATTN] + [
+    ("cls_train_live_no_dropout", lambda mode: cls_train(mode, "off", drop_rate=0.0)),
+    ("cls_train_deterministic", lambda mode: cls_train(mode, "auto", deterministic=True)),
+    ("cls_train_clip_fp32_residual", lambda mode: cls_train(mode, "auto", clip_residual_dtype="fp32")),
+    ("unfused_layers", unfused_layers),
     ("pretrain", pretrain),
     ("t5_train", lambda mode: t5_train(mode, 1, 1)),
     ("t5_train_position_bias", lambda mode: t5_train(mode, 4, 4)),     # every block trainable, the bias table with them
