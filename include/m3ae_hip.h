@@ -410,6 +410,28 @@ int m3ae_image_resample_u8(const uint8_t* src, int64_t src_bytes, const int64_t*
  * Call it in front of m3ae_image_resample_u8 on the same stream.  Returns as m3ae_image_resample_u8: M3AE_ERR_ARG for a null
  * pointer or a non-positive B / size / tab_ints, M3AE_ERR_UNSUPPORTED for B > 65535 or size > 4096. */
 int m3ae_image_resample_tables(const int64_t* plan, int64_t B, int64_t size, int32_t* tab, int64_t tab_ints, void* stream);
+/* RandAugment(2, 9) on the source bytes of a device image transform batch (csrc/randaug.hip; transforms/randaug.py:164-272 of the
+ * reference in front of the CLIP transform, transforms/transform.py:80-91): two operations per image out of 14, Pillow's
+ * arithmetic restated so that the bytes are Pillow's (m3ae_amd/randaug.py holds the numpy model).  Call it in front of
+ * m3ae_image_resample_tables / m3ae_image_resample_u8 on the same stream.
+ *   src      the pack's source bytes (every image RGB interleaved, rows packed, at a 16-byte aligned offset); augmented in place
+ *   scratch  a second buffer of buf_bytes bytes: stage 0 reads src and writes scratch, stage 1 reads scratch and writes src
+ *   plan     int64 [B][24] per image: 0 byte offset, 1 w (<= 8192), 2 h (<= 16384), 3 zero, then per stage s at 4 + 10 s:
+ *            operation (0 identity, 1 AutoContrast, 2 Equalize, 3 Rotate, 4 Posterize, 5 Solarize, 6 SolarizeAdd, 7 Color,
+ *            8 Contrast, 9 Brightness, 10 Sharpness, 11 ShearX, 12 ShearY, 13 TranslateXabs, 14 TranslateYabs), the sign of a geometric
+ *            operation's value (+1 / -1), a0 .. a5 = the 16.16 fixed-point coefficients of Pillow's affine_fixed for a geometric
+ *            operation (source pixel of output (x, y) = ((a2 + y a1 + x a0) >> 16, (a5 + y a4 + x a3) >> 16); |a| < 2^40), two zeros.
+ *            A record with both operations 0 is passed over; a record that does not lie inside buf_bytes, or names an unknown
+ *            operation, is left unwritten whole.
+ *   workspace  m3ae_image_randaug_workspace_bytes(B) bytes, 4-byte aligned: uint32 histograms [2][B][4][256] (R, G, B, L of the
+ *            input of each stage, for the images whose operation reads one), then the uint8 tables [B][3][256] of the point operations
+ *   flags    bit s: stage s has an operation that reads a histogram (1, 2, 8); bit 2 + s: stage s has a point operation
+ *            (1, 2, 4, 5, 6, 8, 9).  A stage whose bit is clear skips that launch.
+ * Returns M3AE_ERR_ARG (null pointer, src == scratch, non-positive B / buf_bytes, unknown flag bits), M3AE_ERR_UNSUPPORTED
+ * (B > 65535), M3AE_ERR_ALIGN, M3AE_ERR_WORKSPACE. */
+int64_t m3ae_image_randaug_workspace_bytes(int64_t B);
+int m3ae_image_randaug_u8(uint8_t* src, uint8_t* scratch, int64_t buf_bytes, const int64_t* plan, int64_t B, void* workspace,
+                          int64_t workspace_bytes, int flags, void* stream);
 int m3ae_vit_tokens_fwd(const void* patch, const float* cls, const float* pos, void* out, int64_t B, int64_t G,
                         int64_t D, int dtype, void* stream);
 int m3ae_vit_tokens_bwd(const void* d_out, void* d_patch, float* d_cls, float* d_pos, int64_t B, int64_t G,

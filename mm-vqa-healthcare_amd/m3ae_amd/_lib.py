@@ -124,6 +124,9 @@ _SIGS = {
     "m3ae_image_resample_workspace_bytes": (i64, [i64, i64]),
     "m3ae_image_resample_u8": (C.c_int, [vp, i64, vp, vp, i64, i64, i64, vp, i64, vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float), vp]),
     "m3ae_image_resample_tables": (C.c_int, [vp, i64, i64, vp, i64, vp]),
+    # RandAugment(2, 9) on the source bytes of the device image transform (ABI 4, additive)
+    "m3ae_image_randaug_workspace_bytes": (i64, [i64]),
+    "m3ae_image_randaug_u8": (C.c_int, [vp, vp, i64, vp, i64, vp, i64, C.c_int, vp]),
     # dropout row map (ABI 4, additive): (row_base, row_step) before the stream
     "m3ae_gemm_rows": (C.c_int, [C.POINTER(GemmDesc), i64, i64, vp]),
     "m3ae_attn_fwd_rows": (C.c_int, [C.POINTER(AttnDesc), i64, i64, vp]),

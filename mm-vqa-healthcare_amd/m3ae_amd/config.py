@@ -64,6 +64,11 @@ DEFAULTS = dict(
     # (RandomResizedCrop(size, scale=(0.9, 1.0), BICUBIC) in front of the CLIP tail, transform.py:70-77: one crop box per image
     # and epoch, resample.random_resized_crop_box).  Every other split runs "clip" (base_dataset.py:39-41 strips the suffix).
     train_transform_keys=["clip"], val_transform_keys=["clip"],
+    # RandAugment(2, 9) (reference transforms/randaug.py) on every image a train split loads, in front of whichever tail
+    # train_transform_keys names; with "clip" it is the reference's `clip_randaug` (transform.py:80-91).  Under image_transform
+    # "host" Pillow runs the operations on the loader threads, under "device" csrc/randaug.hip does, on the uploaded source bytes:
+    # equal batches (m3ae_amd/randaug.py).  Val / test never augment.  Not available with graph.GraphedStep.
+    randaug=False,
 )
 
 NAMED = {
@@ -124,7 +129,8 @@ VAL_TRANSFORM_KEYS = ("clip",)
 def transform_keys(cfg):
     """The validated (train, val) transform names of a config dict (defaults "clip").  Each key is a list of one name, as on the
     reference's command line; a split other than train drops the "_resizedcrop" suffix first (base_dataset.py:39-41).  The
-    reference's other names ("clip_randaug", "imagenet*": RandAugment) are not available."""
+    reference's other names are not available: "clip_randaug" is `randaug=True` next to "clip" here, the "imagenet*" keys stay out
+    of scope."""
     out = []
     for name, allowed, strip in (("train_transform_keys", TRAIN_TRANSFORM_KEYS, False), ("val_transform_keys", VAL_TRANSFORM_KEYS, True)):
         v = cfg.get(name, ["clip"])
@@ -136,11 +142,20 @@ def transform_keys(cfg):
     return tuple(out)
 
 
+def randaug_enabled(cfg):
+    """The validated `randaug` of a config dict (default False).  (n, m) is the reference's (2, 9); no other value is offered."""
+    v = cfg.get("randaug", False)
+    if not isinstance(v, bool):
+        raise ValueError(f"randaug must be True or False, got {v!r}")
+    return v
+
+
 def resolve_arch(cfg):
     """Fill vit_width/vit_layers/text_* from the `vit` / `tokenizer` names unless given explicitly."""
     cfg = dict(cfg)
     clip_residual_dtype(cfg)
     transform_keys(cfg)
+    randaug_enabled(cfg)
     vit = _ARCH_VIT.get(cfg["vit"], _ARCH_VIT["ViT-B/16"])
     for k, v in vit.items():
         cfg.setdefault(k, v)

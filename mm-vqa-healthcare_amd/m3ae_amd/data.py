@@ -42,6 +42,14 @@ box's coefficient tables on the GPU (`m3ae_image_resample_tables`).  The box is 
 global sample index, slot) -- slot 0 the sample's image, 1 + i its i-th false image; the reference, too, draws per loaded image --
 or, under `image_dedup`, by (seed, epoch, image key): one box per distinct image and epoch (the datasets' `box_key`).  No global
 generator is read, so epoch e gives the same batches whenever it runs.  `val_batches` and the val / test sets never crop.
+
+`randaug=True` (off by default; with the `clip` tail the reference's `clip_randaug`, transforms/transform.py:80-91): every image a
+TRAIN split loads under `train_batches(epoch)` is converted to RGB and run through `RandAugment(2, 9)` (m3ae_amd/randaug.py) in
+front of whichever tail `train_transform_keys` names.  The two operations and their signs are drawn by the crop box's rule from a
+generator of their own (randaug.aug_rng on the same key), so the box of `clip_resizedcrop` is the one it would be without them.
+"host": Pillow runs the operations on the loader threads.  "device": the pack carries an augment plan and csrc/randaug.hip runs the
+operations on the uploaded source bytes in front of the resample -- the same bytes, so the batches are equal.  An image beyond the
+staging caps is augmented and transformed on the host and joins with an identity record.
 """
 import ctypes as C
 import io
@@ -54,7 +62,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import torch
 
-from . import _lib, resample
+from . import _lib, randaug, resample
 from .synth import CLIP_MEAN, CLIP_STD
 
 
@@ -104,22 +112,30 @@ class TransformStats(dict):
             self.decodes += 1
 
 
-def load_image_u8(raw, size, image_transform="host", stats=None, box_key=None):
+def load_image_u8(raw, size, image_transform="host", stats=None, box_key=None, aug_key=None):
     """Encoded image bytes -> uint8 [size, size, 3] (the finished crop, "host") or the source the device transform resizes
     ("device": uint8 [h, w, 3], or the host-made crop of an image it does not take).
     `box_key` (a train split under "clip_resizedcrop"; a tuple of ints / strings): the image is cropped to the box that key draws
     (resample.box_rng, random_resized_crop_box) and the box resized; the device route then returns (source, box) for
-    `resample.pack_batch(..., boxes=)`."""
+    `resample.pack_batch(..., boxes=)`.
+    `aug_key` (a train split under `randaug`): the image is converted to RGB and run through the two operations that key draws
+    (randaug.aug_rng, randaug.draw) first; the device route then returns (source, box or None, operations or None) for
+    `resample.pack_batch(..., augs=)`."""
     from PIL import Image
     img = Image.open(io.BytesIO(raw))
     if stats is not None:
         stats.count_decode()
     box = None if box_key is None else resample.random_resized_crop_box(*img.size, resample.box_rng(*box_key))
+    ops = None if aug_key is None else randaug.draw(randaug.aug_rng(*aug_key))
     if image_transform != "device":
+        if ops is not None:
+            img = randaug.augment_pil(img, ops)
         return clip_resize_crop(img, size) if box is None else clip_resized_crop(img, size, box)
-    route, *a = resample.prepare(img, size, box)
+    route, *a = resample.prepare(img, size, box, ops)
     if stats is not None:
         stats.count(route)
+    if ops is not None:
+        return tuple(a)
     return a[0] if box is None else tuple(a)
 
 
@@ -229,15 +245,23 @@ class MLMCollator:
 # ------------------------------------------------------------------------------------------------------------
 # dataset
 # ------------------------------------------------------------------------------------------------------------
+def _keyed_load(ds, row, key):
+    """`ds.image_u8(row)` under the key of one loaded image: it draws the crop box of a dataset that crops and, through a generator
+    of their own, the RandAugment operations of a dataset with `randaug`."""
+    kw = {"aug_key": key} if ds.randaug else {}
+    return ds.image_u8(row, key if ds.crop else None, **kw)
+
+
 class ArrowVQADataset:
     """BaseDataset + VQAVQARADDataset for `{data_dir}/vqa_vqa_rad_{split}.arrow` (or any `names`)."""
 
     def __init__(self, data_dir, split, image_size, max_text_len, tokenizer, names=None, image_transform="host", stats=None,
-                 train_transform="clip", seed=0, box_key="sample"):
+                 train_transform="clip", seed=0, box_key="sample", randaug=False):
         import pyarrow as pa
         self.image_transform, self.stats = image_transform, stats
-        # the random resized crop: train split only (base_dataset.py:39-41), and only for a fetch that names its epoch
-        self.augment, self.seed, self.box_key = split == "train" and train_transform == "clip_resizedcrop", seed, box_key
+        # the random resized crop and RandAugment: train split only (base_dataset.py:39-41), and only for a fetch that names its epoch
+        self.crop, self.randaug = split == "train" and train_transform == "clip_resizedcrop", split == "train" and bool(randaug)
+        self.augment, self.seed, self.box_key = self.crop or self.randaug, seed, box_key
         self.names = names or [f"vqa_vqa_rad_{split}"]
         tables = []
         for name in self.names:
@@ -254,8 +278,8 @@ class ArrowVQADataset:
     def __len__(self):
         return len(self.index_mapper)
 
-    def image_u8(self, row, box_key=None):
-        return load_image_u8(self.table["image"][row].as_py(), self.image_size, self.image_transform, self.stats, box_key)
+    def image_u8(self, row, box_key=None, aug_key=None):
+        return load_image_u8(self.table["image"][row].as_py(), self.image_size, self.image_transform, self.stats, box_key, aug_key)
 
     def get(self, index, epoch=None, key_index=None):
         """Sample `index`; with `epoch` (train_batches) on an augmenting dataset its image is cropped to the box of (seed, epoch,
@@ -265,7 +289,7 @@ class ArrowVQADataset:
             return {"image_u8": self.image_u8(key[1]), **sample}
         if self.box_key == "image":
             return {"image_u8": self.image_by_key(key, epoch), **sample}
-        return {"image_u8": self.image_u8(key[1], (self.seed, epoch, index if key_index is None else key_index, 0)), **sample}
+        return {"image_u8": _keyed_load(self, key[1], (self.seed, epoch, index if key_index is None else key_index, 0)), **sample}
 
     def __getitem__(self, index):
         return self.get(index)
@@ -292,7 +316,7 @@ class ArrowVQADataset:
         """The image of an image key; with `epoch` on an augmenting dataset, cropped to that image's box of the epoch."""
         if not self.augment or epoch is None:
             return self.image_u8(key[1])
-        return self.image_u8(key[1], (self.seed, epoch, key))
+        return _keyed_load(self, key[1], (self.seed, epoch, key))
 
 
 class ArrowCaptionDataset:
@@ -304,10 +328,11 @@ class ArrowCaptionDataset:
     reference's draws.  A sample that fails to decode is replaced by a random one (:158-160)."""
 
     def __init__(self, data_dir, name, split, image_size, max_text_len, tokenizer, draw_false_image=0, image_transform="host",
-                 stats=None, train_transform="clip", seed=0, box_key="sample"):
+                 stats=None, train_transform="clip", seed=0, box_key="sample", randaug=False):
         import pyarrow as pa
         self.image_transform, self.stats = image_transform, stats
-        self.augment, self.seed, self.box_key = split == "train" and train_transform == "clip_resizedcrop", seed, box_key
+        self.crop, self.randaug = split == "train" and train_transform == "clip_resizedcrop", split == "train" and bool(randaug)
+        self.augment, self.seed, self.box_key = self.crop or self.randaug, seed, box_key
         assert split in ("train", "val", "test")
         self.names = [f"{name}_{split}"]
         path = os.path.join(data_dir, f"{self.names[0]}.arrow")
@@ -323,8 +348,8 @@ class ArrowCaptionDataset:
     def __len__(self):
         return len(self.index_mapper)
 
-    def image_u8(self, row, box_key=None):
-        return load_image_u8(self.table["image"][row].as_py(), self.image_size, self.image_transform, self.stats, box_key)
+    def image_u8(self, row, box_key=None, aug_key=None):
+        return load_image_u8(self.table["image"][row].as_py(), self.image_size, self.image_transform, self.stats, box_key, aug_key)
 
     def get_suite(self, index, epoch=None, key_index=None):
         """`epoch` (train_batches) on an augmenting dataset: every image loaded is cropped to a box of its own -- (seed, epoch,
@@ -332,10 +357,10 @@ class ArrowCaptionDataset:
         if not self.augment or epoch is None:
             load = lambda row, slot: self.image_u8(row)
         elif self.box_key == "image":
-            load = lambda row, slot: self.image_u8(row, (self.seed, epoch, (self.names[0], row)))
+            load = lambda row, slot: _keyed_load(self, row, (self.seed, epoch, (self.names[0], row)))
         else:
             key = index if key_index is None else key_index
-            load = lambda row, slot: self.image_u8(row, (self.seed, epoch, key, slot))
+            load = lambda row, slot: _keyed_load(self, row, (self.seed, epoch, key, slot))
         while True:
             try:
                 row, ci = self.index_mapper[index]
@@ -390,9 +415,12 @@ def collate_host(samples, pin=True, mlm_collator=None, resample_size=None, pmap=
     B = len(samples)
     S = max(len(s["input_ids"]) for s in samples)
     if resample_size:
-        def stack_list(arrays):   # (source, box) pairs under "clip_resizedcrop"
-            boxes = [a[1] for a in arrays] if isinstance(arrays[0], tuple) else None
-            return resample.pack_batch([a[0] for a in arrays] if boxes else arrays, resample_size, pin=pin, pmap=pmap, boxes=boxes)
+        def stack_list(arrays):   # (source, box) pairs under "clip_resizedcrop", (source, box or None, operations) under randaug
+            if not isinstance(arrays[0], tuple):
+                return resample.pack_batch(arrays, resample_size, pin=pin, pmap=pmap)
+            boxes = None if arrays[0][1] is None else [a[1] for a in arrays]
+            augs = [a[2] for a in arrays] if len(arrays[0]) > 2 else None
+            return resample.pack_batch([a[0] for a in arrays], resample_size, pin=pin, pmap=pmap, boxes=boxes, augs=augs)
     else:
         stack_list = lambda arrays: torch.from_numpy(np.stack(arrays))
     stack = lambda k: stack_list([s[k] for s in samples])
@@ -468,7 +496,7 @@ def _finish_image(u8, cur):
     if isinstance(u8, torch.Tensor):
         u8.record_stream(cur)
         return normalize_on_device(u8)
-    for k in ("src", "plan", "tab"):   # uploaded on the copy stream, read here (a pack with boxes has no uploaded tables)
+    for k in ("src", "plan", "tab", "aug"):   # uploaded on the copy stream, read here (a pack with boxes has no uploaded tables)
         if k in u8:
             u8[k].record_stream(cur)
     return resample.resample_on_device(u8)
@@ -514,11 +542,12 @@ class ArrowDataModule:
         if self.image_dedup and any(loss_names.get(k, 0) > 0 for k in ("mim", "itm")):
             raise ValueError("image_dedup=True cannot be combined with the mim / itm objectives (loss_names): they read the image "
                              "pixels per sample")
-        from .config import transform_keys
+        from .config import randaug_enabled, transform_keys
         self.train_transform = transform_keys(cfg)[0]
-        # one crop box per distinct image and epoch under image_dedup, else one per loaded image (the reference's rule)
+        # one crop box (and one RandAugment draw) per distinct image and epoch under image_dedup, else one per loaded image (the
+        # reference's rule)
         tf = dict(image_transform=self.image_transform, stats=self.transform_stats, train_transform=self.train_transform,
-                  seed=cfg["seed"], box_key="image" if self.image_dedup else "sample")
+                  seed=cfg["seed"], box_key="image" if self.image_dedup else "sample", randaug=randaug_enabled(cfg))
         if any(n in ("roco", "medicat") for n in names):   # the pre-training caption tables (config.py:22,31: draw_false_image = 1)
             mk = lambda split: ConcatDataset([ArrowCaptionDataset(root, n, split, cfg["image_size"], cfg["max_text_len"],
                                                                   self.tokenizer, cfg.get("draw_false_image", 0), **tf)

@@ -33,6 +33,10 @@ class GraphedStep:
         visual = getattr(getattr(core, "vision_encoder", None), "visual", None)
         if visual is not None and visual.stream_dtype(core._dtype) != core._dtype:
             raise ValueError('GraphedStep does not cover clip_residual_dtype="fp32" in bf16 mode: run the step eagerly')
+        if (getattr(getattr(core, "hparams", None), "config", None) or {}).get("randaug"):
+            # like the other per-batch plans of the input pipeline: the augment plan and its launches differ from batch to batch and
+            # run in front of the step, outside anything a replay could cover
+            raise ValueError("GraphedStep does not cover randaug=True: run the step eagerly")
         self.model, self.store, self.batch = model, model.store, batch
         self.max_steps, self.grad_scale = max_steps, grad_scale
         dev = self.store.flat.device

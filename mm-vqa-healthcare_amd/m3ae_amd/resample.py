@@ -192,14 +192,29 @@ def resample_model(rgb, size, t=None):
 # ------------------------------------------------------------------------------------------------------------
 # eligibility
 # ------------------------------------------------------------------------------------------------------------
-def prepare(img, size, box=None):
+def prepare(img, size, box=None, aug=None):
     """PIL image -> ("device", uint8 [h, w, 3] RGB source) if the image is opaque and within the caps, else
     ("fallback", uint8 [size, size, 3]): the finished `clip_resize_crop` of the host path, which the device path then
     carries through identity tables.
     With `box` (left, top, cw, ch; train transform "clip_resizedcrop") the answer has a third element, the box the device
     transform applies to the array: `box` itself next to the whole source, (0, 0, size, size) next to the finished
-    `clip_resized_crop` of the fallback route."""
+    `clip_resized_crop` of the fallback route.
+    With `aug` (the drawn operations of randaug.draw; config key `randaug`) the answer is always (route, array, box or None,
+    operations or None).  The chain starts with convert("RGB") (transform.py:90), so alpha is gone before the resize and every
+    image within the caps is a device source, handed over with its operations; beyond them the host augments (randaug.augment_pil)
+    and transforms, and the operations are None."""
     from .data import clip_resize_crop, clip_resized_crop
+    if aug is not None:
+        from . import randaug
+        img = img.convert("RGB")
+        w, h = img.size
+        if w <= MAX_SOURCE_WIDTH and w * h <= MAX_SOURCE_PIXELS and randaug.eligible(w, h):
+            return "device", np.asarray(img, dtype=np.uint8), box, aug
+        img = randaug.augment_pil(img, aug)
+        if box is not None:
+            return "fallback", clip_resized_crop(img, size, box), (0, 0, size, size), None
+        return "fallback", clip_resize_crop(img, size), None, None
+
     def with_box(route, a, b):
         return (route, a) if box is None else (route, a, b)
 
@@ -223,7 +238,7 @@ def _align16(n):
     return (n + 15) & ~15
 
 
-def pack_batch(sources, size, pin=False, pmap=map, boxes=None):
+def pack_batch(sources, size, pin=False, pmap=map, boxes=None, augs=None):
     """uint8 [h_i, w_i, 3] sources -> the three host tensors the kernels read: `src` (bytes, every image at a 16-byte
     aligned offset, rows packed), `plan` (int64 [B, PLAN_FIELDS]) and `tab` (int32; one set of tables per distinct source
     size), plus `rows`, the number of intermediate rows of the batch (the workspace size).  `pmap`: a `map` that may run the copies into the staging buffer
@@ -231,7 +246,10 @@ def pack_batch(sources, size, pin=False, pmap=map, boxes=None):
     `boxes` (one (left, top, cw, ch) per source; "clip_resizedcrop"): image i is `sources[i][top:top + ch, left:left + cw]`
     resized to size x size.  The plan names the box inside the whole source, images with equal (cw, ch) share a table set and
     PLAN_BUILD marks its first owner; the tables themselves are built on the device, so the pack has `tab_ints` (their length)
-    in place of `tab`."""
+    in place of `tab`.
+    `augs` (per source the drawn operations of randaug.draw, or None for a source the host augmented already; config key
+    `randaug`): the pack also carries `aug`, the augment plan (randaug.augment_plan: int64 [B, AUG_FIELDS]), and `aug_flags`
+    (randaug.stage_flags) -- unless no source has an operation."""
     import torch
     offs, total = [], 0
     for s in sources:
@@ -273,17 +291,24 @@ def pack_batch(sources, size, pin=False, pmap=map, boxes=None):
         flat[so[1]:so[1] + so[0].size] = so[0].reshape(-1)
     list(pmap(put, zip(sources, offs)))
     plan_t = torch.from_numpy(plan)
+    extra = {}
+    if augs is not None and any(augs):
+        from . import randaug
+        aug = randaug.augment_plan([s.shape for s in sources], offs, augs)
+        aug_t = torch.from_numpy(aug)
+        extra = {"aug": aug_t.pin_memory() if use_pin else aug_t, "aug_flags": randaug.stage_flags(aug)}
     if boxes is not None:
-        return {"src": src, "plan": plan_t.pin_memory() if use_pin else plan_t, "tab_ints": tab_len, "rows": rows, "size": int(size)}
+        return {"src": src, "plan": plan_t.pin_memory() if use_pin else plan_t, "tab_ints": tab_len, "rows": rows, "size": int(size),
+                **extra}
     tab_t = torch.from_numpy(np.concatenate(tabs).astype(np.int32))
     if use_pin:
         plan_t, tab_t = plan_t.pin_memory(), tab_t.pin_memory()
-    return {"src": src, "plan": plan_t, "tab": tab_t, "rows": rows, "size": int(size)}
+    return {"src": src, "plan": plan_t, "tab": tab_t, "rows": rows, "size": int(size), **extra}
 
 
 def upload(pack, device):
     """The pack's tensors on `device` (non-blocking: call it under the copy stream)."""
-    return {**pack, **{k: pack[k].to(device, non_blocking=True) for k in ("src", "plan", "tab") if k in pack}}
+    return {**pack, **{k: pack[k].to(device, non_blocking=True) for k in ("src", "plan", "tab", "aug") if k in pack}}
 
 
 def workspace_bytes(rows, size):
@@ -305,11 +330,16 @@ def resample_on_device(dpack, want_u8=False, stream=None):
     """Device pack -> fp32 [B, 3, size, size] (ToTensor + Normalize of the resized crop; bit-equal to
     `normalize_on_device(clip_resize_crop(...))`), and with want_u8 also the uint8 [B, size, size, 3] crop.
     A pack made with boxes has no tables: they are built here, on the same stream, in front of the two passes (a record
-    the table kernel refuses keeps zero tap counts)."""
+    the table kernel refuses keeps zero tap counts).
+    A pack with an augment plan (`aug`; config key `randaug`): the two RandAugment stages run first, on the same stream, and leave
+    the augmented sources where they were (randaug.augment_on_device)."""
     import torch
     from . import _lib
     from .synth import CLIP_MEAN, CLIP_STD
     src, plan, size = dpack["src"], dpack["plan"], dpack["size"]
+    if "aug" in dpack:
+        from . import randaug
+        randaug.augment_on_device(src, dpack["aug"], dpack["aug_flags"], stream)
     tab = dpack.get("tab")
     if tab is None:
         with torch.cuda.stream(stream or torch.cuda.current_stream()):

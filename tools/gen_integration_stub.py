@@ -32,6 +32,7 @@ DET_ENTRIES = ("m3ae_gemm_det_workspace_bytes", "m3ae_gemm_det", "m3ae_det_works
                "m3ae_layernorm_bwd_det", "m3ae_layernorm_bwd_drop_det", "m3ae_roberta_embed_bwd_det", "m3ae_bce_logits_det",
                "m3ae_xent_det", "m3ae_mim_loss_fwd_det")
 IMAGE_ENTRIES = ("m3ae_image_resample_workspace_bytes", "m3ae_image_resample_u8", "m3ae_image_resample_tables")
+RANDAUG_ENTRIES = ("m3ae_image_randaug_workspace_bytes", "m3ae_image_randaug_u8")
 SAMPLES_ENTRIES = ("m3ae_expand_samples", "m3ae_segment_sum_rows")
 MIXED_LN_ENTRIES = ("m3ae_layernorm_fwd_mixed", "m3ae_layernorm_bwd_mixed", "m3ae_layernorm_bwd_mixed_det")
 TILED_ENTRIES = ("m3ae_tile_bf16_batched",)
@@ -71,6 +72,11 @@ def block():
     out.append("")
     out.append("# device image transform (ABI 4, additive): Pillow-exact bicubic resize + centre crop + normalize from the source bytes")
     for name in IMAGE_ENTRIES:
+        res, args = _lib._SIGS[name]
+        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
+    out.append("")
+    out.append("# RandAugment(2, 9) on the source bytes of the device image transform (ABI 4, additive): Pillow-exact, two stages")
+    for name in RANDAUG_ENTRIES:
         res, args = _lib._SIGS[name]
         out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
     out.append("")

@@ -20,6 +20,12 @@ temporary directory, one per source size, then per table:
    `m3ae_image_resample_tables` (the coefficient tables built on the GPU) and the two passes, next to the `clip` figures above;
    nothing is asserted about these.
 
+5. the same for `randaug=True` (RandAugment(2, 9) in front of the `clip` tail, two operations per image and epoch): producer
+   images/s of the host path (Pillow runs the operations on the loader threads) and of the device path (csrc/randaug.hip), and
+   the device time of the two stages of one batch (`m3ae_image_randaug_u8`, every timed call on a fresh copy of the sources)
+   against the bytes they move (per stage every augmented image read and written once, and read once more where the stage takes
+   a histogram).  This leg is also written to `--randaug-out` (profiles/r14_randaug.log); nothing is asserted about it.
+
 A run without a GPU fails; nothing here falls back."""
 import argparse
 import io
@@ -34,11 +40,16 @@ sys.path.insert(0, os.path.join(ROOT, "mm-vqa-healthcare_amd"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
-from m3ae_amd import data, resample  # noqa: E402
-from m3ae_amd.config import finetune_vqa_rad_config  # noqa: E402
+from m3ae_amd import data, randaug, resample  # noqa: E402
+from m3ae_amd.config import compose  # noqa: E402
 
 HBM_ACHIEVABLE = 6.3e12   # MI355X_MICROARCH.md: 8.0 TB/s spec, about 6.3 TB/s measured with a float4 copy
 DISTINCT = 16             # distinct images per table; the rows cycle through them
+
+
+def vqa_rad_config(**over):
+    """The fine-tuning config of run_scripts/finetune_m3ae.sh (config.finetune_vqa_rad_config) at the image size asked for."""
+    return compose("task_finetune_vqa_vqa_rad", "clip16", "text_roberta", **over)
 
 
 def jpeg(side, seed):
@@ -117,10 +128,11 @@ def main():
     ap.add_argument("--sources", default="512,1024")
     ap.add_argument("--iters", type=int, default=7)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07_input_pipeline.log"))
+    ap.add_argument("--randaug-out", default=os.path.join(ROOT, "profiles", "r14_randaug.log"))
     a = ap.parse_args()
     assert torch.cuda.is_available(), "input_pipeline_bench.py needs the GPU"
     from arrow_util import HashTokenizer
-    lines, failed = [], []
+    lines, failed, aug_lines = [], [], []
 
     def say(s=""):
         print(s, flush=True)
@@ -136,7 +148,7 @@ def main():
             say(f"\n## JPEG {side}x{side} sources -> {a.size} ({DISTINCT} distinct images, mean {mean_bytes / 1024:.0f} KiB, {a.batch * a.batches} rows)")
             dms = {}
             for mode in ("host", "device"):
-                cfg = finetune_vqa_rad_config(data_root=root, per_gpu_batchsize=a.batch, num_workers=a.workers, image_size=a.size,
+                cfg = vqa_rad_config(data_root=root, per_gpu_batchsize=a.batch, num_workers=a.workers, image_size=a.size,
                                               image_transform=mode)
                 dms[mode] = data.ArrowDataModule(cfg, 0, 1, dev, tokenizer=HashTokenizer())
             rates = {"host": [], "device": []}
@@ -190,7 +202,7 @@ def main():
             # ---- train transform clip_resizedcrop: a box, and so a table set, per image and epoch
             crop = {}
             for mode in ("host", "device"):
-                cfg = finetune_vqa_rad_config(data_root=root, per_gpu_batchsize=a.batch, num_workers=a.workers, image_size=a.size,
+                cfg = vqa_rad_config(data_root=root, per_gpu_batchsize=a.batch, num_workers=a.workers, image_size=a.size,
                                               image_transform=mode, train_transform_keys=["clip_resizedcrop"])
                 crop[mode] = data.ArrowDataModule(cfg, 0, 1, dev, tokenizer=HashTokenizer())
             rates = {"host": [], "device": []}
@@ -223,10 +235,65 @@ def main():
             say(f"clip_resizedcrop, {a.batch} images: m3ae_image_resample_tables median {t_med:.3f} ms, min {t_min:.3f} ms; the two "
                 f"passes on built tables median {p_med:.3f} ms, min {p_min:.3f} ms (clip: {k_med:.3f} ms); tables + memset + passes as "
                 f"resample_on_device runs them median {b_med:.3f} ms, min {b_min:.3f} ms")
-            del dms, dst, dpack, crop, dbpack, with_tab, tab
+
+            # ---- randaug: two operations per image and epoch in front of the clip tail
+            first_aug_line = len(lines)
+            aug = {}
+            for mode in ("host", "device"):
+                cfg = vqa_rad_config(data_root=root, per_gpu_batchsize=a.batch, num_workers=a.workers, image_size=a.size,
+                                              image_transform=mode, randaug=True)
+                aug[mode] = data.ArrowDataModule(cfg, 0, 1, dev, tokenizer=HashTokenizer())
+            rates = {"host": [], "device": []}
+            for w in range(a.windows + 1):
+                for mode in ("host", "device"):
+                    r = producer_window(aug[mode], epoch=w)
+                    if w > 0:
+                        rates[mode].append(r)
+                    say(f"randaug producer {'warm-up window' if w == 0 else f'window {w}      '} {mode:6s} {r:9.1f} images/s")
+            ah, ad = statistics.median(rates["host"]), statistics.median(rates["device"])
+            say(f"randaug producer throughput, JPEG {side} (median of {a.windows} windows): host {ah:.1f} images/s, device {ad:.1f} "
+                f"images/s, device / host = {ad / ah:.2f}x;  against clip (host {mh:.1f}, device {md:.1f} images/s): host {ah / mh:.2f}x, "
+                f"device {ad / md:.2f}x;  routes of the device path: {dict(aug['device'].transform_stats)}")
+            draws = [randaug.draw(randaug.aug_rng(0, 0, i, 0)) for i in range(a.batch)]
+            t0 = time.perf_counter()
+            apack = resample.pack_batch(srcs, a.size, pin=True, augs=draws)
+            say(f"randaug: packing one batch of {a.batch} with its augment plan {(time.perf_counter() - t0) * 1e3:.1f} ms "
+                f"(clip_resizedcrop, with boxes: {t_pack * 1e3:.1f} ms)")
+            aplan = apack["aug"].numpy()
+            npix = aplan[:, randaug.AUG_W] * aplan[:, randaug.AUG_H]
+            moved, users = 0, []
+            for st in range(2):
+                ops = aplan[:, randaug.AUG_STAGE0 + randaug.AUG_STAGE_FIELDS * st]
+                moved += int((3 * npix * (2 + np.isin(ops, randaug.HIST_OPS))).sum())
+                users.append(int(np.isin(ops, randaug.HIST_OPS).sum()))
+            dapack = resample.upload(apack, dev)
+            pristine = dapack["src"].clone()
+            scratch = torch.empty_like(pristine)
+            randaug.augment_on_device(dapack["src"], dapack["aug"], dapack["aug_flags"], scratch=scratch)   # warm the allocator
+            times = []
+            for _ in range(a.iters):
+                dapack["src"].copy_(pristine)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                randaug.augment_on_device(dapack["src"], dapack["aug"], dapack["aug_flags"], scratch=scratch)
+                e1.record()
+                torch.cuda.synchronize()
+                times.append(e0.elapsed_time(e1))
+            s_med, s_min = statistics.median(times), min(times)
+            say(f"m3ae_image_randaug_u8, both stages, {a.batch} images of {side}x{side} (stage flags {apack['aug_flags']:#x}; histogram "
+                f"users per stage {users}): median {s_med:.3f} ms, min {s_min:.3f} ms = {s_med / k_med:.2f} of the two resample passes "
+                f"({k_med:.3f} ms), {s_med / h2d_med:.3f} of the H2D copy")
+            say(f"bytes the stages must move: {moved / 1e6:.1f} MB -> {moved / HBM_ACHIEVABLE * 1e3:.3f} ms at "
+                f"{HBM_ACHIEVABLE / 1e12:.1f} TB/s; achieved {moved / s_med / 1e9:.2f} TB/s = "
+                f"{moved / s_med / 1e9 / (HBM_ACHIEVABLE / 1e12) * 100:.1f} % of the HBM rate")
+            aug_lines += [f"\n## JPEG {side}x{side} sources -> {a.size}", f"clip producer throughput (median of {a.windows} windows): host "
+                          f"{mh:.1f} images/s, device {md:.1f} images/s; m3ae_image_resample_u8 median {k_med:.3f} ms"] + lines[first_aug_line:]
+            del dms, dst, dpack, crop, dbpack, with_tab, tab, aug, dapack, pristine, scratch
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         f.write("\n".join(lines) + "\n")
+    with open(a.randaug_out, "w") as f:
+        f.write(lines[0] + "\n" + "\n".join(aug_lines) + "\n")
     if failed:
         raise SystemExit("FAILED: " + "; ".join(failed))
 
