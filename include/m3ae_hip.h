@@ -304,6 +304,8 @@ int m3ae_xattn_probs_export(const m3ae_xattn_desc* d, int dropped, float* out, i
  * bwd: dx = LN'(dy) (+ dx_add: the residual branch's gradient of a pre-LN block, fused); dgamma / dbeta are
  * ACCUMULATED (+=) in fp32 (dgamma may be NULL for frozen parameters).  workspace: fp32 [2 * nblk * D] with
  * nblk = m3ae_layernorm_bwd_blocks(M).  rms != 0 selects T5 RMSNorm (no mean subtraction, no beta).
+ * Row arrays (x, y, dy, dx, dx_add, dx_drop) are 16-byte aligned for M3AE_F32 and 8-byte aligned for M3AE_BF16, gamma / beta
+ * 16-byte aligned: M3AE_ERR_ALIGN otherwise, before any launch.
  */
 int m3ae_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                        int64_t M, int64_t D, float eps, int dtype, int act, int rms, void* stream);

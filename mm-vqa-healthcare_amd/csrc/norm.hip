@@ -8,6 +8,7 @@
 #include "common.h"
 #include "det_fold.h"
 #include "launch.h"
+#include <initializer_list>
 #include <type_traits>
 
 namespace {
@@ -457,11 +458,21 @@ int launch_fwd_pair(const void* x, const float* g, const float* b, void* y, floa
     return hip_launch_status();
 }
 
+// Alignment the row kernels load with: 4-element chunks = 16 bytes of fp32 rows, 8 bytes of bf16 rows; gamma / beta always 16
+// bytes.  Checked before any launch (a null pointer counts as aligned).
+static bool ln_rows_aligned(int dtype, std::initializer_list<const void*> rows, std::initializer_list<const void*> params) {
+    uintptr_t r = 0, q = 0;
+    for (const void* p : rows) r |= (uintptr_t)p;
+    for (const void* p : params) q |= (uintptr_t)p;
+    return (r & (dtype == M3AE_F32 ? 15u : 7u)) == 0 && (q & 15u) == 0;
+}
+
 extern "C" int m3ae_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean,
                                   float* rstd, int64_t M, int64_t D, float eps, int dtype, int act, int rms,
                                   void* stream) {
     if (!x || !gamma || !y || M <= 0 || D <= 0) return M3AE_ERR_ARG;
     if (D % 4 != 0 || D > 4096) return M3AE_ERR_UNSUPPORTED;
+    if (!ln_rows_aligned(dtype, {x, y}, {gamma, beta})) return M3AE_ERR_ALIGN;
     hipStream_t s = (hipStream_t)stream;
     const bool pair_off = (rms & 2) != 0;   // rms bit 1: diagnostic A / B of the row-pair kernel (tools/ln_bench.py)
     rms &= 1;
@@ -488,6 +499,7 @@ static int layernorm_bwd_impl(const void* dy, const void* x, const float* gamma,
                               int64_t M, int64_t D, int dtype, int act, int rms, void* stream, int det) {
     if (!dy || !x || !gamma || !rstd || !dx || !workspace || M <= 0) return M3AE_ERR_ARG;
     if (D % 4 != 0 || D > 2048) return M3AE_ERR_UNSUPPORTED;
+    if (!ln_rows_aligned(dtype, {dy, x, dx, dx_add}, {gamma, beta})) return M3AE_ERR_ALIGN;
     hipStream_t s = (hipStream_t)stream;
     int nblk = (int)m3ae_layernorm_bwd_blocks(M);   // upper bound (the workspace is sized for it); launch_bwd may lower it
     int rc = M3AE_ERR_UNSUPPORTED;
@@ -523,6 +535,7 @@ static int layernorm_bwd_drop_impl(const void* dy, const void* x, const float* g
     if (!dy || !x || !gamma || !rstd || !dx || !dx_drop || !workspace || M <= 0) return M3AE_ERR_ARG;
     if (!drop_rows_ok(rows, M, D)) return M3AE_ERR_ARG;
     if (D % 4 != 0 || D > 2048) return M3AE_ERR_UNSUPPORTED;
+    if (!ln_rows_aligned(dtype, {dy, x, dx, dx_drop}, {gamma, beta})) return M3AE_ERR_ALIGN;
     hipStream_t s = (hipStream_t)stream;
     int nblk = (int)m3ae_layernorm_bwd_blocks(M);
     const DropState drop = make_drop(dropout_p, dropout_seed, dropout_salt, rows);
