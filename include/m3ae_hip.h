@@ -46,6 +46,9 @@ extern "C" {
  *    m3ae_beam_finalize (csrc/beam.hip); no descriptor changed. */
 /* 4 (additive): tiled weight operand of the NT GEMMs.  M3AE_GEMM_B_TILED in m3ae_gemm_desc.launch_flags and m3ae_tile_bf16_batched,
  *    which writes the tiled copies (layout: csrc/tiled_b.h); no descriptor changed. */
+/* 4 (additive): gradient clipping by global norm with a non-finite step guard.  m3ae_sumsq_segments (+ m3ae_sumsq_workspace_bytes),
+ *    m3ae_clip_finalize and m3ae_adamw_clip (csrc/gradnorm.hip, csrc/misc.hip); the device record is plain 32-bit words
+ *    (M3AE_CLIP_*), no descriptor changed and m3ae_adamw keeps its signature. */
 #define M3AE_ABI_VERSION 4
 
 enum { M3AE_F32 = 0, M3AE_BF16 = 1 };
@@ -459,6 +462,42 @@ int m3ae_adamw(float* p, const float* g, float* m, float* v, void* shadow_bf16, 
 /* hyper_dev (ABI 3): NULL, or a device pointer to {lr, lr * sqrt(1 - beta2^step) / (1 - beta1^step)} of THIS step: the kernel then
  * takes both from there instead of from `lr` / `step` (a hipGraph-captured step replays with frozen arguments; the caller
  * uploads the two floats per group before every replay). */
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Gradient clipping by global norm with a non-finite step guard (ABI 4, additive; csrc/gradnorm.hip).  No atomics, no host
+ * round trip: sums of squares in double -> one-workgroup finalize -> m3ae_adamw_clip reads the factor from device memory.
+ *
+ * m3ae_sumsq_segments: out[s] = sum of x[i]^2 over segment s, as double, accumulated in double from the first add (the square
+ *   of an fp32 value is exact in double, only the adds round: |out - exact| <= (len - 1) * 2^-53 * exact in any order; no finite
+ *   input overflows or underflows).  The segments [begin, end) of x[n] -- sorted, non-overlapping, any alignment, empty ones and
+ *   gaps allowed -- are given cut into pieces by the caller:
+ *     pieces_dev  [npieces][2] int64 {begin, end} in elements, every piece inside one segment, a segment's pieces adjacent and
+ *                 ascending (the binding cuts at most 32768 elements per piece; any length works);
+ *     seg_ptr_dev [nseg + 1] int64, CSR: segment s owns pieces seg_ptr[s] .. seg_ptr[s + 1] - 1 (none: out[s] = 0).
+ *   One workgroup per piece writes one double to `workspace` (fixed lane positions, fixed tree); one wave per segment then adds
+ *   that segment's pieces in ascending order.  The result is a function of (x, tables) alone: two calls give the same bits, and
+ *   deterministic mode takes this same entry point.  Elements outside every piece are never read; piece bounds are clamped to
+ *   [0, n].  x 16-byte aligned.  m3ae_sumsq_workspace_bytes(npieces): bytes of `workspace` (touches no device).
+ * m3ae_clip_finalize (one workgroup): total = seg_sumsq[0] + ... + seg_sumsq[nseg - 1] in ascending index, in double, then the
+ *   record (M3AE_CLIP_RECORD_WORDS 32-bit words on the device, zeroed once by the caller; indices below):
+ *     norm (float)  = sqrt(total) * |grad_scale|                          -- the norm of the averaged gradient under DDP
+ *     coef (float)  = min(1, max_norm / (norm + 1e-6)), formed in double  -- torch.nn.utils.clip_grad_norm_'s rule; exactly 1.0f
+ *                     whenever the norm is inside the bound; max_norm = +inf: guard only
+ *     skip (uint32) = 1 and coef = 0 when total is inf or nan, else 0
+ *     steps / clipped_steps / skipped_steps (uint32): running counters, incremented by this call.
+ *   max_norm in (0, +inf], grad_scale finite, else M3AE_ERR_ARG.
+ * m3ae_adamw_clip: m3ae_adamw with `clip_dev`, the record: skip != 0 -> returns before touching p, m, v or the shadow; otherwise
+ *   grad_scale * coef, formed once in fp32, takes the place of grad_scale (coef == 1.0f: the bits of m3ae_adamw).
+ */
+enum { M3AE_CLIP_NORM = 0, M3AE_CLIP_COEF = 1, M3AE_CLIP_SKIP = 2, M3AE_CLIP_STEPS = 4, M3AE_CLIP_CLIPPED_STEPS = 5,
+       M3AE_CLIP_SKIPPED_STEPS = 6, M3AE_CLIP_RECORD_WORDS = 8 };
+int64_t m3ae_sumsq_workspace_bytes(int64_t npieces);
+int m3ae_sumsq_segments(const float* x, int64_t n, const int64_t* pieces_dev, int64_t npieces, const int64_t* seg_ptr_dev,
+                        int64_t nseg, double* out, void* workspace, int64_t workspace_bytes, void* stream);
+int m3ae_clip_finalize(const double* seg_sumsq, int64_t nseg, float grad_scale, float max_norm, float* record, void* stream);
+int m3ae_adamw_clip(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, float beta1,
+                    float beta2, float eps, float wd, int64_t step, float grad_scale, const float* hyper_dev,
+                    const float* clip_dev, void* stream);
 
 /* bf16 [R, C] <- fp32 [R, C] cast; and the transposed bf16 copy out_t [C, R] (dgrad operand). either may be NULL */
 int m3ae_cast_transpose(const float* in, void* out, void* out_t, int64_t R, int64_t C, void* stream);

@@ -410,9 +410,16 @@ __global__ __launch_bounds__(256) void roberta_embed_bwd_det_kernel(const int* _
 }
 
 // ---- AdamW (transformers 4.6.0 semantics) -----------------------------------------------------------------
+// CLIP (m3ae_adamw_clip): the clipping record of m3ae_clip_finalize (csrc/gradnorm.hip) decides on the device -- a non-finite step
+// leaves before anything is touched, otherwise grad_scale * coef, formed once, is the gradient's factor (coef == 1.0f: same bits).
+template <bool CLIP = false>
 __global__ void adamw_kernel(float* p, const float* g, float* m, float* v, bf16_t* shadow, int64_t n4, float lr,
                              float b1, float b2, float eps, float wd, float step_size, float grad_scale,
-                             const float* hyper_dev) {
+                             const float* hyper_dev, const float* clip_dev) {
+    if (CLIP) {
+        if (((const uint32_t*)clip_dev)[M3AE_CLIP_SKIP] != 0u) return;
+        grad_scale = grad_scale * clip_dev[M3AE_CLIP_COEF];
+    }
     if (hyper_dev) { lr = hyper_dev[0]; step_size = hyper_dev[1]; }   // a captured step: this step's values come from device memory
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         f32x4 pp = ((f32x4*)p)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
@@ -808,17 +815,28 @@ extern "C" int m3ae_xent(const void* logits, const int64_t* labels, float* loss,
     return xent_impl(logits, labels, loss, d_logits, workspace, rows, C, ld, grad_scale, dtype, nullptr, (hipStream_t)stream);
 }
 
-extern "C" int m3ae_adamw(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr,
-                          float beta1, float beta2, float eps, float wd, int64_t step, float grad_scale,
-                          const float* hyper_dev, void* stream) {
-    if (!p || !g || !m || !v || n <= 0 || step <= 0) return M3AE_ERR_ARG;
-    if (n % 4 != 0 || (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15)) return M3AE_ERR_ALIGN;
+template <bool CLIP>
+static int adamw_impl(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, float beta1, float beta2,
+                      float eps, float wd, int64_t step, float grad_scale, const float* hyper_dev, const float* clip_dev,
+                      void* stream) {
+    if (!p || !g || !m || !v || n <= 0 || step <= 0 || (CLIP && !clip_dev)) return M3AE_ERR_ARG;
+    if (n % 4 != 0 || (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) || ((uintptr_t)clip_dev & 3)) return M3AE_ERR_ALIGN;
     hipStream_t s = (hipStream_t)stream;
     const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
     const float step_size = (float)((double)lr * sqrt(bc2) / bc1);
-    hipLaunchKernelGGL(adamw_kernel, dim3(ew_grid(n / 4)), dim3(EW_BLOCK), 0, s, p, g, m, v, (bf16_t*)shadow_bf16, n / 4,
-                       lr, beta1, beta2, eps, wd, step_size, grad_scale, hyper_dev);
+    hipLaunchKernelGGL(adamw_kernel<CLIP>, dim3(ew_grid(n / 4)), dim3(EW_BLOCK), 0, s, p, g, m, v, (bf16_t*)shadow_bf16, n / 4,
+                       lr, beta1, beta2, eps, wd, step_size, grad_scale, hyper_dev, clip_dev);
     return hip_launch_status();
+}
+extern "C" int m3ae_adamw(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr,
+                          float beta1, float beta2, float eps, float wd, int64_t step, float grad_scale,
+                          const float* hyper_dev, void* stream) {
+    return adamw_impl<false>(p, g, m, v, shadow_bf16, n, lr, beta1, beta2, eps, wd, step, grad_scale, hyper_dev, nullptr, stream);
+}
+extern "C" int m3ae_adamw_clip(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr,
+                               float beta1, float beta2, float eps, float wd, int64_t step, float grad_scale,
+                               const float* hyper_dev, const float* clip_dev, void* stream) {
+    return adamw_impl<true>(p, g, m, v, shadow_bf16, n, lr, beta1, beta2, eps, wd, step, grad_scale, hyper_dev, clip_dev, stream);
 }
 
 extern "C" int m3ae_cast_transpose(const float* in, void* out, void* out_t, int64_t R, int64_t C, void* stream) {

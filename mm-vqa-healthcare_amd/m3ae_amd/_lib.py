@@ -60,6 +60,8 @@ GEMM_NO_PERSISTENT, GEMM_F32_X3, GEMM_DETERMINISTIC, GEMM_B_TILED = 1, 2, 4, 8  
 DET_COLSUM, DET_EMBED_BWD, DET_BCE, DET_XENT, DET_MIM = 0, 1, 2, 3, 4   # m3ae_det_workspace_bytes op
 ATTN_LEGACY_KERNELS, ATTN_F32_X3 = 1, 2           # m3ae_attn_desc.launch_flags
 XATTN_NO_PERSISTENT, XATTN_LEGACY_CHAIN = 1, 2    # m3ae_xattn_desc.launch_flags
+# 32-bit word indices of the clipping record m3ae_clip_finalize writes and m3ae_adamw_clip reads (include/m3ae_hip.h)
+CLIP_NORM, CLIP_COEF, CLIP_SKIP, CLIP_STEPS, CLIP_CLIPPED_STEPS, CLIP_SKIPPED_STEPS, CLIP_RECORD_WORDS = 0, 1, 2, 4, 5, 6, 8
 ABI_VERSION = 4
 
 
@@ -141,6 +143,11 @@ _SIGS = {
     # sample expansion of a de-duplicated image batch (ABI 4, additive)
     "m3ae_expand_samples": (C.c_int, [vp, vp, vp, i64, i64, i64, C.c_int, vp]),
     "m3ae_segment_sum_rows": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, C.c_int, vp]),
+    # gradient clipping by global norm + non-finite step guard (ABI 4, additive): record layout below (CLIP_*)
+    "m3ae_sumsq_workspace_bytes": (i64, [i64]),
+    "m3ae_sumsq_segments": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, i64, vp]),
+    "m3ae_clip_finalize": (C.c_int, [vp, i64, f32, f32, vp, vp]),
+    "m3ae_adamw_clip": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i64, f32, vp, vp, vp]),
     # fp32 residual stream of a bf16 model (ABI 4, additive): LayerNorm fp32 rows -> bf16 rows, and its backward
     "m3ae_layernorm_fwd_mixed": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, f32, vp]),
     "m3ae_layernorm_bwd_mixed": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp]),

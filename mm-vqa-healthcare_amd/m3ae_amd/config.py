@@ -69,6 +69,12 @@ DEFAULTS = dict(
     # "host" Pillow runs the operations on the loader threads, under "device" csrc/randaug.hip does, on the uploaded source bytes:
     # equal batches (m3ae_amd/randaug.py).  Val / test never augment.  Not available with graph.GraphedStep.
     randaug=False,
+    # gradient clipping by global norm (Lightning's Trainer flag, PL 1.3.2 norm clipping; torch.nn.utils.clip_grad_norm_'s rule) with a
+    # non-finite step guard: 0.0 = off (the step's launches are what they are without the key) | a bound > 0 | float("inf") = guard
+    # only.  The norm is summed in double on the device (csrc/gradnorm.hip) and the factor reaches the AdamW launches through device
+    # memory: no host round trip.  A step whose gradient holds an inf or a nan updates nothing and is counted
+    # (ParamStore.grad_stats).  Not available with graph.GraphedStep or FlatGradReducer(update_in_backward=True).
+    gradient_clip_val=0.0,
 )
 
 NAMED = {
@@ -150,9 +156,22 @@ def randaug_enabled(cfg):
     return v
 
 
+def gradient_clip_val(cfg):
+    """The validated `gradient_clip_val` of a config dict (default 0.0 = off) as a float: a number >= 0, or float("inf") -- on the
+    command line `gradient_clip_val=inf` -- for the non-finite guard without a bound."""
+    v = cfg.get("gradient_clip_val", 0.0)
+    if v == "inf":   # the command-line grammar has no literal for it
+        v = float("inf")
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v < 0:
+        raise ValueError(f'gradient_clip_val must be a number >= 0 (0: off) or float("inf") (guard only), got {v!r}')
+    return float(v)
+
+
 def resolve_arch(cfg):
     """Fill vit_width/vit_layers/text_* from the `vit` / `tokenizer` names unless given explicitly."""
     cfg = dict(cfg)
+    if "gradient_clip_val" in cfg:
+        cfg["gradient_clip_val"] = gradient_clip_val(cfg)
     clip_residual_dtype(cfg)
     transform_keys(cfg)
     randaug_enabled(cfg)

@@ -222,6 +222,10 @@ class FlatGradReducer:
         traffic (HBM-bound, ~30 registers per lane: its waves fit beside the GEMMs' on a CU) runs under the compute-bound
         rest of backward instead of after it.  `finish()` updates what is left, refreshes the transposed weight copies and
         joins; the caller must NOT call the optimizer's step afterwards."""
+        if self.store.clip_val() > 0:
+            # the buckets are stepped while backward still runs, before the norm of the whole gradient can be known
+            raise ValueError("FlatGradReducer(update_in_backward=True) cannot be combined with gradient_clip_val: the global "
+                             "gradient norm exists only after backward; step the optimizer after finish() instead")
         assert self.update_in_backward
         # the early update of a bucket assumes every later reader of its weights is ordered behind events already recorded: true when
         # the GEMMs read the bf16 shadows / transposed copies the update rewrites LAST (finish()), not the fp32 masters.  A "late

@@ -37,6 +37,12 @@ class GraphedStep:
             # like the other per-batch plans of the input pipeline: the augment plan and its launches differ from batch to batch and
             # run in front of the step, outside anything a replay could cover
             raise ValueError("GraphedStep does not cover randaug=True: run the step eagerly")
+        from .config import gradient_clip_val
+        if gradient_clip_val(getattr(getattr(core, "hparams", None), "config", None) or {}) > 0 or \
+                gradient_clip_val(getattr(getattr(model, "store", None), "cfg", None) or {}) > 0:
+            # the clipped step's launches (norm, finalize, m3ae_adamw_clip) are not the ones capture() records, and the skipped-step
+            # counters are read where the caller syncs: not offered under replay
+            raise ValueError("GraphedStep does not cover gradient_clip_val: run the step eagerly")
         self.model, self.store, self.batch = model, model.store, batch
         self.max_steps, self.grad_scale = max_steps, grad_scale
         dev = self.store.flat.device

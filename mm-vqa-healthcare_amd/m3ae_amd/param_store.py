@@ -158,6 +158,10 @@ class ParamStore:
                 if self.shadow is not None:
                     p.m3ae_c = self.shadow[o:o + p.numel()].view(p.shape)
         self.step_count = 0
+        # per-parameter segments (offset, numel) of the trainable range, in buffer order, for the gradient norm (gradnorm.py): the
+        # ALIGN padding between parameters is in no segment.  Host list; tables and workspace are uploaded on first use.
+        self.grad_segments = sorted((self.offset[id(p)], p.numel(), n) for g in groups[:6] for n, p in g)
+        self._sums = self._clip_record = None
         # weight units: GEMM weights that need a transposed bf16 copy for dgrad
         self.units = list(weight_units() if callable(weight_units) else (weight_units or []))
         self._t_bufs = []
@@ -251,7 +255,10 @@ class ParamStore:
                      group_wds=None):
         """The host part of an optimizer step: per-group learning rates (built-in schedule unless given), step count.  Returns
         the hyper-parameter record `adamw_range` takes; `adamw_step` = begin_update + adamw_range over the six segments, and
-        ddp.FlatGradReducer(update_in_backward=True) applies the same record bucket by bucket while backward still runs."""
+        ddp.FlatGradReducer(update_in_backward=True) applies the same record bucket by bucket while backward still runs.
+        With gradient_clip_val set, a step the non-finite guard skips on the device still consumes its step number here and its
+        scheduler tick at the caller (as Lightning's scheduler ticks through a GradScaler skip): the count lives on the host,
+        which is what keeps the step free of host syncs; grad_stats()["skipped_steps"] counts them."""
         if self.exp_avg is None:
             self.exp_avg = torch.zeros_like(self.grad)
             self.exp_avg_sq = torch.zeros_like(self.grad)
@@ -283,18 +290,22 @@ class ParamStore:
         return [[lr, lr * math.sqrt(bc2) / bc1] for lr in hyper["lrs"]]
 
     @torch.no_grad()
-    def adamw_range(self, a, b, gi, hyper):
-        """The fused AdamW kernel over elements [a, b) of the flat buffers (inside optimizer group `gi`), on the current stream."""
+    def adamw_range(self, a, b, gi, hyper, clip=None):
+        """The fused AdamW kernel over elements [a, b) of the flat buffers (inside optimizer group `gi`), on the current stream.
+        `clip`: the device record of m3ae_clip_finalize; the launch is then m3ae_adamw_clip (skip / grad_scale * coef on the device)."""
         if b <= a:
             return
         from . import ops as _ops
         es = 4
         sh = C.c_void_p(self.shadow.data_ptr() + a * 2) if self.shadow is not None else None
-        _lib.check(_lib.lib().m3ae_adamw(C.c_void_p(self.flat.data_ptr() + a * es), C.c_void_p(self.grad.data_ptr() + a * es),
-                                         C.c_void_p(self.exp_avg.data_ptr() + a * es),
-                                         C.c_void_p(self.exp_avg_sq.data_ptr() + a * es), sh, b - a, hyper["lrs"][gi],
-                                         hyper["b1"], hyper["b2"], hyper["eps"], hyper["wds"][gi], hyper["step"],
-                                         hyper["grad_scale"], self._hyper_dev_ptr(gi), _ops._stream()), "m3ae_adamw")
+        args = (C.c_void_p(self.flat.data_ptr() + a * es), C.c_void_p(self.grad.data_ptr() + a * es),
+                C.c_void_p(self.exp_avg.data_ptr() + a * es), C.c_void_p(self.exp_avg_sq.data_ptr() + a * es), sh, b - a,
+                hyper["lrs"][gi], hyper["b1"], hyper["b2"], hyper["eps"], hyper["wds"][gi], hyper["step"], hyper["grad_scale"],
+                self._hyper_dev_ptr(gi))
+        if clip is None:
+            _lib.check(_lib.lib().m3ae_adamw(*args, _ops._stream()), "m3ae_adamw")
+        else:
+            _lib.check(_lib.lib().m3ae_adamw_clip(*args, C.c_void_p(clip.data_ptr()), _ops._stream()), "m3ae_adamw_clip")
 
     @torch.no_grad()
     def adamw_step(self, max_steps=None, grad_scale=1.0, lr_factor=None, group_lrs=None, betas=(0.9, 0.98), eps=1e-8,
@@ -307,11 +318,65 @@ class ParamStore:
 
     @torch.no_grad()
     def adamw_apply(self, hyper):
-        """The device part of an optimizer step for a begin_update() record: six fused launches + the transposed weight copies."""
+        """The device part of an optimizer step for a begin_update() record: six fused launches + the transposed weight copies.
+        With cfg["gradient_clip_val"] > 0: the sum of squares of the gradient buffer per parameter (double), the one-workgroup
+        finalize with this step's grad_scale, then the six launches as m3ae_adamw_clip -- all on the current stream, the factor and
+        the skip flag never leave the device.  With the key at 0 this is the six m3ae_adamw launches and nothing is allocated."""
+        clip = None
+        max_norm = self.clip_val()
+        if max_norm > 0:
+            from . import gradnorm as _gn, ops as _ops
+            clip = self._clip_buffers()
+            _gn.clip_finalize(self._sums.run(self.grad, _ops._stream()), hyper["grad_scale"], max_norm, clip, _ops._stream())
         for gi in range(6):
             a, b = self.segments[gi]
-            self.adamw_range(a, min(b, self.trainable_end), gi, hyper)
+            self.adamw_range(a, min(b, self.trainable_end), gi, hyper, clip)
         self.sync_shadows(cast=False)
+
+    # ---- gradient norm, clipping, non-finite guard (csrc/gradnorm.hip) ---------------------------------------
+    def clip_val(self):
+        """The validated cfg["gradient_clip_val"]: 0.0 (off), a bound > 0, or inf (guard only)."""
+        from .config import gradient_clip_val
+        return gradient_clip_val(self.cfg)
+
+    def _segment_sums(self):
+        if self._sums is None:
+            from . import gradnorm as _gn
+            self._sums = _gn.SegmentSums([(o, o + n) for o, n, _ in self.grad_segments], self.grad.numel(), self.grad.device)
+        return self._sums
+
+    def _clip_buffers(self):
+        self._segment_sums()
+        if self._clip_record is None:
+            self._clip_record = torch.zeros(_lib.CLIP_RECORD_WORDS, dtype=torch.float32, device=self.grad.device)
+        return self._clip_record
+
+    def grad_stats(self):
+        """{norm, coef, skipped, steps, clipped_steps, skipped_steps} of the last clipped / guarded step (gradient_clip_val set):
+        the norm of the averaged gradient, the factor applied, whether the step was skipped for a non-finite gradient, and the
+        running counters.  One small device-to-host copy that blocks: call it where the caller syncs anyway (the log line)."""
+        if self._clip_record is None:
+            raise RuntimeError("grad_stats(): no step has run with gradient_clip_val set")
+        rec = self._clip_record.cpu()
+        cnt = rec.view(torch.int32)
+        return dict(norm=float(rec[_lib.CLIP_NORM]), coef=float(rec[_lib.CLIP_COEF]), skipped=bool(cnt[_lib.CLIP_SKIP]),
+                    steps=int(cnt[_lib.CLIP_STEPS]), clipped_steps=int(cnt[_lib.CLIP_CLIPPED_STEPS]),
+                    skipped_steps=int(cnt[_lib.CLIP_SKIPPED_STEPS]))
+
+    @torch.no_grad()
+    def grad_norms(self):
+        """{name: L2 norm} of every trainable parameter's gradient as the buffer stands (double sums on the device, one launch
+        chain, one copy back); no clipping, no scaling."""
+        from . import ops as _ops
+        out = self._segment_sums().run(self.grad, _ops._stream()).cpu().sqrt()
+        return {n: float(v) for (_, _, n), v in zip(self.grad_segments, out)}
+
+    @torch.no_grad()
+    def grad_norm(self):
+        """Global L2 norm of the gradient buffer as it stands (from the per-parameter double sums)."""
+        from . import ops as _ops
+        out = self._segment_sums().run(self.grad, _ops._stream()).cpu()
+        return math.sqrt(math.fsum(out.tolist()))
 
     def make_optimizer(self, max_steps=None):
         """([optimizer], [{"scheduler", "interval": "step"}]) in the shape m3ae_utils.set_schedule returns (:240-242)."""
@@ -331,7 +396,9 @@ class FlatAdamW(torch.optim.Optimizer):
     so a Lightning-style loop (`optimizer.step(); scheduler.step(); optimizer.zero_grad()`) and LambdaLR schedulers work.
     `step()` is one fused kernel launch per group over the flat buffers; the learning rates are read from
     `param_groups[i]["lr"]` (whatever a scheduler wrote there).  `state_dict()` / `load_state_dict()` round-trip the
-    moments (per parameter, torch's layout) and the step count."""
+    moments (per parameter, torch's layout) and the step count.
+    With `gradient_clip_val` in the store's config, `step()` clips by global norm and skips a non-finite step on the device
+    (ParamStore.adamw_apply); a skipped step still advances the step count, and the caller's scheduler ticks as usual."""
 
     def __init__(self, store, grad_scale=1.0):
         self.store = store

@@ -12,6 +12,9 @@ arithmetic around `training_step`:
   in place in the flat buffer, the gradient all-reduce runs on the LAST micro-batch only (ddp.FlatGradReducer);
 * `max_steps` optimizer steps, or `max_epoch` epochs when `max_steps` is None / -1 (main.py:51-52);
 * the 6-group AdamW + polynomial schedule stepped once per optimizer step (m3ae_utils.py:112-242, ParamStore);
+* `gradient_clip_val` (Lightning's Trainer flag; 0 = off): clipping by global norm and the non-finite step guard happen inside
+  `optimizer.step()`, after the gradient all-reduce, once per accumulation window (ParamStore.adamw_apply); the periodic log line
+  then also shows the gradient norm, the factor applied and the number of skipped steps;
 * validation every `val_check_interval` of an epoch with the VQA score `val/the_metric` (my_metrics.py:58-83), best +
   last checkpoints (`ModelCheckpoint(save_top_k=1, monitor="val/the_metric", mode="max", save_last=True)`,
   main.py:36-43) written as `{"state_dict": ...}` with the REFERENCE's key names, so the files load in the upstream
@@ -260,9 +263,13 @@ class Trainer:
                         lv = loss.item() * gs
                         dt = time.perf_counter() - t0
                         self.history.append((self.global_step, lv))
+                        clip = ""
+                        if self.store.clip_val() > 0:   # loss.item() above has synced: the record of this step is complete
+                            gs_ = self.store.grad_stats()
+                            clip = f" grad_norm {gs_['norm']:.4g} coef {gs_['coef']:.4f} skipped {gs_['skipped_steps']}"
                         log(f"epoch {self.epoch} step {self.global_step}/{P['max_steps']} loss {lv:.4f} "
                             f"lr x{self.store.lr_factor(self.store.step_count, P['max_steps']):.4f} "
-                            f"{seen / dt:.1f} pairs/s", self.rank)
+                            f"{seen / dt:.1f} pairs/s{clip}", self.rank)
                     if self.global_step >= P["max_steps"]:
                         done = True
                 if nbatch % val_every == 0 or done:

@@ -36,6 +36,7 @@ RANDAUG_ENTRIES = ("m3ae_image_randaug_workspace_bytes", "m3ae_image_randaug_u8"
 SAMPLES_ENTRIES = ("m3ae_expand_samples", "m3ae_segment_sum_rows")
 MIXED_LN_ENTRIES = ("m3ae_layernorm_fwd_mixed", "m3ae_layernorm_bwd_mixed", "m3ae_layernorm_bwd_mixed_det")
 TILED_ENTRIES = ("m3ae_tile_bf16_batched",)
+CLIP_ENTRIES = ("m3ae_sumsq_workspace_bytes", "m3ae_sumsq_segments", "m3ae_clip_finalize", "m3ae_adamw_clip")
 ROWS_ENTRIES = ("m3ae_gemm_rows", "m3ae_attn_fwd_rows", "m3ae_attn_bwd_rows", "m3ae_layernorm_bwd_drop_rows", "m3ae_dropout_rows")
 
 
@@ -98,6 +99,14 @@ def block():
     out.append("# tiled weight operand of the NT GEMMs (ABI 4, additive): B = the tiled copy of W[N][K] (csrc/tiled_b.h), same results")
     out.append(f"GEMM_B_TILED = {_lib.GEMM_B_TILED}     # m3ae_gemm_desc.launch_flags; b_sk = 1, b_sn = K, B 16-byte aligned, K % 32 == 0")
     for name in TILED_ENTRIES:
+        res, args = _lib._SIGS[name]
+        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
+    out.append("")
+    out.append("# gradient clipping by global norm + non-finite step guard (ABI 4, additive): double sums of squares, device-side factor")
+    out.append(f"CLIP_NORM, CLIP_COEF, CLIP_SKIP, CLIP_STEPS, CLIP_CLIPPED_STEPS, CLIP_SKIPPED_STEPS, CLIP_RECORD_WORDS = {_lib.CLIP_NORM}, "
+               f"{_lib.CLIP_COEF}, {_lib.CLIP_SKIP}, {_lib.CLIP_STEPS}, {_lib.CLIP_CLIPPED_STEPS}, {_lib.CLIP_SKIPPED_STEPS}, "
+               f"{_lib.CLIP_RECORD_WORDS}     # 32-bit words of the record")
+    for name in CLIP_ENTRIES:
         res, args = _lib._SIGS[name]
         out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
     out.append("```")
