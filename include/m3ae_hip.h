@@ -49,6 +49,8 @@ extern "C" {
 /* 4 (additive): gradient clipping by global norm with a non-finite step guard.  m3ae_sumsq_segments (+ m3ae_sumsq_workspace_bytes),
  *    m3ae_clip_finalize and m3ae_adamw_clip (csrc/gradnorm.hip, csrc/misc.hip); the device record is plain 32-bit words
  *    (M3AE_CLIP_*), no descriptor changed and m3ae_adamw keeps its signature. */
+/* 4 (additive): the optim_type rules next to AdamW.  m3ae_adam, m3ae_sgd and their _clip forms (csrc/misc.hip); no descriptor
+ *    changed. */
 #define M3AE_ABI_VERSION 4
 
 enum { M3AE_F32 = 0, M3AE_BF16 = 1 };
@@ -498,6 +500,40 @@ int m3ae_clip_finalize(const double* seg_sumsq, int64_t nseg, float grad_scale, 
 int m3ae_adamw_clip(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, float beta1,
                     float beta2, float eps, float wd, int64_t step, float grad_scale, const float* hyper_dev,
                     const float* clip_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * The other two rules of the reference's `optim_type` (m3ae_utils.py:203-210), ABI 4, additive (csrc/misc.hip).  Same contract as
+ * m3ae_adamw: one call per contiguous fp32 segment, n % 4 == 0, fp32 pointers 16-byte aligned, g multiplied by grad_scale first,
+ * the bf16 shadow written in the same pass when given; fp32 arithmetic, one operation per line below.  Neither takes hyper_dev
+ * (a hipGraph-captured step is offered for AdamW only).
+ *
+ * m3ae_adam: single-tensor torch.optim.Adam, no amsgrad, coupled L2 decay; step >= 1:
+ *     g' = g * grad_scale;  if (wd > 0) g' = g' + wd * p
+ *     m  = m * beta1 + g' * (1 - beta1)
+ *     v  = v * beta2 + g' * g' * (1 - beta2)
+ *     denom = sqrtf(v) / bc2_sqrt + eps
+ *     p  = p - step_size * (m / denom)
+ *   with step_size = lr / (1 - beta1^step), bc2_sqrt = sqrt(1 - beta2^step), (1 - beta1) and (1 - beta2) each formed in double on
+ *   the host and rounded to fp32 once (the bias correction of v sits inside the denominator, not in the step size as in
+ *   m3ae_adamw).  beta1 / beta2 are doubles, as torch holds them: at torch's default 0.999 the fp32 value is 1.3e-8 off, but its
+ *   complement 1.0f - 0.999f is 1.3e-5 off 0.001, which v would carry whole (m3ae_adamw's 0.98 is four times closer to its fp32
+ *   value and its complement forty times larger).
+ * m3ae_sgd: torch.optim.SGD with momentum, dampening 0, no Nesterov:
+ *     g'  = g * grad_scale;  if (wd > 0) g' = g' + wd * p
+ *     buf = buf * momentum + g'
+ *     p   = p - lr * buf
+ *   torch's first step sets buf = g'; a zero-initialised buf gives the same bits, so there is no step argument.
+ * The _clip forms take the record of m3ae_clip_finalize exactly as m3ae_adamw_clip does: skip != 0 -> returns before touching
+ *   anything; otherwise grad_scale * coef, formed once in fp32, takes the place of grad_scale (coef == 1.0f: the plain form's bits).
+ */
+int m3ae_adam(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, double beta1, double beta2,
+              float eps, float wd, int64_t step, float grad_scale, void* stream);
+int m3ae_adam_clip(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, double beta1,
+                   double beta2, float eps, float wd, int64_t step, float grad_scale, const float* clip_dev, void* stream);
+int m3ae_sgd(float* p, const float* g, float* buf, void* shadow_bf16, int64_t n, float lr, float momentum, float wd,
+             float grad_scale, void* stream);
+int m3ae_sgd_clip(float* p, const float* g, float* buf, void* shadow_bf16, int64_t n, float lr, float momentum, float wd,
+                  float grad_scale, const float* clip_dev, void* stream);
 
 /* bf16 [R, C] <- fp32 [R, C] cast; and the transposed bf16 copy out_t [C, R] (dgrad operand). either may be NULL */
 int m3ae_cast_transpose(const float* in, void* out, void* out_t, int64_t R, int64_t C, void* stream);

@@ -438,6 +438,61 @@ __global__ void adamw_kernel(float* p, const float* g, float* m, float* v, bf16_
     }
 }
 
+// ---- Adam (torch.optim.Adam, single-tensor rule: no amsgrad, coupled L2 decay) -----------------------------------
+// optim_type "adam".  Unlike the HF AdamW above the bias correction of v sits inside the denominator (sqrt(v) / bc2_sqrt + eps)
+// and the decay joins the gradient before the moments see it.  step_size = lr / (1 - b1^t), bc2_sqrt = sqrt(1 - b2^t) and the
+// complements omb1 = 1 - b1, omb2 = 1 - b2 come from the host, formed in double from double betas as torch forms them: 1.0f - 0.999f
+// is 1.3e-5 off 0.001, and v would carry that.  CLIP as in adamw_kernel.
+template <bool CLIP = false>
+__global__ void adam_kernel(float* p, const float* g, float* m, float* v, bf16_t* shadow, int64_t n4, float b1, float b2,
+                            float omb1, float omb2, float eps, float wd, float step_size, float bc2_sqrt, float grad_scale,
+                            const float* clip_dev) {
+    if (CLIP) {
+        if (((const uint32_t*)clip_dev)[M3AE_CLIP_SKIP] != 0u) return;
+        grad_scale = grad_scale * clip_dev[M3AE_CLIP_COEF];
+    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        f32x4 pp = ((f32x4*)p)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+        const f32x4 gg = ((const f32x4*)g)[i];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            float gt = gg[t] * grad_scale;
+            if (wd > 0.f) gt = gt + wd * pp[t];
+            mm[t] = mm[t] * b1 + gt * omb1;
+            vv[t] = vv[t] * b2 + gt * gt * omb2;
+            const float denom = sqrtf(vv[t]) / bc2_sqrt + eps;
+            pp[t] = pp[t] - step_size * (mm[t] / denom);
+        }
+        ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
+        if (shadow) ((u32x2*)shadow)[i] = (u32x2){pack2bf(pp[0], pp[1]), pack2bf(pp[2], pp[3])};
+    }
+}
+
+// ---- SGD with momentum (torch.optim.SGD: dampening 0, no Nesterov, coupled L2 decay) -----------------------------
+// optim_type "sgd".  torch's first step sets buf = g'; a zero-initialised buffer gives the same bits (0 * momentum + g' = g'), so
+// the kernel takes no step number.  One moment buffer: 22 B / element against AdamW's 30.  CLIP as in adamw_kernel.
+template <bool CLIP = false>
+__global__ void sgd_kernel(float* p, const float* g, float* buf, bf16_t* shadow, int64_t n4, float lr, float momentum, float wd,
+                           float grad_scale, const float* clip_dev) {
+    if (CLIP) {
+        if (((const uint32_t*)clip_dev)[M3AE_CLIP_SKIP] != 0u) return;
+        grad_scale = grad_scale * clip_dev[M3AE_CLIP_COEF];
+    }
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        f32x4 pp = ((f32x4*)p)[i], bb = ((f32x4*)buf)[i];
+        const f32x4 gg = ((const f32x4*)g)[i];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            float gt = gg[t] * grad_scale;
+            if (wd > 0.f) gt = gt + wd * pp[t];
+            bb[t] = bb[t] * momentum + gt;
+            pp[t] = pp[t] - lr * bb[t];
+        }
+        ((f32x4*)p)[i] = pp; ((f32x4*)buf)[i] = bb;
+        if (shadow) ((u32x2*)shadow)[i] = (u32x2){pack2bf(pp[0], pp[1]), pack2bf(pp[2], pp[3])};
+    }
+}
+
 // ---- cast / transpose -------------------------------------------------------------------------------------
 __global__ void cast_transpose_kernel(const float* in, bf16_t* out, bf16_t* out_t, int64_t R, int64_t C) {
     __shared__ float tile[32][33];
@@ -837,6 +892,46 @@ extern "C" int m3ae_adamw_clip(float* p, const float* g, float* m, float* v, voi
                                float beta1, float beta2, float eps, float wd, int64_t step, float grad_scale,
                                const float* hyper_dev, const float* clip_dev, void* stream) {
     return adamw_impl<true>(p, g, m, v, shadow_bf16, n, lr, beta1, beta2, eps, wd, step, grad_scale, hyper_dev, clip_dev, stream);
+}
+
+template <bool CLIP>
+static int adam_impl(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, double beta1, double beta2,
+                     float eps, float wd, int64_t step, float grad_scale, const float* clip_dev, void* stream) {
+    if (!p || !g || !m || !v || n <= 0 || step <= 0 || (CLIP && !clip_dev)) return M3AE_ERR_ARG;
+    if (n % 4 != 0 || (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) || ((uintptr_t)clip_dev & 3)) return M3AE_ERR_ALIGN;
+    const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
+    const float step_size = (float)((double)lr / bc1), bc2_sqrt = (float)sqrt(bc2);
+    hipLaunchKernelGGL(adam_kernel<CLIP>, dim3(ew_grid(n / 4)), dim3(EW_BLOCK), 0, (hipStream_t)stream, p, g, m, v,
+                       (bf16_t*)shadow_bf16, n / 4, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, wd, step_size,
+                       bc2_sqrt, grad_scale, clip_dev);
+    return hip_launch_status();
+}
+extern "C" int m3ae_adam(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, double beta1,
+                         double beta2, float eps, float wd, int64_t step, float grad_scale, void* stream) {
+    return adam_impl<false>(p, g, m, v, shadow_bf16, n, lr, beta1, beta2, eps, wd, step, grad_scale, nullptr, stream);
+}
+extern "C" int m3ae_adam_clip(float* p, const float* g, float* m, float* v, void* shadow_bf16, int64_t n, float lr, double beta1,
+                              double beta2, float eps, float wd, int64_t step, float grad_scale, const float* clip_dev,
+                              void* stream) {
+    return adam_impl<true>(p, g, m, v, shadow_bf16, n, lr, beta1, beta2, eps, wd, step, grad_scale, clip_dev, stream);
+}
+
+template <bool CLIP>
+static int sgd_impl(float* p, const float* g, float* buf, void* shadow_bf16, int64_t n, float lr, float momentum, float wd,
+                    float grad_scale, const float* clip_dev, void* stream) {
+    if (!p || !g || !buf || n <= 0 || (CLIP && !clip_dev)) return M3AE_ERR_ARG;
+    if (n % 4 != 0 || (((uintptr_t)p | (uintptr_t)g | (uintptr_t)buf) & 15) || ((uintptr_t)clip_dev & 3)) return M3AE_ERR_ALIGN;
+    hipLaunchKernelGGL(sgd_kernel<CLIP>, dim3(ew_grid(n / 4)), dim3(EW_BLOCK), 0, (hipStream_t)stream, p, g, buf,
+                       (bf16_t*)shadow_bf16, n / 4, lr, momentum, wd, grad_scale, clip_dev);
+    return hip_launch_status();
+}
+extern "C" int m3ae_sgd(float* p, const float* g, float* buf, void* shadow_bf16, int64_t n, float lr, float momentum, float wd,
+                        float grad_scale, void* stream) {
+    return sgd_impl<false>(p, g, buf, shadow_bf16, n, lr, momentum, wd, grad_scale, nullptr, stream);
+}
+extern "C" int m3ae_sgd_clip(float* p, const float* g, float* buf, void* shadow_bf16, int64_t n, float lr, float momentum,
+                             float wd, float grad_scale, const float* clip_dev, void* stream) {
+    return sgd_impl<true>(p, g, buf, shadow_bf16, n, lr, momentum, wd, grad_scale, clip_dev, stream);
 }
 
 extern "C" int m3ae_cast_transpose(const float* in, void* out, void* out_t, int64_t R, int64_t C, void* stream) {

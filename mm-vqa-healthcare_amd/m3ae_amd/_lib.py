@@ -148,6 +148,11 @@ _SIGS = {
     "m3ae_sumsq_segments": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, vp, i64, vp]),
     "m3ae_clip_finalize": (C.c_int, [vp, i64, f32, f32, vp, vp]),
     "m3ae_adamw_clip": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i64, f32, vp, vp, vp]),
+    # the optim_type rules next to AdamW (ABI 4, additive): torch.optim.Adam / SGD with momentum; _clip = + the record
+    "m3ae_adam": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, C.c_double, C.c_double, f32, f32, i64, f32, vp]),     # betas in double
+    "m3ae_adam_clip": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, C.c_double, C.c_double, f32, f32, i64, f32, vp, vp]),
+    "m3ae_sgd": (C.c_int, [vp, vp, vp, vp, i64, f32, f32, f32, f32, vp]),
+    "m3ae_sgd_clip": (C.c_int, [vp, vp, vp, vp, i64, f32, f32, f32, f32, vp, vp]),
     # fp32 residual stream of a bf16 model (ABI 4, additive): LayerNorm fp32 rows -> bf16 rows, and its backward
     "m3ae_layernorm_fwd_mixed": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, f32, vp]),
     "m3ae_layernorm_bwd_mixed": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp]),

@@ -29,6 +29,8 @@ DEFAULTS = dict(
     num_heads=12, num_layers=6, mlp_ratio=4, drop_rate=0.1,
     mim_prob=0.75, mim_decoder_hidden_size=384, mim_decoder_num_layers=4, mim_decoder_num_heads=6,
     norm_pix_loss=True, mim_layer=-1,
+    # the optimizer rule (m3ae_utils.py:203-210): "adamw" | "adam" | "sgd" -- each one fused launch per parameter group over the
+    # flat buffers (csrc/misc.hip); config.optim_type validates, ParamStore dispatches.  graph.GraphedStep covers "adamw" only.
     optim_type="adamw", learning_rate=1e-5, weight_decay=0.01, decay_power=1, max_epoch=100, max_steps=-1,
     warmup_steps=10000, end_lr=0, lr_multiplier_head=5, lr_multiplier_multi_modal=5,
     mm_encoder_inputs_include_cls_feats=True, mm_encoder_inputs_include_imagetext_feats=False,
@@ -167,9 +169,23 @@ def gradient_clip_val(cfg):
     return float(v)
 
 
+OPTIM_TYPES = ("adamw", "adam", "sgd")
+
+
+def optim_type(cfg):
+    """The validated `optim_type` of a config dict (default "adamw"): the optimizer rule, as the reference's set_schedule builds it
+    (m3ae_utils.py:203-210) -- "adamw" = HF AdamW(betas=(0.9, 0.98), eps=1e-8), "adam" = torch.optim.Adam, "sgd" =
+    torch.optim.SGD(momentum=0.9).  The names are case-sensitive there too; anything else is a ValueError."""
+    v = cfg.get("optim_type", "adamw")
+    if not isinstance(v, str) or v not in OPTIM_TYPES:
+        raise ValueError(f"optim_type must be one of {OPTIM_TYPES}, got {v!r}")
+    return v
+
+
 def resolve_arch(cfg):
     """Fill vit_width/vit_layers/text_* from the `vit` / `tokenizer` names unless given explicitly."""
     cfg = dict(cfg)
+    optim_type(cfg)
     if "gradient_clip_val" in cfg:
         cfg["gradient_clip_val"] = gradient_clip_val(cfg)
     clip_residual_dtype(cfg)

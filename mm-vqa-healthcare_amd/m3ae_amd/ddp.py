@@ -12,7 +12,7 @@ autograd glue never report) and waits.  A parameter can receive SEVERAL in-place
 `infer` passes of a pre-training step, an in-projection used for queries and for keys/values): the reducer LEARNS, on its
 first step, how many reports each parameter makes (no early launches on that step) and afterwards launches a bucket only
 when every parameter in it has reported that many times; a report that arrives after its bucket was launched is an
-error (`relearn()`), never a silently half-reduced gradient.  Averaging (1 / world_size) is folded into the fused AdamW kernel's
+error (`relearn()`), never a silently half-reduced gradient.  Averaging (1 / world_size) is folded into the fused optimizer kernel's
 `grad_scale`, not applied to the buffer.  The 6 tensors that never receive a gradient are not in the
 buffer at all -- no `find_unused_parameters` pass.
 
@@ -216,7 +216,7 @@ class FlatGradReducer:
     # ---- the optimizer inside backward -----------------------------------------------------------------------------------
     def arm_update(self, **kw):
         """Call before backward (every step): this step's optimizer hyper-parameters (arguments of ParamStore.begin_update).
-        From the second step on, a bucket's AdamW update is then issued on a separate stream as soon as the NEXT bucket has
+        From the second step on, a bucket's optimizer update (ParamStore.update_range: the rule of `optim_type`) is then issued on a separate stream as soon as the NEXT bucket has
         completed -- at that point every backward kernel that reads the bucket's weights has been enqueued, and the update
         waits for all of them (events on the compute streams) and for the bucket's all-reduce -- so the 9.9 GB of optimizer
         traffic (HBM-bound, ~30 registers per lane: its waves fit beside the GEMMs' on a CU) runs under the compute-bound
@@ -252,7 +252,7 @@ class FlatGradReducer:
                     h.wait()                        # stream-ordered behind the bucket's all-reduce
                 if self.grad_dtype == "bf16" and self._stage is not None and self.world > 1:
                     self.store.grad[a:b].copy_(self._stage[a:b])
-                self.store.adamw_range(a, b, self.bucket_group[bi], self._hyper)
+                self.store.update_range(a, b, self.bucket_group[bi], self._hyper)
                 self._updated[bi] = True
 
     def _note_stream(self, bi):
@@ -330,7 +330,7 @@ class FlatGradReducer:
                 cur.wait_stream(self._opt_stream)       # updates issued during backward
             for bi, _ in self._complete:                # the rest, here: backward is over, the collectives were waited for
                 if not self._updated[bi]:
-                    self.store.adamw_range(self.bounds[bi], self.bounds[bi + 1], self.bucket_group[bi], self._hyper)
+                    self.store.update_range(self.bounds[bi], self.bounds[bi + 1], self.bucket_group[bi], self._hyper)
                     self._updated[bi] = True
             assert all(self._updated[bi] or self.bounds[bi + 1] == self.bounds[bi] for bi in range(self.nb))
             self.store.sync_shadows(cast=False)

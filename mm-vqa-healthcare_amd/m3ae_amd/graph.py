@@ -43,6 +43,12 @@ class GraphedStep:
             # the clipped step's launches (norm, finalize, m3ae_adamw_clip) are not the ones capture() records, and the skipped-step
             # counters are read where the caller syncs: not offered under replay
             raise ValueError("GraphedStep does not cover gradient_clip_val: run the step eagerly")
+        from .config import optim_type
+        for c in (getattr(getattr(core, "hparams", None), "config", None), getattr(getattr(model, "store", None), "cfg", None)):
+            if optim_type(c or {}) != "adamw":
+                # capture() records m3ae_adamw with hyper_dev (this step's learning rate and step size from device memory); the
+                # Adam and SGD entry points take no hyper_dev, so a replay would step with the captured step's values
+                raise ValueError(f'GraphedStep covers optim_type="adamw" only, got "{optim_type(c)}": run the step eagerly')
         self.model, self.store, self.batch = model, model.store, batch
         self.max_steps, self.grad_scale = max_steps, grad_scale
         dev = self.store.flat.device

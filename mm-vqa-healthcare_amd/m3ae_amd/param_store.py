@@ -3,6 +3,7 @@
 All trainable parameters live in ONE fp32 buffer ordered by optimizer group (m3ae_utils.py:135-204's six groups),
 each tensor 64-element aligned, with `param.data` and `param.grad` re-pointed to views of the flat buffers:
   * AdamW is one fused kernel launch per group segment (6 launches instead of ~670 per-tensor updates, SURVEY a11);
+    cfg["optim_type"] picks the rule -- AdamW, torch's Adam or SGD with momentum -- and with it the kernel (update_range);
   * the gradient all-reduce operates on contiguous byte ranges of the flat gradient buffer (m3ae_amd/ddp.py);
   * query/key/value weights of one attention block are adjacent, so the packed [3D, D] (or [2D, D]) projection the
     kernels want is a zero-copy view (PackedParam) while state_dict names stay the reference's;
@@ -19,6 +20,9 @@ import torch
 from . import _lib
 
 ALIGN = 64
+# default betas per rule: the reference's AdamW(betas=(0.9, 0.98)) (m3ae_utils.py:204) and torch.optim.Adam's own.  begin_update's
+# `betas` default IS the first object: left alone under optim_type "adam" it stands for the second.
+ADAMW_BETAS, ADAM_BETAS = (0.9, 0.98), (0.9, 0.999)
 
 NO_DECAY = ["bias", "LayerNorm.bias", "LayerNorm.weight", "norm.bias", "norm.weight", "norm1.bias", "norm1.weight",
             "norm2.bias", "norm2.weight"]
@@ -114,6 +118,9 @@ class ParamStore:
         # make their own stream wait for the others
         self.streams = set()
         self.hparams_fn = hparams_fn
+        from .config import optim_type
+        self.optim = optim_type(cfg)      # "adamw" | "adam" | "sgd": which fused kernel update_range launches
+        self.momentum = 0.9               # sgd (m3ae_utils.py:208); FlatSGD.step writes its param group's value here
         named = [(n, p) for n, p in module.named_parameters()]
         self.names = {id(p): n for n, p in named}
         # 0..5 optimizer groups; 6..11 = the same classes for parameters without gradient (frozen / never used), kept
@@ -251,17 +258,27 @@ class ParamStore:
         pct = 1 - (step - warm) / (max_steps - warm)
         return ((lr_init - lr_end) * pct ** power + lr_end) / lr_init
 
-    def begin_update(self, max_steps=None, grad_scale=1.0, lr_factor=None, group_lrs=None, betas=(0.9, 0.98), eps=1e-8,
+    def _alloc_state(self):
+        """The optimizer state of the rule, zero-filled on first use: two moments for adamw / adam; under sgd the momentum buffer
+        lives in `exp_avg` and `exp_avg_sq` is never allocated (one trainable-sized fp32 buffer less)."""
+        if self.exp_avg is None:
+            self.exp_avg = torch.zeros_like(self.grad)
+        if self.exp_avg_sq is None and self.optim != "sgd":
+            self.exp_avg_sq = torch.zeros_like(self.grad)
+
+    def begin_update(self, max_steps=None, grad_scale=1.0, lr_factor=None, group_lrs=None, betas=ADAMW_BETAS, eps=1e-8,
                      group_wds=None):
         """The host part of an optimizer step: per-group learning rates (built-in schedule unless given), step count.  Returns
-        the hyper-parameter record `adamw_range` takes; `adamw_step` = begin_update + adamw_range over the six segments, and
+        the hyper-parameter record `update_range` takes; `optimizer_step` = begin_update + update_range over the six segments, and
         ddp.FlatGradReducer(update_in_backward=True) applies the same record bucket by bucket while backward still runs.
+        `betas` left at its default means the rule's own: (0.9, 0.98) for adamw (the reference's), torch's (0.9, 0.999) for adam;
+        sgd reads neither betas nor eps and takes its momentum from `self.momentum`.
         With gradient_clip_val set, a step the non-finite guard skips on the device still consumes its step number here and its
         scheduler tick at the caller (as Lightning's scheduler ticks through a GradScaler skip): the count lives on the host,
         which is what keeps the step free of host syncs; grad_stats()["skipped_steps"] counts them."""
-        if self.exp_avg is None:
-            self.exp_avg = torch.zeros_like(self.grad)
-            self.exp_avg_sq = torch.zeros_like(self.grad)
+        self._alloc_state()
+        if betas is ADAMW_BETAS and self.optim == "adam":
+            betas = ADAM_BETAS
         hp = self.hparams_fn(self.cfg)
         if group_lrs is None:
             if lr_factor is None:
@@ -272,7 +289,7 @@ class ParamStore:
             group_wds = [wd for _, wd in hp]
         self.step_count += 1
         return dict(lrs=[float(x) for x in group_lrs], wds=[float(x) for x in group_wds], b1=float(betas[0]), b2=float(betas[1]),
-                    eps=float(eps), step=self.step_count, grad_scale=grad_scale)
+                    eps=float(eps), step=self.step_count, grad_scale=grad_scale, momentum=float(self.momentum))
 
     # A hipGraph-captured step replays with frozen kernel arguments: graph.GraphedStep makes the AdamW launches read this step's
     # learning rate and bias-corrected step size per group from `hyper_dev` ([6][2] fp32 on the device, uploaded before a replay).
@@ -289,39 +306,50 @@ class ParamStore:
         bc1, bc2 = 1.0 - hyper["b1"] ** t, 1.0 - hyper["b2"] ** t
         return [[lr, lr * math.sqrt(bc2) / bc1] for lr in hyper["lrs"]]
 
+    # ---- the three rules of cfg["optim_type"]: generic names dispatch, the adamw_* names are AdamW and nothing else -----------
+    def _adamw_only(self, name):
+        if self.optim != "adamw":
+            raise ValueError(f'ParamStore.{name} is the AdamW rule, but this store was built with optim_type="{self.optim}": call '
+                             f"{dict(adamw_range='update_range', adamw_apply='update_apply', adamw_step='optimizer_step')[name]}")
+
     @torch.no_grad()
-    def adamw_range(self, a, b, gi, hyper, clip=None):
-        """The fused AdamW kernel over elements [a, b) of the flat buffers (inside optimizer group `gi`), on the current stream.
-        `clip`: the device record of m3ae_clip_finalize; the launch is then m3ae_adamw_clip (skip / grad_scale * coef on the device)."""
+    def update_range(self, a, b, gi, hyper, clip=None):
+        """The rule's fused kernel (m3ae_adamw / m3ae_adam / m3ae_sgd) over elements [a, b) of the flat buffers (inside optimizer
+        group `gi`), on the current stream.  `clip`: the device record of m3ae_clip_finalize; the launch is then the rule's _clip
+        form (skip / grad_scale * coef on the device)."""
         if b <= a:
             return
         from . import ops as _ops
         es = 4
         sh = C.c_void_p(self.shadow.data_ptr() + a * 2) if self.shadow is not None else None
-        args = (C.c_void_p(self.flat.data_ptr() + a * es), C.c_void_p(self.grad.data_ptr() + a * es),
-                C.c_void_p(self.exp_avg.data_ptr() + a * es), C.c_void_p(self.exp_avg_sq.data_ptr() + a * es), sh, b - a,
-                hyper["lrs"][gi], hyper["b1"], hyper["b2"], hyper["eps"], hyper["wds"][gi], hyper["step"], hyper["grad_scale"],
-                self._hyper_dev_ptr(gi))
-        if clip is None:
-            _lib.check(_lib.lib().m3ae_adamw(*args, _ops._stream()), "m3ae_adamw")
+        p, g, m = (C.c_void_p(t.data_ptr() + a * es) for t in (self.flat, self.grad, self.exp_avg))
+        if self.optim == "sgd":
+            name = "m3ae_sgd"
+            args = (p, g, m, sh, b - a, hyper["lrs"][gi], hyper["momentum"], hyper["wds"][gi], hyper["grad_scale"])
         else:
-            _lib.check(_lib.lib().m3ae_adamw_clip(*args, C.c_void_p(clip.data_ptr()), _ops._stream()), "m3ae_adamw_clip")
+            name = "m3ae_" + self.optim
+            args = (p, g, m, C.c_void_p(self.exp_avg_sq.data_ptr() + a * es), sh, b - a, hyper["lrs"][gi], hyper["b1"], hyper["b2"],
+                    hyper["eps"], hyper["wds"][gi], hyper["step"], hyper["grad_scale"])
+            if self.optim == "adamw":
+                args += (self._hyper_dev_ptr(gi),)
+        if clip is not None:
+            name, args = name + "_clip", args + (C.c_void_p(clip.data_ptr()),)
+        _lib.check(getattr(_lib.lib(), name)(*args, _ops._stream()), name)
 
     @torch.no_grad()
-    def adamw_step(self, max_steps=None, grad_scale=1.0, lr_factor=None, group_lrs=None, betas=(0.9, 0.98), eps=1e-8,
-                   group_wds=None):
-        """One AdamW step over the six group segments (m3ae_utils.py:206; transformers-4.6.0 AdamW semantics,
-        betas (0.9, 0.98), eps 1e-8) + the polynomial-decay schedule, stepped per optimizer step.
-        `group_lrs` (one learning rate per group, e.g. an Optimizer's param_groups after its scheduler stepped) overrides
-        the built-in schedule."""
-        self.adamw_apply(self.begin_update(max_steps, grad_scale, lr_factor, group_lrs, betas, eps, group_wds))
+    def optimizer_step(self, max_steps=None, grad_scale=1.0, lr_factor=None, group_lrs=None, betas=ADAMW_BETAS, eps=1e-8,
+                       group_wds=None):
+        """One optimizer step of the rule over the six group segments + the polynomial-decay schedule, stepped per optimizer step.
+        `group_lrs` (one learning rate per group, e.g. an Optimizer's param_groups after its scheduler stepped) overrides the
+        built-in schedule.  Arguments as begin_update's."""
+        self.update_apply(self.begin_update(max_steps, grad_scale, lr_factor, group_lrs, betas, eps, group_wds))
 
     @torch.no_grad()
-    def adamw_apply(self, hyper):
+    def update_apply(self, hyper):
         """The device part of an optimizer step for a begin_update() record: six fused launches + the transposed weight copies.
         With cfg["gradient_clip_val"] > 0: the sum of squares of the gradient buffer per parameter (double), the one-workgroup
-        finalize with this step's grad_scale, then the six launches as m3ae_adamw_clip -- all on the current stream, the factor and
-        the skip flag never leave the device.  With the key at 0 this is the six m3ae_adamw launches and nothing is allocated."""
+        finalize with this step's grad_scale, then the six launches in their _clip form -- all on the current stream, the factor and
+        the skip flag never leave the device.  With the key at 0 this is the six plain launches and nothing is allocated."""
         clip = None
         max_norm = self.clip_val()
         if max_norm > 0:
@@ -330,8 +358,26 @@ class ParamStore:
             _gn.clip_finalize(self._sums.run(self.grad, _ops._stream()), hyper["grad_scale"], max_norm, clip, _ops._stream())
         for gi in range(6):
             a, b = self.segments[gi]
-            self.adamw_range(a, min(b, self.trainable_end), gi, hyper, clip)
+            self.update_range(a, min(b, self.trainable_end), gi, hyper, clip)
         self.sync_shadows(cast=False)
+
+    def adamw_range(self, a, b, gi, hyper, clip=None):
+        """update_range under optim_type "adamw" (m3ae_adamw / m3ae_adamw_clip); a ValueError under any other rule."""
+        self._adamw_only("adamw_range")
+        self.update_range(a, b, gi, hyper, clip)
+
+    def adamw_step(self, max_steps=None, grad_scale=1.0, lr_factor=None, group_lrs=None, betas=ADAMW_BETAS, eps=1e-8,
+                   group_wds=None):
+        """One AdamW step over the six group segments (m3ae_utils.py:206; transformers-4.6.0 AdamW semantics,
+        betas (0.9, 0.98), eps 1e-8) + the polynomial-decay schedule, stepped per optimizer step: optimizer_step under optim_type
+        "adamw"; a ValueError under any other rule."""
+        self._adamw_only("adamw_step")
+        self.optimizer_step(max_steps, grad_scale, lr_factor, group_lrs, betas, eps, group_wds)
+
+    def adamw_apply(self, hyper):
+        """update_apply under optim_type "adamw"; a ValueError under any other rule."""
+        self._adamw_only("adamw_apply")
+        self.update_apply(hyper)
 
     # ---- gradient norm, clipping, non-finite guard (csrc/gradnorm.hip) ---------------------------------------
     def clip_val(self):
@@ -379,9 +425,10 @@ class ParamStore:
         return math.sqrt(math.fsum(out.tolist()))
 
     def make_optimizer(self, max_steps=None):
-        """([optimizer], [{"scheduler", "interval": "step"}]) in the shape m3ae_utils.set_schedule returns (:240-242)."""
+        """([optimizer], [{"scheduler", "interval": "step"}]) in the shape m3ae_utils.set_schedule returns (:240-242); the
+        optimizer is the Flat* class of cfg["optim_type"] (m3ae_utils.py:203-210)."""
         max_steps = max_steps or self.cfg["max_steps"]
-        opt = FlatAdamW(self)
+        opt = {"adamw": FlatAdamW, "adam": FlatAdam, "sgd": FlatSGD}[self.optim](self)
         sched = torch.optim.lr_scheduler.LambdaLR(opt, lambda step: self.lr_factor(step, max_steps))
         return [opt], [{"scheduler": sched, "interval": "step"}]
 
@@ -389,18 +436,32 @@ class ParamStore:
         return [[n for n, _ in g] for g in self.groups[:6]]
 
 
-class FlatAdamW(torch.optim.Optimizer):
-    """torch.optim.Optimizer face of ParamStore's fused AdamW (the object m3ae_utils.set_schedule returns as
-    `optimizer`, m3ae_utils.py:135-206): six param groups -- {base, head x lr_multiplier_head, multi_modal x
-    lr_multiplier_multi_modal} x {weight decay, no decay} -- with the reference's lr / weight_decay / betas / eps per group,
-    so a Lightning-style loop (`optimizer.step(); scheduler.step(); optimizer.zero_grad()`) and LambdaLR schedulers work.
-    `step()` is one fused kernel launch per group over the flat buffers; the learning rates are read from
-    `param_groups[i]["lr"]` (whatever a scheduler wrote there).  `state_dict()` / `load_state_dict()` round-trip the
-    moments (per parameter, torch's layout) and the step count.
-    With `gradient_clip_val` in the store's config, `step()` clips by global norm and skips a non-finite step on the device
-    (ParamStore.adamw_apply); a skipped step still advances the step count, and the caller's scheduler ticks as usual."""
+def state_dict_rule(state_dict):
+    """Which rule wrote an optimizer state dict: "sgd" (torch.optim.SGD, FlatSGD: a `momentum` group key or momentum buffers),
+    "adam" (torch.optim.Adam, FlatAdam: torch's `amsgrad` group key, decay not decoupled) or "adamw" (FlatAdamW, HF AdamW: betas
+    without `amsgrad`).  Adam's and AdamW's per-parameter state look alike; the group keys tell them apart."""
+    groups = state_dict["param_groups"]
+    first = next(iter(state_dict["state"].values()), {})
+    if any("momentum" in g for g in groups) or "momentum_buffer" in first:
+        return "sgd"
+    if any("amsgrad" in g and not g.get("decoupled_weight_decay", False) for g in groups):
+        return "adam"
+    return "adamw"
 
-    def __init__(self, store, grad_scale=1.0):
+
+class _FlatOptimizer(torch.optim.Optimizer):
+    """What the three Optimizer faces of ParamStore share: six param groups -- {base, head x lr_multiplier_head, multi_modal x
+    lr_multiplier_multi_modal} x {weight decay, no decay} -- with the reference's lr / weight_decay per group, a `step()` that is
+    one fused launch per group with the learning rates read from `param_groups[i]["lr"]` (whatever a scheduler wrote there), and
+    `state_dict()` / `load_state_dict()` in torch's per-parameter layout over views of the flat state buffers."""
+    RULE = None
+    STATE = ()            # (torch's state key, ParamStore attribute) per flat state buffer
+    HAS_STEP = True       # torch's per-parameter `step`
+    GROUP_KEYS = ("lr", "weight_decay", "initial_lr")
+
+    def __init__(self, store, defaults, grad_scale=1.0):
+        if store.optim != self.RULE:
+            raise ValueError(f'{type(self).__name__} needs a store built with optim_type="{self.RULE}", got "{store.optim}"')
         self.store = store
         self.grad_scale = grad_scale
         groups = []
@@ -409,19 +470,23 @@ class FlatAdamW(torch.optim.Optimizer):
             if not params:   # torch rejects empty groups: keep the slot with a placeholder so that indices stay group ids
                 params = [torch.nn.Parameter(torch.zeros(0, device=store.device), requires_grad=False)]
             groups.append(dict(params=params, lr=lr, weight_decay=wd, m3ae_group=gi))
-        super().__init__(groups, dict(lr=store.cfg["learning_rate"], betas=(0.9, 0.98), eps=1e-8, weight_decay=0.0))
+        super().__init__(groups, defaults)
 
     def _bind_state(self):
         st = self.store
-        if st.exp_avg is None:
-            st.exp_avg = torch.zeros_like(st.grad)
-            st.exp_avg_sq = torch.zeros_like(st.grad)
+        st._alloc_state()
         for gi in range(6):
             for _, p in st.groups[gi]:
                 o = st.offset[id(p)]
-                self.state[p] = dict(step=torch.tensor(float(st.step_count)),
-                                     exp_avg=st.exp_avg[o:o + p.numel()].view(p.shape),
-                                     exp_avg_sq=st.exp_avg_sq[o:o + p.numel()].view(p.shape))
+                d = dict(step=torch.tensor(float(st.step_count))) if self.HAS_STEP else {}
+                for key, attr in self.STATE:
+                    d[key] = getattr(st, attr)[o:o + p.numel()].view(p.shape)
+                self.state[p] = d
+
+    def _hyper(self, g):
+        """Keyword arguments of ParamStore.optimizer_step from the param groups (by m3ae_group)."""
+        return dict(group_lrs=[g[i]["lr"] for i in range(6)], group_wds=[g[i]["weight_decay"] for i in range(6)],
+                    grad_scale=self.grad_scale)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -429,9 +494,7 @@ class FlatAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        g = {pg["m3ae_group"]: pg for pg in self.param_groups}
-        self.store.adamw_step(group_lrs=[g[i]["lr"] for i in range(6)], group_wds=[g[i]["weight_decay"] for i in range(6)],
-                              betas=g[0]["betas"], eps=g[0]["eps"], grad_scale=self.grad_scale)
+        self.store.optimizer_step(**self._hyper({pg["m3ae_group"]: pg for pg in self.param_groups}))
         return loss
 
     def zero_grad(self, set_to_none=False):
@@ -447,22 +510,96 @@ class FlatAdamW(torch.optim.Optimizer):
         mine = [p for g in self.param_groups for p in g["params"]]
         if len(ids) != len(mine):
             raise ValueError("optimizer state_dict does not match this model's parameter groups")
-        if st.exp_avg is None:
-            st.exp_avg = torch.zeros_like(st.grad)
-            st.exp_avg_sq = torch.zeros_like(st.grad)
+        self._check_rule(state_dict, state_dict_rule(state_dict))     # state of another rule: ValueError
+        st._alloc_state()
         step = None
         for i, p in zip(ids, mine):
             s = state_dict["state"].get(i)
             if s is None or id(p) not in st.offset or p.numel() == 0:
                 continue
             o = st.offset[id(p)]
-            st.exp_avg[o:o + p.numel()].view(p.shape).copy_(s["exp_avg"])
-            st.exp_avg_sq[o:o + p.numel()].view(p.shape).copy_(s["exp_avg_sq"])
-            step = int(s["step"]) if step is None else step
+            for key, attr in self.STATE:
+                getattr(st, attr)[o:o + p.numel()].view(p.shape).copy_(s[key])
+            if self.HAS_STEP:
+                step = int(s["step"]) if step is None else step
         if step is not None:
             st.step_count = step
         for pg, sg in zip(self.param_groups, state_dict["param_groups"]):
-            for k in ("lr", "weight_decay", "betas", "eps", "initial_lr"):
+            for k in self.GROUP_KEYS:
                 if k in sg:
                     pg[k] = sg[k]
         self._bind_state()
+
+    def _check_rule(self, state_dict, rule):
+        if rule != self.RULE:
+            raise ValueError(f'optimizer state_dict was written by the "{rule}" rule, this optimizer is optim_type="{self.RULE}"')
+
+
+class FlatAdamW(_FlatOptimizer):
+    """torch.optim.Optimizer face of ParamStore's fused AdamW (the object m3ae_utils.set_schedule returns as
+    `optimizer`, m3ae_utils.py:135-206): six param groups -- {base, head x lr_multiplier_head, multi_modal x
+    lr_multiplier_multi_modal} x {weight decay, no decay} -- with the reference's lr / weight_decay / betas / eps per group,
+    so a Lightning-style loop (`optimizer.step(); scheduler.step(); optimizer.zero_grad()`) and LambdaLR schedulers work.
+    `step()` is one fused kernel launch per group over the flat buffers; the learning rates are read from
+    `param_groups[i]["lr"]` (whatever a scheduler wrote there).  `state_dict()` / `load_state_dict()` round-trip the
+    moments (per parameter, torch's layout) and the step count.
+    With `gradient_clip_val` in the store's config, `step()` clips by global norm and skips a non-finite step on the device
+    (ParamStore.update_apply); a skipped step still advances the step count, and the caller's scheduler ticks as usual."""
+    RULE = "adamw"
+    STATE = (("exp_avg", "exp_avg"), ("exp_avg_sq", "exp_avg_sq"))
+    GROUP_KEYS = ("lr", "weight_decay", "betas", "eps", "initial_lr")
+
+    def __init__(self, store, grad_scale=1.0):
+        super().__init__(store, dict(lr=store.cfg["learning_rate"], betas=ADAMW_BETAS, eps=1e-8, weight_decay=0.0), grad_scale)
+
+    def _hyper(self, g):
+        return dict(super()._hyper(g), betas=g[0]["betas"], eps=g[0]["eps"])
+
+    def _check_rule(self, state_dict, rule):
+        # (a torch.optim.AdamW dict carries `amsgrad` like Adam's: only a dict FlatAdam wrote is known to be the other rule)
+        if rule == "sgd" or any(g.get("m3ae_rule", "adamw") != "adamw" for g in state_dict["param_groups"]):
+            raise ValueError(f'optimizer state_dict was written by the "{rule}" rule, this optimizer is optim_type="adamw"')
+
+
+class FlatAdam(FlatAdamW):
+    """The same face over the fused torch.optim.Adam rule (optim_type "adam", m3ae_utils.py:205-206): torch's defaults, betas
+    (0.9, 0.999), eps 1e-8, coupled weight decay, no amsgrad.  param_groups carry every key of torch.optim.Adam's defaults, the
+    state is torch's (`step`, `exp_avg`, `exp_avg_sq`): a torch.optim.Adam state dict over the same groups loads here and this
+    one's loads there.  The moments of FlatAdamW mean something else (decoupled decay, another bias correction): its state dicts
+    are refused."""
+    RULE = "adam"
+
+    def __init__(self, store, grad_scale=1.0):
+        d = dict(torch.optim.Adam([torch.zeros(1)], lr=store.cfg["learning_rate"]).defaults)   # torch's keys, whatever its version
+        d.update(betas=ADAM_BETAS, eps=1e-8, weight_decay=0.0, amsgrad=False, m3ae_rule="adam")
+        _FlatOptimizer.__init__(self, store, d, grad_scale)
+
+    def _check_rule(self, state_dict, rule):
+        groups = state_dict["param_groups"]
+        if rule != "adam" or any(g.get("m3ae_rule", "adam") != "adam" for g in groups):
+            raise ValueError('optimizer state_dict was written by an AdamW rule (decoupled decay), this optimizer is optim_type="adam"')
+        if any(g.get("amsgrad") for g in groups):
+            raise ValueError("optim_type adam has no amsgrad variant")
+
+
+class FlatSGD(_FlatOptimizer):
+    """The same face over the fused torch.optim.SGD rule (optim_type "sgd", m3ae_utils.py:207-208): momentum 0.9, dampening 0, no
+    Nesterov, coupled weight decay.  param_groups carry every key of torch.optim.SGD's defaults, the state is torch's
+    (`momentum_buffer`, no step): a torch.optim.SGD state dict over the same groups loads here and this one's loads there.  The
+    buffer is the store's `exp_avg`; `exp_avg_sq` is never allocated."""
+    RULE = "sgd"
+    STATE = (("momentum_buffer", "exp_avg"),)
+    HAS_STEP = False
+    GROUP_KEYS = ("lr", "weight_decay", "momentum", "initial_lr")
+
+    def __init__(self, store, grad_scale=1.0):
+        d = dict(torch.optim.SGD([torch.zeros(1)], lr=store.cfg["learning_rate"], momentum=store.momentum).defaults)
+        d.update(momentum=store.momentum, dampening=0, nesterov=False, weight_decay=0.0, m3ae_rule="sgd")
+        super().__init__(store, d, grad_scale)
+
+    def step(self, closure=None):
+        g0 = self.param_groups[0]
+        if any(pg["momentum"] != g0["momentum"] or pg["dampening"] != 0 or pg["nesterov"] for pg in self.param_groups):
+            raise ValueError("optim_type sgd: one momentum for all groups, dampening 0, no Nesterov")
+        self.store.momentum = float(g0["momentum"])
+        return super().step(closure)

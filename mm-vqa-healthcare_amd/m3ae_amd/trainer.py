@@ -11,9 +11,10 @@ arithmetic around `training_step`:
   the loss of every micro-batch is divided by `grad_steps` (Lightning's `accumulate_grad_batches`), gradients add up
   in place in the flat buffer, the gradient all-reduce runs on the LAST micro-batch only (ddp.FlatGradReducer);
 * `max_steps` optimizer steps, or `max_epoch` epochs when `max_steps` is None / -1 (main.py:51-52);
-* the 6-group AdamW + polynomial schedule stepped once per optimizer step (m3ae_utils.py:112-242, ParamStore);
+* the 6-group optimizer of `optim_type` -- AdamW, Adam or SGD with momentum (m3ae_utils.py:203-210) -- + polynomial schedule
+  stepped once per optimizer step (m3ae_utils.py:112-242, ParamStore.optimizer_step through the Flat* optimizer);
 * `gradient_clip_val` (Lightning's Trainer flag; 0 = off): clipping by global norm and the non-finite step guard happen inside
-  `optimizer.step()`, after the gradient all-reduce, once per accumulation window (ParamStore.adamw_apply); the periodic log line
+  `optimizer.step()`, after the gradient all-reduce, once per accumulation window (ParamStore.update_apply); the periodic log line
   then also shows the gradient norm, the factor applied and the number of skipped steps;
 * validation every `val_check_interval` of an epoch with the VQA score `val/the_metric` (my_metrics.py:58-83), best +
   last checkpoints (`ModelCheckpoint(save_top_k=1, monitor="val/the_metric", mode="max", save_last=True)`,
@@ -168,9 +169,13 @@ class Trainer:
         self.global_step, self.epoch = ck.get("global_step", 0), ck.get("epoch", 0)
         of = ck.get("optimizer_flat")   # checkpoints written before the Optimizer face existed
         if ck.get("optimizer_states"):
-            self.optimizer.load_state_dict(ck["optimizer_states"][0])
+            self.optimizer.load_state_dict(ck["optimizer_states"][0])    # state of another optim_type: ValueError
             self.scheduler.load_state_dict(ck["lr_schedulers"][0])
+            if self.store.optim == "sgd":    # torch's SGD state carries no step count
+                self.store.step_count = self.global_step
         elif of is not None and of["exp_avg"] is not None:
+            if self.store.optim != "adamw":
+                raise ValueError(f'{path}: AdamW moments (optimizer_flat) cannot resume a run with optim_type="{self.store.optim}"')
             self.store.exp_avg = of["exp_avg"].to(self.device)
             self.store.exp_avg_sq = of["exp_avg_sq"].to(self.device)
             self.store.step_count = of["step_count"]

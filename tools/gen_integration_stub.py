@@ -9,7 +9,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mm-vqa-healthcare_amd"))
 BEGIN, END = "<!-- BEGIN GENERATED (tools/gen_integration_stub.py) -->", "<!-- END GENERATED -->"
-_NAMES = {C.c_int64: "C.c_int64", C.c_int32: "C.c_int32", C.c_float: "C.c_float", C.c_void_p: "C.c_void_p",
+_NAMES = {C.c_double: "C.c_double", C.c_int64: "C.c_int64", C.c_int32: "C.c_int32", C.c_float: "C.c_float", C.c_void_p: "C.c_void_p",
           C.c_uint64: "C.c_uint64"}
 
 
@@ -37,6 +37,7 @@ SAMPLES_ENTRIES = ("m3ae_expand_samples", "m3ae_segment_sum_rows")
 MIXED_LN_ENTRIES = ("m3ae_layernorm_fwd_mixed", "m3ae_layernorm_bwd_mixed", "m3ae_layernorm_bwd_mixed_det")
 TILED_ENTRIES = ("m3ae_tile_bf16_batched",)
 CLIP_ENTRIES = ("m3ae_sumsq_workspace_bytes", "m3ae_sumsq_segments", "m3ae_clip_finalize", "m3ae_adamw_clip")
+OPTIM_ENTRIES = ("m3ae_adam", "m3ae_adam_clip", "m3ae_sgd", "m3ae_sgd_clip")
 ROWS_ENTRIES = ("m3ae_gemm_rows", "m3ae_attn_fwd_rows", "m3ae_attn_bwd_rows", "m3ae_layernorm_bwd_drop_rows", "m3ae_dropout_rows")
 
 
@@ -107,6 +108,11 @@ def block():
                f"{_lib.CLIP_COEF}, {_lib.CLIP_SKIP}, {_lib.CLIP_STEPS}, {_lib.CLIP_CLIPPED_STEPS}, {_lib.CLIP_SKIPPED_STEPS}, "
                f"{_lib.CLIP_RECORD_WORDS}     # 32-bit words of the record")
     for name in CLIP_ENTRIES:
+        res, args = _lib._SIGS[name]
+        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
+    out.append("")
+    out.append("# optim_type adam / sgd (ABI 4, additive): torch.optim.Adam and SGD with momentum over a flat segment; _clip = + the record")
+    for name in OPTIM_ENTRIES:
         res, args = _lib._SIGS[name]
         out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
     out.append("```")
