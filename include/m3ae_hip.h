@@ -376,6 +376,9 @@ int m3ae_roberta_embed_bwd(const int64_t* ids, const void* d_out, float* d_word,
 /* ------------------------------------------------------------------------------------------------------------
  * ViT token assembly (clip_model.py:94-99): im2col of non-overlapping patches (column order c, ph, pw = the
  * row-major flattening of conv1.weight[width, 3, P, P]) and [cls | patches] + positional_embedding.
+ * Pointers need the alignment of their element type only.  m3ae_patchify (bf16 output, P % 8 == 0) and m3ae_vit_tokens_fwd
+ * (bf16, D % 8 == 0) move 16 bytes per lane when every pointer they would access that way -- img and out; patch, cls, pos and
+ * out -- is 16-byte aligned, and take the element-wise kernel otherwise: same bits either way.
  */
 int m3ae_patchify(const float* img, void* out, int64_t B, int64_t R, int64_t P, int dtype, void* stream);
 /* Input pipeline tail (transforms/transform.py:60-67 ToTensor + Normalize, after the host-side PIL resize / centre crop):
@@ -565,7 +568,9 @@ int m3ae_add(const void* a, const void* b, void* out, int64_t n, int dtype, void
 int m3ae_act_fwd(const void* x, void* y, int64_t n, int act, int dtype, void* stream);
 int m3ae_act_bwd(const void* dy, const void* x_pre, void* dx, int64_t n, int act, int dtype, void* stream);
 /* rows gather / scatter-add along dim 0 of a [R, D] matrix: out[i] = in[idx[i]] ; d_in[idx[i]] += d_out[i]
- * (MIM masking, m3ae_module.py:170; prediction_heads.py:68). */
+ * (MIM masking, m3ae_module.py:170; prediction_heads.py:68).  idx may repeat rows in m3ae_gather_rows; m3ae_scatter_add_rows is
+ * a plain read-modify-write and requires the entries of idx to be DISTINCT (a permutation slice): with a repeated entry
+ * contributions are lost. */
 int m3ae_gather_rows(const void* in, const int64_t* idx, void* out, int64_t n_out, int64_t D, int dtype,
                      void* stream);
 int m3ae_scatter_add_rows(const void* d_out, const int64_t* idx, void* d_in, int64_t n_out, int64_t D, int dtype,

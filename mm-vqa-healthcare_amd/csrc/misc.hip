@@ -782,7 +782,8 @@ extern "C" int m3ae_patchify(const float* img, void* out, int64_t B, int64_t R, 
     if (!img || !out || B <= 0 || R <= 0 || P <= 0 || R % P) return M3AE_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = B * (R / P) * (R / P) * 3 * P * P;
-    if (dtype == M3AE_BF16 && P % 8 == 0 && total / 8 < (int64_t)1 << 31) {
+    // the x8 form reads img and writes out 16 bytes at a time: both pointers 16-byte aligned, else the scalar form
+    if (dtype == M3AE_BF16 && P % 8 == 0 && total / 8 < (int64_t)1 << 31 && ((((uintptr_t)img) | ((uintptr_t)out)) & 15) == 0) {
         hipLaunchKernelGGL(patchify8_bf16_kernel, dim3(ew_grid(total / 8)), dim3(EW_BLOCK), 0, s, img, (bf16_t*)out,
                            (uint32_t)(total / 8), (uint32_t)R, (uint32_t)P, (uint32_t)(R / P));
         return hip_launch_status();
@@ -802,7 +803,9 @@ extern "C" int m3ae_vit_tokens_fwd(const void* patch, const float* cls, const fl
                                    int64_t G, int64_t D, int dtype, void* stream) {
     if (!patch || !cls || !pos || !out) return M3AE_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == M3AE_BF16 && D % 8 == 0 && B * (G + 1) * D / 8 < (int64_t)1 << 31) {
+    // the x8 form moves patch, cls, pos and out 16 bytes at a time: all four 16-byte aligned, else the scalar form
+    if (dtype == M3AE_BF16 && D % 8 == 0 && B * (G + 1) * D / 8 < (int64_t)1 << 31 &&
+        ((((uintptr_t)patch) | ((uintptr_t)cls) | ((uintptr_t)pos) | ((uintptr_t)out)) & 15) == 0) {
         const int64_t n8 = B * (G + 1) * D / 8;
         hipLaunchKernelGGL(vit_tokens_fwd8_bf16_kernel, dim3(ew_grid(n8)), dim3(EW_BLOCK), 0, s, (const bf16_t*)patch, cls,
                            pos, (bf16_t*)out, (uint32_t)n8, (uint32_t)G, (uint32_t)(D / 8));

@@ -260,7 +260,8 @@ class M3AETransformerSS(_Base):
         ids_restore, keep_rows, mask = ops.mask_ranks(noise, len_keep)
         pos = self.vision_encoder.visual.positional_embedding
         xp = x + pos.to(x.dtype)  # x + pos, cls row included (m3ae_module.py:169,180); pretrain-only glue
-        x_masked = ops.gather_rows(xp, keep_rows).view(B, len_keep + 1, D)
+        # keep_rows: per sample the class row and len_keep patches of distinct rank, a slice of a permutation of the token rows
+        x_masked = ops.gather_rows(xp, keep_rows, unique=True).view(B, len_keep + 1, D)
         return x_masked, mask, ids_restore
 
     def patchify(self, imgs):

@@ -94,7 +94,8 @@ class MIMHead(nn.Module):
         # rows of [x[:, 1:], mask tokens] un-shuffled by ids_restore (prediction_heads.py:65-68), then cls prepended
         src = torch.cat([x[:, 1:, :], self.mask_token.to(x.dtype).expand(B, n_mask, dh)], dim=1)  # [B, L, dh]
         flat_idx = (ids_restore + torch.arange(B, device=x.device).view(B, 1) * L).reshape(-1)
-        x_ = ops.gather_rows(src, flat_idx).view(B, L, dh)
+        # ids_restore holds the ranks 0 .. L - 1 of every sample once each: flat_idx is a permutation of the B * L rows
+        x_ = ops.gather_rows(src, flat_idx, unique=True).view(B, L, dh)
         x = torch.cat([x[:, :1, :], x_], dim=1) + self.decoder_pos_embed.to(x.dtype)
         x = self.decoder(x.contiguous())
         x = ops.layer_norm(x, self.decoder_norm.weight, self.decoder_norm.bias, self.decoder_norm.eps)

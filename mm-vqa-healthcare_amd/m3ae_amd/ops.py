@@ -1737,8 +1737,12 @@ def vocab_linear(x, weight, bias):
 # row gather (MIM masking) -- differentiable in the source
 # ----------------------------------------------------------------------------------------------------------
 class GatherRowsFn(Function):
+    """out[i] = src[idx[i]].  unique: the caller guarantees that idx holds no row twice (a permutation slice); the backward is then
+    m3ae_scatter_add_rows, a plain read-modify-write per row.  Otherwise rows may repeat and the backward is torch's index_add_ in
+    fp32, cast back to the gradient's dtype (fp32 atomics: no ordered form)."""
+
     @staticmethod
-    def forward(ctx, src, idx):
+    def forward(ctx, src, idx, unique):
         idx = idx.contiguous()
         s2 = src.contiguous().view(-1, src.shape[-1])
         out = torch.empty((idx.numel(), s2.shape[1]), dtype=src.dtype, device=src.device)
@@ -1746,20 +1750,26 @@ class GatherRowsFn(Function):
               "m3ae_gather_rows")
         ctx.save_for_backward(idx)
         ctx.shape = src.shape
+        ctx.unique = bool(unique)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         (idx,) = ctx.saved_tensors
         d = dout.contiguous()
+        if not ctx.unique:
+            _no_ordered_form("the gradient of ops.gather_rows with rows that may repeat (torch index_add_; unique=True for a permutation)")
+            dsrc = torch.zeros((math.prod(ctx.shape[:-1]), ctx.shape[-1]), dtype=torch.float32, device=d.device)
+            dsrc.index_add_(0, idx.view(-1), d.float())
+            return dsrc.to(d.dtype).view(ctx.shape), None, None
         dsrc = torch.zeros(ctx.shape, dtype=d.dtype, device=d.device)
         check(_lib.lib().m3ae_scatter_add_rows(_p(d), _p(idx), _p(dsrc), idx.numel(), d.shape[1], _dt(d), _stream()),
               "m3ae_scatter_add_rows")
-        return dsrc, None
+        return dsrc, None, None
 
 
-def gather_rows(src, flat_idx):
-    return GatherRowsFn.apply(src, flat_idx)
+def gather_rows(src, flat_idx, unique=False):
+    return GatherRowsFn.apply(src, flat_idx, unique)
 
 
 # ----------------------------------------------------------------------------------------------------------
