@@ -14,6 +14,7 @@
 // (the LDS-DMA destination is lane-linear) with the same involution on the read, so ds_read_b128 / tr reads are
 // bank-conflict free.  Workgroup ids are remapped so that each XCD (own L2) walks a contiguous range of tiles.
 #include "gemm_nt_common.h"
+#include "pp_ring.h"
 #include "launch.h"
 #include <stdlib.h>
 
@@ -286,17 +287,14 @@ static int launch_nt_t(const MfmaArgs& a, hipStream_t s) {
 
 // ---------------------------------------------------------------------------------------------------------
 // NT "ping-pong" kernel: 256 x 256 tile, 8 waves (2 x 4, 128 x 64 each), 32-deep reduction chunks in a 4-slot LDS
-// ring (128 KiB).  Each chunk is consumed in TWO phases (rows 0-63 / 64-127 of the wave's sub-tile: 16 MFMAs each);
-// a phase is  [LDS fragment reads + 2 LDS-DMA issues] s_barrier [16 MFMAs] s_barrier.  The two wave rows (wr = 0 / 1:
-// one wave of each per SIMD) run staggered by one barrier, so on every SIMD one wave is in its MFMA cluster while the
-// other fetches fragments and issues DMA -- the MFMA pipe never waits for LDS.
-//
-// Ring schedule (phase p = 2c / 2c+1 works on chunk c in slot c & 3; loads are issued in the order B(0) A(0) B(1) A(1) ...):
-//   phase 2c   issues B(c+3) into slot (c-1)&3 -- B(c-1) was last read in phase 2c-2 (two phases earlier: every wave's
-//              reads were retired by an lgkmcnt(0) at least two barriers ago, stagger included);
-//   phase 2c+1 issues A(c+3)                   -- A(c-1) was last read in phase 2c-1;
-//   phase 2c+1 waits (counted vmcnt: the 8 loads of chunks c+2, c+3 stay in flight) for chunk c+1 BEFORE its first
-//              barrier; chunk c+1 is first read in phase 2c+2, i.e. after a barrier every wave passed post-wait.
+// ring (128 KiB): the two-phase schedule of pp_ring.h (ring safety and the counted-wait rule there) -- rows 0-63 / 64-127 of the
+// wave's sub-tile, 16 MFMAs per phase, the two wave rows (wr = 0 / 1: one wave of each per SIMD) staggered by one barrier, 2 + 2
+// LDS-DMA pieces per wave and chunk.  The loop is written out in each of the three kernels that run this schedule (this one,
+// gemm_tn_pp_kernel, xg_kernel with NLOAD == 0).  ONE template over staging / fragment / MFMA callables was built and measured
+// (profiles/r17_pp_ring_ab.log): hipcc no longer shared the row clamps and row products of the three prologue chunks (+120..200
+// instructions per tile) and K = 192 here and the 3072 x 768 wgrad ran 1-2 % slower.  Those builds also carried the slower form of
+// the in-flight rule (pp_ring.h, pp_inflight_next), which alone costs the wgrad kernel 2 %: the template was not measured again
+// without it.
 // The B operand of a chunk comes from the tiled copy of the weight under M3AE_GEMM_B_TILED (one lane-linear 1-KiB block per piece).
 // ---------------------------------------------------------------------------------------------------------
 template <int EPI>
@@ -321,6 +319,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(MfmaArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
+    constexpr int DEPTH = 3, G = 4;   // chunks requested ahead; LDS-DMA pieces per wave and chunk (pp_ring.h)
     const int nc = (int)(a.K / CK);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -330,9 +329,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(MfmaArgs a) {
             nt_stage<CK, 2, NW>(a.A, a.lda, m0, a.M, (int64_t)c * CK, smem + c * SLOT, wave, lane);
         }
     }
-    if (nc >= 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (nc == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm_chunks<G, DEPTH - 1>(pp_inflight_prologue<DEPTH>(nc));
     PP_FENCE();
     __builtin_amdgcn_s_barrier();  // chunk 0 is in LDS for every wave
     PP_FENCE();
@@ -374,12 +371,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(MfmaArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) af[i] = nt_frag<CK>(At, wr * 128 + 64 + i * 16 + frow, fchunk);
         if (more) nt_stage<CK, 2, NW>(a.A, a.lda, m0, a.M, (int64_t)(c + 3) * CK, nxt, wave, lane);
-        {
-            const int rem = nc - 1 - c;  // chunks after this one; chunk c + 1 must have landed before the next phase
-            if (rem >= 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else if (rem == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        wait_vm_chunks<G, DEPTH - 1>(pp_inflight_next<DEPTH>(nc, c));   // chunk c + 1 must have landed before the next phase
         PP_FENCE();
         __builtin_amdgcn_s_barrier();
         PP_FENCE();
@@ -398,7 +390,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(MfmaArgs a) {
         PP_FENCE();
     }
     if (wr == 0) { __builtin_amdgcn_s_barrier(); PP_FENCE(); }  // re-align: every wave has executed 4 nc + 2 barriers
-    // all fragment reads are retired and no DMA is outstanding (vmcnt(0) in the last odd phase): the ring is free
+    // all fragment reads are retired and no DMA is outstanding: the ring is free (pp_ring.h)
 
     if (a.rows_epi) {
         if (a.c_f32) epilogue_rows<float, EPI, 8>(a, smem, wave, lane, m0 + wr * 128, n0 + wc * 64, acc);
@@ -527,21 +519,22 @@ static int launch_nt(const m3ae_gemm_desc& d, hipStream_t s, DropRows rows) {
     const bool has_act = d.act != M3AE_ACT_NONE, has_dact = d.dact_aux != nullptr;
     if (!has_act && !has_dact && !d.preact) return launch_nt_v<EPI_PLAIN>(a, s);
     if (!has_dact && d.act == M3AE_ACT_RELU) return launch_nt_v<EPI_RELU>(a, s);                       // dropout allowed
-    if (!has_act && has_dact && d.dact == M3AE_ACT_MULAUX) return launch_nt_v<EPI_DMUL>(a, s);          // dropout allowed
+    // (the derivative classes store no preact: a descriptor that asks for one takes EPI_ANY)
+    if (!has_act && has_dact && !d.preact && d.dact == M3AE_ACT_MULAUX) return launch_nt_v<EPI_DMUL>(a, s);   // dropout allowed
     if (a.has_drop) return launch_nt_v<EPI_ANY>(a, s);
     if (!has_dact && d.act == M3AE_ACT_GELU) return launch_nt_v<EPI_GELU>(a, s);
     if (!has_dact && d.act == M3AE_ACT_QUICKGELU) return launch_nt_v<EPI_QGELU>(a, s);
-    if (!has_act && d.dact == M3AE_ACT_GELU) return launch_nt_v<EPI_DGELU>(a, s);
-    if (!has_act && d.dact == M3AE_ACT_QUICKGELU) return launch_nt_v<EPI_DQGELU>(a, s);
+    if (!has_act && !d.preact && d.dact == M3AE_ACT_GELU) return launch_nt_v<EPI_DGELU>(a, s);
+    if (!has_act && !d.preact && d.dact == M3AE_ACT_QUICKGELU) return launch_nt_v<EPI_DQGELU>(a, s);
     return launch_nt_v<EPI_ANY>(a, s);
 }
 
 
 // ---------------------------------------------------------------------------------------------------------
-// TN "ping-pong" kernel (wgrad): the structure of gemm_nt_pp_kernel with transposing fragment reads.  256 x 256 output
-// tile, 8 waves (2 x 4, 128 x 64 each), 32 reduction rows per chunk ([32][256] bf16 image of each operand, 16 KiB) in a
-// 4-slot ring; two phases per chunk (output rows 0-63 / 64-127 of the wave), the two wave rows staggered by one
-// barrier; B(c+3) / A(c+3) issued in phases 2c / 2c+1, counted vmcnt(8) in the odd phase.  Split over the reduction
+// TN "ping-pong" kernel (wgrad): the structure of gemm_nt_pp_kernel with transposing fragment reads -- the two-phase schedule of
+// pp_ring.h (ring safety and the counted-wait rule there), written out.  256 x 256 output tile, 8 waves (2 x 4, 128 x 64 each),
+// 32 reduction rows per chunk ([32][256] bf16 image of each operand, 16 KiB) in a 4-slot ring; two phases per chunk (output rows
+// 0-63 / 64-127 of the wave), the two wave rows staggered by one barrier.  Split over the reduction
 // with fp32 atomics; the bias gradient rides on a ones-fragment MFMA in the first column tile's waves.
 // Ring depth: a 5-slot ring (160 KiB, three chunks in flight behind the one awaited) measured the same as 4 slots on every
 // wgrad shape of the step (r02, profiles/r02_tn_ring_depth.log): the kernel is not waiting on load latency.  An L2 prefetch
@@ -578,6 +571,7 @@ extern "C" int m3ae_tn_trace_dump(uint64_t* out) {
 template <bool DET>   // DET: partial planes instead of atomics, see gemm_tn_bf16_kernel
 __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(MfmaArgs a) {
     constexpr int CK = 32, NW = 8, A_BYTES = 256 * CK * 2, SLOT = 2 * A_BYTES;
+    constexpr int DEPTH = 3, G = 4;   // chunks requested ahead; LDS-DMA pieces per wave and chunk (pp_ring.h)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -615,9 +609,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(MfmaArgs a) {
             tn_stage<256, 2, NW>(a.A, a.lda, r0, r_end, m0, smem + c * SLOT, wave, lane);
         }
     }
-    if (nc >= 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (nc == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm_chunks<G, DEPTH - 1>(pp_inflight_prologue<DEPTH>(nc));
     PP_FENCE();
     __builtin_amdgcn_s_barrier();
     PP_FENCE();
@@ -674,12 +666,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(MfmaArgs a) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) af[i] = tn_frag<256>(At, 0, wr * 128 + 64 + i * 16, lane);
         if (more) tn_stage<256, 2, NW>(a.A, a.lda, r3, r_end, m0, nxt, wave, lane);
-        {
-            const int rem = nc - 1 - c;
-            if (rem >= 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else if (rem == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        wait_vm_chunks<G, DEPTH - 1>(pp_inflight_next<DEPTH>(nc, c));   // chunk c + 1 must have landed before the next phase
         PP_FENCE();
         TN_STAMP(5);
         __builtin_amdgcn_s_barrier();
@@ -706,7 +693,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(MfmaArgs a) {
         __builtin_amdgcn_s_barrier();
         PP_FENCE();
     }
-    if (wr == 0) { __builtin_amdgcn_s_barrier(); PP_FENCE(); }
+    if (wr == 0) { __builtin_amdgcn_s_barrier(); PP_FENCE(); }   // re-align; the ring is free (pp_ring.h)
 
     if constexpr (DET) {
         if (do_rowsum && (lane & 15) == 0) {

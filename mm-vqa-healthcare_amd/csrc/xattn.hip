@@ -116,15 +116,15 @@ template <int WN, class RowPtr> DEVINL void slab_store_bf16(const char* slab, in
 // with it (2200 clk against 2 x 384 of MFMA).  A loader's stalls cost nothing.
 //   compute phase c:  [fragment reads of chunk c; lgkmcnt(0)]  barrier  [MI x NJ MFMAs]  barrier
 //   loader  phase c:  [request chunk c + NSLOT - 1 into the slot of chunk c - 1; counted vmcnt: chunk c + 1 landed]  barrier  barrier
-// Ring safety: the loaders run in step with the early group.  RAW: a loader's wait for chunk c + 1 precedes its first
-// barrier of phase c; the early group reads chunk c + 1 after its second barrier of phase c, the late group later still.
-// WAR: chunk c + NSLOT - 1 overwrites chunk c - 1, whose reads every compute wave retired (lgkmcnt(0)) BEFORE the first
-// barrier of its phase c - 1; for the late group that barrier is the loaders' second barrier of phase c - 1.
+// Ring safety (the argument of pp_ring.h; what differs with loaders): they run in step with the early group.  RAW: a loader's
+// wait for chunk c + 1 precedes its first barrier of phase c; the early group reads chunk c + 1 after its second barrier of phase
+// c, the late group later still.  WAR: chunk c + NSLOT - 1 overwrites chunk c - 1, whose reads every compute wave retired
+// (lgkmcnt(0)) BEFORE the first barrier of its phase c - 1; for the late group that barrier is the loaders' second of phase c - 1.
 // Lane layout of the accumulators (D'[n][m] orientation, as gemm_nt_pp_kernel): acc[i][j][r] =
 // C[m = .. + 16 i + (lane & 15)][n = .. + 16 j + 4 (lane >> 4) + r].
 //   NLOAD == 0 (the 128 x 640 whole-row score tile: 160 accumulators per lane leave no room for a third wave per SIMD): the 8
-//   compute waves stage their own operands in gemm_nt_pp_kernel's two-phase schedule (B part of chunk c + NSLOT - 1 requested
-//   in phase 2c, A part in phase 2c + 1, chunk consumed in two halves of the row blocks).
+//   compute waves stage their own operands in the two-phase schedule of pp_ring.h, as gemm_nt_pp_kernel and gemm_tn_pp_kernel do
+//   (B part of chunk c + NSLOT - 1 requested in phase 2c, A part in phase 2c + 1, chunk consumed in two halves of the row blocks).
 //   GEN = 0 (most launches): no memory-row maps and no second operand pair -- their address arithmetic (an integer division per
 //   staged piece) and branches compile out of the staging code, which sits in every chunk's read phase.
 template <int BM, int BN, int WAVES_M, int NSLOT, int NLOAD, int AFORM, int BFORM, int EPI, int GEN>
@@ -201,15 +201,14 @@ __global__ __launch_bounds__(NLOAD ? 768 : 512, NLOAD ? 3 : 2) void xg_kernel(Xg
 #pragma unroll
         for (int c = 0; c < DEPTH; ++c)
             if (c < nc) stage(c, smem + c * SLOT);
-        wait_vm_chunks<G>((nc < DEPTH ? nc : DEPTH) - 1);
+        wait_vm_chunks<G, DEPTH - 1>(pp_inflight_prologue<DEPTH>(nc));
         PP_FENCE();
         __builtin_amdgcn_s_barrier();   // chunk 0 is in LDS
         PP_FENCE();
         int nxt = DEPTH;
         for (int c = 0; c < nc; ++c) {
             if (c + DEPTH < nc) stage(c + DEPTH, smem + nxt * SLOT);
-            const int rem = nc - 1 - c;
-            wait_vm_chunks<G>(rem >= 1 ? (rem - 1 < DEPTH - 1 ? rem - 1 : DEPTH - 1) : 0);
+            wait_vm_chunks<G, DEPTH - 1>(pp_inflight_next<DEPTH>(nc, c));
             PP_FENCE();
             __builtin_amdgcn_s_barrier();
             PP_FENCE();
@@ -257,7 +256,7 @@ __global__ __launch_bounds__(NLOAD ? 768 : 512, NLOAD ? 3 : 2) void xg_kernel(Xg
 #pragma unroll
         for (int c = 0; c < DEPTH; ++c)
             if (c < nc) stage(c, smem + c * SLOT);
-        wait_vm_chunks<G>((nc < DEPTH ? nc : DEPTH) - 1);
+        wait_vm_chunks<G, DEPTH - 1>(pp_inflight_prologue<DEPTH>(nc));
     }
     PP_FENCE();
     __builtin_amdgcn_s_barrier();   // chunk 0 is in LDS
@@ -301,10 +300,7 @@ __global__ __launch_bounds__(NLOAD ? 768 : 512, NLOAD ? 3 : 2) void xg_kernel(Xg
 #pragma unroll
             for (int i = 0; i < HI; ++i) af[i] = frag_a(At, HI + i);
             if (more) stage_a(c + DEPTH, nx);
-            {
-                const int rem = nc - 1 - c;
-                wait_vm_chunks<G>(rem >= 1 ? (rem - 1 < DEPTH - 1 ? rem - 1 : DEPTH - 1) : 0);
-            }
+            wait_vm_chunks<G, DEPTH - 1>(pp_inflight_next<DEPTH>(nc, c));
             PP_FENCE();
             __builtin_amdgcn_s_barrier();
             PP_FENCE();

@@ -1,7 +1,8 @@
 // Helpers shared by the fused cross-attention kernels (xattn.hip: the per-sample batched GEMM template; xflash.hip: the
-// two-GEMM image-query kernel): memory-row maps, LDS-DMA staging with row maps, counted waits, lane-quad reductions.
+// two-GEMM image-query kernel): memory-row maps, LDS-DMA staging with row maps, lane-quad reductions (counted waits: pp_ring.h).
 #pragma once
 #include "mfma_tiles.h"
+#include "pp_ring.h"
 
 // ---- xflash.hip: image queries over text keys (dir 1) as ONE launch: S = x K'^T, the per-head softmax in registers, the
 // (dropped) probabilities kept in LDS as the A operand of the second product, s = drop(drop(P) V' + b_o) + x.
@@ -49,13 +50,6 @@ DEVINL void t_stage128(const bf16_t* G, int64_t ld, int r0, int r_end, int col0,
     const void* src = (grow < r_end && col < ncols) ? (const void*)(G + mrow * ld + col)
                                                     : (const void*)((const char*)g_m3ae_zero_page + (lane & 15) * 16);
     glds16(src, panel + wave * 1024);
-}
-
-template <int N> DEVINL void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-template <int G> DEVINL void wait_vm_chunks(int chunks) {   // chunks in {0, 1, 2}
-    if (chunks >= 2) wait_vm<2 * G>();
-    else if (chunks == 1) wait_vm<G>();
-    else wait_vm<0>();
 }
 
 DEVINL float quad16_max(float v) {   // over the 4 lanes l, l^16, l^32, l^48

@@ -22,7 +22,6 @@
 // all (the barrier-coupled structure), a tile's 66 us = prologue 5 + product 1 24 + softmax / image 5 + product 2 24 + epilogues 6.
 #include "xattn_common.h"
 #include "launch.h"
-#include <type_traits>
 
 #ifndef XF_ST_AUX
 #define XF_ST_AUX 2   // cache policy of the output rows (aux bits of buffer_store): 2 = nt, streaming (-0.8 % on the call, profiles/r04_xflash_nt_store.log)
@@ -124,17 +123,11 @@ __global__ __launch_bounds__(768, 3) void xf1_kernel(XfArgs a) {
         // Ring protocol (both products): at the start of phase k the loader tops the ring up to chunk k + DEPTH (the slot of chunk
         // k - 1: every compute wave retired its reads of it before the barrier that ends phase k - 1), and BETWEEN the phase's two
         // barriers it waits until chunk k + 1 has landed (the early group reads it after the second barrier): the DMA of a chunk
-        // has DEPTH - 1/2 phases to land.
-        auto wait_landed = [&](auto g, int outstanding) {   // all but the youngest `outstanding` chunks of this wave have landed
-            constexpr int G = decltype(g)::value;
-            if (outstanding >= 3) wait_vm<3 * G>();
-            else if (outstanding == 2) wait_vm<2 * G>();
-            else if (outstanding == 1) wait_vm<G>();
-            else wait_vm<0>();
-        };
+        // has DEPTH - 1/2 phases to land.  Waits: wait_vm_chunks (pp_ring.h) on `issued`, this loader's own count of requested
+        // chunks -- all but the youngest issued - 1 (prologue) / issued - (k + 2) (phase k) of them have landed.
         int issued = 0;
         for (; issued < DEPTH1 && issued < nc1; ++issued) stage1(issued, smem + issued * SLOT1, 2);
-        wait_landed(std::integral_constant<int, G1>{}, issued - 1);
+        wait_vm_chunks<G1>(issued - 1);
         PP_FENCE();
         __builtin_amdgcn_s_barrier();   // chunk 0 is in LDS
         PP_FENCE();
@@ -154,7 +147,7 @@ __global__ __launch_bounds__(768, 3) void xf1_kernel(XfArgs a) {
                 ++issued;
                 nxt = nxt + 1 == NSLOT1 ? 0 : nxt + 1;
             }
-            if (k + 1 < nc1) wait_landed(std::integral_constant<int, G1>{}, issued - (k + 2));
+            if (k + 1 < nc1) wait_vm_chunks<G1>(issued - (k + 2));
             XF_ACC(2);
             PP_FENCE();
             __builtin_amdgcn_s_barrier();
@@ -168,7 +161,7 @@ __global__ __launch_bounds__(768, 3) void xf1_kernel(XfArgs a) {
         // product 2: the first chunks land while the compute waves run the softmax
         issued = 0;
         for (; issued < DEPTH2 && issued < nc2; ++issued) stage2(issued, smem + RING2 + issued * SLOT2, 2);
-        wait_landed(std::integral_constant<int, G2>{}, issued - 1);
+        wait_vm_chunks<G2>(issued - 1);
         PP_FENCE();
         if (a.P != nullptr) {           // the compute waves' image copies (training)
             __builtin_amdgcn_s_barrier();
@@ -204,7 +197,7 @@ __global__ __launch_bounds__(768, 3) void xf1_kernel(XfArgs a) {
                 ++issued;
                 nxt = nxt + 1 == NSLOT2 ? 0 : nxt + 1;
             }
-            if (k + 1 < nc2) wait_landed(std::integral_constant<int, G2>{}, issued - (k + 2));
+            if (k + 1 < nc2) wait_vm_chunks<G2>(issued - (k + 2));
             XF_ACC(2);
             PP_FENCE();
             __builtin_amdgcn_s_barrier();

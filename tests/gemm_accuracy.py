@@ -377,8 +377,9 @@ def rounding_shares(exact):
     return inexact.double().mean().item(), tie.double().mean().item()
 
 
-# epilogues of the exact tier (the linear classes of launch_nt: PLAIN, RELU, DMUL), as keyword sets of reference() / model()
-EXACT_EPILOGUES = ("plain", "bias+res", "bias+relu+pre+drop+res", "drop+res+dmul", "alpha0.5+acc")
+# epilogues of the exact tier (the linear classes of launch_nt: PLAIN, RELU, DMUL, and -- "dmul+pre": a derivative operand together
+# with a stored preact, which only the catch-all class serves -- ANY), as keyword sets of reference() / model()
+EXACT_EPILOGUES = ("plain", "bias+res", "bias+relu+pre+drop+res", "drop+res+dmul", "alpha0.5+acc", "dmul+pre")
 
 
 def exact_epilogue(name, ops, keep, cast=lambda t: t):
@@ -393,6 +394,8 @@ def exact_epilogue(name, ops, keep, cast=lambda t: t):
         kw.update(dact_aux=cast(ops["aux"]), dact=ACT_MULAUX, keep=keep, p=0.5, residual=cast(ops["residual"]))
     elif name == "alpha0.5+acc":
         kw.update(alpha=0.5, c_old=cast(ops["c_old"]))
+    elif name == "dmul+pre":   # preact = alpha acc, C = preact * aux
+        kw.update(dact_aux=cast(ops["aux"]), dact=ACT_MULAUX, want_preact=True)
     else:
         assert name == "plain", name
     return kw
@@ -521,7 +524,11 @@ NT_EXACT_CASES = [   # (M, N, K), NT variants
     ((5125, 3336, 256), (10, -1)),
     ((43557, 520, 128), (7,)),
 ]
-TN_EXACT_CASES = [((128, 128, 37), (0, 2)), ((128, 256, 1154), (0, 2)), ((256, 128, 1024), (0, 2)), ((256, 256, 4133), (0, 2, 5))]
+TN_EXACT_CASES = [((128, 128, 37), (0, 2)), ((128, 256, 1154), (0, 2)), ((256, 128, 1024), (0, 2)), ((256, 256, 4133), (0, 2, 5)),
+                  ((256, 256, 4620), (0, 2, 5)), ((256, 256, 4650), (0, 2, 5)), ((256, 256, 4100), (0, 2, 5))]
+# variant 5 (the 256 x 256 ping-pong kernel): 32-row chunks in the LAST split of an accumulating call -- 4 and more fill the ring's
+# prologue, 1 / 2 / 3 take its short branches and the short-remainder waits of the loop
+TN_PP_TAIL_CHUNKS = {(256, 256, 4133): 4, (256, 256, 4620): 1, (256, 256, 4650): 2, (256, 256, 4100): 3}
 GENERIC_EXACT_SHAPES = [(33, 50, 72), (17, 498, 100)]
 BOUND_CASES = [((130, 132, 64), (0, -1)), ((300, 264, 256), (0, 4, 7, 9, -1)), ((257, 136, 768), (0, 7, 9, -1))]
 TN_BOUND_CASES = [((256, 256, 4133), (0, 5, -1)), ((128, 256, 1154), (0, -1))]

@@ -170,7 +170,12 @@ def test_tn_exact(shape, variant):
     rs_old = (torch.arange(M, device=DEV) % 17 - 8).float()
     rs_want = rs_old.double() + o["a"].sum(1)
     if variant == 5:
-        assert M % 256 == 0 and N % 256 == 0 and K >= 4096 and cdiv(K, 64) // 8 == 8 and K % 64 != 0   # 8 splits, ragged last chunk
+        # the split rule of the 256 x 256 kernel (launch_tn_pp, accumulating call): one workgroup per CU, 8 and more 64-row steps per split
+        assert M % 256 == 0 and N % 256 == 0 and K >= 4096 and K % 64 != 0   # several splits, ragged last chunk
+        ksteps = cdiv(K, 64)
+        steps_per = cdiv(ksteps, max(1, min(256 // ((M // 256) * (N // 256)), ksteps // 8)))
+        splits = cdiv(ksteps, steps_per)
+        assert splits >= 8 and cdiv(K - (splits - 1) * steps_per * 64, 32) == ga.TN_PP_TAIL_CHUNKS[shape]
     for det in (False, True):
         with pinned(tn=variant, deterministic=det):
             for accumulate in (True, False):

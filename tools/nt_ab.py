@@ -2,7 +2,7 @@
 (rounds x variants), min and median per variant; every variant's output is first compared bit for bit with variant 4 (the
 2-stage kernel with the same accumulation order).
 
-    B=256 VARS=7,10 ROUNDS=5 python tools/nt_ab.py [tag]      (M=8192: other row counts; SHAPES=2304x768,...: a subset)
+    B=256 VARS=7,10 ROUNDS=5 python tools/nt_ab.py [tag]      (M=8192: other row counts; SHAPES=2304x768,...: a subset, or other NxK, plain)
     VARS=-1,999: by shape with the row-major weight against by shape with the tiled weight (v + 1000: variant v, B from the tiled copy)
 """
 import os
@@ -51,6 +51,9 @@ def main():
     if SHAPES:
         keep = set(SHAPES.split(","))
         cases = [c for c in cases if f"{c[0]}x{c[1]}" in keep or c[2] in keep]
+        # an NxK that is not one of the step's shapes (K = 128 / 192: the class only the first-generation ping-pong kernel takes)
+        have = {f"{c[0]}x{c[1]}" for c in cases}
+        cases += [(int(s.split("x")[0]), int(s.split("x")[1]), "plain") for s in sorted(keep - have) if s[:1].isdigit() and "x" in s]
     print(f"[{tag}] M={m} variants {VARS} rounds {ROUNDS} x {ITERS} launches", flush=True)
     tot = {v: 0.0 for v in VARS}
     for (n, k, kind) in cases:
