@@ -51,6 +51,8 @@ extern "C" {
  *    (M3AE_CLIP_*), no descriptor changed and m3ae_adamw keeps its signature. */
 /* 4 (additive): the optim_type rules next to AdamW.  m3ae_adam, m3ae_sgd and their _clip forms (csrc/misc.hip); no descriptor
  *    changed. */
+/* 4 (additive): device-resident greedy search for the decoder head.  m3ae_greedy_argmax (+ m3ae_greedy_workspace_bytes) and
+ *    m3ae_greedy_step (csrc/greedy.hip); no descriptor changed. */
 #define M3AE_ABI_VERSION 4
 
 enum { M3AE_F32 = 0, M3AE_BF16 = 1 };
@@ -667,6 +669,32 @@ int m3ae_beam_step(const float* top_s, const int32_t* top_i, const int64_t* ids_
 int m3ae_beam_finalize(const int64_t* ids, const float* beam_scores, const int32_t* done, int32_t* n_hyp, double* hyp_score,
                        int32_t* hyp_len, int64_t* hyp_tok, int64_t* seq, int64_t* len, int64_t B, int64_t nb, int64_t max_length,
                        int64_t cur_len, int64_t eos, int64_t pad, double div, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Device-resident greedy search (csrc/greedy.hip; ABI 4, additive): the per-token work of the decoder head's `search_path`
+ * (reference m3ae_decoder.py:141-182) -- argmax over the vocabulary, [SEP] / EOS detection, the growing sequence and the count
+ * of unfinished rows -- on device state.  Integer compares only, no atomics: two calls on the same inputs give the same bits.
+ *
+ * m3ae_greedy_argmax: logits [R][V], dtype M3AE_F32 or M3AE_BF16, row stride ld >= V in elements (columns [V, ld) are never
+ *   read); the base pointer is element-aligned, nothing else is asked of ld.  Rows are split over vocabulary chunks of `chunk`
+ *   elements (0 = 2048; 64 <= chunk <= 65536), one workgroup per (row, chunk); each writes the maximum of its chunk's order keys,
+ *   (monotone image of the fp32 value) << 32 | (2^32 - 1 - column), to workspace[row][chunk] (uint64; the key of beam.hip).  The
+ *   maximum of a row's keys is torch.argmax's choice: the greatest value, the lowest column among equal values (+0 == -0), and
+ *   any NaN (either sign) above every number, the first NaN winning.  workspace: m3ae_greedy_workspace_bytes(R, V, chunk) bytes
+ *   (0 for shapes the call rejects), 8-byte aligned.  tokens: optional int64 [R], receives the decoded column of every row.
+ *   M3AE_ERR_UNSUPPORTED for another dtype, chunk outside its bounds, V >= 2^31 or R * chunks >= 2^31.
+ * m3ae_greedy_step: one search step at position pos (0 <= pos < max_len) from the keys of m3ae_greedy_argmax (nch chunks per row).
+ *   For row r with tok its argmax: last_tok[r] = tok always (the host loop feeds the raw token back after a row has finished,
+ *   too); a finished row gets seq[r][pos] = pad; an open row gets seq[r][pos] = tok and, when tok == sep or (eos >= 0 and
+ *   tok == eos), finished[r] = 1 and len[r] = pos + 1.  open_count[pos] = rows not finished after the step.  seq int64
+ *   [B][max_len], len / last_tok int64 [B], finished int32 [B], open_count int32 [max_len]; err int64 [1] is set to 1 when a
+ *   decoded column is outside [0, V) (the row then continues with token 0: never an address). */
+int64_t m3ae_greedy_workspace_bytes(int64_t R, int64_t V, int64_t chunk);
+int m3ae_greedy_argmax(const void* logits, int64_t ld, int64_t R, int64_t V, int64_t chunk, int dtype, void* workspace,
+                       int64_t workspace_bytes, int64_t* tokens, void* stream);
+int m3ae_greedy_step(const void* keys, int64_t nch, int64_t* seq, int64_t* len, int64_t* last_tok, int32_t* finished,
+                     int32_t* open_count, int64_t* err, int64_t B, int64_t V, int64_t max_len, int64_t pos, int64_t sep, int64_t eos,
+                     int64_t pad, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Sample expansion of a de-duplicated image batch (csrc/samples.hip; ABI 4, additive): the image tower runs once per distinct

@@ -17,6 +17,7 @@
 // m3ae_beam_step / m3ae_beam_finalize: one wave per sample; lane 0 walks the candidates (hypothesis lists in double, as the
 // host's Python floats), the wave copies the token rows.
 #include "common.h"
+#include "order_key.h"   // ord32 / unord32 / make_key / wave_max_u64, shared with csrc/greedy.hip
 
 namespace {
 
@@ -24,23 +25,6 @@ constexpr int BT = 256;          // threads of the top-k kernels
 constexpr int MAX_CHUNK = 4096;  // keys of one chunk live in LDS (32 KB)
 constexpr int DEF_CHUNK = 2048;
 constexpr int MAX_BEAMS = 8;
-
-DEVINL uint32_t ord32(float f) {
-    const uint32_t u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-DEVINL float unord32(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-DEVINL uint64_t make_key(float score, uint32_t flat) { return ((uint64_t)ord32(score) << 32) | (uint64_t)(0xffffffffu - flat); }
-
-DEVINL uint64_t wave_max_u64(uint64_t v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t lo = __shfl_xor((uint32_t)v, o, 64), hi = __shfl_xor((uint32_t)(v >> 32), o, 64);
-        const uint64_t w = ((uint64_t)hi << 32) | lo;
-        v = w > v ? w : v;
-    }
-    return v;
-}
 
 // The K largest keys of keys[0..n) (0 = empty slot) in descending order into out[0..K); thread t owns keys[t], keys[t + BT], ...
 // (reads and clears only those), so the one barrier per round is the exchange of the wave maxima (double-buffered).

@@ -140,6 +140,10 @@ _SIGS = {
     "m3ae_beam_topk": (C.c_int, [vp, i64, vp, i64, i64, i64, i64, vp, i64, vp, vp, vp]),
     "m3ae_beam_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, C.c_double, vp]),
     "m3ae_beam_finalize": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, C.c_double, vp]),
+    # device-resident greedy search for the decoder head (ABI 4, additive)
+    "m3ae_greedy_workspace_bytes": (i64, [i64, i64, i64]),
+    "m3ae_greedy_argmax": (C.c_int, [vp, i64, i64, i64, i64, C.c_int, vp, i64, vp, vp]),
+    "m3ae_greedy_step": (C.c_int, [vp, i64, vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, i64, i64, vp]),
     # sample expansion of a de-duplicated image batch (ABI 4, additive)
     "m3ae_expand_samples": (C.c_int, [vp, vp, vp, i64, i64, i64, C.c_int, vp]),
     "m3ae_segment_sum_rows": (C.c_int, [vp, vp, vp, vp, i64, i64, i64, C.c_int, vp]),

@@ -53,6 +53,10 @@ DEFAULTS = dict(
     # where the beam-search bookkeeping of the T5 head's generate runs (m3ae_amd/modules/t5.py): "host" (one small copy and a Python
     # loop per step) | "device" (csrc/beam.hip, no host round trip per step; same tokens)
     t5_beam_search="host",
+    # where the greedy-search bookkeeping of the decoder head runs (m3ae_amd/modules/m3ae_decoder.py: Decoder.search_path): "host"
+    # (ATen argmax / compares / cat and one blocking `finished.all()` per token) | "device" (csrc/greedy.hip, no host round trip per
+    # token; same tokens)
+    decoder_search="host",
     # arrow VQA batches collated per distinct image (m3ae_amd/data.py: collate_dedup): every distinct image of a batch is decoded,
     # uploaded and run through the image tower once, and ops.expand_samples hands its tokens to the samples that ask about it
     # (batch["image_index"]).  Same samples, same arithmetic per sample; not available with the mim / itm objectives.
@@ -169,6 +173,17 @@ def gradient_clip_val(cfg):
     return float(v)
 
 
+DECODER_SEARCHES = ("host", "device")
+
+
+def decoder_search(cfg):
+    """The validated `decoder_search` of a config dict (default "host")."""
+    v = cfg.get("decoder_search", "host")
+    if not isinstance(v, str) or v not in DECODER_SEARCHES:
+        raise ValueError(f"decoder_search must be one of {DECODER_SEARCHES}, got {v!r}")
+    return v
+
+
 OPTIM_TYPES = ("adamw", "adam", "sgd")
 
 
@@ -186,6 +201,7 @@ def resolve_arch(cfg):
     """Fill vit_width/vit_layers/text_* from the `vit` / `tokenizer` names unless given explicitly."""
     cfg = dict(cfg)
     optim_type(cfg)
+    decoder_search(cfg)
     if "gradient_clip_val" in cfg:
         cfg["gradient_clip_val"] = gradient_clip_val(cfg)
     clip_residual_dtype(cfg)

@@ -22,15 +22,18 @@ the head has 8 heads of 96 channels (768 / 8) and the MFMA attention kernels are
 two attentions run the fp32 materialised-softmax kernels on fp32 copies of the bf16 projections (`ops.attn_forward`:
 T <= 12 tokens against 2 (CLS) or 2 + 577 + 32 encoder tokens -- a few % of the head's work).  train() mode applies the
 reference's dropout sites with the library's counter-hash masks.
+Greedy search: `search_path` (host bookkeeping, the default) or, with `decoder_search=device` / `search="device"`, the same
+search with argmax and bookkeeping on the GPU (`search_path_async`, csrc/greedy.hip); `DecoderModel.generate` wraps either.
 Tokenisation happens outside (`batch["decoder_tokens"]`: int64 [B, T] = [CLS] answer [SEP] [PAD]...) or through a
 `tokenizer` callable; string metrics (ROUGE / BLEU / exact match) stay out of scope.
 """
 import math
+from types import SimpleNamespace as NS
 
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import config, ops
 from ..param_store import ParamStore, group_hparams_decoder, param_group_of_decoder
 from .m3ae_module import M3AETransformerSS, _Base, _HParams, pl
 
@@ -209,11 +212,13 @@ class Decoder(nn.Module):
 
     @torch.no_grad()
     @ops.model_mode
-    def step_logits(self, last_ids, pos, enc_kv, cache):
+    def step_logits(self, last_ids, pos, enc_kv, cache, pe_rows=None):
         """Logits of the next token from the NEW token alone (last_ids [B, 1] at position `pos`): the prefix's keys / values
-        come from `cache`, the encoder side from `enc_kv`; equal to forward(prefix)[:, -1] (eval mode)."""
+        come from `cache`, the encoder side from `enc_kv`; equal to forward(prefix)[:, -1] (eval mode).  `pe_rows`: the
+        position's sinusoid row repeated B times (fp32 [B, D], contiguous) when the caller has built it already."""
         B = last_ids.shape[0]
-        pe_rows = self.positional_encoding.pe[0, pos:pos + 1].to(torch.float32).repeat(B, 1).contiguous()
+        if pe_rows is None:
+            pe_rows = self.positional_encoding.pe[0, pos:pos + 1].to(torch.float32).repeat(B, 1).contiguous()
         t = _DecoderEmbedFn.apply(last_ids.reshape(-1).contiguous(), self.target_embedding.weight, pe_rows,
                                   self.head_dtype)
         x = self.dec_layers[self.num_layers - 1].step(t.view(B, 1, -1), enc_kv, cache, pos)
@@ -221,10 +226,56 @@ class Decoder(nn.Module):
 
     @torch.no_grad()
     @ops.model_mode
-    def search_path(self, cross_attn_feats, cls_id=101, sep_id=102, eos_id=None, pad_id=0, use_cache=True):
+    def search_path_async(self, cross_attn_feats, cls_id=101, sep_id=102, eos_id=None, pad_id=0, lookahead=2, chunk=0):
+        """The greedy search of `search_path` with its bookkeeping on the device (csrc/greedy.hip): per step the decoder row, the
+        vocabulary GEMM, ops.greedy_argmax (on the logits as the GEMM left them: bf16 in perf mode, a strided view of the padded
+        vocabulary) and ops.greedy_step are enqueued with no blocking host call, and the result stays on the device.  Returns a
+        namespace with `seq` int64 [B, max_len] (pad after a row's first [SEP] / EOS), `len` int64 [B] (tokens up to and with
+        that one; max_len for a row that never finished), `err` int64 [1] (nonzero: a decoded token left the vocabulary), `out`
+        (the three in one buffer), `steps` (decoding steps enqueued) and `state` (ops.GreedyState).
+
+        Early exit as in T5's generate_async (ops.OpenCountWatch): the host runs at most `lookahead` steps ahead of the newest
+        step known to have completed and stops once a completed step reports no open row; lookahead=None runs all max_len steps.
+        Steps past the one that finished the last row write pad only, so the tokens are the same either way."""
+        watch = ops.OpenCountWatch(self.max_len, lookahead)
+        B, dev = cross_attn_feats.shape[0], cross_attn_feats.device
+        D = self.target_embedding.weight.shape[1]
+        enc_kv = self.dec_layers[self.num_layers - 1].cross_kv(cross_attn_feats.to(self.head_dtype))
+        cache = torch.empty((B, self.max_len, 2 * D), dtype=self.head_dtype, device=dev)
+        st = ops.GreedyState(B, self.max_len, dev, cls_id, pad_id)
+        # the sinusoid row of every position repeated B times, once per call: step `pos` reads pe_rows[pos] ([B, D], contiguous)
+        pe_rows = self.positional_encoding.pe[0, :self.max_len].to(torch.float32)[:, None, :].expand(self.max_len, B, D).contiguous()
+        ws, steps = None, 0
+        for pos in range(self.max_len):
+            logits = self.step_logits(st.last_tok.view(B, 1), pos, enc_kv, cache, pe_rows[pos])
+            if ws is None:
+                V = logits.shape[-1]
+                ws = ops.greedy_workspace(B, V, dev, chunk)
+            ops.greedy_argmax(logits, chunk, ws)
+            ops.greedy_step(st, ws, V, pos, sep_id, eos_id, pad_id)
+            steps += 1
+            if watch.enqueued(st.open_count, pos):
+                break
+        return NS(seq=st.seq, len=st.len, err=st.err, out=st.out, steps=steps, state=st)
+
+    @torch.no_grad()
+    @ops.model_mode
+    def search_path(self, cross_attn_feats, cls_id=101, sep_id=102, eos_id=None, pad_id=0, use_cache=True, search="host",
+                    lookahead=2):
         """m3ae_decoder.py:141-182: greedy decoding.  The reference re-runs the whole prefix every step; here a step is one
         decoder row: the prefix's self-attention keys / values are cached, the encoder-side keys / values are projected
-        once (`use_cache=False` keeps the reference's loop; both give the same tokens)."""
+        once (`use_cache=False` keeps the reference's loop; both give the same tokens).
+        search="host" (default): ATen argmax / compares / cat and one blocking `finished.all()` per token.  search="device":
+        `search_path_async` plus one copy of its result at the end; same tokens."""
+        if search == "device":
+            if not use_cache:
+                raise ValueError("search='device' decodes one cached row per step: use_cache=False is the host form's")
+            r = self.search_path_async(cross_attn_feats, cls_id, sep_id, eos_id, pad_id, lookahead)
+            if int(r.out.cpu()[-1]) != 0:
+                raise ops._lib.M3AEHipError("device greedy search: a decoded token left [0, vocab_size)")
+            return r.seq
+        if search != "host":
+            raise ValueError(f"search must be 'host' or 'device', got {search!r}")
         B, dev = cross_attn_feats.shape[0], cross_attn_feats.device
         seq = torch.full((B, 1), cls_id, dtype=torch.long, device=dev)
         finished = torch.zeros(B, dtype=torch.bool, device=dev)
@@ -269,6 +320,7 @@ class DecoderModel(_Base):
             vocab_size = tokenizer.vocab_size
             special_ids = (tokenizer.cls_token_id, tokenizer.sep_token_id, tokenizer.pad_token_id)
         self.cls_id, self.sep_id, self.pad_id = special_ids
+        self.decoder_search = config.decoder_search(m3ae_config)   # build extension: "host" | "device" (Decoder.search_path)
         self.m3ae = M3AETransformerSS(m3ae_config)
         self.decoder = Decoder(num_layers=6, d_model=768, num_heads=8, d_ff=768 * 4, dropout=0.1, max_len=128,
                                target_vocab_size=vocab_size)
@@ -331,7 +383,7 @@ class DecoderModel(_Base):
         enc = self.features(batch)
         if len(self.current_tasks) == 0 or test:
             return {"vqa_loss": 0, "generated_ids": self.decoder.search_path(enc, self.cls_id, self.sep_id, None,
-                                                                             self.pad_id)}
+                                                                             self.pad_id, search=self.decoder_search)}
         tokens = self.tokens_of(batch)
         tin = tokens[:, :-1].clone()
         tin[tin == self.sep_id] = self.pad_id                   # :344-348
@@ -341,6 +393,26 @@ class DecoderModel(_Base):
         labels = torch.where(gold == self.pad_id, torch.full_like(gold, -100), gold)  # ignore_index = [PAD] (:226)
         loss = ops.cross_entropy(logits, labels.contiguous())
         return {"vqa_loss": loss, "vqa_logits": logits}
+
+    @ops.model_mode
+    def generate_async(self, batch, lookahead=2):
+        """The features of `batch` and the device-resident greedy search over them, nothing copied to the host: the namespace of
+        Decoder.search_path_async (`seq`, `len`, `err`, `out`, `steps`, `state`)."""
+        if self.store is None:
+            raise RuntimeError("call finalize(device) before the first forward")
+        return self.decoder.search_path_async(self.features(batch), self.cls_id, self.sep_id, None, self.pad_id, lookahead)
+
+    @ops.model_mode
+    def generate(self, batch, search=None):
+        """The generated token ids of `batch`, int64 [B, max_len] (pad after a row's [SEP]), by `search` ("host" | "device";
+        None: the config's decoder_search).  With a tokenizer: (ids, the decoded strings, special tokens skipped)."""
+        if self.store is None:
+            raise RuntimeError("call finalize(device) before the first forward")
+        ids = self.decoder.search_path(self.features(batch), self.cls_id, self.sep_id, None, self.pad_id,
+                                       search=self.decoder_search if search is None else search)
+        if self.tokenizer is None:
+            return ids
+        return ids, self.tokenizer.batch_decode(ids.cpu().tolist(), skip_special_tokens=True)
 
     def training_step(self, batch, batch_idx=0):
         """m3ae_decoder.py:390-396."""

@@ -292,13 +292,12 @@ class T5ForConditionalGeneration(nn.Module):
         (length of the best hypothesis, before the EOS), `err` int64 [1] (nonzero: a candidate index left its range), `out`
         (the three in one buffer), `steps` (decoding steps enqueued) and `state` (ops.BeamState).
 
-        Early exit: steps after every sample is done change no token, so leaving the loop is an optimisation only.  The count
-        of open samples after each step is copied to pinned host memory behind the step, with an event; the host runs at most
-        `lookahead` steps past the newest step whose event has completed (it waits on the event of the step `lookahead` back,
-        so the device always has work queued) and stops enqueuing once a completed step reports zero open samples.
-        lookahead=None always runs max_length - 1 steps."""
-        if lookahead is not None and lookahead < 1:
-            raise ValueError("lookahead must be >= 1 or None")
+        Early exit (ops.OpenCountWatch): steps after every sample is done change no token, so leaving the loop is an
+        optimisation only.  The count of open samples after each step is copied to pinned host memory behind the step, with an
+        event; the host runs at most `lookahead` steps past the newest step whose event has completed (it waits on the event of
+        the step `lookahead` back, so the device always has work queued) and stops enqueuing once a completed step reports zero
+        open samples.  lookahead=None always runs max_length - 1 steps."""
+        watch = ops.OpenCountWatch(max_length, lookahead, first=1)
         B, nb, dev = enc.shape[0], num_beams, enc.device
         R = B * nb
         enc_r = enc.repeat_interleave(nb, dim=0).contiguous()
@@ -308,11 +307,6 @@ class T5ForConditionalGeneration(nn.Module):
         st = ops.BeamState(B, nb, max_length, dev, self.config.decoder_start_token_id, pad_token_id)
         ws = None
         top = (torch.empty((B, 2 * nb), dtype=torch.float32, device=dev), torch.empty((B, 2 * nb), dtype=torch.int32, device=dev))
-        if lookahead is not None:
-            open_host = torch.empty(max_length, dtype=torch.int32, pin_memory=True)
-            open_np = open_host.numpy()      # read through numpy: plain host memory, filled by the copies below
-            events = {}
-        seen = 0                             # newest step whose event is known to have completed
         steps, cur_len = 0, 1
         while cur_len < max_length:
             logits = self.next_token_logits_cached(enc_r, st.last_tok.view(R, 1), cross_kv, self_cache, cur_len - 1)
@@ -323,20 +317,9 @@ class T5ForConditionalGeneration(nn.Module):
             ops.beam_step(st, top[0], top[1], V, cur_len, eos_token_id, pad_token_id, length_penalty)
             self_cache = [ops.gather_rows(c.view(R, -1), st.order).view_as(c) for c in self_cache]
             steps += 1
-            if lookahead is not None:
-                open_host[cur_len:cur_len + 1].copy_(st.open_count[cur_len:cur_len + 1], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                events[cur_len] = ev
-                if cur_len + 1 - lookahead >= 1:     # step cur_len + 1 may be enqueued once step cur_len + 1 - lookahead is through
-                    events[cur_len + 1 - lookahead].synchronize()
-                    seen = max(seen, cur_len + 1 - lookahead)
-                while seen < cur_len and events[seen + 1].query():
-                    seen += 1
-                if any(open_np[s] == 0 for s in range(1, seen + 1)):
-                    cur_len += 1
-                    break
             cur_len += 1
+            if watch.enqueued(st.open_count, cur_len - 1):
+                break
         ops.beam_finalize(st, cur_len, eos_token_id, pad_token_id, length_penalty, len_offset)
         return NS(seq=st.seq, len=st.len, err=st.err, out=st.out, steps=steps, state=st)
 

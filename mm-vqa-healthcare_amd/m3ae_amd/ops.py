@@ -1992,6 +1992,103 @@ def beam_finalize(st, cur_len, eos_id, pad_id, length_penalty=1.0, len_offset=0)
     return st.seq, st.len
 
 
+class OpenCountWatch:
+    """The early exit of a device-resident search loop (t5.generate_async, Decoder.search_path_async).  Steps after every row is
+    done change no token, so leaving the loop is an optimisation only.  The count of open rows after each step is copied to pinned
+    host memory behind the step, with an event; the host runs at most `lookahead` steps past the newest step whose event has
+    completed (it waits on the event of the step `lookahead` back, so the device always has work queued) and stops enqueuing once a
+    completed step reports zero.  Steps are numbered from `first`; lookahead=None never stops (and copies nothing)."""
+
+    def __init__(self, n_steps, lookahead, first=0):
+        if lookahead is not None and lookahead < 1:
+            raise ValueError("lookahead must be >= 1 or None")
+        self.lookahead, self.first = lookahead, first
+        self.seen = first - 1                # newest step whose event is known to have completed
+        if lookahead is not None:
+            self.host = torch.empty(n_steps, dtype=torch.int32, pin_memory=True)
+            self.np = self.host.numpy()      # read through numpy: plain host memory, filled by the copies below
+            self.events = {}
+
+    def enqueued(self, open_count, t):
+        """Call after step t has been enqueued (open_count int32 [n_steps] on the device, slot t written by it).  True: stop."""
+        if self.lookahead is None:
+            return False
+        self.host[t:t + 1].copy_(open_count[t:t + 1], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.events[t] = ev
+        back = t + 1 - self.lookahead
+        if back >= self.first:               # step t + 1 may be enqueued once step t + 1 - lookahead is through
+            self.events[back].synchronize()
+            self.seen = max(self.seen, back)
+        while self.seen < t and self.events[self.seen + 1].query():
+            self.seen += 1
+        return any(self.np[s] == 0 for s in range(self.first, self.seen + 1))
+
+
+# ------------------------------------------------------------------------------------------------------------
+# device-resident greedy search (csrc/greedy.hip): Decoder.search_path_async
+# ------------------------------------------------------------------------------------------------------------
+GREEDY_CHUNK = 2048   # vocabulary elements per workgroup of m3ae_greedy_argmax when the caller passes chunk=0
+
+
+def greedy_workspace(R, V, device, chunk=0):
+    """The keys buffer of greedy_argmax: int64 [R, chunks of a row] (the bits of the kernels' uint64 order keys)."""
+    n = _lib.lib().m3ae_greedy_workspace_bytes(R, V, chunk)
+    if n <= 0:
+        raise ValueError(f"greedy_workspace: R={R}, V={V}, chunk={chunk} is not a shape m3ae_greedy_argmax takes")
+    return torch.empty((R, n // (8 * R)), dtype=torch.int64, device=device)
+
+
+def greedy_argmax(logits, chunk=0, ws=None, out=None):
+    """logits fp32 or bf16 [R, V] (row stride >= V, unit column stride) -> the keys buffer `ws` int64 [R, chunks]: per vocabulary
+    chunk the greatest order key (value, then lowest column), for greedy_step.  With `out` (int64 [R], for direct testing) the
+    decoded tokens are written there and returned instead: torch.argmax's choice, ties and NaN included."""
+    _need_cuda(logits)
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("greedy_argmax takes fp32 or bf16 logits")
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        raise ValueError(f"greedy_argmax: logits {tuple(logits.shape)} with strides {tuple(logits.stride())}")
+    R, V = logits.shape
+    if ws is None:
+        ws = greedy_workspace(R, V, logits.device, chunk)
+    if ws.dtype != torch.int64 or not ws.is_contiguous() or not ws.is_cuda:
+        raise ValueError("greedy_argmax: ws is the int64 buffer of greedy_workspace")
+    if out is not None and (out.dtype != torch.int64 or tuple(out.shape) != (R,) or not out.is_contiguous() or not out.is_cuda):
+        raise ValueError("greedy_argmax: out int64 [R], contiguous")
+    check(_lib.lib().m3ae_greedy_argmax(_p(logits), logits.stride(0), R, V, chunk, _dt(logits), _p(ws), ws.numel() * 8, _p(out),
+                                        _stream()), "m3ae_greedy_argmax")
+    return ws if out is None else out
+
+
+class GreedyState:
+    """The device state of one greedy search (include/m3ae_hip.h, m3ae_greedy_step): allocated once per search_path call."""
+
+    def __init__(self, B, max_len, device, cls_id=101, pad_id=0):
+        self.B, self.max_len = B, max_len
+        self.out = torch.zeros((B * max_len + B + 1,), dtype=torch.int64, device=device)   # seq | len | error word: one copy brings all three to the host
+        self.seq, self.len, self.err = self.out[:B * max_len].view(B, max_len), self.out[B * max_len:-1], self.out[-1:]
+        self.seq.fill_(pad_id)
+        self.len.fill_(max_len)
+        self.last_tok = torch.full((B,), cls_id, dtype=torch.int64, device=device)
+        self.finished = torch.zeros((B,), dtype=torch.int32, device=device)
+        self.open_count = torch.zeros((max_len,), dtype=torch.int32, device=device)
+
+
+def greedy_step(st, keys, V, pos, sep_id, eos_id, pad_id):
+    """One step of the search on `st` at position pos from the keys of greedy_argmax (eos_id None or < 0: no second end token);
+    st.open_count[pos] = rows still unfinished afterwards."""
+    _need_cuda(keys)
+    _need_cuda(st.out)
+    if keys.dtype != torch.int64 or keys.dim() != 2 or keys.shape[0] != st.B or not keys.is_contiguous():
+        raise ValueError("greedy_step: keys int64 [B, chunks], contiguous (the buffer greedy_argmax returns)")
+    if not 0 <= pos < st.max_len:
+        raise ValueError(f"greedy_step: pos {pos} outside [0, {st.max_len})")
+    check(_lib.lib().m3ae_greedy_step(_p(keys), keys.shape[1], _p(st.seq), _p(st.len), _p(st.last_tok), _p(st.finished), _p(st.open_count),
+                                      _p(st.err), st.B, V, st.max_len, pos, sep_id, -1 if eos_id is None else eos_id, pad_id, _stream()),
+          "m3ae_greedy_step")
+
+
 # ------------------------------------------------------------------------------------------------------------
 # masked-image-modelling bookkeeping (pre-training, SURVEY 8a13)
 # ------------------------------------------------------------------------------------------------------------
