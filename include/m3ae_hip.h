@@ -287,7 +287,9 @@ enum { M3AE_XATTN_NO_PERSISTENT = 1,  /* the internal m3ae_gemm calls never take
        M3AE_XATTN_LEGACY_CHAIN = 2    /* dir 1 forward: the round-2 chain (score GEMM + softmax epilogue, P through HBM, P V'
                                        * GEMM) instead of the one-launch kernel of csrc/xflash.hip -- A/B measurements only */ };
 /* dir 1 (image queries): Lk = 32 or 64 text keys, any Lq; probs / probs_drop may be NULL in a forward-only call (the scores and
- * probabilities then never leave the chip).  dir 0 (text queries): Lq = 32 or 64, Lk <= 640. */
+ * probabilities then never leave the chip).  dir 0 (text queries): Lq = 32 or 64, Lk <= 640.  Both: head width D / H a multiple of 32
+ * up to 256, D <= 4096 (the backward: D <= 2048, the LayerNorm backward's widest row); DESIGN.md 2c tabulates the envelope.  The
+ * backward never touches the key-bias half of g_bkv: that gradient is exactly zero. */
 int m3ae_xattn_supported(const m3ae_xattn_desc* d);   /* 1 if the fused forward covers these shapes */
 int m3ae_xattn_bwd_supported(const m3ae_xattn_desc* d);   /* 1 if m3ae_xattn_bwd does too */
 int64_t m3ae_xattn_probs_ld(const m3ae_xattn_desc* d);

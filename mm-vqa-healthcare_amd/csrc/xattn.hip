@@ -1031,6 +1031,11 @@ extern "C" int m3ae_xattn_supported(const m3ae_xattn_desc* d) {
     if (d->H <= 0 || d->D % d->H != 0) return 0;
     const int64_t dh = d->D / d->H;
     if (I < 1 || dh % 32 != 0 || d->D % 128 != 0) return 0;
+    // head widths above 256 are refused: xattn_headvec_kernel (the bias gradients of the absorbed projections) gives a workgroup's 256
+    // threads to dh columns x 256 / dh row lanes, which is no lane at all from dh = 288 on -- the gradients of b_v (dir 0) and b_q
+    // (dir 1) would stay zero.  No configuration of the product is wider than 64; every width up to 256 is tested.
+    if (dh > 256) return 0;
+    if (d->D > 4096) return 0;   // the closing m3ae_layernorm_fwd covers rows of up to 4096 elements
     if (d->dir == 0) return ((T == 32 || T == 64) && I <= 640) ? 1 : 0;   // text queries: the whole-row score tile covers 640 keys
     // image queries (xflash.hip): 32 text keys (fine-tuning) or 64 (pre-training), any number of image tokens
     if (d->launch_flags & M3AE_XATTN_LEGACY_CHAIN) return (T == 32 && I <= 640) ? 1 : 0;
@@ -1039,6 +1044,9 @@ extern "C" int m3ae_xattn_supported(const m3ae_xattn_desc* d) {
 
 extern "C" int m3ae_xattn_bwd_supported(const m3ae_xattn_desc* d) {
     if (!m3ae_xattn_supported(d)) return 0;
+    // m3ae_layernorm_bwd(_drop), the first call of the backward, covers rows of up to 2048 elements: wider layers answered 1 here and
+    // then failed in m3ae_xattn_bwd with M3AE_ERR_UNSUPPORTED; they take the composition for training now (forward-only calls stay fused)
+    if (d->D > 2048) return 0;
     return 1;   // round 3: 32 or 64 text tokens in both directions (the softmax-backward epilogue sums 32- or 64-column groups)
 }
 
@@ -1356,9 +1364,12 @@ extern "C" int m3ae_xattn_bwd(const m3ae_xattn_desc* dp, void* stream) {
         hipLaunchKernelGGL(xattn_headvec_kernel, dim3(H, (B * T + 255) / 256), dim3(256), 0, s, (const float*)dcb,
                            (const bf16_t*)d.proj, (int64_t)2 * D, d.g_bq, B * T, T, R, 1, T, dh);
         XCHK(hip_launch_status());
-        // dWkv += dkv^T y (+ bias gradient), dy = dkv Wkv                                     (bert_model.py:276-277 backward)
-        const m3ae_gemm_desc w = dense_wgrad(d, 2 * D, dkv, d.y, d.g_wkv, d.g_bkv);
+        // dWkv += dkv^T y, dbv += column sums of dv, dy = dkv Wkv                              (bert_model.py:276-277 backward)
+        // The key bias adds the same number to every key of a row and drops out of the softmax: its gradient is exactly zero, and
+        // the column sums of dk are rounding noise only.  They are not added (dir 0 never forms them either): g_bkv[0, D) is left alone.
+        const m3ae_gemm_desc w = dense_wgrad(d, 2 * D, dkv, d.y, d.g_wkv, nullptr);
         XCHK(m3ae_gemm(&w, stream));
+        XCHK(m3ae_colsum(dkv + D, d.g_bkv + D, (int64_t)B * T, D, (int64_t)2 * D, M3AE_BF16, 1, stream));
         if (d.dy) {
             const m3ae_gemm_desc y = dense_dgrad(d, 2 * D, dkv, d.wkv_t, d.dy);
             XCHK(m3ae_gemm(&y, stream));

@@ -956,7 +956,13 @@ def xattn_supported(h2, L, other2, Lo, mask, P, backward=False):
     return bool(_lib.lib().m3ae_xattn_bwd_supported(C.byref(d)))
 
 
-def xattn_fwd(h2, B, L, other2, Lo, mask, P, pdrop=0.0, need_bwd=True, want_probs=False):
+def _xattn_alloc(dev):
+    """The default allocator of the fused cross-attention buffers: alloc(name, shape, dtype) -> an uninitialised contiguous tensor.
+    xattn_fwd / xattn_bwd take another one through `alloc` (tests: every buffer the descriptor names as a view of a fenced one)."""
+    return lambda name, shape, dt=torch.bfloat16: torch.empty(shape, dtype=dt, device=dev)
+
+
+def xattn_fwd(h2, B, L, other2, Lo, mask, P, pdrop=0.0, need_bwd=True, want_probs=False, alloc=None):
     """BertAttention as crossattention (bert_model.py:480-488) through the fused kernels.  Returns (out, saved).
     need_bwd=False (forward-only call): the image-query direction keeps scores and probabilities on chip, unless want_probs
     (attention maps asked for: the same launch copies them out of LDS, xattn_probs reads them)."""
@@ -964,31 +970,31 @@ def xattn_fwd(h2, B, L, other2, Lo, mask, P, pdrop=0.0, need_bwd=True, want_prob
     dev, D, H = h2.device, h2.shape[1], P.heads
     seeds = (next_dropout_seed(), next_dropout_seed()) if pdrop > 0 else None
     d = _xattn_desc(h2, B, L, other2, Lo, mask, P, pdrop, seeds)
-    bf = torch.bfloat16
+    f32 = torch.float32
     T, R = min(L, Lo), H * min(L, Lo)
-    e = lambda *shape, dt=bf: torch.empty(shape, dtype=dt, device=dev)
+    e = alloc or _xattn_alloc(dev)
     t = {}
     if d.dir == 0:
-        t["proj"] = e(B * L, D)
-        t["prime"] = e(B, R, D)
-        t["probs"] = e(B, R, 640)
-        t["zctx"] = e(B, R, D)
-        t["ctx"] = e(B * L, D)
+        t["proj"] = e("proj", (B * L, D))
+        t["prime"] = e("prime", (B, R, D))
+        t["probs"] = e("probs", (B, R, 640))
+        t["zctx"] = e("zctx", (B, R, D))
+        t["ctx"] = e("ctx", (B * L, D))
         if pdrop > 0:
-            t["probs_drop"] = e(B, R, 640)
-            t["rowsum"] = e(B, R, dt=torch.float32)
+            t["probs_drop"] = e("probs_drop", (B, R, 640))
+            t["rowsum"] = e("rowsum", (B, R), f32)
     else:
-        t["proj"] = e(B * Lo, 2 * D)
-        t["prime"] = e(2, B, R, D)
-        t["colbias"] = e(B, R, dt=torch.float32)
+        t["proj"] = e("proj", (B * Lo, 2 * D))
+        t["prime"] = e("prime", (2, B, R, D))
+        t["colbias"] = e("colbias", (B, R), f32)
         if need_bwd or XATTN_LEGACY_CHAIN or want_probs:
-            t["probs"] = e(B, L, R)
+            t["probs"] = e("probs", (B, L, R))
             if pdrop > 0:
-                t["probs_drop"] = e(B, L, R)
-    t["s"] = e(B * L, D)
-    t["out"] = e(B * L, D)
-    t["mean"] = e(B * L, dt=torch.float32)
-    t["rstd"] = e(B * L, dt=torch.float32)
+                t["probs_drop"] = e("probs_drop", (B, L, R))
+    t["s"] = e("s", (B * L, D))
+    t["out"] = e("out", (B * L, D))
+    t["mean"] = e("mean", (B * L,), f32)
+    t["rstd"] = e("rstd", (B * L,), f32)
     for k, v in t.items():
         setattr(d, k, v.data_ptr())
     e0 = _prof_begin()
@@ -1021,7 +1027,7 @@ def xattn_probs(saved):
     return out
 
 
-def xattn_bwd(dy, saved, B, L, Lo, P, need_dother=True):
+def xattn_bwd(dy, saved, B, L, Lo, P, need_dother=True, alloc=None):
     """Backward of xattn_fwd (m3ae_xattn_bwd): returns (dx, dother); parameter gradients accumulate in place."""
     _no_ordered_form("the fused cross-attention backward (m3ae_xattn_bwd; its forward ran before the mode was switched on)")
     _, h2, other2, mask, t, seeds, pdrop = saved
@@ -1029,20 +1035,21 @@ def xattn_bwd(dy, saved, B, L, Lo, P, need_dother=True):
     d = _xattn_desc(h2, B, L, other2, Lo, mask, P, pdrop, seeds)
     for k, v in t.items():
         setattr(d, k, v.data_ptr())
-    bf = torch.bfloat16
-    e = lambda *shape, dt=bf: torch.empty(shape, dtype=dt, device=dev)
+    f32 = torch.float32
+    e = alloc or _xattn_alloc(dev)
     dyc = dy.contiguous()
-    dx = e(B * L, D)
-    dother = e(B * Lo, D) if need_dother else None
+    dx = e("dx", (B * L, D))
+    dother = e("dy", (B * Lo, D)) if need_dother else None
     L_ = _lib.lib()
-    w = {"ws_ds": e(B * L, D), "ws_dscores": torch.empty_like(t["probs"]), "ws_dprime": torch.empty_like(t["prime"]),
-         "ws_dproj": torch.empty_like(t["proj"]), "ws_vec": e(3 * B * H * min(L, Lo), dt=torch.float32),
-         "ws_ln": e(2 * L_.m3ae_layernorm_bwd_blocks(B * L) * D, dt=torch.float32)}
+    w = {"ws_ds": e("ws_ds", (B * L, D)), "ws_dscores": e("ws_dscores", tuple(t["probs"].shape)),
+         "ws_dprime": e("ws_dprime", tuple(t["prime"].shape)), "ws_dproj": e("ws_dproj", tuple(t["proj"].shape)),
+         "ws_vec": e("ws_vec", (3 * B * H * min(L, Lo),), f32),
+         "ws_ln": e("ws_ln", (2 * L_.m3ae_layernorm_bwd_blocks(B * L) * D,), f32)}
     if pdrop > 0:
-        w["ws_dsd"] = e(B * L, D)
+        w["ws_dsd"] = e("ws_dsd", (B * L, D))
     if d.dir == 0:
-        w["ws_dz"] = torch.empty_like(t["zctx"])
-        w["ws_dctx"] = e(B * L, D)
+        w["ws_dz"] = e("ws_dz", tuple(t["zctx"].shape))
+        w["ws_dctx"] = e("ws_dctx", (B * L, D))
     for k, v in w.items():
         setattr(d, k, v.data_ptr())
     d.d_out, d.dx = dyc.data_ptr(), dx.data_ptr()

@@ -7,7 +7,9 @@
   (2) the unfused composition (m3ae_gemm + m3ae_attn_fwd + m3ae_gemm + m3ae_layernorm_fwd) under dropout with the same
       seeds: both paths apply the same counter-hash masks (same index conventions), so they agree to bf16 noise.
 Tolerance: the output is a LayerNorm output (rms 1); bf16 rounding of the intermediates gives rms errors of ~6e-3 and
-max errors of ~4e-2 for BOTH paths; the fused path is held to 1.5x the unfused path's rms error and an absolute 0.08."""
+max errors of ~4e-2 for BOTH paths; the fused path is held to 1.5x the unfused path's rms error and an absolute 0.08.
+The float64 reference, the rounding-model budget per tensor, the saved probabilities entry by entry, the buffer contracts and the
+envelope of m3ae_xattn_supported are in tests/test_gpu_xattn_accuracy.py (yardsticks: tests/xattn_accuracy.py)."""
 import math
 
 import pytest
