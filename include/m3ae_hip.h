@@ -80,7 +80,8 @@ const char* m3ae_last_gemm_path(void);
  *           if (dact_aux) x *= act'(dact_aux[m][n]) (derivative of `dact` at the saved pre-activation);
  *           if (accumulate) C += x else C = x.
  * Strides are in ELEMENTS.  preact / residual / dact_aux share C's strides and dtype.
- * a_rowsum (single-batch only): additionally accumulates the row sums of op(A) over the reduction -- for wgrad
+ * a_rowsum (single-batch only: M3AE_ERR_UNSUPPORTED, before any launch, with batch1 * batch2 != 1 -- the vector has no batch
+ * stride): additionally accumulates the row sums of op(A) over the reduction -- for wgrad
  * (A = dY^T) that is the bias gradient, so no separate column-sum pass over dY is needed.
  * Dispatch: bf16 A,B with K-contiguous operands (a_sk == b_sk == 1) -> MFMA "NT" kernel;
  *           bf16 A,B with reduction-strided operands (a_sm == b_sn == 1), fp32 C, accumulate -> MFMA "TN" (wgrad)
@@ -170,6 +171,11 @@ int m3ae_gemm_det(const m3ae_gemm_desc* d, void* workspace, int64_t workspace_by
  *   q [B, Lq, H*Dh], k / v [B, Lk, H*Dh] with explicit batch and token strides (head h at element offset h*Dh, Dh
  *   contiguous), so packed QKV buffers are addressed in place.  o like q.
  *   key_mask: additive fp32 [B, Lk] (the reference's (1-mask)*-10000.0 extended mask, m3ae_module.py:232) or NULL.
+ *             Contract: the values are ADDED to the scaled scores.  They are finite, with one exception: -inf on SOME keys of a
+ *             row (those probabilities are exactly 0), never on all keys of a row (the row maximum would be -inf and the row
+ *             NaN); +inf and NaN are not allowed.  -10000 on every key of a row is fine: the row maximum is subtracted before
+ *             the exponential, and the row comes out as the softmax of its unmasked scores, at the 2^-11 resolution fp32 has
+ *             beside 10000.  (Pinned on the fp32 path by tests/test_gpu_parity_accuracy.py, tier B1.)
  *   pos_bias: additive fp32 [H, Lq, Lk] or NULL.  lse: fp32 [B, H, lse_stride] (lse_stride >= Lq, multiple of 32).
  *   Dh must be 64 for the bf16 kernels.  workspace: see m3ae_attn_workspace_bytes (fp32 path only).
  */

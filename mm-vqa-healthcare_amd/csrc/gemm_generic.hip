@@ -4,6 +4,8 @@
 // within ~1e-6 of the reference's fp32 ATen path); (2) the odd shapes of "perf mode" that the MFMA kernels reject
 // (N = 498 answer logits, batched per-head products of the fp32 attention path, strided token-0 gathers of the
 // poolers).  LDS-tiled 64x64x16, 256 threads, 4x4 micro-tile per thread, arbitrary element strides.
+// The ascending-k claim is tested bit for bit (tests/test_gpu_parity_accuracy.py, tier A2): the kk loop below is one fmaf chain
+// per output element, k0 outer, kk inner; reordering it, or splitting the reduction, changes the bits that test pins.
 #include "common.h"
 
 namespace {

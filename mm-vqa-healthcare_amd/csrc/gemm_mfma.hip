@@ -934,6 +934,8 @@ extern "C" int m3ae_gemm_rows(const m3ae_gemm_desc* dp, int64_t row_base, int64_
     if (route == ROUTE_BAD_DIMS) return M3AE_ERR_ARG;
     const DropRows rows{row_base, row_step};
     if (!drop_rows_ok(rows, d.M, d.N)) return M3AE_ERR_ARG;
+    // a_rowsum is one fp32 [M] vector with no batch stride: every batch of a batched call would add into the same rows
+    if (d.a_rowsum && (d.batch1 != 1 || d.batch2 != 1)) return M3AE_ERR_UNSUPPORTED;
     // the tiled weight copy (tiled_b.h) is defined for one K-contiguous bf16 matrix with K % 32 == 0; the NT and the generic kernels read it
     if ((d.launch_flags & M3AE_GEMM_B_TILED) &&
         (d.dtype_a != M3AE_BF16 || d.dtype_b != M3AE_BF16 || d.b_sk != 1 || d.b_sn != d.K || d.K % 32 != 0 || d.batch1 != 1 ||
