@@ -319,8 +319,15 @@ int m3ae_xattn_probs_export(const m3ae_xattn_desc* d, int dropped, float* out, i
  * bwd: dx = LN'(dy) (+ dx_add: the residual branch's gradient of a pre-LN block, fused); dgamma / dbeta are
  * ACCUMULATED (+=) in fp32 (dgamma may be NULL for frozen parameters).  workspace: fp32 [2 * nblk * D] with
  * nblk = m3ae_layernorm_bwd_blocks(M).  rms != 0 selects T5 RMSNorm (no mean subtraction, no beta).
- * Row arrays (x, y, dy, dx, dx_add, dx_drop) are 16-byte aligned for M3AE_F32 and 8-byte aligned for M3AE_BF16, gamma / beta
- * 16-byte aligned: M3AE_ERR_ALIGN otherwise, before any launch.
+ *
+ * The family: m3ae_layernorm_fwd / _bwd; _bwd_drop and _bwd_drop_rows (a second output under a dropout mask); _fwd_mixed / _bwd_mixed
+ * (fp32 rows next to bf16 rows); and, declared with the deterministic mode below, _bwd_det / _bwd_drop_det / _bwd_mixed_det (the
+ * same calls with the dgamma / dbeta fold in a fixed order).  Every one of them checks in this order, before any launch:
+ *   1. M3AE_ERR_ARG: a required pointer is NULL, M <= 0 (the forwards: D <= 0), or a bad row map.  Required: x, gamma, y of a
+ *      forward; dy, x, gamma, rstd, dx, workspace of a backward, plus dx_drop of the dropout forms and mean of the mixed forms.
+ *   2. M3AE_ERR_UNSUPPORTED: D % 4 != 0, D > 4096 (m3ae_layernorm_fwd) or D > 2048 (every other call), an unknown dtype.
+ *   3. M3AE_ERR_ALIGN: every array is aligned to 4 of its own elements -- fp32 rows, gamma and beta to 16 bytes, bf16 rows to 8 bytes
+ *      (a NULL optional array counts as aligned).
  */
 int m3ae_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
                        int64_t M, int64_t D, float eps, int dtype, int act, int rms, void* stream);
@@ -340,8 +347,7 @@ int m3ae_layernorm_bwd_drop_rows(const void* dy, const void* x, const float* gam
                                  const void* dropout_salt, float* dgamma, float* dbeta, float* workspace, int64_t M, int64_t D,
                                  int dtype, int64_t row_base, int64_t row_step, void* stream);
 /* fp32 residual stream of a bf16 model (ABI 4, additive): the LayerNorm between fp32 rows and bf16 GEMM operands, plain LayerNorm
- * only (no activation, no RMS mode), D % 4 == 0, D <= 2048; x / dx / dx_add 16-byte aligned, the bf16 arrays 8-byte aligned
- * (M3AE_ERR_ALIGN otherwise).
+ * only (no activation, no RMS mode); x / dx / dx_add are the fp32 rows, y / dy / dx_lo the bf16 rows of the checks above.
  * fwd_mixed: x fp32 [M][D] -> y bf16 [M][D] = rne_bf16 of what m3ae_layernorm_fwd (M3AE_F32) writes for x, from the same fp32
  *   arithmetic in the same order; mean / rstd are that call's, bit for bit.
  * bwd_mixed: dy bf16 (what a dgrad GEMM wrote), x fp32 (the saved stream), dx_add fp32 (the stream's gradient, may be NULL) ->
@@ -614,8 +620,8 @@ int m3ae_mim_loss_bwd(const void* x, const float* target, const float* mask, con
  * that depends on the shapes alone.  m3ae_det_workspace_bytes(op, rows, cols) gives the size (touches no device):
  *   M3AE_DET_COLSUM (M, N); M3AE_DET_EMBED_BWD (B * S, D); M3AE_DET_BCE (B, C); M3AE_DET_XENT (rows, C) -- this workspace
  *   replaces m3ae_xent's float[1]; M3AE_DET_MIM (B * L, D).
- * m3ae_layernorm_bwd_det / _drop_det: the dgamma / dbeta fold walks all partial rows of `workspace` (sized as for
- *   m3ae_layernorm_bwd) in one workgroup per 32 columns.
+ * m3ae_layernorm_bwd_det / _drop_det (and _bwd_mixed_det above): the dgamma / dbeta fold walks all partial rows of `workspace`
+ *   (sized as for m3ae_layernorm_bwd) in one workgroup per 32 columns; arguments and checks: the LayerNorm section.
  * m3ae_roberta_embed_bwd_det: the first token that carries a word id (position id) owns that table row and adds the rows of
  *   all tokens with the same id in ascending token order, then adds the sum into the table: no atomics, any duplicates.
  *   D <= 2048.

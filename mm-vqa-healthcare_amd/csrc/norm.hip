@@ -8,6 +8,7 @@
 #include "common.h"
 #include "det_fold.h"
 #include "launch.h"
+#include "ln_limits.h"
 #include <initializer_list>
 #include <type_traits>
 
@@ -381,70 +382,38 @@ template <typename K> int resident_blocks(K kernel, size_t lds) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, lds) != hipSuccess || per_cu <= 0) return 1 << 30;
     return per_cu * device_cus();
 }
-template <typename T, int CPL, typename TO = T>
-int launch_fwd(const void* x, const float* g, const float* b, void* y, float* mean, float* rstd, int64_t M, int D,
-               float eps, int act, int rms, hipStream_t s) {
-    static const int cap = resident_blocks(ln_fwd_kernel<T, CPL, TO>, 0);
-    const int64_t want = cdiv(M, 4);
-    hipLaunchKernelGGL((ln_fwd_kernel<T, CPL, TO>), dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, s, (const T*)x, g, b,
-                       (TO*)y, mean, rstd, M, D, eps, act, rms);
-    return hip_launch_status();
+
+// The dispatches of a call, each handing its choice to a generic lambda as a type (attention.hip's `pick` idiom).
+// Row types: T for the rows of x (and dx, dx_add, dx_drop), TO for the rows on the other side (y of a forward, dy of a backward).
+// The fp32-stream forms are T = float with TO = bf16; no other mix has a kernel.
+template <typename T, typename TO = T> struct LnTypes { using row = T; using other = TO; };
+template <class F> int pick_types(int row_dtype, int other_dtype, F&& f) {
+    if (row_dtype == M3AE_F32 && other_dtype == M3AE_F32) return f(LnTypes<float>{});
+    if (row_dtype == M3AE_BF16 && other_dtype == M3AE_BF16) return f(LnTypes<bf16_t>{});
+    if (row_dtype == M3AE_F32 && other_dtype == M3AE_BF16) return f(LnTypes<float, bf16_t>{});
+    return M3AE_ERR_UNSUPPORTED;
 }
-template <typename T, int CPL, typename TD = T>
-int launch_bwd(const void* dy, const void* x, const float* g, const float* b, const float* mean, const float* rstd,
-               void* dx, const void* dx_add, float* part, int* nblk_io, int64_t M, int D, int act, int rms, hipStream_t s,
-               void* dx_drop = nullptr, DropState drop = DropState{}, void* dx_lo = nullptr) {
-    const size_t lds = (size_t)8 * D * sizeof(float);
-    static int cap_act = 0, cap_plain = 0, cap_d = -1;   // per instantiation; the LDS size follows D
-    constexpr bool MIXED = !std::is_same<TD, T>::value;   // the fp32-stream form is plain LayerNorm: no ACT instantiation of it
-    if (cap_d != D) {
-        if constexpr (!MIXED) cap_act = resident_blocks(ln_bwd_kernel<T, CPL, true, TD>, lds);
-        cap_plain = resident_blocks(ln_bwd_kernel<T, CPL, false, TD>, lds);
-        cap_d = D;
-    }
-    const int cap = act != M3AE_ACT_NONE ? cap_act : cap_plain;
-    const int nblk = *nblk_io < cap ? *nblk_io : cap;
-    *nblk_io = nblk;
-    if constexpr (MIXED) {
-        if (act != M3AE_ACT_NONE) return M3AE_ERR_UNSUPPORTED;
-    }
-    if (act != M3AE_ACT_NONE) {
-        if constexpr (!MIXED)
-            hipLaunchKernelGGL((ln_bwd_kernel<T, CPL, true, TD>), dim3((unsigned)nblk), dim3(256), lds, s,
-                               (const TD*)dy, (const T*)x, g, b, mean, rstd, (T*)dx, (const T*)dx_add, part, M, D, act, rms,
-                               (T*)dx_drop, drop, (bf16_t*)dx_lo);
-    } else
-        hipLaunchKernelGGL((ln_bwd_kernel<T, CPL, false, TD>), dim3((unsigned)nblk), dim3(256), lds, s,
-                           (const TD*)dy, (const T*)x, g, b, mean, rstd, (T*)dx, (const T*)dx_add, part, M, D, act, rms,
-                           (T*)dx_drop, drop, (bf16_t*)dx_lo);
-    return hip_launch_status();
+// CPL, the 4-element chunks a lane holds of a row of D elements
+template <int N> using cpl_c = std::integral_constant<int, N>;
+template <class F> int pick_cpl(int D, F&& f) {
+    const int cpl = (int)cdiv(D / 4, 64);
+    if (cpl <= 1) return f(cpl_c<1>{});
+    if (cpl <= 2) return f(cpl_c<2>{});
+    if (cpl <= 3) return f(cpl_c<3>{});
+    if (cpl <= 4) return f(cpl_c<4>{});
+    if (cpl <= 6) return f(cpl_c<6>{});
+    if (cpl <= 8) return f(cpl_c<8>{});
+    if (cpl <= 16) return f(cpl_c<16>{});
+    return M3AE_ERR_UNSUPPORTED;
 }
 
-// the fp32-stream forms as launchers of the DISPATCH_CPL shape (T = float throughout)
-template <typename T, int CPL>
-int launch_fwd_mixed(const void* x, const float* g, const float* b, void* y, float* mean, float* rstd, int64_t M, int D, float eps,
-                     hipStream_t s) {
-    return launch_fwd<T, CPL, bf16_t>(x, g, b, y, mean, rstd, M, D, eps, M3AE_ACT_NONE, 0, s);
+// The one alignment rule: an array of T is aligned to 4 of its elements, the chunk the kernels load and store (16 bytes of fp32 rows,
+// gamma and beta; 8 bytes of bf16 rows).  A null pointer counts as aligned.
+template <typename T> bool aligned4(std::initializer_list<const void*> arrays) {
+    uintptr_t bits = 0;
+    for (const void* p : arrays) bits |= (uintptr_t)p;
+    return (bits & (4 * sizeof(T) - 1)) == 0;
 }
-template <typename T, int CPL>
-int launch_bwd_mixed(const void* dy, const void* x, const float* g, const float* mean, const float* rstd, void* dx, const void* dx_add,
-                     void* dx_lo, float* part, int* nblk_io, int64_t M, int D, hipStream_t s) {
-    return launch_bwd<T, CPL, bf16_t>(dy, x, g, nullptr, mean, rstd, dx, dx_add, part, nblk_io, M, D, M3AE_ACT_NONE, 0, s, nullptr,
-                                      DropState{}, dx_lo);
-}
-
-#define DISPATCH_CPL(FN, T, ...)                                                  \
-    do {                                                                          \
-        const int cpl = (int)cdiv(D / 4, 64);                                     \
-        if (cpl <= 1) return FN<T, 1>(__VA_ARGS__);                               \
-        if (cpl <= 2) return FN<T, 2>(__VA_ARGS__);                               \
-        if (cpl <= 3) return FN<T, 3>(__VA_ARGS__);                               \
-        if (cpl <= 4) return FN<T, 4>(__VA_ARGS__);                               \
-        if (cpl <= 6) return FN<T, 6>(__VA_ARGS__);                               \
-        if (cpl <= 8) return FN<T, 8>(__VA_ARGS__);                               \
-        if (cpl <= 16) return FN<T, 16>(__VA_ARGS__);                             \
-        return M3AE_ERR_UNSUPPORTED;                                              \
-    } while (0)
 
 }  // namespace
 
@@ -458,33 +427,53 @@ int launch_fwd_pair(const void* x, const float* g, const float* b, void* y, floa
     return hip_launch_status();
 }
 
-// Alignment the row kernels load with: 4-element chunks = 16 bytes of fp32 rows, 8 bytes of bf16 rows; gamma / beta always 16
-// bytes.  Checked before any launch (a null pointer counts as aligned).
-static bool ln_rows_aligned(int dtype, std::initializer_list<const void*> rows, std::initializer_list<const void*> params) {
-    uintptr_t r = 0, q = 0;
-    for (const void* p : rows) r |= (uintptr_t)p;
-    for (const void* p : params) q |= (uintptr_t)p;
-    return (r & (dtype == M3AE_F32 ? 15u : 7u)) == 0 && (q & 15u) == 0;
+// Every export below fills a call record and hands it to the runner of its direction.  The runners refuse in one order, before any
+// launch: M3AE_ERR_ARG (a pointer every form needs is null, M <= 0, a bad row map; an export first refuses the null pointers only
+// its own form needs), then M3AE_ERR_UNSUPPORTED (D % 4, D over the form's limit, row types without a kernel), then M3AE_ERR_ALIGN.
+struct LnFwdCall {
+    const void* x; const float *gamma, *beta; void* y; float *mean, *rstd;
+    int64_t M, D; float eps;
+    int x_dtype, y_dtype, act, rms, max_d;   // max_d: the export's width limit (ln_limits.h)
+    void* stream;
+};
+
+static int ln_fwd_run(const LnFwdCall& c) {
+    if (!c.x || !c.gamma || !c.y || c.M <= 0 || c.D <= 0) return M3AE_ERR_ARG;
+    if (c.D % 4 != 0 || c.D > c.max_d) return M3AE_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)c.stream;
+    const int D = (int)c.D, rms = c.rms & 1;
+    const bool pair_off = (c.rms & 2) != 0;   // rms bit 1: diagnostic A / B of the row-pair kernel (tools/ln_bench.py)
+    return pick_types(c.x_dtype, c.y_dtype, [&](auto types) -> int {
+        using T = typename decltype(types)::row;
+        using TO = typename decltype(types)::other;
+        if (!aligned4<T>({c.x}) || !aligned4<TO>({c.y}) || !aligned4<float>({c.gamma, c.beta})) return M3AE_ERR_ALIGN;
+        if constexpr (std::is_same<T, bf16_t>::value) {   // the row-pair kernel: plain LayerNorm of many rows whose pairs sit on 16 bytes
+            if (c.act == M3AE_ACT_NONE && !rms && c.M >= 1024 && ((((uintptr_t)c.x) | ((uintptr_t)c.y)) & 15) == 0 && !pair_off) {
+                if (D == 512) return launch_fwd_pair<2>(c.x, c.gamma, c.beta, c.y, c.mean, c.rstd, c.M, c.eps, s);
+                if (D == 768) return launch_fwd_pair<3>(c.x, c.gamma, c.beta, c.y, c.mean, c.rstd, c.M, c.eps, s);
+                if (D == 1024) return launch_fwd_pair<4>(c.x, c.gamma, c.beta, c.y, c.mean, c.rstd, c.M, c.eps, s);
+            }
+        }
+        return pick_cpl(D, [&](auto cpl) {
+            constexpr auto kernel = ln_fwd_kernel<T, decltype(cpl)::value, TO>;
+            static const int cap = resident_blocks(kernel, 0);
+            const int64_t want = cdiv(c.M, 4);
+            hipLaunchKernelGGL(kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(256), 0, s, (const T*)c.x, c.gamma, c.beta, (TO*)c.y,
+                               c.mean, c.rstd, c.M, D, c.eps, c.act, rms);
+            return hip_launch_status();
+        });
+    });
 }
 
 extern "C" int m3ae_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean,
                                   float* rstd, int64_t M, int64_t D, float eps, int dtype, int act, int rms,
                                   void* stream) {
-    if (!x || !gamma || !y || M <= 0 || D <= 0) return M3AE_ERR_ARG;
-    if (D % 4 != 0 || D > 4096) return M3AE_ERR_UNSUPPORTED;
-    if (!ln_rows_aligned(dtype, {x, y}, {gamma, beta})) return M3AE_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    const bool pair_off = (rms & 2) != 0;   // rms bit 1: diagnostic A / B of the row-pair kernel (tools/ln_bench.py)
-    rms &= 1;
-    if (dtype == M3AE_BF16 && act == M3AE_ACT_NONE && !rms && M >= 1024 && ((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0 &&
-        ((((uintptr_t)gamma) | ((uintptr_t)beta)) & 15) == 0 && !pair_off) {
-        if (D == 512) return launch_fwd_pair<2>(x, gamma, beta, y, mean, rstd, M, eps, s);
-        if (D == 768) return launch_fwd_pair<3>(x, gamma, beta, y, mean, rstd, M, eps, s);
-        if (D == 1024) return launch_fwd_pair<4>(x, gamma, beta, y, mean, rstd, M, eps, s);
-    }
-    if (dtype == M3AE_F32) DISPATCH_CPL(launch_fwd, float, x, gamma, beta, y, mean, rstd, M, (int)D, eps, act, rms, s);
-    if (dtype == M3AE_BF16) DISPATCH_CPL(launch_fwd, bf16_t, x, gamma, beta, y, mean, rstd, M, (int)D, eps, act, rms, s);
-    return M3AE_ERR_UNSUPPORTED;
+    return ln_fwd_run({x, gamma, beta, y, mean, rstd, M, D, eps, dtype, dtype, act, rms, LN_FWD_MAX_D, stream});
+}
+// fp32 residual stream of a bf16 model: fp32 rows in, bf16 rows out (plain LayerNorm; the arithmetic of the fp32 kernel, rounded once)
+extern "C" int m3ae_layernorm_fwd_mixed(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
+                                        int64_t M, int64_t D, float eps, void* stream) {
+    return ln_fwd_run({x, gamma, beta, y, mean, rstd, M, D, eps, M3AE_F32, M3AE_BF16, M3AE_ACT_NONE, 0, LN_FWD_MIXED_MAX_D, stream});
 }
 
 extern "C" int64_t m3ae_layernorm_bwd_blocks(int64_t M) {
@@ -494,121 +483,105 @@ extern "C" int64_t m3ae_layernorm_bwd_blocks(int64_t M) {
     return n < 1024 ? n : 1024;
 }
 
-static int layernorm_bwd_impl(const void* dy, const void* x, const float* gamma, const float* beta, const float* mean,
-                              const float* rstd, void* dx, const void* dx_add, float* dgamma, float* dbeta, float* workspace,
-                              int64_t M, int64_t D, int dtype, int act, int rms, void* stream, int det) {
-    if (!dy || !x || !gamma || !rstd || !dx || !workspace || M <= 0) return M3AE_ERR_ARG;
-    if (D % 4 != 0 || D > 2048) return M3AE_ERR_UNSUPPORTED;
-    if (!ln_rows_aligned(dtype, {dy, x, dx, dx_add}, {gamma, beta})) return M3AE_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    int nblk = (int)m3ae_layernorm_bwd_blocks(M);   // upper bound (the workspace is sized for it); launch_bwd may lower it
-    int rc = M3AE_ERR_UNSUPPORTED;
-    auto run = [&]() -> int {
-        if (dtype == M3AE_F32)
-            DISPATCH_CPL(launch_bwd, float, dy, x, gamma, beta, mean, rstd, dx, dx_add, workspace, &nblk, M, (int)D, act, rms, s);
-        if (dtype == M3AE_BF16)
-            DISPATCH_CPL(launch_bwd, bf16_t, dy, x, gamma, beta, mean, rstd, dx, dx_add, workspace, &nblk, M, (int)D, act, rms, s);
-        return M3AE_ERR_UNSUPPORTED;
-    };
-    rc = run();
-    if (rc) return rc;
-    if (!dgamma) return 0;
-    return ln_bwd_fold(workspace, dgamma, dbeta, nblk, (int)D, det, s);
+// dx_drop (with its mask and row map in `drop`) and dx_lo are the optional second outputs of the dropout and fp32-stream forms;
+// det picks the fold of dgamma / dbeta.  All of them are independent fields here: the exports fix the combinations that exist.
+struct LnBwdCall {
+    const void *dy, *x; const float *gamma, *beta, *mean, *rstd;
+    void* dx; const void* dx_add; float *dgamma, *dbeta, *workspace;
+    int64_t M, D;
+    int x_dtype, dy_dtype, act, rms, det;   // x_dtype: the rows of x, dx, dx_add and dx_drop
+    void* stream;
+    void* dx_drop = nullptr; DropState drop = DropState{}; void* dx_lo = nullptr;
+};
+
+static int ln_bwd_run(const LnBwdCall& c) {
+    if (!c.dy || !c.x || !c.gamma || !c.rstd || !c.dx || !c.workspace || c.M <= 0) return M3AE_ERR_ARG;
+    if (c.dx_drop && !drop_rows_ok(DropRows{c.drop.row_base, c.drop.row_step}, c.M, c.D)) return M3AE_ERR_ARG;
+    if (c.D % 4 != 0 || c.D > LN_BWD_MAX_D) return M3AE_ERR_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)c.stream;
+    const int D = (int)c.D;
+    return pick_types(c.x_dtype, c.dy_dtype, [&](auto types) -> int {
+        using T = typename decltype(types)::row;
+        using TD = typename decltype(types)::other;
+        if (!aligned4<T>({c.x, c.dx, c.dx_add, c.dx_drop}) || !aligned4<TD>({c.dy}) || !aligned4<bf16_t>({c.dx_lo}) ||
+            !aligned4<float>({c.gamma, c.beta}))
+            return M3AE_ERR_ALIGN;
+        int nblk = (int)m3ae_layernorm_bwd_blocks(c.M);   // upper bound (the workspace is sized for it); the resident cap may lower it
+        auto launch = [&](auto cpl, auto with_act) -> int {
+            // the fp32-stream form is plain LayerNorm: no ACT instantiation of it
+            if constexpr (decltype(with_act)::value && !std::is_same<TD, T>::value) return M3AE_ERR_UNSUPPORTED;
+            else {
+                constexpr auto kernel = ln_bwd_kernel<T, decltype(cpl)::value, decltype(with_act)::value, TD>;
+                const size_t lds = (size_t)8 * D * sizeof(float);
+                static int cap = 0, cap_d = -1;   // per instantiation; the LDS size follows D
+                if (cap_d != D) { cap = resident_blocks(kernel, lds); cap_d = D; }
+                if (cap < nblk) nblk = cap;
+                hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(256), lds, s, (const TD*)c.dy, (const T*)c.x, c.gamma, c.beta, c.mean,
+                                   c.rstd, (T*)c.dx, (const T*)c.dx_add, c.workspace, c.M, D, c.act, c.rms, (T*)c.dx_drop, c.drop,
+                                   (bf16_t*)c.dx_lo);
+                return hip_launch_status();
+            }
+        };
+        const int rc = pick_cpl(D, [&](auto cpl) {
+            return c.act != M3AE_ACT_NONE ? launch(cpl, std::true_type{}) : launch(cpl, std::false_type{});
+        });
+        if (rc || !c.dgamma) return rc;
+        return ln_bwd_fold(c.workspace, c.dgamma, c.dbeta, nblk, D, c.det, s);
+    });
 }
+
 extern "C" int m3ae_layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* beta,
                                   const float* mean, const float* rstd, void* dx, const void* dx_add, float* dgamma,
                                   float* dbeta, float* workspace, int64_t M, int64_t D, int dtype, int act, int rms,
                                   void* stream) {
-    return layernorm_bwd_impl(dy, x, gamma, beta, mean, rstd, dx, dx_add, dgamma, dbeta, workspace, M, D, dtype, act, rms, stream, 0);
+    return ln_bwd_run({dy, x, gamma, beta, mean, rstd, dx, dx_add, dgamma, dbeta, workspace, M, D, dtype, dtype, act, rms, 0, stream});
 }
 extern "C" int m3ae_layernorm_bwd_det(const void* dy, const void* x, const float* gamma, const float* beta,
                                       const float* mean, const float* rstd, void* dx, const void* dx_add, float* dgamma,
                                       float* dbeta, float* workspace, int64_t M, int64_t D, int dtype, int act, int rms,
                                       void* stream) {
-    return layernorm_bwd_impl(dy, x, gamma, beta, mean, rstd, dx, dx_add, dgamma, dbeta, workspace, M, D, dtype, act, rms, stream, 1);
+    return ln_bwd_run({dy, x, gamma, beta, mean, rstd, dx, dx_add, dgamma, dbeta, workspace, M, D, dtype, dtype, act, rms, 1, stream});
 }
 
-static int layernorm_bwd_drop_impl(const void* dy, const void* x, const float* gamma, const float* beta, const float* mean,
-                                   const float* rstd, void* dx, void* dx_drop, float dropout_p, uint64_t dropout_seed,
-                                   const void* dropout_salt, float* dgamma, float* dbeta, float* workspace, int64_t M, int64_t D,
-                                   int dtype, void* stream, int det, DropRows rows = DropRows{0, 1}) {
-    if (!dy || !x || !gamma || !rstd || !dx || !dx_drop || !workspace || M <= 0) return M3AE_ERR_ARG;
-    if (!drop_rows_ok(rows, M, D)) return M3AE_ERR_ARG;
-    if (D % 4 != 0 || D > 2048) return M3AE_ERR_UNSUPPORTED;
-    if (!ln_rows_aligned(dtype, {dy, x, dx, dx_drop}, {gamma, beta})) return M3AE_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    int nblk = (int)m3ae_layernorm_bwd_blocks(M);
-    const DropState drop = make_drop(dropout_p, dropout_seed, dropout_salt, rows);
-    auto run = [&]() -> int {
-        if (dtype == M3AE_F32)
-            DISPATCH_CPL(launch_bwd, float, dy, x, gamma, beta, mean, rstd, dx, nullptr, workspace, &nblk, M, (int)D, 0, 0, s, dx_drop, drop);
-        if (dtype == M3AE_BF16)
-            DISPATCH_CPL(launch_bwd, bf16_t, dy, x, gamma, beta, mean, rstd, dx, nullptr, workspace, &nblk, M, (int)D, 0, 0, s, dx_drop, drop);
-        return M3AE_ERR_UNSUPPORTED;
-    };
-    int rc = run();
-    if (rc) return rc;
-    if (!dgamma) return 0;
-    return ln_bwd_fold(workspace, dgamma, dbeta, nblk, (int)D, det, s);
-}
+// the dropout forms need dx_drop (a null mean is not refused, as in the plain form, where an RMS call has none)
 extern "C" int m3ae_layernorm_bwd_drop(const void* dy, const void* x, const float* gamma, const float* beta,
                                        const float* mean, const float* rstd, void* dx, void* dx_drop, float dropout_p,
                                        uint64_t dropout_seed, const void* dropout_salt, float* dgamma, float* dbeta,
                                        float* workspace, int64_t M, int64_t D, int dtype, void* stream) {
-    return layernorm_bwd_drop_impl(dy, x, gamma, beta, mean, rstd, dx, dx_drop, dropout_p, dropout_seed, dropout_salt, dgamma, dbeta,
-                                   workspace, M, D, dtype, stream, 0);
+    if (!dx_drop) return M3AE_ERR_ARG;
+    return ln_bwd_run({dy, x, gamma, beta, mean, rstd, dx, nullptr, dgamma, dbeta, workspace, M, D, dtype, dtype, M3AE_ACT_NONE, 0, 0, stream,
+                       dx_drop, make_drop(dropout_p, dropout_seed, dropout_salt)});
 }
 extern "C" int m3ae_layernorm_bwd_drop_rows(const void* dy, const void* x, const float* gamma, const float* beta,
                                             const float* mean, const float* rstd, void* dx, void* dx_drop, float dropout_p,
                                             uint64_t dropout_seed, const void* dropout_salt, float* dgamma, float* dbeta,
                                             float* workspace, int64_t M, int64_t D, int dtype, int64_t row_base, int64_t row_step,
                                             void* stream) {
-    return layernorm_bwd_drop_impl(dy, x, gamma, beta, mean, rstd, dx, dx_drop, dropout_p, dropout_seed, dropout_salt, dgamma, dbeta,
-                                   workspace, M, D, dtype, stream, 0, DropRows{row_base, row_step});
+    if (!dx_drop) return M3AE_ERR_ARG;
+    return ln_bwd_run({dy, x, gamma, beta, mean, rstd, dx, nullptr, dgamma, dbeta, workspace, M, D, dtype, dtype, M3AE_ACT_NONE, 0, 0, stream,
+                       dx_drop, make_drop(dropout_p, dropout_seed, dropout_salt, DropRows{row_base, row_step})});
 }
 extern "C" int m3ae_layernorm_bwd_drop_det(const void* dy, const void* x, const float* gamma, const float* beta,
                                            const float* mean, const float* rstd, void* dx, void* dx_drop, float dropout_p,
                                            uint64_t dropout_seed, const void* dropout_salt, float* dgamma, float* dbeta,
                                            float* workspace, int64_t M, int64_t D, int dtype, void* stream) {
-    return layernorm_bwd_drop_impl(dy, x, gamma, beta, mean, rstd, dx, dx_drop, dropout_p, dropout_seed, dropout_salt, dgamma, dbeta,
-                                   workspace, M, D, dtype, stream, 1);
+    if (!dx_drop) return M3AE_ERR_ARG;
+    return ln_bwd_run({dy, x, gamma, beta, mean, rstd, dx, nullptr, dgamma, dbeta, workspace, M, D, dtype, dtype, M3AE_ACT_NONE, 0, 1, stream,
+                       dx_drop, make_drop(dropout_p, dropout_seed, dropout_salt)});
 }
 
-// fp32 residual stream of a bf16 model: fp32 rows in, bf16 rows out (plain LayerNorm; the arithmetic of the fp32 kernel, rounded once)
-extern "C" int m3ae_layernorm_fwd_mixed(const float* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd,
-                                        int64_t M, int64_t D, float eps, void* stream) {
-    if (!x || !gamma || !y || M <= 0 || D <= 0) return M3AE_ERR_ARG;
-    if (D % 4 != 0 || D > 2048) return M3AE_ERR_UNSUPPORTED;
-    if (((((uintptr_t)x) | ((uintptr_t)gamma) | ((uintptr_t)beta)) & 15) != 0 || (((uintptr_t)y) & 7) != 0) return M3AE_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    DISPATCH_CPL(launch_fwd_mixed, float, x, gamma, beta, y, mean, rstd, M, (int)D, eps, s);
-}
-
-static int layernorm_bwd_mixed_impl(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
-                                    float* dx, const float* dx_add, void* dx_lo, float* dgamma, float* dbeta, float* workspace,
-                                    int64_t M, int64_t D, void* stream, int det) {
-    if (!dy || !x || !gamma || !mean || !rstd || !dx || !workspace || M <= 0) return M3AE_ERR_ARG;
-    if (D % 4 != 0 || D > 2048) return M3AE_ERR_UNSUPPORTED;
-    if (((((uintptr_t)x) | ((uintptr_t)dx) | ((uintptr_t)dx_add) | ((uintptr_t)gamma)) & 15) != 0 ||
-        ((((uintptr_t)dy) | ((uintptr_t)dx_lo)) & 7) != 0)
-        return M3AE_ERR_ALIGN;
-    hipStream_t s = (hipStream_t)stream;
-    int nblk = (int)m3ae_layernorm_bwd_blocks(M);
-    auto run = [&]() -> int {
-        DISPATCH_CPL(launch_bwd_mixed, float, dy, x, gamma, mean, rstd, dx, dx_add, dx_lo, workspace, &nblk, M, (int)D, s);
-    };
-    int rc = run();
-    if (rc) return rc;
-    if (!dgamma) return 0;
-    return ln_bwd_fold(workspace, dgamma, dbeta, nblk, (int)D, det, s);
-}
+// the fp32-stream forms (fp32 x / dx / dx_add, bf16 dy / dx_lo, no beta in the arithmetic) need mean
 extern "C" int m3ae_layernorm_bwd_mixed(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
                                         float* dx, const float* dx_add, void* dx_lo, float* dgamma, float* dbeta, float* workspace,
                                         int64_t M, int64_t D, void* stream) {
-    return layernorm_bwd_mixed_impl(dy, x, gamma, mean, rstd, dx, dx_add, dx_lo, dgamma, dbeta, workspace, M, D, stream, 0);
+    if (!mean) return M3AE_ERR_ARG;
+    return ln_bwd_run({dy, x, gamma, nullptr, mean, rstd, dx, dx_add, dgamma, dbeta, workspace, M, D, M3AE_F32, M3AE_BF16, M3AE_ACT_NONE, 0, 0,
+                       stream, nullptr, DropState{}, dx_lo});
 }
 extern "C" int m3ae_layernorm_bwd_mixed_det(const void* dy, const float* x, const float* gamma, const float* mean, const float* rstd,
                                             float* dx, const float* dx_add, void* dx_lo, float* dgamma, float* dbeta,
                                             float* workspace, int64_t M, int64_t D, void* stream) {
-    return layernorm_bwd_mixed_impl(dy, x, gamma, mean, rstd, dx, dx_add, dx_lo, dgamma, dbeta, workspace, M, D, stream, 1);
+    if (!mean) return M3AE_ERR_ARG;
+    return ln_bwd_run({dy, x, gamma, nullptr, mean, rstd, dx, dx_add, dgamma, dbeta, workspace, M, D, M3AE_F32, M3AE_BF16, M3AE_ACT_NONE, 0, 1,
+                       stream, nullptr, DropState{}, dx_lo});
 }

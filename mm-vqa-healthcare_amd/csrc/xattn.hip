@@ -24,6 +24,7 @@
 // ds_read_b64_tr_b16) and the epilogue as template parameters.
 #include "xattn_common.h"
 #include "launch.h"
+#include "ln_limits.h"
 
 namespace {
 
@@ -1035,7 +1036,7 @@ extern "C" int m3ae_xattn_supported(const m3ae_xattn_desc* d) {
     // threads to dh columns x 256 / dh row lanes, which is no lane at all from dh = 288 on -- the gradients of b_v (dir 0) and b_q
     // (dir 1) would stay zero.  No configuration of the product is wider than 64; every width up to 256 is tested.
     if (dh > 256) return 0;
-    if (d->D > 4096) return 0;   // the closing m3ae_layernorm_fwd covers rows of up to 4096 elements
+    if (d->D > LN_FWD_MAX_D) return 0;   // the closing m3ae_layernorm_fwd
     if (d->dir == 0) return ((T == 32 || T == 64) && I <= 640) ? 1 : 0;   // text queries: the whole-row score tile covers 640 keys
     // image queries (xflash.hip): 32 text keys (fine-tuning) or 64 (pre-training), any number of image tokens
     if (d->launch_flags & M3AE_XATTN_LEGACY_CHAIN) return (T == 32 && I <= 640) ? 1 : 0;
@@ -1044,9 +1045,9 @@ extern "C" int m3ae_xattn_supported(const m3ae_xattn_desc* d) {
 
 extern "C" int m3ae_xattn_bwd_supported(const m3ae_xattn_desc* d) {
     if (!m3ae_xattn_supported(d)) return 0;
-    // m3ae_layernorm_bwd(_drop), the first call of the backward, covers rows of up to 2048 elements: wider layers answered 1 here and
-    // then failed in m3ae_xattn_bwd with M3AE_ERR_UNSUPPORTED; they take the composition for training now (forward-only calls stay fused)
-    if (d->D > 2048) return 0;
+    // m3ae_layernorm_bwd(_drop) is the first call of the backward: layers wider than its rows take the composition for training
+    // (forward-only calls stay fused)
+    if (d->D > LN_BWD_MAX_D) return 0;
     return 1;   // round 3: 32 or 64 text tokens in both directions (the softmax-backward epilogue sums 32- or 64-column groups)
 }
 

@@ -653,14 +653,26 @@ def ln_fwd_raw(x2, ln, act=ACT_NONE, rms=False, out_dtype=None, rms_mean=False):
     y = torch.empty_like(x2, dtype=out_dtype or x2.dtype)
     mean = None if rms and not rms_mean else torch.empty(M, dtype=torch.float32, device=x2.device)
     rstd = torch.empty(M, dtype=torch.float32, device=x2.device)
+    head = (_p(x2), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), M, D, eps)
     if y.dtype != x2.dtype:   # fp32 rows -> bf16 rows (the fp32 residual stream of a bf16 CLIP tower)
         _ln_mixed_ok(x2, y, act, rms)
-        check(_lib.lib().m3ae_layernorm_fwd_mixed(_p(x2), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), M, D, eps, _stream()),
-              "LayerNorm forward (mixed form)")
+        check(_lib.lib().m3ae_layernorm_fwd_mixed(*head, _stream()), "LayerNorm forward (mixed form)")
     else:
-        check(_lib.lib().m3ae_layernorm_fwd(_p(x2), _p(gamma), _p(beta), _p(y), _p(mean), _p(rstd), M, D, eps, _dt(x2), act,
-                                            int(rms), _stream()), "LayerNorm forward")
+        check(_lib.lib().m3ae_layernorm_fwd(*head, _dt(x2), act, int(rms), _stream()), "LayerNorm forward")
     return y, mean, rstd
+
+
+# The backward's choice.  form: (atomic entry, ordered entry -- None: there is none --, the call's label in an error, the entry's
+# arguments between (dy, x, gamma) and the stream, by the names ln_bwd_raw gives them).
+_LN_DROP_ARGS = "beta mean rstd dx second p seed salt dgamma dbeta ws M D dtype".split()
+_LN_BWD = {
+    "plain": ("m3ae_layernorm_bwd", "m3ae_layernorm_bwd_det", "LayerNorm backward",
+              "beta mean rstd dx dx_add dgamma dbeta ws M D dtype act rms".split()),
+    "drop": ("m3ae_layernorm_bwd_drop", "m3ae_layernorm_bwd_drop_det", "LayerNorm backward (dropout form)", _LN_DROP_ARGS),
+    "rows": ("m3ae_layernorm_bwd_drop_rows", None, "LayerNorm backward (dropout form)", _LN_DROP_ARGS + ["row_base", "row_step"]),
+    "mixed": ("m3ae_layernorm_bwd_mixed", "m3ae_layernorm_bwd_mixed_det", "LayerNorm backward (mixed form)",
+              "mean rstd dx dx_add second dgamma dbeta ws M D".split()),
+}
 
 
 def ln_bwd_raw(dy, x2, ln, mean, rstd, dx_add=None, act=ACT_NONE, rms=False, drop=None, rows=None, want_lo=False, train=None):
@@ -668,47 +680,38 @@ def ln_bwd_raw(dy, x2, ln, mean, rstd, dx_add=None, act=ACT_NONE, rms=False, dro
     With drop = (p, seed) returns (dx, dx_drop): dx_drop is dx under the dropout mask of the dense layer that fed this LayerNorm,
     rows = (row_base, row_step) the row map of that mask.  bf16 dy on fp32 x2 (the fp32 residual stream of a bf16 CLIP tower): dx
     and dx_add are fp32, and want_lo returns (dx, dx rounded to bf16).
-    The entry point follows from (dropout, row map, mixed dtypes, deterministic mode); a row map in deterministic mode has none
-    and raises DeterministicError."""
+    The entry point is the atomic or the ordered one (deterministic mode) of the form's row in _LN_BWD; a row map in deterministic
+    mode has none and raises DeterministicError."""
     M, D = x2.shape
     gamma, beta, eps = _ln_params(ln)
     drop = drop if drop is not None and drop[0] > 0 else None
     mixed = dy.dtype != x2.dtype
-    rows = rows if drop is not None else None   # (only the dropout mask has rows to map)
-    if rows is not None:
+    # (only the dropout mask has rows to map)
+    form = ("drop" if rows is None else "rows") if drop is not None else "mixed" if mixed else "plain"
+    atomic, ordered, label, names = _LN_BWD[form]
+    if ordered is None:
         _no_ordered_form("the LayerNorm backward under a dropout row map (the live-row form)")
-    if drop is not None:
+    if form in ("drop", "rows"):
         assert dx_add is None and act == ACT_NONE and not rms and not mixed and not want_lo
-    elif mixed:
+    elif form == "mixed":
         _ln_mixed_ok(x2, dy, act, rms)
         assert dx_add is None or dx_add.dtype == torch.float32
     else:
         assert not want_lo
     L = _lib.lib()
-    if drop is not None:
-        fn = L.m3ae_layernorm_bwd_drop_rows if rows is not None else \
-            L.m3ae_layernorm_bwd_drop_det if _DETERMINISTIC else L.m3ae_layernorm_bwd_drop
-    elif mixed:
-        fn = L.m3ae_layernorm_bwd_mixed_det if _DETERMINISTIC else L.m3ae_layernorm_bwd_mixed
-    else:
-        fn = L.m3ae_layernorm_bwd_det if _DETERMINISTIC else L.m3ae_layernorm_bwd
+    fn = getattr(L, ordered if _DETERMINISTIC else atomic)
     dx = torch.empty_like(x2)
     ws = torch.empty(2 * L.m3ae_layernorm_bwd_blocks(M) * D, dtype=torch.float32, device=x2.device)
     train = gamma.requires_grad if train is None else train
     gg = _grad_buf(gamma) if train else None
     gb = _grad_buf(beta) if (train and beta is not None) else None
-    second = None   # the second output: dx under the dropout mask, or dx rounded to bf16
-    if drop is not None:
-        second = torch.empty_like(x2)
-        check(fn(_p(dy), _p(x2), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dx), _p(second), drop[0], drop[1], _salt(), _p(gg),
-                 _p(gb), _p(ws), M, D, _dt(x2), *(rows or ()), _stream()), "LayerNorm backward (dropout form)")
-    elif mixed:
-        second = torch.empty_like(dy) if want_lo else None
-        check(fn(_p(dy), _p(x2), _p(gamma), _p(mean), _p(rstd), _p(dx), _p(dx_add), _p(second), _p(gg), _p(gb), _p(ws), M, D,
-                 _stream()), "LayerNorm backward (mixed form)")
-    else:
-        check(fn(_p(dy), _p(x2), _p(gamma), _p(beta), _p(mean), _p(rstd), _p(dx), _p(dx_add), _p(gg), _p(gb), _p(ws), M, D,
-                 _dt(x2), act, int(rms), _stream()), "LayerNorm backward")
+    # the second output: dx under the dropout mask, or dx rounded to bf16
+    second = torch.empty_like(x2) if drop is not None else torch.empty_like(dy) if want_lo else None
+    p, seed = drop or (None, None)
+    row_base, row_step = rows or (None, None)
+    a = dict(beta=_p(beta), mean=_p(mean), rstd=_p(rstd), dx=_p(dx), dx_add=_p(dx_add), second=_p(second), p=p, seed=seed, salt=_salt(),
+             dgamma=_p(gg), dbeta=_p(gb), ws=_p(ws), M=M, D=D, dtype=_dt(x2), act=act, rms=int(rms), row_base=row_base, row_step=row_step)
+    check(fn(_p(dy), _p(x2), _p(gamma), *(a[n] for n in names), _stream()), label)
     if train:
         _done(gamma)
         _done(beta)
