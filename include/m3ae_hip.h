@@ -53,6 +53,9 @@ extern "C" {
  *    changed. */
 /* 4 (additive): device-resident greedy search for the decoder head.  m3ae_greedy_argmax (+ m3ae_greedy_workspace_bytes) and
  *    m3ae_greedy_step (csrc/greedy.hip); no descriptor changed. */
+/* 4 (additive): attention summaries.  m3ae_attn_colmean (+ m3ae_attn_colmean_workspace_bytes) and m3ae_xattn_probs_colmean: the mean
+ *    of an attention map over heads and queries, fp32 [B][Lk], without the map; m3ae_heatmap_upsample (csrc/heatmap.hip): bilinear
+ *    upsample of a patch grid; no descriptor changed. */
 #define M3AE_ABI_VERSION 4
 
 enum { M3AE_F32 = 0, M3AE_BF16 = 1 };
@@ -228,6 +231,22 @@ int m3ae_attn_bwd_rows(const m3ae_attn_desc* d, int64_t row_base, int64_t row_st
  * p_sh = Lq*Lk, p_sb = H*Lq*Lk).
  * No pos_bias, no causal mask (M3AE_ERR_UNSUPPORTED).  ABI 4. */
 int m3ae_attn_probs(const m3ae_attn_desc* d, float* probs, int64_t p_sb, int64_t p_sh, int64_t p_sq, void* stream);
+/* The received attention of the same call: the mean of the map m3ae_attn_probs defines over heads and queries,
+ *   out[b * out_sb + k] = 1 / (H Lq) * sum_h sum_q probs[b][h][q][k]      (fp32, k < Lk, out_sb >= Lk),
+ * over all Lq query rows, without the map ever reaching memory.  Descriptor contract, dtype dispatch and refusals as
+ * m3ae_attn_probs (q, k, lse, key mask, dropout fields; the identity row map; pos_bias / causal: M3AE_ERR_UNSUPPORTED).
+ * bf16 (Dh = 64): every entry is formed by the expression of m3ae_attn_probs, so each summed entry has the bits that call writes; a
+ *   workgroup sums its 128 query rows on chip and writes one partial row per (b, h, query block) to the workspace, and a second
+ *   kernel adds the partial rows in ascending (h, query block) order and multiplies by the rounded 1 / (H Lq).  No atomics: the
+ *   result is a function of the inputs alone.  Workspace: B * H * ceil(Lq / 128) * Lk floats.
+ * fp32 (and M3AE_ATTN_F32_X3): the scores GEMM, row softmax and dropout of m3ae_attn_probs run over M3AE_ATTN_COLMEAN_F32_CHUNK
+ *   samples at a time into the workspace, whose columns the same fold adds (queries, then heads).  Workspace:
+ *   min(B, chunk) * H * (Lq + 1) * Lk floats -- a function of the chunk, not of B.
+ * The workspace is caller-owned and 16-byte aligned; missing, misaligned or shorter than m3ae_attn_colmean_workspace_bytes(d):
+ * M3AE_ERR_WORKSPACE before any launch.  ABI 4, additive. */
+#define M3AE_ATTN_COLMEAN_F32_CHUNK 4
+int64_t m3ae_attn_colmean_workspace_bytes(const m3ae_attn_desc* d);
+int m3ae_attn_colmean(const m3ae_attn_desc* d, float* out, int64_t out_sb, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Fused cross-attention sub-block of BertCrossLayer (north_star's kernel), bf16: BertAttention as `crossattention`
@@ -311,6 +330,25 @@ int m3ae_xattn_bwd(const m3ae_xattn_desc* d, void* stream);
  * the chosen buffer only.  ABI 4. */
 int m3ae_xattn_probs_export(const m3ae_xattn_desc* d, int dropped, float* out, int64_t o_sb, int64_t o_sh, int64_t o_sq,
                             void* stream);
+/* The received attention of the same buffer: out[b * out_sb + k] = 1 / (H Lq) * sum_h sum_q P[b][h][q][k] for k < Lk (fp32,
+ * out_sb >= Lk), P as m3ae_xattn_probs_export reads it (layout, padding columns, leading dimension m3ae_xattn_probs_ld); the stored
+ * bf16 values widen exactly.  One streaming pass with 16-byte loads; every output element has one owner (no atomics, fixed
+ * order).  Reads d->dir, B, Lq, Lk, H and the chosen buffer only.  M3AE_ERR_ALIGN for a buffer off 16 bytes; M3AE_ERR_UNSUPPORTED for
+ * dir 0 with Lk > 640, dir 1 with Lk % 8 != 0, B > 65535.  ABI 4, additive. */
+int m3ae_xattn_probs_colmean(const m3ae_xattn_desc* d, int dropped, float* out, int64_t out_sb, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Bilinear upsample of a patch grid (csrc/heatmap.hip): in [B][g][g] fp32 (sample stride in_sb elements, rows dense) ->
+ * out [B][S][S] fp32, dense, torch.nn.functional.interpolate(mode="bilinear", align_corners=False) semantics.  `in` may point at
+ * token 1 of a [B][1 + g*g] row of received attention with in_sb = 1 + g*g: the class token is skipped without a copy.
+ * Per axis and destination index d, in fp32 with no contraction:
+ *   scale = (float)g / (float)S;  src = max(scale * ((float)d + 0.5f) - 0.5f, 0);  i0 = min((int)src, g - 1);
+ *   i1 = min(i0 + 1, g - 1);  l1 = src - (float)i0;  l0 = 1 - l1;
+ * and out = l0y * (l0x * a + l1x * b) + l1y * (l0x * c + l1x * d) with a, b = in[i0y][i0x], in[i0y][i1x]; c, d the same of row
+ * i1y: rows first, then columns, every product and sum rounded once.
+ * M3AE_ERR_ARG for a null pointer, B < 1, g < 1, S < 1 or in_sb < g*g; M3AE_ERR_UNSUPPORTED for B > 65535, g or S > 16384.
+ * ABI 4, additive. */
+int m3ae_heatmap_upsample(const float* in, int64_t in_sb, int64_t g, float* out, int64_t B, int64_t S, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * LayerNorm (biased variance, eps inside the sqrt, fp32 statistics), optional fused activation on the output.

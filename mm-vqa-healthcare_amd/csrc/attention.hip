@@ -453,6 +453,100 @@ __global__ __launch_bounds__(256, 2) void attn_probs_kernel(AttnArgs a, float* _
     }
 }
 
+// received attention (m3ae_attn_colmean): the column sums of the same P over the workgroup's 128 query rows, P never stored.
+// Tile, staging and the expression of every entry are attn_probs_kernel's (same MFMA shape and k order, same exp argument, same
+// dropout key), so each summed entry has the bits that kernel writes.  In the unswapped tile a lane's 16 accumulator registers are
+// 16 query rows of ONE key (kt * 32 + r): the sum over queries is in-lane (registers in ascending order, rows beyond Lq left out),
+// then the other lane half (lane ^ 32), then the four waves through a 1-KiB LDS table, double-buffered like the K images so that the
+// tile's one barrier covers it.  Lanes 0..31 of wave 0 write the tile's 32 sums to this block's partial row
+// part[((b H + h) gridDim.x + bx) Lk + key]: one owner per element, fixed order, no atomics.
+template <bool MASK, bool DROP>
+__global__ __launch_bounds__(256, 2) void attn_colsum_kernel(AttnArgs a, float* __restrict__ part) {
+#pragma clang fp contract(off)   // the rescaled entry p / (1 - p_drop) is rounded before it is added, as the stored one is
+    if (DROP) drop_resolve(a.drop);
+    __shared__ __attribute__((aligned(16))) char lds[2 * RIMG];
+    __shared__ float red[2][4][32];
+    const int t = threadIdx.x;
+    const int lane = t & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    const int r = lane & 31, h = lane >> 5;
+    const AttnBlock blk = attn_block();
+    const int head = blk.head;
+    const int64_t b = blk.b;
+    const int64_t q0 = ((int64_t)blk.bx * 4 + wave) * 32;
+    const bool active = q0 < a.Lq;  // wave-uniform; inactive waves help with the cooperative loads and contribute zeros
+
+    const int64_t qa = q0 + r < a.Lq ? q0 + r : a.Lq - 1;   // A operand row (clamped: its results are left out of the sums)
+    const bf16_t* qp = a.q + b * a.q_sb + qa * a.q_sl + head * 64;
+    s16x8 qf[4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) qf[ks] = row_frag(qp, ks, h);
+    const float* lrow = a.lse + (b * a.H + head) * a.lse_stride;
+    float nl[16];
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const int64_t q = q0 + crow(reg, h);
+        nl[reg] = -lrow[q < a.Lq ? q : a.Lq - 1];
+    }
+    float* prow = part + ((b * a.H + head) * (int64_t)gridDim.x + blk.bx) * a.Lk;
+    const uint64_t drow0 = (uint64_t)drop_row(a.drop, (b * a.H + head) * a.Lq) * drop_ldk(a.Lk);
+    const bf16_t* kbase = a.k + b * a.k_sb + head * 64;
+    const float* mrow = MASK ? a.key_mask + b * a.Lk : nullptr;
+    const int nkt = (int)((a.Lk + 31) / 32);
+
+    s16x8 kreg = coop_load(kbase, a.k_sl, 0, a.Lk, t);
+    put_row_img(lds, kreg, t);
+    if (nkt > 1) kreg = coop_load(kbase, a.k_sl, 32, a.Lk, t);
+    coop_barrier();
+    for (int kt = 0; kt < nkt; ++kt) {
+        const bool last = kt + 1 == nkt;
+        s16x8 kreg2 = kreg;
+        if (kt + 2 < nkt) kreg2 = coop_load(kbase, a.k_sl, (int64_t)(kt + 2) * 32, a.Lk, t);
+        const char* kimg = lds + (kt & 1) * RIMG;
+        float cs = 0.f;
+        if (active) {
+            f32x16 s = zero16();
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks) s = mfma32(qf[ks], get_row_frag(kimg, r, ks, h), s);  // S[q][key] = Q . K^T
+            const int64_t key = (int64_t)kt * 32 + r;
+            const bool kin = key < a.Lk;
+            const float madd = MASK ? mrow[kin ? key : a.Lk - 1] * LOG2E : 0.f;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int64_t q = q0 + crow(reg, h);
+                float p = fast_exp2(fmaf(s[reg], a.scale_log2, madd) + nl[reg]);
+                if (DROP) p = drop_keep(a.drop, drow0 + (uint64_t)(q * a.drop.row_step) * drop_ldk(a.Lk) + (uint64_t)key) ? p * a.drop.inv_keep : 0.f;
+                cs += q < a.Lq ? p : 0.f;
+            }
+        }
+        cs += __shfl_xor(cs, 32, 64);
+        if (h == 0) red[kt & 1][wave][r] = cs;   // (columns beyond Lk hold the clamped key row's values: never read out)
+        if (!last) put_row_img(lds + ((kt + 1) & 1) * RIMG, kreg, t);
+        kreg = kreg2;
+        coop_barrier();
+        // red[kt & 1] is written again in tile kt + 2, behind the barrier of tile kt + 1, which these reads precede
+        if (t < 32) {
+            const int64_t key = (int64_t)kt * 32 + t;
+            const float (*rd)[32] = red[kt & 1];
+            if (key < a.Lk) prow[key] = ((rd[0][t] + rd[1][t]) + rd[2][t]) + rd[3][t];
+        }
+    }
+}
+
+// out[i * o_s + k] = scale * sum_{j < n} src[(i n + j) Lk + k], j ascending: the fold of the partial rows of the received attention
+// (and of the materialised fp32 maps).  One thread per (i, k), lanes along k; one rounding per addition and one for the product.
+__global__ __launch_bounds__(256) void colfold_kernel(const float* __restrict__ src, int64_t n, int64_t Lk, float* __restrict__ out,
+                                                      int64_t o_s, float scale, int kblocks) {
+    const int64_t i = blockIdx.x / kblocks;
+    const int64_t k = (int64_t)(blockIdx.x % kblocks) * 256 + threadIdx.x;
+    if (k >= Lk) return;
+    const float* p = src + i * n * Lk + k;
+    float acc = 0.f;
+#pragma unroll 4
+    for (int64_t j = 0; j < n; ++j) acc += p[j * Lk];
+    out[i * o_s + k] = acc * scale;
+}
+
 template <bool MASK, bool BIAS, bool CAUSAL, bool DROP>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_coop_kernel(AttnArgs a) {
     if (DROP) drop_resolve(a.drop);
@@ -1279,6 +1373,71 @@ extern "C" int m3ae_attn_probs(const m3ae_attn_desc* dp, float* probs, int64_t p
     if (rc) return rc;
     if (d.dropout_p > 0.f)
         return m3ae_dropout(probs, probs, nullptr, d.B * d.H * d.Lq, d.Lk, d.dropout_p, d.dropout_seed, d.dropout_salt, M3AE_F32, stream);
+    return 0;
+}
+
+namespace {
+int colfold(const float* src, int64_t count, int64_t n, int64_t Lk, float* out, int64_t o_s, float scale, hipStream_t s) {
+    const int64_t kblocks = cdiv(Lk, 256);
+    if (kblocks > INT32_MAX / count) return M3AE_ERR_UNSUPPORTED;   // grid.x
+    hipLaunchKernelGGL(colfold_kernel, dim3((unsigned)(count * kblocks)), dim3(256), 0, s, src, n, Lk, out, o_s, scale, (int)kblocks);
+    return hip_launch_status();
+}
+int64_t colmean_chunk(const m3ae_attn_desc& d) { return d.B < M3AE_ATTN_COLMEAN_F32_CHUNK ? d.B : M3AE_ATTN_COLMEAN_F32_CHUNK; }
+}  // namespace
+
+extern "C" int64_t m3ae_attn_colmean_workspace_bytes(const m3ae_attn_desc* d) {
+    if (!d || d->B <= 0 || d->H <= 0 || d->Lq <= 0 || d->Lk <= 0) return 0;
+    if (d->dtype == M3AE_BF16) return d->B * d->H * cdiv(d->Lq, 128) * d->Lk * (int64_t)sizeof(float);
+    return colmean_chunk(*d) * d->H * (d->Lq + 1) * d->Lk * (int64_t)sizeof(float);   // the chunk's maps + their per-head sums
+}
+
+extern "C" int m3ae_attn_colmean(const m3ae_attn_desc* dp, float* out, int64_t out_sb, void* workspace, int64_t workspace_bytes,
+                                 void* stream) {
+    if (!dp || !dp->q || !dp->k || !out) return M3AE_ERR_ARG;
+    const m3ae_attn_desc& d = *dp;
+    if (d.B <= 0 || d.H <= 0 || d.Lq <= 0 || d.Lk <= 0 || d.Dh <= 0) return M3AE_ERR_ARG;
+    if (out_sb < d.Lk) return M3AE_ERR_ARG;
+    if (d.pos_bias || d.causal) return M3AE_ERR_UNSUPPORTED;   // as m3ae_attn_probs
+    if (d.dtype != M3AE_BF16 && d.dtype != M3AE_F32) return M3AE_ERR_UNSUPPORTED;
+    if (d.dtype == M3AE_BF16) {
+        if (!bf16_layout_ok(d, LAYOUT_QK)) return M3AE_ERR_UNSUPPORTED;
+        if (d.H > 65535 || d.B > 65535) return M3AE_ERR_UNSUPPORTED;
+    }
+    if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < m3ae_attn_colmean_workspace_bytes(dp)) return M3AE_ERR_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const float inv = 1.0f / (float)(d.H * d.Lq);
+    float* ws = (float*)workspace;
+    if (d.dtype == M3AE_BF16) {
+        AttnArgs a = to_args(d);
+        const int64_t nqb = cdiv(d.Lq, 128);
+        dim3 grid((unsigned)nqb, (unsigned)d.H, (unsigned)d.B);
+        int rc = attn_dispatch(a, [&](auto mask, auto, auto, auto drop) {   // (no bias, not causal: refused above)
+            hipLaunchKernelGGL((attn_colsum_kernel<mask.value, drop.value>), grid, dim3(256), 0, s, a, ws);
+            return hip_launch_status();
+        });
+        if (rc) return rc;
+        return colfold(ws, d.B, d.H * nqb, d.Lk, out, out_sb, inv, s);
+    }
+    // parity mode: m3ae_attn_probs' materialised maps, a chunk of samples at a time, then their columns: queries, then heads
+    const int64_t chunk = colmean_chunk(d);
+    float* hsum = ws + chunk * d.H * d.Lq * d.Lk;
+    for (int64_t b0 = 0; b0 < d.B; b0 += chunk) {
+        m3ae_attn_desc c = d;
+        c.B = d.B - b0 < chunk ? d.B - b0 : chunk;
+        c.q = (const float*)d.q + b0 * d.q_sb;
+        c.k = (const float*)d.k + b0 * d.k_sb;
+        if (d.key_mask) c.key_mask = d.key_mask + b0 * d.Lk;
+        int rc = attn_f32_scores(c, ws, s);
+        if (rc) return rc;
+        const int64_t rows = c.B * d.H * d.Lq;
+        if (d.dropout_p > 0.f &&   // the chunk's rows of the call's mask: m3ae_attn_probs' index ((b H + h) Lq + q) ld(Lk) + k
+            (rc = m3ae_dropout_rows(ws, ws, nullptr, rows, d.Lk, d.dropout_p, d.dropout_seed, d.dropout_salt, M3AE_F32, b0 * d.H * d.Lq, 1,
+                                    stream)))
+            return rc;
+        if ((rc = colfold(ws, c.B * d.H, d.Lq, d.Lk, hsum, d.Lk, 1.0f, s))) return rc;
+        if ((rc = colfold(hsum, c.B, d.H, d.Lk, out + b0 * out_sb, out_sb, inv, s))) return rc;
+    }
     return 0;
 }
 

@@ -1501,3 +1501,77 @@ extern "C" int m3ae_xattn_probs_export(const m3ae_xattn_desc* d, int dropped, fl
                        (const bf16_t*)src, s_b, s_h, s_q, out, o_sb, o_sh, o_sq, H, Lq, Lk, rows);
     return hip_launch_status();
 }
+
+namespace {
+// recv[b][k] = scale * sum_h sum_q P[b*s_b + h*s_h + q*s_q + k]: the stored P is streamed once with 16-byte loads (8 bf16 key
+// columns per lane, CG lanes side by side = CG * 16 contiguous bytes of a row, 256 / CG row lanes per workgroup striding over the
+// query rows).  A lane adds its rows in ascending (h, q) order; the row lanes are then added in ascending order through LDS by the
+// one thread that owns the output element.  cg_shift = log2(CG), CG <= 8.
+__global__ __launch_bounds__(256) void xattn_probs_colmean_kernel(const bf16_t* __restrict__ src, int64_t s_b, int64_t s_h,
+                                                                   int64_t s_q, float* __restrict__ out, int64_t o_sb, int H,
+                                                                   int64_t Lq, int64_t Lk, int cg_shift, float scale) {
+    __shared__ float red[256][9];   // (9: the 8 sums of a lane one bank apart from the next lane's)
+    const int t = threadIdx.x;
+    const int CG = 1 << cg_shift, RL = 256 >> cg_shift;
+    const int cg = t & (CG - 1), rl = t >> cg_shift;
+    const int64_t k0 = ((int64_t)blockIdx.x * CG + cg) * 8;
+    const int64_t b = blockIdx.y;
+    float acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+    if (k0 < Lk) {   // (k0 + 7 stays inside the row: its stride is a multiple of 8 columns >= Lk)
+        const bf16_t* p = src + b * s_b + k0;
+        for (int h = 0; h < H; ++h) {
+            const bf16_t* ph = p + h * s_h;
+#pragma unroll 4
+            for (int64_t q = rl; q < Lq; q += RL) {
+                const u32x4 w = *(const u32x4*)(ph + q * s_q);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    acc[2 * j] += __uint_as_float(w[j] << 16);
+                    acc[2 * j + 1] += __uint_as_float(w[j] & 0xffff0000u);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) red[t][j] = acc[j];
+    __syncthreads();
+    if (t < 8 * CG) {
+        const int c = t >> 3, j = t & 7;
+        const int64_t k = ((int64_t)blockIdx.x * CG + c) * 8 + j;
+        if (k < Lk) {
+            float sum = 0.f;
+            for (int r = 0; r < RL; ++r) sum += red[(r << cg_shift) + c][j];
+            out[b * o_sb + k] = sum * scale;
+        }
+    }
+}
+}  // namespace
+
+extern "C" int m3ae_xattn_probs_colmean(const m3ae_xattn_desc* d, int dropped, float* out, int64_t out_sb, void* stream) {
+    if (!d || !out) return M3AE_ERR_ARG;
+    const void* src = dropped ? d->probs_drop : d->probs;
+    if (!src || d->B <= 0 || d->H <= 0 || d->Lq <= 0 || d->Lk <= 0) return M3AE_ERR_ARG;
+    if (out_sb < d->Lk) return M3AE_ERR_ARG;
+    const int64_t H = d->H, Lq = d->Lq, Lk = d->Lk;
+    int64_t s_b, s_h, s_q;   // as m3ae_xattn_probs_export
+    if (d->dir == 0) {
+        if (Lk > 640) return M3AE_ERR_UNSUPPORTED;
+        s_h = 640; s_q = H * 640; s_b = Lq * H * 640;
+    } else if (d->dir == 1) {
+        if (Lk % 8 != 0) return M3AE_ERR_UNSUPPORTED;   // a head's columns start on a 16-byte boundary
+        s_h = Lk; s_q = H * Lk; s_b = Lq * H * Lk;
+    } else {
+        return M3AE_ERR_ARG;
+    }
+    if (d->B > 65535 || H > INT32_MAX) return M3AE_ERR_UNSUPPORTED;   // grid.y
+    if ((uintptr_t)src & 15) return M3AE_ERR_ALIGN;
+    const int64_t groups = cdiv(Lk, 8);
+    int cg_shift = 3;   // 8 lanes = one 128-byte segment of a row; fewer where a row has fewer columns (32 text keys: 4)
+    while (cg_shift > 0 && (1 << cg_shift) > groups) --cg_shift;
+    hipLaunchKernelGGL(xattn_probs_colmean_kernel, dim3((unsigned)cdiv(groups, (int64_t)1 << cg_shift), (unsigned)d->B), dim3(256), 0,
+                       (hipStream_t)stream, (const bf16_t*)src, s_b, s_h, s_q, out, out_sb, (int)H, Lq, Lk, cg_shift,
+                       1.0f / (float)(H * Lq));
+    return hip_launch_status();
+}

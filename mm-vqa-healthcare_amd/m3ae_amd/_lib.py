@@ -161,6 +161,11 @@ _SIGS = {
     "m3ae_layernorm_fwd_mixed": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, f32, vp]),
     "m3ae_layernorm_bwd_mixed": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp]),
     "m3ae_layernorm_bwd_mixed_det": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp]),
+    # attention summaries (ABI 4, additive): the head-and-query mean of a map without the map, and the heatmap upsample
+    "m3ae_attn_colmean_workspace_bytes": (i64, [C.POINTER(AttnDesc)]),
+    "m3ae_attn_colmean": (C.c_int, [C.POINTER(AttnDesc), vp, i64, vp, i64, vp]),
+    "m3ae_xattn_probs_colmean": (C.c_int, [C.POINTER(XattnDesc), C.c_int, vp, i64, vp]),
+    "m3ae_heatmap_upsample": (C.c_int, [vp, i64, i64, vp, i64, i64, vp]),
 }
 
 EXPORTS = tuple(_SIGS)

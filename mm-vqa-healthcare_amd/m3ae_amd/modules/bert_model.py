@@ -149,12 +149,15 @@ class BertCrossLayer(nn.Module):
         self._bp = None
 
     def forward(self, hidden_states, encoder_hidden_states, attention_mask=None, encoder_attention_mask=None,
-                output_attentions=False, cls_only=False):
+                output_attentions=False, cls_only=False, output_attention_summary=False):
         """Returns the layer output; with output_attentions the reference's tuple (output, self-attention probabilities
         [B, H, L, L], cross-attention probabilities [B, H, L, Lo]) (bert_model.py:457-498): fp32, contiguous, detached (the
         reference's gradient hook on them is disabled, :328); in training mode the dropped P the layer used (:334).
+        output_attention_summary: the tuple ends with the received attention of the two maps, their means over heads and queries
+        (self [B, L], cross [B, Lo]; fp32, contiguous, detached), formed without the maps: (output, self_recv, cross_recv), or
+        after the two maps when both flags are set.
         cls_only: the caller reads token 0 of the output alone; the layer computes that row ([B, 1, D], equal to row 0 of the
-        full output: ops.BertCrossLayerFn's live-row form).  Attention maps are full-layer outputs: output_attentions wins."""
+        full output: ops.BertCrossLayerFn's live-row form).  Attention maps and summaries are full-layer outputs: they win."""
         if self._bp is None:
             self._bp = NS(attn=self.attention.block_params(), cross=self.crossattention.block_params(),
                           ffn=_ffn_params(self))
@@ -162,11 +165,11 @@ class BertCrossLayer(nn.Module):
         opts = ops.BlockOpts(
             pdrop=self.drop_rate if self.training else 0.0,
             # (deterministic mode keeps the full layer: the live form's LayerNorm backward has no ordered entry point)
-            cls_only=bool(cls_only) and not output_attentions and not ops.deterministic(),
+            cls_only=bool(cls_only) and not output_attentions and not output_attention_summary and not ops.deterministic(),
             # forward-only calls always take the fused cross-attention sub-block; training takes it with its fused backward
             fused_cross=(not torch.is_grad_enabled()) or (ops.XATTN_TRAIN != "off" and
                                                           hidden_states.shape[0] >= ops.XATTN_TRAIN_MIN_BATCH),
-            want_probs=bool(output_attentions), need_bwd=torch.is_grad_enabled())
+            want_probs=bool(output_attentions), need_bwd=torch.is_grad_enabled(), want_summary=bool(output_attention_summary))
         return ops.BertCrossLayerFn.apply(hidden_states, encoder_hidden_states, attention_mask, encoder_attention_mask,
                                           self._bp, opts, *self._anchors)
 

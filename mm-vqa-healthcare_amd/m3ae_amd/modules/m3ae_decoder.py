@@ -367,6 +367,16 @@ class DecoderModel(_Base):
             parts.append(out["multi_modal_cls_feats"].view(-1, 2, 768))
         return torch.cat(parts, dim=1).to(self.decoder.head_dtype).contiguous()
 
+    @ops.model_mode
+    def visualize_attention_heatmap(self, batch, layer_idx=-1):
+        """m3ae_decoder.py:225-290 without the drawing.  The reference method reads two names it never defines (`output`,
+        `layer_idx`) and plots with matplotlib / seaborn; this one returns the tensors that plot needs, {"heatmaps": fp32
+        [B, S, S] (S = image_size), "images": the batch's images}: the image layer's self-attention of fusion layer `layer_idx`,
+        averaged over heads and queries, class token dropped, as the patch grid, upsampled bilinearly
+        (M3AETransformerSS.attention_heatmaps(which="image_self")).  Plotting is left to the caller."""
+        return {"heatmaps": self.m3ae.attention_heatmaps(batch, layer=layer_idx, which="image_self"),
+                "images": self.m3ae.heatmap_images(batch)}
+
     def tokens_of(self, batch):
         if "decoder_tokens" in batch:
             return batch["decoder_tokens"]

@@ -13,6 +13,7 @@ fusion layers' maps (fp32 [B, H, Lq, Lk], detached: the reference's gradient hoo
 (`module.training`, RoBERTa p = 0.1, fusion layers p = `drop_rate`) uses the library's counter-hash masks fused into
 the kernels (seeded by `ops.set_dropout_seed`), not torch's Philox stream.
 """
+import math
 import os
 
 import torch
@@ -198,7 +199,21 @@ class M3AETransformerSS(_Base):
                 warn_off(False)
         return self._side_stream
 
-    def _fusion_two_streams(self, text_tower, v, mt, mv, mask_image, ret, main, side, ev_inputs, attns=None, live=False):
+    @staticmethod
+    def _collect_attention(out, attns, summ, side_key):
+        """Splits a fusion layer's result (output, [self map, cross map], [self recv, cross recv]) and files the extras."""
+        if attns is None and summ is None:
+            return out
+        out, *extra = out
+        if attns is not None:
+            attns[f"{side_key}_attns"].append(tuple(extra[:2]))
+            extra = extra[2:]
+        if summ is not None:
+            summ[side_key].append(tuple(extra))
+        return out
+
+    def _fusion_two_streams(self, text_tower, v, mt, mv, mask_image, ret, main, side, ev_inputs, attns=None, live=False,
+                            summ=None):
         """The text tower and the text half of every fusion layer on a second HIP stream.  The towers are independent until the
         fusion layers and a fusion layer's two halves read only the PREVIOUS layer's outputs, so the short text-side kernels
         (B*32 rows: half-empty grids) fill the tail rounds of the image-side launches instead of running alone.  Events order
@@ -225,21 +240,23 @@ class M3AETransformerSS(_Base):
             y.record_stream(side)
             last = live and layer_idx == len(self.multi_modal_language_layers) - 1   # (live: token 0 of the last pair only)
             with torch.cuda.stream(side):
-                x1 = text_layer(xa, yb, mt, mv, output_attentions=attns is not None, cls_only=last)
+                x1 = text_layer(xa, yb, mt, mv, output_attentions=attns is not None, cls_only=last,
+                                output_attention_summary=summ is not None)
                 ev_x1 = side.record_event()
             main.wait_event(ev_x)
             x.record_stream(main)
-            y1 = image_layer(ya, xb, mv, mt, output_attentions=attns is not None, cls_only=last)
-            if attns is not None:   # (the layers' reference-shaped tuples: output, self-attention map, cross-attention map)
-                (x1, *tmaps), (y1, *imaps) = x1, y1
-                attns["text2image_attns"].append(tuple(tmaps))
-                attns["image2text_attns"].append(tuple(imaps))
+            y1 = image_layer(ya, xb, mv, mt, output_attentions=attns is not None, cls_only=last,
+                             output_attention_summary=summ is not None)
+            # (the layers' reference-shaped tuples: output, self-attention map, cross-attention map; then the two summaries)
+            x1 = self._collect_attention(x1, attns, summ, "text2image")
+            y1 = self._collect_attention(y1, attns, summ, "image2text")
             ev_y = main.record_event()
             x, y, ev_x = x1, y1, ev_x1
         main.wait_event(ev_x)
         x.record_stream(main)
-        if attns is not None:   # the text maps were written on the side stream: ordered before ev_x, handed to the caller's stream
-            for p in attns["text2image_attns"]:
+        # the text maps and summaries were written on the side stream: ordered before ev_x, handed to the caller's stream
+        for pairs in ((attns["text2image_attns"] if attns is not None else ()), (summ["text2image"] if summ is not None else ())):
+            for p in pairs:
                 for t in p:
                     t.record_stream(main)
         if torch.is_grad_enabled():
@@ -286,12 +303,16 @@ class M3AETransformerSS(_Base):
 
     @ops.model_mode
     def infer(self, batch, mask_text=False, mask_image=False, image_token_type_idx=1, img=None,
-              output_attentions=False, unimodal=False, cls_only=False):
+              output_attentions=False, unimodal=False, cls_only=False, output_attention_summary=False):
         """m3ae_module.py:203-312.  With `batch["image_index"]` (int64 [B]) the image tensor holds one row per DISTINCT image
         ([U, 3, H, W], U <= B, every row used): the tower runs on the U images and `ops.expand_samples` hands sample b the tokens
         of image image_index[b] before the fusion layers; image_index == arange(B) is the path without the key.  cls_only: the caller reads `multi_modal_cls_feats` alone (the VQA and ITM heads): the last fusion
         pair then computes only its token-0 rows (ops.CLS_ONLY) and the two full-sequence feature entries are left out of the
-        result.  Attention maps (output_attentions) and deterministic mode keep the full computation."""
+        result.  Attention maps (output_attentions) and deterministic mode keep the full computation.
+        output_attention_summary: ret["attention_summary"] = {"text2image": [(self_recv, cross_recv) per fusion layer],
+        "image2text": [...]}, the received attention of every map of ret["attentions"] -- its mean over heads and queries, fp32
+        [B, Lk], contiguous, detached, per sample (after the expansion of a de-duplicated batch) -- formed without the maps
+        (ops.attn_colmean, ops.xattn_colmean).  Like the maps it keeps the full computation; both flags may be set."""
         if self.store is None:
             raise RuntimeError("call finalize(device) before the first forward")
         ret = dict()
@@ -352,7 +373,9 @@ class M3AETransformerSS(_Base):
 
         # m3ae_module.py:266,280-283: per fusion layer the (self, cross) attention maps of each direction
         attns = {"text2image_attns": [], "image2text_attns": []} if output_attentions else None
-        live = bool(cls_only) and ops.CLS_ONLY and not output_attentions and not ops.deterministic()
+        summ = {"text2image": [], "image2text": []} if output_attention_summary else None
+        live = (bool(cls_only) and ops.CLS_ONLY and not output_attentions and not output_attention_summary
+                and not ops.deterministic())
         n_fusion = len(self.multi_modal_language_layers)
         if side is None:
             t = text_tower()
@@ -364,15 +387,14 @@ class M3AETransformerSS(_Base):
                     ret[f"multi_modal_text_feats_{layer_idx}"], ret[f"multi_modal_image_feats_{layer_idx}"] = x, y
                 (xa, xb), (ya, yb) = ops.fork2(x), ops.fork2(y)
                 last = live and layer_idx == n_fusion - 1
-                x1 = text_layer(xa, yb, mt, mv, output_attentions=output_attentions, cls_only=last)
-                y1 = image_layer(ya, xb, mv, mt, output_attentions=output_attentions, cls_only=last)
-                if output_attentions:
-                    (x1, *tmaps), (y1, *imaps) = x1, y1
-                    attns["text2image_attns"].append(tuple(tmaps))
-                    attns["image2text_attns"].append(tuple(imaps))
-                x, y = x1, y1
+                x1 = text_layer(xa, yb, mt, mv, output_attentions=output_attentions, cls_only=last,
+                                output_attention_summary=output_attention_summary)
+                y1 = image_layer(ya, xb, mv, mt, output_attentions=output_attentions, cls_only=last,
+                                 output_attention_summary=output_attention_summary)
+                x = self._collect_attention(x1, attns, summ, "text2image")
+                y = self._collect_attention(y1, attns, summ, "image2text")
         else:
-            x, y = self._fusion_two_streams(text_tower, v, mt, mv, mask_image, ret, main, side, ev_inputs, attns, live)
+            x, y = self._fusion_two_streams(text_tower, v, mt, mv, mask_image, ret, main, side, ev_inputs, attns, live, summ)
         # == Output (m3ae_module.py:287-297) ==
         cls_t = self.multi_modal_language_pooler(x)
         cls_v = self.multi_modal_vision_pooler(y)
@@ -393,7 +415,44 @@ class M3AETransformerSS(_Base):
         if mask_image:  # only MIM needs it (the reference recomputes it on every call, m3ae_module.py:301)
             ret["patched_images"] = self.patchify(img)
         ret["attentions"] = attns
+        if summ is not None:
+            ret["attention_summary"] = summ
         return ret
+
+    HEATMAP_SOURCES = {"image_self": ("image2text", 0), "text2image": ("text2image", 1)}
+
+    @staticmethod
+    def heatmap_images(batch):
+        """The images attention_heatmaps(batch) lies over: infer's ret["images"] for image_token_type_idx = 1."""
+        return batch["image_0" if "image_0" in batch else "image"][0]
+
+    def attention_heatmaps(self, batch, layer=-1, which="image_self", size=None):
+        """Per-sample attention heatmaps over the image, fp32 [B, size, size] on the device (size: config["image_size"] by
+        default): the received attention of the image patches in fusion layer `layer`, class token dropped, as the g x g patch
+        grid, upsampled bilinearly (align_corners=False) -- what the reference's DecoderModel.visualize_attention_heatmap
+        (m3ae_decoder.py:225-290) computes from a full attention map before it plots.
+        which = "image_self": the reference's choice, the image layer's self-attention (image2text[layer][0]) -- how much attention
+        each patch receives from the image tokens; "text2image": the text layer's cross-attention (text2image[layer][1]) -- how
+        much the question's tokens attend to each patch.  One infer under no_grad with output_attention_summary; no map is formed."""
+        if which not in self.HEATMAP_SOURCES:
+            raise ValueError(f"which={which!r}: expected one of {sorted(self.HEATMAP_SOURCES)}")
+        cfg = self.hparams.config
+        img = self.heatmap_images(batch)
+        # I - 1: the image tokens without the class token, known before anything runs
+        tokens = (img.shape[-2] // cfg["patch_size"]) * (img.shape[-1] // cfg["patch_size"])
+        g = math.isqrt(tokens)
+        if g * g != tokens:
+            raise ValueError(f"{tokens} image patches (I - 1) are not a square grid: no heatmap")
+        size = cfg["image_size"] if size is None else int(size)
+        if size < 1:
+            raise ValueError(f"size={size}")
+        with torch.no_grad():
+            ret = self.infer(batch, output_attention_summary=True)
+        side, idx = self.HEATMAP_SOURCES[which]
+        recv = ret["attention_summary"][side][layer][idx]
+        if recv.shape[1] != tokens + 1:
+            raise ValueError(f"the summary has {recv.shape[1]} image tokens, expected 1 + {tokens}")
+        return ops.heatmap_upsample(recv[:, 1:], size)
 
     def vqa_head_forward(self, cls):
         """m3ae_module.py:120-125: Linear -> LayerNorm -> GELU (fused into the LN kernel) -> Linear."""

@@ -104,6 +104,13 @@ class T5VQA_MMEncoderInput(_Base):
         x[:, P] = proj
         return {"inputs_embeds": x, "attention_mask": torch.ones(B, MAX_SEQ_LEN, dtype=torch.long, device=dev)}
 
+    @ops.model_mode
+    def attention_heatmaps(self, batch, layer=-1, which="image_self", size=None):
+        """{"heatmaps": M3AETransformerSS.attention_heatmaps(batch, layer, which, size) (fp32 [B, size, size]), "images": the
+        batch's images}: the encoder's attention over the image for the questions this model answers; plotting is the caller's."""
+        return {"heatmaps": self.m3ae.attention_heatmaps(batch, layer=layer, which=which, size=size),
+                "images": self.m3ae.heatmap_images(batch)}
+
     def labels_of(self, batch):
         if "t5_labels" in batch:
             return batch["t5_labels"]

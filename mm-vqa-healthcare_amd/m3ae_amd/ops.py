@@ -834,6 +834,58 @@ def attn_probs(q, k, lse, heads, key_mask=None, scale=None, dropout=None):
     return out
 
 
+def attn_colmean(q, k, lse, heads, key_mask=None, scale=None, dropout=None):
+    """The received attention of the attn_forward call that returned `lse` for these q / k: the mean over heads and queries of the
+    map attn_probs returns for the same arguments, fp32 [B, Lk], formed without the map (m3ae_attn_colmean).  A fresh tensor
+    outside autograd."""
+    _need_cuda(q)
+    B, Lq, D = q.shape
+    Lk = k.shape[1]
+    Dh = D // heads
+    if q.dtype == torch.bfloat16 and Dh != 64:   # attn_probs' fp32 detour
+        return attn_colmean(q.float(), k.float(), None, heads, key_mask, scale, dropout)
+    scale = (1.0 / math.sqrt(Dh)) if scale is None else scale
+    out = torch.empty((B, Lk), dtype=torch.float32, device=q.device)
+    lse_stride = lse.shape[-1] if lse is not None else 0
+    d = _attn_desc(B, heads, Lq, Lk, Dh, q, k, k, q, key_mask, None, scale, False, lse, lse_stride, _dt(q))
+    _set_dropout(d, dropout)
+    L = _lib.lib()
+    n = L.m3ae_attn_colmean_workspace_bytes(C.byref(d))
+    ws = torch.empty(n, dtype=torch.uint8, device=q.device)
+    e0 = _prof_begin()
+    check(L.m3ae_attn_colmean(C.byref(d), C.c_void_p(out.data_ptr()), out.stride(0), C.c_void_p(ws.data_ptr()), n, _stream()),
+          "m3ae_attn_colmean")
+    _prof_end(e0, "attn_colmean", (B, heads, Lq, Lk, Dh))
+    del ws
+    return out
+
+
+def heatmap_upsample(recv, size):
+    """Bilinear upsample (align_corners=False) of patch grids to [B, size, size] fp32 (m3ae_heatmap_upsample).  recv: fp32
+    [B, g, g], or a [B, g * g] view with unit stride along the tokens -- such as recv[:, 1:] of a [B, 1 + g * g] summary, whose
+    class token is then skipped without a copy."""
+    _need_cuda(recv)
+    if recv.dtype != torch.float32:
+        raise ValueError(f"heatmap_upsample takes fp32 grids, got {recv.dtype}")
+    if recv.dim() == 3:
+        if recv.shape[1] != recv.shape[2]:
+            raise ValueError(f"heatmap_upsample takes square grids, got {tuple(recv.shape)}")
+        recv = recv.reshape(recv.shape[0], -1)
+    B, n = recv.shape
+    g = math.isqrt(n)
+    if g * g != n or g < 1:
+        raise ValueError(f"heatmap_upsample: {n} tokens are not a square grid")
+    size = int(size)
+    if size < 1:
+        raise ValueError(f"heatmap_upsample: size {size}")
+    if recv.stride(1) != 1 or (B > 1 and recv.stride(0) < n):
+        recv = recv.contiguous()
+    out = torch.empty((B, size, size), dtype=torch.float32, device=recv.device)
+    check(_lib.lib().m3ae_heatmap_upsample(C.c_void_p(recv.data_ptr()), max(recv.stride(0), n), g, C.c_void_p(out.data_ptr()), B, size,
+                                           _stream()), "m3ae_heatmap_upsample")
+    return out
+
+
 class SelfAttnFn(Function):
     """softmax(QK^T / sqrt(dh) + mask) V on a packed [B, L, 3D] projection (rows Q | K | V)."""
 
@@ -1006,12 +1058,12 @@ def xattn_fwd(h2, B, L, other2, Lo, mask, P, pdrop=0.0, need_bwd=True, want_prob
     return t["out"], ("xattn", h2, other2, mask, t, seeds, pdrop)
 
 
-def xattn_probs(saved):
-    """The attention probabilities of an xattn_fwd call from its saved buffers: fp32 [B, H, Lq, Lk], contiguous
-    (m3ae_xattn_probs_export: padding keys sliced off; under dropout the dropped and rescaled P the call used)."""
+def _xattn_probs_desc(saved, what):
+    """The descriptor fields m3ae_xattn_probs_export / m3ae_xattn_probs_colmean read, from what an xattn_fwd call saved:
+    (descriptor, dropped, B, Lq, Lk)."""
     _, h2, other2, mask, t, seeds, pdrop = saved
     if "probs" not in t:
-        raise _lib.M3AEHipError("this fused cross-attention call kept its probabilities on chip (xattn_fwd(want_probs=True))")
+        raise _lib.M3AEHipError(f"this fused cross-attention call kept its probabilities on chip ({what} needs xattn_fwd(want_probs=True))")
     d = XattnDesc()
     prime = t["prime"]
     dir1 = prime.dim() == 4                  # dir 1 keeps K' and V' ([2, B, R, D]), dir 0 Q' ([B, R, D])
@@ -1024,9 +1076,26 @@ def xattn_probs(saved):
     dropped = pdrop > 0
     if dropped:
         d.probs_drop = t["probs_drop"].data_ptr()
-    out = torch.empty((B, d.H, L, Lo), dtype=torch.float32, device=h2.device)
+    return d, dropped, B, L, Lo
+
+
+def xattn_probs(saved):
+    """The attention probabilities of an xattn_fwd call from its saved buffers: fp32 [B, H, Lq, Lk], contiguous
+    (m3ae_xattn_probs_export: padding keys sliced off; under dropout the dropped and rescaled P the call used)."""
+    d, dropped, B, L, Lo = _xattn_probs_desc(saved, "xattn_probs")
+    out = torch.empty((B, d.H, L, Lo), dtype=torch.float32, device=saved[1].device)
     check(_lib.lib().m3ae_xattn_probs_export(C.byref(d), int(dropped), C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1),
                                              out.stride(2), _stream()), "m3ae_xattn_probs_export")
+    return out
+
+
+def xattn_colmean(saved):
+    """The received attention of an xattn_fwd call from its saved buffers: the mean of xattn_probs(saved) over heads and queries,
+    fp32 [B, Lk] (m3ae_xattn_probs_colmean: one pass over the stored bf16 P)."""
+    d, dropped, B, L, Lo = _xattn_probs_desc(saved, "xattn_colmean")
+    out = torch.empty((B, Lo), dtype=torch.float32, device=saved[1].device)
+    check(_lib.lib().m3ae_xattn_probs_colmean(C.byref(d), int(dropped), C.c_void_p(out.data_ptr()), out.stride(0), _stream()),
+          "m3ae_xattn_probs_colmean")
     return out
 
 
@@ -1208,6 +1277,16 @@ def _attn_sub_probs(saved, B, L, Lo, P):
     return attn_probs(q3, k3, lse, P.heads, mask, dropout=da)
 
 
+def _attn_sub_colmean(saved, B, L, Lo, P):
+    """The received attention of an _attn_sub_fwd call (fp32 [B, Lo]: the mean of _attn_sub_probs over heads and queries) from what
+    it saved, with the same dispatch; the map itself is not formed."""
+    if isinstance(saved[0], str):
+        return xattn_colmean(saved)
+    q3, k3, _ = _qkv_views(saved[2], B)
+    lse, mask, da = saved[4], saved[8], saved[9]
+    return attn_colmean(q3, k3, lse, P.heads, mask, dropout=da)
+
+
 def _post_ln_bwd(dy, s, ln, mean, rstd, dh, rows=None):
     """Backward of the post-LayerNorm of a BERT sub-block whose dense output was dropped with dh = (p, seed) or None:
     (ds, dsd) = the gradient of the LayerNorm input (residual branch) and of the dense output before its dropout."""
@@ -1249,12 +1328,14 @@ def _ffn_sub_bwd(dy, saved, P):
 class BlockOpts(NamedTuple):
     """The per-call options of the fused block functions, built by the module at every call and passed beside `P` (which holds
     parameters only).  pdrop: dropout probability of this call (0 in eval mode).  cls_only: BertCrossLayerFn's live-row form.
-    fused_cross / need_bwd / want_probs: see _attn_sub_fwd."""
+    fused_cross / need_bwd / want_probs: see _attn_sub_fwd.  want_summary: BertCrossLayerFn also returns the received attention of
+    its two attentions (_attn_sub_colmean); like want_probs it needs the full layer and a fused call's P in memory."""
     pdrop: float = 0.0
     cls_only: bool = False
     fused_cross: bool = False
     want_probs: bool = False
     need_bwd: bool = True
+    want_summary: bool = False
 
 
 class BertCrossLayerFn(Function):
@@ -1274,20 +1355,26 @@ class BertCrossLayerFn(Function):
         # the fused cross-attention sub-block (csrc/xattn.hip) where the shapes are covered: forward-only calls always,
         # training with its fused backward (ops.XATTN_TRAIN)
         c, s2 = _attn_sub_fwd(a, B, L, other2, Lo, mask_other, P.cross, pd, fused_cross=opts.fused_cross, need_bwd=opts.need_bwd,
-                              want_probs=opts.want_probs, live=live)
+                              want_probs=opts.want_probs or opts.want_summary, live=live)
         y, s3 = _ffn_sub_fwd(c, P.ffn, pd, rows=(0, L) if live else None)
         ctx.saved = (s1, s2, s3)
         ctx.P, ctx.dims, ctx.n_anchor = P, (B, L, Lo, D), len(anchors)
         ctx.need_other = other.requires_grad
+        extra = ()
         if opts.want_probs:
             # the two attention maps (bert_model.py:346 of the self- and the cross-attention), read-only outputs
-            maps = (_attn_sub_probs(s1, B, L, L, P.attn), _attn_sub_probs(s2, B, L, Lo, P.cross))
-            ctx.mark_non_differentiable(*maps)
-            return (y.view(B, L, D),) + maps
+            extra += (_attn_sub_probs(s1, B, L, L, P.attn), _attn_sub_probs(s2, B, L, Lo, P.cross))
+        if opts.want_summary:
+            # their means over heads and queries, [B, L] and [B, Lo], after the maps when both are asked for
+            assert not live, "attention summaries are full-layer outputs"
+            extra += (_attn_sub_colmean(s1, B, L, L, P.attn), _attn_sub_colmean(s2, B, L, Lo, P.cross))
+        if extra:
+            ctx.mark_non_differentiable(*extra)
+            return (y.view(B, L, D),) + extra
         return y.view(B, -1, D)
 
     @staticmethod
-    def backward(ctx, dy, *_maps):   # (the maps, when returned, carry no gradient)
+    def backward(ctx, dy, *_maps):   # (the maps and summaries, when returned, carry no gradient)
         B, L, Lo, D = ctx.dims
         s1, s2, s3 = ctx.saved
         ctx.saved = None

@@ -39,6 +39,7 @@ TILED_ENTRIES = ("m3ae_tile_bf16_batched",)
 CLIP_ENTRIES = ("m3ae_sumsq_workspace_bytes", "m3ae_sumsq_segments", "m3ae_clip_finalize", "m3ae_adamw_clip")
 OPTIM_ENTRIES = ("m3ae_adam", "m3ae_adam_clip", "m3ae_sgd", "m3ae_sgd_clip")
 GREEDY_ENTRIES = ("m3ae_greedy_workspace_bytes", "m3ae_greedy_argmax", "m3ae_greedy_step")
+SUMMARY_ENTRIES = ("m3ae_attn_colmean_workspace_bytes", "m3ae_attn_colmean", "m3ae_xattn_probs_colmean", "m3ae_heatmap_upsample")
 ROWS_ENTRIES = ("m3ae_gemm_rows", "m3ae_attn_fwd_rows", "m3ae_attn_bwd_rows", "m3ae_layernorm_bwd_drop_rows", "m3ae_dropout_rows")
 
 
@@ -119,6 +120,11 @@ def block():
     out.append("")
     out.append("# device-resident greedy search for the decoder head (ABI 4, additive): order keys per vocabulary chunk, then the step")
     for name in GREEDY_ENTRIES:
+        res, args = _lib._SIGS[name]
+        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
+    out.append("")
+    out.append("# attention summaries (ABI 4, additive): fp32 [B, Lk] head-and-query mean of a map without the map; heatmap upsample")
+    for name in SUMMARY_ENTRIES:
         res, args = _lib._SIGS[name]
         out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
     out.append("```")
