@@ -56,6 +56,8 @@ extern "C" {
 /* 4 (additive): attention summaries.  m3ae_attn_colmean (+ m3ae_attn_colmean_workspace_bytes) and m3ae_xattn_probs_colmean: the mean
  *    of an attention map over heads and queries, fp32 [B][Lk], without the map; m3ae_heatmap_upsample (csrc/heatmap.hip): bilinear
  *    upsample of a patch grid; no descriptor changed. */
+/* 4 (additive): device-side VQA evaluation.  m3ae_vqa_eval (+ m3ae_vqa_eval_workspace_bytes) and m3ae_seq_match
+ *    (csrc/vqa_eval.hip): prediction, top-k answers and the closed / open / overall score record; no descriptor changed. */
 #define M3AE_ABI_VERSION 4
 
 enum { M3AE_F32 = 0, M3AE_BF16 = 1 };
@@ -764,6 +766,50 @@ int m3ae_expand_samples(const void* in, const int64_t* src, void* out, int64_t n
                         void* stream);
 int m3ae_segment_sum_rows(const void* d_out, const int64_t* offsets, const int64_t* members, void* d_in, int64_t n_in,
                           int64_t n_out, int64_t R, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Device-side VQA evaluation (csrc/vqa_eval.hip; ABI 4, additive): the prediction, the top-k answers and the closed / open / overall
+ * score sums of a validation pass, with no host involvement.
+ *
+ * The record: double rec[M3AE_VQA_REC_DOUBLES] in device memory, zeroed by the caller (m3ae_zero) before the first update.  For
+ *   group g of (all, closed, open): rec[3 g + 0] = n_g rows seen, rec[3 g + 1] = sum of hit1, rec[3 g + 2] = sum of hitk;
+ *   rec[9] = number of update calls.  A row's group is types[r]: M3AE_ANS_CLOSED or M3AE_ANS_OPEN (the reference's values,
+ *   my_metrics.py:180-181); any other value, and every row when types is NULL, counts in "all" only.
+ *
+ * m3ae_vqa_eval: one workgroup per row.  logits [B][C], dtype M3AE_F32 or M3AE_BF16, row stride ld >= C in elements; the base
+ *   pointer is element-aligned, nothing else is asked of ld, and columns [C, ld) are never read (as m3ae_greedy_argmax).  targets
+ *   fp32 [B][C] with row stride ldt >= C, or NULL; types int32 [B] or NULL.
+ *   Ranking: by the order key of m3ae_greedy_argmax -- value descending, the lowest column among equal values (+0 == -0), every
+ *   NaN of either sign above every number, the first NaN first.  Rank 0 is torch.max(logits, 1)[1], the reference's prediction
+ *   (my_metrics.py:68); ranks 0 .. k - 1 are the top-k, 0 <= k <= 16.  The row is read once; keys of distinct columns are distinct,
+ *   so the result depends on no order.
+ *   Per row: hit1 = targets[r][rank 0]; hitk = the maximum of targets[r][col] over the top-k (k = 0: 0).
+ *   Outputs, each may be NULL: pred int64 [B] (rank 0); topk_idx int32 [B][k]; topk_prob fp32 [B][k] = 1 / (1 + expf(-x)) of the
+ *   fp32-widened logit (a NaN logit gives NaN); hit1 fp32 [B] (written only with targets).  NULL targets skip the hits and the
+ *   record; NULL rec skips the record.
+ *   The fold (targets and rec given): one launch of one workgroup adds the rows' hit1 / hitk and the counts onto rec, in double,
+ *   in an order that depends on B alone; no atomics, so deterministic mode needs no second form.  With scores in {0} u [2^-20, 1]
+ *   and at most 1024 rows accumulated every sum is exact, whatever the order.  workspace: m3ae_vqa_eval_workspace_bytes(B, k)
+ *   bytes (the rows' {hit1, hitk}; 0 for a B or k the call rejects), 8-byte aligned, needed only when the fold runs.
+ *   M3AE_ERR_ARG: NULL logits, B < 1, C < 1, k < 0.  M3AE_ERR_UNSUPPORTED, before any launch: k > 16, k > C, C >= 2^31, B >= 2^31,
+ *   a dtype other than fp32 / bf16, ld < C (ldt < C), a missing or short workspace.  M3AE_ERR_ALIGN: a pointer off its element size.
+ *
+ * m3ae_seq_match: TOKEN exact match for the generator heads.  gen int64 [B][Lg] (row stride ldg), ref int64 [B][Lr] (row stride
+ *   ldr), skip int64 [ns], 0 <= ns <= 8 (device memory; pad / start / end ids).  Row r matches iff the subsequence of gen[r] with
+ *   ids outside skip equals the same subsequence of ref[r]; hit1 = hitk = 1.0 or 0.0 go onto rec through the same fold (types,
+ *   rec and workspace as above; rec is required).  match: optional int32 [B].  One thread per row, one workgroup per 256 rows.
+ *   Equal ids imply equal decoded strings, so this is a LOWER BOUND of the reference's string VQAExactMatch (my_metrics.py:80-96:
+ *   two id sequences may decode to the same text); it is not that metric.
+ *   M3AE_ERR_UNSUPPORTED: ns > 8, B >= 2^31, ldg < Lg, ldr < Lr, a missing or short workspace. */
+enum { M3AE_ANS_CLOSED = 0, M3AE_ANS_OPEN = 1 };
+enum { M3AE_VQA_REC_DOUBLES = 10 };
+int64_t m3ae_vqa_eval_workspace_bytes(int64_t B, int64_t k);
+int m3ae_vqa_eval(const void* logits, int64_t ld, const float* targets, int64_t ldt, const int32_t* types, int64_t B, int64_t C,
+                  int64_t k, int dtype, int64_t* pred, int32_t* topk_idx, float* topk_prob, float* hit1, double* rec,
+                  void* workspace, int64_t workspace_bytes, void* stream);
+int m3ae_seq_match(const int64_t* gen, int64_t ldg, int64_t Lg, const int64_t* ref, int64_t ldr, int64_t Lr, const int64_t* skip,
+                   int64_t ns, const int32_t* types, int64_t B, int32_t* match, double* rec, void* workspace,
+                   int64_t workspace_bytes, void* stream);
 
 /* self-test of hardware idioms the kernels rely on (MFMA fragment maps, ds_read_b64_tr_b16, accumulator-as-
  * operand k-order).  out: int32[8 + 256] device buffer (tail = scratch), out[0] = number of mismatches. */

@@ -1,0 +1,256 @@
+// Device-side VQA evaluation (m3ae_amd/metrics.py, M3AETransformerSS.predict): the prediction of the reference's VQARADScore
+// (my_metrics.py:68, torch.max(logits, 1)[1]), the top-k answers with their probabilities, the per-row hits against the soft
+// targets and the running record {n, sum_top1, sum_topk} x {all, closed, open}, with no host involvement.
+//
+// m3ae_vqa_eval, one launch (+ the fold when there are targets and a record):
+//   vqa_eval_kernel, one workgroup per row.  The row is read ONCE (scalar head up to the first 16-byte boundary, 16-byte loads,
+//   scalar tail, as csrc/greedy.hip: no load touches a column at or past C).  Every value becomes the order key of
+//   csrc/order_key.h with greedy.hip's NaN / -0 handling; a thread keeps the kk = max(k, 1) greatest keys of ITS columns in LDS
+//   (cand[slot][thread]; 0 = empty, no key is 0).  The row's top-k is a subset of the union of the threads' top-k, so rank j is
+//   "the greatest candidate below rank j - 1": k passes over LDS, each a wave maximum and a four-way fold.  Keys of distinct
+//   columns are distinct integers: the result does not depend on any order.  The value of a chosen column is decoded from its
+//   key (exact but for -0 -> +0 and the NaN payload, neither of which the sigmoid sees).
+//   vqa_fold_kernel, one workgroup: thread t adds rows t, t + 256, ... in double, lanes then waves combine in a fixed tree, thread
+//   0 adds the nine sums onto the record and counts the call.  The order depends on B alone; no atomics.
+// m3ae_seq_match: one thread per row walks gen[r] and ref[r] with the skip ids dropped; then the same fold.
+#include "common.h"
+#include "order_key.h"
+#include <math.h>
+
+namespace {
+
+constexpr int VT = 256;          // threads of every kernel here
+constexpr int V_MAX_K = 16;
+constexpr int V_MAX_SKIP = 8;
+
+DEVINL uint64_t eval_key(uint32_t u, uint32_t col) {   // u = the bits of an fp32 value; csrc/greedy.hip's rule
+    if ((u & 0x7fffffffu) > 0x7f800000u) return ((uint64_t)0xffffffffu << 32) | (uint64_t)(0xffffffffu - col);   // NaN: above +inf
+    return make_key(__uint_as_float(u == 0x80000000u ? 0u : u), col);                                           // -0 -> +0
+}
+DEVINL uint32_t bits_of(float v) { return __float_as_uint(v); }
+DEVINL uint32_t bits_of(bf16_t v) { return (uint32_t)v << 16; }
+
+// The kk greatest keys a thread has seen, in cand[slot * VT + tid]; mn / mnpos = the least of them and its slot.
+struct Keep {
+    uint64_t* c;
+    int kk, mnpos;
+    uint64_t mn;
+    DEVINL void put(uint64_t key) {
+        if (key <= mn) return;
+        c[mnpos * VT] = key;
+        mn = c[0];
+        mnpos = 0;
+        for (int s = 1; s < kk; ++s) {
+            const uint64_t v = c[s * VT];
+            if (v < mn) { mn = v; mnpos = s; }
+        }
+    }
+};
+
+template <typename T>
+__global__ __launch_bounds__(VT) void vqa_eval_kernel(const T* __restrict__ logits, int64_t ld, const float* __restrict__ targets,
+                                                      int64_t ldt, int64_t C, int k, int64_t* __restrict__ pred,
+                                                      int32_t* __restrict__ topk_idx, float* __restrict__ topk_prob,
+                                                      float* __restrict__ hit1_out, float* __restrict__ rows) {
+    constexpr int W = 16 / (int)sizeof(T);   // elements of one 16-byte load
+    __shared__ uint64_t cand[V_MAX_K * VT];
+    __shared__ uint64_t red[2][VT / 64];
+    __shared__ uint64_t sel[V_MAX_K];
+    const int64_t r = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int kk = k > 0 ? k : 1;
+    const T* x = logits + r * ld;
+    for (int s = 0; s < kk; ++s) cand[s * VT + tid] = 0;   // a thread reads and writes its own column of cand only
+    Keep keep{cand + tid, kk, 0, 0};
+
+    // x is element-aligned (host check): `mis` elements past a 16-byte boundary
+    const int64_t mis = (int64_t)(((uintptr_t)x & 15) / sizeof(T));
+    int64_t head = mis ? W - mis : 0;
+    head = head < C ? head : C;
+    const int64_t nvec = (C - head) / W;
+    const int64_t tail0 = head + nvec * W;
+    if (tid < head) keep.put(eval_key(bits_of(x[tid]), (uint32_t)tid));
+    const u32x4* xv = (const u32x4*)(x + head);
+    for (int64_t i = tid; i < nvec; i += VT) {
+        const u32x4 q = xv[i];
+        const uint32_t j0 = (uint32_t)(head + i * W);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            if (sizeof(T) == 4) {
+                keep.put(eval_key(q[e], j0 + e));
+            } else {   // two bf16 per dword, the lower column in the low half
+                keep.put(eval_key(q[e] << 16, j0 + 2 * e));
+                keep.put(eval_key(q[e] & 0xffff0000u, j0 + 2 * e + 1));
+            }
+        }
+    }
+    if (tail0 + tid < C) keep.put(eval_key(bits_of(x[tail0 + tid]), (uint32_t)(tail0 + tid)));   // < W <= VT columns
+
+    // rank j = the greatest candidate below rank j - 1 (rank 0: the greatest)
+    uint64_t prev = 0;
+    for (int j = 0; j < kk; ++j) {
+        uint64_t best = 0;
+        for (int s = 0; s < kk; ++s) {
+            const uint64_t v = cand[s * VT + tid];
+            if ((j == 0 || v < prev) && v > best) best = v;
+        }
+        best = wave_max_u64(best);
+        if ((tid & 63) == 0) red[j & 1][tid >> 6] = best;
+        __syncthreads();   // one barrier a pass: pass j + 2 reuses red[j & 1] only after every thread has passed the barrier of j + 1
+        const uint64_t a = red[j & 1][0], b = red[j & 1][1], c = red[j & 1][2], d = red[j & 1][3];
+        const uint64_t ab = a > b ? a : b, cd = c > d ? c : d;
+        prev = ab > cd ? ab : cd;
+        if (tid == 0) sel[j] = prev;
+    }
+    __syncthreads();
+
+    // a key of 0 (fewer than kk columns: the host refuses k > C) or a column outside [0, C) is never an address
+    if (tid < k) {
+        const uint64_t g = sel[tid];
+        const int64_t col = (int64_t)(0xffffffffu - (uint32_t)g);
+        const bool ok = g != 0 && col < C;
+        if (topk_idx) topk_idx[r * k + tid] = ok ? (int32_t)col : -1;
+        if (topk_prob) {
+            const uint32_t hi = (uint32_t)(g >> 32);
+            const float v = hi == 0xffffffffu ? __uint_as_float(0x7fc00000u) : unord32(hi);
+            topk_prob[r * k + tid] = ok ? 1.0f / (1.0f + expf(-v)) : 0.0f;
+        }
+    }
+    if (tid == 0) {
+        const uint64_t g0 = sel[0];
+        const int64_t top = (int64_t)(0xffffffffu - (uint32_t)g0);
+        const bool ok0 = g0 != 0 && top < C;
+        if (pred) pred[r] = ok0 ? top : -1;
+        if (targets) {
+            const float* t = targets + r * ldt;
+            const float h1 = ok0 ? t[top] : 0.0f;
+            float hk = k > 0 ? h1 : 0.0f;      // k = 0: the maximum over no column
+            for (int j = 1; j < k; ++j) {
+                const uint64_t g = sel[j];
+                const int64_t col = (int64_t)(0xffffffffu - (uint32_t)g);
+                if (g != 0 && col < C) {
+                    const float v = t[col];
+                    hk = v > hk ? v : hk;
+                }
+            }
+            if (hit1_out) hit1_out[r] = h1;
+            if (rows) { rows[2 * r] = h1; rows[2 * r + 1] = hk; }
+        }
+    }
+}
+
+DEVINL double shfl_xor_d(double v, int o) { return __shfl_xor(v, o, 64); }
+
+// rows fp32 [B][2] = {hit1, hitk}; rec double [10] += {n, sum_top1, sum_topk} of (all, closed, open), rec[9] += 1
+__global__ __launch_bounds__(VT) void vqa_fold_kernel(const float* __restrict__ rows, const int32_t* __restrict__ types, int64_t B,
+                                                      double* __restrict__ rec) {
+    __shared__ double red[VT / 64][9];
+    const int tid = threadIdx.x;
+    double acc[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) acc[i] = 0.0;
+    for (int64_t r = tid; r < B; r += VT) {
+        const double h1 = (double)rows[2 * r], hk = (double)rows[2 * r + 1];
+        const int ty = types ? types[r] : -1;
+        acc[0] += 1.0; acc[1] += h1; acc[2] += hk;
+        if (ty == M3AE_ANS_CLOSED) { acc[3] += 1.0; acc[4] += h1; acc[5] += hk; }
+        if (ty == M3AE_ANS_OPEN) { acc[6] += 1.0; acc[7] += h1; acc[8] += hk; }
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc[i] += shfl_xor_d(acc[i], o);
+    }
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) red[tid >> 6][i] = acc[i];
+    }
+    __syncthreads();
+    if (tid < 9) rec[tid] += (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
+    if (tid == 9) rec[9] += 1.0;
+}
+
+struct SkipIds { int64_t id[V_MAX_SKIP]; };
+
+__global__ __launch_bounds__(VT) void seq_match_kernel(const int64_t* __restrict__ gen, int64_t ldg, int64_t Lg,
+                                                       const int64_t* __restrict__ ref, int64_t ldr, int64_t Lr,
+                                                       const int64_t* __restrict__ skip, int ns, int64_t B,
+                                                       int32_t* __restrict__ match, float* __restrict__ rows) {
+    const int64_t r = (int64_t)blockIdx.x * VT + threadIdx.x;
+    if (r >= B) return;
+    SkipIds sk;
+#pragma unroll
+    for (int i = 0; i < V_MAX_SKIP; ++i) sk.id[i] = i < ns ? skip[i] : 0;
+    auto skipped = [&](int64_t t) {
+        bool s = false;
+#pragma unroll
+        for (int i = 0; i < V_MAX_SKIP; ++i) s = s || (i < ns && t == sk.id[i]);
+        return s;
+    };
+    const int64_t* g = gen + r * ldg;
+    const int64_t* f = ref + r * ldr;
+    int64_t i = 0, j = 0;
+    bool same = true;
+    while (same) {
+        while (i < Lg && skipped(g[i])) ++i;
+        while (j < Lr && skipped(f[j])) ++j;
+        if (i >= Lg || j >= Lr) {
+            same = i >= Lg && j >= Lr;     // both subsequences end together
+            break;
+        }
+        same = g[i] == f[j];
+        ++i;
+        ++j;
+    }
+    if (match) match[r] = same ? 1 : 0;
+    rows[2 * r] = rows[2 * r + 1] = same ? 1.0f : 0.0f;
+}
+
+inline int64_t rows_bytes(int64_t B) { return B * 2 * (int64_t)sizeof(float); }
+
+}  // namespace
+
+extern "C" int64_t m3ae_vqa_eval_workspace_bytes(int64_t B, int64_t k) {
+    if (B < 1 || B > (int64_t)INT32_MAX || k < 0 || k > V_MAX_K) return 0;
+    return rows_bytes(B);
+}
+
+extern "C" int m3ae_vqa_eval(const void* logits, int64_t ld, const float* targets, int64_t ldt, const int32_t* types, int64_t B,
+                             int64_t C, int64_t k, int dtype, int64_t* pred, int32_t* topk_idx, float* topk_prob, float* hit1,
+                             double* rec, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!logits || B < 1 || C < 1 || k < 0) return M3AE_ERR_ARG;
+    if (dtype != M3AE_F32 && dtype != M3AE_BF16) return M3AE_ERR_UNSUPPORTED;
+    if (k > V_MAX_K || k > C || C > (int64_t)INT32_MAX || B > (int64_t)INT32_MAX || ld < C || (targets && ldt < C)) return M3AE_ERR_UNSUPPORTED;
+    const bool fold = targets && rec;
+    if (fold && (!workspace || workspace_bytes < rows_bytes(B))) return M3AE_ERR_UNSUPPORTED;
+    if (((uintptr_t)logits & (dtype == M3AE_F32 ? 3 : 1)) || ((uintptr_t)targets & 3) || ((uintptr_t)types & 3) || ((uintptr_t)pred & 7) ||
+        ((uintptr_t)topk_idx & 3) || ((uintptr_t)topk_prob & 3) || ((uintptr_t)hit1 & 3) || ((uintptr_t)rec & 7) ||
+        (fold && ((uintptr_t)workspace & 7)))
+        return M3AE_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    float* rows = fold ? (float*)workspace : nullptr;
+    if (dtype == M3AE_F32)
+        hipLaunchKernelGGL(vqa_eval_kernel<float>, dim3((unsigned)B), dim3(VT), 0, s, (const float*)logits, ld, targets, ldt, C, (int)k, pred,
+                           topk_idx, topk_prob, hit1, rows);
+    else
+        hipLaunchKernelGGL(vqa_eval_kernel<bf16_t>, dim3((unsigned)B), dim3(VT), 0, s, (const bf16_t*)logits, ld, targets, ldt, C, (int)k,
+                           pred, topk_idx, topk_prob, hit1, rows);
+    if (fold) hipLaunchKernelGGL(vqa_fold_kernel, dim3(1), dim3(VT), 0, s, (const float*)rows, types, B, rec);
+    return hip_launch_status();
+}
+
+extern "C" int m3ae_seq_match(const int64_t* gen, int64_t ldg, int64_t Lg, const int64_t* ref, int64_t ldr, int64_t Lr,
+                              const int64_t* skip, int64_t ns, const int32_t* types, int64_t B, int32_t* match, double* rec,
+                              void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!gen || !ref || !rec || B < 1 || Lg < 0 || Lr < 0 || ns < 0 || (ns > 0 && !skip)) return M3AE_ERR_ARG;
+    if (ns > V_MAX_SKIP || B > (int64_t)INT32_MAX || ldg < Lg || ldr < Lr) return M3AE_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < rows_bytes(B)) return M3AE_ERR_UNSUPPORTED;
+    if (((uintptr_t)gen & 7) || ((uintptr_t)ref & 7) || ((uintptr_t)skip & 7) || ((uintptr_t)types & 3) || ((uintptr_t)match & 3) ||
+        ((uintptr_t)rec & 7) || ((uintptr_t)workspace & 7))
+        return M3AE_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(seq_match_kernel, dim3((unsigned)cdiv(B, VT)), dim3(VT), 0, s, gen, ldg, Lg, ref, ldr, Lr, skip, (int)ns, B, match,
+                       (float*)workspace);
+    hipLaunchKernelGGL(vqa_fold_kernel, dim3(1), dim3(VT), 0, s, (const float*)workspace, types, B, rec);
+    return hip_launch_status();
+}

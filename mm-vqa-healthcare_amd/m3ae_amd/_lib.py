@@ -62,6 +62,8 @@ ATTN_LEGACY_KERNELS, ATTN_F32_X3 = 1, 2           # m3ae_attn_desc.launch_flags
 XATTN_NO_PERSISTENT, XATTN_LEGACY_CHAIN = 1, 2    # m3ae_xattn_desc.launch_flags
 # 32-bit word indices of the clipping record m3ae_clip_finalize writes and m3ae_adamw_clip reads (include/m3ae_hip.h)
 CLIP_NORM, CLIP_COEF, CLIP_SKIP, CLIP_STEPS, CLIP_CLIPPED_STEPS, CLIP_SKIPPED_STEPS, CLIP_RECORD_WORDS = 0, 1, 2, 4, 5, 6, 8
+# the record of m3ae_vqa_eval / m3ae_seq_match (include/m3ae_hip.h): 10 doubles, {n, sum_top1, sum_topk} of (all, closed, open), calls
+ANS_CLOSED, ANS_OPEN, VQA_REC_DOUBLES, VQA_MAX_K, SEQ_MAX_SKIP = 0, 1, 10, 16, 8
 ABI_VERSION = 4
 
 
@@ -166,6 +168,10 @@ _SIGS = {
     "m3ae_attn_colmean": (C.c_int, [C.POINTER(AttnDesc), vp, i64, vp, i64, vp]),
     "m3ae_xattn_probs_colmean": (C.c_int, [C.POINTER(XattnDesc), C.c_int, vp, i64, vp]),
     "m3ae_heatmap_upsample": (C.c_int, [vp, i64, i64, vp, i64, i64, vp]),
+    # device-side VQA evaluation (ABI 4, additive): prediction, top-k answers, the score record (VQA_REC_*), token exact match
+    "m3ae_vqa_eval_workspace_bytes": (i64, [i64, i64]),
+    "m3ae_vqa_eval": (C.c_int, [vp, i64, vp, i64, vp, i64, i64, i64, C.c_int, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "m3ae_seq_match": (C.c_int, [vp, i64, i64, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -57,6 +57,11 @@ DEFAULTS = dict(
     # (ATen argmax / compares / cat and one blocking `finished.all()` per token) | "device" (csrc/greedy.hip, no host round trip per
     # token; same tokens)
     decoder_search="host",
+    # where validation / test compute their metric (m3ae_amd/trainer.py, m3ae_amd/metrics.py): "host" (ATen float / argmax /
+    # gather / sum: the overall VQA score alone) | "device" (csrc/vqa_eval.hip: overall, closed and open scores, the score within
+    # the top `eval_topk` answers, and token exact match for the generator heads in test()).  eval_topk is honoured only with "device".
+    vqa_metrics="host",
+    eval_topk=5,
     # arrow VQA batches collated per distinct image (m3ae_amd/data.py: collate_dedup): every distinct image of a batch is decoded,
     # uploaded and run through the image tower once, and ops.expand_samples hands its tokens to the samples that ask about it
     # (batch["image_index"]).  Same samples, same arithmetic per sample; not available with the mim / itm objectives.
@@ -184,6 +189,20 @@ def decoder_search(cfg):
     return v
 
 
+VQA_METRICS = ("host", "device")
+
+
+def vqa_metrics(cfg):
+    """The validated `vqa_metrics` of a config dict (default "host"); with "device", `eval_topk` must be an int in [0, 16]."""
+    v = cfg.get("vqa_metrics", "host")
+    if not isinstance(v, str) or v not in VQA_METRICS:
+        raise ValueError(f"vqa_metrics must be one of {VQA_METRICS}, got {v!r}")
+    k = cfg.get("eval_topk", 5)
+    if v == "device" and (isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= 16):
+        raise ValueError(f"eval_topk must be an integer in [0, 16] with vqa_metrics='device', got {k!r}")
+    return v
+
+
 OPTIM_TYPES = ("adamw", "adam", "sgd")
 
 
@@ -202,6 +221,7 @@ def resolve_arch(cfg):
     cfg = dict(cfg)
     optim_type(cfg)
     decoder_search(cfg)
+    vqa_metrics(cfg)
     if "gradient_clip_val" in cfg:
         cfg["gradient_clip_val"] = gradient_clip_val(cfg)
     clip_residual_dtype(cfg)

@@ -74,6 +74,20 @@ def init_weights(module):
         module.bias.data.zero_()
 
 
+def answers_of(labels, probs, label2ans):
+    """Rows of label ids and probabilities -> rows of (answer, probability) through label2ans[str(label)]."""
+    out = []
+    for ls, ps in zip(labels, probs):
+        row = []
+        for l, p in zip(ls, ps):
+            key = str(int(l))
+            if key not in label2ans:
+                raise KeyError(f"label {key} is not in label2ans ({len(label2ans)} answers)")
+            row.append((label2ans[key], float(p)))
+        out.append(row)
+    return out
+
+
 class M3AETransformerSS(_Base):
     def __init__(self, config):
         super().__init__()
@@ -462,6 +476,35 @@ class M3AETransformerSS(_Base):
         # 498 answers: N % 4 != 0 / K % 64 != 0 would send forward, dgrad and wgrad to the fp32-FMA generic kernel in perf mode
         # (6 launches per step at 3 TFLOP/s); the zero-padded operand copies of ops.vocab_linear keep them on the MFMA kernels
         return ops.vocab_linear(h, self.vqa_head[3].weight, self.vqa_head[3].bias)
+
+    @ops.model_mode
+    def predict(self, batch, k=5):
+        """The k most probable answers of every sample: {"labels": int64 [B, k] (answer label ids, best first: labels[:, 0] is
+        torch.max(logits, 1)[1], the reference's prediction), "probs": fp32 [B, k] (sigmoid of their logits), "logits": the head's
+        logits [B, vqa_label_size]}, all on the device.  Runs under no_grad in eval mode (the training flag is restored), with the
+        CLS-only last fusion layer; ranking and probabilities come from ops.vqa_eval on the logits as the head left them."""
+        if not hasattr(self, "vqa_head"):
+            raise RuntimeError('predict needs the VQA head (loss_names["vqa"] > 0)')
+        k = int(k)
+        if not 1 <= k <= 16:
+            raise ValueError(f"k={k} outside [1, 16]")
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                infer = self.infer(batch, mask_text=False, mask_image=False, cls_only=True)
+                logits = self.vqa_head_forward(infer["multi_modal_cls_feats"])
+                rows = ops.vqa_eval(logits, None, None, None, k=k, want_rows=True)
+        finally:
+            self.train(was_training)
+        return {"labels": rows.topk_idx.long(), "probs": rows.topk_prob, "logits": logits}
+
+    def answers(self, batch, label2ans, k=1):
+        """The k best answers of every sample as text: a list of B lists of (answer, probability), best first.  label2ans: the
+        reference's mapping with STRING keys (label2ans[str(label)], objectives.py:183-185).  A label it does not hold is a
+        KeyError that names it.  One blocking copy of the k labels and probabilities."""
+        out = self.predict(batch, k=k)
+        return answers_of(out["labels"].cpu().tolist(), out["probs"].cpu().tolist(), label2ans)
 
     @ops.model_mode
     def forward(self, batch, test=False):

@@ -134,6 +134,16 @@ class T5VQA_MMEncoderInput(_Base):
         out = self.t5(inputs["inputs_embeds"], self.labels_of(batch))
         return {"vqa_loss": out.loss, "vqa_logits": out.logits}
 
+    @ops.model_mode
+    def generate_async(self, batch, lookahead=2):
+        """The encoder output of `batch` and the device-resident beam search over it (forward(test=True)'s settings), nothing
+        copied to the host: the namespace of T5ForConditionalGeneration.generate_async (`seq`, `len`, `err`, `out`, ...)."""
+        if self.store is None:
+            raise RuntimeError("call finalize(device) before the first forward")
+        with torch.no_grad():
+            enc = self.t5.encoder(self.prepare_inputs(batch)["inputs_embeds"])
+        return self.t5.generate_async(enc, num_beams=4, max_length=self.max_answer_length, lookahead=lookahead)
+
     def training_step(self, batch, batch_idx=0):
         """m3ae_t5_mm_encoder_input.py:340-346."""
         self.current_tasks = [k for k, v in self.m3ae.hparams.config["loss_names"].items() if v > 0]

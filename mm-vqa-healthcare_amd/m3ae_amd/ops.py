@@ -2187,6 +2187,97 @@ def greedy_step(st, keys, V, pos, sep_id, eos_id, pad_id):
 
 
 # ------------------------------------------------------------------------------------------------------------
+# device-side VQA evaluation (csrc/vqa_eval.hip): m3ae_amd/metrics.py, M3AETransformerSS.predict
+# ------------------------------------------------------------------------------------------------------------
+class VqaRows(NamedTuple):
+    """The per-row outputs of vqa_eval(want_rows=True); topk_* are None for k = 0, hit1 without targets."""
+    pred: torch.Tensor                 # int64 [B]: torch.max(logits, 1)[1]
+    topk_idx: torch.Tensor | None      # int32 [B, k]
+    topk_prob: torch.Tensor | None     # fp32 [B, k]
+    hit1: torch.Tensor | None          # fp32 [B]
+
+
+def vqa_record(device):
+    """A zeroed record of vqa_eval / seq_match: float64 [10] (include/m3ae_hip.h)."""
+    return torch.zeros((_lib.VQA_REC_DOUBLES,), dtype=torch.float64, device=device)
+
+
+def _eval_common(what, B, types, rec, device):
+    if types is not None:
+        _need_cuda(types)
+        if types.dtype != torch.int32 or tuple(types.shape) != (B,) or not types.is_contiguous():
+            raise ValueError(f"{what}: types int32 [B], contiguous")
+    if rec is not None:
+        _need_cuda(rec)
+        if rec.dtype != torch.float64 or tuple(rec.shape) != (_lib.VQA_REC_DOUBLES,) or not rec.is_contiguous():
+            raise ValueError(f"{what}: rec float64 [{_lib.VQA_REC_DOUBLES}], contiguous (ops.vqa_record)")
+        return torch.empty((B, 2), dtype=torch.float32, device=device)
+    return None
+
+
+def vqa_eval(logits, targets, types, rec, k=0, want_rows=False):
+    """One update of the VQA score record from a batch, enqueued on the current stream (no host sync).
+    logits fp32 or bf16 [B, C] (row stride >= C, unit column stride: the [..., :498] view of vocab_linear's padded buffer is
+    taken as it is); targets fp32 [B, C] or None; types int32 [B] (_lib.ANS_CLOSED / ANS_OPEN, anything else: "all" only) or
+    None; rec float64 [10] (ops.vqa_record) or None.  Adds {n, hit1, hitk} of the rows onto rec, where hit1 is the target of
+    torch.max(logits, 1)[1] and hitk the best target among the top-k (0 <= k <= 16).  want_rows: returns VqaRows."""
+    _need_cuda(logits)
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("vqa_eval takes fp32 or bf16 logits")
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        raise ValueError(f"vqa_eval: logits {tuple(logits.shape)} with strides {tuple(logits.stride())}")
+    B, Cc = logits.shape
+    k = int(k)
+    if not 0 <= k <= min(_lib.VQA_MAX_K, Cc):
+        raise ValueError(f"vqa_eval: k={k} outside [0, min({_lib.VQA_MAX_K}, C={Cc})]")
+    if targets is not None:
+        _need_cuda(targets)
+        if targets.dtype != torch.float32 or tuple(targets.shape) != (B, Cc) or targets.stride(1) != 1 or targets.stride(0) < Cc:
+            raise ValueError(f"vqa_eval: targets fp32 {(B, Cc)}, unit column stride; got {targets.dtype} {tuple(targets.shape)}")
+    ws = _eval_common("vqa_eval", B, types, rec if targets is not None else None, logits.device)
+    if rec is not None and targets is None:
+        raise ValueError("vqa_eval: a record needs targets")
+    dev = logits.device
+    pred = idx = prob = hit1 = None
+    if want_rows:
+        pred = torch.empty((B,), dtype=torch.int64, device=dev)
+        if k:
+            idx = torch.empty((B, k), dtype=torch.int32, device=dev)
+            prob = torch.empty((B, k), dtype=torch.float32, device=dev)
+        if targets is not None:
+            hit1 = torch.empty((B,), dtype=torch.float32, device=dev)
+    check(_lib.lib().m3ae_vqa_eval(_p(logits), logits.stride(0), _p(targets), 0 if targets is None else targets.stride(0), _p(types), B,
+                                   Cc, k, _dt(logits), _p(pred), _p(idx), _p(prob), _p(hit1), _p(rec), _p(ws),
+                                   0 if ws is None else ws.numel() * 4, _stream()), "m3ae_vqa_eval")
+    return VqaRows(pred, idx, prob, hit1) if want_rows else None
+
+
+def seq_match(gen, ref, skip, types, rec, want_rows=False):
+    """Token exact match of generated ids against reference ids, enqueued on the current stream (no host sync): gen int64
+    [B, Lg], ref int64 [B, Lr] (unit column stride), skip int64 [ns <= 8] on the device (ids dropped from both sides before the
+    compare: pad / start / end), types and rec as vqa_eval.  Adds {n, match, match} of the rows onto rec.  want_rows: the
+    per-row int32 [B] (1 = match).  Equal ids imply equal strings: a lower bound of the reference's string exact match."""
+    _need_cuda(gen)
+    _need_cuda(ref)
+    _need_cuda(skip)
+    for name, t in (("gen", gen), ("ref", ref)):
+        if t.dtype != torch.int64 or t.dim() != 2 or t.shape[0] != gen.shape[0] or t.shape[0] < 1 or \
+                (t.shape[1] > 0 and (t.stride(1) != 1 or t.stride(0) < t.shape[1])):
+            raise ValueError(f"seq_match: {name} int64 [B, L], unit column stride; got {t.dtype} {tuple(t.shape)} {tuple(t.stride())}")
+    if skip.dtype != torch.int64 or skip.dim() != 1 or skip.shape[0] > _lib.SEQ_MAX_SKIP or not skip.is_contiguous():
+        raise ValueError(f"seq_match: skip int64 [ns], ns <= {_lib.SEQ_MAX_SKIP}")
+    if rec is None:
+        raise ValueError("seq_match: rec is required (ops.vqa_record)")
+    B = gen.shape[0]
+    ws = _eval_common("seq_match", B, types, rec, gen.device)
+    match = torch.empty((B,), dtype=torch.int32, device=gen.device) if want_rows else None
+    check(_lib.lib().m3ae_seq_match(_p(gen), gen.stride(0), gen.shape[1], _p(ref), ref.stride(0), ref.shape[1],
+                                    _p(skip) if skip.shape[0] else None, skip.shape[0], _p(types), B, _p(match), _p(rec), _p(ws),
+                                    ws.numel() * 4, _stream()), "m3ae_seq_match")
+    return match
+
+
+# ------------------------------------------------------------------------------------------------------------
 # masked-image-modelling bookkeeping (pre-training, SURVEY 8a13)
 # ------------------------------------------------------------------------------------------------------------
 def mask_ranks(noise, len_keep):

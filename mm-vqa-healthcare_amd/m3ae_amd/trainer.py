@@ -19,7 +19,9 @@ arithmetic around `training_step`:
 * validation every `val_check_interval` of an epoch with the VQA score `val/the_metric` (my_metrics.py:58-83), best +
   last checkpoints (`ModelCheckpoint(save_top_k=1, monitor="val/the_metric", mode="max", save_last=True)`,
   main.py:36-43) written as `{"state_dict": ...}` with the REFERENCE's key names, so the files load in the upstream
-  code and upstream checkpoints load here (`load_path`); `save_weights_only` when "finetune" is in `exp_name`;
+  code and upstream checkpoints load here (`load_path`); `save_weights_only` when "finetune" is in `exp_name`; with
+  `vqa_metrics=device` the score is kept on the GPU (m3ae_amd/metrics.py) and validation also reports the closed / open scores
+  and the score within the top `eval_topk` answers, `test()` token exact match for the generator heads;
 * one process per GPU: launched under `python -m torch.distributed.run --nproc-per-node N main.py with ...`
   (RANK / LOCAL_RANK / WORLD_SIZE), RCCL through `torch.distributed`; `num_gpus` * `num_nodes` must equal the world.
 
@@ -40,6 +42,7 @@ import torch
 import torch.distributed as dist
 
 from . import config as config_mod
+from . import metrics as metrics_mod
 from . import ops, synth
 from .ddp import FlatGradReducer
 
@@ -147,6 +150,10 @@ class Trainer:
         self.ckpt_dir = os.path.join(cfg["log_dir"], run_name, "checkpoints")
         self.weights_only = "finetune" in exp  # main.py:42
         self.history = []
+        # config key `vqa_metrics`: "host" (the overall score in ATen) | "device" (m3ae_amd/metrics.py: overall / closed / open / @k,
+        # and token exact match in test() for the generator heads).  metrics / exact_match: the result() dicts of the last pass.
+        self.vqa_metrics = config_mod.vqa_metrics(cfg)
+        self.metrics, self.exact_match = None, None
 
     # -- checkpoints (reference key names; loadable by m3ae_module.py:105-113 upstream) ------------------------
     def save(self, name, metric=None):
@@ -155,6 +162,8 @@ class Trainer:
         os.makedirs(self.ckpt_dir, exist_ok=True)
         ck = {"state_dict": state_dict_cpu(self.model), "global_step": self.global_step, "epoch": self.epoch,
               "hyper_parameters": {"config": {k: v for k, v in self.cfg.items()}}, "val/the_metric": metric}
+        if self.metrics is not None:
+            ck["val/closed_score"], ck["val/open_score"] = self.metrics["closed"], self.metrics["open"]
         if not self.weights_only:   # Lightning's keys
             ck["optimizer_states"] = [self.optimizer.state_dict()]
             ck["lr_schedulers"] = [self.scheduler.state_dict()]
@@ -192,9 +201,33 @@ class Trainer:
         out = self.model.training_step(batch)
         return out["loss"] if isinstance(out, dict) else out
 
-    def validate(self):
+    def _generator_metric(self):
+        """TokenExactMatch for the generator head of the model with its pad / start / end ids as the skip set, and the function
+        batch -> reference token ids; (None, None) for the classification model."""
+        m = self.model
+        if hasattr(m, "tokens_of"):       # decoder head: [CLS] answer [SEP] [PAD]...
+            return metrics_mod.TokenExactMatch((m.pad_id, m.cls_id, m.sep_id), self.device), m.tokens_of
+        if hasattr(m, "labels_of"):       # T5 head: answer </s> <pad>...
+            c = m.t5.config
+            return metrics_mod.TokenExactMatch((c.pad_token_id, c.decoder_start_token_id, c.eos_token_id), self.device), m.labels_of
+        return None, None
+
+    def metrics_text(self):
+        """The closed / open / @k part of the validation log line ("" with vqa_metrics="host")."""
+        r = self.metrics
+        if r is None:
+            return ""
+        return f" closed {r['closed']:.4f} ({r['n_closed']}) open {r['open']:.4f} ({r['n_open']}) @{self.cfg.get('eval_topk', 5)} {r['score_at_k']:.4f}"
+
+    def validate(self, generate=False):
+        """The monitored quantity over the validation batches.  generate (test() with vqa_metrics="device"): the generator heads
+        also run their device-resident search per batch and feed TokenExactMatch from the ids, which stay on the device."""
         self.model.eval()
         tot, cnt = torch.zeros((), device=self.device), 0
+        device_metrics = self.vqa_metrics == "device"
+        score = metrics_mod.VQARADScore(self.device, k=self.cfg.get("eval_topk", 5)) if device_metrics and hasattr(self.model, "vqa_head_forward") else None
+        em, refs_of = self._generator_metric() if device_metrics and generate else (None, None)
+        fed = 0
         with torch.no_grad():
             for batch in self.dm.val_batches():
                 n = batch["text_ids"].shape[0]
@@ -202,18 +235,29 @@ class Trainer:
                 if hasattr(self.model, "vqa_head_forward"):
                     self.model.set_task()
                     ret = self.model(batch, test=True)
+                if ret is not None and "vqa_logits" in ret and score is not None:
+                    score.update(ret["vqa_logits"], ret["vqa_targets"], batch.get("answer_types"))   # enqueued; read once below
+                    fed += 1
+                    continue
                 if ret is not None and "vqa_logits" in ret:
                     s, n = vqa_score(ret["vqa_logits"], ret["vqa_targets"])
                 elif ret is not None:   # pre-training objectives: negative summed loss as the monitored quantity
                     s = -sum(v.float() for k, v in ret.items() if k.endswith("_loss")) * n
                 else:                   # generator heads: negative teacher-forced loss
                     s = -self._loss(batch).float() * n
+                    if em is not None:
+                        em.update(self.model.generate_async(batch).seq, refs_of(batch), batch.get("answer_types"))
                 tot += s
                 cnt += n
+        self.model.train()
+        if em is not None:
+            self.exact_match = em.result()
+        if fed:
+            self.metrics = score.result()    # the record's all-reduce and its one blocking copy
+            return self.metrics["score"]
         t = torch.stack([tot, torch.tensor(float(cnt), device=self.device)])
         if self.world > 1:
             dist.all_reduce(t)
-        self.model.train()
         return (t[0] / t[1]).item()
 
     def fit(self):
@@ -279,7 +323,7 @@ class Trainer:
                         done = True
                 if nbatch % val_every == 0 or done:
                     m = self.validate()
-                    log(f"val/the_metric {m:.4f} (best {max(self.best, m):.4f})", self.rank)
+                    log(f"val/the_metric {m:.4f} (best {max(self.best, m):.4f}){self.metrics_text()}", self.rank)
                     if m > self.best:
                         self.best = m
                         self.save("best.ckpt", m)
@@ -291,8 +335,12 @@ class Trainer:
         return {"global_step": self.global_step, "best": self.best, "history": self.history}
 
     def test(self):
-        m = self.validate()
-        log(f"test/the_metric {m:.4f}", self.rank)
+        m = self.validate(generate=True)
+        em = ""
+        if self.exact_match is not None:
+            r = self.exact_match
+            em = f" token_exact_match {r['score']:.4f} ({r['n']}) closed {r['closed']:.4f} ({r['n_closed']}) open {r['open']:.4f} ({r['n_open']})"
+        log(f"test/the_metric {m:.4f}{self.metrics_text()}{em}", self.rank)
         return m
 
 

@@ -40,6 +40,7 @@ CLIP_ENTRIES = ("m3ae_sumsq_workspace_bytes", "m3ae_sumsq_segments", "m3ae_clip_
 OPTIM_ENTRIES = ("m3ae_adam", "m3ae_adam_clip", "m3ae_sgd", "m3ae_sgd_clip")
 GREEDY_ENTRIES = ("m3ae_greedy_workspace_bytes", "m3ae_greedy_argmax", "m3ae_greedy_step")
 SUMMARY_ENTRIES = ("m3ae_attn_colmean_workspace_bytes", "m3ae_attn_colmean", "m3ae_xattn_probs_colmean", "m3ae_heatmap_upsample")
+VQA_EVAL_ENTRIES = ("m3ae_vqa_eval_workspace_bytes", "m3ae_vqa_eval", "m3ae_seq_match")
 ROWS_ENTRIES = ("m3ae_gemm_rows", "m3ae_attn_fwd_rows", "m3ae_attn_bwd_rows", "m3ae_layernorm_bwd_drop_rows", "m3ae_dropout_rows")
 
 
@@ -125,6 +126,13 @@ def block():
     out.append("")
     out.append("# attention summaries (ABI 4, additive): fp32 [B, Lk] head-and-query mean of a map without the map; heatmap upsample")
     for name in SUMMARY_ENTRIES:
+        res, args = _lib._SIGS[name]
+        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
+    out.append("")
+    out.append("# device-side VQA evaluation (ABI 4, additive): prediction, top-k answers, the closed / open / overall record; token exact match")
+    out.append(f"ANS_CLOSED, ANS_OPEN, VQA_REC_DOUBLES = {_lib.ANS_CLOSED}, {_lib.ANS_OPEN}, {_lib.VQA_REC_DOUBLES}     "
+               "# types values; double rec[10] = {n, sum_top1, sum_topk} x (all, closed, open), calls")
+    for name in VQA_EVAL_ENTRIES:
         res, args = _lib._SIGS[name]
         out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
     out.append("```")
