@@ -802,7 +802,7 @@ int m3ae_segment_sum_rows(const void* d_out, const int64_t* offsets, const int64
  *   two id sequences may decode to the same text); it is not that metric.
  *   M3AE_ERR_UNSUPPORTED: ns > 8, B >= 2^31, ldg < Lg, ldr < Lr, a missing or short workspace. */
 enum { M3AE_ANS_CLOSED = 0, M3AE_ANS_OPEN = 1 };
-enum { M3AE_VQA_REC_DOUBLES = 10 };
+enum { M3AE_VQA_REC_DOUBLES = 10, M3AE_VQA_MAX_K = 16 /* the bound on k above */, M3AE_SEQ_MAX_SKIP = 8 /* the bound on ns */ };
 int64_t m3ae_vqa_eval_workspace_bytes(int64_t B, int64_t k);
 int m3ae_vqa_eval(const void* logits, int64_t ld, const float* targets, int64_t ldt, const int32_t* types, int64_t B, int64_t C,
                   int64_t k, int dtype, int64_t* pred, int32_t* topk_idx, float* topk_prob, float* hit1, double* rec,

@@ -20,8 +20,8 @@
 namespace {
 
 constexpr int VT = 256;          // threads of every kernel here
-constexpr int V_MAX_K = 16;
-constexpr int V_MAX_SKIP = 8;
+constexpr int V_MAX_K = M3AE_VQA_MAX_K;
+constexpr int V_MAX_SKIP = M3AE_SEQ_MAX_SKIP;
 
 DEVINL uint64_t eval_key(uint32_t u, uint32_t col) {   // u = the bits of an fp32 value; csrc/greedy.hip's rule
     if ((u & 0x7fffffffu) > 0x7f800000u) return ((uint64_t)0xffffffffu << 32) | (uint64_t)(0xffffffffu - col);   // NaN: above +inf

@@ -9,6 +9,7 @@ LIB_PATH = os.path.join(_PKG, "lib_diag" if DIAGNOSTIC else "lib", "libm3ae_hip.
 
 F32, BF16 = 0, 1
 ACT_NONE, ACT_GELU, ACT_QUICKGELU, ACT_TANH, ACT_RELU, ACT_MULAUX = 0, 1, 2, 3, 4, 5
+ERR_ARG, ERR_UNSUPPORTED, ERR_ALIGN, ERR_WORKSPACE = -1, -2, -3, -4   # negative return values: rejected before any launch
 
 vp, i64, i32, f32 = C.c_void_p, C.c_int64, C.c_int32, C.c_float
 
@@ -214,6 +215,6 @@ def lib():
 
 def check(rc, what):
     if rc != 0:
-        kind = {-1: "invalid argument", -2: "unsupported shape/dtype", -3: "misaligned", -4: "workspace too small"}.get(
-            rc, f"hipError_t {rc}" if rc > 0 else f"error {rc}")
+        kind = {ERR_ARG: "invalid argument", ERR_UNSUPPORTED: "unsupported shape/dtype", ERR_ALIGN: "misaligned",
+                ERR_WORKSPACE: "workspace too small"}.get(rc, f"hipError_t {rc}" if rc > 0 else f"error {rc}")
         raise M3AEHipError(f"{what} failed: {kind}")

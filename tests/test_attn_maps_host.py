@@ -2,7 +2,6 @@
 accepts output_attentions, and the reference fixture holds what the GPU tests read."""
 import inspect
 import os
-import re
 import sys
 
 import numpy as np
@@ -21,17 +20,13 @@ ENTRIES = ("m3ae_attn_probs", "m3ae_xattn_probs_export")
 
 def test_attention_map_entry_points_are_declared_bound_and_in_the_stub():
     import gen_integration_stub as gen
-    hdr = open(os.path.join(ROOT, "include", "m3ae_hip.h")).read()
-    assert int(re.search(r"#define M3AE_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == 4
     stub = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    for name in ENTRIES:
-        assert re.search(r"\bint " + name + r"\(", hdr), name
+    for name in ENTRIES:         # declared == bound, argument by argument, and the ABI number: tests/test_host_logic.py
         assert name in _lib.EXPORTS
         assert f"lib.{name}.restype" in gen.block() and f"lib.{name}.restype" in stub
-    res, args = _lib._SIGS["m3ae_attn_probs"]
-    assert args[0]._type_ is _lib.AttnDesc and len(args) == 6
-    res, args = _lib._SIGS["m3ae_xattn_probs_export"]
-    assert args[0]._type_ is _lib.XattnDesc and len(args) == 7
+    # the binding names the descriptor each call reads, so that the stub prints C.POINTER(AttnDesc) / C.POINTER(XattnDesc)
+    assert _lib._SIGS["m3ae_attn_probs"][1][0]._type_ is _lib.AttnDesc
+    assert _lib._SIGS["m3ae_xattn_probs_export"][1][0]._type_ is _lib.XattnDesc
 
 
 def test_infer_accepts_output_attentions():

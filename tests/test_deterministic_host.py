@@ -3,85 +3,33 @@ ABI number and descriptor layouts unchanged), the config key, the mode switch, a
 split-K wgrad (which touches no device)."""
 import ctypes as C
 import os
-import re
 import sys
 
 import pytest
 
+import abi_header
 from m3ae_amd import _lib, config, ops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "m3ae_hip.h")).read()
-
-DET_ENTRIES = ("m3ae_gemm_det_workspace_bytes", "m3ae_gemm_det", "m3ae_det_workspace_bytes", "m3ae_colsum_det",
-               "m3ae_layernorm_bwd_det", "m3ae_layernorm_bwd_drop_det", "m3ae_roberta_embed_bwd_det", "m3ae_bce_logits_det",
-               "m3ae_xent_det", "m3ae_mim_loss_fwd_det")
-# sizeof(m3ae_gemm_desc), sizeof(m3ae_attn_desc), sizeof(m3ae_xattn_desc) of ABI 4 before this mode existed
-PARENT_DESC_SIZES = (272, 280, 456)
-
-
-def _header_prototype(name):
-    m = re.search(r"^(int64_t|int)\s+" + name + r"\s*\(([^;]*)\)\s*;", HEADER, flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/m3ae_hip.h"
-    return m.group(1), [a.strip() for a in m.group(2).split(",")]
-
-
-def _header_struct(name):
-    """ctypes mirror of `typedef struct { ... } name;` built from the header text alone."""
-    end = re.search(r"\}\s*" + name + r"\s*;", HEADER).start()
-    start = HEADER.rfind("typedef struct {", 0, end) + len("typedef struct {")
-    body = re.sub(r"/\*.*?\*/", "", HEADER[start:end], flags=re.S)
-    scalar = {"int64_t": C.c_int64, "int32_t": C.c_int32, "uint64_t": C.c_uint64, "float": C.c_float}
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        m = re.match(r"^(const\s+)?(void|float|int32_t|int64_t|uint64_t)\s*(.*)$", decl, flags=re.S)
-        base = m.group(2)
-        for part in m.group(3).split(","):
-            part = part.strip()
-            fields.append((part.replace("*", "").strip(), C.c_void_p if "*" in part else scalar[base]))
-    return type(name, (C.Structure,), {"_fields_": fields})
-
-
-def test_abi_number_and_descriptor_layouts_are_the_parents():
-    assert re.search(r"#define M3AE_ABI_VERSION (\d+)", HEADER).group(1) == "4"
-    assert _lib.ABI_VERSION == 4 and _lib.lib().m3ae_abi_version() == 4
-    sizes = (C.c_int64 * 3)()
-    _lib.lib().m3ae_desc_sizes(sizes)
-    from_header = tuple(C.sizeof(_header_struct(n)) for n in ("m3ae_gemm_desc", "m3ae_attn_desc", "m3ae_xattn_desc"))
-    assert tuple(sizes) == PARENT_DESC_SIZES == from_header
-    assert (C.sizeof(_lib.GemmDesc), C.sizeof(_lib.AttnDesc), C.sizeof(_lib.XattnDesc)) == PARENT_DESC_SIZES
 
 
 def test_header_binding_and_integration_stub_agree_on_the_new_entry_points():
+    """Signatures, constant values, the ABI number and the descriptor layouts: tests/test_host_logic.py, for the whole ABI."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import gen_integration_stub as gen
-    assert re.search(r"M3AE_GEMM_DETERMINISTIC\s*=\s*(\d+)", HEADER).group(1) == "4" and _lib.GEMM_DETERMINISTIC == 4
+    header = abi_header.constants()
+    assert header["M3AE_GEMM_DETERMINISTIC"] == _lib.GEMM_DETERMINISTIC == 4
     assert _lib.GEMM_DETERMINISTIC & (_lib.GEMM_NO_PERSISTENT | _lib.GEMM_F32_X3) == 0
     assert _lib.GEMM_DETERMINISTIC & (0xF << 8 | 0xF << 12 | 0xF << 16 | 0x3 << 20) == 0   # clear of the selector fields
-    enum = re.search(r"enum \{ (M3AE_DET_COLSUM[^}]*)\}", HEADER).group(1)
-    values = {k.strip(): int(v) for k, v in (kv.split("=") for kv in enum.split(","))}
-    assert values == {"M3AE_DET_COLSUM": _lib.DET_COLSUM, "M3AE_DET_EMBED_BWD": _lib.DET_EMBED_BWD, "M3AE_DET_BCE": _lib.DET_BCE,
-                      "M3AE_DET_XENT": _lib.DET_XENT, "M3AE_DET_MIM": _lib.DET_MIM}
+    assert {k: v for k, v in header.items() if k.startswith("M3AE_DET_")} == {
+        "M3AE_DET_COLSUM": _lib.DET_COLSUM, "M3AE_DET_EMBED_BWD": _lib.DET_EMBED_BWD, "M3AE_DET_BCE": _lib.DET_BCE,
+        "M3AE_DET_XENT": _lib.DET_XENT, "M3AE_DET_MIM": _lib.DET_MIM}
     text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     stub = text[text.index(gen.BEGIN):text.index(gen.END)]
     assert f"GEMM_DETERMINISTIC = {_lib.GEMM_DETERMINISTIC}" in stub
-    lib = _lib.lib()
-    for name in DET_ENTRIES:
-        res, args = _header_prototype(name)
-        bres, bargs = _lib._SIGS[name]
-        assert bres is (C.c_int64 if res == "int64_t" else C.c_int), name
-        assert len(args) == len(bargs), (name, args, bargs)
-        for a, b in zip(args, bargs):   # pointer for pointer, width for width
-            if "*" in a:
-                assert b is C.c_void_p or hasattr(b, "_type_") and not isinstance(b._type_, str), (name, a, b)
-            else:
-                want = {"int64_t": C.c_int64, "int": C.c_int, "float": C.c_float, "uint64_t": C.c_uint64}[a.split()[0]]
-                assert b is want, (name, a, b)
-        assert hasattr(lib, name)
-        assert f"lib.{name}.restype" in stub, f"{name} is missing from the INTEGRATION.md stub"
+    # the stub's section of the mode lists every ordered form the header declares (the mixed LayerNorm's sits with its family)
+    declared = {n for n in abi_header.prototypes() if n.endswith("_det") or "_det_" in n}
+    assert declared == set(gen.DET_ENTRIES) | {"m3ae_layernorm_bwd_mixed_det"} and len(gen.DET_ENTRIES) == 10
 
 
 def test_config_key_and_mode_switch():

@@ -4,13 +4,13 @@ post-processing on scripted tokens.  The GPU tests (tests/test_gpu_greedy.py) th
 the host-side surface of the feature: the declared symbols, the config key, the argument checks that need no GPU."""
 import inspect
 import os
-import re
 import sys
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 import greedy_model as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -149,23 +149,9 @@ def test_header_binding_and_stub_agree_on_the_greedy_symbols():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import gen_integration_stub as gen
     names = {"m3ae_greedy_workspace_bytes", "m3ae_greedy_argmax", "m3ae_greedy_step"}
-    hdr = open(os.path.join(ROOT, "include", "m3ae_hip.h")).read()
-    assert {n for n in re.findall(r"\b(m3ae_greedy_[a-z0-9_]+)\s*\(", hdr)} == names
+    assert {n for n in abi_header.prototypes() if n.startswith("m3ae_greedy_")} == names
     assert {n for n in _lib.EXPORTS if n.startswith("m3ae_greedy_")} == names == set(gen.GREEDY_ENTRIES)
-    # the header's parameter lists and the binding's argument lists have the same lengths and pointer / integer kinds
-    for name in names:
-        decl = re.search(r"^(?:int|int64_t) " + name + r"\(([^;]*)\);", hdr, flags=re.M | re.S).group(1)
-        params = [p.strip() for p in decl.replace("\n", " ").split(",")]
-        res, args = _lib._SIGS[name]
-        assert len(params) == len(args), name
-        for p, a in zip(params, args):
-            assert ("*" in p) == (a is _lib.vp), (name, p)
-    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    committed = text[text.index(gen.BEGIN):text.index(gen.END)]
-    for name in names:
-        assert f"lib.{name}.restype" in committed and f"lib.{name}.restype" in gen.block()
-    assert _lib.ABI_VERSION == 4 == int(re.search(r"#define M3AE_ABI_VERSION (\d+)", hdr).group(1))
-    assert _lib.lib().m3ae_abi_version() == 4
+    # (parameter lists against argument lists, and the stub's sections in INTEGRATION.md: tests/test_host_logic.py, for the whole ABI)
     # sizing needs no GPU: 8 bytes per (row, chunk); 0 for a shape the launch would reject
     L = _lib.lib()
     assert L.m3ae_greedy_workspace_bytes(5, 30522, 0) == 5 * 15 * 8

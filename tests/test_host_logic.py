@@ -3,12 +3,12 @@ C-ABI library loads and exports every symbol include/m3ae_hip.h declares (no com
 product path refuses to run on the CPU instead of silently falling back."""
 import os
 import sys
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 from m3ae_amd import _lib, config, ops
 from m3ae_amd.modules import M3AETransformerSS, state_dict_spec
 from m3ae_amd.param_store import param_group_of
@@ -53,30 +53,98 @@ def test_param_groups_match_reference_fixture():
     assert counts == [151, 192, 3, 3, 124, 196]  # SURVEY Appendix A "Observed split"
 
 
+ABI_4 = 4
+ABI_4_DESC_SIZES = (272, 280, 456)   # sizeof(m3ae_gemm_desc), sizeof(m3ae_attn_desc), sizeof(m3ae_xattn_desc): additive changes keep them
+DESCRIPTORS = dict(zip(abi_header.DESCRIPTORS, (_lib.GemmDesc, _lib.AttnDesc, _lib.XattnDesc)))
+# entry points INTEGRATION.md binds in its prose and examples, not in the generated stub.  New entry points go into the stub
+# (tools/gen_integration_stub.py: SECTIONS), not here.
+BOUND_IN_PROSE = frozenset("""
+    m3ae_abi_version m3ae_desc_sizes m3ae_last_gemm_path m3ae_gemm m3ae_attn_workspace_bytes m3ae_attn_fwd m3ae_attn_bwd
+    m3ae_xattn_supported m3ae_xattn_bwd_supported m3ae_xattn_probs_ld m3ae_xattn_fwd m3ae_xattn_bwd m3ae_layernorm_fwd
+    m3ae_layernorm_bwd_blocks m3ae_layernorm_bwd m3ae_layernorm_bwd_drop m3ae_dropout m3ae_colsum m3ae_roberta_embed_fwd
+    m3ae_roberta_embed_bwd m3ae_patchify m3ae_image_normalize_u8 m3ae_vit_tokens_fwd m3ae_vit_tokens_bwd m3ae_bce_logits m3ae_xent
+    m3ae_adamw m3ae_cast_transpose m3ae_cast_transpose_batched m3ae_transpose_bf16_batched m3ae_cast m3ae_zero m3ae_add m3ae_act_fwd
+    m3ae_act_bwd m3ae_gather_rows m3ae_scatter_add_rows m3ae_mask_ranks m3ae_mim_targets m3ae_mim_loss_fwd m3ae_mim_loss_bwd
+    m3ae_selftest m3ae_beam_topk_workspace_bytes m3ae_beam_topk m3ae_beam_step m3ae_beam_finalize""".split())
+
+
+def _gen():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import gen_integration_stub as gen
+    return gen
+
+
 def test_library_exports_every_declared_symbol():
-    hdr = open(os.path.join(ROOT, "include", "m3ae_hip.h")).read()
-    declared = set(re.findall(r"\b(m3ae_[a-z0-9_]+)\s*\(", hdr))
-    declared -= {"m3ae_gemm_desc", "m3ae_attn_desc"}
+    declared = set(abi_header.prototypes())
     assert declared == set(_lib.EXPORTS), declared ^ set(_lib.EXPORTS)
     lib = _lib.lib()  # raises if the .so is missing or a symbol is absent; also checks ABI version and descriptor sizes
-    assert lib.m3ae_abi_version() == _lib.ABI_VERSION == int(re.search(r"#define M3AE_ABI_VERSION (\d+)", hdr).group(1))
+    for name in declared:
+        assert hasattr(lib, name), name
+
+
+def test_every_binding_signature_is_the_headers():
+    """A wrong ctypes entry is no error at the call: it is a float where the library reads a double, or 32 bits where it reads 64.
+    For every declared function: return type, argument count, every scalar by its exact ctypes type, every pointer as c_void_p
+    or a POINTER to the header's pointee (a descriptor: to the Structure with the header's field list)."""
+    wrong = []
+    for name, (res_text, params) in abi_header.prototypes().items():
+        res, args = abi_header.ctypes_signature(name)
+        if name not in _lib._SIGS:
+            wrong.append(f"{name}: declared in include/m3ae_hip.h, no entry in _lib._SIGS")
+            continue
+        bres, bargs = _lib._SIGS[name]
+        if bres is not res:
+            wrong.append(f"{name}: returns `{res_text}`, bound as {bres}")
+        if len(bargs) != len(args):
+            wrong.append(f"{name}: {len(args)} parameters declared, {len(bargs)} bound")
+        wrong += [f"{name}: parameter {i} `{text}` is bound as {bound}"
+                  for i, (want, bound, text) in enumerate(zip(args, bargs, params)) if not abi_header.binding_agrees(want, bound)]
+    assert not wrong, "\n".join(wrong)
 
 
 def test_descriptor_layouts_match_header_binding_and_integration_stub():
-    """A binding with a shorter struct than the library's is read past its end: the library reports its sizeof()s
-    (m3ae_desc_sizes), the header's field lists equal the ctypes field lists name by name, and the stub printed in
-    INTEGRATION.md is the generator's output for the binding the tests exercise."""
-    import ctypes as C
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import gen_integration_stub as gen
-    sizes = (C.c_int64 * 3)()
-    _lib.lib().m3ae_desc_sizes(sizes)
-    assert tuple(sizes) == (C.sizeof(_lib.GemmDesc), C.sizeof(_lib.AttnDesc), C.sizeof(_lib.XattnDesc))
-    for cls, name in ((_lib.GemmDesc, "m3ae_gemm_desc"), (_lib.AttnDesc, "m3ae_attn_desc"), (_lib.XattnDesc, "m3ae_xattn_desc")):
-        assert gen.header_fields(name) == [f for f, _ in cls._fields_], name
+    """A binding with a shorter struct than the library's is read past its end: the header's field lists equal the
+    ctypes field lists, names and types in order, and the stub printed in INTEGRATION.md is the generator's output for the
+    binding the tests exercise."""
+    gen = _gen()
+    for name, cls in DESCRIPTORS.items():
+        assert abi_header.struct_fields(name) == cls._fields_, \
+            (name, [(h, b) for h, b in zip(abi_header.struct_fields(name), cls._fields_) if h != b])
     text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
     committed = text[text.index(gen.BEGIN) + len(gen.BEGIN):text.index(gen.END)].strip()
     assert committed == gen.block().strip(), "run: python tools/gen_integration_stub.py --write"
+
+
+def test_abi_number_and_descriptor_sizes_are_those_of_abi_4():
+    """Additive changes keep both: header, binding and library (m3ae_abi_version, m3ae_desc_sizes) all say so."""
+    import ctypes as C
+    assert abi_header.abi_version() == _lib.ABI_VERSION == _lib.lib().m3ae_abi_version() == ABI_4
+    sizes = (C.c_int64 * 3)()
+    _lib.lib().m3ae_desc_sizes(sizes)
+    assert tuple(sizes) == ABI_4_DESC_SIZES
+    assert tuple(abi_header.struct_sizeof(n) for n in DESCRIPTORS) == ABI_4_DESC_SIZES
+    assert tuple(C.sizeof(cls) for cls in DESCRIPTORS.values()) == ABI_4_DESC_SIZES
+
+
+def test_binding_constants_are_the_headers():
+    header = abi_header.constants()
+    for name, value in header.items():          # every header constant the binding names
+        if hasattr(_lib, name[len("M3AE_"):]):
+            assert getattr(_lib, name[len("M3AE_"):]) == value, name
+    mirrors = {k: v for k, v in vars(_lib).items() if k.isupper() and type(v) is int}
+    assert {"F32", "ERR_WORKSPACE", "CLIP_RECORD_WORDS", "VQA_MAX_K", "SEQ_MAX_SKIP"} <= set(mirrors)
+    for name in mirrors:                        # every integer constant of the binding has a header name
+        assert "M3AE_" + name in header, f"_lib.{name} has no M3AE_{name} in include/m3ae_hip.h"
+
+
+def test_every_export_is_in_the_integration_stub_or_bound_in_prose():
+    gen = _gen()
+    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    stub = text[text.index(gen.BEGIN):text.index(gen.END)]
+    in_stub = {name for name in _lib.EXPORTS if f"lib.{name}.restype" in stub}
+    assert in_stub == {name for s in gen.SECTIONS.values() for name in s.entries}
+    assert not in_stub & BOUND_IN_PROSE, in_stub & BOUND_IN_PROSE
+    assert in_stub | BOUND_IN_PROSE == set(_lib.EXPORTS), set(_lib.EXPORTS) ^ (in_stub | BOUND_IN_PROSE)
 
 
 def test_no_cpu_fallback():

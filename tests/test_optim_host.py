@@ -3,19 +3,15 @@ the CPU, the config key and its validator, the C ABI additions (header, ctypes b
 agree; ABI number unchanged), the argument checks that come before any launch, and the host-side dispatch of ParamStore, the
 Flat* optimizers, FlatGradReducer and GraphedStep (no library call is made)."""
 import ctypes as C
-import os
-import re
-import sys
 
 import numpy as np
 import pytest
 import torch
 
+import abi_header
 from m3ae_amd import _lib, config
 import optim_model as OM
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "m3ae_hip.h")).read()
 OPTIM_ENTRIES = ("m3ae_adam", "m3ae_adam_clip", "m3ae_sgd", "m3ae_sgd_clip")
 RTOL, ATOL = 1e-5, 1e-6      # the bound tests/test_gpu_ops.py::test_adamw_matches_hf_semantics holds m3ae_adamw to
 N, STEPS, GRAD_SCALE = 4096, 5, 0.5
@@ -105,48 +101,24 @@ def test_config_key_default_and_validator():
 # ---------------------------------------------------------------------------------------------------------------------------------
 # 3. C ABI
 # ---------------------------------------------------------------------------------------------------------------------------------
-def _header_prototype(name):
-    m = re.search(r"^(int64_t|int)\s+" + name + r"\s*\(([^;]*)\)\s*;", HEADER, flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/m3ae_hip.h"
-    return m.group(1), [" ".join(a.split()) for a in m.group(2).split(",")]
-
-
 def test_header_binding_library_and_stub_agree_and_the_abi_is_still_4():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import gen_integration_stub as gen
-    assert re.search(r"#define M3AE_ABI_VERSION (\d+)", HEADER).group(1) == "4" and _lib.ABI_VERSION == 4
-    lib = _lib.lib()
-    assert lib.m3ae_abi_version() == 4
-    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    stub = text[text.index(gen.BEGIN):text.index(gen.END)]
-    for name in OPTIM_ENTRIES:
-        res, args = _header_prototype(name)
-        bres, bargs = _lib._SIGS[name]
-        assert name in _lib.EXPORTS and hasattr(lib, name)
-        assert res == "int" and bres is C.c_int
-        assert len(args) == len(bargs), (name, args, bargs)
-        for a, b in zip(args, bargs):   # pointer for pointer, width for width
-            if "*" in a:
-                assert b is C.c_void_p, (name, a, b)
-            else:
-                assert b is {"int64_t": C.c_int64, "int": C.c_int, "float": C.c_float, "double": C.c_double}[a.split()[0]], (name, a, b)
-        assert f"lib.{name}.restype" in stub, f"{name} is missing from the INTEGRATION.md stub"
+    """The relations between the optimizer entry points, in the header's text and in the binding.  (Binding against header type
+    by type, the stub, the ABI number and the descriptor sizes: tests/test_host_logic.py, for the whole ABI.)"""
+    protos = abi_header.prototypes()
+    assert all(protos[name][0] == "int" for name in OPTIM_ENTRIES)
     # each _clip form is its plain form plus the record in front of the stream; neither rule takes hyper_dev
     for plain, nargs in (("m3ae_adam", 14), ("m3ae_sgd", 10)):
         a, c = _lib._SIGS[plain][1], _lib._SIGS[plain + "_clip"][1]
         assert len(a) == nargs and c == a[:-1] + [C.c_void_p, a[-1]]
-        pa, pc = _header_prototype(plain)[1], _header_prototype(plain + "_clip")[1]
+        pa, pc = protos[plain][1], protos[plain + "_clip"][1]
         assert pc == pa[:-1] + ["const float* clip_dev", pa[-1]] and pa[-1] == "void* stream"
         assert not any("hyper_dev" in x for x in pc)
     # m3ae_adam is m3ae_adamw without hyper_dev and with the betas in double; m3ae_adamw keeps its signature
     w = _lib._SIGS["m3ae_adamw"][1]
     assert len(w) == 15 and [C.c_float if x is C.c_double else x for x in _lib._SIGS["m3ae_adam"][1]] == w[:-2] + [w[-1]]
-    assert [x.replace("double", "float") for x in _header_prototype("m3ae_adam")[1]] == \
-        [x for x in _header_prototype("m3ae_adamw")[1] if "hyper_dev" not in x]
-    assert _header_prototype("m3ae_adam")[1][7:9] == ["double beta1", "double beta2"]
-    sizes = (C.c_int64 * 3)()
-    lib.m3ae_desc_sizes(sizes)
-    assert tuple(sizes) == (272, 280, 456)      # no descriptor changed
+    assert len(protos["m3ae_adamw"][1]) == 15
+    assert [x.replace("double", "float") for x in protos["m3ae_adam"][1]] == [x for x in protos["m3ae_adamw"][1] if "hyper_dev" not in x]
+    assert protos["m3ae_adam"][1][7:9] == ["double beta1", "double beta2"]
 
 
 def test_entry_points_check_their_arguments_before_any_launch():

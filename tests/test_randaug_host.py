@@ -4,13 +4,13 @@ augment plan of a pack and the declaration of the entry points."""
 import io
 import os
 import random
-import re
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_header  # noqa: E402
 from randaug_cases import HOST_SIZES, OP_SIGNS, degenerate_images, image  # noqa: E402
 
 from m3ae_amd import _lib, data, resample  # noqa: E402
@@ -287,12 +287,12 @@ def test_pack_carries_the_augment_plan():
 
 
 def test_entry_points_are_declared_and_bound():
-    hdr = open(os.path.join(ROOT, "include", "m3ae_hip.h")).read()
-    assert re.search(r"\bint\s+m3ae_image_randaug_u8\s*\(\s*uint8_t\*\s*src,\s*uint8_t\*\s*scratch,\s*int64_t buf_bytes,\s*const int64_t\*\s*plan,"
-                     r"\s*int64_t B,\s*void\*\s*workspace,\s*int64_t workspace_bytes,\s*int flags,\s*void\*\s*stream\)", hdr)
-    assert re.search(r"\bint64_t\s+m3ae_image_randaug_workspace_bytes\s*\(\s*int64_t B\)", hdr)
-    for name, nargs in (("m3ae_image_randaug_u8", 9), ("m3ae_image_randaug_workspace_bytes", 1)):
-        assert name in _lib.EXPORTS and len(_lib._SIGS[name][1]) == nargs
+    protos = abi_header.prototypes()            # bound as declared: tests/test_host_logic.py, for the whole ABI
+    assert protos["m3ae_image_randaug_u8"] == ("int", [
+        "uint8_t* src", "uint8_t* scratch", "int64_t buf_bytes", "const int64_t* plan", "int64_t B", "void* workspace",
+        "int64_t workspace_bytes", "int flags", "void* stream"])
+    assert protos["m3ae_image_randaug_workspace_bytes"] == ("int64_t", ["int64_t B"])
+    for name in ("m3ae_image_randaug_u8", "m3ae_image_randaug_workspace_bytes"):
         assert f"lib.{name}.argtypes" in open(os.path.join(ROOT, "INTEGRATION.md")).read()
     src = open(os.path.join(ROOT, "mm-vqa-healthcare_amd", "csrc", "randaug.hip")).read()
     assert f"AUG_FIELDS = {ra.AUG_FIELDS}, AUG_STAGE0 = {ra.AUG_STAGE0}, AUG_STAGE_FIELDS = {ra.AUG_STAGE_FIELDS}" in src

@@ -1,7 +1,6 @@
 """Device image transform, host half (m3ae_amd/resample.py): the tables and the numpy model of the two kernels against
 Pillow itself, the folded crop, the 24-bit coefficient bound, eligibility, and the declarations of the new entry points."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -123,11 +122,7 @@ def test_eligibility():
 
 
 def test_entry_points_are_declared_and_bound_and_the_default_is_host():
-    hdr = open(os.path.join(ROOT, "include", "m3ae_hip.h")).read()
-    for name in ("m3ae_image_resample_u8", "m3ae_image_resample_workspace_bytes"):
-        assert re.search(r"\b%s\s*\(" % name, hdr), name
-        assert name in _lib.EXPORTS
-    assert re.search(r"#define\s+M3AE_ABI_VERSION\s+4\b", hdr) and _lib.ABI_VERSION == 4
+    assert {"m3ae_image_resample_u8", "m3ae_image_resample_workspace_bytes"} <= set(_lib.EXPORTS)   # == declared: test_host_logic.py
     assert os.path.exists(os.path.join(ROOT, "mm-vqa-healthcare_amd", "csrc", "image.hip"))
     assert compose()["image_transform"] == "host"
     assert compose("task_finetune_vqa_vqa_rad", image_transform="device")["image_transform"] == "device"

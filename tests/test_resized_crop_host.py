@@ -2,13 +2,13 @@
 numpy model of the two kernels on a box against Pillow itself, the host transform, the plan of a pack made with boxes, and the
 declaration of the table kernel's entry point."""
 import os
-import re
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_header  # noqa: E402
 from resample_cases import source  # noqa: E402
 
 from m3ae_amd import _lib, resample  # noqa: E402
@@ -277,11 +277,8 @@ def test_datasets_key_their_boxes_per_loaded_image_or_per_image(tmp_path):
 
 
 def test_entry_point_is_declared_and_bound():
-    hdr = open(os.path.join(ROOT, "include", "m3ae_hip.h")).read()
-    assert re.search(r"\bint\s+m3ae_image_resample_tables\s*\(\s*const int64_t\*\s*plan,\s*int64_t B,\s*int64_t size,\s*int32_t\*\s*tab,"
-                     r"\s*int64_t tab_ints,\s*void\*\s*stream\)", hdr)
-    assert "m3ae_image_resample_tables" in _lib.EXPORTS
-    assert len(_lib._SIGS["m3ae_image_resample_tables"][1]) == 6
-    assert re.search(r"#define\s+M3AE_ABI_VERSION\s+4\b", hdr) and _lib.ABI_VERSION == 4
+    # bound as declared, and the ABI number: tests/test_host_logic.py, for the whole ABI
+    assert abi_header.prototypes()["m3ae_image_resample_tables"] == ("int", [
+        "const int64_t* plan", "int64_t B", "int64_t size", "int32_t* tab", "int64_t tab_ints", "void* stream"])
     assert resample.PLAN_BUILD == 13 and resample.PLAN_FIELDS == 16
     assert "lib.m3ae_image_resample_tables.argtypes" in open(os.path.join(ROOT, "INTEGRATION.md")).read()

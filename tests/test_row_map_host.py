@@ -1,50 +1,27 @@
-"""Dropout row map, the part that needs no GPU: the additive `*_rows` entry points are declared in the header, bound with the same
-argument widths and listed in the INTEGRATION.md stub; the ABI number stays 4; and a bad map (row_step < 1, negative row_base, a
-mapped index past 2^63 - 1) is rejected with M3AE_ERR_ARG before any HIP call (without a GPU a launch attempt would come back as
+"""Dropout row map, the part that needs no GPU: the additive `*_rows` entry points are their plain entry points plus the map, in the
+header and in the binding (tests/test_host_logic.py holds binding, header and stub together for the whole ABI); and a bad map
+(row_step < 1, negative row_base, a mapped index past 2^63 - 1) is rejected with M3AE_ERR_ARG before any HIP call (without a GPU a launch attempt would come back as
 a positive hipError_t instead; with one, nothing is launched on the placeholder pointers)."""
 import ctypes as C
-import os
-import re
-import sys
 
+import abi_header
 from m3ae_amd import _lib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = open(os.path.join(ROOT, "include", "m3ae_hip.h")).read()
 ROWS_ENTRIES = ("m3ae_gemm_rows", "m3ae_attn_fwd_rows", "m3ae_attn_bwd_rows", "m3ae_layernorm_bwd_drop_rows", "m3ae_dropout_rows")
-ERR_ARG = -1
+ERR_ARG = _lib.ERR_ARG
 FAKE = 0x1000   # a non-null "device pointer": the argument checks compare pointers with NULL and never dereference them
 
 
-def _header_prototype(name):
-    m = re.search(r"^(int64_t|int)\s+" + name + r"\s*\(([^;]*)\)\s*;", HEADER, flags=re.M | re.S)
-    assert m, f"{name} is not declared in include/m3ae_hip.h"
-    return m.group(1), [a.strip() for a in m.group(2).split(",")]
-
-
 def test_header_binding_and_stub_agree_on_the_rows_entry_points():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import gen_integration_stub as gen
-    assert re.search(r"#define M3AE_ABI_VERSION (\d+)", HEADER).group(1) == "4" and _lib.ABI_VERSION == 4
-    text = open(os.path.join(ROOT, "INTEGRATION.md")).read()
-    stub = text[text.index(gen.BEGIN):text.index(gen.END)]
-    lib = _lib.lib()
-    widths = {"int64_t": C.c_int64, "uint64_t": C.c_uint64, "float": C.c_float, "int": C.c_int}
+    """A `_rows` entry point is its plain entry point plus `int64_t row_base, int64_t row_step` right before `void* stream`, in the
+    header and in the binding.  (Binding against header type by type, and the stub: tests/test_host_logic.py, for the whole ABI.)"""
+    protos = abi_header.prototypes()
     for name in ROWS_ENTRIES:
-        res, args = _header_prototype(name)
-        bres, bargs = _lib._SIGS[name]
-        assert res == "int" and bres is C.c_int, name
-        assert len(args) == len(bargs), (name, args, bargs)
-        for a, b in zip(args, bargs):
-            if "*" in a:
-                assert b is C.c_void_p or hasattr(b, "_type_"), (name, a, b)
-            else:
-                assert b is widths[a.split()[-2]], (name, a, b)
-        # (row_base, row_step) sit right before the stream, as the header says
-        assert [a.split()[-1] for a in args[-3:]] == ["row_base", "row_step", "stream"], (name, args)
-        assert hasattr(lib, name) and f"lib.{name}.restype" in stub, name
         base = name[:-len("_rows")]
-        assert base in _lib._SIGS and _lib._SIGS[base][1] == bargs[:-3] + bargs[-1:], name   # the plain entry point + the map
+        (res, args), (bres, bargs) = protos[name], _lib._SIGS[name]
+        assert res == "int" and args[-3:] == ["int64_t row_base", "int64_t row_step", "void* stream"], (name, args)
+        assert (res, args[:-3] + args[-1:]) == protos[base], name
+        assert _lib._SIGS[base] == (bres, bargs[:-3] + bargs[-1:]), name
 
 
 def _gemm_desc(M=8, N=64, K=64, p=0.5):

@@ -1,9 +1,9 @@
 """Regenerates the ctypes descriptor stubs of INTEGRATION.md from m3ae_amd/_lib.py (the binding the tests exercise), so the
 documented struct layouts cannot drift from the library:   python tools/gen_integration_stub.py [--write]
-tests/test_host_logic.py::test_integration_stub_is_generated_from_the_binding compares the committed block with this output."""
+tests/test_host_logic.py::test_descriptor_layouts_match_header_binding_and_integration_stub compares the committed block with this output."""
+import collections
 import ctypes as C
 import os
-import re
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,21 +27,64 @@ def struct_stub(cls, c_name):
            f"    _fields_ = [\n{body}]\n"
 
 
-MAP_ENTRIES = ("m3ae_attn_probs", "m3ae_xattn_probs_export")
-DET_ENTRIES = ("m3ae_gemm_det_workspace_bytes", "m3ae_gemm_det", "m3ae_det_workspace_bytes", "m3ae_colsum_det",
-               "m3ae_layernorm_bwd_det", "m3ae_layernorm_bwd_drop_det", "m3ae_roberta_embed_bwd_det", "m3ae_bce_logits_det",
-               "m3ae_xent_det", "m3ae_mim_loss_fwd_det")
-IMAGE_ENTRIES = ("m3ae_image_resample_workspace_bytes", "m3ae_image_resample_u8", "m3ae_image_resample_tables")
-RANDAUG_ENTRIES = ("m3ae_image_randaug_workspace_bytes", "m3ae_image_randaug_u8")
-SAMPLES_ENTRIES = ("m3ae_expand_samples", "m3ae_segment_sum_rows")
-MIXED_LN_ENTRIES = ("m3ae_layernorm_fwd_mixed", "m3ae_layernorm_bwd_mixed", "m3ae_layernorm_bwd_mixed_det")
-TILED_ENTRIES = ("m3ae_tile_bf16_batched",)
-CLIP_ENTRIES = ("m3ae_sumsq_workspace_bytes", "m3ae_sumsq_segments", "m3ae_clip_finalize", "m3ae_adamw_clip")
-OPTIM_ENTRIES = ("m3ae_adam", "m3ae_adam_clip", "m3ae_sgd", "m3ae_sgd_clip")
-GREEDY_ENTRIES = ("m3ae_greedy_workspace_bytes", "m3ae_greedy_argmax", "m3ae_greedy_step")
-SUMMARY_ENTRIES = ("m3ae_attn_colmean_workspace_bytes", "m3ae_attn_colmean", "m3ae_xattn_probs_colmean", "m3ae_heatmap_upsample")
-VQA_EVAL_ENTRIES = ("m3ae_vqa_eval_workspace_bytes", "m3ae_vqa_eval", "m3ae_seq_match")
-ROWS_ENTRIES = ("m3ae_gemm_rows", "m3ae_attn_fwd_rows", "m3ae_attn_bwd_rows", "m3ae_layernorm_bwd_drop_rows", "m3ae_dropout_rows")
+# The block after the descriptor classes, in order.  A section is a heading comment, constant lines -- (names of m3ae_amd/_lib.py,
+# the text after their values) -- and the entry points whose restype / argtypes lines follow.
+Section = collections.namedtuple("Section", "heading consts entries")
+SECTIONS = {
+    "LAUNCH_FLAGS": Section(
+        "# launch_flags bits (fp32x3 mode, ABI 4: additive)",
+        (("GEMM_NO_PERSISTENT, GEMM_F32_X3", "     # m3ae_gemm_desc.launch_flags"),
+         ("ATTN_LEGACY_KERNELS, ATTN_F32_X3", "    # m3ae_attn_desc.launch_flags")),
+        ()),
+    "MAP_ENTRIES": Section(
+        "# attention maps (ABI 4): fp32 [B, H, Lq, Lk] out of an m3ae_attn_fwd / m3ae_xattn_fwd call", (),
+        ("m3ae_attn_probs", "m3ae_xattn_probs_export")),
+    "DET_ENTRIES": Section(
+        "# deterministic mode (ABI 4, additive): ordered reductions, caller-owned workspaces",
+        (("GEMM_DETERMINISTIC", "     # m3ae_gemm_desc.launch_flags, accepted by m3ae_gemm_det only"),
+         ("DET_COLSUM, DET_EMBED_BWD, DET_BCE, DET_XENT, DET_MIM", "     # m3ae_det_workspace_bytes(op, rows, cols)")),
+        ("m3ae_gemm_det_workspace_bytes", "m3ae_gemm_det", "m3ae_det_workspace_bytes", "m3ae_colsum_det", "m3ae_layernorm_bwd_det",
+         "m3ae_layernorm_bwd_drop_det", "m3ae_roberta_embed_bwd_det", "m3ae_bce_logits_det", "m3ae_xent_det", "m3ae_mim_loss_fwd_det")),
+    "IMAGE_ENTRIES": Section(
+        "# device image transform (ABI 4, additive): Pillow-exact bicubic resize + centre crop + normalize from the source bytes", (),
+        ("m3ae_image_resample_workspace_bytes", "m3ae_image_resample_u8", "m3ae_image_resample_tables")),
+    "RANDAUG_ENTRIES": Section(
+        "# RandAugment(2, 9) on the source bytes of the device image transform (ABI 4, additive): Pillow-exact, two stages", (),
+        ("m3ae_image_randaug_workspace_bytes", "m3ae_image_randaug_u8")),
+    "ROWS_ENTRIES": Section(
+        "# dropout row map (ABI 4, additive): mask row = row_base + row * row_step, (row_base, row_step) before the stream", (),
+        ("m3ae_gemm_rows", "m3ae_attn_fwd_rows", "m3ae_attn_bwd_rows", "m3ae_layernorm_bwd_drop_rows", "m3ae_dropout_rows")),
+    "SAMPLES_ENTRIES": Section(
+        "# de-duplicated image batches (ABI 4, additive): out[b] = in[src[b]] over whole rows, and the ordered per-image sum back", (),
+        ("m3ae_expand_samples", "m3ae_segment_sum_rows")),
+    "MIXED_LN_ENTRIES": Section(
+        "# fp32 residual stream of a bf16 model (ABI 4, additive): LayerNorm from fp32 rows to bf16 rows and its backward", (),
+        ("m3ae_layernorm_fwd_mixed", "m3ae_layernorm_bwd_mixed", "m3ae_layernorm_bwd_mixed_det")),
+    "TILED_ENTRIES": Section(
+        "# tiled weight operand of the NT GEMMs (ABI 4, additive): B = the tiled copy of W[N][K] (csrc/tiled_b.h), same results",
+        (("GEMM_B_TILED", "     # m3ae_gemm_desc.launch_flags; b_sk = 1, b_sn = K, B 16-byte aligned, K % 32 == 0"),),
+        ("m3ae_tile_bf16_batched",)),
+    "CLIP_ENTRIES": Section(
+        "# gradient clipping by global norm + non-finite step guard (ABI 4, additive): double sums of squares, device-side factor",
+        (("CLIP_NORM, CLIP_COEF, CLIP_SKIP, CLIP_STEPS, CLIP_CLIPPED_STEPS, CLIP_SKIPPED_STEPS, CLIP_RECORD_WORDS",
+          "     # 32-bit words of the record"),),
+        ("m3ae_sumsq_workspace_bytes", "m3ae_sumsq_segments", "m3ae_clip_finalize", "m3ae_adamw_clip")),
+    "OPTIM_ENTRIES": Section(
+        "# optim_type adam / sgd (ABI 4, additive): torch.optim.Adam and SGD with momentum over a flat segment; _clip = + the record", (),
+        ("m3ae_adam", "m3ae_adam_clip", "m3ae_sgd", "m3ae_sgd_clip")),
+    "GREEDY_ENTRIES": Section(
+        "# device-resident greedy search for the decoder head (ABI 4, additive): order keys per vocabulary chunk, then the step", (),
+        ("m3ae_greedy_workspace_bytes", "m3ae_greedy_argmax", "m3ae_greedy_step")),
+    "SUMMARY_ENTRIES": Section(
+        "# attention summaries (ABI 4, additive): fp32 [B, Lk] head-and-query mean of a map without the map; heatmap upsample", (),
+        ("m3ae_attn_colmean_workspace_bytes", "m3ae_attn_colmean", "m3ae_xattn_probs_colmean", "m3ae_heatmap_upsample")),
+    "VQA_EVAL_ENTRIES": Section(
+        "# device-side VQA evaluation (ABI 4, additive): prediction, top-k answers, the closed / open / overall record; token exact match",
+        (("ANS_CLOSED, ANS_OPEN, VQA_REC_DOUBLES",
+          "     # types values; double rec[10] = {n, sum_top1, sum_topk} x (all, closed, open), calls"),),
+        ("m3ae_vqa_eval_workspace_bytes", "m3ae_vqa_eval", "m3ae_seq_match")),
+}
+globals().update({key: s.entries for key, s in SECTIONS.items() if s.entries})   # MAP_ENTRIES, DET_ENTRIES, ...: views of the table
 
 
 def _ctype_name(t):
@@ -58,102 +101,15 @@ def block():
     out.append(struct_stub(_lib.GemmDesc, "m3ae_gemm_desc"))
     out.append(struct_stub(_lib.XattnDesc, "m3ae_xattn_desc"))
     out.append(struct_stub(_lib.AttnDesc, "m3ae_attn_desc"))
-    out.append("# launch_flags bits (fp32x3 mode, ABI 4: additive)")
-    out.append(f"GEMM_NO_PERSISTENT, GEMM_F32_X3 = {_lib.GEMM_NO_PERSISTENT}, {_lib.GEMM_F32_X3}     # m3ae_gemm_desc.launch_flags")
-    out.append(f"ATTN_LEGACY_KERNELS, ATTN_F32_X3 = {_lib.ATTN_LEGACY_KERNELS}, {_lib.ATTN_F32_X3}    # m3ae_attn_desc.launch_flags")
-    out.append("")
-    out.append("# attention maps (ABI 4): fp32 [B, H, Lq, Lk] out of an m3ae_attn_fwd / m3ae_xattn_fwd call")
-    for name in MAP_ENTRIES:
-        res, args = _lib._SIGS[name]
-        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
-    out.append("")
-    out.append("# deterministic mode (ABI 4, additive): ordered reductions, caller-owned workspaces")
-    out.append(f"GEMM_DETERMINISTIC = {_lib.GEMM_DETERMINISTIC}     # m3ae_gemm_desc.launch_flags, accepted by m3ae_gemm_det only")
-    out.append(f"DET_COLSUM, DET_EMBED_BWD, DET_BCE, DET_XENT, DET_MIM = {_lib.DET_COLSUM}, {_lib.DET_EMBED_BWD}, {_lib.DET_BCE}, "
-               f"{_lib.DET_XENT}, {_lib.DET_MIM}     # m3ae_det_workspace_bytes(op, rows, cols)")
-    for name in DET_ENTRIES:
-        res, args = _lib._SIGS[name]
-        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
-    out.append("")
-    out.append("# device image transform (ABI 4, additive): Pillow-exact bicubic resize + centre crop + normalize from the source bytes")
-    for name in IMAGE_ENTRIES:
-        res, args = _lib._SIGS[name]
-        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
-    out.append("")
-    out.append("# RandAugment(2, 9) on the source bytes of the device image transform (ABI 4, additive): Pillow-exact, two stages")
-    for name in RANDAUG_ENTRIES:
-        res, args = _lib._SIGS[name]
-        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
-    out.append("")
-    out.append("# dropout row map (ABI 4, additive): mask row = row_base + row * row_step, (row_base, row_step) before the stream")
-    for name in ROWS_ENTRIES:
-        res, args = _lib._SIGS[name]
-        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
-    out.append("")
-    out.append("# de-duplicated image batches (ABI 4, additive): out[b] = in[src[b]] over whole rows, and the ordered per-image sum back")
-    for name in SAMPLES_ENTRIES:
-        res, args = _lib._SIGS[name]
-        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
-    out.append("")
-    out.append("# fp32 residual stream of a bf16 model (ABI 4, additive): LayerNorm from fp32 rows to bf16 rows and its backward")
-    for name in MIXED_LN_ENTRIES:
-        res, args = _lib._SIGS[name]
-        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
-    out.append("")
-    out.append("# tiled weight operand of the NT GEMMs (ABI 4, additive): B = the tiled copy of W[N][K] (csrc/tiled_b.h), same results")
-    out.append(f"GEMM_B_TILED = {_lib.GEMM_B_TILED}     # m3ae_gemm_desc.launch_flags; b_sk = 1, b_sn = K, B 16-byte aligned, K % 32 == 0")
-    for name in TILED_ENTRIES:
-        res, args = _lib._SIGS[name]
-        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
-    out.append("")
-    out.append("# gradient clipping by global norm + non-finite step guard (ABI 4, additive): double sums of squares, device-side factor")
-    out.append(f"CLIP_NORM, CLIP_COEF, CLIP_SKIP, CLIP_STEPS, CLIP_CLIPPED_STEPS, CLIP_SKIPPED_STEPS, CLIP_RECORD_WORDS = {_lib.CLIP_NORM}, "
-               f"{_lib.CLIP_COEF}, {_lib.CLIP_SKIP}, {_lib.CLIP_STEPS}, {_lib.CLIP_CLIPPED_STEPS}, {_lib.CLIP_SKIPPED_STEPS}, "
-               f"{_lib.CLIP_RECORD_WORDS}     # 32-bit words of the record")
-    for name in CLIP_ENTRIES:
-        res, args = _lib._SIGS[name]
-        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
-    out.append("")
-    out.append("# optim_type adam / sgd (ABI 4, additive): torch.optim.Adam and SGD with momentum over a flat segment; _clip = + the record")
-    for name in OPTIM_ENTRIES:
-        res, args = _lib._SIGS[name]
-        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
-    out.append("")
-    out.append("# device-resident greedy search for the decoder head (ABI 4, additive): order keys per vocabulary chunk, then the step")
-    for name in GREEDY_ENTRIES:
-        res, args = _lib._SIGS[name]
-        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
-    out.append("")
-    out.append("# attention summaries (ABI 4, additive): fp32 [B, Lk] head-and-query mean of a map without the map; heatmap upsample")
-    for name in SUMMARY_ENTRIES:
-        res, args = _lib._SIGS[name]
-        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
-    out.append("")
-    out.append("# device-side VQA evaluation (ABI 4, additive): prediction, top-k answers, the closed / open / overall record; token exact match")
-    out.append(f"ANS_CLOSED, ANS_OPEN, VQA_REC_DOUBLES = {_lib.ANS_CLOSED}, {_lib.ANS_OPEN}, {_lib.VQA_REC_DOUBLES}     "
-               "# types values; double rec[10] = {n, sum_top1, sum_topk} x (all, closed, open), calls")
-    for name in VQA_EVAL_ENTRIES:
-        res, args = _lib._SIGS[name]
-        out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
+    for i, section in enumerate(SECTIONS.values()):
+        out += [""] * (i > 0) + [section.heading]
+        for names, tail in section.consts:
+            out.append(f"{names} = {', '.join(str(getattr(_lib, n)) for n in names.split(', '))}{tail}")
+        for name in section.entries:
+            res, args = _lib._SIGS[name]
+            out.append(f"lib.{name}.restype, lib.{name}.argtypes = {_ctype_name(res)}, [{', '.join(_ctype_name(a) for a in args)}]")
     out.append("```")
     return "\n".join(out)
-
-
-def header_fields(struct_name):
-    """Field names of `typedef struct { ... } struct_name;` in include/m3ae_hip.h, in order."""
-    hdr = open(os.path.join(ROOT, "include", "m3ae_hip.h")).read()
-    end = re.search(r"\}\s*" + struct_name + r"\s*;", hdr).start()
-    start = hdr.rfind("typedef struct {", 0, end) + len("typedef struct {")
-    body = re.sub(r"/\*.*?\*/", "", hdr[start:end], flags=re.S)
-    names = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        decl = re.sub(r"^(const\s+)?(void|float|int32_t|int64_t|uint64_t)\s*", "", decl)
-        for part in decl.split(","):
-            names.append(part.replace("*", "").strip())
-    return names
 
 
 if __name__ == "__main__":
