@@ -58,6 +58,8 @@ extern "C" {
  *    upsample of a patch grid; no descriptor changed. */
 /* 4 (additive): device-side VQA evaluation.  m3ae_vqa_eval (+ m3ae_vqa_eval_workspace_bytes) and m3ae_seq_match
  *    (csrc/vqa_eval.hip): prediction, top-k answers and the closed / open / overall score record; no descriptor changed. */
+/* 4 (additive): exponential moving average of the weights.  m3ae_ema_update and m3ae_ema_swap (csrc/misc.hip); no descriptor
+ *    changed. */
 #define M3AE_ABI_VERSION 4
 
 enum { M3AE_F32 = 0, M3AE_BF16 = 1 };
@@ -593,6 +595,22 @@ int m3ae_sgd(float* p, const float* g, float* buf, void* shadow_bf16, int64_t n,
              float grad_scale, void* stream);
 int m3ae_sgd_clip(float* p, const float* g, float* buf, void* shadow_bf16, int64_t n, float lr, float momentum, float wd,
                   float grad_scale, const float* clip_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Exponential moving average of the weights (ABI 4, additive; csrc/misc.hip).  Same contract as m3ae_adamw: one call per contiguous
+ * fp32 segment, n % 4 == 0, p and ema 16-byte aligned, clip_dev 4-byte aligned; M3AE_ERR_ARG / M3AE_ERR_ALIGN before any launch.
+ *
+ * m3ae_ema_update: per element, two fp32 roundings:
+ *     d   = p - ema
+ *     ema = fmaf(w, d, ema)
+ *   with w = 1 - decay of THIS update, formed in double by the caller and rounded to fp32 once (1.0f - 0.9999f is 3e-4 relative off
+ *   1e-4).  p == ema or w == 0 leaves every bit of a finite ema (but its sign where it is a zero: -0 + 0 = +0).  clip_dev: NULL, or the record of m3ae_clip_finalize: skip != 0 -> returns
+ *   before touching ema (the step the guard skipped changed no weight); coef is not read.
+ * m3ae_ema_swap: exchanges p[i] and ema[i] exactly; shadow_bf16 (NULL, or 8-byte aligned) receives the bf16 rounding of the new p[i]
+ *   as the optimizer kernels round it.  Two calls are the identity on all three buffers.
+ */
+int m3ae_ema_update(const float* p, float* ema, int64_t n, float w, const float* clip_dev, void* stream);
+int m3ae_ema_swap(float* p, float* ema, void* shadow_bf16, int64_t n, void* stream);
 
 /* bf16 [R, C] <- fp32 [R, C] cast; and the transposed bf16 copy out_t [C, R] (dgrad operand). either may be NULL */
 int m3ae_cast_transpose(const float* in, void* out, void* out_t, int64_t R, int64_t C, void* stream);

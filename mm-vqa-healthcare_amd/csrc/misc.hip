@@ -493,6 +493,34 @@ __global__ void sgd_kernel(float* p, const float* g, float* buf, bf16_t* shadow,
     }
 }
 
+// ---- EMA of the weights (cfg["ema_decay"]) ------------------------------------------------------------------------
+// e' = fmaf(w, p - e, e) with w = 1 - decay_t, formed in double on the host and rounded once (1.0f - decay in here would be the
+// adam_kernel mistake).  The difference form is exact where it matters: p == e or w == 0 leaves every bit of e.  Two roundings per
+// element, 12 B / element.  A step the guard skipped changed no weight, so the average does not move either: same first lines as
+// the CLIP kernels above, but the record is optional at run time and only its skip word is read.
+__global__ void ema_update_kernel(const float* p, float* ema, int64_t n4, float w, const float* clip_dev) {
+    if (clip_dev && ((const uint32_t*)clip_dev)[M3AE_CLIP_SKIP] != 0u) return;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        const f32x4 pp = ((const f32x4*)p)[i];
+        f32x4 ee = ((f32x4*)ema)[i];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const float d = pp[t] - ee[t];
+            ee[t] = __builtin_fmaf(w, d, ee[t]);
+        }
+        ((f32x4*)ema)[i] = ee;
+    }
+}
+
+// p <-> ema, exactly; the bf16 shadow of the new p in the same pass (pack2bf, as the optimizer kernels round it).  Twice = identity.
+__global__ void ema_swap_kernel(float* p, float* ema, bf16_t* shadow, int64_t n4) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+        const f32x4 pp = ((f32x4*)p)[i], ee = ((f32x4*)ema)[i];
+        ((f32x4*)p)[i] = ee; ((f32x4*)ema)[i] = pp;
+        if (shadow) ((u32x2*)shadow)[i] = (u32x2){pack2bf(ee[0], ee[1]), pack2bf(ee[2], ee[3])};
+    }
+}
+
 // ---- cast / transpose -------------------------------------------------------------------------------------
 __global__ void cast_transpose_kernel(const float* in, bf16_t* out, bf16_t* out_t, int64_t R, int64_t C) {
     __shared__ float tile[32][33];
@@ -935,6 +963,19 @@ extern "C" int m3ae_sgd(float* p, const float* g, float* buf, void* shadow_bf16,
 extern "C" int m3ae_sgd_clip(float* p, const float* g, float* buf, void* shadow_bf16, int64_t n, float lr, float momentum,
                              float wd, float grad_scale, const float* clip_dev, void* stream) {
     return sgd_impl<true>(p, g, buf, shadow_bf16, n, lr, momentum, wd, grad_scale, clip_dev, stream);
+}
+
+extern "C" int m3ae_ema_update(const float* p, float* ema, int64_t n, float w, const float* clip_dev, void* stream) {
+    if (!p || !ema || n <= 0) return M3AE_ERR_ARG;
+    if (n % 4 != 0 || (((uintptr_t)p | (uintptr_t)ema) & 15) || ((uintptr_t)clip_dev & 3)) return M3AE_ERR_ALIGN;
+    hipLaunchKernelGGL(ema_update_kernel, dim3(ew_grid(n / 4)), dim3(EW_BLOCK), 0, (hipStream_t)stream, p, ema, n / 4, w, clip_dev);
+    return hip_launch_status();
+}
+extern "C" int m3ae_ema_swap(float* p, float* ema, void* shadow_bf16, int64_t n, void* stream) {
+    if (!p || !ema || n <= 0) return M3AE_ERR_ARG;
+    if (n % 4 != 0 || (((uintptr_t)p | (uintptr_t)ema) & 15) || ((uintptr_t)shadow_bf16 & 7)) return M3AE_ERR_ALIGN;
+    hipLaunchKernelGGL(ema_swap_kernel, dim3(ew_grid(n / 4)), dim3(EW_BLOCK), 0, (hipStream_t)stream, p, ema, (bf16_t*)shadow_bf16, n / 4);
+    return hip_launch_status();
 }
 
 extern "C" int m3ae_cast_transpose(const float* in, void* out, void* out_t, int64_t R, int64_t C, void* stream) {

@@ -160,6 +160,9 @@ _SIGS = {
     "m3ae_adam_clip": (C.c_int, [vp, vp, vp, vp, vp, i64, f32, C.c_double, C.c_double, f32, f32, i64, f32, vp, vp]),
     "m3ae_sgd": (C.c_int, [vp, vp, vp, vp, i64, f32, f32, f32, f32, vp]),
     "m3ae_sgd_clip": (C.c_int, [vp, vp, vp, vp, i64, f32, f32, f32, f32, vp, vp]),
+    # EMA of the weights (ABI 4, additive): ema += w * (p - ema) over a flat segment, and the exact p <-> ema exchange
+    "m3ae_ema_update": (C.c_int, [vp, vp, i64, f32, vp, vp]),
+    "m3ae_ema_swap": (C.c_int, [vp, vp, vp, i64, vp]),
     # fp32 residual stream of a bf16 model (ABI 4, additive): LayerNorm fp32 rows -> bf16 rows, and its backward
     "m3ae_layernorm_fwd_mixed": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, f32, vp]),
     "m3ae_layernorm_bwd_mixed": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, vp]),

@@ -86,6 +86,13 @@ DEFAULTS = dict(
     # memory: no host round trip.  A step whose gradient holds an inf or a nan updates nothing and is counted
     # (ParamStore.grad_stats).  Not available with graph.GraphedStep or FlatGradReducer(update_in_backward=True).
     gradient_clip_val=0.0,
+    # exponential moving average of the trainable weights (not in the reference; m3ae_amd/param_store.py): ema_decay 0.0 = off (the
+    # step's launches are what they are without the key, nothing is allocated) | a float in (0, 1).  One more flat fp32 buffer and
+    # one streaming launch per optimizer range (csrc/misc.hip: m3ae_ema_update).  ema_warmup: decay_t = min(ema_decay, (1 + t) /
+    # (10 + t)) at the t-th update (1-based), so that a short run is not dominated by its starting point.  ema_eval: validation and
+    # test -- and with them the choice of best.ckpt -- run on the averaged weights (ParamStore.ema_weights).  load_ema: `load_path`
+    # takes a checkpoint's `ema_state_dict` over its `state_dict`.  Not available with graph.GraphedStep.
+    ema_decay=0.0, ema_warmup=True, ema_eval=True, load_ema=False,
 )
 
 NAMED = {
@@ -178,6 +185,30 @@ def gradient_clip_val(cfg):
     return float(v)
 
 
+def ema_decay(cfg):
+    """The validated `ema_decay` of a config dict (default 0.0 = off) as a float in [0, 1); `ema_warmup`, `ema_eval` and `load_ema`
+    next to it must be bools."""
+    v = cfg.get("ema_decay", 0.0)
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0 <= v < 1:
+        raise ValueError(f"ema_decay must be a number in [0, 1) (0: off), got {v!r}")
+    for key, default in (("ema_warmup", True), ("ema_eval", True), ("load_ema", False)):
+        if not isinstance(cfg.get(key, default), bool):
+            raise ValueError(f"{key} must be True or False, got {cfg[key]!r}")
+    return float(v)
+
+
+def ema_decay_at(decay, t, warmup=True):
+    """decay_t of the t-th EMA update (t = 1, 2, ...): min(decay, (1 + t) / (10 + t)) under `ema_warmup`, else `decay`."""
+    return min(decay, (1.0 + t) / (10.0 + t)) if warmup else decay
+
+
+def ema_weight(decay, t, warmup=True):
+    """w = 1 - decay_t as the float m3ae_ema_update takes: formed in double, rounded to fp32 once (struct round trip).  In fp32
+    arithmetic 1.0f - 0.9999f is 3e-4 relative off 1e-4, and the average would carry that."""
+    import struct
+    return struct.unpack("f", struct.pack("f", 1.0 - ema_decay_at(decay, t, warmup)))[0]
+
+
 DECODER_SEARCHES = ("host", "device")
 
 
@@ -224,6 +255,10 @@ def resolve_arch(cfg):
     vqa_metrics(cfg)
     if "gradient_clip_val" in cfg:
         cfg["gradient_clip_val"] = gradient_clip_val(cfg)
+    if "ema_decay" in cfg:
+        cfg["ema_decay"] = ema_decay(cfg)
+    else:
+        ema_decay(cfg)
     clip_residual_dtype(cfg)
     transform_keys(cfg)
     randaug_enabled(cfg)

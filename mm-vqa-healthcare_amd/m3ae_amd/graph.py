@@ -43,6 +43,12 @@ class GraphedStep:
             # the clipped step's launches (norm, finalize, m3ae_adamw_clip) are not the ones capture() records, and the skipped-step
             # counters are read where the caller syncs: not offered under replay
             raise ValueError("GraphedStep does not cover gradient_clip_val: run the step eagerly")
+        from .config import ema_decay
+        for c in (getattr(getattr(core, "hparams", None), "config", None), getattr(getattr(model, "store", None), "cfg", None)):
+            if ema_decay(c or {}) > 0:
+                # m3ae_ema_update takes this update's weight (1 - decay_t, warmup included) as a kernel argument: a replay would
+                # average with the captured step's value
+                raise ValueError("GraphedStep does not cover ema_decay: run the step eagerly")
         from .config import optim_type
         for c in (getattr(getattr(core, "hparams", None), "config", None), getattr(getattr(model, "store", None), "cfg", None)):
             if optim_type(c or {}) != "adamw":

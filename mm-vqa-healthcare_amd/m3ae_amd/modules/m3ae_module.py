@@ -170,7 +170,14 @@ class M3AETransformerSS(_Base):
         # upstream checkpoints are Lightning pickles (callbacks / hyper_parameters hold class globals): the weights-only
         # unpickler of torch >= 2.6 rejects them, as it would for the reference's own torch.load (m3ae_module.py:105)
         ckpt = torch.load(path, map_location="cpu", weights_only=False)
-        sd = adapt_position_encoding(ckpt["state_dict"], after=self.hparams.config["image_size"],
+        weights = ckpt["state_dict"]
+        if self.hparams.config.get("load_ema", False):
+            # config key `load_ema`: the averaged weights of a run with ema_decay > 0 (trainer.Trainer.save) over the raw ones; the
+            # average has the trainable parameters only, everything else (frozen weights, buffers) comes from state_dict
+            if ckpt.get("ema_state_dict") is None:
+                raise ValueError(f"load_ema=True, but {path} has no ema_state_dict (it was not written by a run with ema_decay > 0)")
+            weights = dict(weights, **ckpt["ema_state_dict"])
+        sd = adapt_position_encoding(weights, after=self.hparams.config["image_size"],
                                      patch_size=self.hparams.config["patch_size"])
         self.load_state_dict(sd, strict=False)
         if getattr(self, "store", None) is not None:   # also reachable from __init__ (load_path), before finalize()

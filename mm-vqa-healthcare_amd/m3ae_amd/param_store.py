@@ -12,6 +12,7 @@ each tensor 64-element aligned, with `param.data` and `param.grad` re-pointed to
 Parameters that never receive a gradient (CLIP text-tower leftovers, RoBERTa pooler) keep their names and
 values but are left out of the gradient / optimizer / all-reduce buffers.
 """
+import contextlib
 import ctypes as C
 import math
 
@@ -165,6 +166,10 @@ class ParamStore:
                 if self.shadow is not None:
                     p.m3ae_c = self.shadow[o:o + p.numel()].view(p.shape)
         self.step_count = 0
+        # EMA of the trainable weights (cfg["ema_decay"] > 0): allocated by the first begin_update, see there
+        from .config import ema_decay
+        self.ema_decay = ema_decay(cfg)
+        self.ema, self.ema_updates, self._ema_open = None, 0, False
         # per-parameter segments (offset, numel) of the trainable range, in buffer order, for the gradient norm (gradnorm.py): the
         # ALIGN padding between parameters is in no segment.  Host list; tables and workspace are uploaded on first use.
         self.grad_segments = sorted((self.offset[id(p)], p.numel(), n) for g in groups[:6] for n, p in g)
@@ -275,7 +280,12 @@ class ParamStore:
         sgd reads neither betas nor eps and takes its momentum from `self.momentum`.
         With gradient_clip_val set, a step the non-finite guard skips on the device still consumes its step number here and its
         scheduler tick at the caller (as Lightning's scheduler ticks through a GradScaler skip): the count lives on the host,
-        which is what keeps the step free of host syncs; grad_stats()["skipped_steps"] counts them."""
+        which is what keeps the step free of host syncs; grad_stats()["skipped_steps"] counts them.
+        With ema_decay > 0 the record carries `ema_w` = 1 - decay_t of this update (config.ema_weight: double, rounded once), and the
+        first call allocates `self.ema` as a copy of the trainable weights as they stand before that step.  The count `ema_updates`
+        is the host's too: a step the guard skips leaves the average where it is (m3ae_ema_update reads the same record) but still
+        consumes its warmup tick, as it consumes its step number."""
+        self._no_ema_open("begin_update")
         self._alloc_state()
         if betas is ADAMW_BETAS and self.optim == "adam":
             betas = ADAM_BETAS
@@ -288,8 +298,80 @@ class ParamStore:
         if group_wds is None:
             group_wds = [wd for _, wd in hp]
         self.step_count += 1
-        return dict(lrs=[float(x) for x in group_lrs], wds=[float(x) for x in group_wds], b1=float(betas[0]), b2=float(betas[1]),
-                    eps=float(eps), step=self.step_count, grad_scale=grad_scale, momentum=float(self.momentum))
+        hyper = dict(lrs=[float(x) for x in group_lrs], wds=[float(x) for x in group_wds], b1=float(betas[0]), b2=float(betas[1]),
+                     eps=float(eps), step=self.step_count, grad_scale=grad_scale, momentum=float(self.momentum))
+        if self.ema_decay > 0:
+            from .config import ema_weight
+            self._alloc_ema()
+            self.ema_updates += 1
+            hyper["ema_w"] = ema_weight(self.ema_decay, self.ema_updates, self.cfg.get("ema_warmup", True))
+        return hyper
+
+    # ---- EMA of the trainable weights (cfg["ema_decay"]; csrc/misc.hip: m3ae_ema_update / m3ae_ema_swap) ------------------------
+    def _alloc_ema(self):
+        """`self.ema`: fp32 [trainable_end], on first use a copy of the trainable weights as they stand.  Frozen and never-used
+        parameters (flat[trainable_end:]) do not change and are not averaged."""
+        if self.ema is None:
+            with torch.no_grad():
+                self.ema = self.flat[:self.trainable_end].clone()
+
+    def _no_ema_open(self, what):
+        if self._ema_open:
+            raise RuntimeError(f"ParamStore.{what} inside ema_weights(): the weights are exchanged with their average; leave the "
+                               "context before stepping the optimizer")
+
+    def _ema_swap(self):
+        if self.trainable_end == 0:
+            return
+        sh = C.c_void_p(self.shadow.data_ptr()) if self.shadow is not None else None
+        _lib.check(_lib.lib().m3ae_ema_swap(C.c_void_p(self.flat.data_ptr()), C.c_void_p(self.ema.data_ptr()), sh, self.trainable_end,
+                                            C.c_void_p(torch.cuda.current_stream().cuda_stream)), "m3ae_ema_swap")
+        self.sync_shadows(cast=False)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Evaluate with the averaged weights: on entry one exact exchange of flat[:trainable_end] with `ema` that also writes the bf16
+        shadow (m3ae_ema_swap), then the transposed and tiled copies (sync_shadows(cast=False)), on the current stream; on exit, in a
+        `finally`, the same again -- which restores every buffer bit for bit.  Runs under no_grad, is not re-entrant, and the
+        optimizer entry points raise RuntimeError while it is open.  fp32 / fp32x3: no shadow, the exchange alone."""
+        if self.ema is None:
+            raise RuntimeError("ema_weights(): no average yet (ema_decay is 0, or no optimizer step has run and none was loaded)")
+        if self._ema_open:
+            raise RuntimeError("ema_weights() is not re-entrant")
+        with torch.no_grad():
+            self._ema_swap()
+            self._ema_open = True
+            try:
+                yield self
+            finally:
+                self._ema_open = False
+                self._ema_swap()
+
+    def ema_state_dict(self):
+        """{name: CPU fp32 tensor} of the averaged weights, one entry per trainable parameter under its state_dict name."""
+        if self.ema is None:
+            raise RuntimeError("ema_state_dict(): no average yet (ema_decay is 0, or no optimizer step has run and none was loaded)")
+        if self._ema_open:
+            raise RuntimeError("ema_state_dict() inside ema_weights(): `ema` holds the raw weights there")
+        host = self.ema.cpu()
+        return {n: host[self.offset[id(p)]:self.offset[id(p)] + p.numel()].view(p.shape).clone() for g in self.groups[:6] for n, p in g}
+
+    @torch.no_grad()
+    def load_ema_state_dict(self, sd, updates):
+        """Restore the average and its update count (a checkpoint's `ema_state_dict` / `ema_updates`); a ValueError names a trainable
+        parameter that is missing or has another shape, and nothing is written then."""
+        self._no_ema_open("load_ema_state_dict")
+        named = [(n, p) for g in self.groups[:6] for n, p in g]
+        for n, p in named:
+            if n not in sd:
+                raise ValueError(f"ema_state_dict has no entry for the trainable parameter {n!r}")
+            if tuple(sd[n].shape) != tuple(p.shape):
+                raise ValueError(f"ema_state_dict[{n!r}] has shape {tuple(sd[n].shape)}, the parameter {tuple(p.shape)}")
+        self._alloc_ema()
+        for n, p in named:
+            o = self.offset[id(p)]
+            self.ema[o:o + p.numel()].view(p.shape).copy_(sd[n].to(dtype=torch.float32))
+        self.ema_updates = int(updates)
 
     # A hipGraph-captured step replays with frozen kernel arguments: graph.GraphedStep makes the AdamW launches read this step's
     # learning rate and bias-corrected step size per group from `hyper_dev` ([6][2] fp32 on the device, uploaded before a replay).
@@ -316,7 +398,9 @@ class ParamStore:
     def update_range(self, a, b, gi, hyper, clip=None):
         """The rule's fused kernel (m3ae_adamw / m3ae_adam / m3ae_sgd) over elements [a, b) of the flat buffers (inside optimizer
         group `gi`), on the current stream.  `clip`: the device record of m3ae_clip_finalize; the launch is then the rule's _clip
-        form (skip / grad_scale * coef on the device)."""
+        form (skip / grad_scale * coef on the device).  With ema_decay > 0, m3ae_ema_update follows right behind over the same
+        [a, b) with the same record (a skipped step moves neither): one rule for update_apply and ddp.FlatGradReducer alike."""
+        self._no_ema_open("update_range")
         if b <= a:
             return
         from . import ops as _ops
@@ -335,6 +419,10 @@ class ParamStore:
         if clip is not None:
             name, args = name + "_clip", args + (C.c_void_p(clip.data_ptr()),)
         _lib.check(getattr(_lib.lib(), name)(*args, _ops._stream()), name)
+        if "ema_w" in hyper:
+            _lib.check(_lib.lib().m3ae_ema_update(p, C.c_void_p(self.ema.data_ptr() + a * es), b - a, hyper["ema_w"],
+                                                  None if clip is None else C.c_void_p(clip.data_ptr()), _ops._stream()),
+                       "m3ae_ema_update")
 
     @torch.no_grad()
     def optimizer_step(self, max_steps=None, grad_scale=1.0, lr_factor=None, group_lrs=None, betas=ADAMW_BETAS, eps=1e-8,
@@ -350,6 +438,7 @@ class ParamStore:
         With cfg["gradient_clip_val"] > 0: the sum of squares of the gradient buffer per parameter (double), the one-workgroup
         finalize with this step's grad_scale, then the six launches in their _clip form -- all on the current stream, the factor and
         the skip flag never leave the device.  With the key at 0 this is the six plain launches and nothing is allocated."""
+        self._no_ema_open("update_apply")
         clip = None
         max_norm = self.clip_val()
         if max_norm > 0:

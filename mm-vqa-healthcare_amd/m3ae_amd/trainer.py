@@ -16,6 +16,10 @@ arithmetic around `training_step`:
 * `gradient_clip_val` (Lightning's Trainer flag; 0 = off): clipping by global norm and the non-finite step guard happen inside
   `optimizer.step()`, after the gradient all-reduce, once per accumulation window (ParamStore.update_apply); the periodic log line
   then also shows the gradient norm, the factor applied and the number of skipped steps;
+* `ema_decay` (not in the reference; 0 = off): an exponential moving average of the trainable weights, updated inside
+  `optimizer.step()` (ParamStore.update_range).  With `ema_eval` validation and test run on the averaged weights
+  (ParamStore.ema_weights), so `best.ckpt` is chosen by their metric and the log line says `(ema)`; checkpoints keep `state_dict` as
+  the raw weights -- `resume` stays exact -- and carry `ema_state_dict` / `ema_updates` next to it (`load_ema` reads them);
 * validation every `val_check_interval` of an epoch with the VQA score `val/the_metric` (my_metrics.py:58-83), best +
   last checkpoints (`ModelCheckpoint(save_top_k=1, monitor="val/the_metric", mode="max", save_last=True)`,
   main.py:36-43) written as `{"state_dict": ...}` with the REFERENCE's key names, so the files load in the upstream
@@ -154,6 +158,8 @@ class Trainer:
         # and token exact match in test() for the generator heads).  metrics / exact_match: the result() dicts of the last pass.
         self.vqa_metrics = config_mod.vqa_metrics(cfg)
         self.metrics, self.exact_match = None, None
+        self.ema_eval = config_mod.ema_decay(cfg) > 0 and cfg.get("ema_eval", True)
+        self.validated_on_ema = False    # whether the last validate() ran on the averaged weights
 
     # -- checkpoints (reference key names; loadable by m3ae_module.py:105-113 upstream) ------------------------
     def save(self, name, metric=None):
@@ -164,6 +170,8 @@ class Trainer:
               "hyper_parameters": {"config": {k: v for k, v in self.cfg.items()}}, "val/the_metric": metric}
         if self.metrics is not None:
             ck["val/closed_score"], ck["val/open_score"] = self.metrics["closed"], self.metrics["open"]
+        if self.store.ema is not None:   # ema_decay > 0: the average next to the raw weights, in weights-only checkpoints too
+            ck["ema_state_dict"], ck["ema_updates"] = self.store.ema_state_dict(), self.store.ema_updates
         if not self.weights_only:   # Lightning's keys
             ck["optimizer_states"] = [self.optimizer.state_dict()]
             ck["lr_schedulers"] = [self.scheduler.state_dict()]
@@ -176,6 +184,12 @@ class Trainer:
         self.model.load_state_dict(ck["state_dict"], strict=False)
         self.store.sync_shadows()
         self.global_step, self.epoch = ck.get("global_step", 0), ck.get("epoch", 0)
+        if ck.get("ema_state_dict") is not None and self.store.ema_decay > 0:
+            self.store.load_ema_state_dict(ck["ema_state_dict"], ck.get("ema_updates", 0))
+        elif self.store.ema_decay > 0:
+            self.store.ema, self.store.ema_updates = None, 0
+            self.store._alloc_ema()
+            log(f"{path} has no ema_state_dict: the average starts from the loaded weights", self.rank)
         of = ck.get("optimizer_flat")   # checkpoints written before the Optimizer face existed
         if ck.get("optimizer_states"):
             self.optimizer.load_state_dict(ck["optimizer_states"][0])    # state of another optim_type: ValueError
@@ -221,7 +235,15 @@ class Trainer:
 
     def validate(self, generate=False):
         """The monitored quantity over the validation batches.  generate (test() with vqa_metrics="device"): the generator heads
-        also run their device-resident search per batch and feed TokenExactMatch from the ids, which stay on the device."""
+        also run their device-resident search per batch and feed TokenExactMatch from the ids, which stay on the device.
+        With ema_decay > 0, `ema_eval` and an average to read, the whole pass runs inside ParamStore.ema_weights()."""
+        self.validated_on_ema = bool(self.ema_eval and self.store.ema is not None)
+        if self.validated_on_ema:
+            with self.store.ema_weights():
+                return self._validate(generate)
+        return self._validate(generate)
+
+    def _validate(self, generate):
         self.model.eval()
         tot, cnt = torch.zeros((), device=self.device), 0
         device_metrics = self.vqa_metrics == "device"
@@ -323,7 +345,7 @@ class Trainer:
                         done = True
                 if nbatch % val_every == 0 or done:
                     m = self.validate()
-                    log(f"val/the_metric {m:.4f} (best {max(self.best, m):.4f}){self.metrics_text()}", self.rank)
+                    log(f"val/the_metric{' (ema)' if self.validated_on_ema else ''} {m:.4f} (best {max(self.best, m):.4f}){self.metrics_text()}", self.rank)
                     if m > self.best:
                         self.best = m
                         self.save("best.ckpt", m)
@@ -340,7 +362,7 @@ class Trainer:
         if self.exact_match is not None:
             r = self.exact_match
             em = f" token_exact_match {r['score']:.4f} ({r['n']}) closed {r['closed']:.4f} ({r['n_closed']}) open {r['open']:.4f} ({r['n_open']})"
-        log(f"test/the_metric {m:.4f}{self.metrics_text()}{em}", self.rank)
+        log(f"test/the_metric{' (ema)' if self.validated_on_ema else ''} {m:.4f}{self.metrics_text()}{em}", self.rank)
         return m
 
 

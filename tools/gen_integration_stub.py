@@ -72,6 +72,9 @@ SECTIONS = {
     "OPTIM_ENTRIES": Section(
         "# optim_type adam / sgd (ABI 4, additive): torch.optim.Adam and SGD with momentum over a flat segment; _clip = + the record", (),
         ("m3ae_adam", "m3ae_adam_clip", "m3ae_sgd", "m3ae_sgd_clip")),
+    "EMA_ENTRIES": Section(
+        "# EMA of the weights (ABI 4, additive): ema = fmaf(w, p - ema, ema) over a flat segment; exact p <-> ema swap + bf16 shadow", (),
+        ("m3ae_ema_update", "m3ae_ema_swap")),
     "GREEDY_ENTRIES": Section(
         "# device-resident greedy search for the decoder head (ABI 4, additive): order keys per vocabulary chunk, then the step", (),
         ("m3ae_greedy_workspace_bytes", "m3ae_greedy_argmax", "m3ae_greedy_step")),
