@@ -60,6 +60,9 @@ extern "C" {
  *    (csrc/vqa_eval.hip): prediction, top-k answers and the closed / open / overall score record; no descriptor changed. */
 /* 4 (additive): exponential moving average of the weights.  m3ae_ema_update and m3ae_ema_swap (csrc/misc.hip); no descriptor
  *    changed. */
+/* 4 (additive): device-side token evaluation for rows of vocabulary width.  m3ae_token_eval (+ m3ae_token_eval_workspace_bytes) and
+ *    m3ae_record_add (csrc/token_eval.hip): argmax, label rank, negative log-likelihood, top-k tokens with softmax probabilities and
+ *    the {n, hit1, hitk, sum_nll, calls} record of the labelled rows; no descriptor changed. */
 #define M3AE_ABI_VERSION 4
 
 enum { M3AE_F32 = 0, M3AE_BF16 = 1 };
@@ -828,6 +831,48 @@ int m3ae_vqa_eval(const void* logits, int64_t ld, const float* targets, int64_t 
 int m3ae_seq_match(const int64_t* gen, int64_t ldg, int64_t Lg, const int64_t* ref, int64_t ldr, int64_t Lr, const int64_t* skip,
                    int64_t ns, const int32_t* types, int64_t B, int32_t* match, double* rec, void* workspace,
                    int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Device-side token evaluation (csrc/token_eval.hip; ABI 4, additive): what the reference's `Accuracy` metric computes for the MLM
+ * and ITM objectives (my_metrics.py: preds = logits.argmax(-1) over the rows whose target is not -100), plus the label's rank, the
+ * negative log-likelihood and the top-k tokens with their softmax probabilities, for rows of vocabulary width, on the device.
+ *
+ * The record: double rec[M3AE_TOKEN_REC_DOUBLES] in device memory, zeroed by the caller before the first update: rec[0] = n, the
+ *   evaluated rows that carry a label; rec[1] = hit1, those with rank == 0; rec[2] = hitk, those with rank < k; rec[3] = the sum of
+ *   their nll; rec[4] = number of update calls.
+ *
+ * m3ae_token_eval.  logits [R][V], dtype M3AE_F32 or M3AE_BF16, row stride ld >= V in elements; the base pointer is
+ *   element-aligned, nothing else is asked of ld, and columns [V, ld) are never read (as m3ae_greedy_argmax: scalar head up to the
+ *   first 16-byte boundary, 16-byte loads, scalar tail).  labels int64 [R] or NULL; select uint8 [R] or NULL.  chunk: columns per
+ *   workgroup, 0 = 8192, 64 <= chunk <= 65536.  0 <= k <= M3AE_TOKEN_MAX_K and k <= V.
+ *   Which rows are evaluated: with select, the rows with select[r] != 0; else, with labels, the rows with labels[r] !=
+ *   M3AE_TOKEN_IGNORE (-100); else every row.  An evaluated row whose label is neither -100 nor in [0, V) sets err[0] = 1 (int64,
+ *   required with labels) and is skipped: a label is turned into an address only after that check.  No logit of a row that is not
+ *   evaluated is read.
+ *   Ranking: the order key of m3ae_greedy_argmax -- value descending, the lowest column among equal values (+0 == -0), every NaN of
+ *   either sign above every number, the first NaN first.  pred is rank 0, torch.argmax's choice.  rank = the number of columns whose
+ *   key is strictly greater than the label's: 0 iff pred == label, so a label that ties the maximum from a higher column is no hit.
+ *   lse: per chunk (m, s) = (maximum, sum of e(x, m)) in fp32 with e(x, m) = x == m ? 1 : expf(x - m); pairs merge as
+ *   m' = fmaxf(m1, m2), s' = s1 e(m1, m') + s2 e(m2, m'); lse = m + logf(s).  Non-finite rows get what torch.logsumexp gives, by the
+ *   same arithmetic and no special case: a NaN anywhere gives lse = NaN; a +inf gives lse = +inf (nll = +inf, or NaN when the label
+ *   is that column); a row of -inf alone gives lse = -inf and nll = -inf - -inf = NaN.  Such an nll goes into rec[3] as it is.
+ *   Outputs, each may be NULL: pred int64 [R]; rank int32 [R] (-1 for an evaluated row without a label); nll fp32 [R] = lse -
+ *   x[label] (the lse itself for an evaluated row without a label); topk_idx int32 [R][k]; topk_prob fp32 [R][k] = expf(x_j - lse).
+ *   A row that is not evaluated gets pred -1, rank -1, nll 0, topk_idx -1, topk_prob 0.
+ *   The fold (rec given): one launch of one workgroup adds the labelled rows onto rec in double, in an order that depends on R
+ *   alone; no atomics, so two calls on the same inputs give the same bits and deterministic mode needs no second form.
+ *   workspace: m3ae_token_eval_workspace_bytes(R, V, chunk, k) bytes (0 for shapes the call rejects), 8-byte aligned, always needed.
+ *   M3AE_ERR_ARG: NULL logits or workspace, R < 1, V < 1, ld < V, chunk < 0, k < 0, labels without err.  M3AE_ERR_UNSUPPORTED, before
+ *   any launch: k > 16, k > V, chunk outside its bounds, V >= 2^31, R >= 2^31, R * chunks >= 2^31, a dtype other than fp32 / bf16, a
+ *   short workspace.  M3AE_ERR_ALIGN: a pointer off its element size.
+ * m3ae_record_add: rec[0] += value[0] (a device fp32 scalar, widened), rec[1] += 1, in double: the running sum and count of a
+ *   per-batch loss (the reference's `Scalar` metric) without a host round trip. */
+enum { M3AE_TOKEN_REC_DOUBLES = 5, M3AE_TOKEN_MAX_K = 16 /* the bound on k above */, M3AE_TOKEN_IGNORE = -100 };
+int64_t m3ae_token_eval_workspace_bytes(int64_t R, int64_t V, int64_t chunk, int64_t k);
+int m3ae_token_eval(const void* logits, int64_t ld, const int64_t* labels, const uint8_t* select, int64_t R, int64_t V, int64_t chunk,
+                    int64_t k, int dtype, int64_t* pred, int32_t* rank, float* nll, int32_t* topk_idx, float* topk_prob, double* rec,
+                    int64_t* err, void* workspace, int64_t workspace_bytes, void* stream);
+int m3ae_record_add(const float* value, double* rec, void* stream);
 
 /* self-test of hardware idioms the kernels rely on (MFMA fragment maps, ds_read_b64_tr_b16, accumulator-as-
  * operand k-order).  out: int32[8 + 256] device buffer (tail = scratch), out[0] = number of mismatches. */

@@ -6,7 +6,7 @@
 //   vqa_eval_kernel, one workgroup per row.  The row is read ONCE (scalar head up to the first 16-byte boundary, 16-byte loads,
 //   scalar tail, as csrc/greedy.hip: no load touches a column at or past C).  Every value becomes the order key of
 //   csrc/order_key.h with greedy.hip's NaN / -0 handling; a thread keeps the kk = max(k, 1) greatest keys of ITS columns in LDS
-//   (cand[slot][thread]; 0 = empty, no key is 0).  The row's top-k is a subset of the union of the threads' top-k, so rank j is
+//   (cand[slot][thread]; 0 = empty, no key is 0; csrc/topk_keep.h, shared with csrc/token_eval.hip).  The row's top-k is a subset of the union of the threads' top-k, so rank j is
 //   "the greatest candidate below rank j - 1": k passes over LDS, each a wave maximum and a four-way fold.  Keys of distinct
 //   columns are distinct integers: the result does not depend on any order.  The value of a chosen column is decoded from its
 //   key (exact but for -0 -> +0 and the NaN payload, neither of which the sigmoid sees).
@@ -15,37 +15,14 @@
 // m3ae_seq_match: one thread per row walks gen[r] and ref[r] with the skip ids dropped; then the same fold.
 #include "common.h"
 #include "order_key.h"
+#include "topk_keep.h"
 #include <math.h>
 
 namespace {
 
-constexpr int VT = 256;          // threads of every kernel here
+constexpr int VT = KEEP_T;       // threads of every kernel here (256: the scheme of csrc/topk_keep.h)
 constexpr int V_MAX_K = M3AE_VQA_MAX_K;
 constexpr int V_MAX_SKIP = M3AE_SEQ_MAX_SKIP;
-
-DEVINL uint64_t eval_key(uint32_t u, uint32_t col) {   // u = the bits of an fp32 value; csrc/greedy.hip's rule
-    if ((u & 0x7fffffffu) > 0x7f800000u) return ((uint64_t)0xffffffffu << 32) | (uint64_t)(0xffffffffu - col);   // NaN: above +inf
-    return make_key(__uint_as_float(u == 0x80000000u ? 0u : u), col);                                           // -0 -> +0
-}
-DEVINL uint32_t bits_of(float v) { return __float_as_uint(v); }
-DEVINL uint32_t bits_of(bf16_t v) { return (uint32_t)v << 16; }
-
-// The kk greatest keys a thread has seen, in cand[slot * VT + tid]; mn / mnpos = the least of them and its slot.
-struct Keep {
-    uint64_t* c;
-    int kk, mnpos;
-    uint64_t mn;
-    DEVINL void put(uint64_t key) {
-        if (key <= mn) return;
-        c[mnpos * VT] = key;
-        mn = c[0];
-        mnpos = 0;
-        for (int s = 1; s < kk; ++s) {
-            const uint64_t v = c[s * VT];
-            if (v < mn) { mn = v; mnpos = s; }
-        }
-    }
-};
 
 template <typename T>
 __global__ __launch_bounds__(VT) void vqa_eval_kernel(const T* __restrict__ logits, int64_t ld, const float* __restrict__ targets,
@@ -86,23 +63,7 @@ __global__ __launch_bounds__(VT) void vqa_eval_kernel(const T* __restrict__ logi
     }
     if (tail0 + tid < C) keep.put(eval_key(bits_of(x[tail0 + tid]), (uint32_t)(tail0 + tid)));   // < W <= VT columns
 
-    // rank j = the greatest candidate below rank j - 1 (rank 0: the greatest)
-    uint64_t prev = 0;
-    for (int j = 0; j < kk; ++j) {
-        uint64_t best = 0;
-        for (int s = 0; s < kk; ++s) {
-            const uint64_t v = cand[s * VT + tid];
-            if ((j == 0 || v < prev) && v > best) best = v;
-        }
-        best = wave_max_u64(best);
-        if ((tid & 63) == 0) red[j & 1][tid >> 6] = best;
-        __syncthreads();   // one barrier a pass: pass j + 2 reuses red[j & 1] only after every thread has passed the barrier of j + 1
-        const uint64_t a = red[j & 1][0], b = red[j & 1][1], c = red[j & 1][2], d = red[j & 1][3];
-        const uint64_t ab = a > b ? a : b, cd = c > d ? c : d;
-        prev = ab > cd ? ab : cd;
-        if (tid == 0) sel[j] = prev;
-    }
-    __syncthreads();
+    keep_select(cand, kk, red, sel, tid);   // rank j = the greatest candidate below rank j - 1 (rank 0: the greatest)
 
     // a key of 0 (fewer than kk columns: the host refuses k > C) or a column outside [0, C) is never an address
     if (tid < k) {

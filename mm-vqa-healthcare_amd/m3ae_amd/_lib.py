@@ -65,6 +65,8 @@ XATTN_NO_PERSISTENT, XATTN_LEGACY_CHAIN = 1, 2    # m3ae_xattn_desc.launch_flags
 CLIP_NORM, CLIP_COEF, CLIP_SKIP, CLIP_STEPS, CLIP_CLIPPED_STEPS, CLIP_SKIPPED_STEPS, CLIP_RECORD_WORDS = 0, 1, 2, 4, 5, 6, 8
 # the record of m3ae_vqa_eval / m3ae_seq_match (include/m3ae_hip.h): 10 doubles, {n, sum_top1, sum_topk} of (all, closed, open), calls
 ANS_CLOSED, ANS_OPEN, VQA_REC_DOUBLES, VQA_MAX_K, SEQ_MAX_SKIP = 0, 1, 10, 16, 8
+# m3ae_token_eval (include/m3ae_hip.h): double rec[5] = {n, hit1, hitk, sum_nll, calls}; the bound on k; the label that marks "no label"
+TOKEN_REC_DOUBLES, TOKEN_MAX_K, TOKEN_IGNORE = 5, 16, -100
 ABI_VERSION = 4
 
 
@@ -176,6 +178,10 @@ _SIGS = {
     "m3ae_vqa_eval_workspace_bytes": (i64, [i64, i64]),
     "m3ae_vqa_eval": (C.c_int, [vp, i64, vp, i64, vp, i64, i64, i64, C.c_int, vp, vp, vp, vp, vp, vp, i64, vp]),
     "m3ae_seq_match": (C.c_int, [vp, i64, i64, vp, i64, i64, vp, i64, vp, i64, vp, vp, vp, i64, vp]),
+    # device-side token evaluation for rows of vocabulary width (ABI 4, additive): argmax, label rank, nll, top-k, the record (TOKEN_*)
+    "m3ae_token_eval_workspace_bytes": (i64, [i64, i64, i64, i64]),
+    "m3ae_token_eval": (C.c_int, [vp, i64, vp, vp, i64, i64, i64, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
+    "m3ae_record_add": (C.c_int, [vp, vp, vp]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -62,6 +62,11 @@ DEFAULTS = dict(
     # the top `eval_topk` answers, and token exact match for the generator heads in test()).  eval_topk is honoured only with "device".
     vqa_metrics="host",
     eval_topk=5,
+    # what a validation pass of the pre-training objectives reports (m3ae_amd/trainer.py, m3ae_amd/metrics.py): "host" (the monitored
+    # negative summed loss alone, as before) | "device" (csrc/token_eval.hip: MLM accuracy, accuracy within the top `eval_topk` tokens
+    # and perplexity, ITM accuracy and the mean loss per objective, accumulated on the GPU and read with one copy; the monitored
+    # quantity stays what it is).  eval_topk is shared with vqa_metrics and checked with either "device".
+    pretrain_metrics="host",
     # arrow VQA batches collated per distinct image (m3ae_amd/data.py: collate_dedup): every distinct image of a batch is decoded,
     # uploaded and run through the image tower once, and ops.expand_samples hands its tokens to the samples that ask about it
     # (batch["image_index"]).  Same samples, same arithmetic per sample; not available with the mim / itm objectives.
@@ -234,6 +239,20 @@ def vqa_metrics(cfg):
     return v
 
 
+PRETRAIN_METRICS = ("host", "device")
+
+
+def pretrain_metrics(cfg):
+    """The validated `pretrain_metrics` of a config dict (default "host"); with "device", `eval_topk` must be an int in [0, 16]."""
+    v = cfg.get("pretrain_metrics", "host")
+    if not isinstance(v, str) or v not in PRETRAIN_METRICS:
+        raise ValueError(f"pretrain_metrics must be one of {PRETRAIN_METRICS}, got {v!r}")
+    k = cfg.get("eval_topk", 5)
+    if v == "device" and (isinstance(k, bool) or not isinstance(k, int) or not 0 <= k <= 16):
+        raise ValueError(f"eval_topk must be an integer in [0, 16] with pretrain_metrics='device', got {k!r}")
+    return v
+
+
 OPTIM_TYPES = ("adamw", "adam", "sgd")
 
 
@@ -253,6 +272,7 @@ def resolve_arch(cfg):
     optim_type(cfg)
     decoder_search(cfg)
     vqa_metrics(cfg)
+    pretrain_metrics(cfg)
     if "gradient_clip_val" in cfg:
         cfg["gradient_clip_val"] = gradient_clip_val(cfg)
     if "ema_decay" in cfg:

@@ -513,6 +513,48 @@ class M3AETransformerSS(_Base):
         out = self.predict(batch, k=k)
         return answers_of(out["labels"].cpu().tolist(), out["probs"].cpu().tolist(), label2ans)
 
+    def default_mask_token_id(self):
+        """The id fill_mask looks for when it is given none: `self.tokenizer.mask_token_id` when a tokenizer has been attached
+        to the module, else config["mask_token_id"], else the id of the vocabulary config["tokenizer"] names -- 50264 (`<mask>`)
+        for the RoBERTa vocabularies, 103 (`[MASK]`) for the BERT ones."""
+        tok = getattr(self, "tokenizer", None)
+        cfg = self.hparams.config
+        if tok is not None and getattr(tok, "mask_token_id", None) is not None:
+            return int(tok.mask_token_id)
+        if cfg.get("mask_token_id") is not None:
+            return int(cfg["mask_token_id"])
+        return 50264 if "roberta" in str(cfg["tokenizer"]) else 103
+
+    @ops.model_mode
+    def fill_mask(self, batch, k=5, mask_token_id=None):
+        """The k most probable tokens at every masked position of batch["text_ids"]: {"tokens": int64 [B, S, k] (best first),
+        "probs": fp32 [B, S, k] (softmax probabilities over the vocabulary), "mask": bool [B, S] (text_ids == mask_token_id)}, all
+        dense and on the device -- a position that is not masked holds -1 / 0, and nothing is copied to the host to count the
+        masked ones.  Runs under no_grad in eval mode (the training flag is restored): infer(mask_text=False), the MLM head, and
+        ops.token_eval on the logits as the head left them, which reads the masked rows alone.  mask_token_id: None = the id
+        default_mask_token_id() finds."""
+        if not hasattr(self, "mlm_head"):
+            raise RuntimeError('fill_mask needs the MLM head (loss_names["mlm"] > 0)')
+        k = int(k)
+        if not 1 <= k <= 16:
+            raise ValueError(f"k={k} outside [1, 16]")
+        V = self.hparams.config["vocab_size"]
+        mid = self.default_mask_token_id() if mask_token_id is None else int(mask_token_id)
+        if not 0 <= mid < V:
+            raise ValueError(f"mask_token_id={mid} outside the vocabulary [0, {V}): pass mask_token_id=")
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                infer = self.infer(batch, mask_text=False, mask_image=False)
+                logits = self.mlm_head(infer["multi_modal_text_feats"])
+                B, S = logits.shape[0], logits.shape[1]
+                mask = infer["text_ids"] == mid                 # built on the device
+                rows = ops.token_eval(logits.view(B * S, logits.shape[-1]), None, mask.reshape(-1).contiguous(), None, k=k, want_topk=True)
+        finally:
+            self.train(was_training)
+        return {"tokens": rows.topk_idx.long().view(B, S, k), "probs": rows.topk_prob.view(B, S, k), "mask": mask}
+
     @ops.model_mode
     def forward(self, batch, test=False):
         """m3ae_module.py:314-345."""

@@ -1,5 +1,6 @@
-"""Loss arithmetic of the reference's m3ae/modules/objectives.py (the string metrics / logging around it are out
-of scope).  Each function returns the same `ret` keys the reference does for the tensors it computes."""
+"""Loss arithmetic of the reference's m3ae/modules/objectives.py.  Each function returns the same `ret` keys the reference does
+for the tensors it computes; its `Accuracy` / `Scalar` logging (objectives.py:32-36, :70-74, :114-117) is fed from those keys by the
+trainer under `pretrain_metrics="device"` (m3ae_amd/metrics.py: PretrainMetrics), the string metrics stay out of scope."""
 import torch
 
 from .. import ops

@@ -2278,6 +2278,90 @@ def seq_match(gen, ref, skip, types, rec, want_rows=False):
 
 
 # ------------------------------------------------------------------------------------------------------------
+# device-side token evaluation for rows of vocabulary width (csrc/token_eval.hip): m3ae_amd/metrics.py (TokenAccuracy, LossMean),
+# M3AETransformerSS.fill_mask
+# ------------------------------------------------------------------------------------------------------------
+class TokenRows(NamedTuple):
+    """The per-row outputs of token_eval(want_rows=True / want_topk=True); a group that was not asked for is None.  A row that was
+    not evaluated holds pred -1, rank -1, nll 0, topk_idx -1, topk_prob 0."""
+    pred: torch.Tensor | None          # int64 [R]: torch.argmax(logits, -1)
+    rank: torch.Tensor | None          # int32 [R]: columns ranked above the label (0: a hit); -1 without a label
+    nll: torch.Tensor | None           # fp32 [R]: logsumexp(row) - row[label]
+    topk_idx: torch.Tensor | None      # int32 [R, k]
+    topk_prob: torch.Tensor | None     # fp32 [R, k]: softmax probabilities
+    err: torch.Tensor | None           # int64 [1]: 1 after a label that is neither -100 nor in [0, V) (with labels)
+
+
+def token_record(device):
+    """A zeroed record of token_eval: float64 [5] = {n, hit1, hitk, sum_nll, calls} (include/m3ae_hip.h)."""
+    return torch.zeros((_lib.TOKEN_REC_DOUBLES,), dtype=torch.float64, device=device)
+
+
+def token_eval(logits, labels=None, select=None, rec=None, k=0, chunk=0, want_rows=False, want_topk=False):
+    """One update of the token record from the rows of `logits`, enqueued on the current stream (no host sync).
+    logits fp32 or bf16 [R, V] (row stride >= V, unit column stride: the [..., :V] view of vocab_linear's padded buffer is taken as
+    it is); labels int64 [R] or None (-100: no label); select uint8 / bool [R] or None; rec float64 [5] (ops.token_record) or None.
+    Evaluated rows: select != 0 if given, else labels != -100 if given, else all; the logits of the other rows are not read.
+    Adds {n, rank == 0, rank < k, nll} of the labelled evaluated rows onto rec.  0 <= k <= min(16, V); chunk: columns per workgroup
+    (0: 8192).  want_rows: pred / rank / nll, want_topk: topk_idx / topk_prob (k > 0), returned as TokenRows."""
+    _need_cuda(logits)
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError("token_eval takes fp32 or bf16 logits")
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        raise ValueError(f"token_eval: logits {tuple(logits.shape)} with strides {tuple(logits.stride())}")
+    R, V = logits.shape
+    k, chunk = int(k), int(chunk)
+    if not 0 <= k <= min(_lib.TOKEN_MAX_K, V):
+        raise ValueError(f"token_eval: k={k} outside [0, min({_lib.TOKEN_MAX_K}, V={V})]")
+    if chunk != 0 and not 64 <= chunk <= 65536:
+        raise ValueError(f"token_eval: chunk={chunk} is neither 0 nor in [64, 65536]")
+    if want_topk and k == 0:
+        raise ValueError("token_eval: want_topk needs k > 0")
+    dev = logits.device
+    if labels is not None:
+        _need_cuda(labels)
+        if labels.dtype != torch.int64 or tuple(labels.shape) != (R,) or not labels.is_contiguous():
+            raise ValueError(f"token_eval: labels int64 [{R}], contiguous; got {labels.dtype} {tuple(labels.shape)}")
+    if select is not None:
+        _need_cuda(select)
+        if select.dtype not in (torch.uint8, torch.bool) or tuple(select.shape) != (R,) or not select.is_contiguous():
+            raise ValueError(f"token_eval: select uint8 / bool [{R}], contiguous; got {select.dtype} {tuple(select.shape)}")
+    if rec is not None:
+        _need_cuda(rec)
+        if rec.dtype != torch.float64 or tuple(rec.shape) != (_lib.TOKEN_REC_DOUBLES,) or not rec.is_contiguous():
+            raise ValueError(f"token_eval: rec float64 [{_lib.TOKEN_REC_DOUBLES}], contiguous (ops.token_record)")
+    L = _lib.lib()
+    need = L.m3ae_token_eval_workspace_bytes(R, V, chunk, k)
+    if need <= 0:
+        raise ValueError(f"token_eval: unsupported shape R={R}, V={V}, chunk={chunk}, k={k}")
+    ws = torch.empty((need // 8,), dtype=torch.int64, device=dev)
+    err = torch.zeros((1,), dtype=torch.int64, device=dev) if labels is not None else None
+    pred = rank = nll = idx = prob = None
+    if want_rows:
+        pred = torch.empty((R,), dtype=torch.int64, device=dev)
+        rank = torch.empty((R,), dtype=torch.int32, device=dev)
+        nll = torch.empty((R,), dtype=torch.float32, device=dev)
+    if want_topk:
+        idx = torch.empty((R, k), dtype=torch.int32, device=dev)
+        prob = torch.empty((R, k), dtype=torch.float32, device=dev)
+    check(L.m3ae_token_eval(_p(logits), logits.stride(0), _p(labels), _p(select), R, V, chunk, k, _dt(logits), _p(pred), _p(rank),
+                            _p(nll), _p(idx), _p(prob), _p(rec), _p(err), _p(ws), need, _stream()), "m3ae_token_eval")
+    return TokenRows(pred, rank, nll, idx, prob, err) if (want_rows or want_topk) else None
+
+
+def record_add(value, rec):
+    """rec[0] += value, rec[1] += 1 in double on the device (metrics.LossMean): value a device fp32 scalar (0-d or [1]), rec a
+    float64 [2] device tensor.  Enqueued on the current stream; no ATen arithmetic, no host sync."""
+    _need_cuda(value)
+    _need_cuda(rec)
+    if value.dtype != torch.float32 or value.numel() != 1:
+        raise ValueError(f"record_add: value is one fp32 number on the device; got {value.dtype} {tuple(value.shape)}")
+    if rec.dtype != torch.float64 or tuple(rec.shape) != (2,) or not rec.is_contiguous():
+        raise ValueError("record_add: rec float64 [2], contiguous")
+    check(_lib.lib().m3ae_record_add(_p(value), _p(rec), _stream()), "m3ae_record_add")
+
+
+# ------------------------------------------------------------------------------------------------------------
 # masked-image-modelling bookkeeping (pre-training, SURVEY 8a13)
 # ------------------------------------------------------------------------------------------------------------
 def mask_ranks(noise, len_keep):

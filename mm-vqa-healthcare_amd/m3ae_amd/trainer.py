@@ -25,7 +25,10 @@ arithmetic around `training_step`:
   main.py:36-43) written as `{"state_dict": ...}` with the REFERENCE's key names, so the files load in the upstream
   code and upstream checkpoints load here (`load_path`); `save_weights_only` when "finetune" is in `exp_name`; with
   `vqa_metrics=device` the score is kept on the GPU (m3ae_amd/metrics.py) and validation also reports the closed / open scores
-  and the score within the top `eval_topk` answers, `test()` token exact match for the generator heads;
+  and the score within the top `eval_topk` answers, `test()` token exact match for the generator heads; with
+  `pretrain_metrics=device` a validation pass of the pre-training objectives also reports MLM / ITM accuracy, MLM accuracy within
+  the top `eval_topk` tokens, perplexity and the mean loss per objective (the reference's `Accuracy` / `Scalar` logs,
+  objectives.py:32-36, :70-74, :114-117), accumulated on the GPU; the monitored quantity stays the negative summed loss;
 * one process per GPU: launched under `python -m torch.distributed.run --nproc-per-node N main.py with ...`
   (RANK / LOCAL_RANK / WORLD_SIZE), RCCL through `torch.distributed`; `num_gpus` * `num_nodes` must equal the world.
 
@@ -158,6 +161,10 @@ class Trainer:
         # and token exact match in test() for the generator heads).  metrics / exact_match: the result() dicts of the last pass.
         self.vqa_metrics = config_mod.vqa_metrics(cfg)
         self.metrics, self.exact_match = None, None
+        # config key `pretrain_metrics`: "host" (nothing beyond the monitored loss) | "device" (metrics.PretrainMetrics);
+        # pretrain: its result() dict of the last pass
+        self.pretrain_metrics = config_mod.pretrain_metrics(cfg)
+        self.pretrain = None
         self.ema_eval = config_mod.ema_decay(cfg) > 0 and cfg.get("ema_eval", True)
         self.validated_on_ema = False    # whether the last validate() ran on the averaged weights
 
@@ -170,6 +177,13 @@ class Trainer:
               "hyper_parameters": {"config": {k: v for k, v in self.cfg.items()}}, "val/the_metric": metric}
         if self.metrics is not None:
             ck["val/closed_score"], ck["val/open_score"] = self.metrics["closed"], self.metrics["open"]
+        if self.pretrain:
+            for name in ("mlm", "itm"):
+                if name in self.pretrain:
+                    ck[f"val/{name}_accuracy"] = self.pretrain[name]["accuracy"]
+            for name in ("mlm", "itm", "mim"):
+                if f"{name}_loss" in self.pretrain:
+                    ck[f"val/{name}_loss"] = self.pretrain[f"{name}_loss"]
         if self.store.ema is not None:   # ema_decay > 0: the average next to the raw weights, in weights-only checkpoints too
             ck["ema_state_dict"], ck["ema_updates"] = self.store.ema_state_dict(), self.store.ema_updates
         if not self.weights_only:   # Lightning's keys
@@ -226,12 +240,28 @@ class Trainer:
             return metrics_mod.TokenExactMatch((c.pad_token_id, c.decoder_start_token_id, c.eos_token_id), self.device), m.labels_of
         return None, None
 
+    def pretrain_text(self):
+        """`mlm acc X (n) @k Y ppl Z | itm acc X (n) | mim loss X` of the last pass ("" with pretrain_metrics="host")."""
+        r = self.pretrain
+        if not r:
+            return ""
+        parts = []
+        if "mlm" in r:
+            m = r["mlm"]
+            parts.append(f"mlm acc {m['accuracy']:.4f} ({m['n']}) @{self.cfg.get('eval_topk', 5)} {m['accuracy_at_k']:.4f} ppl {m['perplexity']:.4g}")
+        if "itm" in r:
+            parts.append(f"itm acc {r['itm']['accuracy']:.4f} ({r['itm']['n']})")
+        if "mim_loss" in r:
+            parts.append(f"mim loss {r['mim_loss']:.4f}")
+        return " " + " | ".join(parts) if parts else ""
+
     def metrics_text(self):
-        """The closed / open / @k part of the validation log line ("" with vqa_metrics="host")."""
+        """The closed / open / @k part of the validation log line ("" with vqa_metrics="host"), then the pre-training part
+        ("" with pretrain_metrics="host")."""
         r = self.metrics
         if r is None:
-            return ""
-        return f" closed {r['closed']:.4f} ({r['n_closed']}) open {r['open']:.4f} ({r['n_open']}) @{self.cfg.get('eval_topk', 5)} {r['score_at_k']:.4f}"
+            return self.pretrain_text()
+        return self.pretrain_text() + f" closed {r['closed']:.4f} ({r['n_closed']}) open {r['open']:.4f} ({r['n_open']}) @{self.cfg.get('eval_topk', 5)} {r['score_at_k']:.4f}"
 
     def validate(self, generate=False):
         """The monitored quantity over the validation batches.  generate (test() with vqa_metrics="device"): the generator heads
@@ -249,6 +279,7 @@ class Trainer:
         device_metrics = self.vqa_metrics == "device"
         score = metrics_mod.VQARADScore(self.device, k=self.cfg.get("eval_topk", 5)) if device_metrics and hasattr(self.model, "vqa_head_forward") else None
         em, refs_of = self._generator_metric() if device_metrics and generate else (None, None)
+        pre = None      # pretrain_metrics="device": built at the first batch that brings a pre-training objective
         fed = 0
         with torch.no_grad():
             for batch in self.dm.val_batches():
@@ -264,6 +295,10 @@ class Trainer:
                 if ret is not None and "vqa_logits" in ret:
                     s, n = vqa_score(ret["vqa_logits"], ret["vqa_targets"])
                 elif ret is not None:   # pre-training objectives: negative summed loss as the monitored quantity
+                    if self.pretrain_metrics == "device" and any(k in ret for k in ("mlm_logits", "itm_logits", "mim_loss")):
+                        if pre is None:
+                            pre = metrics_mod.PretrainMetrics(self.device, k=self.cfg.get("eval_topk", 5))
+                        pre.update(ret)          # enqueued; read once below
                     s = -sum(v.float() for k, v in ret.items() if k.endswith("_loss")) * n
                 else:                   # generator heads: negative teacher-forced loss
                     s = -self._loss(batch).float() * n
@@ -274,6 +309,8 @@ class Trainer:
         self.model.train()
         if em is not None:
             self.exact_match = em.result()
+        if pre is not None:
+            self.pretrain = pre.result()     # one all-reduce and one blocking copy for all of them
         if fed:
             self.metrics = score.result()    # the record's all-reduce and its one blocking copy
             return self.metrics["score"]

@@ -86,6 +86,11 @@ SECTIONS = {
         (("ANS_CLOSED, ANS_OPEN, VQA_REC_DOUBLES",
           "     # types values; double rec[10] = {n, sum_top1, sum_topk} x (all, closed, open), calls"),),
         ("m3ae_vqa_eval_workspace_bytes", "m3ae_vqa_eval", "m3ae_seq_match")),
+    "TOKEN_EVAL_ENTRIES": Section(
+        "# device-side token evaluation (ABI 4, additive): argmax, label rank, nll and top-k over vocabulary-wide rows; a loss mean",
+        (("TOKEN_REC_DOUBLES, TOKEN_MAX_K, TOKEN_IGNORE",
+          "     # double rec[5] = {n, hit1, hitk, sum_nll, calls}; the bound on k; the label that means no label"),),
+        ("m3ae_token_eval_workspace_bytes", "m3ae_token_eval", "m3ae_record_add")),
 }
 globals().update({key: s.entries for key, s in SECTIONS.items() if s.entries})   # MAP_ENTRIES, DET_ENTRIES, ...: views of the table
 
