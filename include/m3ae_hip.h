@@ -63,6 +63,9 @@ extern "C" {
 /* 4 (additive): device-side token evaluation for rows of vocabulary width.  m3ae_token_eval (+ m3ae_token_eval_workspace_bytes) and
  *    m3ae_record_add (csrc/token_eval.hip): argmax, label rank, negative log-likelihood, top-k tokens with softmax probabilities and
  *    the {n, hit1, hitk, sum_nll, calls} record of the labelled rows; no descriptor changed. */
+/* 4 (additive): LoRA in merged form on the flat buffers.  m3ae_lora_merge, m3ae_lora_grad and m3ae_lora_grad_workspace_bytes
+ *    (csrc/lora.hip): W = W0 + s B A written into the master and shadow buffers, and dA / dB projected out of the full weight
+ *    gradient, each as one grouped launch chain over a device table of targets; no descriptor changed. */
 #define M3AE_ABI_VERSION 4
 
 enum { M3AE_F32 = 0, M3AE_BF16 = 1 };
@@ -614,6 +617,32 @@ int m3ae_sgd_clip(float* p, const float* g, float* buf, void* shadow_bf16, int64
  */
 int m3ae_ema_update(const float* p, float* ema, int64_t n, float w, const float* clip_dev, void* stream);
 int m3ae_ema_swap(float* p, float* ema, void* shadow_bf16, int64_t n, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * LoRA, merged form (ABI 4, additive; csrc/lora.hip).  The reference has no counterpart.  A table is `ntargets` records of six
+ * int64 {elem_offset, N, K, a_off, b_off, base_off}:  W[N][K] at elem_offset of the flat fp32 master `flat` (and of the bf16 shadow),
+ * A[r][K] at a_off and B[N][r] at b_off of the adapter buffer `lora` (in m3ae_lora_grad: dA / dB at the same offsets of `lora_grad`),
+ * W0[N][K] at base_off of `base`.  One rank r in 1..M3AE_LORA_MAX_RANK for the table, 1 <= ntargets <= M3AE_LORA_MAX_TARGETS
+ * (M3AE_ERR_UNSUPPORTED above either), N, K >= 1, every offset a multiple of 4 elements (ParamStore: 64).  The table is in DEVICE
+ * memory and is not checked against the buffers: the caller validates it (m3ae_amd/lora.py: LoraTable).  No atomics; every result is
+ * a function of the inputs alone.
+ *
+ * m3ae_lora_merge: per element, r + 1 fused multiply-adds in this order
+ *     acc = 0;  for j = 0 .. r-1: acc = fmaf(B[n][j], A[j][k], acc);     W[n][k] = fmaf(s, acc, W0[n][k])
+ *   written to `flat` and, where shadow_bf16 is not NULL, as its round-to-nearest-even bf16 to the shadow.  B = 0 gives W0 bit for
+ *   bit (a W0 of -0 becomes +0).  mode 1: W = W0 and its shadow; A, B and s are not read (lora may be NULL).  Only the N * K elements
+ *   of each target are written.  base, lora, flat 16-byte aligned, shadow 8-byte.
+ * m3ae_lora_grad: dB[n][j] = s * acc, acc = 0; for k = 0 .. K-1: acc = fmaf(dW[n][k], A[j][k], acc);
+ *   dA[j][k] = s * (((P_0 + P_1) + P_2) + ...), P_p = the chain acc = fmaf(B[n][j], dW[n][k], acc) over the rows n of row panel p
+ *   (M3AE_LORA_PANEL_ROWS rows each, ascending).  dW = grad_flat at elem_offset, read once; the outputs are overwritten; the planes
+ *   P_p live in `workspace` (4-byte aligned, m3ae_lora_grad_workspace_bytes of a HOST copy of the same table; NULL: M3AE_ERR_WORKSPACE).
+ */
+enum { M3AE_LORA_MAX_RANK = 64, M3AE_LORA_MAX_TARGETS = 512, M3AE_LORA_PANEL_ROWS = 64 };
+int m3ae_lora_merge(const int64_t* table_dev, int64_t ntargets, int64_t r, float s, const float* base, const float* lora, float* flat,
+                    void* shadow_bf16, int mode, void* stream);
+int64_t m3ae_lora_grad_workspace_bytes(const int64_t* table_host, int64_t ntargets, int64_t r);
+int m3ae_lora_grad(const int64_t* table_dev, int64_t ntargets, int64_t r, float s, const float* lora, const float* grad_flat,
+                   float* lora_grad, void* workspace, void* stream);
 
 /* bf16 [R, C] <- fp32 [R, C] cast; and the transposed bf16 copy out_t [C, R] (dgrad operand). either may be NULL */
 int m3ae_cast_transpose(const float* in, void* out, void* out_t, int64_t R, int64_t C, void* stream);

@@ -67,6 +67,8 @@ CLIP_NORM, CLIP_COEF, CLIP_SKIP, CLIP_STEPS, CLIP_CLIPPED_STEPS, CLIP_SKIPPED_ST
 ANS_CLOSED, ANS_OPEN, VQA_REC_DOUBLES, VQA_MAX_K, SEQ_MAX_SKIP = 0, 1, 10, 16, 8
 # m3ae_token_eval (include/m3ae_hip.h): double rec[5] = {n, hit1, hitk, sum_nll, calls}; the bound on k; the label that marks "no label"
 TOKEN_REC_DOUBLES, TOKEN_MAX_K, TOKEN_IGNORE = 5, 16, -100
+# m3ae_lora_merge / m3ae_lora_grad (include/m3ae_hip.h): the bounds on rank and table, the rows of one row panel of the projection
+LORA_MAX_RANK, LORA_MAX_TARGETS, LORA_PANEL_ROWS = 64, 512, 64
 ABI_VERSION = 4
 
 
@@ -182,6 +184,10 @@ _SIGS = {
     "m3ae_token_eval_workspace_bytes": (i64, [i64, i64, i64, i64]),
     "m3ae_token_eval": (C.c_int, [vp, i64, vp, vp, i64, i64, i64, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]),
     "m3ae_record_add": (C.c_int, [vp, vp, vp]),
+    # LoRA in merged form (ABI 4, additive): W = W0 + s B A into master and shadow; dA / dB out of the full weight gradient
+    "m3ae_lora_merge": (C.c_int, [vp, i64, i64, f32, vp, vp, vp, vp, C.c_int, vp]),
+    "m3ae_lora_grad_workspace_bytes": (i64, [vp, i64, i64]),
+    "m3ae_lora_grad": (C.c_int, [vp, i64, i64, f32, vp, vp, vp, vp, vp]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -98,6 +98,15 @@ DEFAULTS = dict(
     # test -- and with them the choice of best.ckpt -- run on the averaged weights (ParamStore.ema_weights).  load_ema: `load_path`
     # takes a checkpoint's `ema_state_dict` over its `state_dict`.  Not available with graph.GraphedStep.
     ema_decay=0.0, ema_warmup=True, ema_eval=True, load_ema=False,
+    # LoRA fine-tuning in merged form (not in the reference; m3ae_amd/lora.py, csrc/lora.hip): lora_rank 0 = off (a step makes the
+    # calls it makes without the key) | 1..64.  The effective weight W0 + (lora_alpha / lora_rank) B A lives in the ordinary weight
+    # buffers, so the forward, the backward and every state_dict are what they are; only the adapters and the heads are updated.
+    # lora_targets: "all-linear" (every GEMM weight of optimizer groups 0 and 4) | "attention" (the attention projections among
+    # them).  lora_lr_multiplier scales the learning rate of the target's group for the adapters; its default follows the usual
+    # practice of running adapters an order of magnitude above the full fine-tuning rate -- nobody has tuned it on VQA-RAD here.
+    # lora_path: an adapter file (LoraAdapters.state_dict) to load after `load_path`.  Not available with graph.GraphedStep,
+    # FlatGradReducer(update_in_backward=True), ema_decay > 0, gradient_clip_val > 0 or the T5 / decoder wrappers.
+    lora_rank=0, lora_alpha=16.0, lora_targets="all-linear", lora_lr_multiplier=10.0, lora_path="",
 )
 
 NAMED = {
@@ -214,6 +223,28 @@ def ema_weight(decay, t, warmup=True):
     return struct.unpack("f", struct.pack("f", 1.0 - ema_decay_at(decay, t, warmup)))[0]
 
 
+LORA_TARGETS = ("all-linear", "attention")
+LORA_MAX_RANK = 64
+
+
+def lora_rank(cfg):
+    """The validated `lora_rank` of a config dict (default 0 = off): an int in [0, 64].  The keys next to it are checked with it:
+    `lora_alpha` and `lora_lr_multiplier` finite numbers > 0, `lora_targets` one of LORA_TARGETS, `lora_path` a string."""
+    v = cfg.get("lora_rank", 0)
+    if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= LORA_MAX_RANK:
+        raise ValueError(f"lora_rank must be an integer in [0, {LORA_MAX_RANK}] (0: off), got {v!r}")
+    for key, default in (("lora_alpha", 16.0), ("lora_lr_multiplier", 10.0)):
+        x = cfg.get(key, default)
+        if isinstance(x, bool) or not isinstance(x, (int, float)) or not 0 < x < float("inf"):
+            raise ValueError(f"{key} must be a finite number > 0, got {x!r}")
+    tg = cfg.get("lora_targets", "all-linear")
+    if not isinstance(tg, str) or tg not in LORA_TARGETS:
+        raise ValueError(f"lora_targets must be one of {LORA_TARGETS}, got {tg!r}")
+    if not isinstance(cfg.get("lora_path", ""), str):
+        raise ValueError(f"lora_path must be a string, got {cfg['lora_path']!r}")
+    return v
+
+
 DECODER_SEARCHES = ("host", "device")
 
 
@@ -279,6 +310,10 @@ def resolve_arch(cfg):
         cfg["ema_decay"] = ema_decay(cfg)
     else:
         ema_decay(cfg)
+    lora_rank(cfg)
+    for key in ("lora_alpha", "lora_lr_multiplier"):
+        if key in cfg:
+            cfg[key] = float(cfg[key])
     clip_residual_dtype(cfg)
     transform_keys(cfg)
     randaug_enabled(cfg)

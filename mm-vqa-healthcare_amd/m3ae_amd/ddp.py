@@ -226,6 +226,10 @@ class FlatGradReducer:
             # the buckets are stepped while backward still runs, before the norm of the whole gradient can be known
             raise ValueError("FlatGradReducer(update_in_backward=True) cannot be combined with gradient_clip_val: the global "
                              "gradient norm exists only after backward; step the optimizer after finish() instead")
+        if getattr(self.store, "lora", None) is not None:
+            # the adapter gradients are projected out of the whole, reduced weight gradient: there is nothing to step per bucket
+            raise ValueError("FlatGradReducer(update_in_backward=True) cannot be combined with lora_rank > 0: the adapters are "
+                             "stepped from the complete gradient; step the optimizer after finish() instead")
         assert self.update_in_backward
         # the early update of a bucket assumes every later reader of its weights is ordered behind events already recorded: true when
         # the GEMMs read the bf16 shadows / transposed copies the update rewrites LAST (finish()), not the fp32 masters.  A "late

@@ -49,6 +49,11 @@ class GraphedStep:
                 # m3ae_ema_update takes this update's weight (1 - decay_t, warmup included) as a kernel argument: a replay would
                 # average with the captured step's value
                 raise ValueError("GraphedStep does not cover ema_decay: run the step eagerly")
+        if getattr(getattr(model, "store", None), "lora", None) is not None or any(
+                (c or {}).get("lora_rank", 0) for c in (getattr(getattr(core, "hparams", None), "config", None), getattr(getattr(model, "store", None), "cfg", None))):
+            # the step with adapters launches the projection, the adapter update and the merge instead of the six launches capture()
+            # records with hyper_dev: not offered under replay
+            raise ValueError("GraphedStep does not cover lora_rank > 0: run the step eagerly")
         from .config import optim_type
         for c in (getattr(getattr(core, "hparams", None), "config", None), getattr(getattr(model, "store", None), "cfg", None)):
             if optim_type(c or {}) != "adamw":

@@ -336,6 +336,8 @@ class DecoderModel(_Base):
 
     def finalize(self, device="cuda", compute_dtype=None):
         cfg = self.m3ae.hparams.config
+        from ..lora import refuse_wrapper
+        refuse_wrapper(cfg, "the decoder wrapper")
         if compute_dtype is not None:
             self.m3ae.set_compute_dtype(compute_dtype)
         self.decoder.f32x3 = self.m3ae.f32x3

@@ -145,6 +145,7 @@ class M3AETransformerSS(_Base):
         if cfg["load_path"] != "" and cfg["test_only"]:
             self._load(cfg["load_path"])
         self.store = None
+        self.lora = None      # lora.LoraAdapters once attach_lora() has run (cfg["lora_rank"] > 0), else None
         self._dtype = torch.bfloat16 if cfg.get("compute_dtype", "bf16") == "bf16" else torch.float32
         self._x3 = cfg.get("compute_dtype") == "fp32x3"   # fp32x3 mode: fp32 storage, fp32 GEMMs on the split-bf16 MFMA kernel
         # deterministic=True (the reference trainer's flag, main.py:64): ordered reductions in every backward from here on.  The
@@ -204,6 +205,19 @@ class M3AETransformerSS(_Base):
             b.data = b.data.to(device)
         self.store = ParamStore(self, self.hparams.config, device, self._dtype, self.weight_units, frozen=frozen)
         return self
+
+    def attach_lora(self, path=""):
+        """Attach LoRA adapters per the config (lora_rank > 0), after finalize() and after the base weights are loaded: the weights
+        as they stand become the base.  `path`: an adapter file (LoraAdapters.state_dict) to load onto it.  Returns the adapters."""
+        from ..lora import LoraAdapters
+        if self.store is None:
+            raise RuntimeError("attach_lora() needs the flat layout: call finalize() first")
+        self.lora = LoraAdapters(self.store, self, self.hparams.config)
+        if path:
+            self.lora.load_state_dict(torch.load(path, map_location="cpu", weights_only=False))
+        else:
+            self.lora.merge()
+        return self.lora
 
     # ------------------------------------------------------------------------------------------------------
     two_streams = os.environ.get("M3AE_TWO_STREAMS", "1") == "1"   # M3AE_TWO_STREAMS=0: everything on the caller's stream

@@ -75,6 +75,8 @@ class T5VQA_MMEncoderInput(_Base):
 
     def finalize(self, device="cuda", compute_dtype=None):
         cfg = self.m3ae.hparams.config
+        from ..lora import refuse_wrapper
+        refuse_wrapper(cfg, "the T5 wrapper")
         if compute_dtype is not None:
             self.m3ae.set_compute_dtype(compute_dtype)
         self.store = ParamStore(self, cfg, device, self.m3ae._dtype, self.weight_units,

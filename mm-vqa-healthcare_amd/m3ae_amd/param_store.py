@@ -170,6 +170,8 @@ class ParamStore:
         from .config import ema_decay
         self.ema_decay = ema_decay(cfg)
         self.ema, self.ema_updates, self._ema_open = None, 0, False
+        # LoRA (cfg["lora_rank"] > 0): the lora.LoraAdapters attached to this store, whose step() update_apply then takes; None = off
+        self.lora = None
         # per-parameter segments (offset, numel) of the trainable range, in buffer order, for the gradient norm (gradnorm.py): the
         # ALIGN padding between parameters is in no segment.  Host list; tables and workspace are uploaded on first use.
         self.grad_segments = sorted((self.offset[id(p)], p.numel(), n) for g in groups[:6] for n, p in g)
@@ -319,6 +321,9 @@ class ParamStore:
         if self._ema_open:
             raise RuntimeError(f"ParamStore.{what} inside ema_weights(): the weights are exchanged with their average; leave the "
                                "context before stepping the optimizer")
+        if self.lora is not None and self.lora._disabled:
+            raise RuntimeError(f"ParamStore.{what} inside lora.disabled(): the weights are the base model's; leave the context "
+                               "before stepping the optimizer")
 
     def _ema_swap(self):
         if self.trainable_end == 0:
@@ -395,31 +400,35 @@ class ParamStore:
                              f"{dict(adamw_range='update_range', adamw_apply='update_apply', adamw_step='optimizer_step')[name]}")
 
     @torch.no_grad()
-    def update_range(self, a, b, gi, hyper, clip=None):
+    def update_range(self, a, b, gi, hyper, clip=None, bufs=None, lr_mult=None):
         """The rule's fused kernel (m3ae_adamw / m3ae_adam / m3ae_sgd) over elements [a, b) of the flat buffers (inside optimizer
         group `gi`), on the current stream.  `clip`: the device record of m3ae_clip_finalize; the launch is then the rule's _clip
         form (skip / grad_scale * coef on the device).  With ema_decay > 0, m3ae_ema_update follows right behind over the same
-        [a, b) with the same record (a skipped step moves neither): one rule for update_apply and ddp.FlatGradReducer alike."""
+        [a, b) with the same record (a skipped step moves neither): one rule for update_apply and ddp.FlatGradReducer alike.
+        `bufs` = (param, grad, exp_avg, exp_avg_sq, shadow) tensors: the same launch over [a, b) of THOSE buffers with group gi's
+        hyper-parameters, its learning rate times `lr_mult` (lora.LoraAdapters.step: the adapters have buffers of their own)."""
         self._no_ema_open("update_range")
         if b <= a:
             return
         from . import ops as _ops
         es = 4
-        sh = C.c_void_p(self.shadow.data_ptr() + a * 2) if self.shadow is not None else None
-        p, g, m = (C.c_void_p(t.data_ptr() + a * es) for t in (self.flat, self.grad, self.exp_avg))
+        flat, grad, exp_avg, exp_avg_sq, shadow = (self.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.shadow) if bufs is None else bufs
+        lr = hyper["lrs"][gi] if lr_mult is None else hyper["lrs"][gi] * lr_mult
+        sh = C.c_void_p(shadow.data_ptr() + a * 2) if shadow is not None else None
+        p, g, m = (C.c_void_p(t.data_ptr() + a * es) for t in (flat, grad, exp_avg))
         if self.optim == "sgd":
             name = "m3ae_sgd"
-            args = (p, g, m, sh, b - a, hyper["lrs"][gi], hyper["momentum"], hyper["wds"][gi], hyper["grad_scale"])
+            args = (p, g, m, sh, b - a, lr, hyper["momentum"], hyper["wds"][gi], hyper["grad_scale"])
         else:
             name = "m3ae_" + self.optim
-            args = (p, g, m, C.c_void_p(self.exp_avg_sq.data_ptr() + a * es), sh, b - a, hyper["lrs"][gi], hyper["b1"], hyper["b2"],
+            args = (p, g, m, C.c_void_p(exp_avg_sq.data_ptr() + a * es), sh, b - a, lr, hyper["b1"], hyper["b2"],
                     hyper["eps"], hyper["wds"][gi], hyper["step"], hyper["grad_scale"])
             if self.optim == "adamw":
-                args += (self._hyper_dev_ptr(gi),)
+                args += (self._hyper_dev_ptr(gi) if bufs is None else None,)
         if clip is not None:
             name, args = name + "_clip", args + (C.c_void_p(clip.data_ptr()),)
         _lib.check(getattr(_lib.lib(), name)(*args, _ops._stream()), name)
-        if "ema_w" in hyper:
+        if "ema_w" in hyper and bufs is None:
             _lib.check(_lib.lib().m3ae_ema_update(p, C.c_void_p(self.ema.data_ptr() + a * es), b - a, hyper["ema_w"],
                                                   None if clip is None else C.c_void_p(clip.data_ptr()), _ops._stream()),
                        "m3ae_ema_update")
@@ -437,8 +446,12 @@ class ParamStore:
         """The device part of an optimizer step for a begin_update() record: six fused launches + the transposed weight copies.
         With cfg["gradient_clip_val"] > 0: the sum of squares of the gradient buffer per parameter (double), the one-workgroup
         finalize with this step's grad_scale, then the six launches in their _clip form -- all on the current stream, the factor and
-        the skip flag never leave the device.  With the key at 0 this is the six plain launches and nothing is allocated."""
+        the skip flag never leave the device.  With the key at 0 this is the six plain launches and nothing is allocated.
+        With adapters attached (cfg["lora_rank"] > 0, self.lora) the device part is lora.LoraAdapters.step: projection, adapter
+        update, head segments, merge."""
         self._no_ema_open("update_apply")
+        if self.lora is not None:
+            return self.lora.step(hyper)
         clip = None
         max_norm = self.clip_val()
         if max_norm > 0:

@@ -20,6 +20,10 @@ arithmetic around `training_step`:
   `optimizer.step()` (ParamStore.update_range).  With `ema_eval` validation and test run on the averaged weights
   (ParamStore.ema_weights), so `best.ckpt` is chosen by their metric and the log line says `(ema)`; checkpoints keep `state_dict` as
   the raw weights -- `resume` stays exact -- and carry `ema_state_dict` / `ema_updates` next to it (`load_ema` reads them);
+* `lora_rank` (not in the reference; 0 = off): LoRA in merged form (m3ae_amd/lora.py).  `optimizer.step()` projects the adapter
+  gradients out of the weight gradients, steps adapters and heads and merges; checkpoints keep `state_dict` as the merged weights
+  and carry `lora_state_dict` (+ the adapters' moments unless weights-only); next to each checkpoint an adapter-only `*.lora.pt`
+  is written, which `lora_path` loads onto the base from `load_path`;
 * validation every `val_check_interval` of an epoch with the VQA score `val/the_metric` (my_metrics.py:58-83), best +
   last checkpoints (`ModelCheckpoint(save_top_k=1, monitor="val/the_metric", mode="max", save_last=True)`,
   main.py:36-43) written as `{"state_dict": ...}` with the REFERENCE's key names, so the files load in the upstream
@@ -166,6 +170,8 @@ class Trainer:
         self.pretrain_metrics = config_mod.pretrain_metrics(cfg)
         self.pretrain = None
         self.ema_eval = config_mod.ema_decay(cfg) > 0 and cfg.get("ema_eval", True)
+        if getattr(self.store, "lora", None) is not None:
+            log(self.store.lora.describe(), rank)
         self.validated_on_ema = False    # whether the last validate() ran on the averaged weights
 
     # -- checkpoints (reference key names; loadable by m3ae_module.py:105-113 upstream) ------------------------
@@ -186,17 +192,32 @@ class Trainer:
                     ck[f"val/{name}_loss"] = self.pretrain[f"{name}_loss"]
         if self.store.ema is not None:   # ema_decay > 0: the average next to the raw weights, in weights-only checkpoints too
             ck["ema_state_dict"], ck["ema_updates"] = self.store.ema_state_dict(), self.store.ema_updates
+        lora = getattr(self.store, "lora", None)
+        if lora is not None:   # lora_rank > 0: state_dict above holds the merged weights; the adapters (+ heads) next to them
+            ck["lora_state_dict"] = lora.state_dict()
+            if not self.weights_only:
+                ck["lora_optimizer_state"] = lora.optimizer_state()
         if not self.weights_only:   # Lightning's keys
             ck["optimizer_states"] = [self.optimizer.state_dict()]
             ck["lr_schedulers"] = [self.scheduler.state_dict()]
         path = os.path.join(self.ckpt_dir, name)
         torch.save(ck, path)
+        if lora is not None:   # the adapter-only file: base checkpoint + this = the fine-tuned model (config key lora_path)
+            torch.save(ck["lora_state_dict"], os.path.splitext(path)[0] + ".lora.pt")
         return path
 
     def resume(self, path):
         ck = torch.load(path, map_location="cpu", weights_only=False)
         self.model.load_state_dict(ck["state_dict"], strict=False)
         self.store.sync_shadows()
+        lora = getattr(self.store, "lora", None)
+        if lora is not None:
+            # the adapters go back onto the base taken from load_path at attach time (the fingerprint says whether it is the base they
+            # were trained on) and are merged again: the same bits state_dict held
+            if ck.get("lora_state_dict") is None:
+                raise ValueError(f"{path} has no lora_state_dict: it was not written by a run with lora_rank > 0")
+            lora.load_state_dict(ck["lora_state_dict"])
+            lora.load_optimizer_state(ck.get("lora_optimizer_state"))
         self.global_step, self.epoch = ck.get("global_step", 0), ck.get("epoch", 0)
         if ck.get("ema_state_dict") is not None and self.store.ema_decay > 0:
             self.store.load_ema_state_dict(ck["ema_state_dict"], ck.get("ema_updates", 0))
@@ -418,6 +439,10 @@ def init_distributed():
 
 def build_model(cfg, head, device):
     from .modules import DecoderModel, M3AETransformerSS, T5VQA_MMEncoderInput
+    lora_rank = config_mod.lora_rank(cfg)
+    if lora_rank > 0 and head in ("t5", "decoder"):
+        raise ValueError(f"lora_rank > 0 is not available with the {head} head: its M3AE is frozen and produces no weight gradient "
+                         "to project")
     if head == "t5":
         model = T5VQA_MMEncoderInput(cfg)
         model.unfreeze_top_layers(cfg["unfreeze_num_encoder_layers"], cfg["unfreeze_num_decoder_layers"])
@@ -434,6 +459,8 @@ def build_model(cfg, head, device):
         synth.fill_deterministic(model)
     mode = cfg.get("compute_dtype", "bf16")
     model.finalize(device, mode if mode in ("bf16", "fp32", "fp32x3") else torch.float32)
+    if lora_rank > 0:   # after finalize and load_path: the weights as they stand are the base; then lora_path, then the merge
+        model.attach_lora(cfg.get("lora_path", ""))
     return model
 
 

@@ -91,6 +91,10 @@ SECTIONS = {
         (("TOKEN_REC_DOUBLES, TOKEN_MAX_K, TOKEN_IGNORE",
           "     # double rec[5] = {n, hit1, hitk, sum_nll, calls}; the bound on k; the label that means no label"),),
         ("m3ae_token_eval_workspace_bytes", "m3ae_token_eval", "m3ae_record_add")),
+    "LORA_ENTRIES": Section(
+        "# LoRA, merged form (ABI 4, additive): W = W0 + s B A into master and shadow; dA, dB from the full dW; one table of targets",
+        (("LORA_MAX_RANK, LORA_MAX_TARGETS, LORA_PANEL_ROWS", "     # bounds on r and ntargets; rows of one row panel of the projection"),),
+        ("m3ae_lora_merge", "m3ae_lora_grad_workspace_bytes", "m3ae_lora_grad")),
 }
 globals().update({key: s.entries for key, s in SECTIONS.items() if s.entries})   # MAP_ENTRIES, DET_ENTRIES, ...: views of the table
 
