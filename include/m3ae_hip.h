@@ -66,6 +66,9 @@ extern "C" {
 /* 4 (additive): LoRA in merged form on the flat buffers.  m3ae_lora_merge, m3ae_lora_grad and m3ae_lora_grad_workspace_bytes
  *    (csrc/lora.hip): W = W0 + s B A written into the master and shadow buffers, and dA / dB projected out of the full weight
  *    gradient, each as one grouped launch chain over a device table of targets; no descriptor changed. */
+/* 4 (additive): answer-list decoding for the generator heads.  m3ae_trie_scan (+ m3ae_trie_workspace_bytes) and m3ae_trie_step
+ *    (csrc/answer_trie.hip): greedy search constrained to a prefix trie of the candidate answers, with the log-probability of the
+ *    chosen path; m3ae_vqa_label_eval (csrc/vqa_eval.hip): the score record from labels instead of logits; no descriptor changed. */
 #define M3AE_ABI_VERSION 4
 
 enum { M3AE_F32 = 0, M3AE_BF16 = 1 };
@@ -860,6 +863,55 @@ int m3ae_vqa_eval(const void* logits, int64_t ld, const float* targets, int64_t 
 int m3ae_seq_match(const int64_t* gen, int64_t ldg, int64_t Lg, const int64_t* ref, int64_t ldr, int64_t Lr, const int64_t* skip,
                    int64_t ns, const int32_t* types, int64_t B, int32_t* match, double* rec, void* workspace,
                    int64_t workspace_bytes, void* stream);
+/* m3ae_vqa_label_eval: the same record from LABELS (answer-list decoding, below: a generator head's output is a list entry).
+ *   labels int64 [B]; targets fp32 [B][C] with row stride ldt >= C (required); per row hit1 = hitk = targets[r][labels[r]], added
+ *   onto rec through the same fold (types, rec, workspace as m3ae_vqa_eval; rec is required).  A label outside [0, C) scores 0 and
+ *   sets err[0] = 1 (int64, required): a label is turned into an address only after that check.  hit1: optional fp32 [B].
+ *   M3AE_ERR_ARG: NULL labels / targets / rec / err, B < 1, C < 1.  M3AE_ERR_UNSUPPORTED: C >= 2^31, B >= 2^31, ldt < C, a missing or
+ *   short workspace.  M3AE_ERR_ALIGN: a pointer off its element size. */
+int m3ae_vqa_label_eval(const int64_t* labels, const float* targets, int64_t ldt, const int32_t* types, int64_t B, int64_t C,
+                        float* hit1, double* rec, int64_t* err, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Answer-list decoding (csrc/answer_trie.hip; ABI 4, additive): greedy search of a generator head constrained to a prefix trie of
+ * candidate answers, so that every output is a list entry (a label) and arrives with its log-probability.  No atomics, every
+ * reduction in a fixed order: two calls on the same inputs give the same bits, the score included.
+ *
+ * The trie, in device memory, int32: child_off [N + 1], child_tok [E] (ascending within a node), child_node [E], leaf_label [N]
+ *   (the label at the node behind an end token, -1 elsewhere); node 0 is the root; the children of node n are entries
+ *   child_off[n] .. child_off[n + 1] - 1.  The caller checks the table (tokens < V, every non-leaf node has a child); the kernels
+ *   turn no table value into an address without a range check and report a row they cannot advance through err.
+ *
+ * m3ae_trie_scan: logits [R][V], dtype M3AE_F32 or M3AE_BF16, row stride ld >= V in elements, element-aligned base, columns
+ *   [V, ld) never read (as m3ae_greedy_argmax).  node int32 [R]: the row's trie node; finished int32 [R]: nothing of a row with
+ *   a nonzero word is read or written.  chunk: columns per workgroup, 0 = 8192, 64 <= chunk <= 65536.  Per row, chunks + 1
+ *   workgroups: one per vocabulary chunk writes the chunk's (m, s) = (maximum, sum of e(x, m)) in fp32 (the arithmetic of
+ *   m3ae_token_eval) to workspace; one gathers the logits at the child tokens of the row's node, however many, and writes the
+ *   greatest order key (monotone image of the value) << 32 | (2^32 - 1 - child position): the greatest value, the lowest token
+ *   among equal values (+0 == -0), any NaN above every number -- torch.argmax's rule restricted to the allowed columns.
+ *   workspace: m3ae_trie_workspace_bytes(R, V, chunk) bytes (0 for shapes the call rejects), 8-byte aligned.
+ *   M3AE_ERR_ARG: a NULL pointer, R < 1, V < 1, ld < V, chunk < 0, N < 1, E < 1.  M3AE_ERR_UNSUPPORTED: another dtype, chunk outside
+ *   its bounds, V, N or E >= 2^31, R * (chunks + 1) >= 2^31.  M3AE_ERR_ALIGN: a pointer off its element size.  M3AE_ERR_WORKSPACE:
+ *   a missing, misaligned or short workspace.
+ * m3ae_trie_step: one search step at position pos (0 <= pos < max_len) from the workspace of m3ae_trie_scan on the same logits
+ *   (nch = chunks per row).  For an open row: lse = m + logf(s) of the row's pairs folded in ascending chunk order; tok and the
+ *   next node come from the child position the key decodes to; score[r] += (double)(x[tok] - lse) with the difference in fp32;
+ *   seq[r][pos] = last_tok[r] = tok; node[r] = the next node; if leaf_label[node] >= 0 then label[r] = it, len[r] = pos + 1 and
+ *   finished[r] = 1.  A finished row gets seq[r][pos] = pad and keeps node, score, label and last_tok.  open_count[pos] = rows
+ *   not finished after the step.  A non-finite row gives what torch.log_softmax gives, by the same arithmetic.  seq int64
+ *   [B][max_len]; len / label / last_tok int64 [B]; score double [B]; node / finished int32 [B]; open_count int32 [max_len]; err
+ *   int64 [1] is set to 1 when a node, a decoded child position, a token or a next node is outside its range (the row then
+ *   writes token 0, keeps node and score and stays open: never an address).
+ *   M3AE_ERR_ARG: a NULL pointer or a count outside its range.  M3AE_ERR_UNSUPPORTED / _ALIGN / _WORKSPACE as above. */
+int64_t m3ae_trie_workspace_bytes(int64_t R, int64_t V, int64_t chunk);
+int m3ae_trie_scan(const void* logits, int64_t ld, int64_t R, int64_t V, int64_t chunk, int dtype, const int32_t* child_off,
+                   const int32_t* child_tok, int64_t N, int64_t E, const int32_t* node, const int32_t* finished, void* workspace,
+                   int64_t workspace_bytes, void* stream);
+int m3ae_trie_step(const void* logits, int64_t ld, int dtype, const void* workspace, int64_t workspace_bytes, int64_t nch,
+                   const int32_t* child_off, const int32_t* child_tok, const int32_t* child_node, const int32_t* leaf_label, int64_t N,
+                   int64_t E, int64_t* seq, int64_t* len, int64_t* label, double* score, int64_t* last_tok, int32_t* node,
+                   int32_t* finished, int32_t* open_count, int64_t* err, int64_t B, int64_t V, int64_t max_len, int64_t pos,
+                   int64_t pad, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Device-side token evaluation (csrc/token_eval.hip; ABI 4, additive): what the reference's `Accuracy` metric computes for the MLM

@@ -18,6 +18,7 @@
 // s' = s1 e(m1, m') + s2 e(m2, m'); every s is a sum of terms in [0, 1], so there is no inf * 0.
 // m3ae_record_add: rec[0] += value[0], rec[1] += 1 in double (metrics.LossMean).
 #include "common.h"
+#include "lse_pair.h"
 #include "order_key.h"
 #include "topk_keep.h"
 #include <math.h>
@@ -42,12 +43,7 @@ DEVINL int row_state(const int64_t* __restrict__ labels, const uint8_t* __restri
     return label == T_IGNORE ? ROW_UNLABELLED : ROW_LABELLED;
 }
 
-DEVINL float exp_diff(float x, float m) { return x == m ? 1.0f : expf(x - m); }
-DEVINL void ms_merge(float& m, float& s, float m2, float s2) {
-    const float mn = fmaxf(m, m2);
-    s = s * exp_diff(m, mn) + s2 * exp_diff(m2, mn);
-    m = mn;
-}
+// exp_diff, ms_merge: csrc/lse_pair.h
 DEVINL uint64_t max_u64(uint64_t a, uint64_t b) { return a > b ? a : b; }
 
 // What a thread has gathered from its columns of the chunk.

@@ -13,6 +13,8 @@
 //   vqa_fold_kernel, one workgroup: thread t adds rows t, t + 256, ... in double, lanes then waves combine in a fixed tree, thread
 //   0 adds the nine sums onto the record and counts the call.  The order depends on B alone; no atomics.
 // m3ae_seq_match: one thread per row walks gen[r] and ref[r] with the skip ids dropped; then the same fold.
+// m3ae_vqa_label_eval: one thread per row reads targets[r][labels[r]] (answer-list decoding, csrc/answer_trie.hip: the prediction
+//   is a label already); then the same fold.
 #include "common.h"
 #include "order_key.h"
 #include "topk_keep.h"
@@ -167,6 +169,20 @@ __global__ __launch_bounds__(VT) void seq_match_kernel(const int64_t* __restrict
     rows[2 * r] = rows[2 * r + 1] = same ? 1.0f : 0.0f;
 }
 
+// rows[r] = {t, t} with t = targets[r][labels[r]]; a label outside [0, C) scores 0, sets err and is never an address
+__global__ __launch_bounds__(VT) void label_rows_kernel(const int64_t* __restrict__ labels, const float* __restrict__ targets, int64_t ldt,
+                                                        int64_t B, int64_t C, float* __restrict__ hit1_out, float* __restrict__ rows,
+                                                        int64_t* __restrict__ err) {
+    const int64_t r = (int64_t)blockIdx.x * VT + threadIdx.x;
+    if (r >= B) return;
+    const int64_t l = labels[r];
+    const bool ok = l >= 0 && l < C;
+    const float t = ok ? targets[r * ldt + l] : 0.0f;
+    if (!ok) err[0] = 1;
+    if (hit1_out) hit1_out[r] = t;
+    rows[2 * r] = rows[2 * r + 1] = t;
+}
+
 inline int64_t rows_bytes(int64_t B) { return B * 2 * (int64_t)sizeof(float); }
 
 }  // namespace
@@ -212,6 +228,20 @@ extern "C" int m3ae_seq_match(const int64_t* gen, int64_t ldg, int64_t Lg, const
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(seq_match_kernel, dim3((unsigned)cdiv(B, VT)), dim3(VT), 0, s, gen, ldg, Lg, ref, ldr, Lr, skip, (int)ns, B, match,
                        (float*)workspace);
+    hipLaunchKernelGGL(vqa_fold_kernel, dim3(1), dim3(VT), 0, s, (const float*)workspace, types, B, rec);
+    return hip_launch_status();
+}
+
+extern "C" int m3ae_vqa_label_eval(const int64_t* labels, const float* targets, int64_t ldt, const int32_t* types, int64_t B, int64_t C,
+                                   float* hit1, double* rec, int64_t* err, void* workspace, int64_t workspace_bytes, void* stream) {
+    if (!labels || !targets || !rec || !err || B < 1 || C < 1) return M3AE_ERR_ARG;
+    if (C > (int64_t)INT32_MAX || B > (int64_t)INT32_MAX || ldt < C) return M3AE_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < rows_bytes(B)) return M3AE_ERR_UNSUPPORTED;
+    if (((uintptr_t)labels & 7) || ((uintptr_t)targets & 3) || ((uintptr_t)types & 3) || ((uintptr_t)hit1 & 3) || ((uintptr_t)rec & 7) ||
+        ((uintptr_t)err & 7) || ((uintptr_t)workspace & 7))
+        return M3AE_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(label_rows_kernel, dim3((unsigned)cdiv(B, VT)), dim3(VT), 0, s, labels, targets, ldt, B, C, hit1, (float*)workspace, err);
     hipLaunchKernelGGL(vqa_fold_kernel, dim3(1), dim3(VT), 0, s, (const float*)workspace, types, B, rec);
     return hip_launch_status();
 }

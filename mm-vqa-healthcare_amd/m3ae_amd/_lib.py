@@ -188,6 +188,13 @@ _SIGS = {
     "m3ae_lora_merge": (C.c_int, [vp, i64, i64, f32, vp, vp, vp, vp, C.c_int, vp]),
     "m3ae_lora_grad_workspace_bytes": (i64, [vp, i64, i64]),
     "m3ae_lora_grad": (C.c_int, [vp, i64, i64, f32, vp, vp, vp, vp, vp]),
+    # answer-list decoding for the generator heads (ABI 4, additive): trie-constrained greedy with the path's log-probability;
+    # the VQA score record from labels
+    "m3ae_trie_workspace_bytes": (i64, [i64, i64, i64]),
+    "m3ae_trie_scan": (C.c_int, [vp, i64, i64, i64, i64, C.c_int, vp, vp, i64, i64, vp, vp, vp, i64, vp]),
+    "m3ae_trie_step": (C.c_int, [vp, i64, C.c_int, vp, i64, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64,
+                                 i64, i64, vp]),
+    "m3ae_vqa_label_eval": (C.c_int, [vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, i64, vp]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -57,6 +57,10 @@ DEFAULTS = dict(
     # (ATen argmax / compares / cat and one blocking `finished.all()` per token) | "device" (csrc/greedy.hip, no host round trip per
     # token; same tokens)
     decoder_search="host",
+    # how test() scores the generator heads with vqa_metrics="device" (m3ae_amd/trainer.py): "free" (token exact match of the free
+    # search alone, as before) | "list" (also answer-list decoding, csrc/answer_trie.hip: greedy search restricted to the answers
+    # of Trainer.set_answer_list, scored as labels with the closed / open VQA score).  "free" calls no new entry point.
+    answer_decoding="free",
     # where validation / test compute their metric (m3ae_amd/trainer.py, m3ae_amd/metrics.py): "host" (ATen float / argmax /
     # gather / sum: the overall VQA score alone) | "device" (csrc/vqa_eval.hip: overall, closed and open scores, the score within
     # the top `eval_topk` answers, and token exact match for the generator heads in test()).  eval_topk is honoured only with "device".
@@ -256,6 +260,17 @@ def decoder_search(cfg):
     return v
 
 
+ANSWER_DECODINGS = ("free", "list")
+
+
+def answer_decoding(cfg):
+    """The validated `answer_decoding` of a config dict (default "free")."""
+    v = cfg.get("answer_decoding", "free")
+    if not isinstance(v, str) or v not in ANSWER_DECODINGS:
+        raise ValueError(f"answer_decoding must be one of {ANSWER_DECODINGS}, got {v!r}")
+    return v
+
+
 VQA_METRICS = ("host", "device")
 
 
@@ -302,6 +317,7 @@ def resolve_arch(cfg):
     cfg = dict(cfg)
     optim_type(cfg)
     decoder_search(cfg)
+    answer_decoding(cfg)
     vqa_metrics(cfg)
     pretrain_metrics(cfg)
     if "gradient_clip_val" in cfg:

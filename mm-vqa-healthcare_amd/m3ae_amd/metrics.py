@@ -118,6 +118,17 @@ class VQARADScore(_DeviceRecordMetric):
         return ops.vqa_eval(logits.detach(), target.detach(), types_tensor(types, logits.device), self.rec,
                             k=min(self.k, logits.shape[1]), want_rows=want_rows)
 
+    def update_labels(self, labels, target, types=None, want_rows=False):
+        """The same update from LABELS (answer-list decoding of a generator head, ops.vqa_label_eval): labels int64 [B] on the
+        device, target fp32 [B, C]; a row adds target[r, labels[r]] as its score and its score within the top-k alike.  A label
+        outside [0, C) scores 0 and sets `self.label_err` (int64 [1] on the device).  Enqueues only."""
+        if target.dtype != torch.float32:
+            target = target.float()
+        if getattr(self, "label_err", None) is None:
+            self.label_err = torch.zeros((1,), dtype=torch.int64, device=labels.device)
+        return ops.vqa_label_eval(labels.detach().contiguous(), target.detach(), types_tensor(types, labels.device), self.rec,
+                                  err=self.label_err, want_rows=want_rows)
+
 
 class TokenExactMatch(_DeviceRecordMetric):
     """Exact match of generated token ids against reference token ids with the ids of `skip` (pad / start / end) dropped from both

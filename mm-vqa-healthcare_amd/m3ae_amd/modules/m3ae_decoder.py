@@ -24,6 +24,8 @@ T <= 12 tokens against 2 (CLS) or 2 + 577 + 32 encoder tokens -- a few % of the 
 reference's dropout sites with the library's counter-hash masks.
 Greedy search: `search_path` (host bookkeeping, the default) or, with `decoder_search=device` / `search="device"`, the same
 search with argmax and bookkeeping on the GPU (`search_path_async`, csrc/greedy.hip); `DecoderModel.generate` wraps either.
+Answer-list decoding: `answer_path_async` restricts that search to a prefix trie of candidate answers (answer_trie.py,
+csrc/answer_trie.hip) and returns labels with log-probabilities; `DecoderModel.answer` / `answer_async` wrap it.
 Tokenisation happens outside (`batch["decoder_tokens"]`: int64 [B, T] = [CLS] answer [SEP] [PAD]...) or through a
 `tokenizer` callable; string metrics (ROUGE / BLEU / exact match) stay out of scope.
 """
@@ -260,6 +262,37 @@ class Decoder(nn.Module):
 
     @torch.no_grad()
     @ops.model_mode
+    def answer_path_async(self, cross_attn_feats, trie, cls_id=101, pad_id=0, lookahead=2, chunk=0):
+        """Answer-list decoding (csrc/answer_trie.hip): the loop of `search_path_async` with every step's token restricted to the
+        continuations `trie` (m3ae_amd.answer_trie.AnswerTrie) allows, so that every row ends as an entry of the answer list.
+        Per step the decoder row, the vocabulary GEMM, ops.trie_scan and ops.trie_step are enqueued with no blocking host call.
+        At most trie.depth steps.  Returns a namespace with `label` int64 [B] (the list entry), `score` float64 [B] (the sum of
+        the chosen tokens' log-probabilities under the unconstrained softmax), `seq` int64 [B, max_len], `len` int64 [B], `err`
+        int64 [1] (nonzero: the table led a row out of its range), `out` (the five in one buffer), `steps` and `state`
+        (ops.TrieState).  Greedy on a trie: the entry found is not always the list's most probable one."""
+        B, dev = cross_attn_feats.shape[0], cross_attn_feats.device
+        D = self.target_embedding.weight.shape[1]
+        dt = trie.to_device(dev, self.final_linear.weight.shape[0], self.max_len)
+        depth = dt.depth
+        watch = ops.OpenCountWatch(depth, lookahead or None)   # None or 0: no early exit, all `depth` steps
+        enc_kv = self.dec_layers[self.num_layers - 1].cross_kv(cross_attn_feats.to(self.head_dtype))
+        cache = torch.empty((B, self.max_len, 2 * D), dtype=self.head_dtype, device=dev)
+        st = ops.TrieState(B, self.max_len, dev, cls_id, pad_id)
+        pe_rows = self.positional_encoding.pe[0, :depth].to(torch.float32)[:, None, :].expand(depth, B, D).contiguous()
+        ws, steps = None, 0
+        for pos in range(depth):
+            logits = self.step_logits(st.last_tok.view(B, 1), pos, enc_kv, cache, pe_rows[pos])
+            if ws is None:
+                ws = ops.trie_workspace(B, logits.shape[-1], dev, chunk)
+            ops.trie_scan(logits, dt, st, chunk, ws)
+            ops.trie_step(logits, dt, st, ws, pos, pad_id, chunk)
+            steps += 1
+            if watch.enqueued(st.open_count, pos):
+                break
+        return NS(label=st.label, score=st.score, seq=st.seq, len=st.len, err=st.err, out=st.out, steps=steps, state=st)
+
+    @torch.no_grad()
+    @ops.model_mode
     def search_path(self, cross_attn_feats, cls_id=101, sep_id=102, eos_id=None, pad_id=0, use_cache=True, search="host",
                     lookahead=2):
         """m3ae_decoder.py:141-182: greedy decoding.  The reference re-runs the whole prefix every step; here a step is one
@@ -303,6 +336,22 @@ class Decoder(nn.Module):
         after = (special.long().cumsum(1) - special.long()) > 0  # strictly after the first special token
         seq = torch.where(after, torch.full_like(seq, pad_id), seq)
         return torch.nn.functional.pad(seq, (0, self.max_len - seq.shape[1]), value=pad_id)
+
+
+def answer_result(r, label2ans=None):
+    """One copy of an answer-list search's `out` buffer (Decoder.answer_path_async, T5.constrained_greedy_async) -> (labels int64
+    [B], scores float64 [B]) on the host; raises if the error word is set.  With label2ans: a list of (answer, score) through
+    label2ans[str(label)] (m3ae_module.answers_of's rule)."""
+    out = r.out.cpu()
+    if int(out[-1]) != 0:
+        raise ops._lib.M3AEHipError("answer-list decoding: the answer table led a row out of its range")
+    B = r.label.shape[0]
+    n = r.seq.numel()
+    labels, scores = out[n + B:n + 2 * B].clone(), out[n + 2 * B:n + 3 * B].view(torch.float64).clone()
+    if label2ans is None:
+        return labels, scores
+    from .m3ae_module import answers_of
+    return [row[0] for row in answers_of([[l] for l in labels.tolist()], [[s] for s in scores.tolist()], label2ans)]
 
 
 class DecoderModel(_Base):
@@ -413,6 +462,22 @@ class DecoderModel(_Base):
         if self.store is None:
             raise RuntimeError("call finalize(device) before the first forward")
         return self.decoder.search_path_async(self.features(batch), self.cls_id, self.sep_id, None, self.pad_id, lookahead)
+
+    @ops.model_mode
+    def answer_async(self, batch, trie, lookahead=2):
+        """The features of `batch` and answer-list decoding over them (Decoder.answer_path_async), nothing copied to the host:
+        its namespace (`label`, `score`, `seq`, `len`, `err`, `out`, `steps`, `state`)."""
+        if self.store is None:
+            raise RuntimeError("call finalize(device) before the first forward")
+        return self.decoder.answer_path_async(self.features(batch), trie, self.cls_id, self.pad_id, lookahead)
+
+    @ops.model_mode
+    def answer(self, batch, trie, label2ans=None):
+        """The answer of every sample as an entry of the list `trie` was built from: (labels int64 [B], scores float64 [B]: the
+        log-probability of the entry's tokens), both on the host after ONE copy.  With label2ans (the reference's mapping with
+        string keys, as M3AETransformerSS.answers): a list of B (answer, score) instead."""
+        r = self.answer_async(batch, trie)
+        return answer_result(r, label2ans)
 
     @ops.model_mode
     def generate(self, batch, search=None):

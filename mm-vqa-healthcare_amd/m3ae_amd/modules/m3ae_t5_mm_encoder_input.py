@@ -146,6 +146,22 @@ class T5VQA_MMEncoderInput(_Base):
             enc = self.t5.encoder(self.prepare_inputs(batch)["inputs_embeds"])
         return self.t5.generate_async(enc, num_beams=4, max_length=self.max_answer_length, lookahead=lookahead)
 
+    @ops.model_mode
+    def answer_async(self, batch, trie, lookahead=2):
+        """The encoder output of `batch` and answer-list decoding over it (T5ForConditionalGeneration.constrained_greedy_async:
+        one beam, greedy on the trie), nothing copied to the host: its namespace (`label`, `score`, `seq`, `len`, `err`, ...)."""
+        if self.store is None:
+            raise RuntimeError("call finalize(device) before the first forward")
+        with torch.no_grad():
+            enc = self.t5.encoder(self.prepare_inputs(batch)["inputs_embeds"])
+        return self.t5.constrained_greedy_async(enc, trie, max_length=self.max_answer_length, lookahead=lookahead)
+
+    @ops.model_mode
+    def answer(self, batch, trie, label2ans=None):
+        """As DecoderModel.answer: (labels, scores) on the host after one copy, or (answer, score) pairs with label2ans."""
+        from .m3ae_decoder import answer_result
+        return answer_result(self.answer_async(batch, trie), label2ans)
+
     def training_step(self, batch, batch_idx=0):
         """m3ae_t5_mm_encoder_input.py:340-346."""
         self.current_tasks = [k for k, v in self.m3ae.hparams.config["loss_names"].items() if v > 0]

@@ -324,6 +324,32 @@ class T5ForConditionalGeneration(nn.Module):
         return NS(seq=st.seq, len=st.len, err=st.err, out=st.out, steps=steps, state=st)
 
     @torch.no_grad()
+    def constrained_greedy_async(self, enc, trie, max_length=12, pad_token_id=0, lookahead=2, chunk=0):
+        """Answer-list decoding (csrc/answer_trie.hip): greedy search over `next_token_logits_cached` with one beam (no cache
+        re-ordering), every step's token restricted to the continuations `trie` (m3ae_amd.answer_trie.AnswerTrie, sequences
+        ending in </s>) allows.  At most trie.depth <= max_length steps, no blocking host call.  Returns the namespace of
+        Decoder.answer_path_async: `label` int64 [B], `score` float64 [B] (sum of log-probabilities), `seq` int64
+        [B, max_length] (the generated tokens, WITHOUT the start token; pad after the end token), `len`, `err`, `out`, `steps`,
+        `state`.  Constrained BEAM search is not implemented."""
+        B, dev = enc.shape[0], enc.device
+        dt = trie.to_device(dev, self.config.vocab_size, max_length)
+        watch = ops.OpenCountWatch(dt.depth, lookahead or None)   # None or 0: no early exit, all `depth` steps
+        cross_kv = [kv.view(B, enc.shape[1], -1).reshape(B * enc.shape[1], -1) for kv in self.decoder.cross_kv(enc)]
+        self_cache = self.decoder.new_self_cache(B, max_length, enc.dtype, dev)
+        st = ops.TrieState(B, max_length, dev, self.config.decoder_start_token_id, pad_token_id)
+        ws, steps = None, 0
+        for pos in range(dt.depth):
+            logits = self.next_token_logits_cached(enc, st.last_tok.view(B, 1), cross_kv, self_cache, pos)
+            if ws is None:
+                ws = ops.trie_workspace(B, logits.shape[-1], dev, chunk)
+            ops.trie_scan(logits, dt, st, chunk, ws)
+            ops.trie_step(logits, dt, st, ws, pos, pad_token_id, chunk)
+            steps += 1
+            if watch.enqueued(st.open_count, pos):
+                break
+        return NS(label=st.label, score=st.score, seq=st.seq, len=st.len, err=st.err, out=st.out, steps=steps, state=st)
+
+    @torch.no_grad()
     def generate(self, enc, num_beams=4, max_length=12, eos_token_id=1, pad_token_id=0, length_penalty=1.0,
                  len_offset=0, beam_search="host", lookahead=2):
         """HF `generate(encoder_outputs=..., num_beams, early_stopping=True, max_length)` as the reference calls it

@@ -2187,6 +2187,88 @@ def greedy_step(st, keys, V, pos, sep_id, eos_id, pad_id):
 
 
 # ------------------------------------------------------------------------------------------------------------
+# answer-list decoding (csrc/answer_trie.hip): Decoder.answer_path_async, T5.constrained_greedy_async
+# ------------------------------------------------------------------------------------------------------------
+TRIE_CHUNK = 8192   # vocabulary elements per workgroup of m3ae_trie_scan when the caller passes chunk=0
+
+
+def trie_workspace(R, V, device, chunk=0):
+    """The workspace of trie_scan / trie_step: int64 [R, 1 + chunks of a row] words (the child keys, then the (m, s) pairs)."""
+    n = _lib.lib().m3ae_trie_workspace_bytes(R, V, chunk)
+    if n <= 0:
+        raise ValueError(f"trie_workspace: R={R}, V={V}, chunk={chunk} is not a shape m3ae_trie_scan takes")
+    return torch.empty((R, n // (8 * R)), dtype=torch.int64, device=device)
+
+
+class TrieState:
+    """The device state of one answer-list search (include/m3ae_hip.h, m3ae_trie_step): allocated once per call.  `trie` is what
+    AnswerTrie.to_device returned."""
+
+    def __init__(self, B, max_len, device, start_id=101, pad_id=0):
+        self.B, self.max_len = B, max_len
+        n = B * max_len
+        # seq | len | label | score (the bits of float64) | error word: one copy brings all five to the host
+        self.out = torch.zeros((n + 3 * B + 1,), dtype=torch.int64, device=device)
+        self.seq, self.len, self.label = self.out[:n].view(B, max_len), self.out[n:n + B], self.out[n + B:n + 2 * B]
+        self.score, self.err = self.out[n + 2 * B:n + 3 * B].view(torch.float64), self.out[-1:]
+        self.seq.fill_(pad_id)
+        self.len.fill_(max_len)
+        self.label.fill_(-1)
+        self.last_tok = torch.full((B,), start_id, dtype=torch.int64, device=device)
+        self.node = torch.zeros((B,), dtype=torch.int32, device=device)
+        self.finished = torch.zeros((B,), dtype=torch.int32, device=device)
+        self.open_count = torch.zeros((max_len,), dtype=torch.int32, device=device)
+
+
+def _trie_logits(what, logits, st):
+    _need_cuda(logits)
+    _need_cuda(st.out)
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{what} takes fp32 or bf16 logits")
+    if logits.dim() != 2 or logits.shape[0] != st.B or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
+        raise ValueError(f"{what}: logits {tuple(logits.shape)} with strides {tuple(logits.stride())} for {st.B} rows")
+
+
+def _trie_ws(what, ws, B, V, chunk):
+    need = _lib.lib().m3ae_trie_workspace_bytes(B, V, chunk)
+    if need <= 0:
+        raise ValueError(f"{what}: B={B}, V={V}, chunk={chunk} is not a shape m3ae_trie_scan takes")
+    if ws.dtype != torch.int64 or not ws.is_contiguous() or not ws.is_cuda or ws.numel() * 8 < need:
+        raise ValueError(f"{what}: ws is the int64 buffer of trie_workspace")
+    return need // (8 * B) - 1
+
+
+def trie_scan(logits, trie, st, chunk=0, ws=None):
+    """logits fp32 or bf16 [B, V] (row stride >= V, unit column stride), read once: per open row of `st` the (m, s) pair of every
+    vocabulary chunk and the greatest order key among the children of the row's trie node, into `ws`.  Returns ws."""
+    _trie_logits("trie_scan", logits, st)
+    B, V = logits.shape
+    chunk = int(chunk)
+    if chunk != 0 and not 64 <= chunk <= 65536:
+        raise ValueError(f"trie_scan: chunk={chunk} is neither 0 nor in [64, 65536]")
+    if ws is None:
+        ws = trie_workspace(B, V, logits.device, chunk)
+    _trie_ws("trie_scan", ws, B, V, chunk)
+    check(_lib.lib().m3ae_trie_scan(_p(logits), logits.stride(0), B, V, chunk, _dt(logits), _p(trie.child_off), _p(trie.child_tok), trie.N,
+                                    trie.E, _p(st.node), _p(st.finished), _p(ws), ws.numel() * 8, _stream()), "m3ae_trie_scan")
+    return ws
+
+
+def trie_step(logits, trie, st, ws, pos, pad_id, chunk=0):
+    """One step of the search on `st` at position pos from the workspace trie_scan filled from the same logits (same chunk):
+    token, next node, score += log-probability, label / len / finished at a leaf; st.open_count[pos] = rows still open."""
+    _trie_logits("trie_step", logits, st)
+    B, V = logits.shape
+    nch = _trie_ws("trie_step", ws, B, V, int(chunk))
+    if not 0 <= pos < st.max_len:
+        raise ValueError(f"trie_step: pos {pos} outside [0, {st.max_len})")
+    check(_lib.lib().m3ae_trie_step(_p(logits), logits.stride(0), _dt(logits), _p(ws), ws.numel() * 8, nch, _p(trie.child_off),
+                                    _p(trie.child_tok), _p(trie.child_node), _p(trie.leaf_label), trie.N, trie.E, _p(st.seq), _p(st.len),
+                                    _p(st.label), _p(st.score), _p(st.last_tok), _p(st.node), _p(st.finished), _p(st.open_count), _p(st.err),
+                                    B, V, st.max_len, pos, pad_id, _stream()), "m3ae_trie_step")
+
+
+# ------------------------------------------------------------------------------------------------------------
 # device-side VQA evaluation (csrc/vqa_eval.hip): m3ae_amd/metrics.py, M3AETransformerSS.predict
 # ------------------------------------------------------------------------------------------------------------
 class VqaRows(NamedTuple):
@@ -2275,6 +2357,38 @@ def seq_match(gen, ref, skip, types, rec, want_rows=False):
                                     _p(skip) if skip.shape[0] else None, skip.shape[0], _p(types), B, _p(match), _p(rec), _p(ws),
                                     ws.numel() * 4, _stream()), "m3ae_seq_match")
     return match
+
+
+class LabelRows(NamedTuple):
+    """The per-row outputs of vqa_label_eval(want_rows=True)."""
+    hit1: torch.Tensor                 # fp32 [B]: targets[r, labels[r]] (0 for a label outside [0, C))
+    err: torch.Tensor                  # int64 [1]: 1 after a label outside [0, C)
+
+
+def vqa_label_eval(labels, targets, types, rec, err=None, want_rows=False):
+    """One update of the VQA score record from LABELS (answer-list decoding: a generator head's output is a list entry), enqueued
+    on the current stream (no host sync).  labels int64 [B]; targets fp32 [B, C] (unit column stride); types and rec as vqa_eval
+    (rec is required).  Adds {n, t, t} with t = targets[r, labels[r]] onto rec.  err: an int64 [1] device word that is set to 1
+    by a label outside [0, C) (such a row scores 0); a fresh one is made when None.  Returns err, or LabelRows with want_rows."""
+    _need_cuda(labels)
+    _need_cuda(targets)
+    if labels.dtype != torch.int64 or labels.dim() != 1 or labels.shape[0] < 1 or not labels.is_contiguous():
+        raise ValueError(f"vqa_label_eval: labels int64 [B], contiguous; got {labels.dtype} {tuple(labels.shape)}")
+    B = labels.shape[0]
+    if targets.dtype != torch.float32 or targets.dim() != 2 or targets.shape[0] != B or targets.shape[1] < 1 or targets.stride(1) != 1 \
+            or targets.stride(0) < targets.shape[1]:
+        raise ValueError(f"vqa_label_eval: targets fp32 [{B}, C], unit column stride; got {targets.dtype} {tuple(targets.shape)}")
+    if rec is None:
+        raise ValueError("vqa_label_eval: rec is required (ops.vqa_record)")
+    ws = _eval_common("vqa_label_eval", B, types, rec, labels.device)
+    if err is None:
+        err = torch.zeros((1,), dtype=torch.int64, device=labels.device)
+    elif err.dtype != torch.int64 or err.numel() != 1 or not err.is_cuda:
+        raise ValueError("vqa_label_eval: err int64 [1] on the device")
+    hit1 = torch.empty((B,), dtype=torch.float32, device=labels.device) if want_rows else None
+    check(_lib.lib().m3ae_vqa_label_eval(_p(labels), _p(targets), targets.stride(0), _p(types), B, targets.shape[1], _p(hit1), _p(rec),
+                                         _p(err), _p(ws), ws.numel() * 4, _stream()), "m3ae_vqa_label_eval")
+    return LabelRows(hit1, err) if want_rows else err
 
 
 # ------------------------------------------------------------------------------------------------------------

@@ -56,6 +56,7 @@ from . import config as config_mod
 from . import metrics as metrics_mod
 from . import ops, synth
 from .ddp import FlatGradReducer
+from .modules.objectives import build_vqa_targets
 
 
 def log(msg, rank=0):
@@ -165,6 +166,10 @@ class Trainer:
         # and token exact match in test() for the generator heads).  metrics / exact_match: the result() dicts of the last pass.
         self.vqa_metrics = config_mod.vqa_metrics(cfg)
         self.metrics, self.exact_match = None, None
+        # config key `answer_decoding`: "free" | "list" (test() with vqa_metrics="device" and a generator head also decodes on
+        # `answer_trie`, an answer_trie.AnswerTrie: set_answer_list or assign it).  answer_metrics: its result() dict of the last pass.
+        self.answer_decoding = config_mod.answer_decoding(cfg)
+        self.answer_trie, self.answer_metrics = None, None
         # config key `pretrain_metrics`: "host" (nothing beyond the monitored loss) | "device" (metrics.PretrainMetrics);
         # pretrain: its result() dict of the last pass
         self.pretrain_metrics = config_mod.pretrain_metrics(cfg)
@@ -261,6 +266,31 @@ class Trainer:
             return metrics_mod.TokenExactMatch((c.pad_token_id, c.decoder_start_token_id, c.eos_token_id), self.device), m.labels_of
         return None, None
 
+    def set_answer_list(self, label2ans):
+        """Builds `answer_trie` for answer_decoding="list" from the data set's answer list through the model's tokenizer: label2ans
+        is the reference's mapping with string keys ("0" .. str(n - 1)) or a list of answers; entry i becomes label i.  The
+        decoder head's sequences end in [SEP], the T5 head's in </s>."""
+        from .answer_trie import AnswerTrie
+        m = self.model
+        tok = getattr(m, "tokenizer", None)
+        if tok is None or not (hasattr(m, "tokens_of") or hasattr(m, "labels_of")):
+            raise ValueError("set_answer_list needs a generator head constructed with a tokenizer; assign trainer.answer_trie otherwise")
+        answers = [label2ans[str(i)] for i in range(len(label2ans))] if isinstance(label2ans, dict) else list(label2ans)
+        end = m.sep_id if hasattr(m, "tokens_of") else m.t5.config.eos_token_id
+        ids = []
+        for a in answers:
+            t = [int(v) for v in tok(a, add_special_tokens=False).input_ids]
+            ids.append(t[:-1] if t and t[-1] == end else t)
+        self.answer_trie = AnswerTrie.from_answers(ids, end)
+        return self.answer_trie
+
+    def answer_text(self):
+        """` answer_list X (n) closed Y (n) open Z (n)` of the last test pass ("" unless answer_decoding="list" ran)."""
+        r = self.answer_metrics
+        if r is None:
+            return ""
+        return f" answer_list {r['score']:.4f} ({r['n']}) closed {r['closed']:.4f} ({r['n_closed']}) open {r['open']:.4f} ({r['n_open']})"
+
     def pretrain_text(self):
         """`mlm acc X (n) @k Y ppl Z | itm acc X (n) | mim loss X` of the last pass ("" with pretrain_metrics="host")."""
         r = self.pretrain
@@ -300,7 +330,13 @@ class Trainer:
         device_metrics = self.vqa_metrics == "device"
         score = metrics_mod.VQARADScore(self.device, k=self.cfg.get("eval_topk", 5)) if device_metrics and hasattr(self.model, "vqa_head_forward") else None
         em, refs_of = self._generator_metric() if device_metrics and generate else (None, None)
-        pre = None      # pretrain_metrics="device": built at the first batch that brings a pre-training objective
+        ans = ans_err = None    # answer_decoding="list": the generator head's answers as labels, scored like the classification head's
+        if em is not None and self.answer_decoding == "list":
+            if self.answer_trie is None:
+                raise ValueError('answer_decoding="list" needs trainer.answer_trie: call set_answer_list(label2ans) or assign an AnswerTrie')
+            ans = metrics_mod.VQARADScore(self.device, k=0)
+            ans_err = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        pre = None     # pretrain_metrics="device": built at the first batch that brings a pre-training objective
         fed = 0
         with torch.no_grad():
             for batch in self.dm.val_batches():
@@ -325,11 +361,21 @@ class Trainer:
                     s = -self._loss(batch).float() * n
                     if em is not None:
                         em.update(self.model.generate_async(batch).seq, refs_of(batch), batch.get("answer_types"))
+                    if ans is not None:     # enqueued; read once below
+                        r = self.model.answer_async(batch, self.answer_trie)
+                        ans_err += r.err
+                        ans.update_labels(r.label, build_vqa_targets(batch, self.cfg["vqa_label_size"], self.device), batch.get("answer_types"))
                 tot += s
                 cnt += n
         self.model.train()
         if em is not None:
             self.exact_match = em.result()
+        if ans is not None:
+            self.answer_metrics = ans.result()
+            if getattr(ans, "label_err", None) is not None:
+                ans_err += ans.label_err
+            if int(ans_err.cpu()) != 0:
+                raise ops._lib.M3AEHipError("answer-list decoding: a row left the answer table, or a label is outside [0, vqa_label_size)")
         if pre is not None:
             self.pretrain = pre.result()     # one all-reduce and one blocking copy for all of them
         if fed:
@@ -420,7 +466,7 @@ class Trainer:
         if self.exact_match is not None:
             r = self.exact_match
             em = f" token_exact_match {r['score']:.4f} ({r['n']}) closed {r['closed']:.4f} ({r['n_closed']}) open {r['open']:.4f} ({r['n_open']})"
-        log(f"test/the_metric{' (ema)' if self.validated_on_ema else ''} {m:.4f}{self.metrics_text()}{em}", self.rank)
+        log(f"test/the_metric{' (ema)' if self.validated_on_ema else ''} {m:.4f}{self.metrics_text()}{em}{self.answer_text()}", self.rank)
         return m
 
 

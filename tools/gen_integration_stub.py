@@ -95,6 +95,10 @@ SECTIONS = {
         "# LoRA, merged form (ABI 4, additive): W = W0 + s B A into master and shadow; dA, dB from the full dW; one table of targets",
         (("LORA_MAX_RANK, LORA_MAX_TARGETS, LORA_PANEL_ROWS", "     # bounds on r and ntargets; rows of one row panel of the projection"),),
         ("m3ae_lora_merge", "m3ae_lora_grad_workspace_bytes", "m3ae_lora_grad")),
+    "ANSWER_TRIE_ENTRIES": Section(
+        "# answer-list decoding (ABI 4, additive): greedy on a prefix trie of the candidate answers + the path's log-probability; label scoring",
+        (),
+        ("m3ae_trie_workspace_bytes", "m3ae_trie_scan", "m3ae_trie_step", "m3ae_vqa_label_eval")),
 }
 globals().update({key: s.entries for key, s in SECTIONS.items() if s.entries})   # MAP_ENTRIES, DET_ENTRIES, ...: views of the table
 
