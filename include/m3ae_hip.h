@@ -69,6 +69,9 @@ extern "C" {
 /* 4 (additive): answer-list decoding for the generator heads.  m3ae_trie_scan (+ m3ae_trie_workspace_bytes) and m3ae_trie_step
  *    (csrc/answer_trie.hip): greedy search constrained to a prefix trie of the candidate answers, with the log-probability of the
  *    chosen path; m3ae_vqa_label_eval (csrc/vqa_eval.hip): the score record from labels instead of logits; no descriptor changed. */
+/* 4 (additive): constrained beam search on the answer list.  m3ae_triebeam_select and m3ae_triebeam_step (csrc/trie_beam.hip): the
+ *    BeamSearchScorer of m3ae_beam_step with the trie as the prefix constraint and an n-best list of labels with scores as the
+ *    result; m3ae_vqa_labels_eval (csrc/vqa_eval.hip): the score record from n-best labels; no descriptor changed. */
 #define M3AE_ABI_VERSION 4
 
 enum { M3AE_F32 = 0, M3AE_BF16 = 1 };
@@ -912,6 +915,65 @@ int m3ae_trie_step(const void* logits, int64_t ld, int dtype, const void* worksp
                    int64_t E, int64_t* seq, int64_t* len, int64_t* label, double* score, int64_t* last_tok, int32_t* node,
                    int32_t* finished, int32_t* open_count, int64_t* err, int64_t B, int64_t V, int64_t max_len, int64_t pos,
                    int64_t pad, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Constrained beam search on the answer list (csrc/trie_beam.hip; ABI 4, additive): transformers-4.6.0 `beam_search` +
+ * `BeamSearchScorer` (as m3ae_beam_step) with the trie above as the prefix constraint; the result of a sample is an n-best list of
+ * labels with scores.  Log-probabilities come from the UNCONSTRAINED softmax; a token the trie does not allow is not a candidate.
+ * No atomics: two calls on the same inputs give the same bits.
+ *
+ * Rows and state.  R = B * nb beam rows, 1 <= nb <= 8, row b * nb + k is slot k of sample b.  Per row: node int32 (-1 = a DEAD
+ *   slot), beam_score fp32, last_tok int64.  At the start slot 0 of every sample is at the root (node 0) with score 0 and slots 1..
+ *   are dead; a dead slot contributes no candidate (there is no -1e9 trick).  m3ae_trie_scan runs unchanged over the R rows with
+ *   the dead flags (int32 [R], written by the step) as its `finished` argument: nothing of a dead row is read.
+ * Candidates of a sample: the children of its live beams' nodes.  lse of a row = m + logf(s) of its (m, s) pairs folded in
+ *   ascending chunk order (as m3ae_trie_step); score = fl(fl(x[tok] - lse) + beam_score) in fp32.  The best min(2 nb, candidates)
+ *   are kept, by rounded score descending, then (beam, entry) ascending -- which is (beam, token) ascending, tokens ascend within a
+ *   node; +0 == -0, any NaN ranks above every number.
+ * m3ae_triebeam_select: logits [R][V] as m3ae_trie_scan (fp32 or bf16, row stride ld >= V, element-aligned base), workspace = the
+ *   one m3ae_trie_scan filled from the same logits with the same chunk (m3ae_trie_workspace_bytes(R, V, chunk) bytes).  One
+ *   workgroup of 256 threads per sample.  Outputs: top_s fp32 [B][2 nb], top_beam int32 [B][2 nb] (the slot, 0 .. nb - 1), top_edge
+ *   int32 [B][2 nb] (the entry of child_tok / child_node), n_cand int32 [B] (the number kept); unused slots carry score 0, beam -1
+ *   and entry -1.  err int64 [1] is set to 1 by a live node outside [0, N) or without a child range and by a token outside [0, V):
+ *   such a candidate is skipped and never turned into an address.
+ *   M3AE_ERR_ARG: a NULL pointer, B < 1, V < 1, ld < V, chunk < 0, N < 1, E < 1.  M3AE_ERR_UNSUPPORTED: another dtype, nb outside
+ *   [1, 8], nb * E >= 2^31, N >= 2^31, or (B * nb, V, chunk) not a shape m3ae_trie_scan takes.  M3AE_ERR_ALIGN: a pointer off its
+ *   element size.  M3AE_ERR_WORKSPACE: a missing, misaligned or short workspace.
+ * m3ae_triebeam_step: one step at position pos (0 <= pos < max_len); div = (pos + 1) ** length_penalty > 0 (HF's cur_len
+ *   divisor, computed by the caller).  One thread per sample walks the candidates in rank order.  A candidate whose next node is a
+ *   leaf (leaf_label >= 0) is skipped at rank >= nb; at rank < nb it pushes (score / div in double, score, label, pos + 1) into the
+ *   sample's hypothesis list (scores descending, a new entry after equal scores, cut to nb).  Other candidates fill the next beam
+ *   slots (beam_score, last_tok, order = the source row, node = the next node) until nb are filled; the remaining slots become dead:
+ *   node -1, beam_score 0, last_tok = pad, order = b * nb (always a valid row and a valid embedding index).  A sample is done once
+ *   it holds nb hypotheses or has no live beam; all slots of a done sample are dead.  open_count[pos] = samples not done.  Every
+ *   path ends within the trie's depth, so after that many steps no beam is live, every sample holds at least one hypothesis and
+ *   no finalize pass is needed.
+ *   The hypothesis lists are the result: labels int64 [B][nb] (the caller fills them with -1), scores double [B][nb] (normalised),
+ *   logprob double [B][nb] (the raw fp32 sums), hyp_len int64 [B][nb], n_hyp int64 [B] (the caller zeroes it); best int64 [B] =
+ *   max(labels[b][0], 0) and len int64 [B] = hyp_len[b][0] once the sample holds a hypothesis.  order int64 [R] is the index of
+ *   m3ae_gather_rows for the key / value caches; dead int32 [R]; done int32 [B].  err int64 [1] is set to 1 when a slot, an entry
+ *   (also one that is not a child of the slot's node), a token, a next node or a label (A = the number of answers) is outside
+ *   its range: the candidate is skipped.
+ *   M3AE_ERR_ARG: a NULL pointer, a count outside its range, div <= 0.  M3AE_ERR_UNSUPPORTED: nb outside [1, 8], nb * E >= 2^31,
+ *   B * nb >= 2^31.  M3AE_ERR_ALIGN: a pointer off its element size. */
+int m3ae_triebeam_select(const void* logits, int64_t ld, int64_t B, int64_t nb, int64_t V, int64_t chunk, int dtype,
+                          const int32_t* child_off, const int32_t* child_tok, int64_t N, int64_t E, const int32_t* node,
+                          const float* beam_score, const void* workspace, int64_t workspace_bytes, float* top_s, int32_t* top_beam,
+                          int32_t* top_edge, int32_t* n_cand, int64_t* err, void* stream);
+int m3ae_triebeam_step(const float* top_s, const int32_t* top_beam, const int32_t* top_edge, const int32_t* child_off,
+                        const int32_t* child_tok, const int32_t* child_node, const int32_t* leaf_label, int64_t N, int64_t E,
+                        int32_t* node, float* beam_score, int64_t* last_tok, int64_t* order, int32_t* dead, int32_t* done,
+                        int64_t* n_hyp, int64_t* labels, double* scores, double* logprob, int64_t* hyp_len, int64_t* best, int64_t* len,
+                        int32_t* open_count, int64_t* err, int64_t B, int64_t nb, int64_t V, int64_t A, int64_t max_len, int64_t pos,
+                        int64_t pad, double div, void* stream);
+/* m3ae_vqa_labels_eval: the n-best form of m3ae_vqa_label_eval.  labels int64 [B][k] with row stride ldl >= k, 1 <= k <= 16;
+ *   hit1 = targets[r][labels[r][0]], hitk = the maximum of targets[r][l] over the row's entries l >= 0.  An entry of -1 in columns
+ *   1.. is an empty slot and is skipped; any other value outside [0, C), or an empty column 0, scores 0 and sets err[0] = 1.  The
+ *   fold, record and workspace are m3ae_vqa_label_eval's.  M3AE_ERR_ARG: NULL labels / targets / rec / err, B < 1, C < 1, k < 1.
+ *   M3AE_ERR_UNSUPPORTED: k > 16, ldl < k, C >= 2^31, B >= 2^31, ldt < C, a missing or short workspace.  M3AE_ERR_ALIGN as above. */
+int m3ae_vqa_labels_eval(const int64_t* labels, int64_t ldl, int64_t k, const float* targets, int64_t ldt, const int32_t* types,
+                         int64_t B, int64_t C, float* hit1, double* rec, int64_t* err, void* workspace, int64_t workspace_bytes,
+                         void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Device-side token evaluation (csrc/token_eval.hip; ABI 4, additive): what the reference's `Accuracy` metric computes for the MLM

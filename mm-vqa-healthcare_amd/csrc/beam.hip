@@ -18,6 +18,7 @@
 // host's Python floats), the wave copies the token rows.
 #include "common.h"
 #include "order_key.h"   // ord32 / unord32 / make_key / wave_max_u64, shared with csrc/greedy.hip
+#include "hyp_list.h"
 
 namespace {
 
@@ -124,10 +125,9 @@ __global__ __launch_bounds__(BT) void beam_merge_kernel(uint64_t* __restrict__ c
 // appended list), then the list is cut to nb.
 DEVINL void hyp_push(double score, const int64_t* row, int len, int nb, int max_length, int32_t& n, double* hs, int32_t* hl,
                      int64_t* ht) {
-    int p = 0;
-    while (p < n && !(hs[p] < score)) ++p;
-    if (p >= nb) return;
-    const int last = n < nb ? n : nb - 1;   // index the current tail moves to (the old tail of a full list falls off)
+    int last = 0;
+    const int p = hyp_insert_pos(score, nb, n, hs, last);   // csrc/hyp_list.h, shared with csrc/trie_beam.hip
+    if (p < 0) return;
     for (int q = last; q > p; --q) {
         hs[q] = hs[q - 1];
         hl[q] = hl[q - 1];
@@ -136,7 +136,7 @@ DEVINL void hyp_push(double score, const int64_t* row, int len, int nb, int max_
     hs[p] = score;
     hl[p] = len;
     for (int j = 0; j < max_length; ++j) ht[(int64_t)p * max_length + j] = j < len ? row[j] : 0;
-    if (n < nb) ++n;
+    n = hyp_count(n, nb);
 }
 
 __global__ __launch_bounds__(64) void beam_step_kernel(const float* __restrict__ top_s, const int32_t* __restrict__ top_i,

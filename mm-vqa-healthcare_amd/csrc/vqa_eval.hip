@@ -183,6 +183,32 @@ __global__ __launch_bounds__(VT) void label_rows_kernel(const int64_t* __restric
     rows[2 * r] = rows[2 * r + 1] = t;
 }
 
+// the n-best form: rows[r] = {targets[r][labels[r][0]], max over the row's entries l >= 0 of targets[r][l]}.  -1 in columns 1.. is
+// an empty slot; any other value outside [0, C), or an empty column 0, scores 0 and sets err (never an address)
+__global__ __launch_bounds__(VT) void labels_rows_kernel(const int64_t* __restrict__ labels, int64_t ldl, int k,
+                                                         const float* __restrict__ targets, int64_t ldt, int64_t B, int64_t C,
+                                                         float* __restrict__ hit1_out, float* __restrict__ rows, int64_t* __restrict__ err) {
+    const int64_t r = (int64_t)blockIdx.x * VT + threadIdx.x;
+    if (r >= B) return;
+    const int64_t* lr = labels + r * ldl;
+    const float* t = targets + r * ldt;
+    const int64_t l0 = lr[0];
+    const bool ok0 = l0 >= 0 && l0 < C;
+    if (!ok0) err[0] = 1;
+    const float h1 = ok0 ? t[l0] : 0.0f;
+    float hk = h1;
+    for (int j = 1; j < k; ++j) {
+        const int64_t l = lr[j];
+        if (l == -1) continue;
+        if (l < 0 || l >= C) { err[0] = 1; continue; }
+        const float v = t[l];
+        hk = v > hk ? v : hk;
+    }
+    if (hit1_out) hit1_out[r] = h1;
+    rows[2 * r] = h1;
+    rows[2 * r + 1] = hk;
+}
+
 inline int64_t rows_bytes(int64_t B) { return B * 2 * (int64_t)sizeof(float); }
 
 }  // namespace
@@ -242,6 +268,22 @@ extern "C" int m3ae_vqa_label_eval(const int64_t* labels, const float* targets, 
         return M3AE_ERR_ALIGN;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(label_rows_kernel, dim3((unsigned)cdiv(B, VT)), dim3(VT), 0, s, labels, targets, ldt, B, C, hit1, (float*)workspace, err);
+    hipLaunchKernelGGL(vqa_fold_kernel, dim3(1), dim3(VT), 0, s, (const float*)workspace, types, B, rec);
+    return hip_launch_status();
+}
+
+extern "C" int m3ae_vqa_labels_eval(const int64_t* labels, int64_t ldl, int64_t k, const float* targets, int64_t ldt, const int32_t* types,
+                                    int64_t B, int64_t C, float* hit1, double* rec, int64_t* err, void* workspace, int64_t workspace_bytes,
+                                    void* stream) {
+    if (!labels || !targets || !rec || !err || B < 1 || C < 1 || k < 1) return M3AE_ERR_ARG;
+    if (k > V_MAX_K || C > (int64_t)INT32_MAX || B > (int64_t)INT32_MAX || ldt < C || ldl < k) return M3AE_ERR_UNSUPPORTED;
+    if (!workspace || workspace_bytes < rows_bytes(B)) return M3AE_ERR_UNSUPPORTED;
+    if (((uintptr_t)labels & 7) || ((uintptr_t)targets & 3) || ((uintptr_t)types & 3) || ((uintptr_t)hit1 & 3) || ((uintptr_t)rec & 7) ||
+        ((uintptr_t)err & 7) || ((uintptr_t)workspace & 7))
+        return M3AE_ERR_ALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(labels_rows_kernel, dim3((unsigned)cdiv(B, VT)), dim3(VT), 0, s, labels, ldl, (int)k, targets, ldt, B, C, hit1,
+                       (float*)workspace, err);
     hipLaunchKernelGGL(vqa_fold_kernel, dim3(1), dim3(VT), 0, s, (const float*)workspace, types, B, rec);
     return hip_launch_status();
 }

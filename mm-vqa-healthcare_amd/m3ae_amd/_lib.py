@@ -195,6 +195,12 @@ _SIGS = {
     "m3ae_trie_step": (C.c_int, [vp, i64, C.c_int, vp, i64, i64, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64,
                                  i64, i64, vp]),
     "m3ae_vqa_label_eval": (C.c_int, [vp, vp, i64, vp, i64, i64, vp, vp, vp, vp, i64, vp]),
+    # constrained beam search on the answer list (ABI 4, additive): the best 2 nb children across a sample's beams, the
+    # BeamSearchScorer step with a trie node per beam and n-best labels; the VQA score record from n-best labels
+    "m3ae_triebeam_select": (C.c_int, [vp, i64, i64, i64, i64, i64, C.c_int, vp, vp, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]),
+    "m3ae_triebeam_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                      i64, i64, i64, i64, i64, i64, i64, C.c_double, vp]),
+    "m3ae_vqa_labels_eval": (C.c_int, [vp, i64, i64, vp, i64, vp, i64, i64, vp, vp, vp, vp, i64, vp]),
 }
 
 EXPORTS = tuple(_SIGS)

@@ -57,7 +57,8 @@ class AnswerTrie:
         self.leaf_label = np.asarray(leaf_label, dtype=np.int32)
         self.num_nodes, self.num_edges = len(leaf_label), len(child_tok)
         self.max_token = int(self.child_tok.max())
-        self._uploaded = {}
+        self._uploaded = {}             # device -> the int32 trie buffer
+        self._uploaded_answers = {}     # (device, max_len, pad_id) -> the int64 answers table
 
     @classmethod
     def from_answers(cls, id_lists, end_id):
@@ -80,10 +81,18 @@ class AnswerTrie:
             n = int(nodes[j])
         return n
 
-    def to_device(self, device, V, max_len):
+    def answers_table(self, max_len, pad_id):
+        """The answers as a pad-filled int64 [A, max_len] array, row i = label i with its end token."""
+        tab = np.full((self.num_answers, max_len), int(pad_id), dtype=np.int64)
+        for i, s in enumerate(self.sequences):
+            tab[i, :len(s)] = s
+        return tab
+
+    def to_device(self, device, V, max_len, pad_id=None):
         """Uploads the arrays as one int32 buffer and returns a namespace of views of it (child_off, child_tok, child_node,
-        leaf_label, buf, N, E, depth).  ValueError if a token is >= V or the longest answer exceeds max_len: the kernels follow
-        the table as it is."""
+        leaf_label, buf, N, E, A, depth).  ValueError if a token is >= V or the longest answer exceeds max_len: the kernels follow
+        the table as it is.  With `pad_id` the namespace also holds `answers`, the upload of answers_table(max_len, pad_id) (the
+        beam search reads the token row of its best label from it)."""
         import torch
         from types import SimpleNamespace as NS
         if self.max_token >= V:
@@ -98,5 +107,14 @@ class AnswerTrie:
             buf = host.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else host
             self._uploaded[device] = buf
         o1, o2, o3 = N + 1, N + 1 + E, N + 1 + 2 * E
-        return NS(child_off=buf[:o1], child_tok=buf[o1:o2], child_node=buf[o2:o3], leaf_label=buf[o3:], buf=buf, N=N, E=E,
-                  depth=self.depth)
+        ns = NS(child_off=buf[:o1], child_tok=buf[o1:o2], child_node=buf[o2:o3], leaf_label=buf[o3:], buf=buf, N=N, E=E,
+                A=self.num_answers, depth=self.depth)
+        if pad_id is not None:
+            key = (device, int(max_len), int(pad_id))
+            tab = self._uploaded_answers.get(key)
+            if tab is None:
+                host = torch.from_numpy(self.answers_table(max_len, pad_id))
+                tab = host.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else host
+                self._uploaded_answers[key] = tab
+            ns.answers = tab
+        return ns

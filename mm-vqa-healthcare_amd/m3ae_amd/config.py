@@ -61,6 +61,13 @@ DEFAULTS = dict(
     # search alone, as before) | "list" (also answer-list decoding, csrc/answer_trie.hip: greedy search restricted to the answers
     # of Trainer.set_answer_list, scored as labels with the closed / open VQA score).  "free" calls no new entry point.
     answer_decoding="free",
+    # answer_decoding="list" only: the beams of the list search (csrc/trie_beam.hip).  1 = the greedy search with the launches it
+    # always made; 2 .. 8 = constrained beam search, which also yields the n-best answers test() scores `@k`.
+    # answer_length_penalty: hypotheses rank by log-probability / length ** penalty.  0.0 ranks a closed list by the entries'
+    # log-probability (with answer_beams >= the list's size the search is exhaustive and the result is the maximum-likelihood
+    # entry); 1.0 is HF generate's length-normalised ranking.
+    answer_beams=1,
+    answer_length_penalty=0.0,
     # where validation / test compute their metric (m3ae_amd/trainer.py, m3ae_amd/metrics.py): "host" (ATen float / argmax /
     # gather / sum: the overall VQA score alone) | "device" (csrc/vqa_eval.hip: overall, closed and open scores, the score within
     # the top `eval_topk` answers, and token exact match for the generator heads in test()).  eval_topk is honoured only with "device".
@@ -271,6 +278,21 @@ def answer_decoding(cfg):
     return v
 
 
+ANSWER_MAX_BEAMS = 8
+
+
+def answer_beams(cfg):
+    """The validated (`answer_beams`, `answer_length_penalty`) of a config dict (defaults 1 and 0.0): an int in [1, 8] and a finite
+    number.  Read under answer_decoding="list" only, checked always."""
+    nb = cfg.get("answer_beams", 1)
+    if isinstance(nb, bool) or not isinstance(nb, int) or not 1 <= nb <= ANSWER_MAX_BEAMS:
+        raise ValueError(f"answer_beams must be an integer in [1, {ANSWER_MAX_BEAMS}], got {nb!r}")
+    lp = cfg.get("answer_length_penalty", 0.0)
+    if isinstance(lp, bool) or not isinstance(lp, (int, float)) or lp != lp or lp in (float("inf"), float("-inf")):
+        raise ValueError(f"answer_length_penalty must be a finite number, got {lp!r}")
+    return nb, float(lp)
+
+
 VQA_METRICS = ("host", "device")
 
 
@@ -318,6 +340,7 @@ def resolve_arch(cfg):
     optim_type(cfg)
     decoder_search(cfg)
     answer_decoding(cfg)
+    answer_beams(cfg)
     vqa_metrics(cfg)
     pretrain_metrics(cfg)
     if "gradient_clip_val" in cfg:

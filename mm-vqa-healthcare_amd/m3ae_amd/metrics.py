@@ -121,11 +121,20 @@ class VQARADScore(_DeviceRecordMetric):
     def update_labels(self, labels, target, types=None, want_rows=False):
         """The same update from LABELS (answer-list decoding of a generator head, ops.vqa_label_eval): labels int64 [B] on the
         device, target fp32 [B, C]; a row adds target[r, labels[r]] as its score and its score within the top-k alike.  A label
-        outside [0, C) scores 0 and sets `self.label_err` (int64 [1] on the device).  Enqueues only."""
+        outside [0, C) scores 0 and sets `self.label_err` (int64 [1] on the device).  labels int64 [B, k], 1 <= k <= 16 (the
+        n-best list of a constrained beam search, -1 = an empty slot in columns 1..): the score is column 0's and the score
+        within the top-k the best target among the row's entries.  Enqueues only."""
+        if labels.dim() == 2:   # n-best labels [B, k] of a constrained beam search (ops.vqa_labels_eval): -1 = an empty slot in
+            ops._labels_shape("update_labels", labels, target.shape[0])   # columns 1..; score_at_k is the best target among them
+        elif labels.dim() != 1:
+            raise ValueError(f"update_labels: labels int64 [B] or [B, k], got {tuple(labels.shape)}")
         if target.dtype != torch.float32:
             target = target.float()
         if getattr(self, "label_err", None) is None:
             self.label_err = torch.zeros((1,), dtype=torch.int64, device=labels.device)
+        if labels.dim() == 2:
+            return ops.vqa_labels_eval(labels.detach(), target.detach(), types_tensor(types, labels.device), self.rec,
+                                       err=self.label_err, want_rows=want_rows)
         return ops.vqa_label_eval(labels.detach().contiguous(), target.detach(), types_tensor(types, labels.device), self.rec,
                                   err=self.label_err, want_rows=want_rows)
 

@@ -293,6 +293,47 @@ class Decoder(nn.Module):
 
     @torch.no_grad()
     @ops.model_mode
+    def answer_beam_async(self, cross_attn_feats, trie, num_beams=4, length_penalty=0.0, cls_id=101, pad_id=0, lookahead=2, chunk=0):
+        """Constrained beam search on the answer list (csrc/trie_beam.hip): the loop of `answer_path_async` at R = B * num_beams
+        rows, 1 <= num_beams <= 8, with HF's BeamSearchScorer semantics and the trie as the prefix constraint.  Per step the
+        decoder row, the vocabulary GEMM, ops.trie_scan (dead slots skipped), ops.trie_beam_select, ops.trie_beam_step and the
+        re-ordering of the self-attention cache through `state.order` are enqueued with no blocking host call; at most
+        trie.depth steps.  Returns the namespace of `answer_path_async` plus the n-best list: `labels` int64 [B, num_beams]
+        (-1 = no entry), `scores` float64 [B, num_beams] (log-probability / length ** length_penalty, descending), `logprob`
+        float64 [B, num_beams] (the raw sums), `n_hyp` int64 [B]; `label` / `score` are column 0 and `seq` / `len` belong to it.
+        With num_beams >= the number of answers the search is exhaustive: label = the list's arg-max of the normalised score.
+        length_penalty 0 (default) ranks by the sequence log-probability, 1 is HF's length-normalised ranking."""
+        B, nb, dev = cross_attn_feats.shape[0], int(num_beams), cross_attn_feats.device
+        R = B * nb
+        D = self.target_embedding.weight.shape[1]
+        dt = trie.to_device(dev, self.final_linear.weight.shape[0], self.max_len, pad_id=pad_id)
+        depth = dt.depth
+        st = ops.TrieBeamState(B, nb, self.max_len, dev, cls_id, pad_id)
+        watch = ops.OpenCountWatch(depth, lookahead or None)   # None or 0: no early exit, all `depth` steps
+        enc_kv = self.dec_layers[self.num_layers - 1].cross_kv(cross_attn_feats.to(self.head_dtype))
+        enc_kv = enc_kv.repeat_interleave(nb, dim=0)
+        cache = torch.empty((R, depth, 2 * D), dtype=self.head_dtype, device=dev)
+        pe_rows = self.positional_encoding.pe[0, :depth].to(torch.float32)[:, None, :].expand(depth, R, D).contiguous()
+        ws, steps = None, 0
+        for pos in range(depth):
+            logits = self.step_logits(st.last_tok.view(R, 1), pos, enc_kv, cache, pe_rows[pos])
+            if ws is None:
+                V = logits.shape[-1]
+                ws = ops.trie_workspace(R, V, dev, chunk)
+            ops.trie_scan(logits, dt, st, chunk, ws)
+            ops.trie_beam_select(logits, dt, st, ws, chunk)
+            ops.trie_beam_step(dt, st, V, pos, length_penalty)
+            steps += 1
+            if watch.enqueued(st.open_count, pos):
+                break
+            if pos + 1 < depth:
+                cache = ops.gather_rows(cache.view(R, -1), st.order).view_as(cache)
+        ops.trie_beam_result(dt, st)
+        return NS(label=st.label, score=st.score, labels=st.labels, scores=st.scores, logprob=st.logprob, n_hyp=st.n_hyp, seq=st.seq,
+                  len=st.len, err=st.err, out=st.out, steps=steps, state=st)
+
+    @torch.no_grad()
+    @ops.model_mode
     def search_path(self, cross_attn_feats, cls_id=101, sep_id=102, eos_id=None, pad_id=0, use_cache=True, search="host",
                     lookahead=2):
         """m3ae_decoder.py:141-182: greedy decoding.  The reference re-runs the whole prefix every step; here a step is one
@@ -338,20 +379,37 @@ class Decoder(nn.Module):
         return torch.nn.functional.pad(seq, (0, self.max_len - seq.shape[1]), value=pad_id)
 
 
-def answer_result(r, label2ans=None):
-    """One copy of an answer-list search's `out` buffer (Decoder.answer_path_async, T5.constrained_greedy_async) -> (labels int64
-    [B], scores float64 [B]) on the host; raises if the error word is set.  With label2ans: a list of (answer, score) through
-    label2ans[str(label)] (m3ae_module.answers_of's rule)."""
+def answer_result(r, label2ans=None, k=1):
+    """One copy of an answer-list search's `out` buffer (Decoder.answer_path_async / answer_beam_async, T5.constrained_greedy_async /
+    constrained_beam_async) -> (labels int64 [B], scores float64 [B]) on the host; raises if the error word is set.  With label2ans:
+    a list of (answer, score) through label2ans[str(label)] (m3ae_module.answers_of's rule).  k > 1 (a beam search with
+    num_beams >= k): the k best entries per row instead -- (labels [B, k] with -1 for a missing entry, scores [B, k]), or with
+    label2ans a list of B lists of up to k (answer, score)."""
     out = r.out.cpu()
     if int(out[-1]) != 0:
         raise ops._lib.M3AEHipError("answer-list decoding: the answer table led a row out of its range")
     B = r.label.shape[0]
     n = r.seq.numel()
-    labels, scores = out[n + B:n + 2 * B].clone(), out[n + 2 * B:n + 3 * B].view(torch.float64).clone()
+    k = int(k)
+    if hasattr(r, "labels"):   # the beam form: seq | len | labels [B, nb] | scores [B, nb] | logprob | n_hyp | err
+        nb = r.labels.shape[1]
+        if not 1 <= k <= nb:
+            raise ValueError(f"answer_result: k={k} outside [1, num_beams={nb}]")
+        o = n + B
+        labels2 = out[o:o + B * nb].view(B, nb)[:, :k].clone()
+        scores2 = out[o + B * nb:o + 2 * B * nb].view(torch.float64).view(B, nb)[:, :k].clone()
+    else:
+        if k != 1:
+            raise ValueError(f"answer_result: k={k} needs a beam search (num_beams >= k); the greedy search returns one entry")
+        labels2 = out[n + B:n + 2 * B].clone().view(B, 1)
+        scores2 = out[n + 2 * B:n + 3 * B].view(torch.float64).clone().view(B, 1)
     if label2ans is None:
-        return labels, scores
+        return (labels2[:, 0], scores2[:, 0]) if k == 1 else (labels2, scores2)
     from .m3ae_module import answers_of
-    return [row[0] for row in answers_of([[l] for l in labels.tolist()], [[s] for s in scores.tolist()], label2ans)]
+    if k == 1:      # column 0 as it is: a row that ended without a label (-1) is a KeyError of answers_of, as it always was
+        return [row[0] for row in answers_of(labels2.tolist(), scores2.tolist(), label2ans)]
+    rows = [[(l, s) for l, s in zip(lr, sr) if l >= 0] for lr, sr in zip(labels2.tolist(), scores2.tolist())]   # -1 = no entry
+    return answers_of([[l for l, _ in row] for row in rows], [[s for _, s in row] for row in rows], label2ans)
 
 
 class DecoderModel(_Base):
@@ -464,20 +522,24 @@ class DecoderModel(_Base):
         return self.decoder.search_path_async(self.features(batch), self.cls_id, self.sep_id, None, self.pad_id, lookahead)
 
     @ops.model_mode
-    def answer_async(self, batch, trie, lookahead=2):
+    def answer_async(self, batch, trie, lookahead=2, num_beams=1, length_penalty=0.0):
         """The features of `batch` and answer-list decoding over them (Decoder.answer_path_async), nothing copied to the host:
-        its namespace (`label`, `score`, `seq`, `len`, `err`, `out`, `steps`, `state`)."""
+        its namespace (`label`, `score`, `seq`, `len`, `err`, `out`, `steps`, `state`).  num_beams > 1: the constrained beam
+        search (Decoder.answer_beam_async), whose namespace also holds the n-best `labels` / `scores` / `logprob` / `n_hyp`."""
         if self.store is None:
             raise RuntimeError("call finalize(device) before the first forward")
-        return self.decoder.answer_path_async(self.features(batch), trie, self.cls_id, self.pad_id, lookahead)
+        if num_beams == 1:
+            return self.decoder.answer_path_async(self.features(batch), trie, self.cls_id, self.pad_id, lookahead)
+        return self.decoder.answer_beam_async(self.features(batch), trie, num_beams, length_penalty, self.cls_id, self.pad_id, lookahead)
 
     @ops.model_mode
-    def answer(self, batch, trie, label2ans=None):
+    def answer(self, batch, trie, label2ans=None, num_beams=1, k=1, length_penalty=0.0):
         """The answer of every sample as an entry of the list `trie` was built from: (labels int64 [B], scores float64 [B]: the
         log-probability of the entry's tokens), both on the host after ONE copy.  With label2ans (the reference's mapping with
-        string keys, as M3AETransformerSS.answers): a list of B (answer, score) instead."""
-        r = self.answer_async(batch, trie)
-        return answer_result(r, label2ans)
+        string keys, as M3AETransformerSS.answers): a list of B (answer, score) instead.  num_beams > 1 searches with that many
+        beams and k <= num_beams returns the k best entries per row (answer_result)."""
+        r = self.answer_async(batch, trie, num_beams=num_beams, length_penalty=length_penalty)
+        return answer_result(r, label2ans, k)
 
     @ops.model_mode
     def generate(self, batch, search=None):

@@ -147,20 +147,24 @@ class T5VQA_MMEncoderInput(_Base):
         return self.t5.generate_async(enc, num_beams=4, max_length=self.max_answer_length, lookahead=lookahead)
 
     @ops.model_mode
-    def answer_async(self, batch, trie, lookahead=2):
+    def answer_async(self, batch, trie, lookahead=2, num_beams=1, length_penalty=0.0):
         """The encoder output of `batch` and answer-list decoding over it (T5ForConditionalGeneration.constrained_greedy_async:
-        one beam, greedy on the trie), nothing copied to the host: its namespace (`label`, `score`, `seq`, `len`, `err`, ...)."""
+        one beam, greedy on the trie), nothing copied to the host: its namespace (`label`, `score`, `seq`, `len`, `err`, ...).
+        num_beams > 1: constrained_beam_async, whose namespace also holds the n-best `labels` / `scores` / `logprob` / `n_hyp`."""
         if self.store is None:
             raise RuntimeError("call finalize(device) before the first forward")
         with torch.no_grad():
             enc = self.t5.encoder(self.prepare_inputs(batch)["inputs_embeds"])
-        return self.t5.constrained_greedy_async(enc, trie, max_length=self.max_answer_length, lookahead=lookahead)
+        if num_beams == 1:
+            return self.t5.constrained_greedy_async(enc, trie, max_length=self.max_answer_length, lookahead=lookahead)
+        return self.t5.constrained_beam_async(enc, trie, num_beams, self.max_answer_length, length_penalty, lookahead=lookahead)
 
     @ops.model_mode
-    def answer(self, batch, trie, label2ans=None):
-        """As DecoderModel.answer: (labels, scores) on the host after one copy, or (answer, score) pairs with label2ans."""
+    def answer(self, batch, trie, label2ans=None, num_beams=1, k=1, length_penalty=0.0):
+        """As DecoderModel.answer: (labels, scores) on the host after one copy, or (answer, score) pairs with label2ans; the k best
+        of a num_beams search when asked."""
         from .m3ae_decoder import answer_result
-        return answer_result(self.answer_async(batch, trie), label2ans)
+        return answer_result(self.answer_async(batch, trie, num_beams=num_beams, length_penalty=length_penalty), label2ans, k)
 
     def training_step(self, batch, batch_idx=0):
         """m3ae_t5_mm_encoder_input.py:340-346."""

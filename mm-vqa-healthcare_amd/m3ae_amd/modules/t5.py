@@ -330,7 +330,7 @@ class T5ForConditionalGeneration(nn.Module):
         ending in </s>) allows.  At most trie.depth <= max_length steps, no blocking host call.  Returns the namespace of
         Decoder.answer_path_async: `label` int64 [B], `score` float64 [B] (sum of log-probabilities), `seq` int64
         [B, max_length] (the generated tokens, WITHOUT the start token; pad after the end token), `len`, `err`, `out`, `steps`,
-        `state`.  Constrained BEAM search is not implemented."""
+        `state`.  `constrained_beam_async` is the beam form."""
         B, dev = enc.shape[0], enc.device
         dt = trie.to_device(dev, self.config.vocab_size, max_length)
         watch = ops.OpenCountWatch(dt.depth, lookahead or None)   # None or 0: no early exit, all `depth` steps
@@ -348,6 +348,39 @@ class T5ForConditionalGeneration(nn.Module):
             if watch.enqueued(st.open_count, pos):
                 break
         return NS(label=st.label, score=st.score, seq=st.seq, len=st.len, err=st.err, out=st.out, steps=steps, state=st)
+
+    @torch.no_grad()
+    def constrained_beam_async(self, enc, trie, num_beams=4, max_length=12, length_penalty=0.0, pad_token_id=0, lookahead=2, chunk=0):
+        """Constrained beam search on the answer list (csrc/trie_beam.hip): the loop of `constrained_greedy_async` at
+        R = B * num_beams rows, 1 <= num_beams <= 8.  Encoder rows and cross keys / values are repeated as `generate_async` does,
+        the self cache is re-ordered through `state.order` each step, no blocking host call, at most trie.depth <= max_length
+        steps.  Returns the namespace of Decoder.answer_beam_async: `labels` / `scores` / `logprob` [B, num_beams], `n_hyp`, and
+        `label`, `score`, `seq`, `len` of the best entry (seq WITHOUT the start token, pad after the end token)."""
+        B, nb, dev = enc.shape[0], int(num_beams), enc.device
+        R, Ls = B * nb, enc.shape[1]
+        dt = trie.to_device(dev, self.config.vocab_size, max_length, pad_id=pad_token_id)
+        st = ops.TrieBeamState(B, nb, max_length, dev, self.config.decoder_start_token_id, pad_token_id)
+        watch = ops.OpenCountWatch(dt.depth, lookahead or None)   # None or 0: no early exit, all `depth` steps
+        enc_r = enc.repeat_interleave(nb, dim=0).contiguous()
+        cross_kv = [kv.view(B, Ls, -1).repeat_interleave(nb, dim=0).reshape(R * Ls, -1) for kv in self.decoder.cross_kv(enc)]
+        self_cache = self.decoder.new_self_cache(R, dt.depth, enc.dtype, dev)
+        ws, steps = None, 0
+        for pos in range(dt.depth):
+            logits = self.next_token_logits_cached(enc_r, st.last_tok.view(R, 1), cross_kv, self_cache, pos)
+            if ws is None:
+                V = logits.shape[-1]
+                ws = ops.trie_workspace(R, V, dev, chunk)
+            ops.trie_scan(logits, dt, st, chunk, ws)
+            ops.trie_beam_select(logits, dt, st, ws, chunk)
+            ops.trie_beam_step(dt, st, V, pos, length_penalty)
+            steps += 1
+            if watch.enqueued(st.open_count, pos):
+                break
+            if pos + 1 < dt.depth:
+                self_cache = [ops.gather_rows(c.view(R, -1), st.order).view_as(c) for c in self_cache]
+        ops.trie_beam_result(dt, st)
+        return NS(label=st.label, score=st.score, labels=st.labels, scores=st.scores, logprob=st.logprob, n_hyp=st.n_hyp, seq=st.seq,
+                  len=st.len, err=st.err, out=st.out, steps=steps, state=st)
 
     @torch.no_grad()
     def generate(self, enc, num_beams=4, max_length=12, eos_token_id=1, pad_token_id=0, length_penalty=1.0,

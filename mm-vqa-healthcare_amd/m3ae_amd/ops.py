@@ -2269,6 +2269,96 @@ def trie_step(logits, trie, st, ws, pos, pad_id, chunk=0):
 
 
 # ------------------------------------------------------------------------------------------------------------
+# constrained beam search on the answer list (csrc/trie_beam.hip): Decoder.answer_beam_async, T5.constrained_beam_async
+# ------------------------------------------------------------------------------------------------------------
+TRIE_MAX_BEAMS = 8
+
+
+class TrieBeamState:
+    """The device state of one constrained beam search (include/m3ae_hip.h, m3ae_triebeam_step): allocated once per call.
+    R = B * nb beam rows; `B` is the row count trie_scan sees (it runs over the beam rows with `finished` = the dead flags), `Bs`
+    the number of samples.  The result is the hypothesis list of every sample, in `out`:
+    seq [Bs, max_len] | len [Bs] | labels [Bs, nb] | scores [Bs, nb] | logprob [Bs, nb] (the bits of float64) | n_hyp [Bs] | err."""
+
+    def __init__(self, Bs, nb, max_len, device, start_id=101, pad_id=0):
+        if not 1 <= nb <= TRIE_MAX_BEAMS:
+            raise ValueError(f"TrieBeamState: num_beams={nb} outside [1, {TRIE_MAX_BEAMS}]")
+        R = Bs * nb
+        self.Bs, self.nb, self.B, self.max_len, self.pad_id = Bs, nb, R, max_len, pad_id
+        n, h = Bs * max_len, Bs * nb
+        self.out = torch.zeros((n + Bs + 3 * h + Bs + 1,), dtype=torch.int64, device=device)
+        o = self.out
+        self.seq, self.len = o[:n].view(Bs, max_len), o[n:n + Bs]
+        o = o[n + Bs:]
+        self.labels, self.scores, self.logprob = o[:h].view(Bs, nb), o[h:2 * h].view(torch.float64).view(Bs, nb), \
+            o[2 * h:3 * h].view(torch.float64).view(Bs, nb)
+        self.n_hyp, self.err = o[3 * h:3 * h + Bs], o[-1:]
+        self.seq.fill_(pad_id)
+        self.labels.fill_(-1)
+        self.label, self.score = self.labels[:, 0], self.scores[:, 0]
+        z = functools.partial(torch.zeros, device=device)
+        self.hyp_len, self.best = z((Bs, nb), dtype=torch.int64), z((Bs,), dtype=torch.int64)
+        self.node = z((Bs, nb), dtype=torch.int32)
+        self.node[:, 1:] = -1
+        self.node = self.node.view(-1)
+        self.finished = (self.node < 0).to(torch.int32)          # the dead flags: trie_scan's `finished`
+        self.beam_score = z((R,), dtype=torch.float32)
+        self.last_tok = torch.full((Bs, nb), pad_id, dtype=torch.int64, device=device)
+        self.last_tok[:, 0] = start_id
+        self.last_tok = self.last_tok.view(-1)
+        self.order = torch.arange(Bs, device=device, dtype=torch.int64).repeat_interleave(nb) * nb
+        self.done = z((Bs,), dtype=torch.int32)
+        self.open_count = z((max_len,), dtype=torch.int32)
+        self.top_s = z((Bs, 2 * nb), dtype=torch.float32)
+        self.top_beam, self.top_edge = z((Bs, 2 * nb), dtype=torch.int32), z((Bs, 2 * nb), dtype=torch.int32)
+        self.n_cand = z((Bs,), dtype=torch.int32)
+
+
+def trie_beam_select(logits, trie, st, ws, chunk=0):
+    """The candidate selection of one step: logits fp32 or bf16 [B * nb, V] as trie_scan took them, `ws` the workspace trie_scan
+    filled from them (same chunk).  Per sample the best min(2 nb, candidates) children of its live beams' nodes by
+    fl(fl(x[tok] - lse) + beam_score), into st.top_s / st.top_beam / st.top_edge / st.n_cand."""
+    _trie_logits("trie_beam_select", logits, st)
+    R, V = logits.shape
+    _trie_ws("trie_beam_select", ws, R, V, int(chunk))
+    check(_lib.lib().m3ae_triebeam_select(_p(logits), logits.stride(0), st.Bs, st.nb, V, int(chunk), _dt(logits), _p(trie.child_off),
+                                           _p(trie.child_tok), trie.N, trie.E, _p(st.node), _p(st.beam_score), _p(ws), ws.numel() * 8,
+                                           _p(st.top_s), _p(st.top_beam), _p(st.top_edge), _p(st.n_cand), _p(st.err), _stream()),
+          "m3ae_triebeam_select")
+    return st.top_s, st.top_beam, st.top_edge, st.n_cand
+
+
+def trie_beam_step(trie, st, V, pos, length_penalty=0.0):
+    """One BeamSearchScorer step on `st` at position pos from the candidates trie_beam_select left in it: hypotheses, the next
+    beams (st.node / beam_score / last_tok), st.order (the gather index of the caches), the dead flags (st.finished) and
+    st.open_count[pos] = samples not done."""
+    _need_cuda(st.out)
+    if not 0 <= pos < st.max_len:
+        raise ValueError(f"trie_beam_step: pos {pos} outside [0, {st.max_len})")
+    check(_lib.lib().m3ae_triebeam_step(_p(st.top_s), _p(st.top_beam), _p(st.top_edge), _p(trie.child_off), _p(trie.child_tok),
+                                         _p(trie.child_node), _p(trie.leaf_label), trie.N, trie.E, _p(st.node), _p(st.beam_score),
+                                         _p(st.last_tok), _p(st.order), _p(st.finished), _p(st.done), _p(st.n_hyp), _p(st.labels),
+                                         _p(st.scores), _p(st.logprob), _p(st.hyp_len), _p(st.best), _p(st.len), _p(st.open_count),
+                                         _p(st.err), st.Bs, st.nb, V, trie.A, st.max_len, pos, st.pad_id, float(pos + 1) ** length_penalty,
+                                         _stream()), "m3ae_triebeam_step")
+
+
+def trie_beam_result(trie, st):
+    """st.seq = the token rows of the best hypotheses, gathered on the device from the pad-filled answers table of `trie`
+    (AnswerTrie.to_device(..., pad_id=...)): int64 rows moved as pairs of fp32 words by m3ae_gather_rows.  The kernel is called
+    directly, not through `gather_rows`: that wrapper is an autograd node over fp32 / bf16 tensors which allocates its output, and
+    here an int64 table is copied bit for bit INTO st.out, so that one copy still brings the whole result to the host.  st.best is
+    written by m3ae_triebeam_step alone, which takes only labels in [0, A) (A = the rows of the table, checked below)."""
+    tab = trie.answers
+    if tab.shape[0] != trie.A or st.best.dtype != torch.int64 or tuple(st.best.shape) != (st.Bs,) or not tab.is_cuda:
+        raise ValueError(f"trie_beam_result: the answers table has {tab.shape[0]} rows for {trie.A} answers, or the state is not this search's")
+    if tab.dtype != torch.int64 or tuple(tab.shape) != (tab.shape[0], st.max_len) or not tab.is_contiguous():
+        raise ValueError(f"trie_beam_result: the answers table int64 [A, {st.max_len}]")
+    check(_lib.lib().m3ae_gather_rows(_p(tab), _p(st.best), _p(st.seq), st.Bs, 2 * st.max_len, F32, _stream()), "m3ae_gather_rows")
+    return st.seq
+
+
+# ------------------------------------------------------------------------------------------------------------
 # device-side VQA evaluation (csrc/vqa_eval.hip): m3ae_amd/metrics.py, M3AETransformerSS.predict
 # ------------------------------------------------------------------------------------------------------------
 class VqaRows(NamedTuple):
@@ -2388,6 +2478,39 @@ def vqa_label_eval(labels, targets, types, rec, err=None, want_rows=False):
     hit1 = torch.empty((B,), dtype=torch.float32, device=labels.device) if want_rows else None
     check(_lib.lib().m3ae_vqa_label_eval(_p(labels), _p(targets), targets.stride(0), _p(types), B, targets.shape[1], _p(hit1), _p(rec),
                                          _p(err), _p(ws), ws.numel() * 4, _stream()), "m3ae_vqa_label_eval")
+    return LabelRows(hit1, err) if want_rows else err
+
+
+def _labels_shape(what, labels, B=None):
+    """The shape rule of n-best labels (needs no device): int64 [B, k], 1 <= k <= 16, unit column stride, row stride >= k."""
+    if labels.dtype != torch.int64 or labels.dim() != 2 or labels.shape[0] < 1 or (B is not None and labels.shape[0] != B) or \
+            not 1 <= labels.shape[1] <= _lib.VQA_MAX_K or labels.stride(1) != 1 or labels.stride(0) < labels.shape[1]:
+        raise ValueError(f"{what}: labels int64 [B, k] with 1 <= k <= {_lib.VQA_MAX_K}, unit column stride; got {labels.dtype} "
+                         f"{tuple(labels.shape)} {tuple(labels.stride())}")
+    return labels.shape
+
+
+def vqa_labels_eval(labels, targets, types, rec, err=None, want_rows=False):
+    """The n-best form of vqa_label_eval (a constrained beam search's `labels`): labels int64 [B, k] (a view with a row stride is
+    taken as it is), -1 in columns 1.. = an empty slot.  Adds {n, targets[r, labels[r, 0]], max over the row's entries of
+    targets[r, l]} onto rec.  Any other value outside [0, C), or an empty column 0, scores 0 and sets err.  Returns err, or
+    LabelRows with want_rows."""
+    B, k = _labels_shape("vqa_labels_eval", labels)
+    _need_cuda(labels)
+    _need_cuda(targets)
+    if targets.dtype != torch.float32 or targets.dim() != 2 or targets.shape[0] != B or targets.shape[1] < 1 or targets.stride(1) != 1 \
+            or targets.stride(0) < targets.shape[1]:
+        raise ValueError(f"vqa_labels_eval: targets fp32 [{B}, C], unit column stride; got {targets.dtype} {tuple(targets.shape)}")
+    if rec is None:
+        raise ValueError("vqa_labels_eval: rec is required (ops.vqa_record)")
+    ws = _eval_common("vqa_labels_eval", B, types, rec, labels.device)
+    if err is None:
+        err = torch.zeros((1,), dtype=torch.int64, device=labels.device)
+    elif err.dtype != torch.int64 or err.numel() != 1 or not err.is_cuda:
+        raise ValueError("vqa_labels_eval: err int64 [1] on the device")
+    hit1 = torch.empty((B,), dtype=torch.float32, device=labels.device) if want_rows else None
+    check(_lib.lib().m3ae_vqa_labels_eval(_p(labels), labels.stride(0), k, _p(targets), targets.stride(0), _p(types), B, targets.shape[1],
+                                          _p(hit1), _p(rec), _p(err), _p(ws), ws.numel() * 4, _stream()), "m3ae_vqa_labels_eval")
     return LabelRows(hit1, err) if want_rows else err
 
 

@@ -169,7 +169,10 @@ class Trainer:
         # config key `answer_decoding`: "free" | "list" (test() with vqa_metrics="device" and a generator head also decodes on
         # `answer_trie`, an answer_trie.AnswerTrie: set_answer_list or assign it).  answer_metrics: its result() dict of the last pass.
         self.answer_decoding = config_mod.answer_decoding(cfg)
-        self.answer_trie, self.answer_metrics = None, None
+        self.answer_trie, self.answer_metrics, self.answer_k = None, None, 1
+        # config keys `answer_beams` / `answer_length_penalty` (read under "list" only): 1 = the greedy list search; 2 .. 8 = the
+        # constrained beam search (csrc/trie_beam.hip), whose min(eval_topk, answer_beams) best labels per row give the `@k` score
+        self.answer_beams, self.answer_length_penalty = config_mod.answer_beams(cfg)
         # config key `pretrain_metrics`: "host" (nothing beyond the monitored loss) | "device" (metrics.PretrainMetrics);
         # pretrain: its result() dict of the last pass
         self.pretrain_metrics = config_mod.pretrain_metrics(cfg)
@@ -285,11 +288,15 @@ class Trainer:
         return self.answer_trie
 
     def answer_text(self):
-        """` answer_list X (n) closed Y (n) open Z (n)` of the last test pass ("" unless answer_decoding="list" ran)."""
+        """` answer_list X (n) closed Y (n) open Z (n)` of the last test pass ("" unless answer_decoding="list" ran), with
+        ` @k W` after a pass with answer_beams > 1 and k = min(eval_topk, answer_beams) > 1."""
         r = self.answer_metrics
         if r is None:
             return ""
-        return f" answer_list {r['score']:.4f} ({r['n']}) closed {r['closed']:.4f} ({r['n_closed']}) open {r['open']:.4f} ({r['n_open']})"
+        text = f" answer_list {r['score']:.4f} ({r['n']}) closed {r['closed']:.4f} ({r['n_closed']}) open {r['open']:.4f} ({r['n_open']})"
+        if self.answer_k > 1:   # the beam form fed its n-best labels: the best target among a row's k best answers
+            text += f" @{self.answer_k} {r['score_at_k']:.4f}"
+        return text
 
     def pretrain_text(self):
         """`mlm acc X (n) @k Y ppl Z | itm acc X (n) | mim loss X` of the last pass ("" with pretrain_metrics="host")."""
@@ -334,7 +341,8 @@ class Trainer:
         if em is not None and self.answer_decoding == "list":
             if self.answer_trie is None:
                 raise ValueError('answer_decoding="list" needs trainer.answer_trie: call set_answer_list(label2ans) or assign an AnswerTrie')
-            ans = metrics_mod.VQARADScore(self.device, k=0)
+            self.answer_k = max(min(int(self.cfg.get("eval_topk", 5)), self.answer_beams), 1) if self.answer_beams > 1 else 1
+            ans = metrics_mod.VQARADScore(self.device, k=self.answer_k if self.answer_k > 1 else 0)
             ans_err = torch.zeros((1,), dtype=torch.int64, device=self.device)
         pre = None     # pretrain_metrics="device": built at the first batch that brings a pre-training objective
         fed = 0
@@ -362,9 +370,15 @@ class Trainer:
                     if em is not None:
                         em.update(self.model.generate_async(batch).seq, refs_of(batch), batch.get("answer_types"))
                     if ans is not None:     # enqueued; read once below
-                        r = self.model.answer_async(batch, self.answer_trie)
+                        if self.answer_beams > 1:
+                            r = self.model.answer_async(batch, self.answer_trie, num_beams=self.answer_beams,
+                                                        length_penalty=self.answer_length_penalty)
+                            labels = r.labels[:, :self.answer_k] if self.answer_k > 1 else r.label
+                        else:
+                            r = self.model.answer_async(batch, self.answer_trie)
+                            labels = r.label
                         ans_err += r.err
-                        ans.update_labels(r.label, build_vqa_targets(batch, self.cfg["vqa_label_size"], self.device), batch.get("answer_types"))
+                        ans.update_labels(labels, build_vqa_targets(batch, self.cfg["vqa_label_size"], self.device), batch.get("answer_types"))
                 tot += s
                 cnt += n
         self.model.train()

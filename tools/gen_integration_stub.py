@@ -99,6 +99,10 @@ SECTIONS = {
         "# answer-list decoding (ABI 4, additive): greedy on a prefix trie of the candidate answers + the path's log-probability; label scoring",
         (),
         ("m3ae_trie_workspace_bytes", "m3ae_trie_scan", "m3ae_trie_step", "m3ae_vqa_label_eval")),
+    "TRIE_BEAM_ENTRIES": Section(
+        "# constrained beam search on the answer list (ABI 4, additive): best 2 nb children across beams, the scorer step, n-best label scoring",
+        (),
+        ("m3ae_triebeam_select", "m3ae_triebeam_step", "m3ae_vqa_labels_eval")),
 }
 globals().update({key: s.entries for key, s in SECTIONS.items() if s.entries})   # MAP_ENTRIES, DET_ENTRIES, ...: views of the table
 
