@@ -30,12 +30,12 @@ Tokenisation happens outside (`batch["decoder_tokens"]`: int64 [B, T] = [CLS] an
 `tokenizer` callable; string metrics (ROUGE / BLEU / exact match) stay out of scope.
 """
 import math
-from types import SimpleNamespace as NS
 
 import torch
 import torch.nn as nn
 
 from .. import config, ops
+from ..search import DecoderHead, Greedy, TrieBeam, TrieGreedy, answer_result, run as run_search
 from ..param_store import ParamStore, group_hparams_decoder, param_group_of_decoder
 from .m3ae_module import M3AETransformerSS, _Base, _HParams, pl
 
@@ -229,108 +229,44 @@ class Decoder(nn.Module):
     @torch.no_grad()
     @ops.model_mode
     def search_path_async(self, cross_attn_feats, cls_id=101, sep_id=102, eos_id=None, pad_id=0, lookahead=2, chunk=0):
-        """The greedy search of `search_path` with its bookkeeping on the device (csrc/greedy.hip): per step the decoder row, the
-        vocabulary GEMM, ops.greedy_argmax (on the logits as the GEMM left them: bf16 in perf mode, a strided view of the padded
-        vocabulary) and ops.greedy_step are enqueued with no blocking host call, and the result stays on the device.  Returns a
-        namespace with `seq` int64 [B, max_len] (pad after a row's first [SEP] / EOS), `len` int64 [B] (tokens up to and with
-        that one; max_len for a row that never finished), `err` int64 [1] (nonzero: a decoded token left the vocabulary), `out`
-        (the three in one buffer), `steps` (decoding steps enqueued) and `state` (ops.GreedyState).
-
-        Early exit as in T5's generate_async (ops.OpenCountWatch): the host runs at most `lookahead` steps ahead of the newest
-        step known to have completed and stops once a completed step reports no open row; lookahead=None runs all max_len steps.
-        Steps past the one that finished the last row write pad only, so the tokens are the same either way."""
-        watch = ops.OpenCountWatch(self.max_len, lookahead)
-        B, dev = cross_attn_feats.shape[0], cross_attn_feats.device
-        D = self.target_embedding.weight.shape[1]
-        enc_kv = self.dec_layers[self.num_layers - 1].cross_kv(cross_attn_feats.to(self.head_dtype))
-        cache = torch.empty((B, self.max_len, 2 * D), dtype=self.head_dtype, device=dev)
-        st = ops.GreedyState(B, self.max_len, dev, cls_id, pad_id)
-        # the sinusoid row of every position repeated B times, once per call: step `pos` reads pe_rows[pos] ([B, D], contiguous)
-        pe_rows = self.positional_encoding.pe[0, :self.max_len].to(torch.float32)[:, None, :].expand(self.max_len, B, D).contiguous()
-        ws, steps = None, 0
-        for pos in range(self.max_len):
-            logits = self.step_logits(st.last_tok.view(B, 1), pos, enc_kv, cache, pe_rows[pos])
-            if ws is None:
-                V = logits.shape[-1]
-                ws = ops.greedy_workspace(B, V, dev, chunk)
-            ops.greedy_argmax(logits, chunk, ws)
-            ops.greedy_step(st, ws, V, pos, sep_id, eos_id, pad_id)
-            steps += 1
-            if watch.enqueued(st.open_count, pos):
-                break
-        return NS(seq=st.seq, len=st.len, err=st.err, out=st.out, steps=steps, state=st)
+        """The greedy search of `search_path` with its bookkeeping on the device (csrc/greedy.hip, search.Greedy: the argmax reads the
+        logits as the GEMM left them, bf16 in perf mode, a strided view of the padded vocabulary), enqueued with no blocking host
+        call.  Returns a namespace on the device: `seq` int64 [B, max_len] (pad after a row's first [SEP] / EOS), `len` int64 [B]
+        (tokens up to and with that one; max_len for a row that never finished), `err` int64 [1] (nonzero: a decoded token left the
+        vocabulary), `out` (the three in one buffer), `steps` (decoding steps enqueued) and `state` (ops.GreedyState).  The loop is
+        search.run's: it leaves at most `lookahead` steps past the one that finished the last row; None runs all max_len steps."""
+        if lookahead is not None and lookahead < 1:   # ops.OpenCountWatch's rule, raised before any device work
+            raise ValueError("lookahead must be >= 1 or None")
+        greedy = Greedy(cross_attn_feats.shape[0], self.max_len, cross_attn_feats.device, cls_id, sep_id, eos_id, pad_id, chunk)
+        return run_search(DecoderHead(self, cross_attn_feats, self.max_len), greedy, self.max_len, lookahead)
 
     @torch.no_grad()
     @ops.model_mode
     def answer_path_async(self, cross_attn_feats, trie, cls_id=101, pad_id=0, lookahead=2, chunk=0):
-        """Answer-list decoding (csrc/answer_trie.hip): the loop of `search_path_async` with every step's token restricted to the
-        continuations `trie` (m3ae_amd.answer_trie.AnswerTrie) allows, so that every row ends as an entry of the answer list.
-        Per step the decoder row, the vocabulary GEMM, ops.trie_scan and ops.trie_step are enqueued with no blocking host call.
-        At most trie.depth steps.  Returns a namespace with `label` int64 [B] (the list entry), `score` float64 [B] (the sum of
-        the chosen tokens' log-probabilities under the unconstrained softmax), `seq` int64 [B, max_len], `len` int64 [B], `err`
-        int64 [1] (nonzero: the table led a row out of its range), `out` (the five in one buffer), `steps` and `state`
-        (ops.TrieState).  Greedy on a trie: the entry found is not always the list's most probable one."""
+        """Answer-list decoding (csrc/answer_trie.hip, search.TrieGreedy): `search_path_async` with every step's token restricted to
+        the continuations `trie` (m3ae_amd.answer_trie.AnswerTrie) allows, so every row ends as an entry of the answer list, after at
+        most trie.depth steps (lookahead None or 0: all of them).  Returns a namespace with `label` int64 [B] (the list entry),
+        `score` float64 [B] (the sum of the chosen tokens' log-probabilities under the unconstrained softmax), `seq`, `len`, `err`
+        (nonzero: the table led a row out of its range), `out` (all in one buffer), `steps` and `state` (ops.TrieState).  Greedy on
+        a trie: the entry found is not always the list's most probable one."""
         B, dev = cross_attn_feats.shape[0], cross_attn_feats.device
-        D = self.target_embedding.weight.shape[1]
         dt = trie.to_device(dev, self.final_linear.weight.shape[0], self.max_len)
-        depth = dt.depth
-        watch = ops.OpenCountWatch(depth, lookahead or None)   # None or 0: no early exit, all `depth` steps
-        enc_kv = self.dec_layers[self.num_layers - 1].cross_kv(cross_attn_feats.to(self.head_dtype))
-        cache = torch.empty((B, self.max_len, 2 * D), dtype=self.head_dtype, device=dev)
-        st = ops.TrieState(B, self.max_len, dev, cls_id, pad_id)
-        pe_rows = self.positional_encoding.pe[0, :depth].to(torch.float32)[:, None, :].expand(depth, B, D).contiguous()
-        ws, steps = None, 0
-        for pos in range(depth):
-            logits = self.step_logits(st.last_tok.view(B, 1), pos, enc_kv, cache, pe_rows[pos])
-            if ws is None:
-                ws = ops.trie_workspace(B, logits.shape[-1], dev, chunk)
-            ops.trie_scan(logits, dt, st, chunk, ws)
-            ops.trie_step(logits, dt, st, ws, pos, pad_id, chunk)
-            steps += 1
-            if watch.enqueued(st.open_count, pos):
-                break
-        return NS(label=st.label, score=st.score, seq=st.seq, len=st.len, err=st.err, out=st.out, steps=steps, state=st)
+        greedy = TrieGreedy(B, self.max_len, dt, dev, cls_id, pad_id, chunk)
+        return run_search(DecoderHead(self, cross_attn_feats, dt.depth), greedy, dt.depth, lookahead or None)
 
     @torch.no_grad()
     @ops.model_mode
     def answer_beam_async(self, cross_attn_feats, trie, num_beams=4, length_penalty=0.0, cls_id=101, pad_id=0, lookahead=2, chunk=0):
-        """Constrained beam search on the answer list (csrc/trie_beam.hip): the loop of `answer_path_async` at R = B * num_beams
-        rows, 1 <= num_beams <= 8, with HF's BeamSearchScorer semantics and the trie as the prefix constraint.  Per step the
-        decoder row, the vocabulary GEMM, ops.trie_scan (dead slots skipped), ops.trie_beam_select, ops.trie_beam_step and the
-        re-ordering of the self-attention cache through `state.order` are enqueued with no blocking host call; at most
-        trie.depth steps.  Returns the namespace of `answer_path_async` plus the n-best list: `labels` int64 [B, num_beams]
-        (-1 = no entry), `scores` float64 [B, num_beams] (log-probability / length ** length_penalty, descending), `logprob`
-        float64 [B, num_beams] (the raw sums), `n_hyp` int64 [B]; `label` / `score` are column 0 and `seq` / `len` belong to it.
-        With num_beams >= the number of answers the search is exhaustive: label = the list's arg-max of the normalised score.
-        length_penalty 0 (default) ranks by the sequence log-probability, 1 is HF's length-normalised ranking."""
+        """Constrained beam search on the answer list (csrc/trie_beam.hip, search.TrieBeam): `answer_path_async` at B * num_beams
+        rows, 1 <= num_beams <= 8, with HF's BeamSearchScorer semantics and the trie as the prefix constraint.  Returns its namespace
+        plus the n-best list: `labels` int64 [B, num_beams] (-1 = no entry), `scores` float64 [B, num_beams] (log-probability /
+        length ** length_penalty, descending), `logprob` (the raw sums), `n_hyp` int64 [B]; `label` / `score` are column 0 and `seq`
+        / `len` belong to it.  With num_beams >= the number of answers the search is exhaustive: label = the list's arg-max of the
+        normalised score.  length_penalty 0 (default) ranks by the sequence log-probability, 1 is HF's length-normalised ranking."""
         B, nb, dev = cross_attn_feats.shape[0], int(num_beams), cross_attn_feats.device
-        R = B * nb
-        D = self.target_embedding.weight.shape[1]
         dt = trie.to_device(dev, self.final_linear.weight.shape[0], self.max_len, pad_id=pad_id)
-        depth = dt.depth
-        st = ops.TrieBeamState(B, nb, self.max_len, dev, cls_id, pad_id)
-        watch = ops.OpenCountWatch(depth, lookahead or None)   # None or 0: no early exit, all `depth` steps
-        enc_kv = self.dec_layers[self.num_layers - 1].cross_kv(cross_attn_feats.to(self.head_dtype))
-        enc_kv = enc_kv.repeat_interleave(nb, dim=0)
-        cache = torch.empty((R, depth, 2 * D), dtype=self.head_dtype, device=dev)
-        pe_rows = self.positional_encoding.pe[0, :depth].to(torch.float32)[:, None, :].expand(depth, R, D).contiguous()
-        ws, steps = None, 0
-        for pos in range(depth):
-            logits = self.step_logits(st.last_tok.view(R, 1), pos, enc_kv, cache, pe_rows[pos])
-            if ws is None:
-                V = logits.shape[-1]
-                ws = ops.trie_workspace(R, V, dev, chunk)
-            ops.trie_scan(logits, dt, st, chunk, ws)
-            ops.trie_beam_select(logits, dt, st, ws, chunk)
-            ops.trie_beam_step(dt, st, V, pos, length_penalty)
-            steps += 1
-            if watch.enqueued(st.open_count, pos):
-                break
-            if pos + 1 < depth:
-                cache = ops.gather_rows(cache.view(R, -1), st.order).view_as(cache)
-        ops.trie_beam_result(dt, st)
-        return NS(label=st.label, score=st.score, labels=st.labels, scores=st.scores, logprob=st.logprob, n_hyp=st.n_hyp, seq=st.seq,
-                  len=st.len, err=st.err, out=st.out, steps=steps, state=st)
+        beam = TrieBeam(B, nb, self.max_len, dt, dev, cls_id, pad_id, length_penalty, chunk)
+        return run_search(DecoderHead(self, cross_attn_feats, dt.depth, nb), beam, dt.depth, lookahead or None)
 
     @torch.no_grad()
     @ops.model_mode
@@ -345,8 +281,7 @@ class Decoder(nn.Module):
             if not use_cache:
                 raise ValueError("search='device' decodes one cached row per step: use_cache=False is the host form's")
             r = self.search_path_async(cross_attn_feats, cls_id, sep_id, eos_id, pad_id, lookahead)
-            if int(r.out.cpu()[-1]) != 0:
-                raise ops._lib.M3AEHipError("device greedy search: a decoded token left [0, vocab_size)")
+            r.state.host()        # the one copy: raises if a decoded token left [0, vocab_size)
             return r.seq
         if search != "host":
             raise ValueError(f"search must be 'host' or 'device', got {search!r}")
@@ -377,39 +312,6 @@ class Decoder(nn.Module):
         after = (special.long().cumsum(1) - special.long()) > 0  # strictly after the first special token
         seq = torch.where(after, torch.full_like(seq, pad_id), seq)
         return torch.nn.functional.pad(seq, (0, self.max_len - seq.shape[1]), value=pad_id)
-
-
-def answer_result(r, label2ans=None, k=1):
-    """One copy of an answer-list search's `out` buffer (Decoder.answer_path_async / answer_beam_async, T5.constrained_greedy_async /
-    constrained_beam_async) -> (labels int64 [B], scores float64 [B]) on the host; raises if the error word is set.  With label2ans:
-    a list of (answer, score) through label2ans[str(label)] (m3ae_module.answers_of's rule).  k > 1 (a beam search with
-    num_beams >= k): the k best entries per row instead -- (labels [B, k] with -1 for a missing entry, scores [B, k]), or with
-    label2ans a list of B lists of up to k (answer, score)."""
-    out = r.out.cpu()
-    if int(out[-1]) != 0:
-        raise ops._lib.M3AEHipError("answer-list decoding: the answer table led a row out of its range")
-    B = r.label.shape[0]
-    n = r.seq.numel()
-    k = int(k)
-    if hasattr(r, "labels"):   # the beam form: seq | len | labels [B, nb] | scores [B, nb] | logprob | n_hyp | err
-        nb = r.labels.shape[1]
-        if not 1 <= k <= nb:
-            raise ValueError(f"answer_result: k={k} outside [1, num_beams={nb}]")
-        o = n + B
-        labels2 = out[o:o + B * nb].view(B, nb)[:, :k].clone()
-        scores2 = out[o + B * nb:o + 2 * B * nb].view(torch.float64).view(B, nb)[:, :k].clone()
-    else:
-        if k != 1:
-            raise ValueError(f"answer_result: k={k} needs a beam search (num_beams >= k); the greedy search returns one entry")
-        labels2 = out[n + B:n + 2 * B].clone().view(B, 1)
-        scores2 = out[n + 2 * B:n + 3 * B].view(torch.float64).clone().view(B, 1)
-    if label2ans is None:
-        return (labels2[:, 0], scores2[:, 0]) if k == 1 else (labels2, scores2)
-    from .m3ae_module import answers_of
-    if k == 1:      # column 0 as it is: a row that ended without a label (-1) is a KeyError of answers_of, as it always was
-        return [row[0] for row in answers_of(labels2.tolist(), scores2.tolist(), label2ans)]
-    rows = [[(l, s) for l, s in zip(lr, sr) if l >= 0] for lr, sr in zip(labels2.tolist(), scores2.tolist())]   # -1 = no entry
-    return answers_of([[l for l, _ in row] for row in rows], [[s for _, s in row] for row in rows], label2ans)
 
 
 class DecoderModel(_Base):

@@ -19,6 +19,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..param_store import ParamStore, group_hparams_decoder, param_group_of_decoder
+from ..search import answer_result
 from .m3ae_module import M3AETransformerSS, _Base, _HParams, pl
 from .t5 import T5ForConditionalGeneration
 
@@ -163,7 +164,6 @@ class T5VQA_MMEncoderInput(_Base):
     def answer(self, batch, trie, label2ans=None, num_beams=1, k=1, length_penalty=0.0):
         """As DecoderModel.answer: (labels, scores) on the host after one copy, or (answer, score) pairs with label2ans; the k best
         of a num_beams search when asked."""
-        from .m3ae_decoder import answer_result
         return answer_result(self.answer_async(batch, trie, num_beams=num_beams, length_penalty=length_penalty), label2ans, k)
 
     def training_step(self, batch, batch_idx=0):

@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..param_store import PackedParam
+from ..search import Beam, T5Head, TrieBeam, TrieGreedy, run as run_search
 
 T5_ARCH = {
     "t5-small": dict(d_model=512, d_kv=64, d_ff=2048, num_layers=6, num_decoder_layers=6, num_heads=8),
@@ -286,101 +287,38 @@ class T5ForConditionalGeneration(nn.Module):
     @torch.no_grad()
     def generate_async(self, enc, num_beams=4, max_length=12, eos_token_id=1, pad_token_id=0, length_penalty=1.0,
                        len_offset=0, lookahead=2, topk_chunk=0):
-        """The beam search of `generate` with its bookkeeping on the device (csrc/beam.hip): per step the decoder row, the
-        vocabulary GEMM, ops.beam_topk, ops.beam_step and the cache re-ordering are enqueued with no blocking host call, and
-        the result stays on the device.  Returns a namespace with `seq` int64 [B, max_length] (pad-filled), `len` int64 [B]
-        (length of the best hypothesis, before the EOS), `err` int64 [1] (nonzero: a candidate index left its range), `out`
-        (the three in one buffer), `steps` (decoding steps enqueued) and `state` (ops.BeamState).
-
-        Early exit (ops.OpenCountWatch): steps after every sample is done change no token, so leaving the loop is an
-        optimisation only.  The count of open samples after each step is copied to pinned host memory behind the step, with an
-        event; the host runs at most `lookahead` steps past the newest step whose event has completed (it waits on the event of
-        the step `lookahead` back, so the device always has work queued) and stops enqueuing once a completed step reports zero
-        open samples.  lookahead=None always runs max_length - 1 steps."""
-        watch = ops.OpenCountWatch(max_length, lookahead, first=1)
-        B, nb, dev = enc.shape[0], num_beams, enc.device
-        R = B * nb
-        enc_r = enc.repeat_interleave(nb, dim=0).contiguous()
-        Ls = enc.shape[1]
-        cross_kv = [kv.view(B, Ls, -1).repeat_interleave(nb, dim=0).reshape(R * Ls, -1) for kv in self.decoder.cross_kv(enc)]
-        self_cache = self.decoder.new_self_cache(R, max_length, enc.dtype, dev)
-        st = ops.BeamState(B, nb, max_length, dev, self.config.decoder_start_token_id, pad_token_id)
-        ws = None
-        top = (torch.empty((B, 2 * nb), dtype=torch.float32, device=dev), torch.empty((B, 2 * nb), dtype=torch.int32, device=dev))
-        steps, cur_len = 0, 1
-        while cur_len < max_length:
-            logits = self.next_token_logits_cached(enc_r, st.last_tok.view(R, 1), cross_kv, self_cache, cur_len - 1)
-            if ws is None:
-                V = logits.shape[-1]
-                ws = ops.beam_topk_workspace(B, nb, V, dev, topk_chunk)
-            ops.beam_topk(logits, st.beam_scores, B, nb, topk_chunk, ws, top)
-            ops.beam_step(st, top[0], top[1], V, cur_len, eos_token_id, pad_token_id, length_penalty)
-            self_cache = [ops.gather_rows(c.view(R, -1), st.order).view_as(c) for c in self_cache]
-            steps += 1
-            cur_len += 1
-            if watch.enqueued(st.open_count, cur_len - 1):
-                break
-        ops.beam_finalize(st, cur_len, eos_token_id, pad_token_id, length_penalty, len_offset)
-        return NS(seq=st.seq, len=st.len, err=st.err, out=st.out, steps=steps, state=st)
+        """The beam search of `generate` with its bookkeeping on the device (csrc/beam.hip, search.Beam), enqueued with no blocking
+        host call.  Returns a namespace on the device: `seq` int64 [B, max_length] (pad-filled), `len` int64 [B] (length of the best
+        hypothesis, before the EOS), `err` int64 [1] (nonzero: a candidate index left its range), `out` (the three in one buffer),
+        `steps` (decoding steps enqueued) and `state` (ops.BeamState).  The loop is search.run's: it leaves at most `lookahead`
+        steps past the one that closed the last sample (later steps change no token); None always runs max_length - 1 steps."""
+        if lookahead is not None and lookahead < 1:   # ops.OpenCountWatch's rule, raised before any device work
+            raise ValueError("lookahead must be >= 1 or None")
+        beam = Beam(enc.shape[0], num_beams, max_length, enc.device, self.config.decoder_start_token_id, eos_token_id, pad_token_id,
+                    length_penalty, len_offset, topk_chunk)
+        return run_search(T5Head(self, enc, max_length - 1, num_beams), beam, max_length - 1, lookahead, first=1)
 
     @torch.no_grad()
     def constrained_greedy_async(self, enc, trie, max_length=12, pad_token_id=0, lookahead=2, chunk=0):
-        """Answer-list decoding (csrc/answer_trie.hip): greedy search over `next_token_logits_cached` with one beam (no cache
-        re-ordering), every step's token restricted to the continuations `trie` (m3ae_amd.answer_trie.AnswerTrie, sequences
-        ending in </s>) allows.  At most trie.depth <= max_length steps, no blocking host call.  Returns the namespace of
-        Decoder.answer_path_async: `label` int64 [B], `score` float64 [B] (sum of log-probabilities), `seq` int64
-        [B, max_length] (the generated tokens, WITHOUT the start token; pad after the end token), `len`, `err`, `out`, `steps`,
-        `state`.  `constrained_beam_async` is the beam form."""
-        B, dev = enc.shape[0], enc.device
-        dt = trie.to_device(dev, self.config.vocab_size, max_length)
-        watch = ops.OpenCountWatch(dt.depth, lookahead or None)   # None or 0: no early exit, all `depth` steps
-        cross_kv = [kv.view(B, enc.shape[1], -1).reshape(B * enc.shape[1], -1) for kv in self.decoder.cross_kv(enc)]
-        self_cache = self.decoder.new_self_cache(B, max_length, enc.dtype, dev)
-        st = ops.TrieState(B, max_length, dev, self.config.decoder_start_token_id, pad_token_id)
-        ws, steps = None, 0
-        for pos in range(dt.depth):
-            logits = self.next_token_logits_cached(enc, st.last_tok.view(B, 1), cross_kv, self_cache, pos)
-            if ws is None:
-                ws = ops.trie_workspace(B, logits.shape[-1], dev, chunk)
-            ops.trie_scan(logits, dt, st, chunk, ws)
-            ops.trie_step(logits, dt, st, ws, pos, pad_token_id, chunk)
-            steps += 1
-            if watch.enqueued(st.open_count, pos):
-                break
-        return NS(label=st.label, score=st.score, seq=st.seq, len=st.len, err=st.err, out=st.out, steps=steps, state=st)
+        """Answer-list decoding (csrc/answer_trie.hip, search.TrieGreedy): greedy search with every step's token restricted to the
+        continuations `trie` (m3ae_amd.answer_trie.AnswerTrie, sequences ending in </s>) allows; at most trie.depth <= max_length
+        steps, no blocking host call.  Returns the namespace of Decoder.answer_path_async: `label`, `score` (sum of log-probabilities),
+        `seq` int64 [B, max_length] (the generated tokens, WITHOUT the start token; pad after the end token), `len`, `err`, `out`,
+        `steps`, `state`.  `constrained_beam_async` is the beam form."""
+        dt = trie.to_device(enc.device, self.config.vocab_size, max_length)
+        greedy = TrieGreedy(enc.shape[0], max_length, dt, enc.device, self.config.decoder_start_token_id, pad_token_id, chunk)
+        return run_search(T5Head(self, enc, dt.depth), greedy, dt.depth, lookahead or None)   # None or 0: no early exit
 
     @torch.no_grad()
     def constrained_beam_async(self, enc, trie, num_beams=4, max_length=12, length_penalty=0.0, pad_token_id=0, lookahead=2, chunk=0):
-        """Constrained beam search on the answer list (csrc/trie_beam.hip): the loop of `constrained_greedy_async` at
-        R = B * num_beams rows, 1 <= num_beams <= 8.  Encoder rows and cross keys / values are repeated as `generate_async` does,
-        the self cache is re-ordered through `state.order` each step, no blocking host call, at most trie.depth <= max_length
-        steps.  Returns the namespace of Decoder.answer_beam_async: `labels` / `scores` / `logprob` [B, num_beams], `n_hyp`, and
-        `label`, `score`, `seq`, `len` of the best entry (seq WITHOUT the start token, pad after the end token)."""
-        B, nb, dev = enc.shape[0], int(num_beams), enc.device
-        R, Ls = B * nb, enc.shape[1]
-        dt = trie.to_device(dev, self.config.vocab_size, max_length, pad_id=pad_token_id)
-        st = ops.TrieBeamState(B, nb, max_length, dev, self.config.decoder_start_token_id, pad_token_id)
-        watch = ops.OpenCountWatch(dt.depth, lookahead or None)   # None or 0: no early exit, all `depth` steps
-        enc_r = enc.repeat_interleave(nb, dim=0).contiguous()
-        cross_kv = [kv.view(B, Ls, -1).repeat_interleave(nb, dim=0).reshape(R * Ls, -1) for kv in self.decoder.cross_kv(enc)]
-        self_cache = self.decoder.new_self_cache(R, dt.depth, enc.dtype, dev)
-        ws, steps = None, 0
-        for pos in range(dt.depth):
-            logits = self.next_token_logits_cached(enc_r, st.last_tok.view(R, 1), cross_kv, self_cache, pos)
-            if ws is None:
-                V = logits.shape[-1]
-                ws = ops.trie_workspace(R, V, dev, chunk)
-            ops.trie_scan(logits, dt, st, chunk, ws)
-            ops.trie_beam_select(logits, dt, st, ws, chunk)
-            ops.trie_beam_step(dt, st, V, pos, length_penalty)
-            steps += 1
-            if watch.enqueued(st.open_count, pos):
-                break
-            if pos + 1 < dt.depth:
-                self_cache = [ops.gather_rows(c.view(R, -1), st.order).view_as(c) for c in self_cache]
-        ops.trie_beam_result(dt, st)
-        return NS(label=st.label, score=st.score, labels=st.labels, scores=st.scores, logprob=st.logprob, n_hyp=st.n_hyp, seq=st.seq,
-                  len=st.len, err=st.err, out=st.out, steps=steps, state=st)
+        """Constrained beam search on the answer list (csrc/trie_beam.hip, search.TrieBeam): `constrained_greedy_async` at
+        R = B * num_beams rows, 1 <= num_beams <= 8; no blocking host call, at most trie.depth <= max_length steps.  Returns the
+        namespace of Decoder.answer_beam_async: `labels` / `scores` / `logprob` [B, num_beams], `n_hyp`, and `label`, `score`,
+        `seq`, `len` of the best entry (seq WITHOUT the start token, pad after the end token)."""
+        nb, start = int(num_beams), self.config.decoder_start_token_id
+        dt = trie.to_device(enc.device, self.config.vocab_size, max_length, pad_id=pad_token_id)
+        beam = TrieBeam(enc.shape[0], nb, max_length, dt, enc.device, start, pad_token_id, length_penalty, chunk)
+        return run_search(T5Head(self, enc, dt.depth, nb), beam, dt.depth, lookahead or None)   # None or 0: no early exit
 
     @torch.no_grad()
     def generate(self, enc, num_beams=4, max_length=12, eos_token_id=1, pad_token_id=0, length_penalty=1.0,
@@ -394,23 +332,15 @@ class T5ForConditionalGeneration(nn.Module):
         plus one copy of its result at the end; same tokens."""
         if beam_search == "device":
             r = self.generate_async(enc, num_beams, max_length, eos_token_id, pad_token_id, length_penalty, len_offset, lookahead)
-            out = r.out.cpu()
-            if int(out[-1]) != 0:
-                raise ops._lib.M3AEHipError("device beam search: a candidate index left [0, num_beams * vocab_size)")
-            B = enc.shape[0]
-            L = min(int(out[B * max_length:-1].max()) + 1, max_length)
-            return out[:B * max_length].view(B, max_length)[:, :L].contiguous().to(enc.device)
+            h = r.state.host()        # the one copy: raises if a candidate index left [0, num_beams * vocab_size)
+            return h.seq[:, :min(int(h.len.max()) + 1, max_length)].contiguous().to(enc.device)
         if beam_search != "host":
             raise ValueError(f"beam_search must be 'host' or 'device', got {beam_search!r}")
         B, nb, dev = enc.shape[0], num_beams, enc.device
-        enc_r = enc.repeat_interleave(nb, dim=0).contiguous()
-        # encoder-side keys / values once per call; the beams of a sample share their encoder rows, so re-ordering beams
-        # never touches this cache
-        Ls = enc.shape[1]
-        cross_kv = [kv.view(B, Ls, -1).repeat_interleave(nb, dim=0).reshape(B * nb * Ls, -1) for kv in self.decoder.cross_kv(enc)]
+        # the device form's set-up (the beams' own keys / values are re-ordered with the beams: HF `_reorder_cache`), the host's own loop
+        head = T5Head(self, enc, max_length, nb)
+        enc_r, cross_kv, self_cache = head.enc, head.cross_kv, head.cache
         ids = torch.full((B * nb, 1), self.config.decoder_start_token_id, dtype=torch.long, device=dev)
-        # the beams' own keys / values: one decoder row per step; re-ordered with the beams (HF `_reorder_cache`)
-        self_cache = self.decoder.new_self_cache(B * nb, max_length, enc.dtype, dev)
         beam_scores = torch.zeros(B, nb, device=dev)
         beam_scores[:, 1:] = -1e9
         beam_scores = beam_scores.view(-1)

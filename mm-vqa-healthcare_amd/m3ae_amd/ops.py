@@ -12,6 +12,7 @@ import functools
 import math
 import os
 import threading
+from types import SimpleNamespace as _NS
 from typing import NamedTuple
 
 import torch
@@ -2037,8 +2038,33 @@ def beam_topk(logits, beam_scores, B, nb, chunk=0, ws=None, out=None):
     return top_s, top_i
 
 
-class BeamState:
+class _SearchState:
+    """What the four search states share: every result field and the error word `err` live in ONE int64 buffer `out`, so one copy
+    brings a whole result to the host.  `layout` ({field: shape} in buffer order, then err; `scores` and `logprob` hold the bits of
+    float64) is the only description of that buffer: views() applies it to the device buffer (alloc_out) and to a host copy (host).
+    The answer-list states hold `labels` / `scores` [B, nb] for search.answer_result; k_text is its word on a k outside [1, nb]."""
+
+    def views(self, out):
+        parts = out.split([math.prod(shape) for shape in self.layout.values()] + [1])
+        return _NS(err=parts[-1], **{n: (p.view(torch.float64) if n in ("scores", "logprob") else p).view(shape)
+                                     for (n, shape), p in zip(self.layout.items(), parts)})
+
+    def alloc_out(self, device, **layout):
+        self.layout = layout
+        self.out = torch.zeros((sum(map(math.prod, layout.values())) + 1,), dtype=torch.int64, device=device)
+        vars(self).update(vars(self.views(self.out)))
+
+    def host(self):
+        """One device-to-host copy of `out` -> the namespace of its fields on the host; raises if the error word is set."""
+        h = self.views(self.out.cpu())
+        if int(h.err) != 0:
+            raise _lib.M3AEHipError(self.err_text)
+        return h
+
+
+class BeamState(_SearchState):
     """The device state of one beam search (include/m3ae_hip.h, m3ae_beam_step): allocated once per generate call."""
+    err_text = "device beam search: a candidate index left [0, num_beams * vocab_size)"
 
     def __init__(self, B, nb, max_length, device, start_id=0, pad_id=0):
         R = B * nb
@@ -2057,8 +2083,7 @@ class BeamState:
         self.hyp_len = z((B, nb), dtype=torch.int32)
         self.hyp_tok = z((B, nb, max_length), dtype=torch.int64)
         self.open_count = z((max_length,), dtype=torch.int32)
-        self.out = z((B * max_length + B + 1,), dtype=torch.int64)   # seq | len | error word: one copy brings all three to the host
-        self.seq, self.len, self.err = self.out[:B * max_length].view(B, max_length), self.out[B * max_length:-1], self.out[-1:]
+        self.alloc_out(device, seq=(B, max_length), len=(B,))
 
 
 def beam_step(st, top_s, top_i, V, cur_len, eos_id, pad_id, length_penalty=1.0):
@@ -2090,7 +2115,7 @@ def beam_finalize(st, cur_len, eos_id, pad_id, length_penalty=1.0, len_offset=0)
 
 
 class OpenCountWatch:
-    """The early exit of a device-resident search loop (t5.generate_async, Decoder.search_path_async).  Steps after every row is
+    """The early exit of the device-resident search loop (search.run, the one loop of all six searches).  Steps after every row is
     done change no token, so leaving the loop is an optimisation only.  The count of open rows after each step is copied to pinned
     host memory behind the step, with an event; the host runs at most `lookahead` steps past the newest step whose event has
     completed (it waits on the event of the step `lookahead` back, so the device always has work queued) and stops enqueuing once a
@@ -2158,13 +2183,13 @@ def greedy_argmax(logits, chunk=0, ws=None, out=None):
     return ws if out is None else out
 
 
-class GreedyState:
+class GreedyState(_SearchState):
     """The device state of one greedy search (include/m3ae_hip.h, m3ae_greedy_step): allocated once per search_path call."""
+    err_text = "device greedy search: a decoded token left [0, vocab_size)"
 
-    def __init__(self, B, max_len, device, cls_id=101, pad_id=0):
+    def __init__(self, B, max_len, device, cls_id=101, pad_id=0, **more):
         self.B, self.max_len = B, max_len
-        self.out = torch.zeros((B * max_len + B + 1,), dtype=torch.int64, device=device)   # seq | len | error word: one copy brings all three to the host
-        self.seq, self.len, self.err = self.out[:B * max_len].view(B, max_len), self.out[B * max_len:-1], self.out[-1:]
+        self.alloc_out(device, seq=(B, max_len), len=(B,), **more)
         self.seq.fill_(pad_id)
         self.len.fill_(max_len)
         self.last_tok = torch.full((B,), cls_id, dtype=torch.int64, device=device)
@@ -2200,24 +2225,17 @@ def trie_workspace(R, V, device, chunk=0):
     return torch.empty((R, n // (8 * R)), dtype=torch.int64, device=device)
 
 
-class TrieState:
-    """The device state of one answer-list search (include/m3ae_hip.h, m3ae_trie_step): allocated once per call.  `trie` is what
-    AnswerTrie.to_device returned."""
+class TrieState(GreedyState):
+    """The device state of one answer-list search (include/m3ae_hip.h, m3ae_trie_step): allocated once per call.  The greedy
+    search's state plus each row's trie node, label and score (in `out` as the beam state's n-best list with nb = 1)."""
+    err_text = "answer-list decoding: the answer table led a row out of its range"
+    k_text, nb = "answer_result: k={k} needs a beam search (num_beams >= k); the greedy search returns one entry", 1
 
     def __init__(self, B, max_len, device, start_id=101, pad_id=0):
-        self.B, self.max_len = B, max_len
-        n = B * max_len
-        # seq | len | label | score (the bits of float64) | error word: one copy brings all five to the host
-        self.out = torch.zeros((n + 3 * B + 1,), dtype=torch.int64, device=device)
-        self.seq, self.len, self.label = self.out[:n].view(B, max_len), self.out[n:n + B], self.out[n + B:n + 2 * B]
-        self.score, self.err = self.out[n + 2 * B:n + 3 * B].view(torch.float64), self.out[-1:]
-        self.seq.fill_(pad_id)
-        self.len.fill_(max_len)
+        super().__init__(B, max_len, device, start_id, pad_id, labels=(B, 1), scores=(B, 1))
+        self.label, self.score = self.labels[:, 0], self.scores[:, 0]
         self.label.fill_(-1)
-        self.last_tok = torch.full((B,), start_id, dtype=torch.int64, device=device)
         self.node = torch.zeros((B,), dtype=torch.int32, device=device)
-        self.finished = torch.zeros((B,), dtype=torch.int32, device=device)
-        self.open_count = torch.zeros((max_len,), dtype=torch.int32, device=device)
 
 
 def _trie_logits(what, logits, st):
@@ -2274,25 +2292,18 @@ def trie_step(logits, trie, st, ws, pos, pad_id, chunk=0):
 TRIE_MAX_BEAMS = 8
 
 
-class TrieBeamState:
+class TrieBeamState(_SearchState):
     """The device state of one constrained beam search (include/m3ae_hip.h, m3ae_triebeam_step): allocated once per call.
     R = B * nb beam rows; `B` is the row count trie_scan sees (it runs over the beam rows with `finished` = the dead flags), `Bs`
-    the number of samples.  The result is the hypothesis list of every sample, in `out`:
-    seq [Bs, max_len] | len [Bs] | labels [Bs, nb] | scores [Bs, nb] | logprob [Bs, nb] (the bits of float64) | n_hyp [Bs] | err."""
+    the number of samples.  The result is the hypothesis list of every sample, in `out`."""
+    err_text, k_text = TrieState.err_text, "answer_result: k={k} outside [1, num_beams={nb}]"
 
     def __init__(self, Bs, nb, max_len, device, start_id=101, pad_id=0):
         if not 1 <= nb <= TRIE_MAX_BEAMS:
             raise ValueError(f"TrieBeamState: num_beams={nb} outside [1, {TRIE_MAX_BEAMS}]")
         R = Bs * nb
         self.Bs, self.nb, self.B, self.max_len, self.pad_id = Bs, nb, R, max_len, pad_id
-        n, h = Bs * max_len, Bs * nb
-        self.out = torch.zeros((n + Bs + 3 * h + Bs + 1,), dtype=torch.int64, device=device)
-        o = self.out
-        self.seq, self.len = o[:n].view(Bs, max_len), o[n:n + Bs]
-        o = o[n + Bs:]
-        self.labels, self.scores, self.logprob = o[:h].view(Bs, nb), o[h:2 * h].view(torch.float64).view(Bs, nb), \
-            o[2 * h:3 * h].view(torch.float64).view(Bs, nb)
-        self.n_hyp, self.err = o[3 * h:3 * h + Bs], o[-1:]
+        self.alloc_out(device, seq=(Bs, max_len), len=(Bs,), labels=(Bs, nb), scores=(Bs, nb), logprob=(Bs, nb), n_hyp=(Bs,))
         self.seq.fill_(pad_id)
         self.labels.fill_(-1)
         self.label, self.score = self.labels[:, 0], self.scores[:, 0]

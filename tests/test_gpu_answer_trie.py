@@ -376,7 +376,7 @@ def test_answer_path_equals_a_host_loop_over_step_logits(models, feats, mode):
     for chunk in (256, 1000):
         q = d.answer_path_async(feats, t, START, PAD, lookahead=None, chunk=chunk)
         assert torch.equal(q.seq, r.seq) and torch.equal(q.label, r.label)
-    from m3ae_amd.modules.m3ae_decoder import answer_result
+    from m3ae_amd.search import answer_result
     labels, scores = answer_result(r)
     assert labels.tolist() == mod.label.tolist() and np.array_equal(scores.numpy(), score)
     pairs = answer_result(r, {str(i): f"answer {i}" for i in range(len(seqs))})
@@ -491,6 +491,55 @@ def test_constrained_greedy_equals_a_host_loop_over_cached_logits(mode, monkeypa
     assert torch.equal(q.out, r.out)
     with pytest.raises(ValueError, match="room for"):
         m.constrained_greedy_async(enc, t, max_length=t.depth - 1)
+
+
+def small_list(end, depth):
+    """(answers, end ids): three answers of depth 3, or two of depth 1 (a second end id makes a second one-token answer possible)."""
+    return ([[7, 8, end], [7, 9, end], [11, end]], (end,)) if depth == 3 else ([[end], [7]], (end, 7))
+
+
+def recorded(monkeypatch, run):
+    """`run()` under a recording proxy of the library -> (its result, the entry points of the search families it called, in order,
+    the workspace-size query aside)."""
+    L = _lib.lib()
+    names = []
+
+    class Recording:
+        def __getattr__(self, name):
+            names.append(name)
+            return getattr(L, name)
+    monkeypatch.setattr(_lib, "_lib", Recording())
+    r = run()
+    monkeypatch.undo()
+    return r, [n for n in names if n.startswith(("m3ae_greedy_", "m3ae_beam_", "m3ae_trie_", "m3ae_triebeam_")) and not n.endswith("_workspace_bytes")]
+
+
+@pytest.mark.parametrize("depth", [3, 1])
+def test_list_searches_enqueue_scan_and_step_per_position(models, feats, monkeypatch, depth):
+    """Decoder.answer_path_async and T5.constrained_greedy_async, B = 2, no early exit: scan, step per position of the trie and
+    nothing else of the search families (depth 1: a single step); label / seq / len against the numpy model on the same cached logits."""
+    d = models("fp32").decoder
+    t5, enc = build_t5("fp32")
+    f2, enc, ML = feats[:2].contiguous(), enc[:2].contiguous(), 4
+    enc_kv = d.dec_layers[d.num_layers - 1].cross_kv(f2.to(d.head_dtype))
+    cache = torch.empty((2, MAX_LEN, 2 * 768), dtype=d.head_dtype, device=DEV)
+    cross_kv, self_cache = t5.decoder.cross_kv(enc), t5.decoder.new_self_cache(2, ML, enc.dtype, DEV)
+    ids = lambda last_tok: torch.from_numpy(last_tok).to(DEV).view(2, 1)    # noqa: E731
+    for end, max_len, start, run, logits_of in (
+            (SEP, MAX_LEN, START, lambda t: d.answer_path_async(f2, t, START, PAD, lookahead=None),
+             lambda last_tok, pos: d.step_logits(ids(last_tok), pos, enc_kv, cache).float().cpu().numpy()),
+            (1, ML, t5.config.decoder_start_token_id, lambda t: t5.constrained_greedy_async(enc, t, max_length=ML, pad_token_id=PAD, lookahead=None),
+             lambda last_tok, pos: t5.next_token_logits_cached(enc, ids(last_tok), cross_kv, self_cache, pos).cpu().numpy())):
+        seqs, ends = small_list(end, depth)
+        t = AnswerTrie(seqs, ends)
+        run(t)                                                  # warm: the trie is uploaded
+        r, names = recorded(monkeypatch, lambda: run(t))
+        assert names == ["m3ae_trie_scan", "m3ae_trie_step"] * depth and r.steps == depth == t.depth and int(r.err.cpu()) == 0
+        mod, _ = M.search(logits_of, t, 2, max_len, start, PAD, 0, 4, stop_early=False)
+        assert np.array_equal(r.label.cpu().numpy(), mod.label) and np.array_equal(r.seq.cpu().numpy(), mod.seq)
+        assert np.array_equal(r.len.cpu().numpy(), mod.len)
+        for b in range(2):
+            assert r.seq[b, :int(r.len[b])].cpu().tolist() == seqs[int(r.label[b])]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -381,6 +381,32 @@ def test_default_generate_calls_no_beam_entry_point(fixture_model, monkeypatch):
     assert {"m3ae_beam_topk", "m3ae_beam_step", "m3ae_beam_finalize"} <= set(counts), counts
 
 
+@pytest.mark.parametrize("max_length", [3, 2])
+def test_generate_async_enqueues_topk_and_step_per_position_then_finalize(fixture_model, monkeypatch, max_length):
+    """One call without early exit (B = 2, two beams) under a recording proxy of the library: the ordered search entry points (the
+    workspace-size query aside) are top-k, step per position, then finalize; the caches are re-ordered between steps only, so nothing
+    at all is enqueued between the last step and finalize (max_length 2: one step, no re-ordering).  Tokens against the host form."""
+    m, g, enc, _ = fixture_model
+    L = _lib.lib()
+    names = []
+
+    class Recording:
+        def __getattr__(self, name):
+            names.append(name)
+            return getattr(L, name)
+    monkeypatch.setattr(_lib, "_lib", Recording())
+    r = m.generate_async(enc[:2], num_beams=2, max_length=max_length, lookahead=None)
+    monkeypatch.undo()
+    search = [n for n in names if n.startswith(("m3ae_greedy_", "m3ae_beam_", "m3ae_trie_", "m3ae_triebeam_")) and not n.endswith("_workspace_bytes")]
+    assert search == ["m3ae_beam_topk", "m3ae_beam_step"] * (max_length - 1) + ["m3ae_beam_finalize"]
+    assert names[-2:] == ["m3ae_beam_step", "m3ae_beam_finalize"] and r.steps == max_length - 1 and int(r.err.cpu()) == 0
+    after_first_step = names[names.index("m3ae_beam_step") + 1:]
+    assert ("m3ae_gather_rows" in after_first_step) == (max_length > 2)     # (the next step's embedding is a row gather too)
+    host = m.generate(enc[:2], num_beams=2, max_length=max_length)
+    assert m.generate(enc[:2], num_beams=2, max_length=max_length, beam_search="device").tolist() == host.tolist()
+    assert r.seq[:, :host.shape[1]].tolist() == host.tolist()
+
+
 def test_t5vqa_module_passes_the_mode():
     """T5VQA_MMEncoderInput with t5_beam_search=device returns the generated_ids it returns with host (tiny config, B = 2)."""
     from m3ae_amd import synth

@@ -392,6 +392,25 @@ def test_default_search_calls_no_greedy_entry_point(models, feats, monkeypatch):
     assert counts.get("m3ae_greedy_argmax") == counts.get("m3ae_greedy_step") == MAX_LEN, counts
 
 
+def test_search_path_async_enqueues_argmax_and_step_per_position(models, feats, monkeypatch):
+    """One call without early exit under a recording proxy of the library: the ordered search entry points (the workspace-size
+    query aside) are argmax, step per position -- nothing else of the search families, nothing after the last step."""
+    d = models("fp32").decoder
+    L = _lib.lib()
+    names = []
+
+    class Recording:
+        def __getattr__(self, name):
+            names.append(name)
+            return getattr(L, name)
+    monkeypatch.setattr(_lib, "_lib", Recording())
+    r = d.search_path_async(feats[:2], lookahead=None)
+    monkeypatch.undo()
+    search = [n for n in names if n.startswith(("m3ae_greedy_", "m3ae_beam_", "m3ae_trie_", "m3ae_triebeam_")) and not n.endswith("_workspace_bytes")]
+    assert search == ["m3ae_greedy_argmax", "m3ae_greedy_step"] * MAX_LEN and names[-1] == "m3ae_greedy_step"
+    assert r.steps == MAX_LEN and torch.equal(r.seq, d.search_path(feats[:2]))
+
+
 def test_decoder_model_passes_the_mode_and_generates(models):
     """DecoderModel with decoder_search=device returns the generated_ids it returns with the default; generate / generate_async."""
     b = {k: (v.cuda() if isinstance(v, torch.Tensor) else [t.cuda() for t in v] if isinstance(v, list) and v

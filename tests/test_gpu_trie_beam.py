@@ -424,7 +424,7 @@ def test_answer_beam_equals_a_host_loop_over_step_logits(models, feats, mode):
         assert q.steps <= t.depth and torch.equal(q.out, r.out), la
     q = d.answer_beam_async(feats, t, nb, lp, START, PAD, lookahead=None, chunk=256)
     assert torch.equal(q.labels, r.labels) and torch.equal(q.seq, r.seq)
-    from m3ae_amd.modules.m3ae_decoder import answer_result
+    from m3ae_amd.search import answer_result
     labels, scores = answer_result(r)
     assert torch.equal(labels, r.label.cpu()) and torch.equal(scores, r.score.cpu())
     l3, s3 = answer_result(r, k=3)
@@ -617,6 +617,53 @@ def test_constrained_beam_equals_a_host_loop_and_the_teacher_forced_arg_max(mode
         lpv, derived, cached = teacher_forced(short, full, m.config.decoder_start_token_id, 4, EXACT_LOGIT if mode == "fp32" else BF16_LOGIT)
         decided += check_exhaustive(e, b, short, lpv, derived, cached, mode == "fp32", f"t5 {mode}")
     assert decided == B, decided                  # the fixture decides the arg-max of every sample in both modes
+
+
+@pytest.mark.parametrize("depth", [3, 1])
+def test_list_beam_searches_enqueue_scan_select_step_per_position(models, feats, monkeypatch, depth):
+    """Decoder.answer_beam_async and T5.constrained_beam_async, B = 2, two beams, no early exit, under a recording proxy of the
+    library: scan, select, step per position of the trie and nothing else of the search families; the caches are re-ordered between
+    steps only and the best entries' rows are gathered at the end (depth 1: a single step, no re-ordering, the result still
+    gathered).  Depth 3: three answers, every returned row is the entry its label names.  Depth 1: two one-token answers (a second
+    end id), two beams = exhaustive, so `labels` is the float64 ranking of the two tokens' log-probabilities at position 0."""
+    d = models("fp32").decoder
+    t5, enc = build_t5("fp32")
+    f2, enc, ML, nb = feats[:2].contiguous(), enc[:2].contiguous(), 4, 2
+    enc_kv = d.dec_layers[d.num_layers - 1].cross_kv(f2.to(d.head_dtype))
+    first_dec = d.step_logits(torch.full((2, 1), START, device=DEV), 0, enc_kv, torch.empty((2, 1, 2 * 768), dtype=d.head_dtype, device=DEV))
+    start = t5.config.decoder_start_token_id
+    first_t5 = t5.next_token_logits_cached(enc, torch.full((2, 1), start, device=DEV), t5.decoder.cross_kv(enc),
+                                           t5.decoder.new_self_cache(2, 1, enc.dtype, DEV), 0)
+    L = _lib.lib()
+    for end, first, run in ((SEP, first_dec, lambda t: d.answer_beam_async(f2, t, nb, 0.0, START, PAD, lookahead=None)),
+                            (1, first_t5, lambda t: t5.constrained_beam_async(enc, t, nb, ML, 0.0, PAD, lookahead=None))):
+        seqs, ends = ([[7, 8, end], [7, 9, end], [11, end]], (end,)) if depth == 3 else ([[end], [7]], (end, 7))
+        t = AnswerTrie(seqs, ends)
+        run(t)                                                  # warm: the trie and its answers table are uploaded
+        names = []
+
+        class Recording:
+            def __getattr__(self, name):
+                names.append(name)
+                return getattr(L, name)
+        monkeypatch.setattr(_lib, "_lib", Recording())
+        r = run(t)
+        monkeypatch.undo()
+        search = [n for n in names if n.startswith(("m3ae_greedy_", "m3ae_beam_", "m3ae_trie_", "m3ae_triebeam_")) and not n.endswith("_workspace_bytes")]
+        assert search == ["m3ae_trie_scan", "m3ae_triebeam_select", "m3ae_triebeam_step"] * depth
+        last = len(names) - 1 - names[::-1].index("m3ae_triebeam_step")
+        assert names[last + 1:] == ["m3ae_gather_rows"]          # the result's rows; no re-ordering after the last step
+        assert r.steps == depth == t.depth and int(r.err.cpu()) == 0
+        assert torch.equal(r.label, r.labels[:, 0]) and r.n_hyp.cpu().tolist() == [2, 2]
+        for b in range(2):
+            assert r.seq[b, :int(r.len[b])].cpu().tolist() == seqs[int(r.label[b])]
+        if depth == 1:
+            logp = torch.log_softmax(first.double(), dim=-1)[:, [end, 7]].cpu()
+            gap = (logp[:, 0] - logp[:, 1]).abs()
+            print(f"end id {end}: float64 log-probabilities of the two answers {logp.tolist()}")
+            assert (gap > 1e-4).all()                           # a condition on the inputs: far above fp32's error on one row
+            assert r.labels.cpu().tolist() == torch.argsort(-logp, dim=1).tolist()
+            assert (r.scores.cpu() - torch.sort(logp, dim=1, descending=True).values).abs().max() < 1e-4
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
