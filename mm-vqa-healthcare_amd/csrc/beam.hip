@@ -116,7 +116,7 @@ __global__ __launch_bounds__(BT) void beam_merge_kernel(uint64_t* __restrict__ c
     if ((int)threadIdx.x < K) {
         const uint64_t g = best[threadIdx.x];
         top_s[b * K + threadIdx.x] = unord32((uint32_t)(g >> 32));
-        top_i[b * K + threadIdx.x] = (int32_t)(0xffffffffu - (uint32_t)g);
+        top_i[b * K + threadIdx.x] = (int32_t)key_index(g);
     }
 }
 

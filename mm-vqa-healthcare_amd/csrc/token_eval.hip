@@ -3,31 +3,32 @@
 // that carry a label (or are selected), and the running record {n, hit1, hitk, sum_nll, calls}, with no host involvement.
 //
 // m3ae_token_eval, three launches (the third only with a record):
-//   token_chunk_kernel, grid (chunk, row), csrc/greedy.hip's geometry: a workgroup of a row that is not evaluated returns before it
-//   reads a logit.  Otherwise it reads its chunk ONCE (scalar head up to the first 16-byte boundary, 16-byte loads, scalar tail: no
-//   load touches a column at or past V) and leaves four things in workspace slots of its own: the greatest order key
-//   (csrc/order_key.h with greedy.hip's NaN / -0 handling: torch.argmax's rule), the number of keys strictly greater than the label's
-//   key, the chunk's (m, s) = (maximum, sum exp(x - m)) in fp32, and, for k > 0, its k greatest keys (csrc/topk_keep.h).
-//   token_row_kernel, one workgroup per row: the maximum of the chunk keys, the sum of the counts, the merge of the (m, s) pairs,
-//   lse = m + logf(s), the top-k of the chunks' candidates; writes pred / rank / nll / topk_idx / topk_prob.
-//   token_fold_kernel, one workgroup: thread t adds rows t, t + 256, ... in double, lanes then waves combine in a fixed tree, thread
-//   0 .. 3 add the four sums onto the record, thread 4 counts the call.  The order depends on R alone; no atomics.
+//   token_chunk_kernel, grid (chunk, row): a workgroup of a row that is not evaluated returns before it reads a logit.  Otherwise
+//   it reads its chunk ONCE (walk_row's geometry of csrc/row_scan.h, in a copy of its own: no load touches a column at or past V;
+//   see the note at Acc) and leaves four things in workspace slots of its own: the greatest order key (csrc/order_key.h's
+//   eval_key: torch.argmax's rule), the number of keys strictly greater than the label's key, the chunk's
+//   (m, s) = (maximum, sum exp(x - m)) in fp32, and, for k > 0, its k greatest keys (csrc/topk_keep.h).
+//   token_row_kernel, one workgroup per row: the maximum of the chunk keys, the sum of the counts, the merge of the (m, s) pairs
+//   (the folds of csrc/row_scan.h, in their every-thread form), lse = m + logf(s), the top-k of the chunks' candidates; writes
+//   pred / rank / nll / topk_idx / topk_prob.
+//   token_fold_kernel, one workgroup: thread t adds rows t, t + 256, ... in double, lanes then waves combine in a fixed tree
+//   (csrc/row_scan.h's block_add_record), thread 0 .. 3 add the four sums onto the record, thread 4 counts the call.  The order
+//   depends on R alone; no atomics.
 // (m, s) arithmetic.  A term is e(x, m) = x == m ? 1 : expf(x - m), which is expf(x - m) for finite values and keeps inf - inf out
 // of the sum: a row of -inf alone has lse = -inf + logf(count) = -inf, a row with a +inf has lse = +inf, a NaN anywhere gives a NaN
 // (fmaxf skips it, expf does not) -- the values torch.logsumexp returns.  Two pairs merge as m' = fmaxf(m1, m2),
 // s' = s1 e(m1, m') + s2 e(m2, m'); every s is a sum of terms in [0, 1], so there is no inf * 0.
 // m3ae_record_add: rec[0] += value[0], rec[1] += 1 in double (metrics.LossMean).
 #include "common.h"
-#include "lse_pair.h"
-#include "order_key.h"
+#include "row_scan.h"
 #include "topk_keep.h"
 #include <math.h>
 
 namespace {
 
 constexpr int TT = KEEP_T;       // threads of every kernel here
+static_assert(KEEP_T == SCAN_T, "walk_row and the folds stride by SCAN_T, the candidate scheme by KEEP_T");
 constexpr int64_t T_DEF_CHUNK = 8192;                       // measured: tools/token_eval_bench.py --chunks
-constexpr int64_t T_MIN_CHUNK = 64, T_MAX_CHUNK = 65536;     // csrc/greedy.hip's bounds
 constexpr int T_MAX_K = M3AE_TOKEN_MAX_K;
 constexpr int64_t T_IGNORE = M3AE_TOKEN_IGNORE;
 enum { ROW_SKIPPED = 0, ROW_UNLABELLED = 1, ROW_LABELLED = 2 };
@@ -43,9 +44,9 @@ DEVINL int row_state(const int64_t* __restrict__ labels, const uint8_t* __restri
     return label == T_IGNORE ? ROW_UNLABELLED : ROW_LABELLED;
 }
 
-// exp_diff, ms_merge: csrc/lse_pair.h
-DEVINL uint64_t max_u64(uint64_t a, uint64_t b) { return a > b ? a : b; }
-
+// token_chunk_kernel keeps its own body -- its accumulator with the (m, s) part inline, its own copy of the row geometry of
+// csrc/row_scan.h's walk_row and its own fold: on the shared pieces it measured 1 - 1.5 % slower (k = 5) on the MI355X
+// (profiles/r26_row_scan.log), and a kernel that cannot be held level stays as it was.  A change to walk_row must be made here too.
 // What a thread has gathered from its columns of the chunk.
 template <bool TOPK>
 struct Acc {
@@ -210,30 +211,14 @@ __global__ __launch_bounds__(TT) void token_row_kernel(const T* __restrict__ log
         cnt += cnts[s0 + i];
         ms_merge(m, s, ms[2 * (s0 + i)], ms[2 * (s0 + i) + 1]);
     }
-    best = wave_max_u64(best);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        cnt += __shfl_xor(cnt, o, 64);
-        const float m2 = __shfl_xor(m, o, 64), s2 = __shfl_xor(s, o, 64);
-        ms_merge(m, s, m2, s2);
-    }
-    if ((tid & 63) == 0) {
-        redk[tid >> 6] = best;
-        redc[tid >> 6] = cnt;
-        redm[tid >> 6] = m;
-        reds[tid >> 6] = s;
-    }
-    __syncthreads();
     // every thread folds the four waves in the same order: the same bits in every thread
-    best = redk[0];
-    cnt = redc[0];
-    m = redm[0];
-    s = reds[0];
-    for (int w = 1; w < TT / 64; ++w) {
-        best = max_u64(best, redk[w]);
-        cnt += redc[w];
-        ms_merge(m, s, redm[w], reds[w]);
-    }
+    max_put(best, redk, tid);
+    sum_put(cnt, redc, tid);
+    ms_put(m, s, redm, reds, tid);
+    __syncthreads();
+    best = max_get<true>(redk, tid);
+    cnt = sum_get<true>(redc, tid);
+    ms_get<true>(m, s, redm, reds, tid);
     const float lse = m + logf(s);
 
     if (k > 0) {
@@ -243,20 +228,13 @@ __global__ __launch_bounds__(TT) void token_row_kernel(const T* __restrict__ log
         for (int64_t i = tid; i < nc; i += TT) keep.put(tops[s0 * k + i]);    // an empty slot is 0 and is never kept
         keep_select(cand, k, red, sel, tid);
         if (tid < k) {   // a key of 0 (the host refuses k > V) or a column outside [0, V) is never an address
-            const uint64_t g = sel[tid];
-            const int64_t col = (int64_t)(0xffffffffu - (uint32_t)g);
-            const bool ok = g != 0 && col < V;
-            if (topk_idx) topk_idx[r * k + tid] = ok ? (int32_t)col : -1;
-            if (topk_prob) {
-                const uint32_t hi = (uint32_t)(g >> 32);
-                const float v = hi == 0xffffffffu ? __uint_as_float(0x7fc00000u) : unord32(hi);
-                topk_prob[r * k + tid] = ok ? expf(v - lse) : 0.0f;
-            }
+            const int64_t col = key_index_in(sel[tid], V);
+            if (topk_idx) topk_idx[r * k + tid] = (int32_t)col;
+            if (topk_prob) topk_prob[r * k + tid] = col >= 0 ? expf(key_value(sel[tid]) - lse) : 0.0f;
         }
     }
     if (tid == 0) {
-        const int64_t top = (int64_t)(0xffffffffu - (uint32_t)best);
-        if (pred) pred[r] = (best != 0 && top < V) ? top : -1;
+        if (pred) pred[r] = key_index_in(best, V);
         const bool lab = st == ROW_LABELLED;
         const float xl = lab ? Elem<T>::ld(logits + r * ld + label) : 0.0f;   // 0 <= label < V
         const float v = lab ? lse - xl : lse;
@@ -266,8 +244,6 @@ __global__ __launch_bounds__(TT) void token_row_kernel(const T* __restrict__ log
         row_nll[r] = v;
     }
 }
-
-DEVINL double shfl_xor_d(double v, int o) { return __shfl_xor(v, o, 64); }
 
 // row_rank int32 [R] (>= 0: the rank of a labelled row), row_nll fp32 [R]; rec double [5] += {n, hit1, hitk, sum_nll}, rec[4] += 1
 __global__ __launch_bounds__(TT) void token_fold_kernel(const int32_t* __restrict__ row_rank, const float* __restrict__ row_nll, int64_t R,
@@ -284,18 +260,7 @@ __global__ __launch_bounds__(TT) void token_fold_kernel(const int32_t* __restric
             acc[3] += (double)row_nll[r];
         }
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc[i] += shfl_xor_d(acc[i], o);
-    }
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) red[tid >> 6][i] = acc[i];
-    }
-    __syncthreads();
-    if (tid < 4) rec[tid] += (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-    if (tid == 4) rec[4] += 1.0;
+    block_add_record<4>(acc, red, rec, tid);
 }
 
 __global__ void record_add_kernel(const float* __restrict__ value, double* __restrict__ rec) {
@@ -308,8 +273,7 @@ __global__ void record_add_kernel(const float* __restrict__ value, double* __res
 inline int64_t pad8(int64_t b) { return (b + 7) & ~(int64_t)7; }
 
 inline bool token_shape_ok(int64_t R, int64_t V, int64_t chunk, int64_t k) {
-    return R >= 1 && V >= 1 && V <= (int64_t)INT32_MAX && R <= (int64_t)INT32_MAX && chunk >= T_MIN_CHUNK && chunk <= T_MAX_CHUNK &&
-           k >= 0 && k <= T_MAX_K && k <= V && R * cdiv(V, chunk) <= (int64_t)INT32_MAX;
+    return chunk_shape_ok(R, V, chunk, 0) && k >= 0 && k <= T_MAX_K && k <= V;
 }
 
 // workspace: keys u64 [S] | tops u64 [S][k] | ms fp32 [S][2] | cnts i32 [S] | row_rank i32 [R] | row_nll fp32 [R], S = R * chunks
@@ -371,11 +335,10 @@ extern "C" int m3ae_token_eval(const void* logits, int64_t ld, const int64_t* la
         ((uintptr_t)workspace & 7))
         return M3AE_ERR_ALIGN;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == M3AE_F32)
-        launch_token<float>(logits, ld, labels, select, R, V, chunk, nch, (int)k, pred, rank, nll, topk_idx, topk_prob, err, (char*)workspace, w, s);
-    else
-        launch_token<bf16_t>(logits, ld, labels, select, R, V, chunk, nch, (int)k, pred, rank, nll, topk_idx, topk_prob, err, (char*)workspace, w,
-                             s);
+    by_dtype(dtype, [&](auto t) {
+        launch_token<decltype(t)>(logits, ld, labels, select, R, V, chunk, nch, (int)k, pred, rank, nll, topk_idx, topk_prob, err,
+                                  (char*)workspace, w, s);
+    });
     if (rec)
         hipLaunchKernelGGL(token_fold_kernel, dim3(1), dim3(TT), 0, s, (const int32_t*)((char*)workspace + w.row_rank),
                            (const float*)((char*)workspace + w.row_nll), R, (int)k, rec);

@@ -1,5 +1,5 @@
 // The top-k scheme of the evaluation kernels (csrc/vqa_eval.hip, csrc/token_eval.hip): every value becomes the order key of
-// csrc/order_key.h with greedy.hip's NaN / -0 handling; a thread keeps the kk greatest keys it has seen in its own column of an LDS
+// csrc/order_key.h (eval_key: torch.argmax's rule); a thread keeps the kk greatest keys it has seen in its own column of an LDS
 // table (cand[slot][thread]; 0 = empty, no key is 0).  The top-k of the workgroup's keys is a subset of the union of the threads'
 // top-k, so rank j is "the greatest candidate below rank j - 1": kk passes over LDS, each a wave maximum and a four-way fold.  Keys of
 // distinct columns are distinct integers: the result depends on no order.
@@ -10,13 +10,6 @@
 namespace {
 
 constexpr int KEEP_T = 256;      // threads of a workgroup that uses the scheme
-
-DEVINL uint64_t eval_key(uint32_t u, uint32_t col) {   // u = the bits of an fp32 value; csrc/greedy.hip's rule
-    if ((u & 0x7fffffffu) > 0x7f800000u) return ((uint64_t)0xffffffffu << 32) | (uint64_t)(0xffffffffu - col);   // NaN: above +inf
-    return make_key(__uint_as_float(u == 0x80000000u ? 0u : u), col);                                           // -0 -> +0
-}
-DEVINL uint32_t bits_of(float v) { return __float_as_uint(v); }
-DEVINL uint32_t bits_of(bf16_t v) { return (uint32_t)v << 16; }
 
 // The kk greatest keys a thread has seen, in cand[slot * KEEP_T + tid]; mn / mnpos = the least of them and its slot.
 struct Keep {

@@ -12,7 +12,7 @@
 //   chunk order, lse = m + logf(s) (csrc/answer_trie.hip's step).  The workgroup then walks the children of every live beam's node
 //   in passes of 256; child entry e (an index into child_tok / child_node, ascending in token within a node) of beam k gives
 //   score = fl(fl(x[tok] - lse) + beam_score) and the order key (monotone image of the score) << 32 | (2^32 - 1 - (k * E + e))
-//   with csrc/topk_keep.h's NaN / -0 handling.  Every thread keeps its best 2 nb keys in LDS and the ranks are read off as in
+//   with eval_key's NaN / -0 handling.  Every thread keeps its best 2 nb keys in LDS and the ranks are read off as in
 //   csrc/vqa_eval.hip: the best min(2 nb, candidates) by (rounded score descending, (beam, token) ascending), a NaN first.
 // m3ae_triebeam_step, one workgroup, a thread per sample (csrc/answer_trie.hip's step): walks the ranks, pushes leaves at rank < nb
 //   into the sample's hypothesis list (csrc/hyp_list.h), fills the next beam slots, writes the gather order of the caches and the
@@ -23,25 +23,17 @@
 // No atomics; keys of distinct (beam, entry) pairs are distinct: two runs on the same inputs give the same bits.
 #include "common.h"
 #include "hyp_list.h"
-#include "lse_pair.h"
-#include "order_key.h"
+#include "row_scan.h"
 #include "topk_keep.h"
 
-extern "C" int64_t m3ae_trie_workspace_bytes(int64_t R, int64_t V, int64_t chunk);   // csrc/answer_trie.hip: its chunk bounds
+extern "C" int64_t m3ae_trie_workspace_bytes(int64_t R, int64_t V, int64_t chunk);   // csrc/answer_trie.hip: its default chunk
 
 namespace {
 
 constexpr int TB = KEEP_T;       // threads of both kernels (256: the scheme of csrc/topk_keep.h)
+static_assert(KEEP_T == SCAN_T, "walk_row and the folds stride by SCAN_T, the candidate scheme by KEEP_T");
 constexpr int TB_MAX_BEAMS = 8;
 constexpr int TB_MAX_K = 2 * TB_MAX_BEAMS;
-
-// The child range of node n, or false when the table does not hold one (never an address then).
-DEVINL bool tb_child_range(const int32_t* __restrict__ child_off, int64_t n, int64_t N, int64_t E, int64_t& lo, int64_t& hi) {
-    if (n < 0 || n >= N) return false;
-    lo = child_off[n];
-    hi = child_off[n + 1];
-    return lo >= 0 && hi <= E && lo < hi;
-}
 
 template <typename T>
 __global__ __launch_bounds__(TB) void trie_beam_select_kernel(const T* __restrict__ logits, int64_t ld, int64_t V, const float* __restrict__ ms,
@@ -68,7 +60,7 @@ __global__ __launch_bounds__(TB) void trie_beam_select_kernel(const T* __restric
         int64_t lo = 0, hi = 0;          // lo == hi: the beam has no candidate
         float lse = 0.0f, bs = 0.0f;
         if (nd >= 0) {                   // a dead slot: nothing of its row is read, the (m, s) pairs included
-            if (tb_child_range(child_off, nd, N, E, lo, hi)) {
+            if (child_range(child_off, nd, N, E, lo, hi)) {
                 float m = -INFINITY, s = 0.0f;
                 const float* p = ms + 2 * r * nch;
                 for (int64_t i = 0; i < nch; ++i) ms_merge(m, s, p[2 * i], p[2 * i + 1]);
@@ -99,11 +91,9 @@ __global__ __launch_bounds__(TB) void trie_beam_select_kernel(const T* __restric
     keep_select(cand, kk, red, sel, tid);   // rank j = the greatest candidate below rank j - 1 (rank 0: the greatest)
 
     if (tid < kk) {
-        const uint64_t g = sel[tid];
-        const int64_t flat = (int64_t)(0xffffffffu - (uint32_t)g);
-        const bool ok = g != 0 && flat < (int64_t)nb * E;
-        const uint32_t hi = (uint32_t)(g >> 32);
-        top_s[b * kk + tid] = !ok ? 0.0f : (hi == 0xffffffffu ? __uint_as_float(0x7fc00000u) : unord32(hi));
+        const int64_t flat = key_index_in(sel[tid], (int64_t)nb * E);
+        const bool ok = flat >= 0;
+        top_s[b * kk + tid] = ok ? key_value(sel[tid]) : 0.0f;
         top_beam[b * kk + tid] = ok ? (int32_t)(flat / E) : -1;
         top_edge[b * kk + tid] = ok ? (int32_t)(flat % E) : -1;
     }
@@ -149,7 +139,7 @@ __global__ __launch_bounds__(TB) void trie_beam_step_kernel(const float* __restr
                 if (e == -1 && bm == -1) continue;             // an unused slot
                 if (bm < 0 || bm >= nb || e < 0 || e >= E) { err[0] = 1; continue; }   // never an address
                 int64_t lo = 0, hi = 0;
-                if (!tb_child_range(child_off, old_node[bm], N, E, lo, hi) || e < lo || e >= hi) { err[0] = 1; continue; }
+                if (!child_range(child_off, old_node[bm], N, E, lo, hi) || e < lo || e >= hi) { err[0] = 1; continue; }
                 const int64_t tok = child_tok[e], nn = child_node[e];
                 if (tok < 0 || tok >= V || nn < 0 || nn >= N) { err[0] = 1; continue; }
                 const float s = top_s[b * kk + rank];
@@ -219,12 +209,11 @@ extern "C" int m3ae_triebeam_select(const void* logits, int64_t ld, int64_t B, i
     const int64_t nch = need / (8 * R) - 1;                         // workspace: child key u64 [R] | (m, s) fp32 [R][chunks][2]
     const float* ms = (const float*)((const uint64_t*)workspace + R);
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == M3AE_F32)
-        hipLaunchKernelGGL(trie_beam_select_kernel<float>, dim3((unsigned)B), dim3(TB), 0, s, (const float*)logits, ld, V, ms, nch, child_off,
-                           child_tok, N, E, node, beam_score, (int)nb, top_s, top_beam, top_edge, n_cand, err);
-    else
-        hipLaunchKernelGGL(trie_beam_select_kernel<bf16_t>, dim3((unsigned)B), dim3(TB), 0, s, (const bf16_t*)logits, ld, V, ms, nch, child_off,
-                           child_tok, N, E, node, beam_score, (int)nb, top_s, top_beam, top_edge, n_cand, err);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(trie_beam_select_kernel<T>, dim3((unsigned)B), dim3(TB), 0, s, (const T*)logits, ld, V, ms, nch, child_off, child_tok,
+                           N, E, node, beam_score, (int)nb, top_s, top_beam, top_edge, n_cand, err);
+    });
     return hip_launch_status();
 }
 

@@ -3,26 +3,28 @@
 // targets and the running record {n, sum_top1, sum_topk} x {all, closed, open}, with no host involvement.
 //
 // m3ae_vqa_eval, one launch (+ the fold when there are targets and a record):
-//   vqa_eval_kernel, one workgroup per row.  The row is read ONCE (scalar head up to the first 16-byte boundary, 16-byte loads,
-//   scalar tail, as csrc/greedy.hip: no load touches a column at or past C).  Every value becomes the order key of
-//   csrc/order_key.h with greedy.hip's NaN / -0 handling; a thread keeps the kk = max(k, 1) greatest keys of ITS columns in LDS
-//   (cand[slot][thread]; 0 = empty, no key is 0; csrc/topk_keep.h, shared with csrc/token_eval.hip).  The row's top-k is a subset of the union of the threads' top-k, so rank j is
+//   vqa_eval_kernel, one workgroup per row.  The row is read ONCE (csrc/row_scan.h's walk_row: no load touches a column at or past
+//   C).  Every value becomes the order key of csrc/order_key.h (eval_key); a thread keeps the kk = max(k, 1) greatest keys of ITS
+//   columns in LDS (cand[slot][thread]; 0 = empty, no key is 0; csrc/topk_keep.h, shared with csrc/token_eval.hip).  The row's
+//   top-k is a subset of the union of the threads' top-k, so rank j is
 //   "the greatest candidate below rank j - 1": k passes over LDS, each a wave maximum and a four-way fold.  Keys of distinct
 //   columns are distinct integers: the result does not depend on any order.  The value of a chosen column is decoded from its
 //   key (exact but for -0 -> +0 and the NaN payload, neither of which the sigmoid sees).
-//   vqa_fold_kernel, one workgroup: thread t adds rows t, t + 256, ... in double, lanes then waves combine in a fixed tree, thread
-//   0 adds the nine sums onto the record and counts the call.  The order depends on B alone; no atomics.
+//   vqa_fold_kernel, one workgroup: thread t adds rows t, t + 256, ... in double, lanes then waves combine in a fixed tree
+//   (csrc/row_scan.h's block_add_record), threads 0 .. 8 add the nine sums onto the record, thread 9 counts the call.  The order
+//   depends on B alone; no atomics.
 // m3ae_seq_match: one thread per row walks gen[r] and ref[r] with the skip ids dropped; then the same fold.
 // m3ae_vqa_label_eval: one thread per row reads targets[r][labels[r]] (answer-list decoding, csrc/answer_trie.hip: the prediction
 //   is a label already); then the same fold.
 #include "common.h"
-#include "order_key.h"
+#include "row_scan.h"
 #include "topk_keep.h"
 #include <math.h>
 
 namespace {
 
 constexpr int VT = KEEP_T;       // threads of every kernel here (256: the scheme of csrc/topk_keep.h)
+static_assert(KEEP_T == SCAN_T, "walk_row and the folds stride by SCAN_T, the candidate scheme by KEEP_T");
 constexpr int V_MAX_K = M3AE_VQA_MAX_K;
 constexpr int V_MAX_SKIP = M3AE_SEQ_MAX_SKIP;
 
@@ -31,67 +33,38 @@ __global__ __launch_bounds__(VT) void vqa_eval_kernel(const T* __restrict__ logi
                                                       int64_t ldt, int64_t C, int k, int64_t* __restrict__ pred,
                                                       int32_t* __restrict__ topk_idx, float* __restrict__ topk_prob,
                                                       float* __restrict__ hit1_out, float* __restrict__ rows) {
-    constexpr int W = 16 / (int)sizeof(T);   // elements of one 16-byte load
     __shared__ uint64_t cand[V_MAX_K * VT];
     __shared__ uint64_t red[2][VT / 64];
     __shared__ uint64_t sel[V_MAX_K];
     const int64_t r = blockIdx.x;
     const int tid = threadIdx.x;
     const int kk = k > 0 ? k : 1;
-    const T* x = logits + r * ld;
     for (int s = 0; s < kk; ++s) cand[s * VT + tid] = 0;   // a thread reads and writes its own column of cand only
     Keep keep{cand + tid, kk, 0, 0};
 
-    // x is element-aligned (host check): `mis` elements past a 16-byte boundary
-    const int64_t mis = (int64_t)(((uintptr_t)x & 15) / sizeof(T));
-    int64_t head = mis ? W - mis : 0;
-    head = head < C ? head : C;
-    const int64_t nvec = (C - head) / W;
-    const int64_t tail0 = head + nvec * W;
-    if (tid < head) keep.put(eval_key(bits_of(x[tid]), (uint32_t)tid));
-    const u32x4* xv = (const u32x4*)(x + head);
-    for (int64_t i = tid; i < nvec; i += VT) {
-        const u32x4 q = xv[i];
-        const uint32_t j0 = (uint32_t)(head + i * W);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            if (sizeof(T) == 4) {
-                keep.put(eval_key(q[e], j0 + e));
-            } else {   // two bf16 per dword, the lower column in the low half
-                keep.put(eval_key(q[e] << 16, j0 + 2 * e));
-                keep.put(eval_key(q[e] & 0xffff0000u, j0 + 2 * e + 1));
-            }
-        }
-    }
-    if (tail0 + tid < C) keep.put(eval_key(bits_of(x[tail0 + tid]), (uint32_t)(tail0 + tid)));   // < W <= VT columns
+    walk_row(logits + r * ld, C, tid, [&](const uint32_t* u, int cnt, uint32_t j0) {
+        for (int e = 0; e < cnt; ++e) keep.put(eval_key(u[e], j0 + e));
+    });
 
     keep_select(cand, kk, red, sel, tid);   // rank j = the greatest candidate below rank j - 1 (rank 0: the greatest)
 
     // a key of 0 (fewer than kk columns: the host refuses k > C) or a column outside [0, C) is never an address
     if (tid < k) {
-        const uint64_t g = sel[tid];
-        const int64_t col = (int64_t)(0xffffffffu - (uint32_t)g);
-        const bool ok = g != 0 && col < C;
-        if (topk_idx) topk_idx[r * k + tid] = ok ? (int32_t)col : -1;
-        if (topk_prob) {
-            const uint32_t hi = (uint32_t)(g >> 32);
-            const float v = hi == 0xffffffffu ? __uint_as_float(0x7fc00000u) : unord32(hi);
-            topk_prob[r * k + tid] = ok ? 1.0f / (1.0f + expf(-v)) : 0.0f;
-        }
+        const int64_t col = key_index_in(sel[tid], C);
+        if (topk_idx) topk_idx[r * k + tid] = (int32_t)col;
+        if (topk_prob) topk_prob[r * k + tid] = col >= 0 ? 1.0f / (1.0f + expf(-key_value(sel[tid]))) : 0.0f;
     }
     if (tid == 0) {
-        const uint64_t g0 = sel[0];
-        const int64_t top = (int64_t)(0xffffffffu - (uint32_t)g0);
-        const bool ok0 = g0 != 0 && top < C;
-        if (pred) pred[r] = ok0 ? top : -1;
+        const int64_t top = key_index_in(sel[0], C);
+        const bool ok0 = top >= 0;
+        if (pred) pred[r] = top;
         if (targets) {
             const float* t = targets + r * ldt;
             const float h1 = ok0 ? t[top] : 0.0f;
             float hk = k > 0 ? h1 : 0.0f;      // k = 0: the maximum over no column
             for (int j = 1; j < k; ++j) {
-                const uint64_t g = sel[j];
-                const int64_t col = (int64_t)(0xffffffffu - (uint32_t)g);
-                if (g != 0 && col < C) {
+                const int64_t col = key_index_in(sel[j], C);
+                if (col >= 0) {
                     const float v = t[col];
                     hk = v > hk ? v : hk;
                 }
@@ -101,8 +74,6 @@ __global__ __launch_bounds__(VT) void vqa_eval_kernel(const T* __restrict__ logi
         }
     }
 }
-
-DEVINL double shfl_xor_d(double v, int o) { return __shfl_xor(v, o, 64); }
 
 // rows fp32 [B][2] = {hit1, hitk}; rec double [10] += {n, sum_top1, sum_topk} of (all, closed, open), rec[9] += 1
 __global__ __launch_bounds__(VT) void vqa_fold_kernel(const float* __restrict__ rows, const int32_t* __restrict__ types, int64_t B,
@@ -119,18 +90,7 @@ __global__ __launch_bounds__(VT) void vqa_fold_kernel(const float* __restrict__ 
         if (ty == M3AE_ANS_CLOSED) { acc[3] += 1.0; acc[4] += h1; acc[5] += hk; }
         if (ty == M3AE_ANS_OPEN) { acc[6] += 1.0; acc[7] += h1; acc[8] += hk; }
     }
-#pragma unroll
-    for (int i = 0; i < 9; ++i) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc[i] += shfl_xor_d(acc[i], o);
-    }
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) red[tid >> 6][i] = acc[i];
-    }
-    __syncthreads();
-    if (tid < 9) rec[tid] += (red[0][tid] + red[1][tid]) + (red[2][tid] + red[3][tid]);
-    if (tid == 9) rec[9] += 1.0;
+    block_add_record<9>(acc, red, rec, tid);
 }
 
 struct SkipIds { int64_t id[V_MAX_SKIP]; };
@@ -232,12 +192,11 @@ extern "C" int m3ae_vqa_eval(const void* logits, int64_t ld, const float* target
         return M3AE_ERR_ALIGN;
     hipStream_t s = (hipStream_t)stream;
     float* rows = fold ? (float*)workspace : nullptr;
-    if (dtype == M3AE_F32)
-        hipLaunchKernelGGL(vqa_eval_kernel<float>, dim3((unsigned)B), dim3(VT), 0, s, (const float*)logits, ld, targets, ldt, C, (int)k, pred,
-                           topk_idx, topk_prob, hit1, rows);
-    else
-        hipLaunchKernelGGL(vqa_eval_kernel<bf16_t>, dim3((unsigned)B), dim3(VT), 0, s, (const bf16_t*)logits, ld, targets, ldt, C, (int)k,
-                           pred, topk_idx, topk_prob, hit1, rows);
+    by_dtype(dtype, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(vqa_eval_kernel<T>, dim3((unsigned)B), dim3(VT), 0, s, (const T*)logits, ld, targets, ldt, C, (int)k, pred, topk_idx,
+                           topk_prob, hit1, rows);
+    });
     if (fold) hipLaunchKernelGGL(vqa_fold_kernel, dim3(1), dim3(VT), 0, s, (const float*)rows, types, B, rec);
     return hip_launch_status();
 }

@@ -2154,24 +2154,46 @@ class OpenCountWatch:
 GREEDY_CHUNK = 2048   # vocabulary elements per workgroup of m3ae_greedy_argmax when the caller passes chunk=0
 
 
+def _logits_rows(what, logits, rows=None):
+    """The check of every entry point that reads rows of logits the way csrc/row_scan.h does: fp32 or bf16 [R, V], unit column
+    stride, row stride >= V (R == rows where given).  Returns (R, V)."""
+    _need_cuda(logits)
+    if logits.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{what} takes fp32 or bf16 logits")
+    shape = logits.shape           # read once: these checks run per decoding step, where the host's enqueue is the bound
+    if (len(shape) != 2 or shape[0] < 1 or shape[1] < 1 or (rows is not None and shape[0] != rows) or logits.stride(1) != 1
+            or logits.stride(0) < shape[1]):
+        raise ValueError(f"{what}: logits {tuple(shape)} with strides {tuple(logits.stride())}"
+                         + ("" if rows is None else f" for {rows} rows"))
+    return shape
+
+
+def _chunk_arg(what, chunk):
+    """chunk as an int: 0 (the kernel's default) or within the bounds of csrc/row_scan.h."""
+    chunk = int(chunk)
+    if chunk != 0 and not 64 <= chunk <= 65536:
+        raise ValueError(f"{what}: chunk={chunk} is neither 0 nor in [64, 65536]")
+    return chunk
+
+
+def _chunk_workspace(what, nbytes, entry, R, V, device, chunk):
+    """int64 [R, words of a row]: the workspace of `entry`, whose size in bytes nbytes(R, V, chunk) gives."""
+    n = nbytes(R, V, chunk)
+    if n <= 0:
+        raise ValueError(f"{what}: R={R}, V={V}, chunk={chunk} is not a shape {entry} takes")
+    return torch.empty((R, n // (8 * R)), dtype=torch.int64, device=device)
+
+
 def greedy_workspace(R, V, device, chunk=0):
     """The keys buffer of greedy_argmax: int64 [R, chunks of a row] (the bits of the kernels' uint64 order keys)."""
-    n = _lib.lib().m3ae_greedy_workspace_bytes(R, V, chunk)
-    if n <= 0:
-        raise ValueError(f"greedy_workspace: R={R}, V={V}, chunk={chunk} is not a shape m3ae_greedy_argmax takes")
-    return torch.empty((R, n // (8 * R)), dtype=torch.int64, device=device)
+    return _chunk_workspace("greedy_workspace", _lib.lib().m3ae_greedy_workspace_bytes, "m3ae_greedy_argmax", R, V, device, chunk)
 
 
 def greedy_argmax(logits, chunk=0, ws=None, out=None):
     """logits fp32 or bf16 [R, V] (row stride >= V, unit column stride) -> the keys buffer `ws` int64 [R, chunks]: per vocabulary
     chunk the greatest order key (value, then lowest column), for greedy_step.  With `out` (int64 [R], for direct testing) the
     decoded tokens are written there and returned instead: torch.argmax's choice, ties and NaN included."""
-    _need_cuda(logits)
-    if logits.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("greedy_argmax takes fp32 or bf16 logits")
-    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
-        raise ValueError(f"greedy_argmax: logits {tuple(logits.shape)} with strides {tuple(logits.stride())}")
-    R, V = logits.shape
+    R, V = _logits_rows("greedy_argmax", logits)
     if ws is None:
         ws = greedy_workspace(R, V, logits.device, chunk)
     if ws.dtype != torch.int64 or not ws.is_contiguous() or not ws.is_cuda:
@@ -2219,10 +2241,7 @@ TRIE_CHUNK = 8192   # vocabulary elements per workgroup of m3ae_trie_scan when t
 
 def trie_workspace(R, V, device, chunk=0):
     """The workspace of trie_scan / trie_step: int64 [R, 1 + chunks of a row] words (the child keys, then the (m, s) pairs)."""
-    n = _lib.lib().m3ae_trie_workspace_bytes(R, V, chunk)
-    if n <= 0:
-        raise ValueError(f"trie_workspace: R={R}, V={V}, chunk={chunk} is not a shape m3ae_trie_scan takes")
-    return torch.empty((R, n // (8 * R)), dtype=torch.int64, device=device)
+    return _chunk_workspace("trie_workspace", _lib.lib().m3ae_trie_workspace_bytes, "m3ae_trie_scan", R, V, device, chunk)
 
 
 class TrieState(GreedyState):
@@ -2238,15 +2257,6 @@ class TrieState(GreedyState):
         self.node = torch.zeros((B,), dtype=torch.int32, device=device)
 
 
-def _trie_logits(what, logits, st):
-    _need_cuda(logits)
-    _need_cuda(st.out)
-    if logits.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f"{what} takes fp32 or bf16 logits")
-    if logits.dim() != 2 or logits.shape[0] != st.B or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
-        raise ValueError(f"{what}: logits {tuple(logits.shape)} with strides {tuple(logits.stride())} for {st.B} rows")
-
-
 def _trie_ws(what, ws, B, V, chunk):
     need = _lib.lib().m3ae_trie_workspace_bytes(B, V, chunk)
     if need <= 0:
@@ -2259,11 +2269,9 @@ def _trie_ws(what, ws, B, V, chunk):
 def trie_scan(logits, trie, st, chunk=0, ws=None):
     """logits fp32 or bf16 [B, V] (row stride >= V, unit column stride), read once: per open row of `st` the (m, s) pair of every
     vocabulary chunk and the greatest order key among the children of the row's trie node, into `ws`.  Returns ws."""
-    _trie_logits("trie_scan", logits, st)
-    B, V = logits.shape
-    chunk = int(chunk)
-    if chunk != 0 and not 64 <= chunk <= 65536:
-        raise ValueError(f"trie_scan: chunk={chunk} is neither 0 nor in [64, 65536]")
+    _need_cuda(st.out)
+    B, V = _logits_rows("trie_scan", logits, st.B)
+    chunk = _chunk_arg("trie_scan", chunk)
     if ws is None:
         ws = trie_workspace(B, V, logits.device, chunk)
     _trie_ws("trie_scan", ws, B, V, chunk)
@@ -2275,8 +2283,8 @@ def trie_scan(logits, trie, st, chunk=0, ws=None):
 def trie_step(logits, trie, st, ws, pos, pad_id, chunk=0):
     """One step of the search on `st` at position pos from the workspace trie_scan filled from the same logits (same chunk):
     token, next node, score += log-probability, label / len / finished at a leaf; st.open_count[pos] = rows still open."""
-    _trie_logits("trie_step", logits, st)
-    B, V = logits.shape
+    _need_cuda(st.out)
+    B, V = _logits_rows("trie_step", logits, st.B)
     nch = _trie_ws("trie_step", ws, B, V, int(chunk))
     if not 0 <= pos < st.max_len:
         raise ValueError(f"trie_step: pos {pos} outside [0, {st.max_len})")
@@ -2329,8 +2337,8 @@ def trie_beam_select(logits, trie, st, ws, chunk=0):
     """The candidate selection of one step: logits fp32 or bf16 [B * nb, V] as trie_scan took them, `ws` the workspace trie_scan
     filled from them (same chunk).  Per sample the best min(2 nb, candidates) children of its live beams' nodes by
     fl(fl(x[tok] - lse) + beam_score), into st.top_s / st.top_beam / st.top_edge / st.n_cand."""
-    _trie_logits("trie_beam_select", logits, st)
-    R, V = logits.shape
+    _need_cuda(st.out)
+    R, V = _logits_rows("trie_beam_select", logits, st.B)
     _trie_ws("trie_beam_select", ws, R, V, int(chunk))
     check(_lib.lib().m3ae_triebeam_select(_p(logits), logits.stride(0), st.Bs, st.nb, V, int(chunk), _dt(logits), _p(trie.child_off),
                                            _p(trie.child_tok), trie.N, trie.E, _p(st.node), _p(st.beam_score), _p(ws), ws.numel() * 8,
@@ -2404,12 +2412,7 @@ def vqa_eval(logits, targets, types, rec, k=0, want_rows=False):
     taken as it is); targets fp32 [B, C] or None; types int32 [B] (_lib.ANS_CLOSED / ANS_OPEN, anything else: "all" only) or
     None; rec float64 [10] (ops.vqa_record) or None.  Adds {n, hit1, hitk} of the rows onto rec, where hit1 is the target of
     torch.max(logits, 1)[1] and hitk the best target among the top-k (0 <= k <= 16).  want_rows: returns VqaRows."""
-    _need_cuda(logits)
-    if logits.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("vqa_eval takes fp32 or bf16 logits")
-    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
-        raise ValueError(f"vqa_eval: logits {tuple(logits.shape)} with strides {tuple(logits.stride())}")
-    B, Cc = logits.shape
+    B, Cc = _logits_rows("vqa_eval", logits)
     k = int(k)
     if not 0 <= k <= min(_lib.VQA_MAX_K, Cc):
         raise ValueError(f"vqa_eval: k={k} outside [0, min({_lib.VQA_MAX_K}, C={Cc})]")
@@ -2552,17 +2555,11 @@ def token_eval(logits, labels=None, select=None, rec=None, k=0, chunk=0, want_ro
     Evaluated rows: select != 0 if given, else labels != -100 if given, else all; the logits of the other rows are not read.
     Adds {n, rank == 0, rank < k, nll} of the labelled evaluated rows onto rec.  0 <= k <= min(16, V); chunk: columns per workgroup
     (0: 8192).  want_rows: pred / rank / nll, want_topk: topk_idx / topk_prob (k > 0), returned as TokenRows."""
-    _need_cuda(logits)
-    if logits.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError("token_eval takes fp32 or bf16 logits")
-    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] < 1 or logits.stride(1) != 1 or logits.stride(0) < logits.shape[1]:
-        raise ValueError(f"token_eval: logits {tuple(logits.shape)} with strides {tuple(logits.stride())}")
-    R, V = logits.shape
-    k, chunk = int(k), int(chunk)
+    R, V = _logits_rows("token_eval", logits)
+    k = int(k)
     if not 0 <= k <= min(_lib.TOKEN_MAX_K, V):
         raise ValueError(f"token_eval: k={k} outside [0, min({_lib.TOKEN_MAX_K}, V={V})]")
-    if chunk != 0 and not 64 <= chunk <= 65536:
-        raise ValueError(f"token_eval: chunk={chunk} is neither 0 nor in [64, 65536]")
+    chunk = _chunk_arg("token_eval", chunk)
     if want_topk and k == 0:
         raise ValueError("token_eval: want_topk needs k > 0")
     dev = logits.device

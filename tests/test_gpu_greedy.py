@@ -25,19 +25,19 @@ def rounded(x, dtype):
     return torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).to(dtype).float().numpy()
 
 
-def on_device(x, dtype, ld, pad_value):
-    """x float32 [R, V] of values exact in `dtype` -> a [R, V] view of a [R, ld] device buffer with the same bits (NaN signs and
-    payloads included) whose padding columns [V, ld) hold `pad_value`."""
+def on_device(x, dtype, ld, pad_value, off=0):
+    """x float32 [R, V] of values exact in `dtype` -> a [R, V] view, `off` elements into the rows of a [R, ld + off] device buffer,
+    with the same bits (NaN signs and payloads included); every other element holds `pad_value`."""
     R, V = x.shape
-    buf = torch.full((R, ld), pad_value, dtype=dtype, device=DEV)
+    buf = torch.full((R, ld + off), pad_value, dtype=dtype, device=DEV)
     if dtype == torch.float32:
         body = torch.from_numpy(np.ascontiguousarray(x))
     else:
         hi = (np.ascontiguousarray(x).view(np.uint32) >> 16).astype(np.uint16).view(np.int16)
         body = torch.from_numpy(hi.copy()).view(torch.bfloat16)
         assert np.array_equal(body.float().numpy().view(np.uint32), x.view(np.uint32))
-    buf[:, :V] = body.to(DEV)
-    return buf[:, :V]
+    buf[:, off:off + V] = body.to(DEV)
+    return buf[:, off:off + V]
 
 
 def tokens(xd, chunk=0):
@@ -87,6 +87,10 @@ def test_argmax_equals_the_rule(shape, dname):
         assert np.array_equal(keys.cpu().numpy().view(np.uint64), M.chunk_keys(x))              # every chunk's key, not only the winner
         for chunk in CHUNKS:
             assert np.array_equal(tokens(xd, chunk), want), (chunk, pad_value)
+        xd = on_device(x, dtype, ld, pad_value, off=1)                                           # a base pointer one element off
+        assert np.array_equal(ops.greedy_argmax(xd).cpu().numpy().view(np.uint64), M.chunk_keys(x))
+        for chunk in CHUNKS:
+            assert np.array_equal(tokens(xd, chunk), want), (chunk, pad_value, "off=1")
 
 
 @pytest.mark.parametrize("dname", list(DTYPES))
