@@ -72,6 +72,10 @@ extern "C" {
 /* 4 (additive): constrained beam search on the answer list.  m3ae_triebeam_select and m3ae_triebeam_step (csrc/trie_beam.hip): the
  *    BeamSearchScorer of m3ae_beam_step with the trie as the prefix constraint and an n-best list of labels with scores as the
  *    result; m3ae_vqa_labels_eval (csrc/vqa_eval.hip): the score record from n-best labels; no descriptor changed. */
+/* 4 (additive): exhaustive answer-list scoring.  m3ae_tree_attn (csrc/tree_attn.hip): attention whose keys are a row's trie
+ *    ancestors; m3ae_listscore_lse (+ m3ae_listscore_workspace_bytes), m3ae_listscore_edges and m3ae_listscore_fold (+
+ *    m3ae_listscore_fold_workspace_bytes) (csrc/list_score.hip): every list entry's log-probability from one pass over the trie's
+ *    internal nodes, the k best entries, probabilities over the list and the list's mass; no descriptor changed. */
 #define M3AE_ABI_VERSION 4
 
 enum { M3AE_F32 = 0, M3AE_BF16 = 1 };
@@ -974,6 +978,68 @@ int m3ae_triebeam_step(const float* top_s, const int32_t* top_beam, const int32_
 int m3ae_vqa_labels_eval(const int64_t* labels, int64_t ldl, int64_t k, const float* targets, int64_t ldt, const int32_t* types,
                          int64_t B, int64_t C, float* hit1, double* rec, int64_t* err, void* workspace, int64_t workspace_bytes,
                          void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Exhaustive answer-list scoring (csrc/tree_attn.hip, csrc/list_score.hip; ABI 4, additive): the log-probability of EVERY entry of
+ * the answer list from one decoder pass over the internal nodes of the answer trie (the nodes that have children: a decoder row
+ * computed for a node serves every answer through it), the list's arg-max, its k best entries with probabilities over the list and
+ * the mass the head puts on the list.  No atomics, every reduction in a fixed order: two calls on the same inputs give the same bits.
+ *
+ * Tables, int32, device memory, beside the trie above: internal [Ni] (the nodes with children, ascending), anc [Ni][Dmax] (for
+ *   internal row i the internal rows from the root, first, to i itself, last, then -1), parent [N] (-1 at the root), depth [N],
+ *   level_off [Dmax + 2] (the nodes of depth d are level_off[d] .. level_off[d + 1] - 1), leaf_node [A] (the leaf of each label).
+ *   Nodes are numbered breadth-first in the order their edges are made: the edge into node n is entry n - 1 of child_tok, E = N - 1,
+ *   a parent precedes its children.  The caller checks the tables; the kernels turn no table value into an address without a range
+ *   check and report through err int64 [1].
+ *
+ * m3ae_tree_attn: attention whose keys are a row's trie ancestors, forward only, no dropout.  q, k, v [G][Ni][H * Dh] with row
+ *   strides ldq / ldk / ldv >= H * Dh in elements (row g * Ni + i starts at row * ld: the thirds of a packed qkv buffer qualify),
+ *   out [G][Ni][H * Dh] with row stride ldo, all of dtype M3AE_F32 or M3AE_BF16; Dh 64 or 96; 1 <= Dmax <= 32.  rel_bias fp32
+ *   [H][Dmax] or NULL: rel_bias[h][depth(query) - depth(key)] is added to a score.  One wave per (group, row, head); arithmetic in
+ *   fp32 in the order csrc/tree_attn.hip documents: dot product (a lane's one or two products, then a 6-stage butterfly), s =
+ *   fmaf(dot, scale, bias), softmax with the maximum subtracted over the row's 1 .. 32 keys, the weighted sum by ascending key,
+ *   one division, one rounding to the output dtype.  A row with one key gives v exactly.  A row whose anc holds no leading entry
+ *   >= 0 or an entry >= Ni sets err[0] = 1 and is written as zeros.
+ *   M3AE_ERR_ARG: a NULL pointer (rel_bias aside), a count < 1, a stride < H * Dh.  M3AE_ERR_UNSUPPORTED: another dtype, Dh not 64 /
+ *   96, Dmax > 32, G * Ni >= 2^31.  M3AE_ERR_ALIGN: a pointer off its element size.
+ * m3ae_listscore_lse: logits [R][V] as m3ae_trie_scan takes them (fp32 or bf16, row stride ld >= V, element-aligned base, columns
+ *   [V, ld) never read), R = G * Ni; chunk as there (0 = 8192).  One workgroup per (chunk, row) writes the chunk's (m, s) in fp32,
+ *   by the arithmetic of m3ae_trie_scan's chunk items, to workspace fp32 [R][chunks][2]: m3ae_listscore_workspace_bytes(R, V, chunk)
+ *   bytes (0 for shapes the call rejects), 8-byte aligned.  Status codes as m3ae_trie_scan.
+ * m3ae_listscore_edges: from the same logits and that workspace (nch = chunks per row), one workgroup per row g * Ni + i: lse = m +
+ *   logf(s) of the row's pairs folded in ascending chunk order (as m3ae_trie_step); edge_lp[g][e] = x[child_tok[e]] - lse in fp32
+ *   for every child entry e of node internal[i], any number of them; edge_lp fp32 [G][E].  A node outside [0, N) or without a child
+ *   range sets err[0] = 1 and writes nothing; a token outside [0, V) sets err[0] = 1 and its edge is NaN.
+ *   M3AE_ERR_ARG: a NULL pointer, a count < 1, ld < V.  M3AE_ERR_UNSUPPORTED: another dtype, V, N, E or G * Ni >= 2^31, Ni > N.
+ *   M3AE_ERR_ALIGN; M3AE_ERR_WORKSPACE: a missing, misaligned or short (m, s) workspace.
+ * m3ae_listscore_fold: one workgroup per sample b of edge_lp fp32 [B][N - 1].  node_lp[0] = 0 and level by level node_lp[n] =
+ *   node_lp[parent[n]] + (double)edge_lp[b][n - 1] -- fp32 terms added in double in path order, m3ae_trie_step's rule, so that on
+ *   the same logits an entry's log-probability has the bits that search accumulates along its path.  all_logprob double [B][A] =
+ *   node_lp at the labels' leaves; score = logprob / pen[len], pen double [Dmax + 1] = len ** length_penalty from the caller, len =
+ *   depth[leaf]; log_mass double [B] = M + log(sum_i exp(logprob_i - M)) over the finite entries, M their maximum, summed in label
+ *   order; the 1 <= k <= 16 best entries by (score descending, label ascending) into labels int64 / scores / logprob / probs double
+ *   [B][k], probs = exp(logprob - log_mass); ranks >= A hold label -1 and zeros; n_hyp int64 [B] = min(k, A); best int64 [B] =
+ *   labels[b][0], len int64 [B] = its token count.  Non-finite values: an entry whose logprob is not finite has probability 0 and adds
+ *   nothing to the mass; with no finite entry log_mass = -inf and every probability is 0; a NaN score ranks after every number,
+ *   label ascending among NaNs; +0 == -0.  A parent that is not in an earlier level, a level outside [1, N], a leaf outside [1, N) or a depth outside
+ *   [1, Dmax] sets err[0] = 1 and yields NaN, never an address.  workspace: m3ae_listscore_fold_workspace_bytes(B, N) bytes (0 while
+ *   node_lp fits the workgroup's LDS, N <= 4096; -1 for counts the call rejects), 8-byte aligned.
+ *   M3AE_ERR_ARG: a NULL pointer, B < 1, N < 2, A < 1, Dmax < 1, k < 1.  M3AE_ERR_UNSUPPORTED: k > 16, Dmax > 32, A >= N, N or B >=
+ *   2^31.  M3AE_ERR_ALIGN: a pointer off its element size.  M3AE_ERR_WORKSPACE: a missing, misaligned or short workspace. */
+int m3ae_tree_attn(const void* q, int64_t ldq, const void* k, int64_t ldk, const void* v, int64_t ldv, void* out, int64_t ldo,
+                   const int32_t* anc, int64_t Dmax, const float* rel_bias, float scale, int64_t G, int64_t Ni, int64_t H, int64_t Dh,
+                   int dtype, int64_t* err, void* stream);
+int64_t m3ae_listscore_workspace_bytes(int64_t R, int64_t V, int64_t chunk);
+int m3ae_listscore_lse(const void* logits, int64_t ld, int64_t R, int64_t V, int64_t chunk, int dtype, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int m3ae_listscore_edges(const void* logits, int64_t ld, int64_t G, int64_t Ni, int64_t V, int dtype, const void* workspace,
+                         int64_t workspace_bytes, int64_t nch, const int32_t* internal, const int32_t* child_off, const int32_t* child_tok,
+                         int64_t N, int64_t E, float* edge_lp, int64_t* err, void* stream);
+int64_t m3ae_listscore_fold_workspace_bytes(int64_t B, int64_t N);
+int m3ae_listscore_fold(const float* edge_lp, const int32_t* parent, const int32_t* depth, const int32_t* level_off,
+                        const int32_t* leaf_node, const double* pen, int64_t B, int64_t N, int64_t A, int64_t Dmax, int64_t k,
+                        void* workspace, int64_t workspace_bytes, double* all_logprob, int64_t* labels, double* scores, double* logprob,
+                        double* probs, double* log_mass, int64_t* n_hyp, int64_t* best, int64_t* len, int64_t* err, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Device-side token evaluation (csrc/token_eval.hip; ABI 4, additive): what the reference's `Accuracy` metric computes for the MLM

@@ -201,6 +201,15 @@ _SIGS = {
     "m3ae_triebeam_step": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                       i64, i64, i64, i64, i64, i64, i64, C.c_double, vp]),
     "m3ae_vqa_labels_eval": (C.c_int, [vp, i64, i64, vp, i64, vp, i64, i64, vp, vp, vp, vp, i64, vp]),
+    # exhaustive answer-list scoring (ABI 4, additive): attention over a row's trie ancestors; per-chunk (m, s), the edges'
+    # log-probabilities, and the fold into every entry's log-probability, the k best, probabilities and the list's mass
+    "m3ae_tree_attn": (C.c_int, [vp, i64, vp, i64, vp, i64, vp, i64, vp, i64, vp, f32, i64, i64, i64, i64, C.c_int, vp, vp]),
+    "m3ae_listscore_workspace_bytes": (i64, [i64, i64, i64]),
+    "m3ae_listscore_lse": (C.c_int, [vp, i64, i64, i64, i64, C.c_int, vp, i64, vp]),
+    "m3ae_listscore_edges": (C.c_int, [vp, i64, i64, i64, i64, C.c_int, vp, i64, i64, vp, vp, vp, i64, i64, vp, vp, vp]),
+    "m3ae_listscore_fold_workspace_bytes": (i64, [i64, i64]),
+    "m3ae_listscore_fold": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                      vp]),
 }
 
 EXPORTS = tuple(_SIGS)

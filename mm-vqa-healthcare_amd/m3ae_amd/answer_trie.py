@@ -11,6 +11,7 @@ the list alone.  Every sequence ends with an end token and holds none before, so
 a row of the search cannot get stuck.  The device follows the table unchecked (as lora.LoraTable): `to_device` is the check."""
 import numpy as np
 
+SCORE_MAX_DEPTH = 32    # the longest answer exhaustive list scoring takes: the key count of one wave pass of m3ae_tree_attn
 
 class AnswerTrie:
     def __init__(self, sequences, end_ids):
@@ -59,6 +60,9 @@ class AnswerTrie:
         self.max_token = int(self.child_tok.max())
         self._uploaded = {}             # device -> the int32 trie buffer
         self._uploaded_answers = {}     # (device, max_len, pad_id) -> the int64 answers table
+        self._score_tables = None       # score_tables(), built on first use
+        self._uploaded_score = {}       # device -> the int32 buffer of the score tables
+        self._uploaded_pen = {}         # device -> {length_penalty: the double table of len ** length_penalty}
 
     @classmethod
     def from_answers(cls, id_lists, end_id):
@@ -87,6 +91,73 @@ class AnswerTrie:
         for i, s in enumerate(self.sequences):
             tab[i, :len(s)] = s
         return tab
+
+    def score_tables(self):
+        """The tables of exhaustive list scoring (csrc/tree_attn.hip, csrc/list_score.hip), a function of the list alone; all int32:
+          parent    [N]           the parent node, -1 at the root
+          depth     [N]           the node's depth, 0 at the root
+          in_tok    [N]           the token on the edge into the node (-1 at the root: the start id is filled in at upload)
+          internal  [Ni]          the nodes that have children, ascending -- breadth-first numbering, so ascending in depth too
+          row_of    [N]           the inverse of `internal`, -1 at leaves
+          anc       [Ni, depth]   for internal row i the internal rows from the root (first) to itself (last), then -1
+          level_off [depth + 2]   the nodes of depth d are level_off[d] .. level_off[d + 1] - 1
+          leaf_node [A]           the leaf of each label
+        The edge into node n is entry n - 1 of child_tok / child_node: every edge makes one node, in the order the edges are made.
+        ValueError if the longest answer has more than SCORE_MAX_DEPTH tokens (the depth cap of m3ae_tree_attn)."""
+        if self._score_tables is not None:
+            return self._score_tables
+        if self.depth > SCORE_MAX_DEPTH:
+            raise ValueError(f"AnswerTrie: the longest answer has {self.depth} tokens, list scoring has room for {SCORE_MAX_DEPTH}")
+        N, D = self.num_nodes, self.depth
+        if not np.array_equal(self.child_node, np.arange(1, N, dtype=np.int32)):
+            raise ValueError("AnswerTrie: the nodes are not numbered in the order of their edges")
+        parent = np.full(N, -1, dtype=np.int32)
+        depth = np.zeros(N, dtype=np.int32)
+        in_tok = np.full(N, -1, dtype=np.int32)
+        counts = np.diff(self.child_off)
+        parent[1:] = np.repeat(np.arange(N, dtype=np.int32), counts)
+        in_tok[1:] = self.child_tok
+        for n in range(1, N):                   # a parent precedes its children
+            depth[n] = depth[parent[n]] + 1
+        internal = np.flatnonzero(counts > 0).astype(np.int32)
+        row_of = np.full(N, -1, dtype=np.int32)
+        row_of[internal] = np.arange(len(internal), dtype=np.int32)
+        anc = np.full((len(internal), D), -1, dtype=np.int32)
+        for i, n in enumerate(internal):
+            d = int(depth[n])
+            anc[i, d] = i
+            if d:
+                anc[i, :d] = anc[row_of[parent[n]], :d]
+        level_off = np.searchsorted(depth, np.arange(D + 2)).astype(np.int32)      # depth is non-decreasing in node order
+        leaf_node = np.zeros(self.num_answers, dtype=np.int32)
+        leaves = np.flatnonzero(self.leaf_label >= 0)
+        leaf_node[self.leaf_label[leaves]] = leaves
+        self._score_tables = dict(parent=parent, depth=depth, in_tok=in_tok, internal=internal, row_of=row_of, anc=anc,
+                                  level_off=level_off, leaf_node=leaf_node)
+        return self._score_tables
+
+    def score_to_device(self, device, V, max_len, pad_id=0):
+        """to_device(device, V, max_len, pad_id) plus the upload of score_tables(), once per device: the namespace also holds parent,
+        node_depth, in_tok, internal, anc ([Ni, Dmax], Dmax = depth), level_off, leaf_node and Ni.  This upload is the range check the
+        list-score kernels rely on (they still turn no table value into an address unchecked)."""
+        import torch
+        t = self.score_tables()
+        ns = self.to_device(device, V, max_len, pad_id)
+        device = torch.device(device)
+        buf = self._uploaded_score.get(device)
+        names = ("parent", "depth", "in_tok", "internal", "anc", "level_off", "leaf_node")
+        if buf is None:
+            host = torch.from_numpy(np.concatenate([t[n].reshape(-1) for n in names]))
+            buf = host.pin_memory().to(device, non_blocking=True) if device.type == "cuda" else host
+            self._uploaded_score[device] = buf
+        o = 0
+        for n in names:
+            view = buf[o:o + t[n].size].view(t[n].shape)
+            setattr(ns, "node_depth" if n == "depth" else n, view)
+            o += t[n].size
+        ns.Ni, ns.score_buf = len(t["internal"]), buf
+        ns.pen = self._uploaded_pen.setdefault(device, {})     # length_penalty -> the double table len ** length_penalty (ops.listscore_fold)
+        return ns
 
     def to_device(self, device, V, max_len, pad_id=None):
         """Uploads the arrays as one int32 buffer and returns a namespace of views of it (child_off, child_tok, child_node,

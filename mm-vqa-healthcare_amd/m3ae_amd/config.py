@@ -68,6 +68,10 @@ DEFAULTS = dict(
     # entry); 1.0 is HF generate's length-normalised ranking.
     answer_beams=1,
     answer_length_penalty=0.0,
+    # answer_decoding="list" only: "search" (the list search above, the launches it always made) | "exhaustive" (every list entry
+    # scored in one tree-shaped decoder pass, csrc/tree_attn.hip + csrc/list_score.hip: the list's arg-max, the min(eval_topk, 16)
+    # best answers for `@k`, and the mean mass the head puts on the list; answer_beams is then ignored).
+    answer_scoring="search",
     # where validation / test compute their metric (m3ae_amd/trainer.py, m3ae_amd/metrics.py): "host" (ATen float / argmax /
     # gather / sum: the overall VQA score alone) | "device" (csrc/vqa_eval.hip: overall, closed and open scores, the score within
     # the top `eval_topk` answers, and token exact match for the generator heads in test()).  eval_topk is honoured only with "device".
@@ -293,6 +297,19 @@ def answer_beams(cfg):
     return nb, float(lp)
 
 
+ANSWER_SCORINGS = ("search", "exhaustive")
+
+
+def answer_scoring(cfg):
+    """The validated `answer_scoring` of a config dict (default "search": the list search of `answer_beams`).  "exhaustive" scores
+    every list entry in one tree-shaped decoder pass instead (csrc/list_score.hip).  Read under answer_decoding="list" only,
+    checked always."""
+    v = cfg.get("answer_scoring", "search")
+    if not isinstance(v, str) or v not in ANSWER_SCORINGS:
+        raise ValueError(f"answer_scoring must be one of {ANSWER_SCORINGS}, got {v!r}")
+    return v
+
+
 VQA_METRICS = ("host", "device")
 
 
@@ -341,6 +358,7 @@ def resolve_arch(cfg):
     decoder_search(cfg)
     answer_decoding(cfg)
     answer_beams(cfg)
+    answer_scoring(cfg)
     vqa_metrics(cfg)
     pretrain_metrics(cfg)
     if "gradient_clip_val" in cfg:

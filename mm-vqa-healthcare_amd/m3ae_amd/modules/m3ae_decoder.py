@@ -26,10 +26,13 @@ Greedy search: `search_path` (host bookkeeping, the default) or, with `decoder_s
 search with argmax and bookkeeping on the GPU (`search_path_async`, csrc/greedy.hip); `DecoderModel.generate` wraps either.
 Answer-list decoding: `answer_path_async` restricts that search to a prefix trie of candidate answers (answer_trie.py,
 csrc/answer_trie.hip) and returns labels with log-probabilities; `DecoderModel.answer` / `answer_async` wrap it.
+`answer_scores_async` scores EVERY list entry in one tree-shaped pass instead (csrc/tree_attn.hip, csrc/list_score.hip): the
+list's arg-max, its k best entries, probabilities over the list (`DecoderModel.answer_probs`) and the list's mass.
 Tokenisation happens outside (`batch["decoder_tokens"]`: int64 [B, T] = [CLS] answer [SEP] [PAD]...) or through a
 `tokenizer` callable; string metrics (ROUGE / BLEU / exact match) stay out of scope.
 """
 import math
+from types import SimpleNamespace as NS
 
 import torch
 import torch.nn as nn
@@ -268,6 +271,59 @@ class Decoder(nn.Module):
         beam = TrieBeam(B, nb, self.max_len, dt, dev, cls_id, pad_id, length_penalty, chunk)
         return run_search(DecoderHead(self, cross_attn_feats, dt.depth, nb), beam, dt.depth, lookahead or None)
 
+    def default_score_rows(self):
+        """The default `max_rows` of answer_scores_async: the rows whose (padded) logits fill 2 GiB.  Not measured: DESIGN.md 9."""
+        V = self.final_linear.weight.shape[0]
+        return (2 << 30) // ((V + 127) // 128 * 128 * (2 if self.head_dtype == torch.bfloat16 else 4))
+
+    @torch.no_grad()
+    @ops.model_mode
+    def answer_scores_async(self, cross_attn_feats, trie, k=1, length_penalty=0.0, cls_id=101, pad_id=0, max_rows=None, chunk=0):
+        """Exhaustive scoring of the answer list (csrc/tree_attn.hip, csrc/list_score.hip): the teacher-forced log-probability of EVERY
+        entry of `trie` in one pass of the live layer over the trie's Ni internal nodes -- a row computed for a node serves every
+        answer through it -- with no search loop and no blocking host call.  The self-attention half sees 2 * emb + pe alone, so it
+        runs once per call at Ni rows (a row's keys are its trie ancestors: ops.tree_attention); the rest runs per group of samples at
+        group * Ni rows, `max_rows` capping that product (None: default_score_rows(); a group holds at least one sample), and the
+        list-score kernels read the logits as the GEMM left them.  Returns a namespace on the device: `labels` int64 [B, k] (the k
+        <= 16 best entries by logprob / len ** length_penalty, -1 past the list's end), `scores`, `logprob`, `probs` float64 [B, k]
+        (probs = exp(logprob - log_mass): a probability over the list), `log_mass` float64 [B] (the log of the probability the head
+        puts on the list at all), `n_hyp`, `label` / `score` (column 0: the list's arg-max), `seq` / `len` (its tokens), `err`, `out`
+        (all of these in one buffer), `all_logprob` float64 [B, A] and `state` (ops.ListScoreState)."""
+        B, dev = cross_attn_feats.shape[0], cross_attn_feats.device
+        V, D, H = self.final_linear.weight.shape[0], self.target_embedding.weight.shape[1], self.num_heads
+        dt = trie.score_to_device(dev, V, self.max_len, pad_id)
+        st = ops.ListScoreState(B, k, self.max_len, dt, dev, pad_id)
+        Ni, layer = dt.Ni, self.dec_layers[self.num_layers - 1]
+        rows = dt.internal.long()
+        ids = dt.in_tok.index_select(0, rows).long()
+        ids[:1].fill_(cls_id)        # internal[0] is the root: the start token stands before it (fill_: a launch, not a host copy)
+        pe_rows = self.positional_encoding.pe[0].index_select(0, dt.node_depth.index_select(0, rows).long()).to(torch.float32).contiguous()
+        # once per call: the self-attention half and the cross-attention query
+        t = _DecoderEmbedFn.apply(ids, self.target_embedding.weight, pe_rows, self.head_dtype).view(1, Ni, D)
+        qkv = ops.linear(layer._ln(layer.pre_norm, t), layer.mha1.in_proj_weight, layer.mha1.in_proj_bias)[0]
+        ctx = ops.tree_attention(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], dt.anc, H, err=st.err).view(1, Ni, D)
+        x = ops.linear(ctx, layer.mha1.out_proj.weight, layer.mha1.out_proj.bias, residual=t)
+        q = ops.linear(layer._ln(layer.layernorm1, x), layer.mha2.in_proj_weight, layer.mha2.in_proj_bias)[..., :D]
+        # per group of samples: cross-attention onward at group * Ni rows
+        cap = self.default_score_rows() if max_rows is None else int(max_rows)
+        Gmax = max(1, min(B, cap // Ni))
+        qg, xg = q.expand(Gmax, Ni, D).contiguous(), x.expand(Gmax, Ni, D).contiguous()
+        feats = cross_attn_feats.to(self.head_dtype)
+        ws = ops.listscore_workspace(Gmax * Ni, V, dev, chunk)
+        for g0 in range(0, B, Gmax):
+            G = min(Gmax, B - g0)
+            enc_kv = layer.cross_kv(feats[g0:g0 + G])
+            ctx, _ = ops.attn_forward(qg[:G], enc_kv[..., :D], enc_kv[..., D:], H)
+            y = ops.linear(ctx, layer.mha2.out_proj.weight, layer.mha2.out_proj.bias, residual=xg[:G])
+            y = ops.mlp(layer._ln(layer.layernorm2, y), layer.ffn[0].weight, layer.ffn[0].bias, layer.ffn[2].weight, layer.ffn[2].bias,
+                        ops.ACT_RELU, residual=y)
+            logits = ops.vocab_linear(layer._ln(layer.layernorm3, y).view(G * Ni, D), self.final_linear.weight, self.final_linear.bias)
+            ops.listscore_lse(logits, chunk, ws)
+            ops.listscore_edges(logits, dt, st, ws, g0, chunk)
+        ops.listscore_fold(dt, st, length_penalty)
+        return NS(**{f: getattr(st, f) for f in ("label", "score", "labels", "scores", "logprob", "probs", "log_mass", "n_hyp", "seq", "len",
+                                                 "err", "out", "all_logprob")}, groups=-(-B // Gmax), state=st)
+
     @torch.no_grad()
     @ops.model_mode
     def search_path(self, cross_attn_feats, cls_id=101, sep_id=102, eos_id=None, pad_id=0, use_cache=True, search="host",
@@ -435,11 +491,29 @@ class DecoderModel(_Base):
         return self.decoder.answer_beam_async(self.features(batch), trie, num_beams, length_penalty, self.cls_id, self.pad_id, lookahead)
 
     @ops.model_mode
-    def answer(self, batch, trie, label2ans=None, num_beams=1, k=1, length_penalty=0.0):
+    def answer_scores_async(self, batch, trie, k=1, length_penalty=0.0):
+        """The features of `batch` and the exhaustive scoring of the answer list over them (Decoder.answer_scores_async), nothing
+        copied to the host: its namespace (`labels`, `scores`, `logprob`, `probs`, `log_mass`, `all_logprob`, ...)."""
+        if self.store is None:
+            raise RuntimeError("call finalize(device) before the first forward")
+        return self.decoder.answer_scores_async(self.features(batch), trie, k, length_penalty, self.cls_id, self.pad_id)
+
+    @ops.model_mode
+    def answer_probs(self, batch, trie):
+        """The head's distribution over the answer list, fp32 [B, A] on the device: exp(all_logprob - log_mass), each row summing to
+        1 -- the generator head's counterpart of the classification head's `predict` probabilities."""
+        r = self.answer_scores_async(batch, trie)
+        return torch.exp(r.all_logprob - r.log_mass[:, None]).to(torch.float32)
+
+    @ops.model_mode
+    def answer(self, batch, trie, label2ans=None, num_beams=1, k=1, length_penalty=0.0, exhaustive=False):
         """The answer of every sample as an entry of the list `trie` was built from: (labels int64 [B], scores float64 [B]: the
         log-probability of the entry's tokens), both on the host after ONE copy.  With label2ans (the reference's mapping with
         string keys, as M3AETransformerSS.answers): a list of B (answer, score) instead.  num_beams > 1 searches with that many
-        beams and k <= num_beams returns the k best entries per row (answer_result)."""
+        beams and k <= num_beams returns the k best entries per row (answer_result).  exhaustive=True scores every entry instead of
+        searching (answer_scores_async): the list's arg-max, or its k <= 16 best entries; num_beams is not read."""
+        if exhaustive:
+            return answer_result(self.answer_scores_async(batch, trie, k, length_penalty), label2ans, k)
         r = self.answer_async(batch, trie, num_beams=num_beams, length_penalty=length_penalty)
         return answer_result(r, label2ans, k)
 

@@ -161,9 +161,27 @@ class T5VQA_MMEncoderInput(_Base):
         return self.t5.constrained_beam_async(enc, trie, num_beams, self.max_answer_length, length_penalty, lookahead=lookahead)
 
     @ops.model_mode
-    def answer(self, batch, trie, label2ans=None, num_beams=1, k=1, length_penalty=0.0):
+    def answer_scores_async(self, batch, trie, k=1, length_penalty=0.0):
+        """The encoder output of `batch` and the exhaustive scoring of the answer list over it
+        (T5ForConditionalGeneration.list_scores_async), nothing copied to the host: its namespace."""
+        if self.store is None:
+            raise RuntimeError("call finalize(device) before the first forward")
+        with torch.no_grad():
+            enc = self.t5.encoder(self.prepare_inputs(batch)["inputs_embeds"])
+        return self.t5.list_scores_async(enc, trie, k, self.max_answer_length, length_penalty)
+
+    @ops.model_mode
+    def answer_probs(self, batch, trie):
+        """As DecoderModel.answer_probs: the head's distribution over the answer list, fp32 [B, A] on the device."""
+        r = self.answer_scores_async(batch, trie)
+        return torch.exp(r.all_logprob - r.log_mass[:, None]).to(torch.float32)
+
+    @ops.model_mode
+    def answer(self, batch, trie, label2ans=None, num_beams=1, k=1, length_penalty=0.0, exhaustive=False):
         """As DecoderModel.answer: (labels, scores) on the host after one copy, or (answer, score) pairs with label2ans; the k best
-        of a num_beams search when asked."""
+        of a num_beams search when asked; exhaustive=True scores every entry instead of searching (answer_scores_async)."""
+        if exhaustive:
+            return answer_result(self.answer_scores_async(batch, trie, k, length_penalty), label2ans, k)
         return answer_result(self.answer_async(batch, trie, num_beams=num_beams, length_penalty=length_penalty), label2ans, k)
 
     def training_step(self, batch, batch_idx=0):

@@ -320,6 +320,51 @@ class T5ForConditionalGeneration(nn.Module):
         beam = TrieBeam(enc.shape[0], nb, max_length, dt, enc.device, start, pad_token_id, length_penalty, chunk)
         return run_search(T5Head(self, enc, dt.depth, nb), beam, dt.depth, lookahead or None)   # None or 0: no early exit
 
+    def default_score_rows(self):
+        """The default `max_rows` of list_scores_async: the rows whose fp32 logits fill 2 GiB.  Not measured: DESIGN.md 9."""
+        return (2 << 30) // (4 * self.config.vocab_size)
+
+    @torch.no_grad()
+    def list_scores_async(self, enc, trie, k=1, max_length=12, length_penalty=0.0, pad_token_id=0, max_rows=None, chunk=0):
+        """Exhaustive scoring of the answer list (csrc/tree_attn.hip, csrc/list_score.hip; Decoder.answer_scores_async for this
+        head): every decoder block runs once at [group, Ni] rows, Ni = the trie nodes with children; a row's self-attention keys are
+        its trie ancestors with the relative-position bias taken by depth difference (ops.t5_self_attn_tree); cross-attention and
+        feed-forward are the blocks' own (ops.t5_attn_fwd with the group's keys / values, ops.t5_ff_fwd); then the final norm, the
+        tied head with d_model ** -0.5, and the list-score kernels on the fp32 logits.  Inference arithmetic (no dropout), no
+        blocking host call.  `max_rows` caps group * Ni (None: default_score_rows()).  Returns the namespace of
+        Decoder.answer_scores_async: `labels`, `scores`, `logprob`, `probs` [B, k], `log_mass`, `n_hyp`, `label`, `score`, `seq`
+        (WITHOUT the start token), `len`, `err`, `out`, `all_logprob` [B, A], `groups`, `state`."""
+        B, dev, V, d = enc.shape[0], enc.device, self.config.vocab_size, self.config.d_model
+        dt = trie.score_to_device(dev, V, max_length, pad_token_id)
+        st = ops.ListScoreState(B, k, max_length, dt, dev, pad_token_id)
+        Ni, Dmax = dt.Ni, dt.depth
+        ids = dt.in_tok.index_select(0, dt.internal.long()).long()
+        ids[:1].fill_(self.config.decoder_start_token_id)          # internal[0] is the root: the start token stands before it
+        emb = self.embed(ids.view(1, Ni), enc.dtype)[0]            # [Ni, d]
+        sa = self.decoder.block[0].layer[0].SelfAttention
+        # position_bias[h, q, k] depends on k - q alone: the last query's row, reversed, is the bias by depth(query) - depth(key)
+        rel_bias = sa.position_bias(Dmax, Dmax).detach()[:, Dmax - 1, :].flip(-1).contiguous()
+        cap = self.default_score_rows() if max_rows is None else int(max_rows)
+        Gmax = max(1, min(B, cap // Ni))
+        hg = emb.expand(Gmax, Ni, d).contiguous()
+        ws = ops.listscore_workspace(Gmax * Ni, V, dev, chunk)
+        ln = self.decoder.final_layer_norm
+        for g0 in range(0, B, Gmax):
+            G = min(Gmax, B - g0)
+            h2 = hg[:G].view(G * Ni, d)
+            for blk, kv in zip(self.decoder.block, self.decoder.cross_kv(enc[g0:g0 + G])):
+                P = blk.params()
+                a = ops.t5_self_attn_tree(h2, G, Ni, P.attn, rel_bias, dt.anc, st.err)
+                c, _ = ops.t5_attn_fwd(a, G, P.cross, None, False, 0.0, kv=kv)
+                h2, _ = ops.t5_ff_fwd(c, P.ffn, 0.0)
+            dec = ops.layer_norm(h2, ln.weight, None, ln.eps, rms=True)
+            logits = ops.linear(dec, self.shared.weight, None, alpha=d ** -0.5).float()
+            ops.listscore_lse(logits, chunk, ws)
+            ops.listscore_edges(logits, dt, st, ws, g0, chunk)
+        ops.listscore_fold(dt, st, length_penalty)
+        return NS(**{f: getattr(st, f) for f in ("label", "score", "labels", "scores", "logprob", "probs", "log_mass", "n_hyp", "seq", "len",
+                                                 "err", "out", "all_logprob")}, groups=-(-B // Gmax), state=st)
+
     @torch.no_grad()
     def generate(self, enc, num_beams=4, max_length=12, eos_token_id=1, pad_token_id=0, length_penalty=1.0,
                  len_offset=0, beam_search="host", lookahead=2):

@@ -1500,6 +1500,19 @@ def t5_self_attn_step(h2, B, P, bias_row, cache, t, pdrop=0.0):
     return y
 
 
+def t5_self_attn_tree(h2, G, Ni, P, rel_bias, anc, err):
+    """Exhaustive list scoring: the T5 self-attention sub-layer over the rows of the answer trie's internal nodes, h2 [G Ni, D]
+    (sample g at internal row i in row g Ni + i).  As t5_self_attn_step, but a row's keys are its trie ancestors (tree_attention,
+    scale 1) and rel_bias fp32 [H, Dmax] holds the relative-position bias by depth difference.  Inference only: no dropout."""
+    n, _, _ = ln_fwd_raw(h2, P.ln, rms=True)
+    D, inner, M = n.shape[1], P.w_o.shape[1], G * Ni
+    qkv, _ = mm_nt(n, D, M, compute_weight(P.w_qkv))
+    q3 = qkv.view(G, Ni, 3 * inner)
+    o = tree_attention(q3[..., :inner], q3[..., inner:2 * inner], q3[..., 2 * inner:], anc, P.heads, 1.0, rel_bias, err)
+    y, _ = mm_nt(o.view(M, inner), inner, M, compute_weight(P.w_o), residual=h2)
+    return y
+
+
 def _t5_attn_bwd(dy, saved, B, P, bias, causal, dbias, need_dh=True, need_dsrc=True):
     h2, rstd, n, proj, o, lse, xkv, da, dh_drop = saved
     need_dh = need_dh or P.ln.weight.requires_grad  # the RMSNorm scale gradient comes out of the same kernel
@@ -2041,12 +2054,12 @@ def beam_topk(logits, beam_scores, B, nb, chunk=0, ws=None, out=None):
 class _SearchState:
     """What the four search states share: every result field and the error word `err` live in ONE int64 buffer `out`, so one copy
     brings a whole result to the host.  `layout` ({field: shape} in buffer order, then err; `scores` and `logprob` hold the bits of
-    float64) is the only description of that buffer: views() applies it to the device buffer (alloc_out) and to a host copy (host).
+    float64, as do `probs` and `log_mass` of the list-score state) is the only description of that buffer: views() applies it to the device buffer (alloc_out) and to a host copy (host).
     The answer-list states hold `labels` / `scores` [B, nb] for search.answer_result; k_text is its word on a k outside [1, nb]."""
 
     def views(self, out):
         parts = out.split([math.prod(shape) for shape in self.layout.values()] + [1])
-        return _NS(err=parts[-1], **{n: (p.view(torch.float64) if n in ("scores", "logprob") else p).view(shape)
+        return _NS(err=parts[-1], **{n: (p.view(torch.float64) if n in ("scores", "logprob", "probs", "log_mass") else p).view(shape)
                                      for (n, shape), p in zip(self.layout.items(), parts)})
 
     def alloc_out(self, device, **layout):
@@ -2375,6 +2388,136 @@ def trie_beam_result(trie, st):
         raise ValueError(f"trie_beam_result: the answers table int64 [A, {st.max_len}]")
     check(_lib.lib().m3ae_gather_rows(_p(tab), _p(st.best), _p(st.seq), st.Bs, 2 * st.max_len, F32, _stream()), "m3ae_gather_rows")
     return st.seq
+
+
+# ------------------------------------------------------------------------------------------------------------
+# exhaustive answer-list scoring (csrc/tree_attn.hip, csrc/list_score.hip): Decoder.answer_scores_async
+# ------------------------------------------------------------------------------------------------------------
+LIST_MAX_K, LIST_MAX_DEPTH = 16, 32
+
+
+def tree_attention(q, k, v, anc, heads, scale=None, rel_bias=None, err=None):
+    """Attention whose keys are a row's trie ancestors (m3ae_tree_attn): q, k, v [G, Ni, D] or [Ni, D] (fp32 or bf16, unit last
+    stride, rows of a group one row stride apart: thirds of a packed qkv buffer qualify), anc int32 [Ni, Dmax <= 32] contiguous
+    (AnswerTrie.score_tables), rel_bias fp32 [heads, Dmax] or None, err int64 [1] (allocated when None).  D / heads is 64 or 96.
+    Returns out [.., Ni, D] in the input dtype, contiguous; err is set by a table value out of range (that row is zeros)."""
+    for t in (q, k, v, anc):
+        _need_cuda(t)
+    shape = q.shape
+    if q.dim() == 2:
+        q, k, v = q.unsqueeze(0), k.unsqueeze(0), v.unsqueeze(0)
+    if q.dim() != 3 or k.shape != q.shape or v.shape != q.shape or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError(f"tree_attention: q {tuple(q.shape)} {q.dtype}, k {tuple(k.shape)} {k.dtype}, v {tuple(v.shape)} {v.dtype}")
+    G, Ni, D = q.shape
+    if G < 1 or Ni < 1 or D % heads:
+        raise ValueError(f"tree_attention: shape {tuple(q.shape)} for {heads} heads")
+    for t in (q, k, v):
+        if t.stride(2) != 1 or t.stride(1) < D or (G > 1 and t.stride(0) != Ni * t.stride(1)):
+            raise ValueError(f"tree_attention: strides {tuple(t.stride())} (unit last stride, groups a whole number of rows apart)")
+    if anc.dtype != torch.int32 or anc.dim() != 2 or anc.shape[0] != Ni or not 1 <= anc.shape[1] <= LIST_MAX_DEPTH or not anc.is_contiguous():
+        raise ValueError(f"tree_attention: anc int32 [{Ni}, 1 .. {LIST_MAX_DEPTH}], contiguous")
+    Dmax = anc.shape[1]
+    if rel_bias is not None and (rel_bias.dtype != torch.float32 or tuple(rel_bias.shape) != (heads, Dmax) or not rel_bias.is_contiguous()
+                                 or not rel_bias.is_cuda):
+        raise ValueError(f"tree_attention: rel_bias fp32 [{heads}, {Dmax}], contiguous")
+    if err is None:
+        err = torch.zeros((1,), dtype=torch.int64, device=q.device)
+    elif err.dtype != torch.int64 or err.numel() != 1 or not err.is_cuda:
+        raise ValueError("tree_attention: err int64 [1]")
+    Dh = D // heads
+    out = torch.empty((G, Ni, D), dtype=q.dtype, device=q.device)
+    check(_lib.lib().m3ae_tree_attn(_p(q), q.stride(1), _p(k), k.stride(1), _p(v), v.stride(1), _p(out), D, _p(anc), Dmax, _p(rel_bias),
+                                    (1.0 / math.sqrt(Dh)) if scale is None else float(scale), G, Ni, heads, Dh, _dt(q), _p(err), _stream()),
+          "m3ae_tree_attn")
+    return out.view(*shape[:-1], D)
+
+
+def listscore_workspace(R, V, device, chunk=0):
+    """The workspace of listscore_lse / listscore_edges: int64 [R, chunks of a row] words (the bits of the fp32 (m, s) pairs)."""
+    return _chunk_workspace("listscore_workspace", _lib.lib().m3ae_listscore_workspace_bytes, "m3ae_listscore_lse", R, V, device, chunk)
+
+
+class ListScoreState(_SearchState):
+    """The device state of one exhaustive scoring of the answer list (include/m3ae_hip.h, m3ae_listscore_fold): allocated once per
+    call.  `trie` is what AnswerTrie.score_to_device returned.  The k best entries of every sample with scores, log-probabilities and
+    probabilities over the list, the list's log-mass and the token row of the best entry live in `out`; all_logprob double [B, A]
+    has a buffer of its own, as have the scratch arrays (edge_lp fp32 [B, E], best int64 [B], the fold's workspace)."""
+    err_text, k_text = TrieState.err_text, "answer_result: k={k} outside [1, the k={nb} the list was scored with]"
+
+    def __init__(self, B, k, max_len, trie, device, pad_id=0):
+        k = int(k)
+        if not 1 <= k <= LIST_MAX_K:
+            raise ValueError(f"ListScoreState: k={k} outside [1, {LIST_MAX_K}]")
+        if trie.depth > max_len or trie.depth > LIST_MAX_DEPTH:
+            raise ValueError(f"ListScoreState: the longest answer has {trie.depth} tokens, there is room for {min(max_len, LIST_MAX_DEPTH)}")
+        self.B, self.nb, self.max_len, self.pad_id = B, k, max_len, pad_id
+        self.alloc_out(device, seq=(B, max_len), len=(B,), labels=(B, k), scores=(B, k), logprob=(B, k), probs=(B, k), log_mass=(B,),
+                       n_hyp=(B,))
+        self.label, self.score = self.labels[:, 0], self.scores[:, 0]
+        self.all_logprob = torch.zeros((B, trie.A), dtype=torch.float64, device=device)
+        self.edge_lp = torch.zeros((B, trie.E), dtype=torch.float32, device=device)
+        self.best = torch.zeros((B,), dtype=torch.int64, device=device)
+        need = _lib.lib().m3ae_listscore_fold_workspace_bytes(B, trie.N)
+        if need < 0:
+            raise ValueError(f"ListScoreState: B={B}, N={trie.N} is not a shape m3ae_listscore_fold takes")
+        self.fold_ws = torch.empty((need // 8,), dtype=torch.float64, device=device) if need else None
+
+
+def _listscore_ws(what, ws, R, V, chunk):
+    need = _lib.lib().m3ae_listscore_workspace_bytes(R, V, chunk)
+    if need <= 0:
+        raise ValueError(f"{what}: R={R}, V={V}, chunk={chunk} is not a shape m3ae_listscore_lse takes")
+    if ws.dtype != torch.int64 or not ws.is_contiguous() or not ws.is_cuda or ws.numel() * 8 < need:
+        raise ValueError(f"{what}: ws is the int64 buffer of listscore_workspace")
+    return need // (8 * R)
+
+
+def listscore_lse(logits, chunk=0, ws=None):
+    """logits fp32 or bf16 [R, V] (row stride >= V, unit column stride), read once: the (m, s) pair of every vocabulary chunk of
+    every row, into `ws` (listscore_workspace).  Returns ws."""
+    R, V = _logits_rows("listscore_lse", logits)
+    chunk = _chunk_arg("listscore_lse", chunk)
+    if ws is None:
+        ws = listscore_workspace(R, V, logits.device, chunk)
+    _listscore_ws("listscore_lse", ws, R, V, chunk)
+    check(_lib.lib().m3ae_listscore_lse(_p(logits), logits.stride(0), R, V, chunk, _dt(logits), _p(ws), ws.numel() * 8, _stream()),
+          "m3ae_listscore_lse")
+    return ws
+
+
+def listscore_edges(logits, trie, st, ws, first=0, chunk=0):
+    """logits [G * Ni, V] of samples first .. first + G - 1 (row g * Ni + i: sample first + g at node trie.internal[i]) and the
+    workspace listscore_lse filled from them (same chunk): st.edge_lp[first + g, e] = x[tok_e] - lse for every edge of the trie."""
+    _need_cuda(st.out)
+    R, V = _logits_rows("listscore_edges", logits)
+    G, Ni = R // trie.Ni, trie.Ni
+    if G * Ni != R or first < 0 or first + G > st.B or tuple(st.edge_lp.shape) != (st.B, trie.E):
+        raise ValueError(f"listscore_edges: {R} rows for {Ni} internal nodes, samples {first} .. {first + G - 1} of {st.B}")
+    nch = _listscore_ws("listscore_edges", ws, R, V, _chunk_arg("listscore_edges", chunk))
+    check(_lib.lib().m3ae_listscore_edges(_p(logits), logits.stride(0), G, Ni, V, _dt(logits), _p(ws), ws.numel() * 8, nch, _p(trie.internal),
+                                           _p(trie.child_off), _p(trie.child_tok), trie.N, trie.E, _p(st.edge_lp[first:]), _p(st.err), _stream()),
+          "m3ae_listscore_edges")
+
+
+def listscore_fold(trie, st, length_penalty=0.0):
+    """Every entry's log-probability from st.edge_lp, the list's log-mass and the k best entries of every sample (m3ae_listscore_fold),
+    then st.seq = the token rows of the best entries, gathered on the device from the answers table (as trie_beam_result)."""
+    _need_cuda(st.out)
+    tab = trie.answers
+    if (tab.dtype != torch.int64 or tuple(tab.shape) != (trie.A, st.max_len) or not tab.is_contiguous() or not tab.is_cuda
+            or tuple(st.all_logprob.shape) != (st.B, trie.A) or tuple(st.edge_lp.shape) != (st.B, trie.E) or trie.E != trie.N - 1):
+        raise ValueError(f"listscore_fold: the answers table int64 [{trie.A}, {st.max_len}] and a state built for this list")
+    pen = trie.pen.get(float(length_penalty))
+    if pen is None:      # len ** length_penalty per depth, uploaded once per value: pos + 1 is per leaf here
+        host = torch.tensor([1.0] + [float(d) ** float(length_penalty) for d in range(1, trie.depth + 1)], dtype=torch.float64)
+        pen = trie.pen[float(length_penalty)] = host.pin_memory().to(tab.device, non_blocking=True)
+    ws = st.fold_ws
+    check(_lib.lib().m3ae_listscore_fold(_p(st.edge_lp), _p(trie.parent), _p(trie.node_depth), _p(trie.level_off), _p(trie.leaf_node), _p(pen),
+                                          st.B, trie.N, trie.A, trie.depth, st.nb, _p(ws), 0 if ws is None else ws.numel() * 8,
+                                          _p(st.all_logprob), _p(st.labels), _p(st.scores), _p(st.logprob), _p(st.probs), _p(st.log_mass),
+                                          _p(st.n_hyp), _p(st.best), _p(st.len), _p(st.err), _stream()), "m3ae_listscore_fold")
+    check(_lib.lib().m3ae_gather_rows(_p(tab), _p(st.best), _p(st.seq), st.B, 2 * st.max_len, F32, _stream()), "m3ae_gather_rows")
+    return st
 
 
 # ------------------------------------------------------------------------------------------------------------

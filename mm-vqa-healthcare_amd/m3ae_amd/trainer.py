@@ -173,6 +173,11 @@ class Trainer:
         # config keys `answer_beams` / `answer_length_penalty` (read under "list" only): 1 = the greedy list search; 2 .. 8 = the
         # constrained beam search (csrc/trie_beam.hip), whose min(eval_topk, answer_beams) best labels per row give the `@k` score
         self.answer_beams, self.answer_length_penalty = config_mod.answer_beams(cfg)
+        # config key `answer_scoring` (read under "list" only): "search" = the list search above; "exhaustive" = every entry scored in
+        # one tree-shaped decoder pass (Decoder.answer_scores_async), min(eval_topk, 16, A) best labels for `@k`, and `answer_mass`,
+        # the mean probability the head puts on the list; answer_beams is then ignored
+        self.answer_scoring = config_mod.answer_scoring(cfg)
+        self.answer_mass = None
         # config key `pretrain_metrics`: "host" (nothing beyond the monitored loss) | "device" (metrics.PretrainMetrics);
         # pretrain: its result() dict of the last pass
         self.pretrain_metrics = config_mod.pretrain_metrics(cfg)
@@ -296,6 +301,10 @@ class Trainer:
         text = f" answer_list {r['score']:.4f} ({r['n']}) closed {r['closed']:.4f} ({r['n_closed']}) open {r['open']:.4f} ({r['n_open']})"
         if self.answer_k > 1:   # the beam form fed its n-best labels: the best target among a row's k best answers
             text += f" @{self.answer_k} {r['score_at_k']:.4f}"
+        if self.answer_mass is not None:   # answer_scoring="exhaustive": `@k` always, then the mean of exp(log_mass)
+            if self.answer_k <= 1:
+                text += f" @1 {r['score']:.4f}"
+            text += f" mass {self.answer_mass:.4f}"
         return text
 
     def pretrain_text(self):
@@ -342,6 +351,14 @@ class Trainer:
             if self.answer_trie is None:
                 raise ValueError('answer_decoding="list" needs trainer.answer_trie: call set_answer_list(label2ans) or assign an AnswerTrie')
             self.answer_k = max(min(int(self.cfg.get("eval_topk", 5)), self.answer_beams), 1) if self.answer_beams > 1 else 1
+            exhaustive, self.answer_mass = self.answer_scoring == "exhaustive", None
+            if exhaustive:
+                if not hasattr(self.model, "answer_scores_async"):
+                    raise ValueError('answer_scoring="exhaustive" needs a generator head with answer_scores_async')
+                self.answer_k = max(min(int(self.cfg.get("eval_topk", 5)), ops.LIST_MAX_K, self.answer_trie.num_answers), 1)
+                mass = torch.zeros((2,), dtype=torch.float64, device=self.device)     # sum of exp(log_mass), samples
+                if self.answer_beams > 1:
+                    log(f'answer_scoring="exhaustive": answer_beams={self.answer_beams} is ignored', self.rank)
             ans = metrics_mod.VQARADScore(self.device, k=self.answer_k if self.answer_k > 1 else 0)
             ans_err = torch.zeros((1,), dtype=torch.int64, device=self.device)
         pre = None     # pretrain_metrics="device": built at the first batch that brings a pre-training objective
@@ -370,7 +387,12 @@ class Trainer:
                     if em is not None:
                         em.update(self.model.generate_async(batch).seq, refs_of(batch), batch.get("answer_types"))
                     if ans is not None:     # enqueued; read once below
-                        if self.answer_beams > 1:
+                        if exhaustive:
+                            r = self.model.answer_scores_async(batch, self.answer_trie, self.answer_k, self.answer_length_penalty)
+                            labels = r.labels if self.answer_k > 1 else r.label
+                            mass[0] += torch.exp(r.log_mass).sum()
+                            mass[1] += n
+                        elif self.answer_beams > 1:
                             r = self.model.answer_async(batch, self.answer_trie, num_beams=self.answer_beams,
                                                         length_penalty=self.answer_length_penalty)
                             labels = r.labels[:, :self.answer_k] if self.answer_k > 1 else r.label
@@ -388,7 +410,15 @@ class Trainer:
             self.answer_metrics = ans.result()
             if getattr(ans, "label_err", None) is not None:
                 ans_err += ans.label_err
-            if int(ans_err.cpu()) != 0:
+            if exhaustive:      # the error word and the mass in the one blocking copy
+                if self.world > 1:
+                    dist.all_reduce(mass)
+                both = torch.cat([ans_err.to(torch.float64), mass]).cpu()
+                self.answer_mass = float(both[1] / both[2]) if float(both[2]) > 0 else None
+                bad = float(both[0]) != 0
+            else:
+                bad = int(ans_err.cpu()) != 0
+            if bad:
                 raise ops._lib.M3AEHipError("answer-list decoding: a row left the answer table, or a label is outside [0, vqa_label_size)")
         if pre is not None:
             self.pretrain = pre.result()     # one all-reduce and one blocking copy for all of them

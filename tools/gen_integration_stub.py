@@ -103,6 +103,11 @@ SECTIONS = {
         "# constrained beam search on the answer list (ABI 4, additive): best 2 nb children across beams, the scorer step, n-best label scoring",
         (),
         ("m3ae_triebeam_select", "m3ae_triebeam_step", "m3ae_vqa_labels_eval")),
+    "LIST_SCORE_ENTRIES": Section(
+        "# exhaustive answer-list scoring (ABI 4, additive): attention over trie ancestors; every entry's log-probability, k best, list mass",
+        (),
+        ("m3ae_tree_attn", "m3ae_listscore_workspace_bytes", "m3ae_listscore_lse", "m3ae_listscore_edges",
+         "m3ae_listscore_fold_workspace_bytes", "m3ae_listscore_fold")),
 }
 globals().update({key: s.entries for key, s in SECTIONS.items() if s.entries})   # MAP_ENTRIES, DET_ENTRIES, ...: views of the table
 
